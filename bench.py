@@ -13,7 +13,9 @@ mean across ranks (RCCL all-reduce), as Lightning DDP does for the reference.
     python bench.py --gpus 1 --steps 5 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, ...); --full adds everything else the line can carry (CPU baseline, per-kernel timing and rooflines,
+the other arithmetic modes, the full stack).  --dump-outputs DIR writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -635,6 +637,37 @@ def _time_steps(step, warmup, steps, world):
     return time.perf_counter() - t0
 
 
+def _flat_grads(params):
+    """Every parameter's gradient, flattened and concatenated in parameters() order (zeros where a parameter has none)."""
+    return torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params])
+
+
+DUMP_ELEMS_PER_ARRAY = 1 << 21                             # 8 MiB of float32 per array; the workloads dump <= 5 arrays
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in float32 (float64 stays float64).  An array with more than
+    DUMP_ELEMS_PER_ARRAY elements is written as a fixed sample of its rows (1-D: of its elements), picked by a permutation
+    of seed 0 and kept in ascending order, so that runs with the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        rows = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(-1, 1)
+        keep = max(1, DUMP_ELEMS_PER_ARRAY // rows.shape[1])
+        if rows.shape[0] > keep:
+            idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            rows = rows.index_select(0, idx.to(rows.device))
+        a = rows.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        a = a.reshape(-1) if t.dim() <= 1 else a.reshape((a.shape[0],) + tuple(t.shape[1:]))
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would write more than {DUMP_MAX_BYTES} bytes (at {name})")
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def make_layer_workload(graphs, rank, world, device, K=K_NBR):
     """One GATConvNodes layer (non-first: H_Net with damping), forward + full backward."""
     import cgat_amd as P
@@ -646,7 +679,9 @@ def make_layer_workload(graphs, rank, world, device, K=K_NBR):
     x.requires_grad_(True); e.requires_grad_(True); x0.requires_grad_(True)
     averager = GradientAverager(params, force=FORCE_ALLREDUCE, static_graph=True) if (world > 1 or FORCE_ALLREDUCE) else None
 
-    def step():
+    kept = {}
+
+    def step(keep=False):
         if averager is not None:
             averager.zero_grad()                           # gradients accumulate straight into the all-reduce buckets
         else:
@@ -657,7 +692,11 @@ def make_layer_workload(graphs, rank, world, device, K=K_NBR):
         y.backward(cot)
         if averager is not None:
             averager.finish()
+        if keep:
+            kept["out"] = y.detach()
     step.averager = averager
+    step.outputs = lambda: {"out": kept["out"], "grad_x": x.grad, "grad_edge_attr": e.grad, "grad_x0": x0.grad,
+                            "grad_params": _flat_grads(params)}
     return step, x.shape[0], ei.shape[1]
 
 
@@ -673,7 +712,9 @@ def make_stack_workload(graphs, rank, world, device):
     roost = tuple(t.to(device) for t in roost)
     averager = GradientAverager(params, force=FORCE_ALLREDUCE, static_graph=True) if (world > 1 or FORCE_ALLREDUCE) else None
 
-    def step():
+    kept = {}
+
+    def step(keep=False):
         if averager is not None:
             averager.zero_grad()
         else:
@@ -684,6 +725,9 @@ def make_stack_workload(graphs, rank, world, device):
         loss.backward()
         if averager is not None:
             averager.finish()
+        if keep:
+            kept["out"], kept["loss"] = out.detach(), loss.detach().reshape(1)
+    step.outputs = lambda: {"out": kept["out"], "loss": kept["loss"], "grad_params": _flat_grads(params)}
     return step, b.num_nodes, b.edge_index.shape[1]
 
 
@@ -728,12 +772,75 @@ def layer_step_bytes(N, E):
     return compulsory, executed, {k: {"read_GB": round(r / 1e9, 2), "write_GB": round(w / 1e9, 2)} for k, (r, w) in fam.items()}
 
 
+def _headline(args, world, mode, stress, layer_like, K_used, N, E, elapsed):
+    """The fields of the line that every run prints: what `value` measures, in which arithmetic, on which batch."""
+    import cgat_amd as P
+    metric = ("edges/sec through one CGAT attention layer (fwd+bwd), 1M-edge batch" if args.workload == "layer"
+              else "edges/sec through one CGAT attention layer (fwd+bwd), 64M-edge large-neighbour batch in closed "
+                   "chunks [BASELINE configs[4]]" if stress
+              else "batch-edges/sec through the full CGAT stack (4 layers, fwd+bwd), 1M-edge batch [informational]")
+    dtype = {"f16x3c": "f32 storage / f16x3c (24-bit operands: exact h + l + t split, 3 fp16 + 3 six-bit matrix passes "
+                       "where built, six bf16 passes elsewhere; fp32 accumulate)",
+             "f16x3": "f32 storage / f16x3 split (22-bit operands, fp32 accumulate)",
+             "bf16x6": "f32 storage / bf16x6 split (24-bit operands, fp32 accumulate)",
+             "bf16x3": "f32 storage / bf16x3 split (16-bit products; diagnostic mode)",
+             "f32": "f32 (f32-input MFMA)"}[mode]
+    return {
+        "metric": metric,
+        "value": world * E * args.steps / elapsed, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": dtype + ("; Z / gZ of the edge phase stored as bf16 (tolerance 1e-2)"
+                                               if args.edge_storage == "bf16" else
+                                               "; Z of the edge phase stored as bf16 and the two per-edge backward products "
+                                               "on bf16 operands (one matrix pass, fp32 accumulate; tolerance 1e-2)"
+                                               if args.edge_storage == "bf16-mma" else ""),
+        "data": "synthetic", "bilinear_mode": mode, "edge_storage": args.edge_storage,
+        "config": {"workload": (f"one GATConvNodes layer (H_Net update) fwd+bwd, {args.graphs} crystals x {ATOMS} atoms x "
+                                f"{K_used} nbrs per rank: N={N}, E={E}, C=Ce={C_FEA}, H={HEADS}, scalar attention" +
+                                (f", closed chunks of <= {P.chunked.max_edges_per_pass()} edges with per-chunk "
+                                 "recomputation of the per-edge attention in backward (2 attention forward + 1 hypernetwork forward + 1 "
+                                 "backward pass per step)" if stress else ""))
+                   if layer_like else
+                   (f"CGAtNet(200,128,4,msg_heads=3,update_edges=True) fwd+bwd of L1 loss, {args.graphs} crystals: "
+                    f"N={N}, E={E}"),
+                   "edges_per_rank": E, "parallelism": f"dp{world} (graphs sharded, gradient all-reduce)"}}
+
+
+def _add_run_info(out, per_rank, ar_report, launch_rep):
+    """The ranks' own timings and the all-reduce statistics of a distributed run, and the launch-bound report that
+    --hipgraph or a batch below 512 crystals asks for."""
+    import torch.distributed as dist
+    if dist.is_initialized():
+        out["ranks"] = {"what": "one process per GPU; ms_per_step of every rank's own timed region (value = edges of all "
+                                "ranks / the maximum), the communicator the gradient all-reduce ran over",
+                        "world_size": dist.get_world_size(), "backend": dist.get_backend(),
+                        "collective_library": "RCCL (torch.distributed backend 'nccl' on ROCm)"
+                        if dist.get_backend() == "nccl" else dist.get_backend(),
+                        "ms_per_step_per_rank": [round(x, 3) for x in per_rank] if per_rank else [round(out["ms_per_step"], 3)],
+                        "devices_visible_to_rank0": torch.cuda.device_count()}
+    if ar_report is not None:
+        out["allreduce"] = ar_report
+    if launch_rep is not None:
+        out["launch_bound"] = launch_rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)      # 20 x 25 ms: the clocks settle within the first steps
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--graphs", type=int, default=GRAPHS, help="crystals per rank (default: the 1M-edge batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="layer / stack / stress workloads: everything beyond the headline figure -- the CPU baseline, the "
+                         "plan-build probe, per-kernel HIP-event timing in the timed region with the rooflines built on it, "
+                         "the serial pass for exclusive durations and the legs in the other arithmetic modes, on the side "
+                         "stream and through the full stack.  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="layer / stack / stress workloads: after the timed steps, write what the last timed step computed "
+                         "(the output, the input and parameter gradients) as DIR/<name>.npy, float32; arrays above "
+                         f"{DUMP_ELEMS_PER_ARRAY} elements as a fixed seeded sample of their rows")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exclusive-pass", action="store_true",
                     help="skip the 2-step serial pass after the timed region (exclusive durations of the kernels that "
@@ -756,6 +863,8 @@ def main():
                     help="layer: BASELINE metric (one GATConvNodes layer).  stack: informational, the full "
                          "CGAtNet(200,128,4,msg_heads=3) fwd+bwd of config 3 on the same 1M-edge batch")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("layer", "stack", "stress"):
+        ap.error("--dump-outputs: the layer, stack and stress workloads only")
 
     import torch.distributed as dist
     import cgat_amd as P
@@ -783,7 +892,7 @@ def main():
 
     # CPU leg FIRST (rank 0, N = 1 only): the GPU leg that follows is then one contiguous block of device work
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.workload == "layer":
+    if world == 1 and args.full and not args.no_cpu_baseline and args.workload == "layer":
         cpu = cpu_baseline()
 
     P.set_edge_storage(args.edge_storage)
@@ -810,7 +919,7 @@ def main():
     # shares it), so the timed steps below do not contain it; what one build costs -- kernels plus the two host
     # synchronisations of the index validation -- is reported beside ms_per_step.
     plan_build_ms = None
-    if layer_like and not stress:
+    if args.full and layer_like and not stress:
         ei_probe = make_inputs(args.graphs, rank, device, K_used)[0]
         reps = []
         for _ in range(4):
@@ -822,13 +931,16 @@ def main():
         plan_build_ms = round(sorted(reps[1:])[1], 3)
         del ei_probe
     ops.prof_reset()
-    ops.prof_enable(True)                                  # HIP events around the kernel launches, on their stream
+    ops.prof_enable(args.full)                             # --full: HIP events around the kernel launches, on their stream
+    last = args.steps - 1 if args.dump_outputs else -1
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep=i == last)
     _fence(world)
     elapsed = time.perf_counter() - t0
     ops.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs())
     ar_report = _allreduce_report(step_averager, args.warmup + args.steps) if step_averager is not None else None
     launch_rep = None
     if not stress and (args.hipgraph or args.graphs < 512):
@@ -840,7 +952,7 @@ def main():
     # beside share the chip, so their timed-region durations are not exclusive.  A short serial pass AFTER the timed
     # region (not part of `value`) gives those kernels' exclusive durations; both are reported.
     concurrent = ("bilinear_wgrad", "edge_seg_bwd", "edge_ge", "edge_gw", "edge_gj", "rows_ge", "rows_gw", "rows_dw") \
-        if (ops.overlap_enabled() and not args.no_exclusive_pass) else ()
+        if (args.full and ops.overlap_enabled() and not args.no_exclusive_pass) else ()
     prof_x = {}
     if concurrent:
         raw_overlap = ops.get_overlap_wgrad()
@@ -868,7 +980,7 @@ def main():
     # whose operands carry >= 24 significand bits, and the full 4-layer stack of BASELINE configs[2] ----
     mode = P.get_bilinear_mode()
     modes_ms, stack_ms, side_ms = {mode: 1e3 * elapsed / args.steps}, None, None
-    if world == 1 and not args.no_extra_legs and args.workload == "layer" and K_used == K_NBR:
+    if world == 1 and args.full and not args.no_extra_legs and args.workload == "layer" and K_used == K_NBR:
         del step
         torch.cuda.empty_cache()
         sstep, _, _ = make_stack_workload(args.graphs, rank, world, device)
@@ -886,7 +998,7 @@ def main():
                 continue
             k, w = (args.steps, args.warmup) if m != "f32" else (max(3, args.steps // 4), 2)
             cmd = [sys.executable, os.path.abspath(__file__), "--mode", m, "--steps", str(k), "--warmup", str(w)] + same_cfg + \
-                  ["--no-cpu-baseline", "--no-extra-legs", "--no-exclusive-pass"]
+                  ["--full", "--no-cpu-baseline", "--no-extra-legs", "--no-exclusive-pass"]
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -898,7 +1010,7 @@ def main():
         # modes, cgat_amd/ops.py: it halves the chip for the dominant kernel's launch) -- informational, never `value`
         if not ops.overlap_enabled():
             cmd = [sys.executable, os.path.abspath(__file__), "--mode", mode, "--steps", str(args.steps), "--warmup",
-                   str(args.warmup)] + same_cfg + ["--no-cpu-baseline", "--no-extra-legs", "--no-exclusive-pass"]
+                   str(args.warmup)] + same_cfg + ["--full", "--no-cpu-baseline", "--no-extra-legs", "--no-exclusive-pass"]
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=180,
                                    env=dict(os.environ, CGAT_OVERLAP_WGRAD="1"))
@@ -907,7 +1019,11 @@ def main():
             except Exception as ex:
                 sys.stderr.write(f"bench.py: side-stream leg failed: {ex}\n")
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        out = _headline(args, world, mode, stress, layer_like, K_used, N, E, elapsed)
+        _add_run_info(out, per_rank, ar_report, launch_rep)
+        print(json.dumps(out), flush=True)
+    elif rank == 0:
         ms = 1e3 * elapsed / args.steps
         # The three hypernetwork contraction kernels execute 2*N*C^3 flop per launch and predicted layer each (SURVEY 8a
         # a8.2: C*(C*C)*2 per row; the fused backward kernel produces two gradients from ONE such contraction, so it is
@@ -1115,40 +1231,13 @@ def main():
                 roof["other_kernels"] = {t: v for t, v in hbm.items() if t != top}
                 if contr is not None:
                     roof["contraction_kernels"] = {k: contr[k] for k in ("kernel", "achieved", "frac", "ms_per_step")}
-        metric = ("edges/sec through one CGAT attention layer (fwd+bwd), 1M-edge batch" if args.workload == "layer"
-                  else "edges/sec through one CGAT attention layer (fwd+bwd), 64M-edge large-neighbour batch in closed "
-                       "chunks [BASELINE configs[4]]" if stress
-                  else "batch-edges/sec through the full CGAT stack (4 layers, fwd+bwd), 1M-edge batch [informational]")
-        dtype = {"f16x3c": "f32 storage / f16x3c (24-bit operands: exact h + l + t split, 3 fp16 + 3 six-bit matrix passes "
-                           "where built, six bf16 passes elsewhere; fp32 accumulate)",
-                 "f16x3": "f32 storage / f16x3 split (22-bit operands, fp32 accumulate)",
-                 "bf16x6": "f32 storage / bf16x6 split (24-bit operands, fp32 accumulate)",
-                 "bf16x3": "f32 storage / bf16x3 split (16-bit products; diagnostic mode)",
-                 "f32": "f32 (f32-input MFMA)"}[mode]
-        out = {
-            "metric": metric,
-            "value": world * E * args.steps / elapsed, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms, "plan_build_ms": plan_build_ms,
-            "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": dtype + ("; Z / gZ of the edge phase stored as bf16 (tolerance 1e-2)"
-                                                   if args.edge_storage == "bf16" else
-                                                   "; Z of the edge phase stored as bf16 and the two per-edge backward products "
-                                                   "on bf16 operands (one matrix pass, fp32 accumulate; tolerance 1e-2)"
-                                                   if args.edge_storage == "bf16-mma" else ""),
-            "data": "synthetic", "bilinear_mode": mode, "edge_storage": args.edge_storage,
-            "config": {"workload": (f"one GATConvNodes layer (H_Net update) fwd+bwd, {args.graphs} crystals x {ATOMS} atoms x "
-                                    f"{K_used} nbrs per rank: N={N}, E={E}, C=Ce={C_FEA}, H={HEADS}, scalar attention" +
-                                    (f", closed chunks of <= {P.chunked.max_edges_per_pass()} edges with per-chunk "
-                                     "recomputation of the per-edge attention in backward (2 attention forward + 1 hypernetwork forward + 1 "
-                                     "backward pass per step)" if stress else ""))
-                       if layer_like else
-                       (f"CGAtNet(200,128,4,msg_heads=3,update_edges=True) fwd+bwd of L1 loss, {args.graphs} crystals: "
-                        f"N={N}, E={E}"),
-                       "edges_per_rank": E, "parallelism": f"dp{world} (graphs sharded, gradient all-reduce)"},
+        out = _headline(args, world, mode, stress, layer_like, K_used, N, E, elapsed)
+        out.update({
+            "plan_build_ms": plan_build_ms,
             "roofline": roof, "hbm_bound_kernels": hbm if layer_like else None,
             "edge_product_kernels": edge_mfma if layer_like else None,
             "kernel_ms_per_step": shares,
-        }
+        })
         if args.workload == "layer":
             fl = layer_step_flops(N, E)
             comp, execd, by_family = layer_step_bytes(N, E)
@@ -1180,18 +1269,7 @@ def main():
                                                    "on the same 1M-edge batch, default arithmetic mode (3 steps after 1 warm-up)"}
         if cpu is not None:
             out["cpu_baseline"] = cpu
-        if dist.is_initialized():
-            out["ranks"] = {"what": "one process per GPU; ms_per_step of every rank's own timed region (value = edges of all "
-                                    "ranks / the maximum), the communicator the gradient all-reduce ran over",
-                            "world_size": dist.get_world_size(), "backend": dist.get_backend(),
-                            "collective_library": "RCCL (torch.distributed backend 'nccl' on ROCm)"
-                            if dist.get_backend() == "nccl" else dist.get_backend(),
-                            "ms_per_step_per_rank": [round(x, 3) for x in per_rank] if per_rank else [round(ms, 3)],
-                            "devices_visible_to_rank0": torch.cuda.device_count()}
-        if ar_report is not None:
-            out["allreduce"] = ar_report
-        if launch_rep is not None:
-            out["launch_bound"] = launch_rep
+        _add_run_info(out, per_rank, ar_report, launch_rep)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.barrier()

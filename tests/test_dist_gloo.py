@@ -18,6 +18,12 @@ def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
+def _host_rank():
+    """These ranks run on the host cores (gloo, the oracle model).  On a machine with a GPU, init_from_env would give
+    rank r the device cuda:r (a second GPU for rank 1): the rank must see no GPU, before anything asks."""
+    torch.cuda.is_available = lambda: False
+
+
 def _loss_sum(model, batch, x, e, x0, lo, hi, A, K):
     """sum over crystals [lo,hi) of the squared node outputs, through one GATConvNodes layer"""
     n0, n1 = lo * A, hi * A
@@ -28,6 +34,7 @@ def _loss_sum(model, batch, x, e, x0, lo, hi, A, K):
 
 
 def _worker(rank, world, port, bucket_bytes, out, mode="plain"):
+    _host_rank()
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
@@ -124,6 +131,7 @@ def _net_worker(rank, world, port, out):
     """The shipped network structure (update_edges=True, no_hyper=True: Edge.MH_A / Edge.MH_M never receive a gradient,
     reference CGAT.py:224-225) over two ranks: after the first step those parameters are cold and must not gate a
     bucket, so buckets launch from the hooks, i.e. while backward is still running."""
+    _host_rank()
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
@@ -206,6 +214,7 @@ def test_unused_parameters_do_not_gate_the_buckets():
 def _static_worker(rank, world, port, out):
     """static_graph=True: after two steps with the same global bitmap the cold set freezes -- no bitmap all-reduce, no
     host synchronisation in finish() -- the mean stays right, and a cold parameter that gets a gradient raises."""
+    _host_rank()
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
@@ -273,6 +282,7 @@ def test_static_graph_freezes_the_cold_set():
 
 def _two_obs_worker(port, out):
     """No parameter is cold in step 1: the initial (empty) cold set must not count as an observation."""
+    _host_rank()
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                       CGAT_DIST_FORCE="1")

@@ -7,7 +7,7 @@ run() {
   touch cgat_amd/csrc/$F.hip
   CGAT_HIPCC_FLAGS="$1" bash cgat_amd/build_lib.sh > /dev/null 2>&1 || { echo "build failed: $1"; return; }
   for r in 1 2; do
-  python bench.py --no-cpu-baseline --no-extra-legs --no-exclusive-pass --steps 20 --warmup 5 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-extra-legs --no-exclusive-pass --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']
 print('[$1]', round(d['ms_per_step'],3), {t:k[t]['ms_per_step'] for t in '$TAGS'.split() if t in k})

@@ -6,7 +6,7 @@ VAR=$1; VALS=$2; REPS=${3:-2}; shift 3
 TAGS="$*"
 for r in $(seq 1 $REPS); do
   for v in $VALS; do
-    env $VAR=$v python bench.py --no-cpu-baseline --no-extra-legs --no-exclusive-pass --steps 20 --warmup 5 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --no-cpu-baseline --no-extra-legs --no-exclusive-pass --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernel_ms_per_step']

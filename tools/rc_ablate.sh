@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 for abl in 0 1 2 4 8 16 3 5 6 12 20 7 15 31 0; do
   touch cgat_amd/csrc/bilinear.hip
   CGAT_HIPCC_FLAGS="-DCGAT_DEV_ABLATIONS -DRC_ABL=$abl" bash cgat_amd/build_lib.sh > /dev/null 2>&1 || { echo "RC_ABL=$abl build failed"; continue; }
-  timeout 300 python bench.py --no-cpu-baseline --no-extra-legs --no-exclusive-pass --steps 10 --warmup 3 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-cpu-baseline --no-extra-legs --no-exclusive-pass --steps 10 --warmup 3 2>/dev/null | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']
