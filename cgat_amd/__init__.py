@@ -14,6 +14,7 @@ from .graph import GraphBatch, synthetic_batch
 from .collate import PackedDataset
 from .optim import FusedAdamW, FusedLamb, RobustL1, RobustL2, cyclical_lr
 from .ops import get_bilinear_mode, set_bilinear_mode, set_validate_indices, set_edge_storage, get_edge_storage
+from .ops import set_fused_inference, get_fused_inference
 from .trainer import DataParallelTrainer, Normalizer
 from .chunked import set_max_edges_per_pass
 from .capture import GraphedStep
@@ -23,4 +24,4 @@ __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAtt
            "HyperFC", "SimpleNetwork", "ResidualNetwork", "Rezero", "Roost", "MessageLayer", "WeightedAttention",
            "GraphBatch", "synthetic_batch", "PackedDataset", "FusedAdamW", "FusedLamb", "RobustL1", "RobustL2", "cyclical_lr", "set_bilinear_mode", "get_bilinear_mode",
            "set_validate_indices", "DataParallelTrainer", "Normalizer", "set_max_edges_per_pass",
-           "set_edge_storage", "get_edge_storage", "GraphedStep", "debug"]
+           "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "GraphedStep", "debug"]

@@ -622,25 +622,39 @@ __global__ __launch_bounds__(512, 2) void edge_zc_kernel(const float* __restrict
 // Operand: prepare_T_bf16's image as it is (12-KB k-step chunks (a, half, s) = [plane][cb][lane] x 16 B); a ring chunk
 // here is (a, half, pair of 16-column blocks) = 24 one-KB pieces [s][plane][cb2] picked out of four of those, three per
 // wave.  LDS: 4 slots x 24 KB + fc_out_A's weight.
+//
+// One 256-row tile of it is z6w_tile below, in three forms (MODE):
+//   0  Z stored, logits of the attention blocks (edge_z6w_kernel: the training forward);
+//   1  logits only, over the attention column blocks, nothing stored but a [E, H] (the forward without grad);
+//   2  the message column blocks: each 32-column slice of z = part + Pi[dst] + Pj[src] is staged in LDS (rounded to bf16
+//      first under bf16 edge storage, as mode 0 stores it), and red(a, ch) reduces it into the weighted segment sums
+//      (edge_msg_wsum_kernel).  Nothing per edge reaches memory.
+// Rows >= row_lim are clamped to row_lim - 1 (their results are discarded).  The counted wait below allows for the
+// stores of mode 0 only; modes 1 and 2 wait for the gathers of the current slice with 4 fewer younger operations (in
+// mode 2 the weighted sums' stores of the previous slice are older still: waited for too, never overtaken).
 // ---------------------------------------------------------------------------------------
-template <bool ZB>
-__global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restrict__ e, long lde, const int* __restrict__ perm,
-                                                          const uint4* __restrict__ Wq, int ncb,
-                                                          const float* __restrict__ Pi, const int* __restrict__ dsti,
-                                                          const float* __restrict__ Pj, const int* __restrict__ srci,
-                                                          long ld_add, float* __restrict__ Z, long ldz, int E,
-                                                          const float* __restrict__ wA, const float* __restrict__ bA,
-                                                          int H, int cb_per_head, float* __restrict__ a_out, int act,
-                                                          float* __restrict__ omax) {
-  constexpr int CH = 24 * 64;                         // 16-byte pieces per ring chunk (24 KB)
-  constexpr int SLOTS = 4;
-  __shared__ uint4 smem[SLOTS * CH + 512];            // the ring + fc_out_A's weight (<= 2048 floats)
+constexpr int Z6_CH = 24 * 64;                        // 16-byte pieces per ring chunk (24 KB)
+constexpr int Z6_SLOTS = 4;
+struct Z6NoRed {
+  __device__ void operator()(int, int) const {}
+};
+template <int MODE, bool ZB, class Red>
+__device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e, long lde,
+                                         const int* perm, const uint4* Wq, int ncb,
+                                         const float* Pi, const int* dsti,
+                                         const float* Pj, const int* srci, long ld_add,
+                                         float* Z, long ldz, int row0, int row_lim,
+                                         const float* wA, const float* bA, int H,
+                                         int cb_per_head, float* a_out, int act, float* omax,
+                                         const Red& red) {
+  constexpr int CH = Z6_CH;
+  constexpr int SLOTS = Z6_SLOTS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int n16 = lane & 15, kg = lane >> 4;
-  const int row_w = blockIdx.x * 256 + wave * 32;
+  const int row_w = (unsigned)row0 + wave * 32;
   const int row_a = row_w + n16, row_b = row_w + 16 + n16;
-  const int rca = row_a < E ? row_a : E - 1, rcb = row_b < E ? row_b : E - 1;
+  const int rca = row_a < row_lim ? row_a : row_lim - 1, rcb = row_b < row_lim ? row_b : row_lim - 1;
   const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
   const bf16x8* ring = reinterpret_cast<const bf16x8*>(smem) + lane;
   const unsigned l_off = (unsigned)lane * 16;
@@ -759,14 +773,26 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
         vb = make_float4(vb.x > 0.f ? vb.x : 0.01f * vb.x, vb.y > 0.f ? vb.y : 0.01f * vb.y,   \
                          vb.z > 0.f ? vb.z : 0.01f * vb.z, vb.w > 0.f ? vb.w : 0.01f * vb.w);  \
       }                                                                                        \
-      if constexpr (ZB) {                                                                      \
-        store4_bf16(reinterpret_cast<__bf16*>(Z) + (long)ra_ * ldz + col, va);                 \
-        store4_bf16(reinterpret_cast<__bf16*>(Z) + (long)rb_ * ldz + col, vb);                 \
-      } else {                                                                                 \
-        *reinterpret_cast<float4*>(Z + (long)ra_ * ldz + col) = va;                            \
-        *reinterpret_cast<float4*>(Z + (long)rb_ * ldz + col) = vb;                            \
+      if constexpr (MODE == 2) {   /* the slice in LDS: [256 rows][32 columns], LeakyReLU applied */ \
+        float4 sa = va, sb = vb;                                                               \
+        if constexpr (ZB) { sa = unpack4_bf16(pack4_bf16(va)); sb = unpack4_bf16(pack4_bf16(vb)); } \
+        sa = make_float4(sa.x > 0.f ? sa.x : 0.01f * sa.x, sa.y > 0.f ? sa.y : 0.01f * sa.y,   \
+                         sa.z > 0.f ? sa.z : 0.01f * sa.z, sa.w > 0.f ? sa.w : 0.01f * sa.w);  \
+        sb = make_float4(sb.x > 0.f ? sb.x : 0.01f * sb.x, sb.y > 0.f ? sb.y : 0.01f * sb.y,   \
+                         sb.z > 0.f ? sb.z : 0.01f * sb.z, sb.w > 0.f ? sb.w : 0.01f * sb.w);  \
+        const int cl_ = 16 * cb2 + 4 * (lk_ >> 4);                                             \
+        *reinterpret_cast<float4*>(zst + (wave_u * 32 + n16) * 32 + cl_) = sa;                 \
+        *reinterpret_cast<float4*>(zst + (wave_u * 32 + 16 + n16) * 32 + cl_) = sb;            \
+      } else if constexpr (MODE == 0) {                                                        \
+        if constexpr (ZB) {                                                                    \
+          store4_bf16(reinterpret_cast<__bf16*>(Z) + (long)ra_ * ldz + col, va);               \
+          store4_bf16(reinterpret_cast<__bf16*>(Z) + (long)rb_ * ldz + col, vb);               \
+        } else {                                                                               \
+          *reinterpret_cast<float4*>(Z + (long)ra_ * ldz + col) = va;                          \
+          *reinterpret_cast<float4*>(Z + (long)rb_ * ldz + col) = vb;                          \
+        }                                                                                      \
       }                                                                                        \
-      if (omax) {   /* (kernel argument: uniform) max |stored value|; dot_b is free in a launch without logits */ \
+      if (MODE == 0 && omax) {   /* (kernel argument: uniform) max |stored value|; dot_b is free in a launch without logits */ \
         dot_b = fmaxf(fmaxf(dot_b, fmaxf(fabsf(va.x), fabsf(va.y))), fmaxf(fabsf(va.z), fabsf(va.w))); \
         dot_b = fmaxf(fmaxf(dot_b, fmaxf(fabsf(vb.x), fabsf(vb.y))), fmaxf(fabsf(vb.z), fabsf(vb.w))); \
       }                                                                                        \
@@ -813,11 +839,17 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
     __builtin_amdgcn_sched_barrier(0);                                                         \
     /* gathers of THIS chunk (issued one iteration ago): younger are the 4 stores of the previous chunk and this       \
        iteration's 3 pieces + 8 gathers; the ring needs nothing more (chunk i + 2's pieces are older still) */          \
-    wait_vmcnt<15>();                                                                          \
+    wait_vmcnt<MODE == 0 ? 15 : 11>();                                                         \
+    if constexpr (MODE == 2) {   /* every wave is done reducing the previous slice */          \
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                       \
+      __builtin_amdgcn_s_barrier();                                                            \
+    }                                                                                          \
     Z6_EPILOGUE(GCUR_, a_, ch_)                                                                \
     __builtin_amdgcn_sched_barrier(0);                                                         \
+    if constexpr (MODE == 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                \
     __builtin_amdgcn_s_barrier();                                                              \
     asm volatile("" ::: "memory");                                                             \
+    if constexpr (MODE == 2) red(a_, ch_);                                                     \
   }
   Z6_READ(fa1, fa2, fa3, 0, 0);
   f32x4 part[4], partn[4];
@@ -829,7 +861,7 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
     Z6_CHUNK(a, 3, GB, GA)
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (omax) block_absmax_commit(dot_b, omax);
+  if constexpr (MODE == 0) if (omax) block_absmax_commit(dot_b, omax);
 #undef Z6_TLOAD
 #undef Z6_GATHER
 #undef Z6_READ
@@ -837,6 +869,130 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
 #undef Z6_EPILOGUE
 #undef Z6_CHUNK
 }
+
+// MODE 0 (the training forward) and MODE 1 (logits only: Z, ZB, act and omax unused)
+template <bool ZB, int MODE = 0>
+__global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restrict__ e, long lde, const int* __restrict__ perm,
+                                                          const uint4* __restrict__ Wq, int ncb,
+                                                          const float* __restrict__ Pi, const int* __restrict__ dsti,
+                                                          const float* __restrict__ Pj, const int* __restrict__ srci,
+                                                          long ld_add, float* __restrict__ Z, long ldz, int E,
+                                                          const float* __restrict__ wA, const float* __restrict__ bA,
+                                                          int H, int cb_per_head, float* __restrict__ a_out, int act,
+                                                          float* __restrict__ omax) {
+  __shared__ uint4 smem[Z6_SLOTS * Z6_CH + 512];      // the ring + fc_out_A's weight (<= 2048 floats)
+  z6w_tile<MODE, ZB>(smem, nullptr, e, lde, perm, Wq, ncb, Pi, dsti, Pj, srci, ld_add, Z, ldz, blockIdx.x * 256, E, wA, bA,
+                     H, cb_per_head, a_out, act, omax, Z6NoRed{});
+}
+
+// ---------------------------------------------------------------------------------------
+// The message half of the forward without grad (reference CGAT.py:319-329 under torch.no_grad(): predict.py, the
+// embeddings of calculate_embeddings.py): with the coefficients alpha [E, H] already formed by seg_softmax_fwd from the
+// logits launch above,
+//     S[n, c] = sum_{t in seg(n)} leaky(z[t, c]) * alpha[t, c / Hd],   z = the message columns of Z,
+// summed in EXACTLY the order of seg_wsum_vec_kernel / seg_wsum_long_kernel (segment.hip), so S -- and everything after
+// it -- is bit-identical to the training forward's, without Z ever reaching memory.
+//   * Workgroup w owns the destination segments [lb(w R), lb((w + 1) R)), lb(v) = the first segment starting at row >= v
+//     (binary search in dst_rowptr), and with them a contiguous row range that starts and ends at segment boundaries.
+//     R < 256 (host: 256 minus the mean in-degree rounded up to 16) keeps a range within one 256-row sub-tile for
+//     ordinary segments; a longer range is walked in 256-row sub-tiles.  No segment is split between workgroups,
+//     workgroups never wait on each other.
+//   * Per 32-column slice the tile stages leaky(z) of its 256 rows in LDS (32 KB); 16 x 32 reducer threads (segment
+//     part, column) then run the chain acc = fma(leaky(z), alpha, acc) over the part's rows in ascending order, as
+//     seg_wsum_vec_kernel does (its update contracts to v_fma_f32).  A segment of more than SEG_LONG rows keeps
+//     seg_wsum_long_kernel's G strided row groups (G = 1024 / min(HHd / 4, 256)) and adds them in group order at its end.
+//   * Only the part that continues past a sub-tile carries its partial sums (G x HHd floats of LDS) to the next one;
+//     it is the last part of one sub-tile and the first of the next, and the thread that finishes one sub-tile's first
+//     part also runs its last part -- in that order -- so the carry is read before it is overwritten.
+//   * Segments without rows get S = 0 (seg_wsum_vec_kernel writes its zero accumulator for them).
+// ---------------------------------------------------------------------------------------
+#define WSUM_CARRY 4096   // floats: G * HHd <= 4096 for HHd <= 1024
+template <bool ZB>
+__global__ __launch_bounds__(512, 2) void edge_msg_wsum_kernel(const float* __restrict__ e, long lde,
+                                                               const int* __restrict__ perm, const uint4* __restrict__ Wq,
+                                                               int ncb, const float* __restrict__ Pi,
+                                                               const int* __restrict__ dsti, const float* __restrict__ Pj,
+                                                               const int* __restrict__ srci, long ld_add, int H, int Hd,
+                                                               const float* __restrict__ alpha,
+                                                               const int* __restrict__ rowptr, int N, int R,
+                                                               float* __restrict__ S) {
+  __shared__ uint4 smem[Z6_SLOTS * Z6_CH];            // the ring (96 KB)
+  __shared__ float zst[256 * 32];                     // one staged 32-column slice (32 KB)
+  __shared__ float carry[WSUM_CARRY];                 // partial sums of the part continuing past the sub-tile (16 KB)
+  __shared__ float alst[256 * 8];                     // alpha of the sub-tile's rows (H <= 8)
+  __shared__ int plo[256], pseg[256], pr0[256], pr1[256];   // the sub-tile's segment parts: first local row, segment, rows
+  __shared__ int sh[12];
+  const int tid = threadIdx.x;
+  const int HHd = H * Hd;
+  const int quads = HHd / 4, tpr = quads < 256 ? quads : 256, Glong = 1024 / tpr;   // seg_wsum_long_kernel's row groups
+  if (tid == 0) {
+    auto lb = [&](long v) {   // first s in [0, N] with rowptr[s] >= v
+      int lo = 0, hi = N;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rowptr[mid] >= v) hi = mid; else lo = mid + 1;
+      }
+      return lo;
+    };
+    const int s0 = lb((long)blockIdx.x * R);
+    const int s1 = blockIdx.x + 1 == gridDim.x ? N : lb((long)(blockIdx.x + 1) * R);
+    sh[0] = s0; sh[1] = s1; sh[2] = rowptr[s0]; sh[3] = rowptr[s1];
+  }
+  __syncthreads();
+  const int s_begin = sh[0], s_end = sh[1], R0 = sh[2], R1 = sh[3];
+  // segments without rows
+  for (long i = tid; i < (long)(s_end - s_begin) * quads; i += 512) {
+    const int s = s_begin + (int)(i / quads), q = (int)(i % quads);
+    if (rowptr[s] == rowptr[s + 1]) *reinterpret_cast<float4*>(S + (long)s * HHd + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const int c = tid & 31, slot = tid >> 5;
+  for (int t0 = R0; t0 < R1; t0 += 256) {
+    const int t1 = t0 + 256 < R1 ? t0 + 256 : R1;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                     // the previous sub-tile's reductions are done
+    // parts: a row starts one where its segment differs from the previous row's (or at the sub-tile's first row)
+    const int r = t0 + tid;
+    const int sg = tid < 256 && r < t1 ? dsti[r] : -1;
+    const bool start = sg >= 0 && (tid == 0 || dsti[r - 1] != sg);
+    const unsigned long long bal = __ballot(start);
+    const int lane = tid & 63, w = tid >> 6;
+    if (lane == 0) sh[4 + w] = __popcll(bal);
+    for (int i = tid; i < (t1 - t0) * H; i += 512) alst[i] = alpha[(long)t0 * H + i];
+    __syncthreads();
+    if (start) {
+      int idx = __popcll(bal & ((1ull << lane) - 1));
+      for (int k = 0; k < w; ++k) idx += sh[4 + k];
+      plo[idx] = tid; pseg[idx] = sg; pr0[idx] = rowptr[sg]; pr1[idx] = rowptr[sg + 1];
+    }
+    const int nparts = sh[4] + sh[5] + sh[6] + sh[7];
+    __syncthreads();
+    __syncthreads();
+    // one part of one segment for column col of the slice (a, ch): rows of group g are r0 + g + k G
+    auto part = [&](int i, int a, int ch) {
+      const int col = a * 128 + (ch >> 1) * 64 + (ch & 1) * 32 + c, h = col / Hd;
+      const int r0 = pr0[i], r1 = pr1[i], lo = t0 + plo[i], hi = i + 1 < nparts ? t0 + plo[i + 1] : t1;
+      const int G = r1 - r0 > SEG_LONG ? Glong : 1;
+      const bool cin = r0 < t0, cout = r1 > t1;
+      float tot = 0.f;
+      for (int g = 0; g < G; ++g) {
+        float acc = cin ? carry[g * HHd + col] : 0.f;
+        int r = lo + (((g - (lo - r0)) % G) + G) % G;
+        for (; r < hi; r += G) acc = __builtin_fmaf(zst[(r - t0) * 32 + c], alst[(r - t0) * H + h], acc);
+        if (cout) carry[g * HHd + col] = acc;
+        else tot = g == 0 ? acc : tot + acc;
+      }
+      if (!cout) S[(long)pseg[i] * HHd + col] = tot;
+    };
+    // slot 0 runs part 0 (the one that may continue a carry) first and the last part (the one that may leave one) last
+    auto red = [&](int a, int ch) {
+      for (int i = slot; i < nparts - 1; i += 16) part(i, a, ch);
+      if (slot == 0) part(nparts - 1, a, ch);
+    };
+    z6w_tile<2, ZB>(smem, zst, e, lde, perm, Wq, ncb, Pi, dsti, Pj, srci, ld_add, nullptr, 0, t0, t1, nullptr, nullptr, H,
+                    Hd / 128, nullptr, CGAT_ACT_NONE, nullptr, red);
+  }
+}
+#undef WSUM_CARRY
 
 // ---------------------------------------------------------------------------------------
 // The per-edge launch with the x_j projection folded in (f16x3 arithmetic):
@@ -1250,6 +1406,58 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
   else if (bilinear_mode() != 3) { if (adds) EZ_GO(6, true); else EZ_GO(6, false); }
   else { if (adds) EZ_GO(3, true); else EZ_GO(3, false); }
 #undef EZ_GO
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+
+// ---- the forward without grad (edge_z6w_kernel<., 1> and edge_msg_wsum_kernel above) ----
+// Exactly the shapes at which edge_z_launch runs the per-edge launch as edge_z6w_kernel (24-bit modes, C = Ce = 128,
+// Hd % 128 == 0, >= 128 row tiles of 256, no opt-in f16x3c kernel), at most 1024 message columns (the carry of a long
+// segment's row groups lives in 16 KB of LDS), 32-bit gather offsets and E * H % 4 == 0.
+bool edge_infer_fused(int N, int E, int C, int Ce, int H, int Hd) {
+  const long HHd = (long)H * Hd;
+  return (bilinear_mode() == 4 || bilinear_mode() == 6) && edge_z6w_on() && !(bilinear_mode() == 4 && edge_zc_on()) &&
+         C == 128 && Ce == 128 && Hd % 128 == 0 && HHd <= 1024 && N > 0 && E > 0 && cdiv(E, 256) >= 128 &&
+         // the training forward's S sits behind Z and alpha in the saved buffer and is 16-byte aligned only when
+         // E * H % 4 == 0; otherwise seg_wsum_launch takes its scalar kernel, whose order is not the one built here
+         ((long)E * H) % 4 == 0 &&
+         (long)N * 4 * (2 * HHd) < (1l << 32);
+}
+int edge_logits_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
+                       const float* Pi, const int* dsti, const float* Pj, const int* srci, int E, const float* wA,
+                       const float* bA, int H, int Hd, float* a_out, hipStream_t stream) {
+  CGAT_CHECK_ARG(W2 == 2 * H * Hd && Hd % 128 == 0 && (lde % 4) == 0 && wA && a_out && perm &&
+                 ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)wA)) & 15) == 0,
+                 "edge_logits: needs Hd %% 128 == 0, 16-byte aligned rows and fc_out_A's weight");
+  CGAT_TRY(prepare_T_bf16_launch(We, Wq, W2 / 128, 128 * ldw, 1, ldw, 0, stream));   // (the whole W2 image: edge_msg_wsum's too)
+  CGAT_PROF("edge_logits", stream);
+  hipLaunchKernelGGL((edge_z6w_kernel<false, 1>), dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq,
+                     H * Hd / 128, Pi, dsti, Pj, srci, (long)W2, (float*)nullptr, 0l, E, wA, bA, H, Hd / 128, a_out,
+                     CGAT_ACT_NONE, (float*)nullptr);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+// Wq: the image edge_logits_launch made; Pi / Pj: [N, W2] (the message columns are the second half)
+int edge_msg_wsum_launch(const float* e, long lde, const int* perm, const float* Wq, int W2, const float* Pi,
+                         const int* dsti, const float* Pj, const int* srci, int N, int E, int H, int Hd, const float* alpha,
+                         const int* rowptr, float* S, int z_bf16, hipStream_t stream) {
+  const int HHd = H * Hd;
+  CGAT_CHECK_ARG(W2 == 2 * HHd && Hd % 128 == 0 && HHd <= 1024 && (lde % 4) == 0 && perm && N > 0 &&
+                 ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)S)) & 15) == 0,
+                 "edge_msg_wsum: needs Hd %% 128 == 0, H * Hd <= 1024 and 16-byte aligned rows");
+  if (E <= 0) return CGAT_OK;
+  // rows per workgroup: a range that starts and ends at segment boundaries is at most R + (longest segment - 1) rows, so
+  // 256 minus the mean in-degree (rounded up to 16) keeps ordinary ranges in one 256-row sub-tile
+  const long deg = cdiv(E, N);
+  const int R = (int)(deg >= 128 ? 128 : 256 - 16 * cdiv(deg, 16));
+  const uint4* Wm = reinterpret_cast<const uint4*>(Wq) + (long)(HHd / 128) * 6144;   // the message column blocks' image
+  CGAT_PROF("edge_msg_wsum", stream);
+  if (z_bf16)
+    hipLaunchKernelGGL(edge_msg_wsum_kernel<true>, dim3(cdiv(E, R)), dim3(512), 0, stream, e, lde, perm, Wm, HHd / 128,
+                       Pi + HHd, dsti, Pj + HHd, srci, (long)W2, H, Hd, alpha, rowptr, N, R, S);
+  else
+    hipLaunchKernelGGL(edge_msg_wsum_kernel<false>, dim3(cdiv(E, R)), dim3(512), 0, stream, e, lde, perm, Wm, HHd / 128,
+                       Pi + HHd, dsti, Pj + HHd, srci, (long)W2, H, Hd, alpha, rowptr, N, R, S);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }

@@ -168,6 +168,16 @@ static inline int z_col_groups(int row_tiles, int ncb, int unit = 1) {
     if (ncb % g == 0 && (ncb / g) % unit == 0) { G = g; if ((long)row_tiles * G >= 512) break; }
   return G;
 }
+// The forward without grad at the shapes of the six-pass per-edge launch (edgez.hip): the logits alone (attention column
+// blocks, no Z) and the message blocks reduced straight into S[N, H * Hd] = the softmax-weighted segment sums that
+// seg_wsum_launch forms from Z, bit-identical.  edge_infer_fused: the host-only predicate of shapes, mode and storage.
+bool edge_infer_fused(int N, int E, int C, int Ce, int H, int Hd);
+int edge_logits_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
+                       const float* Pi, const int* dsti, const float* Pj, const int* srci, int E, const float* wA,
+                       const float* bA, int H, int Hd, float* a_out, hipStream_t stream);
+int edge_msg_wsum_launch(const float* e, long lde, const int* perm, const float* Wq, int W2, const float* Pi,
+                         const int* dsti, const float* Pj, const int* srci, int N, int E, int H, int Hd, const float* alpha,
+                         const int* rowptr, float* S, int z_bf16, hipStream_t stream);
 size_t linear128_heads_image_floats(int n_out);
 int linear128_heads_launch(int heads, const float* in, long ldi, long s_in, const float* W, long so, long sk, long s_w,
                            const float* bias, long s_bias, int act, int accumulate, float* out, long ldo, long s_out, int rows,
@@ -327,6 +337,7 @@ int copy2d_multi_launch(const Copy2DJobs& j, hipStream_t s);   // n <= 4 copies 
 int fill_launch(float* p, float v, long n, hipStream_t s);
 
 // ---- segment kernels (rows sorted by segment, rowptr[S+1]), segment.hip ----
+#define SEG_LONG 256   // segments of more rows go to the *_long kernels (segment.hip) -- and keep their order in edgez.hip
 int seg_softmax_fwd_launch(const float* a, const float* mult, const int* rowptr, int S, int F, float eps, float* alpha,
                            float* ssum, hipStream_t s);
 int seg_softmax_bwd_launch(const float* alpha, const float* galpha, const float* gssum, const float* mult,

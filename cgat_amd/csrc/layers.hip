@@ -711,8 +711,15 @@ static int stack_in_weights(Ctx& c, const cgat_attn_params* p, const AttnDims& d
   return CGAT_OK;
 }
 
+// The forward without grad (infer): at the shapes edge_infer_fused takes (edgez.hip) the logits launch and the fused
+// message + weighted-sum launch replace the per-edge launch and seg_wsum, and alpha / S / ssum live in the workspace --
+// nothing of size E x H x Hd is formed; everywhere else the saved buffer of the training forward is carved out of the
+// workspace and the same launches run.  Either way the results are bit-identical to the training forward's.
+static bool attn_infer_fused(const AttnDims& d) {
+  return edge_infer_fused(d.N, d.E, d.C, d.Ce, d.H, d.Hd) && (!edge_bf16_storage() || attn_bf16(d));
+}
 static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x, const float* e,
-                             float* aggr, float* saved) {
+                             float* aggr, float* saved, bool infer = false) {
   const AttnDims d = attn_dims(plan, p);
   float* Wcat = c.take<float>((size_t)d.W2 * d.D);
   float* bcat = c.take<float>((size_t)d.W2);
@@ -721,8 +728,17 @@ static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_para
   float* a = c.take<float>((size_t)d.E * d.H);
   float* Wq = c.take<float>(edge_z_wq_floats(d.W2) > edge_zx_wq_floats(d.W2) ? edge_z_wq_floats(d.W2)
                                                                               : edge_zx_wq_floats(d.W2));
+  const bool fused_inf = infer && attn_infer_fused(d);
+  AttnSaved inf = {};
+  if (fused_inf) {
+    inf.alpha = c.take<float>((size_t)d.E * d.H);
+    inf.S = c.take<float>((size_t)d.N * d.HHd);
+    inf.ssum = c.take<float>((size_t)d.N * d.H);
+  } else if (infer) {
+    saved = c.take<float>(cgat_nodes_attention_saved_floats(d.N, d.E, d.H, d.Hd));
+  }
   c.seal();
-  AttnSaved sv = c.dry ? AttnSaved{} : attn_saved(saved, d);
+  AttnSaved sv = c.dry ? AttnSaved{} : fused_inf ? inf : attn_saved(saved, d);
   // f16x3 mode at the benchmark widths: the x_j projection is folded into the per-edge kernel (edge_zx_kernel), so
   // Pj is never formed
   const bool zx = !c.dry && d.N > 0 &&
@@ -746,6 +762,15 @@ static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_para
     g = gemm_params(d.N, d.W2, d.C, x, d.C, Wcat + d.C + d.Ce, d.D, Pj, d.W2);
     CGAT_TRY(c.gemm(g));
   }
+  if (fused_inf) {   // logits, softmax (the same launch as below), message columns summed straight into S
+    CGAT_CHECK_ARG(((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)p->A_out_w)) & 15) == 0,
+                   "nodes_attention_infer: edge_attr and MH_A.fc_out.weight must be 16-byte aligned");
+    RUN(edge_logits_launch(e, d.Ce, plan->dst_perm, Wcat + d.C, d.D, Wq, d.W2, Pi, plan->dst_sorted, Pj, plan->src_sorted,
+                           d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, a, c.s));
+    RUN(seg_softmax_fwd_launch(a, nullptr, plan->dst_rowptr, d.N, d.H, 1e-16f, sv.alpha, sv.ssum, c.s));
+    RUN(edge_msg_wsum_launch(e, d.Ce, plan->dst_perm, Wq, d.W2, Pi, plan->dst_sorted, Pj, plan->src_sorted, d.N, d.E, d.H,
+                             d.Hd, sv.alpha, plan->dst_rowptr, sv.S, attn_bf16(d) ? 1 : 0, c.s));
+  } else {
   // Z[t] = W_e e[perm[t]] + Pi[dst[t]] + Pj[src[t]]      (x_i = x[edge_index[1]], x_j = x[edge_index[0]])
   // and the attention logits a[t,h] = fc_out_A(leaky(zA)): one fused split-bf16 kernel at the benchmark widths,
   // the generic GEMM + row-dot otherwise (and in the f32 arithmetic mode)
@@ -779,6 +804,7 @@ static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_para
   RUN(seg_wsum_launch(zb ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(sv.Z) + d.HHd) : sv.Z + d.HHd, d.W2,
                       nullptr, sv.alpha, d.H, d.Hd, plan->dst_rowptr, d.N, d.HHd, CGAT_ACT_LEAKY, sv.S, d.HHd, c.s, 0,
                       zb ? 1 : 0));
+  }
   // aggr = (1/H) [ sum_h S[:,h,:] fc_out_M[h]^T + ssum b ].  At the benchmark widths the H products run as
   // H * Hd / 128 accumulating launches of the dense-layer kernel (K = 128 each; the generic f32 GEMM tile took 0.1 ms
   // per head) and 1/H is applied by the bias product that closes the sum.
@@ -1289,6 +1315,28 @@ extern "C" int cgat_nodes_attention_forward(const cgat_plan* plan, const cgat_at
     c.scratch_need = dry.scratch_need;
     return attn_forward_impl(c, plan, p, x, edge_attr, aggr, saved);
   }
+}
+extern "C" int32_t cgat_nodes_attention_infer_fused(const cgat_plan* plan, const cgat_attn_params* p) {
+  if (attn_check(plan, p) != CGAT_OK) return 0;
+  return attn_infer_fused(attn_dims(plan, p)) ? 1 : 0;
+}
+extern "C" size_t cgat_nodes_attention_infer_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p) {
+  Ctx c(nullptr, 0, true, nullptr);
+  attn_forward_impl(c, plan, p, nullptr, nullptr, nullptr, nullptr, true);
+  return c.total();
+}
+extern "C" int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                          const float* edge_attr, float* aggr, void* ws, size_t ws_bytes, void* stream) {
+  CGAT_TRY(attn_check(plan, p));
+  Ctx dry(nullptr, 0, true, nullptr);
+  attn_forward_impl(dry, plan, p, nullptr, nullptr, nullptr, nullptr, true);
+  if (ws_bytes < dry.total()) {
+    cgat_set_error("nodes_attention_infer: workspace too small (%zu < %zu)", ws_bytes, dry.total());
+    return CGAT_ERR_WORKSPACE;
+  }
+  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
+  c.scratch_need = dry.scratch_need;
+  return attn_forward_impl(c, plan, p, x, edge_attr, aggr, nullptr, true);
 }
 // ---- debug: the sign pattern of the saved pre-activations in original edge order (include/cgat_hip.h) ----
 __global__ void attn_signs_kernel(const float* __restrict__ Z, const int* __restrict__ perm, long E, int W2,

@@ -29,8 +29,7 @@ __device__ __forceinline__ float act_f(float v, int act) {
 // the rows of ONE segment and combine through wavefront (DPP / shuffle) and LDS reductions in a fixed order, so the
 // results stay bitwise reproducible.  Which segments are long is found on the device (every workgroup of a long
 // kernel scans the row pointers of its share of segments and collects the long ones in LDS): no host round trip, no
-// workspace, nothing to capture around.
-#define SEG_LONG 256
+// workspace, nothing to capture around.  (SEG_LONG: kernels.h, shared with edgez.hip's fused weighted sum)
 
 __device__ __forceinline__ float wave_max64(float v) {
 #pragma unroll

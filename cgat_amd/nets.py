@@ -21,6 +21,7 @@ from .mlp import ResidualNetwork, SimpleNetwork
 from .ops import (AttentionPoolFn, attention_pool, EdgeHiddenFn, EdgeHiddenHeadsFn, HeadsLinear1Fn, HeadsLinearFn, NodeLayerFn, NodesAttentionFn, SegmentPlan, SegmentSoftmaxFn, SegmentSumFn, gather_rows, get_plan, get_segment_plan, linear, small_embedding,
                   segment_softmax, segment_sum)
 from .ops import overlap_enabled as ops_overlap_enabled
+from .ops import HNetFn, infer_route, nodes_attention_infer
 from .ops import branch_stream
 from .roost import Roost
 
@@ -228,10 +229,18 @@ class GATConvNodes(nn.Module):
             self.Pooling_NN = H_Net(out_channels, 3, out_channels, out_channels, 2, out_channels, out_channels)
 
     # -- fused scalar-attention path: one call into cgat_nodes_attention_forward ---------
-    def _aggregate_fused(self, x, edge_attr, plan):
+    #    (no backward can follow -- torch.no_grad(), inference_mode(), nothing requires grad --: the forward without
+    #    grad, ops.nodes_attention_infer: same results, no saved buffer, no per-edge activations at the benchmark widths)
+    def _attn_params(self):
         a, m = self.MH_A, self.MH_M
-        return NodesAttentionFn.apply(x, edge_attr, plan, self.heads, a.fc_in.weight, a.fc_in.bias, a.fc_out.weight,
-                                      a.fc_out.bias, m.fc_in.weight, m.fc_in.bias, m.fc_out.weight, m.fc_out.bias)
+        return (a.fc_in.weight, a.fc_in.bias, a.fc_out.weight, a.fc_out.bias, m.fc_in.weight, m.fc_in.bias,
+                m.fc_out.weight, m.fc_out.bias)
+
+    def _aggregate_fused(self, x, edge_attr, plan):
+        params = self._attn_params()
+        if infer_route(x, edge_attr, params):
+            return nodes_attention_infer(x, edge_attr, plan, self.heads, *params)
+        return NodesAttentionFn.apply(x, edge_attr, plan, self.heads, *params)
 
     # -- vector attention (CGAT.py:286-290: MH_A emits one logit per head AND channel): the shared first layer of both
     #    networks runs as one operand-split op in destination-sorted order, so the concatenated message [E, 2C+Ce],
@@ -296,6 +305,10 @@ class GATConvNodes(nn.Module):
             with torch.no_grad():
                 pool.damping.data = pool.damping.data.clamp(0.0, 1.0)      # Hypernetworksmp.py:307, as H_Net.forward
             h0, damping = x_0, pool.damping
+        if infer_route(x, edge_attr, self._attn_params()):
+            # the attention half without grad; the hypernetwork as its own node (NodeLayerFn's forward runs the same call)
+            aggr = nodes_attention_infer(x, edge_attr, plan, self.heads, *self._attn_params())
+            return HNetFn.apply(h0, aggr, damping, hyper.n_fc, len(hyper.layers), *flat)
         return NodeLayerFn.apply(x, edge_attr, h0, plan, self.heads, damping, hyper.n_fc, len(hyper.layers),
                                  a.fc_in.weight, a.fc_in.bias, a.fc_out.weight, a.fc_out.bias,
                                  m.fc_in.weight, m.fc_in.bias, m.fc_out.weight, m.fc_out.bias, *flat)

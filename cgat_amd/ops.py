@@ -273,6 +273,54 @@ class NodesAttentionFn(torch.autograd.Function):
         return (g_x, g_e, None, None, *grads)
 
 
+_fused_infer = os.environ.get("CGAT_FUSED_INFER", "1") != "0"
+
+
+def set_fused_inference(flag):
+    """The forward-without-grad route of the scalar-attention node layer (default on; env CGAT_FUSED_INFER=0 starts it
+    off): under torch.no_grad() / inference_mode(), or when nothing of a layer requires grad, GATConvNodes runs
+    nodes_attention_infer instead of the autograd node -- same results bit for bit, no saved buffer, and at the
+    benchmark widths no per-edge activations at all.  Off: the training forward runs (the A/B reference)."""
+    global _fused_infer
+    _fused_infer = bool(flag)
+
+
+def get_fused_inference():
+    return _fused_infer
+
+
+def nodes_attention_infer(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b):
+    """NodesAttentionFn's forward without the autograd node and without a saved buffer (cgat_nodes_attention_infer):
+    buffers from workspace(), nothing allocated but the result.  Never records a backward."""
+    weights = [A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b]
+    _require_gpu(x, edge_attr, *weights)
+    x, edge_attr = _f32c(x.detach()), _f32c(edge_attr.detach())
+    weights = [_f32c(w.detach()) for w in weights]
+    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
+        raise ValueError("nodes_attention_infer handles scalar attention (MH_A output_dim == 1)")
+    N, E = plan.N, plan.E
+    if x.shape[0] != N or edge_attr.shape[0] != E:
+        raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, edge_attr {tuple(edge_attr.shape)}")
+    p, Hd = _attn_params(x, edge_attr, H, weights)
+    dev = x.device
+    aggr = torch.empty(N, x.shape[1], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_nodes_attention_infer_workspace_bytes(C.byref(plan.c), C.byref(p)), dev)
+        check(lib.cgat_nodes_attention_infer(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(edge_attr), _ptr(aggr), _ptr(ws),
+                                             ws.numel(), _stream()), "cgat_nodes_attention_infer")
+    return aggr
+
+
+def infer_route(x, edge_attr, params):
+    """True when a scalar-attention node layer takes nodes_attention_infer: the route is on, no backward can follow
+    (grad mode off, or nothing involved requires grad) and no debug recording wants the saved buffer."""
+    if not _fused_infer or debug.recording():
+        return False
+    if not torch.is_grad_enabled():
+        return True
+    return not any(t is not None and t.requires_grad for t in (x, edge_attr, *params))
+
+
 class EdgeHiddenFn(torch.autograd.Function):
     """hidden[t] = LeakyReLU(w_in [x_i ; edge_attr ; x_j] + b_in) in destination-sorted slot order t (plan.dst_perm):
     the first layer of both message networks (reference CGAT.py:96,105-108 on the concatenated message of 316-318)

@@ -164,6 +164,22 @@ int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params*
                                   float* g_x /* [N,C] */, float* g_edge_attr /* [E,Ce] */, const cgat_attn_grads* g,
                                   void* ws, size_t ws_bytes, void* stream);
 
+/* The same forward without grad (replaces CGAT/CGAT.py:307-335 where it runs under torch.no_grad(): predictions,
+ * graph embeddings): aggr as cgat_nodes_attention_forward computes it, bit-identical, with nothing saved for backward.
+ * Where cgat_nodes_attention_infer_fused says 1 -- a host-only predicate of shapes, arithmetic mode and edge storage:
+ * the 24-bit split modes (f16x3c, bf16x6), C = Ce = 128, Hd a multiple of 128, H*Hd <= 1024, >= 128 tiles of 256 edges,
+ * E*H % 4 == 0 -- the per-edge
+ * work of CGAT.py:319-329 (MH_A's logits, softmax, MH_M's first layer weighted by alpha and summed per destination) runs
+ * as two launches that write no per-edge activation: the workspace holds the node projections, logits, alpha, the
+ * per-node sums and weight images, and does not grow with E*H*Hd.  The call then refuses (CGAT_ERR_ARG) inputs those
+ * launches cannot take, such as a misaligned edge_attr, instead of taking another route.  Elsewhere it runs the
+ * launches of cgat_nodes_attention_forward with the saved buffer carved out of the workspace. */
+int32_t cgat_nodes_attention_infer_fused(const cgat_plan* plan, const cgat_attn_params* p);
+size_t cgat_nodes_attention_infer_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p);
+int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn_params* p, const float* x /* [N,C] */,
+                               const float* edge_attr /* [E,Ce], original edge order */, float* aggr /* out [N,C] */,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* Debug / parity instrumentation (tests only, not on the hot path): the LeakyReLU derivative pattern the backward of
  * cgat_nodes_attention_forward will use -- mask[e, c] = (Z[slot(e), c] > 0) for the pre-activations of MH_A (columns
  * [0, H*Hd)) and MH_M ([H*Hd, 2*H*Hd)) of CGAT/CGAT.py:96,105-108, in ORIGINAL edge order.  LeakyReLU's derivative
