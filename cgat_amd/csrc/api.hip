@@ -232,7 +232,7 @@ extern "C" int cgat_heads_linear_backward_dact(const float* x, int64_t ldx, int6
   hipStream_t s = (hipStream_t)stream;
   const bool have_ws = ws && ws_bytes >= cgat_heads_linear_backward_dact_workspace_bytes(M, K, N, H);
   const int kb = K / 128;
-  if (have_ws && H > 1 && M > 0 && (bilinear_mode() == 2 || bilinear_mode() == 4 || bilinear_mode() == 6) && N == 128 &&
+  if (have_ws && H > 1 && M > 0 && (mode_f16() || mode_24bit()) && N == 128 &&
       K % 128 == 0 && H * kb <= DW_BATCH_MAX &&
       heads_strides_ok(s_x, s_w, s_gy, s_gx) && heads_strides_ok(s_dact, s_gw, s_gb, ld_dact) &&
       linear128_fast(N, K, ldgy, ldgx, g_y, g_x) && (((uintptr_t)gx_dact) & 15) == 0) {
@@ -301,7 +301,7 @@ static int linear_backward_impl(const float* x, int64_t ldx, const float* w, int
     DwBatchDesc b;
     memset(&b, 0, sizeof(b));
     b.rows = M; b.ldg = ldgp; b.ldx = ldx; b.ldo = ldgw;
-    if (g_w && M > 0 && N % 128 == 0 && K % 128 == 0 && nb * kb <= DW_BATCH_MAX && nb * kb > 1 && bilinear_mode() != 0) {
+    if (g_w && M > 0 && N % 128 == 0 && K % 128 == 0 && nb * kb <= DW_BATCH_MAX && nb * kb > 1 && mode_split()) {
       for (int i = 0; i < nb; ++i)
         for (int j = 0; j < kb; ++j)
           b.it[b.n++] = {gp + 128 * i, x + 128 * j, g_w + (size_t)128 * i * ldgw + 128 * j,

@@ -32,7 +32,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // a partial slab when asplit > 1 (summed in fixed order by slab_sum_rows_kernel).
 // JS = j-steps per LDS chunk (a chunk is 2*JS rows of T = JS KB), FLUSH = number of consecutive
 // `a` whose products share one partial accumulator (two-level summation, see below).
-template <int JS, int FLUSH, int ABL = 0>  // ABL: timing-only ablations (1 no barrier, 2 no global loads, 3 both): wrong results
+template <int JS, int FLUSH>
 __global__ __launch_bounds__(256, 1) void bilinear_rows128_kernel(const float* __restrict__ p, long ldp,
                                                                   const float* __restrict__ q, long ldq,
                                                                   const float* __restrict__ T,
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256, 1) void bilinear_rows128_kernel(const float* _
       float pa_next = p[rowc * ldp + an];
 #pragma unroll
       for (int jc = 0; jc < NCH; ++jc) {
-        if constexpr (!(ABL & 2)) { if (jc + 1 < NCH) BIL_GLOAD(a, jc + 1) else BIL_GLOAD(an, 0); }
+        if (jc + 1 < NCH) BIL_GLOAD(a, jc + 1) else BIL_GLOAD(an, 0);
         // B operands of step jj for this lane's four blocks: one 16-byte LDS read, fetched ahead
         const float4* bs = reinterpret_cast<const float4*>(&Bs[buf][(hi * JS) * 128 + 4 * r]);
         float4 bv = bs[0];
@@ -136,8 +136,8 @@ __global__ __launch_bounds__(256, 1) void bilinear_rows128_kernel(const float* _
           part[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv.w, part[3], 0, 0, 0);
           bv = bn;
         }
-        if constexpr (!(ABL & 2)) BIL_LSTORE(buf ^ 1);
-        if constexpr (!(ABL & 1)) __syncthreads();
+        BIL_LSTORE(buf ^ 1);
+        __syncthreads();
         buf ^= 1;
       }
       pa = pa_next;
@@ -208,14 +208,13 @@ __global__ __launch_bounds__(256, 1) void bilinear_rows128_kernel(const float* _
 //   Tq[a][half = c/64][kh = b/64][s2 = (b/32)%2][piece][cb = (c%64)/16][kg = (b%32)/8][i = c%16][j = b%8]
 // one chunk = (a, half, kh) = 2 k-steps x 3 planes x 4 column blocks x 1 KB; a fragment is one ds_read_b128.
 
-// Timing-only ablations of the fp16 form at 83 340 rows (tools/ring_ablation.py; ABL bits: 1 no barrier, 2 no global
-// loads, 4 no fragment reads, 8 no flush -- the last two let the compiler drop MFMAs and are not usable as skeleton
-// times): 754 us as is, 729 without the barrier, 682 without the LDS-DMA loads, 673 without both, against 520 us of
+// Timing-only ablations of the fp16 form at 83 340 rows (the ablation build and its driver are in the history at
+// 43b4fa4): 754 us as is, 729 without the barrier, 682 without the LDS-DMA loads, 673 without both, against 520 us of
 // pure MFMA issue at the 1.9 GHz the chip holds here.  Tried and dropped (round 1): 4 waves x 64 rows per workgroup
 // (one wave per SIMD on the 512-register budget, every T fragment feeding four row blocks instead of two, i.e. half
 // the LDS fragment traffic): 777 us -- what it saves in LDS reads it loses by having no second wave to cover the
 // flush, the barrier wait and the accumulator-register copies.
-template <int PASSES, int ABL = 0>
+template <int PASSES>
 __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16_kernel(
     const float* __restrict__ p, long ldp, const float* __restrict__ q, long ldq, const uint4* __restrict__ Tq,
     const float* __restrict__ init, long ldi, float* __restrict__ out, long ldo, int nrows, int NA, int tiles, int asplit,
@@ -338,11 +337,9 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16_kernel(
 #define RG_READ(F1_, F2_, F3_, slot_, s2_, cb_)                                                \
   {                                                                                            \
     const bf16x8* fp = ring + (slot_) * (CH16) + (((s2_) * NP) * 4 + (cb_)) * 64;              \
-    if (!(ABL & 4) || (slot_) + (s2_) + (cb_) == 0) {                                          \
-      F1_ = fp[0];                                                                             \
-      F2_ = fp[4 * 64];                                                                        \
-      if (PASSES >= 6) F3_ = fp[8 * 64];                                                       \
-    }                                                                                          \
+    F1_ = fp[0];                                                                               \
+    F2_ = fp[4 * 64];                                                                          \
+    if (PASSES >= 6) F3_ = fp[8 * 64];                                                         \
   }
 #define RG_MFMA1(F1_, F2_, F3_, qi_, P_)                                                       \
   {                                                                                            \
@@ -361,16 +358,13 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16_kernel(
     RG_MFMA1(F1_, F2_, F3_, 2 * (s_) + 1, part[2 * (cb_) + 1])                                 \
   }
   RG_READ(fa1, fa2, fa3, 0, 0, 0);
-  if constexpr ((ABL & 4) != 0) { fb1 = fa1; fb2 = fa2; fb3 = fa3; }
   f32x4 part[8];
   for (int a = a_beg; a < a_end; ++a) {
 #pragma unroll
     for (int ch = 0; ch < 4; ++ch) {
       const int half = ch >> 1, c2 = ch & 1;
-      if constexpr (!(ABL & 2)) {
-        RG_TLOAD((long)a * 4 + ch + 3);
-        if (ch == 0) RG_PLOAD(a + 2);          // AFTER the T loads: see the wait below
-      }
+      RG_TLOAD((long)a * 4 + ch + 3);
+      if (ch == 0) RG_PLOAD(a + 2);          // AFTER the T loads: see the wait below
       if (c2 == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) part[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -391,7 +385,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16_kernel(
           RG_MFMA(fb1, fb2, fb3, s, 2 * cbp + 1);
         }
       }
-      if (c2 == 1 && !(ABL & 8)) {
+      if (c2 == 1) {
         float pva = pst[(a & 3) * PST], pvb = pst[(a & 3) * PST + 16];
         if constexpr (F16) { pva *= rs_a; pvb *= rs_b; }
         const float pas_a = (a & 1) ? -pva : pva, pas_b = (a & 1) ? -pvb : pvb;
@@ -408,7 +402,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16_kernel(
       // used to be, every ch == 0 wait drained it -- a 64-line strided load -- within one k-step)
       if (ch < 2) wait_vmcnt<NP + 1>();
       else wait_vmcnt<NP>();
-      if constexpr (!(ABL & 1)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     }
   }
@@ -538,14 +532,8 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16c_kernel(
 #pragma unroll
   for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(acc[i]));
 
-#if !defined(CGAT_DEV_ABLATIONS)   // the product build: the timing-only variants below do not exist, whatever -DRC_ABL says
-#undef RC_ABL
-#define RC_ABL 0
-#elif !defined(RC_ABL)
-#define RC_ABL 0   // timing-only ablations (wrong results; tools/rc_ablate.sh): 1 no LDS-DMA, 2 no fragment reads, 4 no matrix
-#endif             // instructions, 8 no flush, 16 no wait + barrier per chunk
 #define RC_TLOAD(gi_)                                                                          \
-  { if (!(RC_ABL & 1)) {                                                                         \
+  {                                                                                            \
     const long gi = (gi_) < last_chunk ? (gi_) : last_chunk;                                   \
     const uint4* tb = Tq + gi * CH16;                                                          \
     const unsigned dst = wave_t + (unsigned)((gi_) & 3) * (CH16 * 16);                         \
@@ -553,12 +541,12 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16c_kernel(
     glds_b128(tb + 512, t_off, dst + 8192);                                                    \
     glds_b128(tb + 1024, t_off, dst + 16384);                                                  \
     if (wave_u == 0) glds_b128(tb + 1536, t_off, dst + 24576);                                 \
-  } }
+  }
 #define RC_PLOAD(a_)                                                                           \
-  { if (!(RC_ABL & 1)) {                                                                         \
+  {                                                                                            \
     const int aa = (a_) < a_end ? (a_) : a_end - 1;                                            \
     glds_b32(p + aa, prow_off, wave_p + (unsigned)((a_) & 3) * (PST * 4));                     \
-  } }
+  }
   // everything except the N_ youngest vector-memory operations of this wave (wave 0: + its extra piece) has landed
 #define RC_WAIT(N_) { if (wave_u == 0) wait_vmcnt<(N_) + 1>(); else wait_vmcnt<(N_)>(); }
   RC_PLOAD(a_beg);
@@ -574,21 +562,20 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16c_kernel(
   frag6 ce;
   // group g = 2 s + cb2 of a chunk: the two planes of block cb2 at k-step s
 #define RC_READ(F1_, F2_, slot_, g_)                                                           \
-  { if (!(RC_ABL & 2)) {                                                                         \
+  {                                                                                            \
     const bf16x8* fp = ring + (slot_) * CH16 + ((((g_) >> 1) * 2) * 2 + ((g_) & 1)) * 64;      \
     F1_ = fp[0];                                                                               \
     F2_ = fp[2 * 64];                                                                          \
-  } }
+  }
   // 6-bit fragment j = 3 cb2 + term of a chunk
 #define RC_CREAD(slot_, j_)                                                                    \
-  { if (!(RC_ABL & 2)) {                                                                         \
+  {                                                                                            \
     const unsigned char* cp = cring + (slot_) * (CH16 * 16) + (j_) * 1536;                     \
     const uint4 u_ = *reinterpret_cast<const uint4*>(cp + lane * 16);                          \
     const uint2 w_ = *reinterpret_cast<const uint2*>(cp + 1024 + lane * 8);                    \
     ce.w[0] = u_.x; ce.w[1] = u_.y; ce.w[2] = u_.z; ce.w[3] = u_.w; ce.w[4] = w_.x; ce.w[5] = w_.y; \
-  } }
+  }
 #define RC_MFMA(F1_, F2_, g_)                                                                  \
-  { if (RC_ABL & 4) { part[2 * ((g_) & 1)][0] += (float)F1_[0] + (float)F2_[1]; } else           \
   {                                                                                            \
     _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) {                                         \
       f32x4& P_ = part[2 * ((g_) & 1) + nb];                                                   \
@@ -596,10 +583,9 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16c_kernel(
       P_ = mma16<true>(F1_, q2[2 * ((g_) >> 1) + nb], P_);                                     \
       P_ = mma16<true>(F1_, q1[2 * ((g_) >> 1) + nb], P_);                                     \
     }                                                                                          \
-  } }
+  }
   // correction fragment j (held in ce) into the partial accumulators of its block
 #define RC_CORR(j_)                                                                            \
-  { if (RC_ABL & 4) { part[2 * ((j_) / 3)][1] += __uint_as_float(ce.w[0]); } else                \
   {                                                                                            \
     _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) {                                         \
       f32x4& P_ = part[2 * ((j_) / 3) + nb];                                                   \
@@ -607,7 +593,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16c_kernel(
       else if ((j_) % 3 == 1) P_ = f16c_mma_ht(ce, qt6[nb], P_);                               \
       else P_ = f16c_mma_ll(ce, ql6[nb], P_);                                                  \
     }                                                                                          \
-  } }
+  }
   RC_READ(fa1, fa2, 0, 0);
   RC_CREAD(0, 0);
   f32x4 part[4];
@@ -635,7 +621,6 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16c_kernel(
         RC_MFMA(fb1, fb2, 2 * gp + 1);
       }
       __builtin_amdgcn_sched_barrier(0);       // the flush stays HERE: moved into the next chunk it would keep two sets
-      if (RC_ABL & 8) { acc[4 * ch][0] += part[0][0] + part[1][1] + part[2][2] + part[3][3]; } else
       {                                        // of partial accumulators alive
         float pva = pst[(a & 3) * PST] * rs_a, pvb = pst[(a & 3) * PST + 16] * rs_b;
         const float pas_a = (a & 1) ? -pva : pva, pas_b = (a & 1) ? -pvb : pvb;
@@ -654,11 +639,9 @@ __global__ __launch_bounds__(512, 2) void bilinear_rows128_ring16c_kernel(
       __builtin_amdgcn_sched_barrier(0);
       // chunk i + 2 (issued one iteration ago) must have landed.  Younger than it: this iteration's three (four) T loads
       // and, for ch < 2, the p load issued right behind the T loads of ch == 0
-      if (!(RC_ABL & 16)) {
-        if (ch < 2) RC_WAIT(4)
-        else RC_WAIT(3)
-        __builtin_amdgcn_s_barrier();
-      }
+      if (ch < 2) RC_WAIT(4)
+      else RC_WAIT(3)
+      __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     }
   }
@@ -1402,22 +1385,6 @@ __global__ void prepare_T_f16c_kernel(const float* __restrict__ src, uint4* __re
   if (i >= (long)NA * 512) return;
   prepare_T_f16c_item(src, dst, i, sa, sb, sc, alternate, tmax[per_a ? (int)(i >> 9) : 0]);   // per_a: one scale per block a
 }
-// out[a] = max |W[(128 a + c) * ldw + b]|, b, c < 128: one workgroup per block
-__global__ __launch_bounds__(256) void absmax_blocks128_kernel(const float* __restrict__ W, long ldw, float* __restrict__ out) {
-  const float* blk = W + (long)blockIdx.x * 128 * ldw;
-  float m = 0.f;
-  for (int i = threadIdx.x; i < 128 * 32; i += 256) {
-    const float4 v = *reinterpret_cast<const float4*>(blk + (long)(i >> 5) * ldw + 4 * (i & 31));
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-  }
-  __shared__ float wm[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-}
-
 // Weight operands of the edge / dense kernels in the fp16 form: one workgroup per 128 x 128 block `a` keeps the block
 // in registers, takes its largest magnitude, and writes the two planes of 2^k(a) W[a] in the bf16 kernel's order with
 // two planes per k-step; max |W[a]| goes to wmax[a] behind the planes (the consumer undoes 2^k(a) per column block).
@@ -1663,23 +1630,6 @@ int prepare_T_f16c_launch(const float* src, void* dst, int NA, long sa, long sb,
   return CGAT_OK;
 }
 
-// The same image for a dense-layer weight given as W2 output rows of 128 contiguous inputs (row stride ldw; block a = rows
-// 128 a .. 128 a + 127), e.g. a column slice of a stacked weight: the maximum is taken over exactly those elements
-// (edgez.hip, edge_zc_kernel) -- and PER BLOCK a: an output block whose weights are small beside the tensor's largest keeps
-// its own 24 bits.  NA * F16C_A_FLOATS floats + the NA maxima.
-size_t prepare_W_f16c_rows_floats(int W2) { return (size_t)(W2 / 128) * F16C_A_FLOATS + (size_t)(W2 / 128) + 4; }
-int prepare_W_f16c_rows_launch(const float* W, long ldw, int W2, void* dst, hipStream_t stream) {
-  const int NA = W2 / 128;
-  if (NA <= 0) return CGAT_OK;
-  float* tmax = (float*)dst + (size_t)NA * F16C_A_FLOATS;
-  hipLaunchKernelGGL(absmax_blocks128_kernel, dim3(NA), dim3(256), 0, stream, W, ldw, tmax);
-  CGAT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(prepare_T_f16c_kernel, dim3(cdiv((long)NA * 512, 256)), dim3(256), 0, stream, W, (uint4*)dst, NA,
-                     (long)128 * ldw, 1l, ldw, 0, (const float*)tmax, 1);
-  CGAT_LAUNCH_CHECK();
-  return CGAT_OK;
-}
-
 // ---- the same for several [NA,128,128] tensors at once (the predicted layers of a hypernetwork: 4 x (memset + absmax +
 // prepare) = 12 launches of ~8 us each with a dispatch gap between every pair -> 2 launches).  Maxima without atomics:
 // stage 1 writes one partial maximum per workgroup, every workgroup of stage 2 folds the 64 partials of its tensor.
@@ -1745,10 +1695,9 @@ size_t bilinear_prepare_T_batch_ws_floats(int n) { return (size_t)(n > 0 ? n : 1
 int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, int n0, int n1, int n2, int perm0,
                              int perm1, int perm2, float* part, hipStream_t stream, int alternate) {
   int dims[3] = {n0, n1, n2};
-  const int mode = bilinear_mode();
   static int off = -1;   // CGAT_NO_TPREP_BATCH=1 (debug): prepare the operands one by one
   if (off < 0) { const char* e = getenv("CGAT_NO_TPREP_BATCH"); off = (e && e[0] == '1') ? 1 : 0; }
-  if (off || n < 1 || n > TPREP_MAX || (mode != 2 && mode != 4) || !bilinear_T_interleaved(dims[perm1], dims[perm2]))
+  if (off || n < 1 || n > TPREP_MAX || !mode_f16_T() || !bilinear_T_interleaved(dims[perm1], dims[perm2]))
     return CGAT_ERR_UNSUPPORTED;
   const long st[3] = {(long)n1 * n2, (long)n2, 1};
   const int NA = dims[perm0];
@@ -1761,7 +1710,7 @@ int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, 
   }
   hipLaunchKernelGGL(absmax_partial_batch_kernel, dim3(TPREP_PARTS, n), dim3(256), 0, stream, b, total, part);
   CGAT_LAUNCH_CHECK();
-  if (mode == 4)
+  if (mode_f16c())
     hipLaunchKernelGGL(prepare_T_f16c_batch_kernel, dim3(cdiv((long)NA * 512, 256), n), dim3(256), 0, stream, b, NA,
                        st[perm0], st[perm1], st[perm2], alternate, (const float*)part);
   else
@@ -1826,36 +1775,8 @@ __global__ void slab_sum_ln_tanh_kernel(const float* __restrict__ slab, int spli
   y[(long)row * 128 + 64 + lane] = tanhf((x1 - mean) * rstd);
 }
 
-// any NA, NB, NC: one thread per output element (used for widths other than 128 and as a
-// cross-check of the MFMA kernel in the tests)
-__global__ void bilinear_rows_generic_kernel(const float* __restrict__ p, long ldp, const float* __restrict__ q,
-                                             long ldq, const float* __restrict__ T, const float* __restrict__ init,
-                                             long ldi, float* __restrict__ out, long ldo, int nrows, int NA, int NB,
-                                             int NC) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)nrows * NC) return;
-  int n = (int)(i / NC), c = (int)(i % NC);
-  float s = init ? init[(long)n * ldi + c] : 0.f;
-  for (int a = 0; a < NA; ++a) {
-    float pa = p[(long)n * ldp + a];
-    float t = 0.f;
-    for (int b = 0; b < NB; ++b) t = fmaf(q[(long)n * ldq + b], T[((long)a * NB + b) * NC + c], t);
-    s = fmaf(pa, t, s);
-  }
-  out[(long)n * ldo + c] = s;
-}
-
-static bool force_generic() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CGAT_FORCE_GENERIC");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
 static bool rows_fast(const float* q, long ldq, int NB, int NC) {
-  return NB == 128 && NC == 128 && (ldq % 4) == 0 && (((uintptr_t)q) & 15) == 0 && !force_generic();
+  return NB == 128 && NC == 128 && (ldq % 4) == 0 && (((uintptr_t)q) & 15) == 0;
 }
 
 // how many ways to split the `a` range so that tiles*split fills 256 CUs without a ragged last wave
@@ -1882,37 +1803,34 @@ static int rows_asplit(int nrows, int rows_wg) {
   return best;
 }
 
-int bilinear_mode();
 // rows per workgroup of the kernel that will run (the split-bf16 ring kernel uses 8 waves = 256 rows)
-static int rows_per_wg() { return bilinear_mode() == 0 ? 128 : 256; }
+static int rows_per_wg() { return mode_split() ? 256 : 128; }
 
-bool bilinear_T_interleaved(int NB, int NC) { return NB == 128 && NC == 128 && !force_generic(); }
+bool bilinear_T_interleaved(int NB, int NC) { return NB == 128 && NC == 128; }
 
-// 0 = f32-input MFMA (exact fp32), 6 = 3-way bf16 split with 6 MFMA passes (24-bit operands), 3 = 3 passes,
-// 2 = 2-way fp16 split with 3 passes (22-bit operands, scaled per row / per tensor),
-// 4 = "f16x3c" (DEFAULT): 24-bit operands -- the fp16 passes of mode 2 plus the three 6-bit correction terms
-//     (mfma_bf16.h) in the kernels that have that form (the hypernetwork contractions); every other matrix-core kernel
-//     runs its six-pass bf16 form, exactly as in mode 6 (tests on `bilinear_mode() == 2` are false, `!= 0` / `!= 3` true)
+// the arithmetic mode (ArithMode, kernels.h)
 static int g_bilinear_mode = -1;
 int bilinear_mode() {
   if (g_bilinear_mode < 0) {
     const char* e = getenv("CGAT_BILINEAR_MODE");   // f32 | bf16x6 | bf16x3 | f16x3 | f16x3c (default)
-    g_bilinear_mode = 4;
-    if (e && !strcmp(e, "f32")) g_bilinear_mode = 0;
-    if (e && !strcmp(e, "bf16x3")) g_bilinear_mode = 3;
-    if (e && !strcmp(e, "bf16x6")) g_bilinear_mode = 6;
-    if (e && !strcmp(e, "f16x3")) g_bilinear_mode = 2;
+    g_bilinear_mode = MODE_F16X3C;
+    if (e && !strcmp(e, "f32")) g_bilinear_mode = MODE_F32;
+    if (e && !strcmp(e, "bf16x3")) g_bilinear_mode = MODE_BF16X3;
+    if (e && !strcmp(e, "bf16x6")) g_bilinear_mode = MODE_BF16X6;
+    if (e && !strcmp(e, "f16x3")) g_bilinear_mode = MODE_F16X3;
   }
   return g_bilinear_mode;
 }
-void bilinear_set_mode(int m) { g_bilinear_mode = (m == 6 || m == 3 || m == 2 || m == 4) ? m : 0; }
+void bilinear_set_mode(int m) {   // an unknown value selects f32
+  g_bilinear_mode = (m == MODE_BF16X6 || m == MODE_BF16X3 || m == MODE_F16X3 || m == MODE_F16X3C) ? m : MODE_F32;
+}
 // floats of workspace the prepared T occupies (the bf16 form stores three 2-byte planes, the fp16 form two and its scale,
 // the f16x3c form the fp16 form + 18 bits per element of 6-bit images)
 size_t bilinear_T_floats(int NA, int NB, int NC) {
   size_t n = (size_t)NA * NB * NC;
-  if (!bilinear_T_interleaved(NB, NC) || bilinear_mode() == 0) return n;
-  if (bilinear_mode() == 4) return (size_t)NA * F16C_A_FLOATS + 4;
-  return bilinear_mode() == 2 ? n + 4 : (n * 3 + 1) / 2;
+  if (!bilinear_T_interleaved(NB, NC) || !mode_split()) return n;
+  if (mode_f16c()) return (size_t)NA * F16C_A_FLOATS + 4;
+  return mode_f16() ? n + 4 : (n * 3 + 1) / 2;
 }
 
 size_t bilinear_T_floats_max(int NA, int NB, int NC) {   // the mode may change between a size query and the call
@@ -1929,7 +1847,7 @@ size_t bilinear_rows_ws_bytes(int nrows, int NA, int NB, int NC) {
 // T must come from bilinear_prepare_T (interleaved columns iff bilinear_T_interleaved(NB, NC))
 // ---- fused pair of contractions (see bilinear_rows128_dual_kernel); widths 128, split-bf16 modes only ----
 bool bilinear_dual_fast(int NA, int NB, int NC) {
-  return bilinear_mode() != 0 && NA == 128 && NB == 128 && NC == 128 && !force_generic();
+  return mode_split() && NA == 128 && NB == 128 && NC == 128;
 }
 static int dual_dv_ld(int nrows) { return cdiv(nrows, 256) * 256; }   // rows padded to whole tiles (128 or 256 rows)
 static int dual_asplit_max(int nrows) {   // the f16x3c form runs 256-row workgroups, the others 128-row ones
@@ -1948,7 +1866,7 @@ int bilinear_dual_launch(const float* p, long ldp, const float* q, long ldq, con
   CGAT_CHECK_ARG((ldq % 4) == 0 && (((uintptr_t)q) & 15) == 0 && (((uintptr_t)T) & 15) == 0 && ldp < (1l << 22) &&
                      (long)dual_dv_ld(nrows) * 512 < (1l << 31),
                  "bilinear_dual: q and T must be 16-byte aligned with ldq %% 4 == 0, nrows < 2^23");
-  const bool c256 = bilinear_mode() == 4;   // the f16x3c form: 256-row workgroups, dv complete per row
+  const bool c256 = mode_f16c();   // the f16x3c form: 256-row workgroups, dv complete per row
   const int tiles = cdiv(nrows, c256 ? 256 : 128);
   const int sp = rows_asplit(nrows, c256 ? 256 : 128);
   if (!ws || ws_bytes < bilinear_dual_ws_bytes(nrows)) {
@@ -1965,20 +1883,20 @@ int bilinear_dual_launch(const float* p, long ldp, const float* q, long ldq, con
   {
     CGAT_PROF("bilinear_dual", stream);
     const float* tmax = T + (size_t)128 * 128 * 128;   // f16x3: max |T| behind the two planes
-    if (bilinear_mode() == 6)
-      hipLaunchKernelGGL((bilinear_rows128_dual_kernel<6>), dim3(tiles * sp), dim3(512), 0, stream, p, ldp, q, ldq, zz, ldz,
-                         (const uint4*)T, init1, ldi1, dst, dld, dvp, dv_ld, nrows, 128, tiles, sp, stride, vec_io, tmax);
-    else if (c256) {   // prepare_T_f16c_kernel's image, max |T| behind it
+    if (c256) {   // prepare_T_f16c_kernel's image, max |T| behind it
       CGAT_CHECK_ARG((ldz % 4) == 0 && (((uintptr_t)zz) & 15) == 0 && ldz < (1l << 22),
                      "bilinear_dual: zz must be 16-byte aligned with ldz %% 4 == 0");
       hipLaunchKernelGGL(bilinear_rows128_dualc_kernel, dim3(tiles * sp), dim3(512), 0, stream, p, ldp, q, ldq, zz, ldz,
                          (const uint4*)T, init1, ldi1, dst, dld, dvp, dv_ld, nrows, 128, tiles, sp, stride, vec_io,
                          T + (size_t)128 * F16C_A_FLOATS);
-    } else if (bilinear_mode() == 2)
+    } else if (mode_f16())
       hipLaunchKernelGGL((bilinear_rows128_dual_kernel<2>), dim3(tiles * sp), dim3(512), 0, stream, p, ldp, q, ldq, zz, ldz,
                          (const uint4*)T, init1, ldi1, dst, dld, dvp, dv_ld, nrows, 128, tiles, sp, stride, vec_io, tmax);
-    else
+    else if (mode_bf16x3())
       hipLaunchKernelGGL((bilinear_rows128_dual_kernel<3>), dim3(tiles * sp), dim3(512), 0, stream, p, ldp, q, ldq, zz, ldz,
+                         (const uint4*)T, init1, ldi1, dst, dld, dvp, dv_ld, nrows, 128, tiles, sp, stride, vec_io, tmax);
+    else
+      hipLaunchKernelGGL((bilinear_rows128_dual_kernel<6>), dim3(tiles * sp), dim3(512), 0, stream, p, ldp, q, ldq, zz, ldz,
                          (const uint4*)T, init1, ldi1, dst, dld, dvp, dv_ld, nrows, 128, tiles, sp, stride, vec_io, tmax);
     CGAT_LAUNCH_CHECK();
   }
@@ -2017,7 +1935,7 @@ int bilinear_rows_launch(const float* p, long ldp, const float* q, long ldq, con
       dld = 128;
       stride = (long)nrows * 128;
     }
-    if (bilinear_mode() != 0) {
+    if (mode_split()) {
       CGAT_PROF("bilinear_rows", stream);
       const int tiles2 = cdiv(nrows, 256);
       const int vec_io = ((ldo % 4) == 0 && (dld % 4) == 0 && (((uintptr_t)dst) & 15) == 0 &&
@@ -2027,57 +1945,23 @@ int bilinear_rows_launch(const float* p, long ldp, const float* q, long ldq, con
         return CGAT_ERR_ARG;
       }
       const float* tmax = T + (size_t)NA * 128 * 128;   // f16x3: max |T| behind the two planes (f16x3c: behind its image)
-      if (bilinear_mode() == 6)
-        hipLaunchKernelGGL((bilinear_rows128_ring16_kernel<6>), dim3(tiles2 * sp), dim3(512), 0, stream, p, ldp, q, ldq,
-                           (const uint4*)T, init, ldi, dst, dld, nrows, NA, tiles2, sp, stride, vec_io, tmax);
-      else if (bilinear_mode() == 4)
+      if (mode_f16c())
         hipLaunchKernelGGL(bilinear_rows128_ring16c_kernel, dim3(tiles2 * sp), dim3(512), 0, stream, p, ldp, q, ldq,
                            (const uint4*)T, init, ldi, dst, dld, nrows, NA, tiles2, sp, stride, vec_io,
                            T + (size_t)NA * F16C_A_FLOATS);
-#ifdef CGAT_DEV_ABLATIONS   // timing-only variants (wrong results): only in builds made for tools/ring_ablation.py
-      else if (bilinear_mode() == 2 && getenv("CGAT_RING_ABL")) {
-#define RG_ABL(A_) hipLaunchKernelGGL((bilinear_rows128_ring16_kernel<2, A_>), dim3(tiles2 * sp), dim3(512), 0, stream, p, ldp, q, ldq, (const uint4*)T, init, ldi, dst, dld, nrows, NA, tiles2, sp, stride, vec_io, tmax)
-        switch (atoi(getenv("CGAT_RING_ABL"))) {
-          case 1: RG_ABL(1); break; case 2: RG_ABL(2); break; case 3: RG_ABL(3); break; case 4: RG_ABL(4); break;
-          case 7: RG_ABL(7); break; case 8: RG_ABL(8); break; case 15: RG_ABL(15); break; default: RG_ABL(0); break;
-        }
-#undef RG_ABL
-      }
-#endif
-      else if (bilinear_mode() == 2)
+      else if (mode_f16())
         hipLaunchKernelGGL((bilinear_rows128_ring16_kernel<2>), dim3(tiles2 * sp), dim3(512), 0, stream, p, ldp, q, ldq,
                            (const uint4*)T, init, ldi, dst, dld, nrows, NA, tiles2, sp, stride, vec_io, tmax);
-      else
+      else if (mode_bf16x3())
         hipLaunchKernelGGL((bilinear_rows128_ring16_kernel<3>), dim3(tiles2 * sp), dim3(512), 0, stream, p, ldp, q, ldq,
+                           (const uint4*)T, init, ldi, dst, dld, nrows, NA, tiles2, sp, stride, vec_io, tmax);
+      else
+        hipLaunchKernelGGL((bilinear_rows128_ring16_kernel<6>), dim3(tiles2 * sp), dim3(512), 0, stream, p, ldp, q, ldq,
                            (const uint4*)T, init, ldi, dst, dld, nrows, NA, tiles2, sp, stride, vec_io, tmax);
     } else {
       CGAT_PROF("bilinear_rows", stream);
-      static int variant = -1;  // dev knob: CGAT_BIL_VARIANT = <JS><FLUSH>, e.g. 161, 162, 322, 324
-      if (variant < 0) {
-        const char* ev = getenv("CGAT_BIL_VARIANT");
-        variant = ev ? atoi(ev) : 162;
-      }
-#ifdef CGAT_DEV_ABLATIONS
-      const char* ev2 = getenv("CGAT_BIL_VARIANT_LIVE");  // re-read on every call (A/B in one process)
-      const int v = ev2 ? atoi(ev2) : variant;
-#else
-      const int v = variant >= 900 ? 162 : variant;       // 90x = timing-only ablations: dev builds only
-#endif
-#define BIL_LAUNCH(JS_, FL_)                                                                                     \
-  hipLaunchKernelGGL((bilinear_rows128_kernel<JS_, FL_>), dim3(tiles * sp), dim3(256), 0, stream, p, ldp, q, ldq, \
-                     T, init, ldi, dst, dld, nrows, NA, tiles, sp, stride)
-      switch (v) {
-        case 161: BIL_LAUNCH(16, 1); break;
-        case 901: hipLaunchKernelGGL((bilinear_rows128_kernel<16, 2, 1>), dim3(tiles * sp), dim3(256), 0, stream, p, ldp, q, ldq, T, init, ldi, dst, dld, nrows, NA, tiles, sp, stride); break;
-        case 902: hipLaunchKernelGGL((bilinear_rows128_kernel<16, 2, 2>), dim3(tiles * sp), dim3(256), 0, stream, p, ldp, q, ldq, T, init, ldi, dst, dld, nrows, NA, tiles, sp, stride); break;
-        case 903: hipLaunchKernelGGL((bilinear_rows128_kernel<16, 2, 3>), dim3(tiles * sp), dim3(256), 0, stream, p, ldp, q, ldq, T, init, ldi, dst, dld, nrows, NA, tiles, sp, stride); break;
-        case 164: BIL_LAUNCH(16, 4); break;
-        case 321: BIL_LAUNCH(32, 1); break;
-        case 322: BIL_LAUNCH(32, 2); break;
-        case 324: BIL_LAUNCH(32, 4); break;
-        default: BIL_LAUNCH(16, 2); break;
-      }
-#undef BIL_LAUNCH
+      hipLaunchKernelGGL((bilinear_rows128_kernel<16, 2>), dim3(tiles * sp), dim3(256), 0, stream, p, ldp, q, ldq, T, init,
+                         ldi, dst, dld, nrows, NA, tiles, sp, stride);
     }
     CGAT_LAUNCH_CHECK();
     if (sp > 1 && ln_out) {
@@ -2090,21 +1974,16 @@ int bilinear_rows_launch(const float* p, long ldp, const float* q, long ldq, con
                          (const float*)ws, sp, stride, nrows, out, ldo);
       CGAT_LAUNCH_CHECK();
     }
-  } else if (!force_generic()) {
+  } else {
     // Widths other than 128: out = init + (p (x) q) T, the row-wise outer product [nrows, NA * NB] formed in the operand
-    // loader of the fp32 engine (gemm.hip) and T [NA * NB, NC] as it lies: 0.6 ms at 83 340 rows of width 64 where the
-    // one-thread-per-output kernel below took 5.4 (and 850 ms at width 256)
+    // loader of the fp32 engine (gemm.hip) and T [NA * NB, NC] as it lies: 0.6 ms at 83 340 rows of width 64 where a
+    // one-thread-per-output kernel took 5.4 (and 850 ms at width 256)
     if (init && (init != out || ldi != ldo)) CGAT_TRY(copy2d_launch(init, ldi, out, ldo, nrows, NC, stream));
     GemmParams g = gemm_params(nrows, NC, NA * NB, q, ldq, T, NC, out, ldo);
     g.b_kmajor = 1;
     g.a_outer = p; g.ld_a_outer = ldp; g.outer_n = NB;
     g.beta = init ? 1.f : 0.f;
     CGAT_TRY(gemm_launch(g, nullptr, 0, stream));
-  } else {
-    CGAT_PROF("bilinear_rows_generic", stream);
-    hipLaunchKernelGGL(bilinear_rows_generic_kernel, dim3(cdiv((long)nrows * NC, 256)), dim3(256), 0, stream, p, ldp,
-                       q, ldq, T, init, ldi, out, ldo, nrows, NA, NB, NC);
-    CGAT_LAUNCH_CHECK();
   }
   if (ln_out && !ln_done) {
     if (NC != 128 || ldo != 128) {
@@ -2260,19 +2139,6 @@ __global__ void slab_sum_kernel(const float* __restrict__ slab, int splits, long
   out[i] = s;
 }
 
-__global__ void bilinear_wgrad_generic_kernel(const float* __restrict__ p, long ldp, const float* __restrict__ q,
-                                              long ldq, const float* __restrict__ rr, long ldr,
-                                              float* __restrict__ out, int nrows, int NA, int NB, int NC) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)NA * NB * NC) return;
-  int c = (int)(i % NC);
-  int b = (int)((i / NC) % NB);
-  int a = (int)(i / ((long)NC * NB));
-  float s = 0.f;
-  for (int n = 0; n < nrows; ++n) s = fmaf(p[(long)n * ldp + a] * q[(long)n * ldq + b], rr[(long)n * ldr + c], s);
-  out[i] = s;
-}
-
 // ---------------------------------------------------------------------------------------
 // Split-bf16 weight gradient:  out[a,b,c] = sum_n p[n,a] q[n,b] r[n,c]  with the contraction
 // index n on the MFMA k axis.  Pre-passes (once per call, ~0.1 ms at N = 83k):
@@ -2356,7 +2222,7 @@ int absmax_rows128_launch(const float* t, long ld, int rows, float* out, hipStre
 // for the 16 product splits (4 cycles each) and its MFMAs hold the port for 8 cycles apiece; 96 16x16x32 MFMAs
 // (768 cycles of issue) leave less room beside them than 48 32x32x16 ones (384), so here the 32x32x16 shape wins
 // although it clocks lower.  Fewer VALU instructions per split is the remaining lever.
-template <int PASSES, int ABL = 0>   // ABL (timing only, wrong results): 1 no global loads, 2 no split, 4 no barrier
+template <int PASSES>
 __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_bf16_kernel(const float* __restrict__ pT,
                                                                         const float* __restrict__ qT,
                                                                         const uint4* __restrict__ Rq,
@@ -2443,7 +2309,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_bf16_kernel(const fl
   __syncthreads();
   for (int c = 0; c < nchunks; ++c) {
     const int cur = c & 1;
-    if constexpr (!(ABL & 1)) { if (c + 1 < nchunks) WG_GLOAD(nbeg + (c + 1) * 32); }
+    if (c + 1 < nchunks) WG_GLOAD(nbeg + (c + 1) * 32);
     if ((c & 15) == 0 && c > 0) {   // two-level summation over the long row dimension (512-row partials);
       // groups alternate in sign (see bilinear_rows128_bf16_kernel: cancels the bf16 MFMA's floor bias)
       const float sg = (((c >> 4) - 1) & 1) ? -1.f : 1.f;
@@ -2463,11 +2329,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_bf16_kernel(const fl
       const float av[8] = {pa.x * qa.x, pa.y * qa.y, pa.z * qa.z, pa.w * qa.w,
                            pb.x * qb.x, pb.y * qb.y, pb.z * qb.z, pb.w * qb.w};
       bf16x8 a1, a2v, a3;
-      if constexpr (ABL & 2) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { a1[j] = (__bf16)av[j]; }
-        a2v = a1; a3 = a1;
-      } else if constexpr (F16) {
+      if constexpr (F16) {
         split2_x8_f16(av, a1, a2v);
       } else {
         split3_x8(av, a1, a2v, a3);
@@ -2494,7 +2356,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_bf16_kernel(const fl
       }
     }
     if (c + 1 < nchunks) WG_LSTORE(cur ^ 1);
-    if constexpr (!(ABL & 4)) __syncthreads();
+    __syncthreads();
   }
 #undef WG_GLOAD
 #undef WG_LSTORE
@@ -2859,7 +2721,7 @@ static int wgrad_splits(int nrows, int NA) {
 
 static bool wgrad_fast(const float* q, long ldq, const float* r, long ldr, int NB, int NC) {
   return NB == 128 && NC == 128 && (ldq % 4) == 0 && (ldr % 4) == 0 && (((uintptr_t)q) & 15) == 0 &&
-         (((uintptr_t)r) & 15) == 0 && !force_generic();
+         (((uintptr_t)r) & 15) == 0;
 }
 
 static int wgrad_bf16_splits(int NA) { return cdiv(256, cdiv(NA, 2)); }   // one 512-thread workgroup per CU
@@ -2897,8 +2759,8 @@ static size_t wgrad_batch_ws(int n_layers, int nrows, int NA, int splits, size_t
   return off;
 }
 bool bilinear_wgrad_batch_fast(int n_layers, int NA, int NB, int NC, long ldq, long ldr) {
-  return (bilinear_mode() == 2 || bilinear_mode() == 4) && n_layers >= 1 && n_layers <= WGB_MAX && NA >= 1 && NA <= 128 && NB == 128 && NC == 128 &&
-         (ldr % 4) == 0 && !force_generic();
+  return mode_f16_T() && n_layers >= 1 && n_layers <= WGB_MAX && NA >= 1 && NA <= 128 && NB == 128 && NC == 128 &&
+         (ldr % 4) == 0;
 }
 size_t bilinear_wgrad_batch_ws_bytes(int n_layers, int nrows, int NA, int NB, int NC) {
   const size_t single = bilinear_wgrad_ws_bytes(nrows, NA, NB, NC);
@@ -2922,7 +2784,7 @@ int bilinear_wgrad_batch_prep(int slot, int n_layers, const float* p, long ldp, 
   if (slot < 0 || slot >= n_layers || ((((uintptr_t)q) | ((uintptr_t)r)) & 15) != 0 || nrows <= 0 || nrows > 8000000 ||
       !bilinear_wgrad_batch_fast(n_layers, NA, NB, NC, ldq, ldr))
     return CGAT_ERR_UNSUPPORTED;
-  if (bilinear_mode() == 4)
+  if (mode_f16c())
     return wgradc_prep(slot, 1, n_layers, &p, ldp, &q, ldq, &r, ldr, nrows, NA, ws, ws_bytes, stream);
   const int np = cdiv(nrows, 32) * 32;
   int rps = 0;
@@ -2971,7 +2833,7 @@ int bilinear_wgrad_batch_launch(int n_layers, const float* const* p, long ldp, c
                                      max_wgs > 0 && max_wgs < 256 ? max_wgs / cdiv(NA, 2) : 0));
     return CGAT_OK;
   }
-  if (bilinear_mode() == 4)
+  if (mode_f16c())
     return wgradc_launch(n_layers, p, ldp, q, ldq, r, ldr, out, nrows, NA, ws, ws_bytes, stream, max_wgs, prepared);
   if (max_wgs <= 0 || max_wgs > 256) max_wgs = 256;
   const int npairs = cdiv(NA, 2);
@@ -3053,13 +2915,13 @@ size_t bilinear_wgrad_ws_bytes(int nrows, int NA, int NB, int NC) {
 int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, const float* r, long ldr, float* out,
                           int nrows, int NA, int NB, int NC, void* ws, size_t ws_bytes, hipStream_t stream,
                           int force_splits) {
-  if (wgrad_fast(q, ldq, r, ldr, NB, NC) && (bilinear_mode() == 2 || bilinear_mode() == 4) && nrows > 0 &&
+  if (wgrad_fast(q, ldq, r, ldr, NB, NC) && mode_f16_T() && nrows > 0 &&
       nrows <= 8000000 && NA <= 128) {
     // f16x3 / f16x3c: the batched kernels with one layer (row splits fill the chip)
     return bilinear_wgrad_batch_launch(1, &p, ldp, &q, ldq, &r, ldr, &out, nrows, NA, NB, NC, ws, ws_bytes, stream,
                                        force_splits > 0 ? force_splits * cdiv(NA, 2) : 0);
   }
-  if (wgrad_fast(q, ldq, r, ldr, NB, NC) && bilinear_mode() != 0 && nrows > 0) {
+  if (wgrad_fast(q, ldq, r, ldr, NB, NC) && mode_split() && nrows > 0) {
     size_t o_pT, o_qT, o_Rq, o_slab;
     const size_t need = wgrad_bf16_ws(nrows, NA, &o_pT, &o_qT, &o_Rq, &o_slab);
     if (!ws || ws_bytes < need) {
@@ -3072,7 +2934,7 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
     __bf16* Rq = (__bf16*)((char*)ws + o_Rq);
     float* slab = (float*)((char*)ws + o_slab);
     float* mx = (float*)((char*)ws + need - 16);
-    const bool f16 = bilinear_mode() == 2;
+    const bool f16 = mode_f16();
     if (f16) CGAT_TRY(fill_launch(mx, 0.f, 4, stream));
     hipLaunchKernelGGL(transpose_pad_kernel, dim3(np / 32, cdiv(NA, 32)), dim3(256), 0, stream, p, ldp, nrows, NA, np, pT,
                        f16 ? mx : (float*)nullptr);
@@ -3094,19 +2956,10 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
     splits = cdiv(np, rps);
     {
       CGAT_PROF("bilinear_wgrad", stream);
-#ifdef CGAT_DEV_ABLATIONS   // timing-only variants (wrong results): only in builds made for tools/wgrad_ablation.py
-      static int abl = -1;
-      if (abl < 0) { const char* e = getenv("CGAT_WGRAD_ABL"); abl = e ? atoi(e) : 0; }
-#else
-      const int abl = 0;
-#endif
-#define WG_GO(A_) hipLaunchKernelGGL((bilinear_wgrad128_bf16_kernel<6, A_>), dim3(cdiv(NA, 2), splits), dim3(512), 0, stream, pT, qT, (const uint4*)Rq, slab, np, rps, NA, (const float*)mx)
       if (f16)
         hipLaunchKernelGGL(bilinear_wgrad128_bf16_kernel<2>, dim3(cdiv(NA, 2), splits), dim3(512), 0, stream, pT, qT,
                            (const uint4*)Rq, slab, np, rps, NA, (const float*)mx);
-      else if (bilinear_mode() != 3 && abl) {
-        switch (abl) { case 1: WG_GO(1); break; case 2: WG_GO(2); break; case 3: WG_GO(3); break; case 4: WG_GO(4); break; default: WG_GO(7); break; }
-      } else if (bilinear_mode() != 3)
+      else if (!mode_bf16x3())
         hipLaunchKernelGGL(bilinear_wgrad128_bf16_kernel<6>, dim3(cdiv(NA, 2), splits), dim3(512), 0, stream, pT, qT,
                            (const uint4*)Rq, slab, np, rps, NA, (const float*)mx);
       else
@@ -3139,7 +2992,7 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
     long n = (long)NA * NB * NC;
     hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, (const float*)ws, splits, n, out);
     CGAT_LAUNCH_CHECK();
-  } else if (!force_generic()) {
+  } else {
     // widths other than 128: out [NA, NB * NC] = p^T (q (x) r) on the fp32 engine, rows split over workgroups when the
     // output has few tiles (33 ms -> 0.7 at 83 340 rows of width 64)
     GemmParams g = gemm_params(NA, NB * NC, nrows, p, ldp, r, ldr, out, (long)NB * NC);
@@ -3148,12 +3001,6 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
     g.splits = gemm_pick_splits(NA, NB * NC, nrows);
     if (g.splits > 1 && (!ws || ws_bytes < ws_round((size_t)g.splits * NA * NB * NC, 4))) g.splits = 1;
     CGAT_TRY(gemm_launch(g, ws, ws_bytes, stream));
-  } else {
-    CGAT_PROF("bilinear_wgrad_generic", stream);
-    long n = (long)NA * NB * NC;
-    hipLaunchKernelGGL(bilinear_wgrad_generic_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, p, ldp, q, ldq, r, ldr,
-                       out, nrows, NA, NB, NC);
-    CGAT_LAUNCH_CHECK();
   }
   return CGAT_OK;
 }
@@ -3190,10 +3037,10 @@ int permute3_launch(const float* src, float* dst, int n0, int n1, int n2, int pe
 int bilinear_prepare_T(const float* src, float* dst, int n0, int n1, int n2, int perm0, int perm1, int perm2,
                        hipStream_t stream) {
   int dims[3] = {n0, n1, n2};
-  if (bilinear_T_interleaved(dims[perm1], dims[perm2]) && bilinear_mode() != 0) {
+  if (bilinear_T_interleaved(dims[perm1], dims[perm2]) && mode_split()) {
     long st[3] = {(long)n1 * n2, (long)n2, 1};   // source strides of dims 0, 1, 2
-    if (bilinear_mode() == 2) return prepare_T_f16_launch(src, dst, dims[perm0], st[perm0], st[perm1], st[perm2], 1, stream);
-    if (bilinear_mode() == 4) return prepare_T_f16c_launch(src, dst, dims[perm0], st[perm0], st[perm1], st[perm2], 1, stream);
+    if (mode_f16()) return prepare_T_f16_launch(src, dst, dims[perm0], st[perm0], st[perm1], st[perm2], 1, stream);
+    if (mode_f16c()) return prepare_T_f16c_launch(src, dst, dims[perm0], st[perm0], st[perm1], st[perm2], 1, stream);
     return prepare_T_bf16_launch(src, dst, dims[perm0], st[perm0], st[perm1], st[perm2], 1, stream);
   }
   return permute3_launch(src, dst, n0, n1, n2, perm0, perm1, perm2,

@@ -329,12 +329,6 @@ int prepare_W_x6_batch_launch(const WPrepBatch& b, float* dst, hipStream_t strea
 }
 
 // (the body as a device function: the single and the batched kernel below call it with their descriptor)
-#if !defined(CGAT_DEV_ABLATIONS)   // the product build: the timing-only variants below do not exist, whatever -DCX_ABL says
-#undef CX_ABL
-#define CX_ABL 0
-#elif !defined(CX_ABL)
-#define CX_ABL 0   // timing-only ablations (wrong results): 1 no epilogue loads (bias, residual, derivative, accumulate), 2 no stores
-#endif
 __device__ __forceinline__ void mlp_chain128_x6_body(const ChainDesc& d) {
   constexpr int CH16 = 2 * 3 * 2 * 64;          // 16-byte pieces per chunk: two k-steps x three planes x two blocks x 64 lanes
   constexpr int XP = 36;                        // pitch (floats) of the layout-exchange tile: 32 columns + 4
@@ -439,11 +433,12 @@ __device__ __forceinline__ void mlp_chain128_x6_body(const ChainDesc& d) {
       // with two of them loads the others in the epilogue as before) -- and the bias are requested HERE, two ring steps
       // before their use.  Loaded where they are used (rounds 3-5) every epilogue paid their full latency: the compiler's
       // wait for them is vmcnt(0), which also drains the LDS-DMA pieces in flight (it cannot see those), and the ring
-      // steps behind it stalled in turn -- 0.46 of the chains' 1.22 ms per step (CX_ABL=1).
+      // steps behind it stalled in turn -- 0.46 of the chains' 1.22 ms per step (a timing-only build without these loads,
+      // in the history at 43b4fa4).
       float4 pre[4], pbias[2];
       const float* pre_src = L.dact ? L.dact : (L.resid ? L.resid : ((L.out && L.accumulate) ? L.out : nullptr));
       const long pre_ld = L.dact ? L.ld_dact : (L.resid ? L.ld_resid : L.ld_out);
-      if (pre_src && !(CX_ABL & 1)) {
+      if (pre_src) {
 #pragma unroll
         for (int cb2 = 0; cb2 < 2; ++cb2) {
           const int col = 16 * (2 * hc + cb2) + 4 * kg;
@@ -451,7 +446,7 @@ __device__ __forceinline__ void mlp_chain128_x6_body(const ChainDesc& d) {
           pre[2 * cb2 + 1] = *reinterpret_cast<const float4*>(pre_src + rcb * pre_ld + col);
         }
       }
-      if (L.bias && !(CX_ABL & 1)) {
+      if (L.bias) {
 #pragma unroll
         for (int cb2 = 0; cb2 < 2; ++cb2) pbias[cb2] = *reinterpret_cast<const float4*>(L.bias + 16 * (2 * hc + cb2) + 4 * kg);
       }
@@ -486,34 +481,34 @@ __device__ __forceinline__ void mlp_chain128_x6_body(const ChainDesc& d) {
         const int col = 16 * b16 + 4 * kg;
         const f32x4 pa = part[2 * cb2 + 0] - partn[2 * cb2 + 0], pb = part[2 * cb2 + 1] - partn[2 * cb2 + 1];
         float4 va = make_float4(pa[0], pa[1], pa[2], pa[3]), vb = make_float4(pb[0], pb[1], pb[2], pb[3]);
-        if (L.bias && !(CX_ABL & 1)) {
+        if (L.bias) {
           const float4 b4 = pbias[cb2];
           va.x += b4.x; va.y += b4.y; va.z += b4.z; va.w += b4.w;
           vb.x += b4.x; vb.y += b4.y; vb.z += b4.z; vb.w += b4.w;
         }
         va = chain_act(va, L.act);
         vb = chain_act(vb, L.act);
-        if (L.resid && !(CX_ABL & 1)) {
+        if (L.resid) {
           const bool hoisted = !L.dact;            // (uniform) the residual is the hoisted operand unless a derivative is
           const float4 ra = hoisted ? pre[2 * cb2 + 0] : *reinterpret_cast<const float4*>(L.resid + rca * L.ld_resid + col);
           const float4 rb = hoisted ? pre[2 * cb2 + 1] : *reinterpret_cast<const float4*>(L.resid + rcb * L.ld_resid + col);
           va.x += ra.x; va.y += ra.y; va.z += ra.z; va.w += ra.w;
           vb.x += rb.x; vb.y += rb.y; vb.z += rb.z; vb.w += rb.w;
         }
-        if (L.dact && !(CX_ABL & 1)) {
+        if (L.dact) {
           va = chain_deriv(va, pre[2 * cb2 + 0], L.dact_type);
           vb = chain_deriv(vb, pre[2 * cb2 + 1], L.dact_type);
         }
         if (L.out) {
           float* oa = L.out + rca * L.ld_out + col;
           float* ob = L.out + rcb * L.ld_out + col;
-          if (L.accumulate && !(CX_ABL & 1)) {
+          if (L.accumulate) {
             const bool hoisted = !L.dact && !L.resid;
             const float4 ua = hoisted ? pre[2 * cb2 + 0] : *reinterpret_cast<const float4*>(oa);
             const float4 ub = hoisted ? pre[2 * cb2 + 1] : *reinterpret_cast<const float4*>(ob);
             if (row_a < rows) *reinterpret_cast<float4*>(oa) = make_float4(ua.x + va.x, ua.y + va.y, ua.z + va.z, ua.w + va.w);
             if (row_b < rows) *reinterpret_cast<float4*>(ob) = make_float4(ub.x + vb.x, ub.y + vb.y, ub.z + vb.z, ub.w + vb.w);
-          } else if (!(CX_ABL & 2)) {
+          } else {
             if (row_a < rows) *reinterpret_cast<float4*>(oa) = va;
             if (row_b < rows) *reinterpret_cast<float4*>(ob) = vb;
           }
@@ -557,12 +552,11 @@ __device__ __forceinline__ void mlp_chain128_x6_body(const ChainDesc& d) {
 
 // floats of one prepared weight image in the current arithmetic mode (0: no fused chain in this mode)
 size_t wprep_image_floats() {
-  const int m = bilinear_mode();
-  return m == 2 ? (size_t)WPREP_IMAGE_FLOATS : ((m == 4 || m == 6) ? (size_t)WPREP_IMAGE_FLOATS_X6 : 0);
+  return mode_f16() ? (size_t)WPREP_IMAGE_FLOATS : (mode_24bit() ? (size_t)WPREP_IMAGE_FLOATS_X6 : 0);
 }
 int prepare_W_batch_launch(const WPrepBatch& b, float* dst, hipStream_t stream) {
-  if (bilinear_mode() == 2) return prepare_W_f16_batch_launch(b, dst, stream);
-  if (bilinear_mode() == 4 || bilinear_mode() == 6) return prepare_W_x6_batch_launch(b, dst, stream);
+  if (mode_f16()) return prepare_W_f16_batch_launch(b, dst, stream);
+  if (mode_24bit()) return prepare_W_x6_batch_launch(b, dst, stream);
   return CGAT_ERR_UNSUPPORTED;
 }
 
@@ -587,7 +581,7 @@ bool mlp_chain128_fast(const ChainDesc& d) {
 
 int mlp_chain128_batch_launch(const ChainDesc* d, int n, hipStream_t stream) {
   if (n <= 0) return CGAT_OK;
-  bool same = n <= CHAIN_BATCH_MAX && bilinear_mode() != 2;
+  bool same = n <= CHAIN_BATCH_MAX && !mode_f16();
   for (int i = 1; i < n; ++i) same = same && d[i].rows == d[0].rows;
   if (!same || n == 1) {
     for (int i = 0; i < n; ++i) CGAT_TRY(mlp_chain128_launch(d[i], stream));
@@ -609,7 +603,7 @@ int mlp_chain128_launch(const ChainDesc& d, hipStream_t stream) {
   if (d.rows <= 0) return CGAT_OK;
   CGAT_CHECK_ARG(mlp_chain128_fast(d), "mlp_chain128: needs a split arithmetic mode, 1..%d layers and 16-byte aligned rows", CHAIN_MAX);
   CGAT_PROF("mlp_chain", stream);
-  if (bilinear_mode() == 2) hipLaunchKernelGGL(mlp_chain128_kernel, dim3(cdiv(d.rows, 128)), dim3(256), 0, stream, d);
+  if (mode_f16()) hipLaunchKernelGGL(mlp_chain128_kernel, dim3(cdiv(d.rows, 128)), dim3(256), 0, stream, d);
   else hipLaunchKernelGGL(mlp_chain128_x6_kernel, dim3(cdiv(d.rows, 128)), dim3(256), 0, stream, d);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;

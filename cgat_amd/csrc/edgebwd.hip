@@ -599,7 +599,7 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
 }
 
 bool edge_ge_fast(int Ce, int W2, long ldg, long gzb, long ldo, const void* gZ, const void* out) {
-  return bilinear_mode() != 0 && Ce == 128 && W2 % 128 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
+  return mode_split() && Ce == 128 && W2 % 128 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
          (ldo % 4) == 0 && ((((uintptr_t)gZ) | ((uintptr_t)out)) & 15) == 0;
 }
 
@@ -614,7 +614,7 @@ int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_
   // f16x3 form: with max |gZ| known, for a weight whose 128 outputs are contiguous (s_out == 1: the backward products)
   // or whose W2 inputs are (s_col == 1: a forward nn.Linear weight [128, W2], round 3)
   const bool out_contig = s_out == 1 && (s_col % 4) == 0, in_contig = s_col == 1 && (s_out % 4) == 0 && W2 % 128 == 0;
-  const bool f16 = bilinear_mode() == 2 && amax && (out_contig || in_contig) && (((uintptr_t)We) & 15) == 0;
+  const bool f16 = mode_f16() && amax && (out_contig || in_contig) && (((uintptr_t)We) & 15) == 0;
   // operand (a = column block, b = column in block, c = output k) = We[(128 a + b) * s_col + c * s_out]
   if (f16) {   // per-tensor weight scale: max |We| behind the two planes
     float* wmax = Wq + (size_t)ncb * 16384;
@@ -633,10 +633,10 @@ int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_
   hipLaunchKernelGGL((edge_ge_kernel<P_, R_>), dim3(grid), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq, ncb, \
                      out, ldo, scatter, E, accumulate, bias, amax, R_ ? *rc : none, HeadBatch{})
   // (the per-EDGE launch only -- rc: the rebuilt gZ rows -- and never in the fp16 mode, which has its own bf16 storage form)
-  const bool one = rc && !f16 && edge_mma_bf16() && bilinear_mode() != 3;
+  const bool one = rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
   if (one) GE_GO(1, true);
-  else if (rc) { if (f16) GE_GO(2, true); else if (bilinear_mode() != 3) GE_GO(6, true); else GE_GO(3, true); }
-  else { if (f16) GE_GO(2, false); else if (bilinear_mode() != 3) GE_GO(6, false); else GE_GO(3, false); }
+  else if (rc) { if (f16) GE_GO(2, true); else if (!mode_bf16x3()) GE_GO(6, true); else GE_GO(3, true); }
+  else { if (f16) GE_GO(2, false); else if (!mode_bf16x3()) GE_GO(6, false); else GE_GO(3, false); }
 #undef GE_GO
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
@@ -650,7 +650,7 @@ int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_
 // so that a block's position in its group has the parity of its position in the row (the sign alternation above).
 // Returns the number of groups a launch of this shape takes; 1 = not worth it / not available (then use edge_ge_launch).
 int edge_ge_ksplit_groups(int E, int W2) {
-  if (bilinear_mode() != 4 && bilinear_mode() != 6) return 1;
+  if (!mode_24bit()) return 1;
   const int ncb = W2 / 128, tiles = cdiv(E, 256);
   if (W2 % 128 != 0 || E < 1024 || tiles >= 192) return 1;     // (the reference's fixtures stay on the unsplit forms)
   int best = 1;
@@ -662,7 +662,7 @@ int edge_ge_ksplit_launch(const float* gZ, long ldg, long gzb, const float* We, 
                           float* slabs, const int* scatter, int E, int S, hipStream_t stream, const EdgeRC* rc) {
   if (E <= 0) return CGAT_OK;
   const int ncb = W2 / 128;
-  CGAT_CHECK_ARG(S >= 1 && ncb % S == 0 && (S == 1 || ((ncb / S) & 1) == 0) && (bilinear_mode() == 4 || bilinear_mode() == 6),
+  CGAT_CHECK_ARG(S >= 1 && ncb % S == 0 && (S == 1 || ((ncb / S) & 1) == 0) && mode_24bit(),
                  "edge_ge_ksplit: %d groups of %d column blocks", S, ncb);
   CGAT_TRY(prepare_T_bf16_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
   CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);
@@ -703,8 +703,8 @@ int edge_ge_prepared_launch(const float* x, long ldx, const void* Wq, int ncb, f
 size_t edge_ge_heads_image_floats(int W2) { return (size_t)(W2 / 128) * 24576 + 4; }
 bool edge_ge_heads_fast(int heads, int W2, long ldx, long ldy, long ldw, const void* x, const void* w, const void* y,
                         const float* amax) {
-  const bool f16 = bilinear_mode() == 2 && amax;
-  const bool six = bilinear_mode() == 4 || bilinear_mode() == 6;      // round 6: the 24-bit modes batch their heads too
+  const bool f16 = mode_f16() && amax;
+  const bool six = mode_24bit();      // round 6: the 24-bit modes batch their heads too
   return (f16 || six) && heads >= 1 && heads <= TPREP_MAX && W2 % 128 == 0 && ldw == W2 &&
          (((uintptr_t)w) & 15) == 0 && edge_ge_fast(128, W2, ldx, 128, ldy, x, y);
 }
@@ -716,7 +716,7 @@ int edge_ge_heads_launch(int heads, const float* x, long ldx, long s_x, const fl
   const size_t img = edge_ge_heads_image_floats(W2);
   const HeadBatch hb = {s_x, (long)(img / 4), s_bias, s_y, 0};
   const EdgeRC none = {};
-  if (bilinear_mode() != 2) {
+  if (!mode_f16()) {
     // operand (a = column block, b = column in block, c = output k) = W_h[c * W2 + 128 a + b], as edge_ge_launch's
     CGAT_TRY(prepare_T_bf16_heads_launch(W, ws, ncb, 128, 1, W2, /*alternate=*/1, heads, s_w, (long)img, stream));
     CGAT_PROF("rows_ge", stream);
@@ -740,7 +740,7 @@ int edge_ge_heads_launch(int heads, const float* x, long ldx, long s_x, const fl
 }
 
 bool edge_gw_fast(int Ce, int W2, long ldg, long gzb, const void* gZ) {
-  return bilinear_mode() != 0 && Ce == 128 && W2 % 256 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
+  return mode_split() && Ce == 128 && W2 % 256 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
          (((uintptr_t)gZ) & 15) == 0;
 }
 static int gw_xcd_order() {   // CGAT_GW_XCD=0: plain workgroup order (A/B switch)
@@ -771,7 +771,7 @@ int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde
   float* planes = ws;
   float* slab = ws + (((size_t)na * 128 * 128 * 3 + 1) / 2 + 15) / 16 * 16;
   // operand (a = slot block, b = slot in block, c = k) = e[perm[128 a + b] * lde + c], zero past E
-  const bool f16 = bilinear_mode() == 2 && gmax && emax;
+  const bool f16 = mode_f16() && gmax && emax;
   CGAT_TRY(prepare_T_bf16_rows_launch(e, lde, perm, E, planes, na, stream, f16 ? emax : nullptr));
   {
     CGAT_PROF(perm ? "edge_gw" : "rows_gw", stream);
@@ -780,10 +780,10 @@ int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde
 #define GW_GO(P_, R_)                                                                                                  \
   hipLaunchKernelGGL((edge_gw_kernel<P_, R_>), dim3(S * (ncb / 2)), dim3(512), 0, stream, gZ, ldg, gzb,                \
                      (const uint4*)planes, slab, E, ncb, nsteps, S, gmax, emax, R_ ? *rc : none, gw_xcd_order())
-    const bool one = rc && !f16 && edge_mma_bf16() && bilinear_mode() != 3;
+    const bool one = rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
     if (one) GW_GO(1, true);
-    else if (rc) { if (f16) GW_GO(2, true); else if (bilinear_mode() != 3) GW_GO(6, true); else GW_GO(3, true); }
-    else { if (f16) GW_GO(2, false); else if (bilinear_mode() != 3) GW_GO(6, false); else GW_GO(3, false); }
+    else if (rc) { if (f16) GW_GO(2, true); else if (!mode_bf16x3()) GW_GO(6, true); else GW_GO(3, true); }
+    else { if (f16) GW_GO(2, false); else if (!mode_bf16x3()) GW_GO(6, false); else GW_GO(3, false); }
 #undef GW_GO
     CGAT_LAUNCH_CHECK();
   }

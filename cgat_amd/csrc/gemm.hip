@@ -200,8 +200,8 @@ struct TileLoader {
   }
 };
 
-// ABL: timing-only ablations (1 no barrier, 2 no global loads, 4 no LDS stores); OUTER: 1 = A, 2 = B is an outer product
-template <bool AKM, bool BKM, int ABL = 0, int OUTER = 0>
+// OUTER: 1 = A, 2 = B is an outer product
+template <bool AKM, bool BKM, int OUTER = 0>
 __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
   constexpr int PA = AKM ? 132 : 129;
   constexpr int PB = BKM ? 132 : 129;
@@ -305,11 +305,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
           for (int t = 0; t < 16; ++t) acc[i][j][t] = 0.f;
         }
     }
-    if constexpr (!(ABL & 2)) {
-      if (c + 1 < nchunks) {
-        la.load(tid, CHUNK_K(c + 1), kend, ra);
-        lb.load(tid, CHUNK_K(c + 1), kend, rb);
-      }
+    if (c + 1 < nchunks) {
+      la.load(tid, CHUNK_K(c + 1), kend, ra);
+      lb.load(tid, CHUNK_K(c + 1), kend, rb);
     }
     const float* as = As[cur] + hi * PA + wm + r;
     const float* bs = Bs[cur] + hi * PB + wn + r;
@@ -322,13 +320,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmParams p) {
       acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
       acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
     }
-    if constexpr (!(ABL & 4)) {
-      if (c + 1 < nchunks) {
-        la.template store<PA>(tid, As[cur ^ 1], ra);
-        lb.template store<PB>(tid, Bs[cur ^ 1], rb);
-      }
+    if (c + 1 < nchunks) {
+      la.template store<PA>(tid, As[cur ^ 1], ra);
+      lb.template store<PB>(tid, Bs[cur ^ 1], rb);
     }
-    if constexpr (!(ABL & 1)) __syncthreads();
+    __syncthreads();
   }
 
 #undef CHUNK_K
@@ -575,27 +571,12 @@ int gemm_launch(GemmParams p, void* ws, size_t ws_bytes, hipStream_t stream) {
   dim3 grid(outer >= 8 ? 8 * inner * cdiv(outer, 8) : outer * inner);
   // split arithmetic modes: the six-pass bf16 form of the same product (gemmsplit.hip; CGAT_GEMM_SPLIT=0: this engine)
   static const bool split_on = [] { const char* e = getenv("CGAT_GEMM_SPLIT"); return !(e && e[0] == '0'); }();
-  bool on_split = split_on && bilinear_mode() != 0;
-#ifdef CGAT_DEV_ABLATIONS
-  if (getenv("CGAT_GEMM_ABL")) on_split = false;
-#endif
-  if (on_split) {
+  if (split_on && mode_split()) {
     CGAT_TRY(gemm_split_launch(p, grid.x, stream));
   } else {
     CGAT_PROF("gemm_f32", stream);
-#ifdef CGAT_DEV_ABLATIONS   // timing-only variants (wrong results): only in builds made for tools/gemm_probe.py
-    const char* ab = getenv("CGAT_GEMM_ABL");
-    const int abl = ab ? atoi(ab) : 0;
-#else
-    const int abl = 0;
-#endif
-    if (p.a_outer) hipLaunchKernelGGL((gemm_f32_kernel<false, true, 0, 1>), grid, dim3(256), 0, stream, p);
-    else if (p.b_outer) hipLaunchKernelGGL((gemm_f32_kernel<true, true, 0, 2>), grid, dim3(256), 0, stream, p);
-    else if (abl == 1 && !p.a_kmajor && !p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, false, 1>), grid, dim3(256), 0, stream, p);
-    else if (abl == 2 && !p.a_kmajor && !p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, false, 2>), grid, dim3(256), 0, stream, p);
-    else if (abl == 4 && !p.a_kmajor && !p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, false, 4>), grid, dim3(256), 0, stream, p);
-    else if (abl == 6 && !p.a_kmajor && !p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, false, 6>), grid, dim3(256), 0, stream, p);
-    else if (abl == 7 && !p.a_kmajor && !p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, false, 7>), grid, dim3(256), 0, stream, p);
+    if (p.a_outer) hipLaunchKernelGGL((gemm_f32_kernel<false, true, 1>), grid, dim3(256), 0, stream, p);
+    else if (p.b_outer) hipLaunchKernelGGL((gemm_f32_kernel<true, true, 2>), grid, dim3(256), 0, stream, p);
     else if (!p.a_kmajor && !p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, stream, p);
     else if (!p.a_kmajor && p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, dim3(256), 0, stream, p);
     else if (p.a_kmajor && !p.b_kmajor) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, dim3(256), 0, stream, p);

@@ -76,7 +76,27 @@ int rowprog_launch(const cgat_rowprog_op* ops, int n_ops, uint32_t* sync_words, 
 // out[n,c] = init[n,c] + sum_{a<NA,b<NB} p[n,a] q[n,b] T3[a,b,c], with T = bilinear_prepare_T(T3 source):
 // a permuted copy whose columns are interleaved for the MFMA kernel when NB == NC == 128.
 bool bilinear_T_interleaved(int NB, int NC);
-int bilinear_mode();               // 0 f32 MFMA, 6 / 3: split-bf16 passes, 2: f16x3 (two fp16 planes), 4: f16x3c (h + l + t)
+// The arithmetic mode of the matrix-core kernels (values: the C ABI's cgat_set/get_bilinear_mode).
+//   F32     f32-input MFMA (exact fp32)
+//   F16X3   two fp16 planes per operand, three passes (22-bit operands, scaled per row / per tensor)
+//   BF16X3  three bf16 planes, three passes (~3e-6; diagnostic, never the default)
+//   F16X3C  (default) 24-bit operands: the fp16 passes of F16X3 plus three 6-bit correction terms (mfma_bf16.h) in the
+//           kernels that have that form (the hypernetwork contractions); every other matrix-core kernel runs its
+//           six-pass bf16 form, exactly as in BF16X6
+//   BF16X6  three bf16 planes, six passes (24-bit operands)
+enum ArithMode : int { MODE_F32 = 0, MODE_F16X3 = 2, MODE_BF16X3 = 3, MODE_F16X3C = 4, MODE_BF16X6 = 6 };
+int bilinear_mode();               // the current ArithMode
+// The decisions the launchers make on it.  Every mode but F32 runs split operands on the matrix cores.
+inline bool mode_split() { return bilinear_mode() != MODE_F32; }
+// the 22-bit fp16 family: bilinear_rows128_ring16_kernel<2>, edge_zx_kernel, the f16p weight gradient, the fp16 weight images
+inline bool mode_f16() { return bilinear_mode() == MODE_F16X3; }
+// the corrected fp16 forms of the hypernetwork contractions: ring16c, dualc, bilinear_wgrad128_f16c_kernel
+inline bool mode_f16c() { return bilinear_mode() == MODE_F16X3C; }
+inline bool mode_bf16x3() { return bilinear_mode() == MODE_BF16X3; }
+// 24-bit operands: the six-pass bf16 per-edge and dense forms (edge_z6w, batched heads, rowprog one-launch paths)
+inline bool mode_24bit() { const int m = bilinear_mode(); return m == MODE_F16X3C || m == MODE_BF16X6; }
+// T operands as fp16-plane images (prepared and differentiated in batches): f16x3 and f16x3c
+inline bool mode_f16_T() { const int m = bilinear_mode(); return m == MODE_F16X3 || m == MODE_F16X3C; }
 void bilinear_set_mode(int m);
 size_t bilinear_T_floats(int NA, int NB, int NC);  // workspace floats of the prepared T
 size_t bilinear_T_floats_max(int NA, int NB, int NC);   // ... in whichever arithmetic mode needs most (size queries)
@@ -122,9 +142,6 @@ int prepare_T_bf16_launch(const float* src, void* dst, int NA, long sa, long sb,
                           hipStream_t stream);
 int prepare_T_bf16_heads_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, int alternate, int heads,
                                 long s_head, long image_floats, hipStream_t stream);
-// f16x3c image (bilinear.hip, prepare_T_f16c_kernel) of a dense-layer weight: W2 output rows of 128 inputs, row stride ldw
-size_t prepare_W_f16c_rows_floats(int W2);
-int prepare_W_f16c_rows_launch(const float* W, long ldw, int W2, void* dst, hipStream_t stream);
 // ---- fused edge pre-activations + attention logits, edgez.hip ----
 bool edge_z_fast(int Ce, int W2, int H, int Hd, long lde, long ld_add, long ldz, const void* e, const void* Pi,
                  const void* Pj, const void* Z, const void* wA);

@@ -35,7 +35,7 @@ struct Ctx {
   }
   static bool tprep_mode() {   // CGAT_NO_TPREP=1: prepare per product, as before round 5 (A/B switch)
     static const bool off = [] { const char* e = getenv("CGAT_NO_TPREP"); return e && e[0] == '1'; }();
-    return !off && (bilinear_mode() == 4 || bilinear_mode() == 6);
+    return !off && mode_24bit();
   }
   int tprep_run() {
     if (dry || !tprep_mode() || tprep.n == 0 || !tprep_images) { if (!tprep_mode()) tprep.n = 0; return CGAT_OK; }
@@ -90,7 +90,7 @@ struct Ctx {
     if (dense128 && linear128_fast(p.K, p.N, p.lda, p.ldc, p.A, p.C) && scratch_bytes >= linear128_ws_bytes(p.N)) {
       const long so = p.b_kmajor ? 1 : p.ldb, sk = p.b_kmajor ? p.ldb : 1;
       return linear128_launch(p.A, p.lda, p.B, so, sk, p.bias, p.act, p.beta == 1.f, p.C, p.ldc, p.M, scratch, s, p.N,
-                              p.N != 128 ? nullptr : (bilinear_mode() == 2 ? wprep_find(p.B, so, sk) : tprep_find(p.B, so, sk)));
+                              p.N != 128 ? nullptr : (mode_f16() ? wprep_find(p.B, so, sk) : tprep_find(p.B, so, sk)));
     }
     return gemm_launch(p, scratch, scratch_bytes, s);
   }
@@ -685,10 +685,10 @@ extern "C" int32_t cgat_get_edge_storage(void) { return edge_storage(); }
 // A layer this predicate rejects makes cgat_nodes_attention_forward return CGAT_ERR_UNSUPPORTED under edge storage "bf16"
 // -- the forward refuses what the backward could not handle (Hd = 128 / 384 ran forward and failed in backward).)
 static bool attn_bf16(const AttnDims& d) {
-  if (!(edge_bf16_storage() && bilinear_mode() != 0 && bilinear_mode() != 3 && d.C == 128 && d.Ce == 128 &&
+  if (!(edge_bf16_storage() && (mode_f16() || mode_24bit()) && d.C == 128 && d.Ce == 128 &&
         d.Hd % 128 == 0 && d.W2 % 256 == 0 && d.N > 0 && d.E > 0))
     return false;
-  if (bilinear_mode() != 2 && !(d.Hd == 256 && d.Hd % 4 == 0)) return false;   // seg_bwd_msg / _att<true>: two 128-column blocks per head
+  if (!mode_f16() && !(d.Hd == 256 && d.Hd % 4 == 0)) return false;   // seg_bwd_msg / _att<true>: two 128-column blocks per head
   return true;
 }
 
@@ -776,7 +776,7 @@ static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_para
   // the generic GEMM + row-dot otherwise (and in the f32 arithmetic mode)
   const bool fused_z = !c.dry && edge_z_fast(d.Ce, d.W2, d.H, d.Hd, d.Ce, d.W2, d.W2, e, Pi, Pj, sv.Z, p->A_out_w);
   // Z stored as bf16 (edge-storage mode "bf16"): by edge_zx in the f16x3 mode, by the six-pass per-edge kernel otherwise
-  const bool zb = attn_bf16(d) && (zx || (fused_z && bilinear_mode() != 2));
+  const bool zb = attn_bf16(d) && (zx || (fused_z && !mode_f16()));
   if (!c.dry && edge_bf16_storage() && !zb && d.N > 0 && d.E > 0) {
     cgat_set_error("nodes_attention_forward: edge storage \"bf16\" is set but this layer (C %d, Ce %d, H %d, Hd %d, arithmetic "
                    "mode %d) has no bf16 form -- refusing to run it in fp32 storage under that label", d.C, d.Ce, d.H, d.Hd,
@@ -808,13 +808,13 @@ static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_para
   // aggr = (1/H) [ sum_h S[:,h,:] fc_out_M[h]^T + ssum b ].  At the benchmark widths the H products run as
   // H * Hd / 128 accumulating launches of the dense-layer kernel (K = 128 each; the generic f32 GEMM tile took 0.1 ms
   // per head) and 1/H is applied by the bias product that closes the sum.
-  const bool out_fast = bilinear_mode() != 0 && d.C == 128 && d.Hd % 128 == 0;
+  const bool out_fast = mode_split() && d.C == 128 && d.Hd % 128 == 0;
   // Round 6: ONE K = H * Hd launch instead (the 24-bit modes, more rows than the small-row programs take): the H per-head
   // weights are not one affine operand, but their six-pass images -- one batched image launch, head h's blocks behind
   // head h - 1's -- are exactly the contiguous operand of the K = W2 -> 128 kernel (edgebwd.hip).  Saves five passes over
   // aggr (42 MB read + written each at 83 340 atoms) and four launches.
   const int ncb_h = d.Hd / 128;
-  const bool out_one = out_fast && (bilinear_mode() == 4 || bilinear_mode() == 6) && d.N > rowprog_max_rows() &&
+  const bool out_one = out_fast && mode_24bit() && d.N > rowprog_max_rows() &&
                        d.H <= TPREP_MAX && (ncb_h % 2) == 0;      // (even: the per-head block parity is the global one)
   const size_t out_img_bytes = (size_t)d.H * ncb_h * 24576 * sizeof(float);
   if (out_one) c.need(out_img_bytes);
@@ -983,13 +983,13 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
   float* gbcat = c.take<float>((size_t)d.W2);
   float* gS = c.take<float>((size_t)d.N * d.HHd);
   float* gs = c.take<float>((size_t)d.N * d.H);
-  float* gas = bilinear_mode() != 0 ? c.take<float>((size_t)d.N * d.C) : nullptr;   // g_aggr / H (fast fc_out path)
+  float* gas = mode_split() ? c.take<float>((size_t)d.N * d.C) : nullptr;   // g_aggr / H (fast fc_out path)
   float* tt = c.take<float>((size_t)d.E * d.H);
   float* ga = c.take<float>((size_t)d.E * d.H);
   // At the benchmark widths gZ [E, W2] is never stored: edge_seg_bwd_kernel leaves one bit per element behind and the
   // three consumers rebuild the rows (struct EdgeRC, kernels.h) -- E * W2 / 8 bytes of workspace instead of 4 E * W2
   // (edge storage mode 2 keeps the stored-gZ backward of round 1 at these widths too: the A/B reference of the tests)
-  const bool rc_shape = bilinear_mode() != 0 && edge_rc_shape(d.Ce, d.H, d.Hd) && d.W2 % 256 == 0 && d.N > 0 && d.E > 0 &&
+  const bool rc_shape = mode_split() && edge_rc_shape(d.Ce, d.H, d.Hd) && d.W2 % 256 == 0 && d.N > 0 && d.E > 0 &&
                         edge_storage() != 2;
   float* gZ = c.take<float>(rc_shape ? (size_t)d.E * (d.W2 / 32) : (size_t)d.E * d.W2);
   float* partial = c.take<float>((size_t)chunks * d.HHd);
@@ -1010,7 +1010,7 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
   // The per-head second layer of the message network at the benchmark widths (C = 128, Hd a multiple of 128): the input
   // gradients on the dense-layer kernel (K = 128 -> Hd outputs per head), the H * Hd / 128 weight-gradient blocks in one
   // batched launch of the rows kernel (rowsdw.hip); 1/H is folded into one scaled copy of g_aggr.
-  const bool out_fast = bilinear_mode() != 0 && d.C == 128 && d.Hd % 128 == 0 && d.H * (d.Hd / 128) <= DW_BATCH_MAX;
+  const bool out_fast = mode_split() && d.C == 128 && d.Hd % 128 == 0 && d.H * (d.Hd / 128) <= DW_BATCH_MAX;
   bool out_done = false;
   if (out_fast) {
     c.need(rows_dw128_batch_ws_bytes(d.H * (d.Hd / 128), d.N));
@@ -1028,7 +1028,7 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
                   c.scratch_bytes >= rows_dw128_batch_ws_bytes(b.n, d.N))) {
       RUN(scale_launch(g_aggr, invH, gas, (long)d.N * d.C, c.s));
       const size_t gs_img_bytes = (size_t)d.H * linear128_heads_image_floats(d.Hd) * sizeof(float);
-      if (!c.dry && (bilinear_mode() == 4 || bilinear_mode() == 6) && d.N > rowprog_max_rows() && d.H > 1 &&
+      if (!c.dry && mode_24bit() && d.N > rowprog_max_rows() && d.H > 1 &&
           c.scratch_bytes >= gs_img_bytes && (((uintptr_t)p->M_out_w) & 15) == 0) {
         // all heads in one launch pair (round 6): head h reads the same gas, its weight at + h * C * Hd, writes gS + h * Hd
         CGAT_TRY(linear128_heads_launch(d.H, gas, d.C, 0, p->M_out_w, 1, d.Hd, (long)d.C * d.Hd, nullptr, 0, CGAT_ACT_NONE, 0, gS,
@@ -1080,13 +1080,13 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
     size_t shm = (size_t)d.HHd * sizeof(float);
     const bool vec = (d.Hd % 4 == 0) && ((((uintptr_t)sv.Z) | ((uintptr_t)gZ) | ((uintptr_t)gS) | ((uintptr_t)Gi) |
                                           ((uintptr_t)p->A_out_w)) & 15) == 0;
-    have_scales = vec && bilinear_mode() == 2 && d.Ce == 128 && (((uintptr_t)e) & 15) == 0;
+    have_scales = vec && mode_f16() && d.Ce == 128 && (((uintptr_t)e) & 15) == 0;
     if (have_scales) CGAT_TRY(fill_launch(scales, 0.f, 8, c.s));
     // the forward stored Z as bf16 under exactly this predicate (same tensors, same alignment)
-    const bool zb_x = attn_bf16(d) && bilinear_mode() == 2 &&
+    const bool zb_x = attn_bf16(d) && mode_f16() &&
                       edge_zx_fast(d.C, d.Ce, d.W2, d.H, d.Hd, d.W2, d.W2, e, x, Gi, sv.Z, p->A_out_w) &&
                       edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, Gi, Gj, Gi, gbcat);
-    const bool zb_6 = attn_bf16(d) && bilinear_mode() != 2 &&
+    const bool zb_6 = attn_bf16(d) && !mode_f16() &&
                       edge_z_fast(d.Ce, d.W2, d.H, d.Hd, d.Ce, d.W2, d.W2, e, Gi, Gj, sv.Z, p->A_out_w);
     zb = zb_x || zb_6;
     if (edge_bf16_storage() && !zb) {
@@ -1219,7 +1219,7 @@ static int edge_hidden_backward_impl(Ctx& c, const cgat_plan* plan, const AttnDi
   // products of the tail (K = W2 -> 128 and K = E) run on two fp16 planes (three passes) instead of the six-pass bf16
   // form they fell back to without scales: 43 + 22 ms of the harness-default network's 252-ms step
   bool have_scales = false;
-  const bool f16_ok = !c.dry && bilinear_mode() == 2 && d.Ce == 128 && (((uintptr_t)e) & 15) == 0 && d.E > 0;
+  const bool f16_ok = !c.dry && mode_f16() && d.Ce == 128 && (((uintptr_t)e) & 15) == 0 && d.E > 0;
   if (g_is_pre) {
     if (f16_ok && gpre_absmax) {
       CGAT_TRY(fill_launch(scales, 0.f, 8, c.s));
@@ -1414,7 +1414,7 @@ static int hnet_forward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const 
   const size_t WW = (size_t)W * W;
   // the re-laid T of every predicted layer, prepared up front in two launches where the batched form exists (f16x3, f16x3c)
   const size_t Tfl = bilinear_T_floats(W, W, W);
-  const bool batch_T = W == 128 && (bilinear_mode() == 2 || bilinear_mode() == 4) && p->n_hyper <= TPREP_MAX;
+  const bool batch_T = W == 128 && mode_f16_T() && p->n_hyper <= TPREP_MAX;
   float* Tp = c.take<float>((batch_T ? (size_t)p->n_hyper : 1) * Tfl);
   float* Tpart = c.take<float>(bilinear_prepare_T_batch_ws_floats(p->n_hyper));
   const bool batch_w = W == 128 && p->n_hyper * (p->n_fc + 2) <= WPREP_MAX;
@@ -1432,7 +1432,7 @@ static int hnet_forward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const 
   if (batch_w) {   // every dense-layer weight of the pass, prepared in one launch (forward orientation [out][in])
     for (int l = 0; l < p->n_hyper; ++l) {
       for (int s = 0; s < p->n_fc; ++s) c.wprep_add(p->layer[l].fc_w[s], W, 1);
-      if (bilinear_mode() == 2) c.wprep_add(p->layer[l].head_b, W, 1);   // read by linear128_launch in that mode only
+      if (mode_f16()) c.wprep_add(p->layer[l].head_b, W, 1);   // read by linear128_launch in that mode only
       else c.tprep_add(p->layer[l].head_b, W, 1);                        // (the 24-bit modes: the dense-layer kernel's image)
       c.wprep_add(p->layer[l].head_w + WW * W, W, 1);
     }
@@ -1553,7 +1553,7 @@ static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const
   const size_t WW = (size_t)W * W;
   const size_t rw = (size_t)rows * W;
   const size_t Tfl = bilinear_T_floats(W, W, W);
-  const bool batch_T = W == 128 && (bilinear_mode() == 2 || bilinear_mode() == 4) && p->n_hyper <= TPREP_MAX && bilinear_dual_fast(W, W, W);
+  const bool batch_T = W == 128 && mode_f16_T() && p->n_hyper <= TPREP_MAX && bilinear_dual_fast(W, W, W);
   float* Tp = c.take<float>((batch_T ? (size_t)p->n_hyper : 1) * Tfl);
   float* Tpart = c.take<float>(bilinear_prepare_T_batch_ws_floats(p->n_hyper));
   float* g_hin = c.take<float>(rw);
@@ -1572,7 +1572,7 @@ static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const
   // predicted layer keeps its own g_t and writes its g_hin term to a slab; the slabs are added in the order the
   // accumulating chains ran in (bit-identical).
   const bool chain_batch = chain_ok && defer_dw && rows <= 8192 && p->n_hyper > 1 && p->n_hyper <= CHAIN_BATCH_MAX &&
-                           bilinear_mode() != 2;
+                           !mode_f16();
   float* g_t_all = c.take<float>((chain_batch ? (size_t)p->n_hyper : 1) * rw);
   float* ghin_slabs = chain_batch ? c.take<float>((size_t)p->n_hyper * rw) : nullptr;
   ChainDesc pending[CHAIN_BATCH_MAX];
@@ -1595,7 +1595,7 @@ static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const
   if (batch_w) {   // the same weights in the transposed orientation (g_in = g_out W)
     for (int l = 0; l < p->n_hyper; ++l) {
       for (int s = 0; s < p->n_fc; ++s) c.wprep_add(p->layer[l].fc_w[s], 1, W);
-      if (bilinear_mode() == 2) c.wprep_add(p->layer[l].head_b, 1, W);
+      if (mode_f16()) c.wprep_add(p->layer[l].head_b, 1, W);
       else { c.tprep_add(p->layer[l].head_b, 1, W); c.tprep_add(p->layer[l].head_w + WW * W, 1, W); }
       c.wprep_add(p->layer[l].head_w + WW * W, 1, W);
     }
@@ -1889,7 +1889,7 @@ extern "C" int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_param
     const char* e = getenv("CGAT_SIDE_DW");
     dw_env = e ? ((e[0] == '1') ? 1 : 0) : -1;
   }
-  const int dw_side = dw_env >= 0 ? dw_env : (bilinear_mode() == 4 ? 1 : 0);
+  const int dw_side = dw_env >= 0 ? dw_env : (mode_f16c() ? 1 : 0);
   HnetSide side = {(hipStream_t)side_stream, side_ws, side_ws_bytes, side_wgs, dw_side};
   return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g, &side);
 }

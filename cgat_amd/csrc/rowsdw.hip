@@ -336,7 +336,6 @@ __global__ __launch_bounds__(256) void rows_dw128_reduce_kernel(const float* __r
   else if (bsum) bsum[i - (long)nx * 16384] = s;
 }
 
-int bilinear_mode();
 static bool dws_enabled();
 int rows_dw128_batch_launch(DwBatchDesc d, void* ws, size_t ws_bytes, hipStream_t stream);
 static int dw_rows_per_wg(int rows) {
@@ -380,7 +379,7 @@ int rows_dw128_launch(const float* G, long ldg, const float* X1, long ldx1, floa
     cgat_set_error("rows_dw128: workspace too small (%zu < %zu)", ws_bytes, need);
     return CGAT_ERR_WORKSPACE;
   }
-  if (nx == 1 && bilinear_mode() != 0 && dws_enabled()) {   // split arithmetic modes: the bf16 matrix-core form, as a batch of one
+  if (nx == 1 && mode_split() && dws_enabled()) {   // split arithmetic modes: the bf16 matrix-core form, as a batch of one
     DwBatchDesc b;
     memset(&b, 0, sizeof(b));
     b.n = 1; b.rows = rows; b.ldg = ldg; b.ldx = ldx1; b.ldo = ldo1;
@@ -456,7 +455,7 @@ int rows_dw128_batch_launch(DwBatchDesc d, void* ws, size_t ws_bytes, hipStream_
     cgat_set_error("rows_dw128_batch: workspace too small (%zu < %zu)", ws_bytes, need);
     return CGAT_ERR_WORKSPACE;
   }
-  const bool split_form = bilinear_mode() != 0 && dws_enabled();   // bf16 matrix cores (exact fp32 MFMA in the f32 mode)
+  const bool split_form = mode_split() && dws_enabled();   // bf16 matrix cores (exact fp32 MFMA in the f32 mode)
   d.splits = dw_batch_splits(d.n, d.rows);
   d.rows_per_unit = cdiv(cdiv(d.rows, d.splits), 32) * 32;   // whole 32-row K-steps (two 16-row double batches)
   // rounding the unit up to 16 rows can leave trailing units that start past the last row (rows = 650, n = 24: unit 9

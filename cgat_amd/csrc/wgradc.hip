@@ -41,12 +41,6 @@ typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
 #ifndef WGC_PRIO
 #define WGC_PRIO 2
 #endif
-#if !defined(CGAT_DEV_ABLATIONS)   // the product build: the timing-only variants below do not exist, whatever -DWGC_ABL says
-#undef WGC_ABL
-#define WGC_ABL 0
-#elif !defined(WGC_ABL)
-#define WGC_ABL 0                           // timing-only ablations (wrong results): 1 no q loads, 2 no split arithmetic,
-#endif                                      // 4 no LDS fragment reads, 8 no LDS-DMA, 16 no matrix instructions
 
 // ------------------------------- operand preparation -------------------------------
 // mx[4 * layer + which] = max |tensor|, which 0 / 1 / 2 = p / q / r  (mx zeroed before)
@@ -187,23 +181,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
                                                                         const unsigned char* __restrict__ Rs_,
                                                                         const float* __restrict__ mx_,
                                                                         WgradBatchDesc u) {
-#if defined(WGC_STAMPS) && !defined(CGAT_DEV_ABLATIONS)
-#error "WGC_STAMPS is a diagnostic build: add -DCGAT_DEV_ABLATIONS"
-#endif
-#ifdef WGC_STAMPS   // diagnostic build (tools/wgrad_stamps.py): s_memtime at the phase boundaries of iterations 100..103 of
-  // workgroup 0, left in out[0] instead of that workgroup's results
-  __shared__ __attribute__((aligned(16))) unsigned char smem[WGC_SLOTS * WGC_SLOT_B + 2048];
-#define WGC_TS(k_)                                                                                       \
-  if (c >= 100 && c < 104) {                                                                             \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                          \
-    if (lane == 0) reinterpret_cast<unsigned long long*>(smem + WGC_SLOTS * WGC_SLOT_B)[(wave * 4 + (c - 100)) * 8 + (k_)] = t_; \
-  }
-#define WGC_TS7(dep_) { unsigned d_ = dep_[0]; asm volatile("" : "+v"(d_)); WGC_TS(7) }   /* after the value exists */
-#else
   __shared__ __attribute__((aligned(16))) unsigned char smem[WGC_SLOTS * WGC_SLOT_B];
-#define WGC_TS(k_)
-#define WGC_TS7(dep_)
-#endif
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wb = wave & 3;
@@ -256,10 +234,10 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
       // their matrix phase (WGC_STEP): issued as a burst by the grp-0 waves before their split, the 13 pieces cost those
       // waves ~800 cycles of their critical path, and the burst of 52 KB landing in LDS beside the fragment reads of the
       // partner's matrix phase and the p reads of the split stretched BOTH (any two of the three cost nothing, all three
-      // +0.45 ms per launch: tools/wgrad_ablate.sh, round 5).  The chunk index is clamped: the last iterations re-load
+      // +0.45 ms per launch, round 5: the ablation build is in the history at 43b4fa4).  The chunk index is clamped: the last iterations re-load
       // the last chunk into a slot nobody reads.
 #define WGC_DMA_PIECE(m_, sl_, rb_, cc_, vo16_, vo4_)   /* branch-free: every piece is one 1-KB global_load_lds_dwordx4 */ \
-  if (!(WGC_ABL & 8)) {                                                                      \
+  {                                                                                          \
     /* the bases are laundered so that each piece's address arithmetic happens HERE: hoisted to the top of the phase   \
        (13 pieces x 64-bit source + LDS address) it spilled 38 SGPRs into vector registers and 159 of those to scratch */ \
     const unsigned char* rbl_ = (rb_);                                                       \
@@ -303,9 +281,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
     f32x4 qv_[8];                                                                                                 \
     /* issued from inline asm: the compiler cannot see the LDS-DMA below and would wait vmcnt(0) -- i.e. for the \
        DMA -- before the last q value; the values are tied to the counted wait instead */                       \
-    if (WGC_ABL & 1) {                                                                                            \
-      _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) qv_[j_] = (f32x4){1.f, 2.f, 3.f, 4.f};                     \
-    } else {                                                                                                      \
+    {                                                                                                             \
       const unsigned qo_ = (unsigned)lq_ * 16u;                                                                   \
       asm volatile("global_load_dwordx4 %0, %8, %9\n\tglobal_load_dwordx4 %1, %8, %9 offset:1024\n\t"             \
                    "global_load_dwordx4 %2, %8, %9 offset:2048\n\tglobal_load_dwordx4 %3, %8, %9 offset:3072\n\t" \
@@ -322,7 +298,6 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
     const unsigned char* ps_ = smem + (unsigned)((ci_) % WGC_SLOTS) * WGC_SLOT_B + grp * 1024 + (lq_ >> 5) * 32;         \
     unsigned T_[16];                                                                                              \
     _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) {                                                            \
-      if (WGC_ABL & 2) { T_[2 * j_] = 0; T_[2 * j_ + 1] = 0; continue; }                                          \
       const float4 pv_ = *reinterpret_cast<const float4*>(ps_ + (j_ >> 1) * 64 + (j_ & 1) * 16);                   \
       const float x0_ = qv_[j_].x * pv_.x, x1_ = qv_[j_].y * pv_.y, x2_ = qv_[j_].z * pv_.z, x3_ = qv_[j_].w * pv_.w; \
       const f16x2 h0_ = __builtin_convertvector((f32x2){x0_, x1_}, f16x2);                                        \
@@ -336,14 +311,12 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
       L[2 * j_] = __builtin_bit_cast(unsigned, l0_); L[2 * j_ + 1] = __builtin_bit_cast(unsigned, l1_);           \
       T_[2 * j_] = __builtin_bit_cast(unsigned, t0_); T_[2 * j_ + 1] = __builtin_bit_cast(unsigned, t1_);         \
     }                                                                                                             \
-    WGC_TS(6)                                                                                                     \
     f16x32 hv_, lv_;                                                                                              \
     bf16x32 tv_;                                                                                                  \
     __builtin_memcpy(&hv_, H, 64);                                                                                \
     __builtin_memcpy(&lv_, L, 64);                                                                                \
     __builtin_memcpy(&tv_, T_, 64);                                                                               \
     const u32x6 l6_ = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(lv_, 1.0f);                                      \
-    WGC_TS7(l6_)                                                                                                  \
     const u32x6 h6_ = __builtin_amdgcn_cvt_scalef32_pk32_bf6_f16(hv_, 4096.0f);                                   \
     const u32x6 t6_ = __builtin_amdgcn_cvt_scalef32_pk32_bf6_bf16(tv_, 0x1p-12f);                                 \
     _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) { A6l[i_] = l6_[i_]; A6h[i_] = h6_[i_]; A6t[i_] = t6_[i_]; } \
@@ -354,14 +327,14 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
       // The B operands of group g + 3 are requested before group g issues (four rotating register sets, order pinned
       // with sched_barrier), i.e. 160-224 cycles of matrix work ahead of their use: left to itself the compiler requests
       // each operand right before its use and the wave sits out the LDS latency 20 times per chunk, and with two groups
-      // of lead a matrix phase still took 2700 cycles for 1920 of matrix work (tools/wgrad_stamps.py).  512-row partial
+      // of lead a matrix phase still took 2700 cycles for 1920 of matrix work (s_memtime stamps: a diagnostic build in the
+      // history at 43b4fa4).  512-row partial
       // sums (8 chunks) go to `tot` with alternating sign (the sign is in the staged p: cancels the matrix instruction's
       // accumulator rounding bias, see bilinear_rows128_ring16_kernel).
 #define WGC_LOADG(g_, X_, Y_)                                                                                     \
   {                                                                                                               \
     constexpr int cb_ = (g_) / 7, k_ = (g_) % 7;                                                                  \
-    if constexpr (WGC_ABL & 4) {                                                                                  \
-    } else if constexpr (k_ & 1) {                                                                                \
+    if constexpr (k_ & 1) {                                                                                       \
       constexpr int im_ = k_ == 1 ? 1 : (k_ == 3 ? 2 : 0);       /* B image: h6 (for t*h), t6 (for h*t), l6 */    \
       X_ = *reinterpret_cast<const uint4*>(sl_ + WGC_PL_B + (im_ * 4 + cb_) * 1536);                              \
       const uint2 y2_ = *reinterpret_cast<const uint2*>(sl8_ + WGC_PL_B + (im_ * 4 + cb_) * 1536 + 1024);         \
@@ -374,8 +347,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
 #define WGC_EXECG(g_, X_, Y_, PART_)   /* PART_ 0: the group's first matrix instruction; 1: the rest */              \
   {                                                                                                               \
     constexpr int cb_ = (g_) / 7, k_ = (g_) % 7;                                                                  \
-    if constexpr (WGC_ABL & 16) {                                                                                 \
-    } else if constexpr (k_ & 1) {                                                                                \
+    if constexpr (k_ & 1) {                                                                                       \
       if constexpr (PART_ == 0) {                                                                                 \
         if constexpr (k_ == 1) acc[cb_] = wgc_mma6(A6t, X_, make_uint2(Y_.x, Y_.y), acc[cb_], 3);                 \
         else if constexpr (k_ == 3) acc[cb_] = wgc_mma6(A6h, X_, make_uint2(Y_.x, Y_.y), acc[cb_], 3);            \
@@ -452,7 +424,6 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
 #pragma clang loop unroll(disable)
         for (int c = 0; c <= nchunks; ++c) {
           unsigned pf = 0;
-          WGC_TS(0)
           if (c < nchunks) {
             // q of the NEXT chunk is pulled into this XCD's L2 by one load per wave whose 64 lanes touch the 64 lines of
             // the wave's 8-KB block (result unused; the register stays reserved until the wait that ends the iteration):
@@ -463,32 +434,23 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
                         const char* nb_ = qF + (long)(c + 1 < nchunks ? c + 1 : c) * 32768;
                         asm volatile("global_load_dword %0, %1, %2" : "=v"(pf) : "v"((unsigned)lq_ * 128u), "s"(nb_) : "memory");
                       }
-                      wait_vmcnt<(WGC_ABL & 8) ? 1 : WGC_NDMA0 + 1>(); WGC_TS(1))
-            WGC_TS(2)
+                      wait_vmcnt<WGC_NDMA0 + 1>();)
             WGC_MFMA(c, 0, 0)
-            WGC_TS(3)
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           asm volatile("" ::"v"(pf));
-          WGC_TS(4)
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
-          WGC_TS(5)
         }
       } else {
 #pragma clang loop unroll(disable)
         for (int c = 0; c <= nchunks; ++c) {
-          WGC_TS(0)
           if (c > 0) WGC_MFMA(c - 1, 0, 0)
-          WGC_TS(1)
           if (c < nchunks) WGC_SPLIT(c, WGC_DMA(c + 1, WGC_NDMA0, 13)   /* (iteration 0 repeats part of the prologue's chunk 1: harmless) */
-                                     wait_vmcnt<(WGC_ABL & 8) ? 0 : 13 - WGC_NDMA0>(); WGC_TS(2))
-          WGC_TS(3)
+                                     wait_vmcnt<13 - WGC_NDMA0>();)
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          WGC_TS(4)
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
-          WGC_TS(5)
         }
       }
 #undef WGC_DMA
@@ -500,13 +462,6 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
 #undef WGC_LOADG
     }
     const int a = a0 + grp;
-#ifdef WGC_STAMPS
-    if (blockIdx.x == 0) {
-      __syncthreads();
-      if (tid < 256) reinterpret_cast<unsigned long long*>(u.out[0])[tid] =
-          reinterpret_cast<unsigned long long*>(smem + WGC_SLOTS * WGC_SLOT_B)[tid];
-    } else
-#endif
     if (a < u.NA) {
       float* o = u.splits == 1 ? u.out[layer] + (long)a * 128 * 128
                                : u.slab + (((long)layer * u.splits + z) * u.NA + a) * 128 * 128;
@@ -626,9 +581,6 @@ int wgradc_launch(int n_layers, const float* const* p, long ldp, const float* co
                        (const float*)((char*)ws + o_qF), (const unsigned char*)ws + o_Rs, (const float*)((char*)ws + o_mx), u);
   }
   CGAT_LAUNCH_CHECK();
-#ifdef WGC_STAMPS
-  return CGAT_OK;
-#endif
   if (splits > 1) {
     const long n = (long)NA * 128 * 128;
     hipLaunchKernelGGL(wgc_slab_sum_kernel, dim3(cdiv(n, 256), n_layers), dim3(256), 0, stream, (const float*)u.slab, splits,
