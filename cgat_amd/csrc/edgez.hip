@@ -361,6 +361,7 @@ __global__ __launch_bounds__(256, 2) void edge_z_kernel(const float* __restrict_
 //   2  the message column blocks: each 32-column slice of z = part + Pi[dst] + Pj[src] is staged in LDS (rounded to bf16
 //      first under bf16 edge storage, as mode 0 stores it), and red(a, ch) reduces it into the weighted segment sums
 //      (edge_msg_wsum_kernel).  Nothing per edge reaches memory.
+// The logits of head h (of the H heads this tile computes) go to a_out[row * lda + h].
 // Rows >= row_lim are clamped to row_lim - 1 (their results are discarded).  The counted wait below allows for the
 // stores of mode 0 only; modes 1 and 2 wait for the gathers of the current slice with 4 fewer younger operations (in
 // mode 2 the weighted sums' stores of the previous slice are older still: waited for too, never overtaken).
@@ -377,7 +378,7 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
                                          const float* Pj, const int* srci, long ld_add,
                                          float* Z, long ldz, int row0, int row_lim,
                                          const float* wA, const float* bA, int H,
-                                         int cb_per_head, float* a_out, int act, float* omax,
+                                         int cb_per_head, float* a_out, int lda, int act, float* omax,
                                          const Red& red) {
   constexpr int CH = Z6_CH;
   constexpr int SLOTS = Z6_SLOTS;
@@ -545,8 +546,8 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
       db += __shfl_xor(db, 16, 64); db += __shfl_xor(db, 32, 64);                              \
       if ((lk_ >> 4) == 0) {   /* (clamped rows rewrite row E - 1's logits with identical values) */ \
         const float bh = bA ? bA[h] : 0.f;                                                     \
-        a_out[(long)ra_ * H + h] = da + bh;                                                    \
-        a_out[(long)rb_ * H + h] = db + bh;                                                    \
+        a_out[(long)ra_ * lda + h] = da + bh;                                                  \
+        a_out[(long)rb_ * lda + h] = db + bh;                                                  \
       }                                                                                        \
       dot_a = 0.f; dot_b = 0.f;                                                                \
     }                                                                                          \
@@ -602,7 +603,9 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
 #undef Z6_CHUNK
 }
 
-// MODE 0 (the training forward) and MODE 1 (logits only: Z, ZB, act and omax unused)
+// MODE 0 (the training forward) and MODE 1 (logits only: Z, ZB, act and omax unused).
+// In MODE 1 the heads are dealt to grid.y groups (few row tiles): group y computes heads [y H / gy, (y + 1) H / gy) from
+// its ncb = (H / gy) * cb_per_head column blocks; each head's logit is the sum over its own blocks, as in one group.
 template <bool ZB, int MODE = 0>
 __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restrict__ e, long lde, const int* __restrict__ perm,
                                                           const uint4* __restrict__ Wq, int ncb,
@@ -613,8 +616,16 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
                                                           int H, int cb_per_head, float* __restrict__ a_out, int act,
                                                           float* __restrict__ omax) {
   __shared__ uint4 smem[Z6_SLOTS * Z6_CH + 512];      // the ring + fc_out_A's weight (<= 2048 floats)
-  z6w_tile<MODE, ZB>(smem, nullptr, e, lde, perm, Wq, ncb, Pi, dsti, Pj, srci, ld_add, Z, ldz, blockIdx.x * 256, E, wA, bA,
-                     H, cb_per_head, a_out, act, omax, Z6NoRed{});
+  if constexpr (MODE == 1) {
+    const int hg = H / (int)gridDim.y, h0 = (int)blockIdx.y * hg;
+    const long c0 = (long)blockIdx.y * ncb * 128;     // the group's first column
+    z6w_tile<1, ZB>(smem, nullptr, e, lde, perm, Wq + c0 / 128 * 6144, ncb, Pi + c0, dsti, Pj + c0, srci, ld_add, Z, ldz,
+                    blockIdx.x * 256, E, wA + c0, bA ? bA + h0 : nullptr, hg, cb_per_head, a_out + h0, H, act, omax,
+                    Z6NoRed{});
+  } else {
+    z6w_tile<MODE, ZB>(smem, nullptr, e, lde, perm, Wq, ncb, Pi, dsti, Pj, srci, ld_add, Z, ldz, blockIdx.x * 256, E, wA, bA,
+                       H, cb_per_head, a_out, H, act, omax, Z6NoRed{});
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -633,12 +644,17 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
 //     part, column) then run the chain acc = fma(leaky(z), alpha, acc) over the part's rows in ascending order, as
 //     seg_wsum_vec_kernel does (its update contracts to v_fma_f32).  A segment of more than SEG_LONG rows keeps
 //     seg_wsum_long_kernel's G strided row groups (G = 1024 / min(HHd / 4, 256)) and adds them in group order at its end.
-//   * Only the part that continues past a sub-tile carries its partial sums (G x HHd floats of LDS) to the next one;
-//     it is the last part of one sub-tile and the first of the next, and the thread that finishes one sub-tile's first
-//     part also runs its last part -- in that order -- so the carry is read before it is overwritten.
+//   * Only the part that continues past a sub-tile carries its partial sums (G x the workgroup's columns, LDS) to the
+//     next one; it is the last part of one sub-tile and the first of the next, and the thread that finishes one
+//     sub-tile's first part also runs its last part -- in that order -- so the carry is read before it is overwritten.
 //   * Segments without rows get S = 0 (seg_wsum_vec_kernel writes its zero accumulator for them).
+//   * The message column blocks are dealt to grid.y groups: group y owns the ncb blocks from column y * ncb * 128 on,
+//     over the same row range as every other group (each column's chain is the same whatever group runs it).  The
+//     launcher takes enough groups that the carry, Glong x ncb * 128 floats, fits WSUM_CARRY -- two at H * Hd = 1280 or
+//     2048, where Glong = 4 -- and, below 128 row tiles of 256, as many as fill the chip (z_col_groups).  What a group
+//     repeats is the edge rows' split (512 bytes a row against 2 x 4 x ncb x 128 gathered) and the part bookkeeping.
 // ---------------------------------------------------------------------------------------
-#define WSUM_CARRY 4096   // floats: G * HHd <= 4096 for HHd <= 1024
+constexpr int WSUM_CARRY = 4096;   // floats: Glong * ncb * 128 <= 4096 (the launcher's column groups)
 template <bool ZB>
 __global__ __launch_bounds__(512, 2) void edge_msg_wsum_kernel(const float* __restrict__ e, long lde,
                                                                const int* __restrict__ perm, const uint4* __restrict__ Wq,
@@ -655,7 +671,7 @@ __global__ __launch_bounds__(512, 2) void edge_msg_wsum_kernel(const float* __re
   __shared__ int plo[256], pseg[256], pr0[256], pr1[256];   // the sub-tile's segment parts: first local row, segment, rows
   __shared__ int sh[12];
   const int tid = threadIdx.x;
-  const int HHd = H * Hd;
+  const int HHd = H * Hd, HHg = ncb * 128, cg0 = (int)blockIdx.y * HHg;   // all columns; this group's: [cg0, cg0 + HHg)
   const int quads = HHd / 4, tpr = quads < 256 ? quads : 256, Glong = 1024 / tpr;   // seg_wsum_long_kernel's row groups
   if (tid == 0) {
     auto lb = [&](long v) {   // first s in [0, N] with rowptr[s] >= v
@@ -673,9 +689,10 @@ __global__ __launch_bounds__(512, 2) void edge_msg_wsum_kernel(const float* __re
   __syncthreads();
   const int s_begin = sh[0], s_end = sh[1], R0 = sh[2], R1 = sh[3];
   // segments without rows
-  for (long i = tid; i < (long)(s_end - s_begin) * quads; i += 512) {
-    const int s = s_begin + (int)(i / quads), q = (int)(i % quads);
-    if (rowptr[s] == rowptr[s + 1]) *reinterpret_cast<float4*>(S + (long)s * HHd + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long i = tid; i < (long)(s_end - s_begin) * (HHg / 4); i += 512) {
+    const int s = s_begin + (int)(i / (HHg / 4)), q = (int)(i % (HHg / 4));
+    if (rowptr[s] == rowptr[s + 1])
+      *reinterpret_cast<float4*>(S + (long)s * HHd + cg0 + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   const int c = tid & 31, slot = tid >> 5;
   for (int t0 = R0; t0 < R1; t0 += 256) {
@@ -699,18 +716,18 @@ __global__ __launch_bounds__(512, 2) void edge_msg_wsum_kernel(const float* __re
     const int nparts = sh[4] + sh[5] + sh[6] + sh[7];
     __syncthreads();
     __syncthreads();
-    // one part of one segment for column col of the slice (a, ch): rows of group g are r0 + g + k G
+    // one part of one segment for column col of the slice (a, ch) (cl: the group's own): rows of group g are r0 + g + k G
     auto part = [&](int i, int a, int ch) {
-      const int col = a * 128 + (ch >> 1) * 64 + (ch & 1) * 32 + c, h = col / Hd;
+      const int cl = a * 128 + (ch >> 1) * 64 + (ch & 1) * 32 + c, col = cg0 + cl, h = col / Hd;
       const int r0 = pr0[i], r1 = pr1[i], lo = t0 + plo[i], hi = i + 1 < nparts ? t0 + plo[i + 1] : t1;
       const int G = r1 - r0 > SEG_LONG ? Glong : 1;
       const bool cin = r0 < t0, cout = r1 > t1;
       float tot = 0.f;
       for (int g = 0; g < G; ++g) {
-        float acc = cin ? carry[g * HHd + col] : 0.f;
+        float acc = cin ? carry[g * HHg + cl] : 0.f;
         int r = lo + (((g - (lo - r0)) % G) + G) % G;
         for (; r < hi; r += G) acc = __builtin_fmaf(zst[(r - t0) * 32 + c], alst[(r - t0) * H + h], acc);
-        if (cout) carry[g * HHd + col] = acc;
+        if (cout) carry[g * HHg + cl] = acc;
         else tot = g == 0 ? acc : tot + acc;
       }
       if (!cout) S[(long)pseg[i] * HHd + col] = tot;
@@ -720,11 +737,10 @@ __global__ __launch_bounds__(512, 2) void edge_msg_wsum_kernel(const float* __re
       for (int i = slot; i < nparts - 1; i += 16) part(i, a, ch);
       if (slot == 0) part(nparts - 1, a, ch);
     };
-    z6w_tile<2, ZB>(smem, zst, e, lde, perm, Wq, ncb, Pi, dsti, Pj, srci, ld_add, nullptr, 0, t0, t1, nullptr, nullptr, H,
-                    Hd / 128, nullptr, CGAT_ACT_NONE, nullptr, red);
+    z6w_tile<2, ZB>(smem, zst, e, lde, perm, Wq + (long)blockIdx.y * ncb * 6144, ncb, Pi + cg0, dsti, Pj + cg0, srci,
+                    ld_add, nullptr, 0, t0, t1, nullptr, nullptr, H, Hd / 128, nullptr, H, CGAT_ACT_NONE, nullptr, red);
   }
 }
-#undef WSUM_CARRY
 
 // ---------------------------------------------------------------------------------------
 // The per-edge launch with the x_j projection folded in (f16x3 arithmetic):
@@ -1105,29 +1121,39 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
 }
 
 // ---- the forward without grad (edge_z6w_kernel<., 1> and edge_msg_wsum_kernel above) ----
-// Exactly the shapes at which edge_z_launch runs the per-edge launch as edge_z6w_kernel (24-bit modes, C = Ce = 128,
-// Hd % 128 == 0, >= 128 row tiles of 256), at most 1024 message columns (the carry of a long
-// segment's row groups lives in 16 KB of LDS), 32-bit gather offsets and E * H % 4 == 0.
+// The shapes at which edge_z_launch runs the per-edge launch of the 24-bit modes with the six-pass arithmetic (C = Ce =
+// 128, Hd % 128 == 0; as edge_z6w_kernel or, below 128 row tiles of 256, as the 128-row kernel with column groups: the
+// same Z and logits), with
+//   * at most 2048 columns per half (fc_out_A's weight in edge_z6w_kernel's LDS, as in edge_z_launch; the carry of
+//     edge_msg_wsum_kernel stays within its 16 KB by column groups) and at most 8 heads (its alpha staging);
+//   * E * H % 4 == 0;
+//   * 32-bit gather offsets: N * 4 * 2 H Hd < 2^32 bytes, kept as a guard rather than widened (the training forward's
+//     six-pass launch has the same bound; 100 000 atoms at H * Hd = 2048 use 1.6 GB of it).
 bool edge_infer_fused(int N, int E, int C, int Ce, int H, int Hd) {
   const long HHd = (long)H * Hd;
   return mode_24bit() && edge_z6w_on() &&
-         C == 128 && Ce == 128 && Hd % 128 == 0 && HHd <= 1024 && N > 0 && E > 0 && cdiv(E, 256) >= 128 &&
+         C == 128 && Ce == 128 && Hd % 128 == 0 && HHd <= 2048 && H <= 8 && N > 0 && E > 0 &&
          // the training forward's S sits behind Z and alpha in the saved buffer and is 16-byte aligned only when
          // E * H % 4 == 0; otherwise seg_wsum_launch takes its scalar kernel, whose order is not the one built here
          ((long)E * H) % 4 == 0 &&
          (long)N * 4 * (2 * HHd) < (1l << 32);
 }
+// Below 128 row tiles of 256 (the harness' shipped 64-crystal batch: 60 - 120 tiles) both launches deal their column
+// blocks to grid.y groups, as the training forward's few-row launch does; CGAT_Z_COL_GROUPS=0 turns that off.
+static bool infer_few_rows(int E) { return cdiv(E, 256) < 128; }
 int edge_logits_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
                        const float* Pi, const int* dsti, const float* Pj, const int* srci, int E, const float* wA,
                        const float* bA, int H, int Hd, float* a_out, hipStream_t stream) {
-  CGAT_CHECK_ARG(W2 == 2 * H * Hd && Hd % 128 == 0 && (lde % 4) == 0 && wA && a_out && perm &&
+  const int ncb = H * Hd / 128;
+  CGAT_CHECK_ARG(W2 == 2 * H * Hd && Hd % 128 == 0 && H * Hd <= 2048 && (lde % 4) == 0 && wA && a_out && perm &&
                  ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)wA)) & 15) == 0,
-                 "edge_logits: needs Hd %% 128 == 0, 16-byte aligned rows and fc_out_A's weight");
+                 "edge_logits: needs Hd %% 128 == 0, H * Hd <= 2048, 16-byte aligned rows and fc_out_A's weight");
   CGAT_TRY(prepare_T_bf16_launch(We, Wq, W2 / 128, 128 * ldw, 1, ldw, 0, stream));   // (the whole W2 image: edge_msg_wsum's too)
+  const int G = infer_few_rows(E) ? z_groups(cdiv(E, 256), ncb, Hd / 128) : 1;       // groups of whole heads
   CGAT_PROF("edge_logits", stream);
-  hipLaunchKernelGGL((edge_z6w_kernel<false, 1>), dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq,
-                     H * Hd / 128, Pi, dsti, Pj, srci, (long)W2, (float*)nullptr, 0l, E, wA, bA, H, Hd / 128, a_out,
-                     CGAT_ACT_NONE, (float*)nullptr);
+  hipLaunchKernelGGL((edge_z6w_kernel<false, 1>), dim3(cdiv(E, 256), G), dim3(512), 0, stream, e, lde, perm,
+                     (const uint4*)Wq, ncb / G, Pi, dsti, Pj, srci, (long)W2, (float*)nullptr, 0l, E, wA, bA, H, Hd / 128,
+                     a_out, CGAT_ACT_NONE, (float*)nullptr);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
@@ -1135,22 +1161,27 @@ int edge_logits_launch(const float* e, long lde, const int* perm, const float* W
 int edge_msg_wsum_launch(const float* e, long lde, const int* perm, const float* Wq, int W2, const float* Pi,
                          const int* dsti, const float* Pj, const int* srci, int N, int E, int H, int Hd, const float* alpha,
                          const int* rowptr, float* S, int z_bf16, hipStream_t stream) {
-  const int HHd = H * Hd;
-  CGAT_CHECK_ARG(W2 == 2 * HHd && Hd % 128 == 0 && HHd <= 1024 && (lde % 4) == 0 && perm && N > 0 &&
+  const int HHd = H * Hd, ncb = HHd / 128;
+  CGAT_CHECK_ARG(W2 == 2 * HHd && Hd % 128 == 0 && HHd <= 2048 && H <= 8 && (lde % 4) == 0 && perm && N > 0 &&
                  ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)S)) & 15) == 0,
-                 "edge_msg_wsum: needs Hd %% 128 == 0, H * Hd <= 1024 and 16-byte aligned rows");
+                 "edge_msg_wsum: needs Hd %% 128 == 0, H * Hd <= 2048, H <= 8 and 16-byte aligned rows");
   if (E <= 0) return CGAT_OK;
   // rows per workgroup: a range that starts and ends at segment boundaries is at most R + (longest segment - 1) rows, so
   // 256 minus the mean in-degree (rounded up to 16) keeps ordinary ranges in one 256-row sub-tile
   const long deg = cdiv(E, N);
   const int R = (int)(deg >= 128 ? 128 : 256 - 16 * cdiv(deg, 16));
-  const uint4* Wm = reinterpret_cast<const uint4*>(Wq) + (long)(HHd / 128) * 6144;   // the message column blocks' image
+  // column groups: to fill the chip at few rows, and at least as many as keep the carry of a long segment's Glong row
+  // groups within WSUM_CARRY floats (the kernel's ncb = ncb / G)
+  const int Glong = 1024 / (HHd / 4 < 256 ? HHd / 4 : 256);
+  int G = infer_few_rows(E) ? z_groups(cdiv(E, R), ncb) : 1;
+  while (ncb % G != 0 || (long)Glong * (ncb / G) * 128 > WSUM_CARRY) ++G;
+  const uint4* Wm = reinterpret_cast<const uint4*>(Wq) + (long)ncb * 6144;   // the message column blocks' image
   CGAT_PROF("edge_msg_wsum", stream);
   if (z_bf16)
-    hipLaunchKernelGGL(edge_msg_wsum_kernel<true>, dim3(cdiv(E, R)), dim3(512), 0, stream, e, lde, perm, Wm, HHd / 128,
+    hipLaunchKernelGGL(edge_msg_wsum_kernel<true>, dim3(cdiv(E, R), G), dim3(512), 0, stream, e, lde, perm, Wm, ncb / G,
                        Pi + HHd, dsti, Pj + HHd, srci, (long)W2, H, Hd, alpha, rowptr, N, R, S);
   else
-    hipLaunchKernelGGL(edge_msg_wsum_kernel<false>, dim3(cdiv(E, R)), dim3(512), 0, stream, e, lde, perm, Wm, HHd / 128,
+    hipLaunchKernelGGL(edge_msg_wsum_kernel<false>, dim3(cdiv(E, R), G), dim3(512), 0, stream, e, lde, perm, Wm, ncb / G,
                        Pi + HHd, dsti, Pj + HHd, srci, (long)W2, H, Hd, alpha, rowptr, N, R, S);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;

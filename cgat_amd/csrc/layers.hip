@@ -711,7 +711,9 @@ static int stack_in_weights(Ctx& c, const cgat_attn_params* p, const AttnDims& d
   return CGAT_OK;
 }
 
-// The forward without grad (infer): at the shapes edge_infer_fused takes (edgez.hip) the logits launch and the fused
+// The forward without grad (infer): at the shapes edge_infer_fused takes (edgez.hip: the 24-bit modes at width 128, up to
+// 2048 columns per half and 8 heads -- the harness' H = 5 -- at any number of edges, its few-row batches included) the
+// logits launch and the fused
 // message + weighted-sum launch replace the per-edge launch and seg_wsum, and alpha / S / ssum live in the workspace --
 // nothing of size E x H x Hd is formed; everywhere else the saved buffer of the training forward is carved out of the
 // workspace and the same launches run.  Either way the results are bit-identical to the training forward's.

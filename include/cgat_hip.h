@@ -167,8 +167,8 @@ int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params*
 /* The same forward without grad (replaces CGAT/CGAT.py:307-335 where it runs under torch.no_grad(): predictions,
  * graph embeddings): aggr as cgat_nodes_attention_forward computes it, bit-identical, with nothing saved for backward.
  * Where cgat_nodes_attention_infer_fused says 1 -- a host-only predicate of shapes, arithmetic mode and edge storage:
- * the 24-bit split modes (f16x3c, bf16x6), C = Ce = 128, Hd a multiple of 128, H*Hd <= 1024, >= 128 tiles of 256 edges,
- * E*H % 4 == 0 -- the per-edge
+ * the 24-bit split modes (f16x3c, bf16x6), C = Ce = 128, Hd a multiple of 128, H*Hd <= 2048, H <= 8, E*H % 4 == 0,
+ * N*8*H*Hd < 2^32, any number of edges -- the per-edge
  * work of CGAT.py:319-329 (MH_A's logits, softmax, MH_M's first layer weighted by alpha and summed per destination) runs
  * as two launches that write no per-edge activation: the workspace holds the node projections, logits, alpha, the
  * per-node sums and weight images, and does not grow with E*H*Hd.  The call then refuses (CGAT_ERR_ARG) inputs those

@@ -1,9 +1,11 @@
 """The forward without grad of the scalar-attention node layer against its opt-out (the training forward under no_grad),
 alternated in one process: layer forward ms, CGAT_PROF tag times and the peak allocation of one call, at BASELINE
 configs[1] (1 000 crystals, E = 240 000) and at the 1M-edge batch (4 167 crystals, E = 1 000 080), plus the
-CGAtNet(200, 128, 4, msg_heads=3) eval forward on the 1M-edge batch.  Prints one JSON line.
+CGAtNet(200, 128, 4, msg_heads=3) eval forward on the 1M-edge batch; and the layer of the harness' scalar-attention
+network (msg_heads = 5, 24 neighbours) at 64 crystals (E = 30 720), 1 000 crystals (E = 480 000) and the 1M-edge batch
+at 24 neighbours (2 084 crystals, E = 1 000 320).  Prints one JSON line.
 
-    python tools/infer_bench.py [--reps 10]
+    python tools/infer_bench.py [--reps 10] [--h5-only]
 """
 import argparse
 import json
@@ -55,19 +57,19 @@ def _peak(fn):
     return torch.cuda.max_memory_allocated() - base
 
 
-def layer_case(graphs, reps):
+def layer_case(graphs, reps, H=3, K=12):
     import cgat_amd as P
     dev = "cuda:0"
-    b, _ = P.synthetic_batch(graphs, 20, 12, seed=0)
+    b, _ = P.synthetic_batch(graphs, 20, K, seed=0)
     g = torch.Generator().manual_seed(1)
     N, E = b.num_nodes, b.edge_index.shape[1]
     x, x0 = torch.randn(N, 128, generator=g).to(dev), torch.randn(N, 128, generator=g).to(dev)
     e = torch.randn(E, 128, generator=g).to(dev)
     ei = b.edge_index.to(dev)
     torch.manual_seed(1)
-    layer = P.GATConvNodes(128, 128, 128, 3, concat=True).to(dev)
+    layer = P.GATConvNodes(128, 128, 128, H, concat=True).to(dev)
     fn = lambda: layer(x, ei, e, x0)
-    res = {"crystals": graphs, "N": N, "E": E}
+    res = {"crystals": graphs, "N": N, "E": E, "H": H, "K": K}
     with torch.no_grad():
         for on in (True, False):             # warm-up of both routes (plans, workspaces)
             P.set_fused_inference(on)
@@ -119,6 +121,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only-profile", action="store_true", help="a few inference-route layer forwards (for rocprofv3)")
+    ap.add_argument("--h5-only", action="store_true", help="only the layer of the harness' scalar network (H = 5, K = 24)")
     args = ap.parse_args()
     import cgat_amd as P
     if args.only_profile:
@@ -135,9 +138,12 @@ def main():
                 layer(x, ei, e, x0)
         torch.cuda.synchronize()
         return
-    out = {"tool": "infer_bench", "mode": P.get_bilinear_mode(), "device": torch.cuda.get_device_name(0),
-           "baseline_configs1": layer_case(1000, args.reps), "batch_1m": layer_case(4167, args.reps),
-           "net_1m": net_case(4167, max(3, args.reps // 2))}
+    out = {"tool": "infer_bench", "mode": P.get_bilinear_mode(), "device": torch.cuda.get_device_name(0)}
+    if not args.h5_only:
+        out.update({"baseline_configs1": layer_case(1000, args.reps), "batch_1m": layer_case(4167, args.reps),
+                    "net_1m": net_case(4167, max(3, args.reps // 2))})
+    out.update({"h5_k24_64": layer_case(64, args.reps, H=5, K=24), "h5_k24_1000": layer_case(1000, args.reps, H=5, K=24),
+                "h5_k24_1m": layer_case(2084, args.reps, H=5, K=24)})
     print(json.dumps(out))
 
 
