@@ -29,7 +29,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // output columns as [r = c % 32][cb = c / 32], so that lane r fetches the B operands of its four
 // accumulator blocks with ONE ds_read_b128.
 // grid = asplit * tiles: workgroup (s, tile) covers a in [s*NA/asplit, (s+1)*NA/asplit) and writes
-// a partial slab when asplit > 1 (summed in fixed order by slab_sum_rows_kernel).
+// a partial slab when asplit > 1 (summed in fixed order by sum_slabs_batch_launch, rowops.hip).
 // JS = j-steps per LDS chunk (a chunk is 2*JS rows of T = JS KB), FLUSH = number of consecutive
 // `a` whose products share one partial accumulator (two-level summation, see below).
 template <int JS, int FLUSH>
@@ -1267,8 +1267,21 @@ __global__ __launch_bounds__(256) void dual_finish_small_kernel(const float* __r
 }
 
 // sgn(a) T[a] (sgn = (-1)^a if alternate, else 1) split into three bf16 planes in the ring kernels' fragment order
-// (layout in the header above); element (a, b, c) of the [NA,128,128] operand is src[a*sa + b*sb + c*sc].
-// F16: two fp16 planes of 2^k sgn(a) T[a], 2^k from tmax[0] = max |T| (pow2_scale), same order with 2 planes per k-step
+// (plane_image_put, mfma_bf16.h); element (a, b, c) of the [NA,128,128] operand is src[a*sa + b*sb + c*sc].
+// NP = 2: two fp16 planes of st sgn(a) T[a], st = 2^k from max |T| (pow2_scale); NP = 3: st = 1.  Item i < NA * 16384.
+template <int NP>
+__device__ __forceinline__ void prepare_T_item(const float* __restrict__ src, void* __restrict__ dst, long i, long sa,
+                                               long sb, long sc, int alternate, float st) {
+  // thread order follows the fastest source stride so that reads coalesce
+  int a = (int)(i >> 14), b, c;
+  if (sc == 1) { b = (int)((i >> 7) & 127); c = (int)(i & 127); }
+  else { c = (int)((i >> 7) & 127); b = (int)(i & 127); }
+  float v = src[a * sa + b * sb + c * sc];
+  if (alternate && (a & 1)) v = -v;
+  if constexpr (NP == 2) v *= st;
+  plane_image_put<NP>(dst, a, b, c, v);
+}
+// F16: the two fp16 planes, 2^k from tmax[0] = max |T|
 // blockIdx.y = head of a multi-head layer: source + head * s_head, image + head * image_elems (0, 0: one operand)
 template <bool F16>
 __global__ void prepare_T_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, int NA, long sa, long sb,
@@ -1276,34 +1289,10 @@ __global__ void prepare_T_bf16_kernel(const float* __restrict__ src, __bf16* __r
                                       long image_elems = 0) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)NA * 128 * 128) return;
-  src += (long)blockIdx.y * s_head;
-  dst += (long)blockIdx.y * image_elems;
-  // thread order follows the fastest source stride so that reads coalesce
-  int a = (int)(i >> 14), b, c;
-  if (sc == 1) { b = (int)((i >> 7) & 127); c = (int)(i & 127); }
-  else { c = (int)((i >> 7) & 127); b = (int)(i & 127); }
-  float v = src[a * sa + b * sb + c * sc];
-  if (alternate && (a & 1)) v = -v;
-  const int half = c >> 6, cb = (c & 63) >> 4, i16 = c & 15;
-  const int kh = b >> 6, s2 = (b >> 5) & 1, kg = (b & 31) >> 3, j = b & 7;
-  constexpr int NP = F16 ? 2 : 3;
-  const long blk = ((((long)a * 2 + half) * 2 + kh) * 2 + s2) * NP;  // planes of one k-step, each [cb][kg][i][j]
-  const long in = (((long)cb * 4 + kg) * 16 + i16) * 8 + j;
-  if constexpr (F16) {
-    float st, it;
-    pow2_scale(tmax[0], st, it);
-    v *= st;
-    const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
-    _Float16* d16 = reinterpret_cast<_Float16*>(dst);
-    d16[(blk + 0) * 2048 + in] = h;
-    d16[(blk + 1) * 2048 + in] = l;
-  } else {
-    __bf16 x1, x2, x3;
-    split3_bf16(v, x1, x2, x3);
-    dst[(blk + 0) * 2048 + in] = x1;
-    dst[(blk + 1) * 2048 + in] = x2;
-    dst[(blk + 2) * 2048 + in] = x3;
-  }
+  float st = 1.f, it;
+  if constexpr (F16) pow2_scale(tmax[0], st, it);
+  prepare_T_item<F16 ? 2 : 3>(src + (long)blockIdx.y * s_head, dst + (long)blockIdx.y * image_elems, i, sa, sb, sc,
+                              alternate, st);
 }
 
 // The same three-plane image (NA = 1, no sign alternation) for SEVERAL 128 x 128 weights in one launch: the operands of the
@@ -1312,22 +1301,7 @@ __global__ void prepare_T_bf16_kernel(const float* __restrict__ src, __bf16* __r
 // Element (k, o) of item i is src[i][o * sc[i] + k * sb[i]]; image i at dst + i * 24576 floats.
 __global__ void prepare_T_bf16_batch_kernel(WPrepBatch b, __bf16* __restrict__ dst) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;            // 16384 elements per item
-  const float* src = b.src[blockIdx.y];
-  const long sb = b.sb[blockIdx.y], sc = b.sc[blockIdx.y];
-  int bb, c;
-  if (sc == 1) { bb = (i >> 7) & 127; c = i & 127; }              // thread order follows the fastest source stride
-  else { c = (i >> 7) & 127; bb = i & 127; }
-  const float v = src[(long)c * sc + (long)bb * sb];
-  const int half = c >> 6, cb = (c & 63) >> 4, i16 = c & 15;
-  const int kh = bb >> 6, s2 = (bb >> 5) & 1, kg = (bb & 31) >> 3, j = bb & 7;
-  const long blk = ((((long)half) * 2 + kh) * 2 + s2) * 3;
-  const long in = (((long)cb * 4 + kg) * 16 + i16) * 8 + j;
-  __bf16 x1, x2, x3;
-  split3_bf16(v, x1, x2, x3);
-  __bf16* d = dst + (size_t)blockIdx.y * 49152;                   // 24576 floats = 49152 bf16
-  d[(blk + 0) * 2048 + in] = x1;
-  d[(blk + 1) * 2048 + in] = x2;
-  d[(blk + 2) * 2048 + in] = x3;
+  prepare_T_item<3>(b.src[blockIdx.y], dst + (size_t)blockIdx.y * 49152, i, 0, b.sb[blockIdx.y], b.sc[blockIdx.y], 0, 1.f);
 }
 int prepare_T_bf16_batch_launch(const WPrepBatch& b, float* dst, hipStream_t stream) {
   if (b.n <= 0) return CGAT_OK;
@@ -1385,19 +1359,14 @@ __global__ void prepare_T_f16c_kernel(const float* __restrict__ src, uint4* __re
   if (i >= (long)NA * 512) return;
   prepare_T_f16c_item(src, dst, i, sa, sb, sc, alternate, tmax[per_a ? (int)(i >> 9) : 0]);   // per_a: one scale per block a
 }
-// Weight operands of the edge / dense kernels in the fp16 form: one workgroup per 128 x 128 block `a` keeps the block
-// in registers, takes its largest magnitude, and writes the two planes of 2^k(a) W[a] in the bf16 kernel's order with
-// two planes per k-step; max |W[a]| goes to wmax[a] behind the planes (the consumer undoes 2^k(a) per column block).
-// No atomics, no second pass, one launch.
-// (blockIdx.y = head of a batch of weights: per-head source and image offsets, see prepare_W_f16_heads_launch)
-__global__ __launch_bounds__(256) void prepare_W_f16_kernel(const float* __restrict__ src, _Float16* __restrict__ dst,
-                                                            long sa, long sb, long sc, float* __restrict__ wmax,
-                                                            long s_head, long image_floats) {
+// Weight operands of the edge / dense kernels in the fp16 form: one workgroup per 128 x 128 block keeps the block in
+// registers, takes its largest magnitude, and writes the two planes of 2^k W in the bf16 kernel's order with two planes
+// per k-step; max |W| goes to *wmax (the consumer undoes 2^k per column block).  No atomics, no second pass, one launch.
+// Element (k = b, c) of the block is src[b * sb + c * sc]; its planes are block 0 of the image at dst.
+__device__ __forceinline__ void prepare_W_f16_block(const float* __restrict__ src, long sb, long sc, void* __restrict__ dst,
+                                                    float* __restrict__ wmax) {
   __shared__ float wm[4];
-  const int a = blockIdx.x, tid = threadIdx.x;
-  src += (long)blockIdx.y * s_head;
-  dst += (long)blockIdx.y * image_floats * 2;
-  wmax += (long)blockIdx.y * image_floats;
+  const int tid = threadIdx.x;
   float v[64];
   float m = 0.f;
 #pragma unroll
@@ -1406,7 +1375,7 @@ __global__ __launch_bounds__(256) void prepare_W_f16_kernel(const float* __restr
     int b, c;
     if (sc == 1) { b = i >> 7; c = i & 127; }
     else { c = i >> 7; b = i & 127; }
-    v[r] = src[a * sa + b * sb + c * sc];
+    v[r] = src[b * sb + c * sc];
     m = fmaxf(m, fabsf(v[r]));
   }
 #pragma unroll
@@ -1414,7 +1383,7 @@ __global__ __launch_bounds__(256) void prepare_W_f16_kernel(const float* __restr
   if ((tid & 63) == 0) wm[tid >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-  if (tid == 0) wmax[a] = m;
+  if (tid == 0) *wmax = m;
   float st, it;
   pow2_scale(m, st, it);
 #pragma unroll
@@ -1423,59 +1392,24 @@ __global__ __launch_bounds__(256) void prepare_W_f16_kernel(const float* __restr
     int b, c;
     if (sc == 1) { b = i >> 7; c = i & 127; }
     else { c = i >> 7; b = i & 127; }
-    const float x = v[r] * st;
-    const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
-    const int half = c >> 6, cb = (c & 63) >> 4, i16 = c & 15;
-    const int kh = b >> 6, s2 = (b >> 5) & 1, kg = (b & 31) >> 3, j = b & 7;
-    const long blk = ((((long)a * 2 + half) * 2 + kh) * 2 + s2) * 2;
-    const long in = (((long)cb * 4 + kg) * 16 + i16) * 8 + j;
-    dst[(blk + 0) * 2048 + in] = h;
-    dst[(blk + 1) * 2048 + in] = l;
+    plane_image_put<2>(dst, 0, b, c, v[r] * st);
   }
+}
+// block a = blockIdx.x of [NA,128,128] (element (a, b, c) at src[a*sa + b*sb + c*sc]), max |W[a]| to wmax[a] behind the
+// planes (blockIdx.y = head of a batch of weights: per-head source and image offsets, see prepare_W_f16_heads_launch)
+__global__ __launch_bounds__(256) void prepare_W_f16_kernel(const float* __restrict__ src, _Float16* __restrict__ dst,
+                                                            long sa, long sb, long sc, float* __restrict__ wmax,
+                                                            long s_head, long image_floats) {
+  const int a = blockIdx.x;
+  prepare_W_f16_block(src + (long)blockIdx.y * s_head + a * sa, sb, sc,
+                      dst + (long)blockIdx.y * image_floats * 2 + (long)a * 32768,
+                      wmax + (long)blockIdx.y * image_floats + a);
 }
 // Many 128 x 128 weights in ONE launch (a dense layer's own prepare is a single workgroup: 11 us of latency per layer,
 // 48 layers per hypernetwork step): item i = (src, sb, sc) goes to dst + i * WPREP_IMAGE_FLOATS, wmax behind its planes.
 __global__ __launch_bounds__(256) void prepare_W_f16_batch_kernel(WPrepBatch b, float* __restrict__ dst) {
-  __shared__ float wm[4];
-  const int it = blockIdx.x, tid = threadIdx.x;
-  const float* src = b.src[it];
-  const long sb = b.sb[it], sc = b.sc[it];
-  float* img = dst + (size_t)it * WPREP_IMAGE_FLOATS;
-  float v[64];
-  float m = 0.f;
-#pragma unroll
-  for (int r = 0; r < 64; ++r) {
-    const int i = r * 256 + tid;
-    int bb, c;
-    if (sc == 1) { bb = i >> 7; c = i & 127; }
-    else { c = i >> 7; bb = i & 127; }
-    v[r] = src[bb * sb + c * sc];
-    m = fmaxf(m, fabsf(v[r]));
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((tid & 63) == 0) wm[tid >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-  if (tid == 0) img[16384] = m;
-  float st, iv;
-  pow2_scale(m, st, iv);
-  _Float16* d16 = reinterpret_cast<_Float16*>(img);
-#pragma unroll
-  for (int r = 0; r < 64; ++r) {
-    const int i = r * 256 + tid;
-    int bb, c;
-    if (sc == 1) { bb = i >> 7; c = i & 127; }
-    else { c = i >> 7; bb = i & 127; }
-    const float x = v[r] * st;
-    const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
-    const int half = c >> 6, cb = (c & 63) >> 4, i16 = c & 15;
-    const int kh = bb >> 6, s2 = (bb >> 5) & 1, kg = (bb & 31) >> 3, j = bb & 7;
-    const long blk = (((long)half * 2 + kh) * 2 + s2) * 2;
-    const long in = (((long)cb * 4 + kg) * 16 + i16) * 8 + j;
-    d16[(blk + 0) * 2048 + in] = h;
-    d16[(blk + 1) * 2048 + in] = l;
-  }
+  float* img = dst + (size_t)blockIdx.x * WPREP_IMAGE_FLOATS;
+  prepare_W_f16_block(b.src[blockIdx.x], b.sb[blockIdx.x], b.sc[blockIdx.x], img, img + 16384);
 }
 int prepare_W_f16_batch_launch(const WPrepBatch& b, float* dst, hipStream_t stream) {
   if (b.n <= 0) return CGAT_OK;
@@ -1499,17 +1433,12 @@ int prepare_W_f16_heads_launch(const float* src, void* dst, int NA, long sa, lon
   return CGAT_OK;
 }
 
-// out[0] = max |src[i]| (out[0] zeroed before; non-negative floats order like their bit patterns, and a maximum does
-// not depend on the order it is taken in: deterministic)
-__global__ void absmax_kernel(const float* __restrict__ src, long n, float* __restrict__ out) {
-  float m = 0.f;
-  const long n4 = n >> 2;
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const float4 v = s4[i];
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = fmaxf(m, fabsf(src[(n4 << 2) + threadIdx.x]));
+// out[0] = max |.| over a [rows, 128] view with row stride ld (absmax_rows128) and the `tail` < 128 floats behind its
+// last row (out[0] zeroed before; non-negative floats order like their bit patterns, and a maximum does not depend on
+// the order it is taken in: deterministic)
+__global__ void absmax_kernel(const float* __restrict__ src, long ld, long rows, int tail, float* __restrict__ out) {
+  float m = absmax_rows128(src, ld, rows, blockIdx.x, gridDim.x);
+  if (blockIdx.x == 0 && (int)threadIdx.x < tail) m = fmaxf(m, fabsf(src[rows * ld + threadIdx.x]));
   block_absmax_commit(m, out);
 }
 int absmax_launch(const float* src, long n, float* out, hipStream_t stream) {
@@ -1517,7 +1446,7 @@ int absmax_launch(const float* src, long n, float* out, hipStream_t stream) {
   if (n <= 0) return CGAT_OK;
   CGAT_CHECK_ARG((((uintptr_t)src) & 15) == 0, "absmax: source must be 16-byte aligned");
   const int blocks = (int)(cdiv(n, 4 * 256) < 512 ? cdiv(n, 4 * 256) : 512);
-  hipLaunchKernelGGL(absmax_kernel, dim3(blocks), dim3(256), 0, stream, src, n, out);
+  hipLaunchKernelGGL(absmax_kernel, dim3(blocks), dim3(256), 0, stream, src, 128l, n >> 7, (int)(n & 127), out);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
@@ -1552,12 +1481,10 @@ __global__ void prepare_T_bf16_rows_kernel(const float* __restrict__ rows, long 
     split3_x8(vv, x1, x2, x3);
   }
   constexpr int NP = F16 ? 2 : 3;
-  const int half = c >> 6, cb = (c & 63) >> 4, i16 = c & 15;
-  const long blk = ((a * 2 + half) * 4 + s) * NP;         // planes of one k-step, each [cb][kg][i] x 16 bytes
-  const long in = ((long)cb * 4 + kg) * 16 + i16;
-  dst[(blk + 0) * 256 + in] = __builtin_bit_cast(uint4, x1);
-  dst[(blk + 1) * 256 + in] = __builtin_bit_cast(uint4, x2);
-  if constexpr (!F16) dst[(blk + 2) * 256 + in] = __builtin_bit_cast(uint4, x3);
+  const long in = plane_image_offset<NP>(a, 32 * s + 8 * kg, c) / 8;   // j = 0: whole 16-byte pieces, 256 per plane
+  dst[in] = __builtin_bit_cast(uint4, x1);
+  dst[in + 256] = __builtin_bit_cast(uint4, x2);
+  if constexpr (!F16) dst[in + 512] = __builtin_bit_cast(uint4, x3);
 }
 
 // emax != null: the fp16 form (two planes of 2^k rows, 2^k from emax[0])
@@ -1635,14 +1562,7 @@ int prepare_T_f16c_launch(const float* src, void* dst, int NA, long sa, long sb,
 // stage 1 writes one partial maximum per workgroup, every workgroup of stage 2 folds the 64 partials of its tensor.
 #define TPREP_PARTS 64
 __global__ void absmax_partial_batch_kernel(TPrepBatch b, long total, float* __restrict__ part) {
-  const float* src = b.src[blockIdx.y];
-  float m = 0.f;
-  const long n4 = total >> 2;                        // total = NA * 16384: a multiple of 4
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const float4 v = s4[i];
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-  }
+  float m = absmax_rows128(b.src[blockIdx.y], 128, total >> 7, blockIdx.x, gridDim.x);   // total = NA * 16384
   __shared__ float wm[4];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -1650,32 +1570,19 @@ __global__ void absmax_partial_batch_kernel(TPrepBatch b, long total, float* __r
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.y * TPREP_PARTS + blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
 }
+// the fp16 image (prepare_T_bf16_kernel<true>) of several tensors: blockIdx.y = tensor, its maximum folded from the partials
 __global__ void prepare_T_f16_batch_kernel(TPrepBatch b, int NA, long sa, long sb, long sc, int alternate,
                                            const float* __restrict__ part) {
-  const float* src = b.src[blockIdx.y];
-  _Float16* d16 = reinterpret_cast<_Float16*>(b.dst[blockIdx.y]);
   float tm = part[blockIdx.y * TPREP_PARTS + (threadIdx.x & 63)];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) tm = fmaxf(tm, __shfl_xor(tm, o, 64));
   const long total = (long)NA * 128 * 128;
   if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<float*>(b.dst[blockIdx.y])[total] = tm;   // behind the planes
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
-  int a = (int)(i >> 14), bb, c;
-  if (sc == 1) { bb = (int)((i >> 7) & 127); c = (int)(i & 127); }
-  else { c = (int)((i >> 7) & 127); bb = (int)(i & 127); }
-  float v = src[a * sa + bb * sb + c * sc];
-  if (alternate && (a & 1)) v = -v;
-  const int half = c >> 6, cb = (c & 63) >> 4, i16 = c & 15;
-  const int kh = bb >> 6, s2 = (bb >> 5) & 1, kg = (bb & 31) >> 3, j = bb & 7;
-  const long blk = ((((long)a * 2 + half) * 2 + kh) * 2 + s2) * 2;   // two planes per k-step, each [cb][kg][i][j]
-  const long in = (((long)cb * 4 + kg) * 16 + i16) * 8 + j;
   float st, it;
   pow2_scale(tm, st, it);
-  v *= st;
-  const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
-  d16[(blk + 0) * 2048 + in] = h;
-  d16[(blk + 1) * 2048 + in] = l;
+  prepare_T_item<2>(b.src[blockIdx.y], b.dst[blockIdx.y], i, sa, sb, sc, alternate, st);
 }
 // the f16x3c image (prepare_T_f16c_kernel) of several tensors: blockIdx.y = tensor, its maximum folded from the partials
 __global__ void prepare_T_f16c_batch_kernel(TPrepBatch b, int NA, long sa, long sb, long sc, int alternate,
@@ -1720,23 +1627,7 @@ int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, 
   return CGAT_OK;
 }
 
-// out[n, c] = sum_s slab[s][n][c]   (fixed order)
-__global__ void slab_sum_rows_kernel(const float* __restrict__ slab, int splits, long slab_stride, int nrows,
-                                     float* __restrict__ out, long ldo) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)nrows * 128) return;
-  float s = 0.f;
-  int z = 0;
-  for (; z + 4 <= splits; z += 4) {                // four independent loads per round trip, added in slab order
-    const float v0 = slab[(long)z * slab_stride + i], v1 = slab[(long)(z + 1) * slab_stride + i];
-    const float v2 = slab[(long)(z + 2) * slab_stride + i], v3 = slab[(long)(z + 3) * slab_stride + i];
-    s += v0; s += v1; s += v2; s += v3;
-  }
-  for (; z < splits; ++z) s += slab[(long)z * slab_stride + i];
-  out[(i >> 7) * ldo + (i & 127)] = s;
-}
-
-// The same sum with the hypernetwork's LayerNorm(no affine) + tanh behind it (reference Hypernetworksmp.py:205-209): one
+// out[n, c] = sum_s slab[s][n][c] in fixed order, with the hypernetwork's LayerNorm(no affine) + tanh behind it (reference Hypernetworksmp.py:205-209): one
 // wave per row sums the slabs into u (kept: backward needs the pre-norm values) and normalises what it holds in
 // registers -- the arithmetic of layernorm_tanh_fwd_kernel (rowops.hip) on the same values, one launch and one read of
 // u less per predicted layer.
@@ -1970,9 +1861,7 @@ int bilinear_rows_launch(const float* p, long ldp, const float* q, long ldq, con
       CGAT_LAUNCH_CHECK();
       ln_done = true;
     } else if (sp > 1) {
-      hipLaunchKernelGGL(slab_sum_rows_kernel, dim3(cdiv((long)nrows * 128, 256)), dim3(256), 0, stream,
-                         (const float*)ws, sp, stride, nrows, out, ldo);
-      CGAT_LAUNCH_CHECK();
+      CGAT_TRY(sum_slabs_batch_launch((const float*)ws, sp, stride, (long)nrows * 128, 1, 0, &out, ldo, stream));
     }
   } else {
     // Widths other than 128: out = init + (p (x) q) T, the row-wise outer product [nrows, NA * NB] formed in the operand
@@ -2131,14 +2020,6 @@ __global__ __launch_bounds__(256, 2) void bilinear_wgrad128_kernel(const float* 
     }
 }
 
-__global__ void slab_sum_kernel(const float* __restrict__ slab, int splits, long n, float* __restrict__ out) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  for (int z = 0; z < splits; ++z) s += slab[(long)z * n + i];
-  out[i] = s;
-}
-
 // ---------------------------------------------------------------------------------------
 // Split-bf16 weight gradient:  out[a,b,c] = sum_n p[n,a] q[n,b] r[n,c]  with the contraction
 // index n on the MFMA k axis.  Pre-passes (once per call, ~0.1 ms at N = 83k):
@@ -2197,21 +2078,12 @@ __global__ void split_rows_bf16_kernel(const float* __restrict__ r, long ldr, in
   }
 }
 
-// out[0] = max |t[n, c]| over a [rows, 128] view with row stride ld (16-byte aligned rows; out zeroed before)
-__global__ void absmax_rows128_kernel(const float* __restrict__ t, long ld, int rows, float* __restrict__ out) {
-  const int c4 = threadIdx.x & 31, r0 = threadIdx.x >> 5;      // 8 rows of 32 float4 per workgroup pass
-  float m = 0.f;
-  for (long n = (long)blockIdx.x * 8 + r0; n < rows; n += (long)gridDim.x * 8) {
-    const float4 v = *reinterpret_cast<const float4*>(t + n * ld + 4 * c4);
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-  }
-  block_absmax_commit(m, out);
-}
 // max |t[n, 0..127]| over rows of stride ld folded into out[0] (NOT zeroed here)
 int absmax_rows128_launch(const float* t, long ld, int rows, float* out, hipStream_t stream) {
   if (rows <= 0) return CGAT_OK;
   CGAT_CHECK_ARG((ld % 4) == 0 && (((uintptr_t)t) & 15) == 0, "absmax_rows128: rows must be 16-byte aligned");
-  hipLaunchKernelGGL(absmax_rows128_kernel, dim3(rows < 8192 ? (rows + 7) / 8 : 1024), dim3(256), 0, stream, t, ld, rows, out);
+  hipLaunchKernelGGL(absmax_kernel, dim3(rows < 8192 ? (rows + 7) / 8 : 1024), dim3(256), 0, stream, t, ld, (long)rows, 0,
+                     out);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
@@ -2395,8 +2267,8 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_bf16_kernel(const fl
 // ---------------------------------------------------------------------------------------
 // (WgradBatchDesc / WgradPrepDesc: wgrad_batch.h)
 
-// mx[4 * layer + which] = max |tensor|, which 0 / 1 / 2 = p / q / r  (mx zeroed before)
-__global__ void absmax_rows_batch_kernel(WgradPrepDesc d, long ldp, long ldq, long ldr, int rows, int NA,
+// mx[4 * (l0 + layer) + which] = max |tensor|, which 0 / 1 / 2 = p / q / r  (mx zeroed before; also wgradc.hip)
+__global__ void absmax_rows_batch_kernel(WgradPrepDesc d, int l0, long ldp, long ldq, long ldr, int rows, int NA,
                                          float* __restrict__ mx) {
   const int layer = blockIdx.y / 3, which = blockIdx.y % 3;
   const float* t = which == 0 ? d.p[layer] : (which == 1 ? d.q[layer] : d.r[layer]);
@@ -2404,16 +2276,18 @@ __global__ void absmax_rows_batch_kernel(WgradPrepDesc d, long ldp, long ldq, lo
   const int cols = which == 0 ? NA : 128;
   float m = 0.f;
   if (cols == 128 && (ld & 3) == 0 && (((uintptr_t)t) & 15) == 0) {
-    const int c4 = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-    for (long n = (long)blockIdx.x * 8 + r0; n < rows; n += (long)gridDim.x * 8) {
-      const float4 v = *reinterpret_cast<const float4*>(t + n * ld + 4 * c4);
-      m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    }
+    m = absmax_rows128(t, ld, rows, blockIdx.x, gridDim.x);
   } else {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (long)rows * cols; i += (long)gridDim.x * blockDim.x)
       m = fmaxf(m, fabsf(t[(i / cols) * ld + (i % cols)]));
   }
-  block_absmax_commit(m, mx + 4 * layer + which);
+  block_absmax_commit(m, mx + 4 * (l0 + layer) + which);
+}
+int absmax_rows_batch_launch(const WgradPrepDesc& d, int l0, int n, long ldp, long ldq, long ldr, int rows, int NA,
+                             float* mx, int wgs, hipStream_t stream) {
+  hipLaunchKernelGGL(absmax_rows_batch_kernel, dim3(wgs, 3 * n), dim3(256), 0, stream, d, l0, ldp, ldq, ldr, rows, NA, mx);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
 }
 
 // z = 2 * layer + which: which 0 -> pT [128][rows_pad] = (p * 2^k * sign(n))^T, 2^k from max|p| max|q| (the products
@@ -2701,16 +2575,6 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16p_kernel(const fl
   }
 }
 
-// out[layer][i] = sum_z slab[layer][z][i]
-__global__ void slab_sum_batch_kernel(const float* __restrict__ slab, int splits, long n, WgradBatchDesc u) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* sl = slab + (long)blockIdx.y * splits * n;
-  float s = 0.f;
-  for (int z = 0; z < splits; ++z) s += sl[(long)z * n + i];
-  u.out[blockIdx.y][i] = s;
-}
-
 static int wgrad_splits(int nrows, int NA) {
   int s = cdiv(512, NA);                 // aim at >= 2 workgroups per CU
   int maxs = nrows / 256;                // at least 8 chunks of 32 rows per split
@@ -2804,8 +2668,7 @@ int bilinear_wgrad_batch_prep(int slot, int n_layers, const float* p, long ldp, 
   memset(&pd, 0, sizeof(pd));
   pd.p[0] = p; pd.q[0] = q; pd.r[0] = r;
   CGAT_TRY(fill_launch(mx, 0.f, 4, stream));
-  hipLaunchKernelGGL(absmax_rows_batch_kernel, dim3(256, 3), dim3(256), 0, stream, pd, ldp, ldq, ldr, nrows, NA, mx);
-  CGAT_LAUNCH_CHECK();
+  CGAT_TRY(absmax_rows_batch_launch(pd, 0, 1, ldp, ldq, ldr, nrows, NA, mx, 256, stream));
   hipLaunchKernelGGL(transpose_pad_batch_kernel, dim3(np / 32, 4, 2), dim3(256), 0, stream, pd, ldp, ldq, nrows, NA, np, rps,
                      pT, qT, sT, (const float*)mx);
   CGAT_LAUNCH_CHECK();
@@ -2861,9 +2724,7 @@ int bilinear_wgrad_batch_launch(int n_layers, const float* const* p, long ldp, c
   u.n_layers = n_layers; u.splits = splits; u.npairs = npairs; u.NA = NA; u.rows_pad = np; u.rows_per_split = rps;
   if (!prepared) {
     CGAT_TRY(fill_launch(mx, 0.f, 64, stream));
-    hipLaunchKernelGGL(absmax_rows_batch_kernel, dim3(256, 3 * n_layers), dim3(256), 0, stream, pd, ldp, ldq, ldr, nrows, NA,
-                       mx);
-    CGAT_LAUNCH_CHECK();
+    CGAT_TRY(absmax_rows_batch_launch(pd, 0, n_layers, ldp, ldq, ldr, nrows, NA, mx, 256, stream));
     hipLaunchKernelGGL(transpose_pad_batch_kernel, dim3(np / 32, 4, 2 * n_layers), dim3(256), 0, stream, pd, ldp, ldq, nrows,
                        NA, np, rps, pT, qT, u.sT, (const float*)mx);
     CGAT_LAUNCH_CHECK();
@@ -2881,9 +2742,7 @@ int bilinear_wgrad_batch_launch(int n_layers, const float* const* p, long ldp, c
   CGAT_LAUNCH_CHECK();
   if (splits > 1) {
     const long n = (long)NA * 128 * 128;
-    hipLaunchKernelGGL(slab_sum_batch_kernel, dim3(cdiv(n, 256), n_layers), dim3(256), 0, stream, (const float*)u.slab, splits,
-                       n, u);
-    CGAT_LAUNCH_CHECK();
+    CGAT_TRY(sum_slabs_batch_launch(u.slab, splits, n, n, n_layers, splits * n, u.out, 128, stream));
   }
   return CGAT_OK;
 }
@@ -2943,7 +2802,7 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
                        f16 ? mx + 1 : (float*)nullptr);
     CGAT_LAUNCH_CHECK();
     if (f16) {
-      hipLaunchKernelGGL(absmax_rows128_kernel, dim3(512), dim3(256), 0, stream, r, ldr, nrows, mx + 2);
+      hipLaunchKernelGGL(absmax_kernel, dim3(512), dim3(256), 0, stream, r, ldr, (long)nrows, 0, mx + 2);
       CGAT_LAUNCH_CHECK();
       hipLaunchKernelGGL(split_rows_bf16_kernel<true>, dim3(cdiv((long)np * 128, 256)), dim3(256), 0, stream, r, ldr, nrows, np, Rq, (const float*)mx);
     } else {
@@ -2968,8 +2827,7 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
     }
     CGAT_LAUNCH_CHECK();
     long n = (long)NA * NB * NC;
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, (const float*)slab, splits, n, out);
-    CGAT_LAUNCH_CHECK();
+    CGAT_TRY(sum_slabs_launch(slab, splits, n, out, n, stream));
     return CGAT_OK;
   }
   if (wgrad_fast(q, ldq, r, ldr, NB, NC)) {
@@ -2990,8 +2848,7 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
     }
     CGAT_LAUNCH_CHECK();
     long n = (long)NA * NB * NC;
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, (const float*)ws, splits, n, out);
-    CGAT_LAUNCH_CHECK();
+    CGAT_TRY(sum_slabs_launch((const float*)ws, splits, n, out, n, stream));
   } else {
     // widths other than 128: out [NA, NB * NC] = p^T (q (x) r) on the fp32 engine, rows split over workgroups when the
     // output has few tiles (33 ms -> 0.7 at 83 340 rows of width 64)

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
                                                          const uint4* __restrict__ Eq, float* __restrict__ slab,
                                                          int E, int ncb, int nsteps, int S,
                                                          const float* __restrict__ gmax, const float* __restrict__ emax,
-                                                         const EdgeRC rc, int xcd_order) {
+                                                         const EdgeRC rc) {
   // PASSES == 2: two fp16 planes, three passes; both operands are indexed by the reduction index (the edge slot), so
   // both scales are per tensor: gmax[0] = max |gZ| (from its producer), emax[0] = max |e| (the planes carry 2^k e)
   // PASSES == 1 (edge storage "bf16-mma"): one bf16 pass on the leading planes of both operands (see edge_ge_kernel)
@@ -325,17 +325,14 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
   int pair, split;
   {
     const int s8 = S >> 3, body = 8 * s8 * npair;
-    if (xcd_order && (int)blockIdx.x < body) {
+    if ((int)blockIdx.x < body) {
       const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
       pair = j % npair;
       split = xcd * s8 + j / npair;
-    } else if (xcd_order) {
+    } else {
       const int r = blockIdx.x - body;
       pair = r % npair;
       split = 8 * s8 + r / npair;
-    } else {
-      pair = blockIdx.x % npair;
-      split = blockIdx.x / npair;
     }
   }
   // ranges in units of two k-steps (the loop is unrolled by two without a tail); a k-step past nsteps holds slots >= E,
@@ -743,10 +740,6 @@ bool edge_gw_fast(int Ce, int W2, long ldg, long gzb, const void* gZ) {
   return mode_split() && Ce == 128 && W2 % 256 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
          (((uintptr_t)gZ) & 15) == 0;
 }
-static int gw_xcd_order() {   // CGAT_GW_XCD=0: plain workgroup order (A/B switch)
-  static const int v = [] { const char* e = getenv("CGAT_GW_XCD"); return (e && e[0] == '0') ? 0 : 1; }();
-  return v;
-}
 static int edge_gw_splits(int W2) {   // ranges x column-block pairs ~ one workgroup per CU
   const int npair = W2 / 256;
   if (npair <= 0) return 1;
@@ -779,7 +772,7 @@ int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde
     const EdgeRC none = {};
 #define GW_GO(P_, R_)                                                                                                  \
   hipLaunchKernelGGL((edge_gw_kernel<P_, R_>), dim3(S * (ncb / 2)), dim3(512), 0, stream, gZ, ldg, gzb,                \
-                     (const uint4*)planes, slab, E, ncb, nsteps, S, gmax, emax, R_ ? *rc : none, gw_xcd_order())
+                     (const uint4*)planes, slab, E, ncb, nsteps, S, gmax, emax, R_ ? *rc : none)
     const bool one = rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
     if (one) GW_GO(1, true);
     else if (rc) { if (f16) GW_GO(2, true); else if (!mode_bf16x3()) GW_GO(6, true); else GW_GO(3, true); }

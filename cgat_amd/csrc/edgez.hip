@@ -1002,23 +1002,14 @@ __global__ __launch_bounds__(256) void prepare_W2_f16_kernel(const float* __rest
 #pragma unroll
     for (int r = 0; r < 64; ++r) {
       const int i = r * 256 + tid, c = i >> 7, b = i & 127;
-      const float x = v[src][r] * st;
-      const _Float16 h = (_Float16)x, l = (_Float16)(x - (float)h);
-      const int half = c >> 6, cb = (c & 63) >> 4, i16 = c & 15;
-      const int kh = 2 * src + (b >> 6), s2 = (b >> 5) & 1, kg = (b & 31) >> 3, j = b & 7;
-      const long blk = ((((long)a * 2 + half) * 4 + kh) * 2 + s2) * 2;
-      const long in = (((long)cb * 4 + kg) * 16 + i16) * 8 + j;
-      dst[(blk + 0) * 2048 + in] = h;
-      dst[(blk + 1) * 2048 + in] = l;
+      plane_image_put<2, 256>(dst, a, 128 * src + b, c, v[src][r] * st);   // k = 128 src + b: W_e then W_j
     }
 }
 
 size_t edge_zx_wq_floats(int W2) { return (size_t)W2 * 256 + W2 / 128 + 64; }
 bool edge_zx_fast(int C, int Ce, int W2, int H, int Hd, long ld_add, long ldz, const void* e, const void* x,
                   const void* Pi, const void* Z, const void* wA) {
-  static int off = -1;
-  if (off < 0) { const char* ev = getenv("CGAT_NO_EDGE_ZX"); off = (ev && ev[0] == '1') ? 1 : 0; }
-  return !off && mode_f16() && C == 128 && Ce == 128 && W2 % 128 == 0 && Hd % 128 == 0 && H * Hd * 2 == W2 &&
+  return mode_f16() && C == 128 && Ce == 128 && W2 % 128 == 0 && Hd % 128 == 0 && H * Hd * 2 == W2 &&
          (ld_add % 4) == 0 && (ldz % 4) == 0 &&
          ((((uintptr_t)e) | ((uintptr_t)x) | ((uintptr_t)Pi) | ((uintptr_t)Z) | ((uintptr_t)wA)) & 15) == 0;
 }

@@ -569,9 +569,8 @@ int gemm_launch(GemmParams p, void* ws, size_t ws_bytes, hipStream_t stream) {
   const int inner = p.splits > 1 ? tiles_m * tiles_n : (swap ? tiles_m : tiles_n);
   const int outer = p.splits > 1 ? p.splits : (swap ? tiles_n : tiles_m);
   dim3 grid(outer >= 8 ? 8 * inner * cdiv(outer, 8) : outer * inner);
-  // split arithmetic modes: the six-pass bf16 form of the same product (gemmsplit.hip; CGAT_GEMM_SPLIT=0: this engine)
-  static const bool split_on = [] { const char* e = getenv("CGAT_GEMM_SPLIT"); return !(e && e[0] == '0'); }();
-  if (split_on && mode_split()) {
+  // split arithmetic modes: the six-pass bf16 form of the same product (gemmsplit.hip)
+  if (mode_split()) {
     CGAT_TRY(gemm_split_launch(p, grid.x, stream));
   } else {
     CGAT_PROF("gemm_f32", stream);

@@ -347,6 +347,11 @@ int mix_bwd_launch(const float* g, const float* a, const float* b, const float* 
 int scale_launch(const float* x, float alpha, float* out, long n, hipStream_t s);   // out = alpha * x
 int axpy_launch(float* y, const float* x, float alpha, long n, hipStream_t s);  // y += alpha*x
 int sum_slabs_launch(const float* slabs, int n, long stride, float* out, long count, hipStream_t s);   // out = 0.f + slab 0 + slab 1 + ...
+// the same for `items` slab sets item_stride apart, item t into out[t] (rows of 128 at row stride ldo)
+#define SLAB_SUM_MAX 8
+struct SlabSumOut { float* out[SLAB_SUM_MAX]; };
+int sum_slabs_batch_launch(const float* slabs, int n, long stride, long count, int items, long item_stride,
+                           float* const* out, long ldo, hipStream_t s);
 int copy2d_launch(const float* src, long lds, float* dst, long ldd, int rows, int cols, hipStream_t s);
 struct Copy2DJob { const float* src; long lds; float* dst; long ldd; int rows, cols; };
 struct Copy2DJobs { Copy2DJob job[4]; int n; };

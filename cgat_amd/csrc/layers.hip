@@ -33,16 +33,12 @@ struct Ctx {
   void tprep_add(const float* W, long so, long sk) {
     if (tprep.n < WPREP_MAX) { tprep.src[tprep.n] = W; tprep.sb[tprep.n] = sk; tprep.sc[tprep.n] = so; ++tprep.n; }
   }
-  static bool tprep_mode() {   // CGAT_NO_TPREP=1: prepare per product, as before round 5 (A/B switch)
-    static const bool off = [] { const char* e = getenv("CGAT_NO_TPREP"); return e && e[0] == '1'; }();
-    return !off && mode_24bit();
-  }
   int tprep_run() {
-    if (dry || !tprep_mode() || tprep.n == 0 || !tprep_images) { if (!tprep_mode()) tprep.n = 0; return CGAT_OK; }
+    if (dry || !mode_24bit() || tprep.n == 0 || !tprep_images) { if (!mode_24bit()) tprep.n = 0; return CGAT_OK; }
     return prepare_T_bf16_batch_launch(tprep, tprep_images, s);
   }
   const void* tprep_find(const float* W, long so, long sk) const {
-    if (dry || !tprep_mode() || !tprep_images) return nullptr;
+    if (dry || !mode_24bit() || !tprep_images) return nullptr;
     for (int i = 0; i < tprep.n; ++i)
       if (tprep.src[i] == W && tprep.sb[i] == sk && tprep.sc[i] == so) return tprep_images + (size_t)i * 24576;
     return nullptr;
@@ -649,11 +645,6 @@ static AttnDims attn_dims(const cgat_plan* plan, const cgat_attn_params* p) {
 struct AttnSaved {
   float *Z, *alpha, *S, *ssum;
 };
-static bool seg_bwd_split() {                      // CGAT_SEG_BWD_SPLIT=0: the one-kernel form (A/B switch)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("CGAT_SEG_BWD_SPLIT"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
 static AttnSaved attn_saved(float* saved, const AttnDims& d) {
   AttnSaved s;
   s.Z = saved;
@@ -1116,7 +1107,7 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
       CGAT_CHECK_ARG(rc_shape && have_scales, "nodes_attention_backward: the bf16 edge storage needs the vector form");
       hipLaunchKernelGGL((edge_seg_bwd_kernel<true, true>), dim3(chunks), dim3(256), shm, c.s, sv.Z, gZ, gzb, sv.alpha, gS, gs,
                          plan->dst_rowptr, p->A_out_w, d.N, d.H, d.Hd, tt, ga, Gi, partial, gzmax, mask, gimax);
-    } else if (vec && mask && d.Hd == 256 && seg_bwd_split()) {
+    } else if (vec && mask && d.Hd == 256) {
       // three small kernels (<= 64 VGPRs: they co-reside with the side stream's dT workgroups); bit-identical results
       const long tasks = (long)d.N * d.H;
       hipLaunchKernelGGL(seg_bwd_msg_kernel<false>, dim3((unsigned)cdiv(tasks, 4)), dim3(256), 0, c.s, sv.Z, sv.alpha, gS, gs,
@@ -1636,9 +1627,8 @@ static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const
   };
   // dT operands are prepared (maxima, scaled transposes, fp16 planes: HBM-bound, 0.25 ms a layer) on the side stream as
   // soon as a layer's gu exists, beside that layer's matrix-bound contraction on the main stream, so that the dT launch
-  // itself can start the moment this function has issued its last kernel (CGAT_SIDE_EARLY_PREP=0: all at the end)
-  static const bool early_env = [] { const char* e = getenv("CGAT_SIDE_EARLY_PREP"); return !(e && e[0] == '0'); }();
-  bool early_prep = side && !c.dry && early_env && rows >= 16384;   // (small batches: 9 more launches cost more than they hide)
+  // itself can start the moment this function has issued its last kernel
+  bool early_prep = side && !c.dry && rows >= 16384;   // (small batches: 9 more launches cost more than they hide)
   int n_prepped = 0;
   const float* gout = g_y;  // gradient wrt the output of predicted layer l (post norm for l < last)
   for (int l = p->n_hyper - 1; l >= 0; --l) {
@@ -1815,8 +1805,8 @@ static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const
     }
   }
   if (dwb.n > 0 && !c.dry) {
-    // HBM-bound, 0.7 ms for 24 products at 83 340 rows; by default on the main stream, right here.  On the side stream
-    // (CGAT_SIDE_DW=1) it goes BEHIND the dT launch: that launch must be resident before the caller's next kernel floods
+    // HBM-bound, 0.7 ms for 24 products at 83 340 rows; in f16x3 on the main stream, right here.  On the side stream
+    // (f16x3c) it goes BEHIND the dT launch: that launch must be resident before the caller's next kernel floods
     // the chip with small workgroups (its 132-KB workgroups are not placed while those keep arriving -- measured: 9.5 ms
     // instead of 6.2 when it started 0.7 ms later), and there it ends up beside the matrix-bound edge_ge (1.3 -> 2.5 ms)
     if (side && side->dw_side) {
@@ -1874,24 +1864,13 @@ extern "C" int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_param
   }
   Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
   c.scratch_need = dry.scratch_need;
-  // half of the chip stays free for the main stream's HBM-bound kernels (CGAT_SIDE_WGRAD_WGS: tuning knob, any value
-  // gives the same results up to the summation order of the row splits)
-  static int side_wgs = -1;
-  if (side_wgs < 0) {
-    const char* e = getenv("CGAT_SIDE_WGRAD_WGS");
-    side_wgs = e ? atoi(e) : 128;
-    if (side_wgs < 8 || side_wgs > 256) side_wgs = 128;
-  }
+  // 128 workgroups: half of the chip stays free for the main stream's HBM-bound kernels
+  const int side_wgs = 128;
   // the batched dense-layer weight gradients: f16x3 -- main stream (behind the dT launch on the side stream the batch
   // collided with the matrix-bound edge_ge: 24.14 vs 23.95 ms per step); f16x3c -- side stream (the 24-bit dT launch is
   // twice as long and still running when edge_ge starts either way: 29.0-29.4 vs 29.5 ms, serial order 29.9-30.0;
-  // tools/side_stream_sweep.sh, profiles/r05_side_stream_sweep.txt).  CGAT_SIDE_DW=0/1 overrides.
-  static int dw_env = -2;
-  if (dw_env == -2) {
-    const char* e = getenv("CGAT_SIDE_DW");
-    dw_env = e ? ((e[0] == '1') ? 1 : 0) : -1;
-  }
-  const int dw_side = dw_env >= 0 ? dw_env : (mode_f16c() ? 1 : 0);
+  // profiles/r05_side_stream_sweep.txt)
+  const int dw_side = mode_f16c() ? 1 : 0;
   HnetSide side = {(hipStream_t)side_stream, side_ws, side_ws_bytes, side_wgs, dw_side};
   return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g, &side);
 }

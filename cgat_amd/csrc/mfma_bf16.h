@@ -160,6 +160,47 @@ __device__ __forceinline__ float4 unpack4_bf16(uint2 u) {
 __device__ __forceinline__ float4 load4_bf16(const __bf16* p) { return unpack4_bf16(*reinterpret_cast<const uint2*>(p)); }
 __device__ __forceinline__ void store4_bf16(__bf16* p, float4 v) { *reinterpret_cast<uint2*>(p) = pack4_bf16(v); }
 
+// The k-step plane image the split-operand kernels read (layout in bilinear.hip above bilinear_rows128_ring16_kernel):
+// element (a, b, c) of a [NA][K][128] operand, b < K the reduction index and c the output column, sits at this offset
+// (in 2-byte values) of the first of its NP planes; plane p follows at + p * 2048.  Per (a, 64-column half) come the
+// K / 32 k-steps s = b / 32, each NP planes of [cb = (c % 64) / 16][kg = (b % 32) / 8][i = c % 16][j = b % 8].
+template <int NP, int K = 128>
+__device__ __forceinline__ long plane_image_offset(long a, int b, int c) {
+  const long blk = ((a * 2 + (c >> 6)) * (K / 32) + (b >> 5)) * NP;
+  return blk * 2048 + ((((c & 63) >> 4) * 4 + ((b & 31) >> 3)) * 16 + (c & 15)) * 8 + (b & 7);
+}
+// v into its NP planes at element (a, b, c): NP = 2 the fp16 pieces h + l of v (v already scaled by 2^k), NP = 3 the
+// three bf16 planes of split3_bf16
+template <int NP, int K = 128>
+__device__ __forceinline__ void plane_image_put(void* dst, long a, int b, int c, float v) {
+  const long o = plane_image_offset<NP, K>(a, b, c);
+  if constexpr (NP == 2) {
+    const _Float16 h = (_Float16)v, l = (_Float16)(v - (float)h);
+    _Float16* d = reinterpret_cast<_Float16*>(dst);
+    d[o] = h;
+    d[o + 2048] = l;
+  } else {
+    __bf16 x1, x2, x3;
+    split3_bf16(v, x1, x2, x3);
+    __bf16* d = reinterpret_cast<__bf16*>(dst);
+    d[o] = x1;
+    d[o + 2048] = x2;
+    d[o + 4096] = x3;
+  }
+}
+
+// max |t[n, c]| over this thread's part of a [rows, 128] view with row stride ld floats (16-byte aligned rows; ld = 128:
+// a flat array): a 256-thread workgroup reads 8 rows of 32 float4 per pass, workgroup w of a grid of g rows 8 w + 8 g j.
+__device__ __forceinline__ float absmax_rows128(const float* t, long ld, long rows, long w, long g) {
+  const int c4 = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+  float m = 0.f;
+  for (long n = w * 8 + r0; n < rows; n += g * 8) {
+    const float4 v = *reinterpret_cast<const float4*>(t + n * ld + 4 * c4);
+    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+  }
+  return m;
+}
+
 // at most one atomic per workgroup (thousands of same-address atomics cost more than the pass itself)
 __device__ __forceinline__ void block_absmax_commit(float m, float* out) {
   __shared__ float wm[16];

@@ -327,20 +327,38 @@ int copy2d_multi_launch(const Copy2DJobs& j, hipStream_t s) {
 // previous replay had left in the reused block, atomicMax compared against them, the operand scale came out wrong and the
 // step returned NaN -- replay 0 and every eager run were fine.  The same zeroing as a kernel node replays bit-identically
 // (tests/test_capture.py).
-// out[i] = sum_z slabs[z * stride + i], z = 0 .. n-1 in that order, starting from 0.f (what n accumulating passes over a
-// zero-filled buffer produce, bit for bit)
-__global__ void sum_slabs_kernel(const float* __restrict__ slabs, int n, long stride, float* __restrict__ out, long count) {
+// The library's one slab sum: item t = blockIdx.y, i < count,
+//   out[t][(i >> 7) * ldo + (i & 127)] = sum_z slabs[t * item_stride + z * stride + i],
+// z = 0 .. n-1 in that order, starting from 0.f (what n accumulating passes over a zero-filled buffer produce, bit for
+// bit); four independent loads per round trip, added in slab order.  ldo = 128: out[t][i].
+__global__ void sum_slabs_kernel(const float* __restrict__ slabs, int n, long stride, long item_stride, long count,
+                                 SlabSumOut o, long ldo) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
+  const float* sl = slabs + (long)blockIdx.y * item_stride + i;
   float s = 0.f;
-  for (int z = 0; z < n; ++z) s += slabs[(long)z * stride + i];
-  out[i] = s;
+  int z = 0;
+  for (; z + 4 <= n; z += 4) {
+    const float v0 = sl[(long)z * stride], v1 = sl[(long)(z + 1) * stride];
+    const float v2 = sl[(long)(z + 2) * stride], v3 = sl[(long)(z + 3) * stride];
+    s += v0; s += v1; s += v2; s += v3;
+  }
+  for (; z < n; ++z) s += sl[(long)z * stride];
+  o.out[blockIdx.y][(i >> 7) * ldo + (i & 127)] = s;
 }
-int sum_slabs_launch(const float* slabs, int n, long stride, float* out, long count, hipStream_t s) {
-  if (count <= 0) return CGAT_OK;
-  hipLaunchKernelGGL(sum_slabs_kernel, dim3(cdiv(count, 256)), dim3(256), 0, s, slabs, n, stride, out, count);
+int sum_slabs_batch_launch(const float* slabs, int n, long stride, long count, int items, long item_stride,
+                           float* const* out, long ldo, hipStream_t s) {
+  if (count <= 0 || items <= 0) return CGAT_OK;
+  CGAT_CHECK_ARG(items <= SLAB_SUM_MAX, "sum_slabs: too many items");
+  SlabSumOut o = {};
+  for (int t = 0; t < items; ++t) o.out[t] = out[t];
+  hipLaunchKernelGGL(sum_slabs_kernel, dim3(cdiv(count, 256), items), dim3(256), 0, s, slabs, n, stride, item_stride, count,
+                     o, ldo);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
+}
+int sum_slabs_launch(const float* slabs, int n, long stride, float* out, long count, hipStream_t s) {
+  return sum_slabs_batch_launch(slabs, n, stride, count, 1, 0, &out, 128, s);
 }
 
 __global__ void fill_kernel(float* __restrict__ p, float v, long n) {

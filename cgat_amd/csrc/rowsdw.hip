@@ -336,16 +336,13 @@ __global__ __launch_bounds__(256) void rows_dw128_reduce_kernel(const float* __r
   else if (bsum) bsum[i - (long)nx * 16384] = s;
 }
 
-static bool dws_enabled();
 int rows_dw128_batch_launch(DwBatchDesc d, void* ws, size_t ws_bytes, hipStream_t stream);
 static int dw_rows_per_wg(int rows) {
   int rps = cdiv(cdiv(rows, 256), 16) * 16;      // one workgroup per CU, whole 16-row double batches
   return rps < 16 ? 16 : rps;
 }
 bool rows_dw128_fast(const float* G, long ldg, const float* X1, long ldx1, const float* X2, long ldx2) {
-  static int off = -1;
-  if (off < 0) { const char* e = getenv("CGAT_NO_ROWS_DW"); off = (e && e[0] == '1') ? 1 : 0; }
-  return !off && (ldg % 4) == 0 && (ldx1 % 4) == 0 && (((uintptr_t)G) & 15) == 0 && (((uintptr_t)X1) & 15) == 0 &&
+  return (ldg % 4) == 0 && (ldx1 % 4) == 0 && (((uintptr_t)G) & 15) == 0 && (((uintptr_t)X1) & 15) == 0 &&
          (!X2 || ((ldx2 % 4) == 0 && (((uintptr_t)X2) & 15) == 0));
 }
 size_t rows_dw128_batch_ws_bytes(int n_items, int rows);
@@ -379,7 +376,7 @@ int rows_dw128_launch(const float* G, long ldg, const float* X1, long ldx1, floa
     cgat_set_error("rows_dw128: workspace too small (%zu < %zu)", ws_bytes, need);
     return CGAT_ERR_WORKSPACE;
   }
-  if (nx == 1 && mode_split() && dws_enabled()) {   // split arithmetic modes: the bf16 matrix-core form, as a batch of one
+  if (nx == 1 && mode_split()) {   // split arithmetic modes: the bf16 matrix-core form, as a batch of one
     DwBatchDesc b;
     memset(&b, 0, sizeof(b));
     b.n = 1; b.rows = rows; b.ldg = ldg; b.ldx = ldx1; b.ldo = ldo1;
@@ -417,11 +414,6 @@ int rows_dw128_launch(const float* G, long ldg, const float* X1, long ldx1, floa
 }
 
 // ---- batched form ----
-static bool dws_enabled() {                            // CGAT_ROWS_DW_F32=1: the f32-input kernel in every mode (A/B switch)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("CGAT_ROWS_DW_F32"); v = (e && e[0] == '1') ? 0 : 1; }
-  return v == 1;
-}
 static int dw_batch_splits(int n_items, int rows) {
   int sp = 256 / (n_items > 0 ? n_items : 1);          // all units resident at once (one workgroup per CU)
   const int most = cdiv(rows, 64);                     // at least 64 rows per unit
@@ -455,7 +447,7 @@ int rows_dw128_batch_launch(DwBatchDesc d, void* ws, size_t ws_bytes, hipStream_
     cgat_set_error("rows_dw128_batch: workspace too small (%zu < %zu)", ws_bytes, need);
     return CGAT_ERR_WORKSPACE;
   }
-  const bool split_form = mode_split() && dws_enabled();   // bf16 matrix cores (exact fp32 MFMA in the f32 mode)
+  const bool split_form = mode_split();   // bf16 matrix cores (exact fp32 MFMA in the f32 mode)
   d.splits = dw_batch_splits(d.n, d.rows);
   d.rows_per_unit = cdiv(cdiv(d.rows, d.splits), 32) * 32;   // whole 32-row K-steps (two 16-row double batches)
   // rounding the unit up to 16 rows can leave trailing units that start past the last row (rows = 650, n = 24: unit 9

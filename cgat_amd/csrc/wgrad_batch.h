@@ -15,6 +15,10 @@ struct WgradPrepDesc {
   const float* r[WGB_MAX];
 };
 
+// mx[4 * (l0 + l) + which] = max |p, q, r of layer l| for l < n (mx zeroed before), wgs workgroups per tensor (bilinear.hip)
+int absmax_rows_batch_launch(const WgradPrepDesc& d, int l0, int n, long ldp, long ldq, long ldr, int rows, int NA,
+                             float* mx, int wgs, hipStream_t stream);
+
 // ---- f16x3c form (wgradc.hip) ----
 int wgradc_pick(int n_layers, int nrows, int NA, int* rps_out);
 size_t wgradc_ws_bytes(int n_layers, int nrows, int NA);

@@ -43,26 +43,7 @@ typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
 #endif
 
 // ------------------------------- operand preparation -------------------------------
-// mx[4 * layer + which] = max |tensor|, which 0 / 1 / 2 = p / q / r  (mx zeroed before)
-__global__ void wgc_absmax_kernel(WgradPrepDesc d, int l0, long ldp, long ldq, long ldr, int rows, int NA,
-                                  float* __restrict__ mx) {
-  const int layer = blockIdx.y / 3, which = blockIdx.y % 3;
-  const float* t = which == 0 ? d.p[layer] : (which == 1 ? d.q[layer] : d.r[layer]);
-  const long ld = which == 0 ? ldp : (which == 1 ? ldq : ldr);
-  const int cols = which == 0 ? NA : 128;
-  float m = 0.f;
-  if (cols == 128 && (ld & 3) == 0 && (((uintptr_t)t) & 15) == 0) {
-    const int c4 = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-    for (long n = (long)blockIdx.x * 8 + r0; n < rows; n += (long)gridDim.x * 8) {
-      const float4 v = *reinterpret_cast<const float4*>(t + n * ld + 4 * c4);
-      m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    }
-  } else {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (long)rows * cols; i += (long)gridDim.x * blockDim.x)
-      m = fmaxf(m, fabsf(t[(i / cols) * ld + (i % cols)]));
-  }
-  block_absmax_commit(m, mx + 4 * (l0 + layer) + which);
-}
+// (the maxima: absmax_rows_batch_launch, bilinear.hip)
 
 // One 64-row chunk of one operand of one layer per workgroup (256 threads; blockIdx.z = operand):
 //  pT [128][rows_pad]      = (p * 2^k * sign(n))^T: 2^k from max|p| max|q| (the products must fit fp16), sign(n) = -1 in the
@@ -483,25 +464,13 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
   }
 }
 
-// out[layer][i] = sum_z slab[layer][z][i]
-__global__ void wgc_slab_sum_kernel(const float* __restrict__ slab, int splits, long n, WgradBatchDesc u) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float* sl = slab + (long)blockIdx.y * splits * n;
-  float s = 0.f;
-  for (int z = 0; z < splits; ++z) s += sl[(long)z * n + i];
-  u.out[blockIdx.y][i] = s;
-}
-
 // ------------------------------- host side -------------------------------
 // row splits per layer: enough units to fill the chip once (more only adds slab traffic), at least 4 chunks per split;
 // a split is a whole number of 512-row sign groups unless it is the only one
 int wgradc_pick(int n_layers, int nrows, int NA, int* rps_out) {
   const int npairs = cdiv(NA, 2), np = cdiv(nrows, WGC_ROWS) * WGC_ROWS;
-  // work units (layer x row split x pair of a) ~ one per CU; CGAT_WGC_UNITS: tuning knob for the side-stream launch,
-  // where units finer than the launch's workgroups balance a grid that is not a divisor of 256
-  static const int target = [] { const char* e = getenv("CGAT_WGC_UNITS"); const int v = e ? atoi(e) : 256; return v >= 64 && v <= 2048 ? v : 256; }();
-  int splits = target / (n_layers * npairs);
+  // work units (layer x row split x pair of a) ~ one per CU
+  int splits = 256 / (n_layers * npairs);
   if (splits > np / 256) splits = np / 256;
   if (splits < 1) splits = 1;
   int rps = cdiv(np / WGC_ROWS, splits) * WGC_ROWS;
@@ -541,9 +510,7 @@ int wgradc_prep(int l0, int n, int n_layers, const float* const* p, long ldp, co
   for (int l = 0; l < n; ++l) { pd.p[l] = p[l]; pd.q[l] = q[l]; pd.r[l] = r[l]; }
   float* mx = (float*)((char*)ws + o_mx);
   CGAT_TRY(fill_launch(mx + 4 * l0, 0.f, 4 * n, stream));
-  hipLaunchKernelGGL(wgc_absmax_kernel, dim3(nrows < 2048 ? cdiv(nrows, 8) : 256, 3 * n), dim3(256), 0, stream, pd, l0, ldp,
-                     ldq, ldr, nrows, NA, mx);
-  CGAT_LAUNCH_CHECK();
+  CGAT_TRY(absmax_rows_batch_launch(pd, l0, n, ldp, ldq, ldr, nrows, NA, mx, nrows < 2048 ? cdiv(nrows, 8) : 256, stream));
   hipLaunchKernelGGL(wgc_prep_kernel, dim3(np / WGC_ROWS, n, 3), dim3(256), 0, stream, pd, l0, ldp, ldq, ldr, nrows, NA, np, rps,
                      (float*)((char*)ws + o_pT), (float*)((char*)ws + o_qF), (unsigned char*)ws + o_Rs, (long)np * 128,
                      (long)(np / WGC_ROWS) * WGC_RS_B, (const float*)mx);
@@ -583,9 +550,7 @@ int wgradc_launch(int n_layers, const float* const* p, long ldp, const float* co
   CGAT_LAUNCH_CHECK();
   if (splits > 1) {
     const long n = (long)NA * 128 * 128;
-    hipLaunchKernelGGL(wgc_slab_sum_kernel, dim3(cdiv(n, 256), n_layers), dim3(256), 0, stream, (const float*)u.slab, splits,
-                       n, u);
-    CGAT_LAUNCH_CHECK();
+    CGAT_TRY(sum_slabs_batch_launch(u.slab, splits, n, n, n_layers, splits * n, u.out, 128, stream));
   }
   return CGAT_OK;
 }

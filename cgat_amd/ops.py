@@ -419,13 +419,12 @@ def side_stream(device, create=True):
     dev = torch.device(device)
     key = dev.index if dev.index is not None else torch.cuda.current_device()
     if key not in _side_streams and create:
-        # CGAT_SIDE_PRIORITY=-1: a high-priority side stream (its workgroups are placed ahead of the main stream's)
-        _side_streams[key] = torch.cuda.Stream(device=dev, priority=int(os.environ.get("CGAT_SIDE_PRIORITY", "0")))
+        _side_streams[key] = torch.cuda.Stream(device=dev)
     return _side_streams.get(key)
 
 
 _branch_streams = {}
-_branch_max_edges = int(os.environ.get("CGAT_BRANCH_STREAM_MAX_EDGES", "262144"))   # 0: never
+_BRANCH_MAX_EDGES = 262144
 
 
 def branch_stream(device, n_edges, which=0):
@@ -435,7 +434,7 @@ def branch_stream(device, n_edges, which=0):
     workgroup needs for its serial chain, so two independent chains side by side cost the longer one, not the sum
     (SURVEY 8 f3).  Works eagerly and under hipGraph capture (fork / join by events); autograd runs each node's backward
     on its forward's stream, so the backward overlaps the same way."""
-    if _branch_max_edges <= 0 or n_edges > _branch_max_edges:
+    if n_edges > _BRANCH_MAX_EDGES:
         return None
     dev = torch.device(device)
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), which)

@@ -5,11 +5,13 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from cgat_amd import _lib  # noqa: E402
+from cgat_amd import _lib, get_bilinear_mode, set_bilinear_mode  # noqa: E402
 
 dev = torch.device("cuda:0")
 lib = _lib.lib
-print("CGAT_GEMM_SPLIT =", os.environ.get("CGAT_GEMM_SPLIT", "(default: on)"))
+if "--f32" in sys.argv:   # the f32-input engine: the f32 arithmetic mode
+    set_bilinear_mode("f32")
+print("arithmetic mode:", get_bilinear_mode())
 for W, rows in [(16, 80), (16, 960), (22, 130), (64, 1000), (96, 333)]:
     g = torch.Generator().manual_seed(W + rows)
     p, q, r = (torch.randn(rows, W, generator=g).to(dev) for _ in range(3))

@@ -7,11 +7,13 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from cgat_amd import _lib  # noqa: E402
+from cgat_amd import _lib, get_bilinear_mode, set_bilinear_mode  # noqa: E402
 
 dev = torch.device("cuda:0")
 ws = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
-print("CGAT_GEMM_SPLIT =", os.environ.get("CGAT_GEMM_SPLIT", "(default: on)"), " passes", os.environ.get("CGAT_GEMM_SPLIT_PASSES", "8"))
+if "--f32" in sys.argv:   # the f32-input engine: the f32 arithmetic mode
+    set_bilinear_mode("f32")
+print("arithmetic mode:", get_bilinear_mode())
 for (M, N, K, bkm) in [(1024, 1024, 1024, 0), (1024, 1024, 1024, 1), (1024, 1024, 64, 0), (512, 512, 8192, 0)]:
     g = torch.Generator().manual_seed(K)
     A = torch.randn(M, K, generator=g).to(dev)

@@ -1,5 +1,5 @@
 """Dev tool: throughput of the generic engine (cgat_gemm) on large plain products, per operand layout.
-Run with CGAT_GEMM_SPLIT=0 for the f32-input engine, default for the six-pass bf16 engine."""
+Run with --f32 for the f32-input engine, default for the current mode's engine (six-pass bf16 in the split modes)."""
 import ctypes as C
 import os
 import sys
@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from cgat_amd import _lib  # noqa: E402
+from cgat_amd import _lib, get_bilinear_mode, set_bilinear_mode  # noqa: E402
 
 dev = torch.device("cuda:0")
 ws = torch.empty(1 << 28, dtype=torch.uint8, device=dev)
@@ -57,7 +57,9 @@ def bias(M, N, K):
     print(f"signed error of {M}x{N}x{K}, positive operands: mean {float(rel.mean()):+.2e}  rms {float(rel.pow(2).mean().sqrt()):.2e}", flush=True)
 
 
-print("CGAT_GEMM_SPLIT =", os.environ.get("CGAT_GEMM_SPLIT", "(default: on)"))
+if "--f32" in sys.argv:   # the f32-input engine: the f32 arithmetic mode
+    set_bilinear_mode("f32")
+print("arithmetic mode:", get_bilinear_mode())
 for akm in (False, True):
     for bkm in (False, True):
         run(f"8192x4096x4096 akm={int(akm)} bkm={int(bkm)}", 8192, 4096, 4096, akm, bkm)

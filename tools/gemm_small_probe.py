@@ -6,11 +6,13 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from cgat_amd import _lib  # noqa: E402
+from cgat_amd import _lib, get_bilinear_mode, set_bilinear_mode  # noqa: E402
 
 dev = torch.device("cuda:0")
 ws = torch.empty(1 << 26, dtype=torch.uint8, device=dev)
-print("CGAT_GEMM_SPLIT =", os.environ.get("CGAT_GEMM_SPLIT", "(default: on)"))
+if "--f32" in sys.argv:   # the f32-input engine: the f32 arithmetic mode
+    set_bilinear_mode("f32")
+print("arithmetic mode:", get_bilinear_mode())
 for (M, N, K) in [(4, 1024, 1024), (4, 1024, 48), (80, 64, 48), (80, 32, 96), (1280, 128, 200), (80, 16, 16), (80, 96, 32),
                   (960, 32, 48), (80, 1, 32), (4, 2, 128), (300, 48, 80)]:
     for akm in (False, True):

@@ -12,6 +12,8 @@ import golden_util as G  # noqa: E402
 import recipe  # noqa: E402
 import cgat_amd as P  # noqa: E402
 
+if "--f32" in sys.argv:   # the f32 arithmetic mode
+    P.set_bilinear_mode("f32")
 fname, cname = sys.argv[1], sys.argv[2]
 cases = recipe.tiny_cases(P) if fname.startswith("tiny") else recipe.base_cases(P)
 case = cases[cname]
@@ -27,6 +29,6 @@ for name, g in grads.items():
     allowed = max(1e-4 * ref_max, G.NOISE_MULT * nf_abs, 1e-6 * case_scale)
     rows.append((err / allowed, name, err, ref_max, nf_abs))
 rows.sort(reverse=True)
-print("engine:", os.environ.get("CGAT_GEMM_SPLIT", "split"), "case scale", case_scale)
+print("arithmetic mode:", P.get_bilinear_mode(), "case scale", case_scale)
 for r in rows[:12]:
     print("  margin %.2f  %-60s err %.3e |ref| %.3e nf %.3e" % r)

@@ -11,14 +11,16 @@ import golden_util as G  # noqa: E402
 import recipe  # noqa: E402
 import cgat_amd as P  # noqa: E402
 
-print("engine:", os.environ.get("CGAT_GEMM_SPLIT", "split"))
+print("arithmetic mode:", P.get_bilinear_mode())
 import types  # noqa: E402
 NS = types.SimpleNamespace(MultiHeadNetwork=P.MultiHeadNetwork, GATConvNodes=P.GATConvNodes, GATConvEdges=P.GATConvEdges,
                            MHAttention=P.MHAttention, CGAtNet=P.CGAtNet, H_Net_0=P.H_Net_0, H_Net=P.H_Net,
                            SimpleNetwork=P.SimpleNetwork, ResidualNetwork=P.ResidualNetwork,
                            WeightedAttention=P.WeightedAttention, MessageLayer=P.MessageLayer, Roost=P.Roost,
                            RoostSimpleNetwork=P.SimpleNetwork)
-ONLY = sys.argv[1] if len(sys.argv) > 1 else ""
+if "--f32" in sys.argv:   # the f32 arithmetic mode
+    P.set_bilinear_mode("f32")
+ONLY = ([a for a in sys.argv[1:] if a != "--f32"] + [""])[0]
 for cname, case in recipe.tiny_cases(NS).items():
     if ONLY not in cname:
         continue

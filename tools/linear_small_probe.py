@@ -5,10 +5,12 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from cgat_amd import _lib, ops  # noqa: E402
+from cgat_amd import _lib, ops, get_bilinear_mode, set_bilinear_mode  # noqa: E402
 
 dev = torch.device("cuda:0")
-print("CGAT_GEMM_SPLIT =", os.environ.get("CGAT_GEMM_SPLIT", "(default: on)"))
+if "--f32" in sys.argv:   # the f32-input engine: the f32 arithmetic mode
+    set_bilinear_mode("f32")
+print("arithmetic mode:", get_bilinear_mode())
 for (M, K, N) in [(4, 1024, 1024), (4, 1024, 512), (4, 512, 512), (4, 384, 1024), (4, 256, 128), (64, 1024, 1024), (4, 1024, 2)]:
     g = torch.Generator().manual_seed(M + K + N)
     x = torch.randn(M, K, generator=g).to(dev).requires_grad_(True)

@@ -50,10 +50,12 @@ def trace(case, dtype, device):
     return rec
 
 
+if "--f32" in sys.argv:   # the f32 arithmetic mode
+    P.set_bilinear_mode("f32")
 cname = sys.argv[1]
 a = trace(recipe.tiny_cases(ns(P))[cname], torch.float32, "cuda:0")
 b = trace(recipe.tiny_cases(ns(O))[cname], torch.float64, "cpu")
-print("engine:", os.environ.get("CGAT_GEMM_SPLIT", "split"))
+print("arithmetic mode:", P.get_bilinear_mode())
 scale_g = max(float(v.abs().max()) for k, v in b.items() if k.startswith("gp:"))
 rows = []
 for k in b:
