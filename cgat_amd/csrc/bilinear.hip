@@ -1521,6 +1521,59 @@ int prepare_T_bf16_heads_launch(const float* src, void* dst, int NA, long sa, lo
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
+// The six-pass image of edge_ge_launch's weight (alternate = 1) whose first nAb blocks -- the attention half of the
+// rebuilt gZ rows, edgebwd.hip -- hold W'[128 a + b][c] = wA[128 a + b] * W[128 a + b][c] (ONE fp32 rounding, then the
+// exact split) instead of W: the row operand of those blocks is then the stored bit of LeakyReLU' alone.  The last H
+// workgroups form cs[h][c] = sgn * sum_b W'[h Hd + b][c] in a fixed order (eight runs of Hd / 8 columns, added 0..7),
+// sgn = the sign the image gives the head's LAST block, i.e. the one the accumulators carry when the head is flushed.
+__global__ __launch_bounds__(256) void prepare_T_bf16_attn_kernel(const float* __restrict__ src, __bf16* __restrict__ dst,
+                                                                  int NA, long sa, long sb, long sc,
+                                                                  const float* __restrict__ wA, int nAb, int Hd,
+                                                                  float* __restrict__ cs, int nprep) {
+  if ((int)blockIdx.x < nprep) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)NA * 128 * 128) return;
+    int a = (int)(i >> 14), b, c;
+    if (sc == 1) { b = (int)((i >> 7) & 127); c = (int)(i & 127); }
+    else { c = (int)((i >> 7) & 127); b = (int)(i & 127); }
+    float v = src[a * sa + b * sb + c * sc];
+    if (a < nAb) v = __fmul_rn(wA[128 * a + b], v);
+    if (a & 1) v = -v;
+    plane_image_put<3>(dst, a, b, c, v);
+    return;
+  }
+  __shared__ float run[8][128];
+  const int h = blockIdx.x - nprep, k4 = threadIdx.x & 31, seg = threadIdx.x >> 5, per = Hd / 8;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < per; ++j) {
+    const long col = (long)h * Hd + seg * per + j;
+    const float w = wA[col];
+    const float* p = src + (col >> 7) * sa + (col & 127) * sb + 4 * k4 * sc;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] = __fadd_rn(s[u], __fmul_rn(w, p[u * sc]));
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) run[seg][4 * k4 + u] = s[u];
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    float t = run[0][threadIdx.x];
+#pragma unroll
+    for (int g = 1; g < 8; ++g) t = __fadd_rn(t, run[g][threadIdx.x]);
+    const int a_last = ((h + 1) * Hd) / 128 - 1;
+    cs[h * 128 + threadIdx.x] = (a_last & 1) ? -t : t;
+  }
+}
+int prepare_T_bf16_attn_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, const float* wA, int H,
+                               int Hd, float* cs, hipStream_t stream) {
+  const long total = (long)NA * 128 * 128;
+  if (total <= 0) return CGAT_OK;
+  CGAT_CHECK_ARG(H > 0 && Hd % 128 == 0 && (long)H * Hd <= (long)NA * 128, "prepare_T_bf16_attn: H = %d, Hd = %d", H, Hd);
+  const int nprep = (int)cdiv(total, 256);
+  hipLaunchKernelGGL(prepare_T_bf16_attn_kernel, dim3(nprep + H), dim3(256), 0, stream, src, (__bf16*)dst, NA, sa, sb, sc,
+                     wA, H * Hd / 128, Hd, cs, nprep);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
 // fp16 form with the maximum already known (tmax[0], device memory): strided sources
 int prepare_T_f16_scaled_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, const float* tmax,
                                 hipStream_t stream, int alternate) {

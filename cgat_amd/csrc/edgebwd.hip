@@ -20,7 +20,23 @@ __device__ __forceinline__ float rc_d(unsigned m, int bit) {
   const unsigned s = (unsigned)((int)(m << (31 - bit)) >> 31);
   return __uint_as_float((s & 0x3F800000u) | (~s & 0x3C23D70Au));
 }
-template <int PASSES, bool RC = false>
+// eight mask bits -> the bf16 fragment of their values 0 / 1 (0x3F80 = 1.0): one plane, exact
+__device__ __forceinline__ bf16x8 bits8_bf16(unsigned m) {
+  uint4 w;
+#define GE_BITPAIR(i_) ((((unsigned)((int)(m << (31 - 2 * (i_))) >> 31)) & 0x3F80u) |                     \
+                        (((unsigned)((int)(m << (30 - 2 * (i_))) >> 31)) & 0x3F800000u))
+  w.x = GE_BITPAIR(0); w.y = GE_BITPAIR(1); w.z = GE_BITPAIR(2); w.w = GE_BITPAIR(3);
+#undef GE_BITPAIR
+  return __builtin_bit_cast(bf16x8, w);
+}
+// BP (with RC, six passes: scalar attention in the 24-bit modes; edge_ge_bitplane below): the k-steps of the ATTENTION
+// half run on the stored bit alone.  There gZ[t, (h, c)] = ga[t, h] wA[h, c] d, d = 1 or 0.01 by the bit m, so with
+// W'[(h, c), :] = wA[h, c] W_e[(h, c), :] (prepare_T_bf16_attn_launch: the image's attention blocks hold W')
+//     sum_c gZ[t, (h, c)] W_e[(h, c), :] = ga[t, h] * (P + 0.01 (cs_h - P)),   P = sum_c m[t, h, c] W'[(h, c), :],
+// cs_h = sum_c W'[(h, c), :].  m is exact in ONE bf16 plane: P takes three passes (the planes of W') instead of six and
+// its row operand is eight shifted bits -- no coefficient, no wA, no multiply, no split.  P is summed per head in a
+// second accumulator set and folded into the first at the head's last block (GA_FLUSH: the arithmetic is pinned there).
+template <int PASSES, bool RC = false, bool BP = false>
 __global__ __launch_bounds__(512, 2) void edge_ge_kernel(const float* __restrict__ gZ, long ldg, long gzb,
                                                          const uint4* __restrict__ Wq, int ncb,
                                                          float* __restrict__ out, long ldo,
@@ -148,17 +164,110 @@ __global__ __launch_bounds__(512, 2) void edge_ge_kernel(const float* __restrict
       split3_x8(g_, Q1_, Q2_, Q3_);                                                                      \
     }                                                                                                    \
   }
+  // BP: the attention k-steps of this launch group come first (whole column blocks: HHd % 128 == 0, groups are whole
+  // blocks), the loop below then starts at block aA.  The accumulators keep the sign convention of that loop -- at the
+  // start of block a they hold (-1)^a times the sum so far -- and so does the per-head set.
+  int aA = 0;
+  if constexpr (BP) {
+    static_assert(RC && PASSES == 6, "the bit-plane body belongs to the six-pass rebuilt form");
+    __shared__ float Cs[8 * 128];                  // cs of every head (H <= 8), signed as the flush meets it
+    const int nA = min(nk, max(0, rc.HHd / 32 - ks0));
+    aA = nA >> 2;
+    if (aA > 0) {
+      for (int i = tid; i < rc.H * 128; i += 512) Cs[i] = rc.cs[i];
+      const int hsteps = rc.Hd >> 5;               // k-steps per head (a multiple of 4)
+      f32x4 part[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) part[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      unsigned ma[4], mb[4], xa[4], xb[4];         // mask words of rows a / b: this block's, the next block's
+#pragma unroll
+      for (int s = 0; s < 4; ++s) { ma[s] = mka[ks0 + s]; mb[s] = mkb[ks0 + s]; }
+      GE_BLOAD(0, sb0, sb1, sb2);
+      GE_BSTORE(0);
+      GE_BLOAD(1, sb0, sb1, sb2);
+      __syncthreads();
+      // k-step ks: its tile is in Bs[ks & 1], the tile of ks + 1 in flight in one register set; the tile of ks + 2 is
+      // requested into the other set, the MFMAs run, the first set is stored into the other buffer
+#define GA_STEP(ks_, buf_, MA_, MB_, UB0, UB1, UB2, TB0, TB1, TB2)                                         \
+      {                                                                                                  \
+        const int kl_ = (ks_) + 2 < nA ? (ks_) + 2 : nA - 1;                                             \
+        GE_BLOAD(kl_, TB0, TB1, TB2);                                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        const bf16x8* bs = reinterpret_cast<const bf16x8*>(&Bs[buf_][lane]);                             \
+        const bf16x8 qa = bits8_bf16((MA_) >> (8 * kg)), qb = bits8_bf16((MB_) >> (8 * kg));             \
+        bf16x8 f1 = bs[0], f2 = bs[256], f3 = bs[512];                                                   \
+        _Pragma("unroll") for (int g = 0; g < 8; ++g) {                                                  \
+          bf16x8 n1, n2, n3;                                                                             \
+          if (g < 7) {                                                                                   \
+            const int o = ((g + 1) >> 2) * HP + ((g + 1) & 3) * 64;                                      \
+            n1 = bs[o]; n2 = bs[o + 256]; n3 = bs[o + 512];                                              \
+          }                                                                                              \
+          /* smallest plane first; rows a and b alternate so that no pass waits for the one before it */   \
+          part[2 * g + 0] = mma16<false>(f3, qa, part[2 * g + 0]);                                       \
+          part[2 * g + 1] = mma16<false>(f3, qb, part[2 * g + 1]);                                       \
+          part[2 * g + 0] = mma16<false>(f2, qa, part[2 * g + 0]);                                       \
+          part[2 * g + 1] = mma16<false>(f2, qb, part[2 * g + 1]);                                       \
+          part[2 * g + 0] = mma16<false>(f1, qa, part[2 * g + 0]);                                       \
+          part[2 * g + 1] = mma16<false>(f1, qb, part[2 * g + 1]);                                       \
+          if (g < 7) { f1 = n1; f2 = n2; f3 = n3; }                                                      \
+        }                                                                                                \
+        Bs[(buf_) ^ 1][tid] = UB0; Bs[(buf_) ^ 1][p1] = UB1; Bs[(buf_) ^ 1][p2] = UB2;                   \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                               \
+        __builtin_amdgcn_s_barrier();                                                                    \
+        asm volatile("" ::: "memory");                                                                   \
+      }
+      for (int a = 0; a < aA; ++a) {
+        const int ks = 4 * a, an = a + 1 < aA ? a + 1 : a;
+        const int h = (ks0 + ks) / hsteps;
+        const float cha = caA[h], chb = cbA[h];      // ga[t, h] of rows a / b: used at the head's last block only
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { xa[s] = mka[ks0 + 4 * an + s]; xb[s] = mkb[ks0 + 4 * an + s]; }
+        GA_STEP(ks, 0, ma[0], mb[0], sb0, sb1, sb2, tb0, tb1, tb2)
+        GA_STEP(ks + 1, 1, ma[1], mb[1], tb0, tb1, tb2, sb0, sb1, sb2)
+        GA_STEP(ks + 2, 0, ma[2], mb[2], sb0, sb1, sb2, tb0, tb1, tb2)
+        GA_STEP(ks + 3, 1, ma[3], mb[3], tb0, tb1, tb2, sb0, sb1, sb2)
+        if ((ks0 + ks + 4) % hsteps == 0) {
+          // GA_FLUSH: acc += ga * (P + 0.01 (cs - P)) as  d = cs - P;  u = fma(0.01, d, P);  acc = fma(ga, u, acc),
+          // each one rounding, in this order (P, cs and acc all carry this block's sign; 0.01f is LeakyReLU's slope)
+          const float* cs = Cs + h * 128 + 4 * kg;
+#pragma unroll
+          for (int g = 0; g < 8; ++g) {
+            const float4 c4 = *reinterpret_cast<const float4*>(cs + 16 * g);
+            const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const float pv = part[2 * g + nb][j];
+                const float u = __fmaf_rn(0.01f, __fsub_rn(cv[j], pv), pv);
+                acc[2 * g + nb][j] = __fmaf_rn(nb ? chb : cha, u, acc[2 * g + nb][j]);
+              }
+              part[2 * g + nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { acc[i] = -acc[i]; part[i] = -part[i]; }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { ma[s] = xa[s]; mb[s] = xb[s]; }
+      }
+#undef GA_STEP
+    }
+  }
+  const int kbeg = 4 * aA;                       // first k-step of the loop below (0 unless BP)
   bf16x8 qa1, qa2, qa3, qb1, qb2, qb3;           // current k-step's gZ fragments (rows a, b)
   bf16x8 na1, na2, na3, nb1, nb2, nb3;           // next k-step's
-  GE_ALOAD(0, ra0, ra1, rb0, rb1, rca_c, rcb_c, rca_m, rcb_m);
-  GE_BLOAD(0, sb0, sb1, sb2);
-  GE_SPLIT(ra0, ra1, rca_c, rca_m, qa1, qa2, qa3);
-  GE_SPLIT(rb0, rb1, rcb_c, rcb_m, qb1, qb2, qb3);
-  GE_BSTORE(0);
-  ra0 = ra1 = rb0 = rb1 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (PASSES < 6) GE_BLOAD(1, sb0, sb1, sb2);   // nk >= 4
-  GE_ALOAD(1, ra0, ra1, rb0, rb1, rca_c, rcb_c, rca_m, rcb_m);
-  __syncthreads();
+  if (!BP || kbeg < nk) {
+    GE_ALOAD(kbeg, ra0, ra1, rb0, rb1, rca_c, rcb_c, rca_m, rcb_m);
+    GE_BLOAD(kbeg, sb0, sb1, sb2);
+    GE_SPLIT(ra0, ra1, rca_c, rca_m, qa1, qa2, qa3);
+    GE_SPLIT(rb0, rb1, rcb_c, rcb_m, qb1, qb2, qb3);
+    GE_BSTORE(0);
+    ra0 = ra1 = rb0 = rb1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (PASSES < 6) GE_BLOAD(kbeg + 1, sb0, sb1, sb2);   // nk >= 4
+    GE_ALOAD(kbeg + 1, ra0, ra1, rb0, rb1, rca_c, rcb_c, rca_m, rcb_m);
+    __syncthreads();
+  }
 
 #define GE_MFMA1(F1_, F2_, F3_, Q1_, Q2_, Q3_, P_)                                                       \
   {                                                                                                      \
@@ -223,7 +332,7 @@ __global__ __launch_bounds__(512, 2) void edge_ge_kernel(const float* __restrict
   // with one sign, tools/f16_bias_probe.py): the weight planes of odd blocks are prepared NEGATED (edge_ge_launch) and
   // the accumulators change sign between blocks (exact), so a block's bias enters the result with the sign (-1)^a and
   // consecutive blocks cancel; after the last block the accumulators hold (-1)^ncb times the sum.
-  for (int a = 0; a < ncb; ++a) {
+  for (int a = aA; a < ncb; ++a) {
     const int ks = 4 * a;
     GE_ITER(ks, 0, ra0, ra1, rb0, rb1, rca_c, rcb_c, rca_m, rcb_m, sa0, sa1, sb0_, sb1_, sca_c, scb_c, sca_m, scb_m,
             sb0, sb1, sb2, tb0, tb1, tb2)
@@ -595,6 +704,13 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
 #undef GW_FLUSH
 }
 
+// The rebuilt rows take the bit-plane body (edge_ge_kernel<6, true, true>) in the 24-bit modes when the attention half is
+// whole heads of whole 128-column blocks (at most 8: the kernel's LDS copy of cs) and a launch group of ncb_g column
+// blocks starts at a head's first block (a group that is the whole row always does).
+static bool edge_ge_bitplane(const EdgeRC* rc, int W2, int ncb_g) {
+  return rc && mode_24bit() && !edge_mma_bf16() && rc->H >= 1 && rc->H <= 8 && rc->Hd % 128 == 0 &&
+         rc->HHd == rc->H * rc->Hd && rc->HHd <= W2 && rc->nw * 32 == W2 && (ncb_g * 128) % rc->Hd == 0;
+}
 bool edge_ge_fast(int Ce, int W2, long ldg, long gzb, long ldo, const void* gZ, const void* out) {
   return mode_split() && Ce == 128 && W2 % 128 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
          (ldo % 4) == 0 && ((((uintptr_t)gZ) | ((uintptr_t)out)) & 15) == 0;
@@ -613,6 +729,9 @@ int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_
   const bool out_contig = s_out == 1 && (s_col % 4) == 0, in_contig = s_col == 1 && (s_out % 4) == 0 && W2 % 128 == 0;
   const bool f16 = mode_f16() && amax && (out_contig || in_contig) && (((uintptr_t)We) & 15) == 0;
   // operand (a = column block, b = column in block, c = output k) = We[(128 a + b) * s_col + c * s_out]
+  const bool bp = !f16 && edge_ge_bitplane(rc, W2, ncb);
+  EdgeRC rcv = rc ? *rc : EdgeRC{};
+  rcv.cs = Wq + edge_ge_cs_offset(W2);
   if (f16) {   // per-tensor weight scale: max |We| behind the two planes
     float* wmax = Wq + (size_t)ncb * 16384;
     CGAT_TRY(fill_launch(wmax, 0.f, 1, stream));
@@ -620,18 +739,23 @@ int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_
     else
       for (int j = 0; j < ncb; ++j) CGAT_TRY(absmax_rows128_launch(We + 128 * j, s_out, 128, wmax, stream));
     CGAT_TRY(prepare_T_f16_scaled_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, wmax, stream, /*alternate=*/1));
+  } else if (bp) {
+    CGAT_TRY(prepare_T_bf16_attn_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, rcv.wA, rcv.H, rcv.Hd,
+                                        const_cast<float*>(rcv.cs), stream));
   } else {
     CGAT_TRY(prepare_T_bf16_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
   }
   CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);   // the per-edge launch / node-side and dense-layer uses
   const int grid = cdiv(E, 256);
-  const EdgeRC none = {};
 #define GE_GO(P_, R_)                                                                                                 \
   hipLaunchKernelGGL((edge_ge_kernel<P_, R_>), dim3(grid), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq, ncb, \
-                     out, ldo, scatter, E, accumulate, bias, amax, R_ ? *rc : none, HeadBatch{})
+                     out, ldo, scatter, E, accumulate, bias, amax, rcv, HeadBatch{})
   // (the per-EDGE launch only -- rc: the rebuilt gZ rows -- and never in the fp16 mode, which has its own bf16 storage form)
   const bool one = rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
-  if (one) GE_GO(1, true);
+  if (bp)
+    hipLaunchKernelGGL((edge_ge_kernel<6, true, true>), dim3(grid), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq,
+                       ncb, out, ldo, scatter, E, accumulate, bias, amax, rcv, HeadBatch{});
+  else if (one) GE_GO(1, true);
   else if (rc) { if (f16) GE_GO(2, true); else if (!mode_bf16x3()) GE_GO(6, true); else GE_GO(3, true); }
   else { if (f16) GE_GO(2, false); else if (!mode_bf16x3()) GE_GO(6, false); else GE_GO(3, false); }
 #undef GE_GO
@@ -661,17 +785,27 @@ int edge_ge_ksplit_launch(const float* gZ, long ldg, long gzb, const float* We, 
   const int ncb = W2 / 128;
   CGAT_CHECK_ARG(S >= 1 && ncb % S == 0 && (S == 1 || ((ncb / S) & 1) == 0) && mode_24bit(),
                  "edge_ge_ksplit: %d groups of %d column blocks", S, ncb);
-  CGAT_TRY(prepare_T_bf16_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
-  CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);
-  const EdgeRC none = {};
   const int ncb_g = ncb / S;
+  const bool bp = edge_ge_bitplane(rc, W2, ncb_g);   // groups that start inside a head keep the six-pass body
+  EdgeRC rcv = rc ? *rc : EdgeRC{};
+  rcv.cs = Wq + edge_ge_cs_offset(W2);
+  if (bp)
+    CGAT_TRY(prepare_T_bf16_attn_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, rcv.wA, rcv.H, rcv.Hd,
+                                        const_cast<float*>(rcv.cs), stream));
+  else
+    CGAT_TRY(prepare_T_bf16_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
+  CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);
   const HeadBatch hb = {(long)ncb_g * gzb, (long)ncb_g * 6144, 0, (long)E * 128, 0, 0, (long)ncb_g * 4};
-  if (rc)     // the rows rebuilt from their ingredients (struct EdgeRC): a group's k-steps start at ks0
+  if (bp)
+    hipLaunchKernelGGL((edge_ge_kernel<6, true, true>), dim3(cdiv(E, 256), S), dim3(512), 0, stream, gZ, ldg, gzb,
+                       (const uint4*)Wq, ncb_g, slabs, 128l, scatter, E, 0, (const float*)nullptr, (const float*)nullptr,
+                       rcv, hb);
+  else if (rc)     // the rows rebuilt from their ingredients (struct EdgeRC): a group's k-steps start at ks0
     hipLaunchKernelGGL((edge_ge_kernel<6, true>), dim3(cdiv(E, 256), S), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq,
                        ncb_g, slabs, 128l, scatter, E, 0, (const float*)nullptr, (const float*)nullptr, *rc, hb);
   else
     hipLaunchKernelGGL((edge_ge_kernel<6, false>), dim3(cdiv(E, 256), S), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq,
-                       ncb_g, slabs, 128l, scatter, E, 0, (const float*)nullptr, (const float*)nullptr, none, hb);
+                       ncb_g, slabs, 128l, scatter, E, 0, (const float*)nullptr, (const float*)nullptr, rcv, hb);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }

@@ -1039,7 +1039,10 @@ bool edge_z_fast(int Ce, int W2, int H, int Hd, long lde, long ld_add, long ldz,
 }
 
 // floats of workspace for the pre-split weight
-size_t edge_z_wq_floats(int W2) { return ((size_t)W2 * 128 * 3 + 1) / 2; }   // three bf16 planes (the fp16 form: two)
+// three bf16 planes (the fp16 form: two), then room for the per-head column sums of edge_ge's bit-plane form
+// (edgebwd.hip: H * 128 <= W2 / 2 floats at edge_ge_cs_offset)
+size_t edge_ge_cs_offset(int W2) { return (((size_t)W2 * 128 * 3 + 1) / 2 + 3) / 4 * 4; }
+size_t edge_z_wq_floats(int W2) { return edge_ge_cs_offset(W2) + (size_t)W2; }
 static bool edge_z6w_on() {   // CGAT_EDGE_Z6W=0: the 128-row form of the six-pass per-edge launch (A/B switch)
   static const bool on = [] { const char* e = getenv("CGAT_EDGE_Z6W"); return !(e && e[0] == '0'); }();
   return on;

@@ -142,10 +142,15 @@ int prepare_T_bf16_launch(const float* src, void* dst, int NA, long sa, long sb,
                           hipStream_t stream);
 int prepare_T_bf16_heads_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, int alternate, int heads,
                                 long s_head, long image_floats, hipStream_t stream);
+// the alternate = 1 image whose first H * Hd / 128 blocks hold wA[b] * src[b][c], and cs[h][c] = the signed column sums
+// of head h's scaled rows (the bit-plane form of edge_ge_kernel, edgebwd.hip); one launch
+int prepare_T_bf16_attn_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, const float* wA, int H,
+                               int Hd, float* cs, hipStream_t stream);
 // ---- fused edge pre-activations + attention logits, edgez.hip ----
 bool edge_z_fast(int Ce, int W2, int H, int Hd, long lde, long ld_add, long ldz, const void* e, const void* Pi,
                  const void* Pj, const void* Z, const void* wA);
-size_t edge_z_wq_floats(int W2);
+size_t edge_ge_cs_offset(int W2);  // floats in front of those column sums
+size_t edge_z_wq_floats(int W2);   // the three-plane image, then W2 floats for the column sums of edge_ge's bit-plane form
 // per-edge launch with the x_j projection folded in (f16x3 mode, C == Ce == 128): edgez.hip edge_zx_kernel
 size_t edge_zx_wq_floats(int W2);
 bool edge_zx_fast(int C, int Ce, int W2, int H, int Hd, long ld_add, long ldz, const void* e, const void* x,
@@ -271,6 +276,7 @@ struct EdgeRC {
   const float* wA;        // [HHd]
   const int* dst;         // [E] destination node of slot t
   int H, Hd, HHd, nw;     // nw = W2 / 32
+  const float* cs;        // [H][128], set by the launchers of edge_ge_kernel's bit-plane form (prepare_T_bf16_attn_launch)
 };
 // edge storage mode 3 ("bf16-mma", layers.hip): the per-edge products over the rebuilt gZ rows run ONE bf16 pass
 bool edge_mma_bf16();

@@ -1357,6 +1357,37 @@ extern "C" int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cga
   return CGAT_OK;
 }
 
+// grad edge_attr's product alone, on caller-supplied ingredients of the rebuilt gZ rows (struct EdgeRC, kernels.h), through
+// the launches attn_backward_impl takes for it: the K-group form at few row tiles, the plain launch otherwise
+extern "C" size_t cgat_debug_edge_ge_rebuilt_workspace_bytes(int32_t E, int32_t H, int32_t Hd) {
+  const int W2 = 2 * H * Hd;
+  const int S = edge_ge_ksplit_groups(E, W2);
+  return (edge_z_wq_floats(W2) + 64 + (S > 1 ? (size_t)S * E * 128 : 0)) * sizeof(float);
+}
+extern "C" int cgat_debug_edge_ge_rebuilt(const uint32_t* mask, const float* ga, const float* alpha, const float* gS,
+                                          const float* wA, const int32_t* dst, const float* We, int32_t H, int32_t Hd,
+                                          int32_t E, float* out, void* ws, size_t ws_bytes, void* stream) {
+  const int W2 = 2 * H * Hd;
+  CGAT_CHECK_ARG(mask && ga && alpha && gS && wA && dst && We && out && ws, "debug_edge_ge_rebuilt: null pointer");
+  CGAT_CHECK_ARG(E > 0 && edge_rc_shape(128, H, Hd) && W2 % 256 == 0 && mode_24bit() && !edge_mma_bf16(),
+                 "debug_edge_ge_rebuilt: H = %d, Hd = %d in a 24-bit mode with fp32 edge storage", H, Hd);
+  CGAT_CHECK_ARG(ws_bytes >= cgat_debug_edge_ge_rebuilt_workspace_bytes(E, H, Hd) &&
+                 ((((uintptr_t)gS) | ((uintptr_t)wA) | ((uintptr_t)We) | ((uintptr_t)out) | ((uintptr_t)ws)) & 15) == 0,
+                 "debug_edge_ge_rebuilt: workspace too small or operands not 16-byte aligned");
+  EdgeRC rc = {};
+  rc.mask = mask; rc.ga = ga; rc.alpha = alpha; rc.gS = gS; rc.wA = wA; rc.dst = dst;
+  rc.H = H; rc.Hd = Hd; rc.HHd = H * Hd; rc.nw = W2 / 32;
+  hipStream_t s = (hipStream_t)stream;
+  float* Wq = (float*)ws;
+  float* slabs = Wq + (edge_z_wq_floats(W2) + 63) / 64 * 64;
+  const int S = edge_ge_ksplit_groups(E, W2);
+  if (S > 1) {
+    CGAT_TRY(edge_ge_ksplit_launch(nullptr, 128, (long)E * 128, We, 128, 1, Wq, W2, slabs, nullptr, E, S, s, &rc));
+    return sum_slabs_launch(slabs, S, (long)E * 128, out, (long)E * 128, s);
+  }
+  return edge_ge_launch(nullptr, 128, (long)E * 128, We, 128, 1, Wq, W2, out, 128, nullptr, E, 0, nullptr, s, nullptr, &rc);
+}
+
 extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
                                              const float* edge_attr, const float* saved, const float* g_aggr,
                                              float* g_x, float* g_edge_attr, const cgat_attn_grads* g, void* ws,

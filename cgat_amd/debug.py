@@ -87,3 +87,23 @@ def note_sorted_hidden(weights, plan, hidden):
     share = hidden.shape[1] // len(weights)
     for k, w in enumerate(weights):
         note(w, m[:, k * share:(k + 1) * share])
+
+
+def edge_ge_rebuilt(mask, ga, alpha, gS, wA, dst, We, H, Hd):
+    """grad edge_attr's product alone on caller-supplied ingredients of the rebuilt rows (cgat_debug_edge_ge_rebuilt,
+    include/cgat_hip.h): mask int32 [E, 2 H Hd / 32] bit words, ga / alpha [E, H], gS [N, H Hd], wA [H Hd], dst int32 [E],
+    We [2 H Hd, 128]; returns [E, 128] in slot order."""
+    E, dev = ga.shape[0], ga.device
+    t = [mask.contiguous(), ga.contiguous(), alpha.contiguous(), gS.contiguous(), wA.contiguous(), dst.contiguous(),
+         We.contiguous()]
+    assert t[0].dtype == torch.int32 and t[5].dtype == torch.int32 and all(v.dtype == torch.float32 for v in t[1:5] + t[6:])
+    out = torch.empty(E, 128, dtype=torch.float32, device=dev)
+    from . import ops
+    nbytes = lib.cgat_debug_edge_ge_rebuilt_workspace_bytes(E, H, Hd)
+    ws = ops.workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        check(lib.cgat_debug_edge_ge_rebuilt(*[C.c_void_p(v.data_ptr()) for v in t], H, Hd, E, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(ws.data_ptr()), ws.numel() * ws.element_size(),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              "cgat_debug_edge_ge_rebuilt")
+    return out

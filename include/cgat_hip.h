@@ -189,6 +189,19 @@ int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn_params* p,
 int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cgat_attn_params* p, const float* saved,
                                      uint8_t* mask /* out [E, 2*H*Hd] */, void* stream);
 
+/* Debug / parity instrumentation (tests only): grad edge_attr's product  out[t, :] = gZ[t, :] W_e  ALONE, with the rows of
+ * gZ rebuilt from caller-supplied ingredients exactly as the backward of cgat_nodes_attention_forward rebuilds them,
+ *     gZ[t, (h, c)]          = ga[t, h]    * wA[h, c]           * d      (attention half, columns [0, H*Hd))
+ *     gZ[t, H*Hd + (h, c)]   = alpha[t, h] * gS[dst[t], (h, c)] * d      (message half)
+ * d = 1 where bit (col & 31) of mask[t, col >> 5] is set, 0.01 elsewhere -- through the launches the backward takes for
+ * this product (K groups at few row tiles).  Its error against an fp64 product of the SAME inputs is that of the kernel.
+ * mask [E, 2*H*Hd / 32], ga / alpha [E, H], gS [N, H*Hd], wA [H*Hd], dst [E] (< N), We [2*H*Hd, 128], out [E, 128]
+ * (slot order, no scatter).  24-bit arithmetic modes, Hd a multiple of 128. */
+size_t cgat_debug_edge_ge_rebuilt_workspace_bytes(int32_t E, int32_t H, int32_t Hd);
+int cgat_debug_edge_ge_rebuilt(const uint32_t* mask, const float* ga, const float* alpha, const float* gS,
+                               const float* wA, const int32_t* dst, const float* We, int32_t H, int32_t Hd, int32_t E,
+                               float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- first layer of the message networks alone (vector-attention variants) ---------------
  * hidden[t, :] = LeakyReLU(w_in [x_i ; edge_attr ; x_j] + b_in), t = destination-sorted edge slot (plan.dst_perm),
  * for the stacked first-layer weights w_in [W2, 2C+Ce] of any number of heads / networks: MultiHeadNetwork's
