@@ -261,9 +261,20 @@ int mlp_chain128_launch(const ChainDesc& d, hipStream_t stream);
 #define CHAIN_BATCH_MAX 4
 // n independent chains over the same rows in one launch (24-bit modes; otherwise one launch each)
 int mlp_chain128_batch_launch(const ChainDesc* d, int n, hipStream_t stream);
+// ---- segment backward of the scalar-attention layer, segbwd.hip ----
+// partialW: [edge_seg_bwd_chunks(N)][H * Hd].  The caller has decided the route: vec (16-byte aligned, Hd % 4 == 0), zb_6 /
+// zb (Z stored as bf16 by the six-pass per-edge kernel / at all), rc_shape (sign bits in `mask` instead of gZ),
+// have_scales (f16x3 maxima: gzmax[0..7] zeroed here first) -- one launch, or three small kernels at Hd == 256 with sign bits.
+int edge_seg_bwd_chunks(int N);
+int edge_seg_bwd_launch(const float* Z, float* gZ, long gz_block, const float* alpha, const float* gS, const float* gs,
+                        const int* rowptr, const float* wA_out, int N, int H, int Hd, float* tt, float* ga, float* Gi,
+                        float* partialW, float* gzmax, unsigned* mask, float* gimax, bool vec, bool zb_6, bool zb,
+                        bool rc_shape, bool have_scales, hipStream_t stream);
+// debug: mask[perm[t]][c] = (Z[t][c] > 0), the saved pre-activations' signs in original edge order
+int attn_signs_launch(const float* Z, const int* perm, long E, int W2, uint8_t* mask, hipStream_t stream);
 // ---- split-bf16 backward products over gZ, edgebwd.hip ----
 // The pre-activation gradient of the scalar-attention layer is never stored when its consumers can rebuild it
-// (edge_seg_bwd_kernel step 3, layers.hip): for destination-sorted slot t and column col of the stacked hidden layer
+// (edge_seg_bwd_kernel step 3, segbwd.hip): for destination-sorted slot t and column col of the stacked hidden layer
 //     gZ[t, col] = (ga[t,h]    * wA[col])                 * d      col <  HHd  (attention network, h = col / Hd)
 //                = (alpha[t,h] * gS[dst[t], col - HHd])   * d      col >= HHd  (message network,  h = (col-HHd) / Hd)
 // with d = 1 if Z[t,col] > 0 else 0.01 (LeakyReLU').  Per edge that is 2 H scalars, one bit per column and a row of a

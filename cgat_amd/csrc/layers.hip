@@ -1,5 +1,5 @@
 // Layer orchestrators: the sequence of kernel launches behind each C-ABI entry point.
-// Host code only decides shapes, carves the caller's workspace and enqueues on the caller's
+// Host code only (no kernel lives here): it decides shapes, carves the caller's workspace and enqueues on the caller's
 // stream -- no allocation, no synchronisation.
 #include <string.h>
 
@@ -144,494 +144,32 @@ static int check_ws(const Ctx& c, const char* who) {
   return CGAT_OK;
 }
 
+// "Size, check, run": every entry point that runs an orchestrator measures it with a dry pass, refuses a workspace smaller
+// than that, and runs the real pass with the dry pass' scratch requirement carried over; the size queries return what the
+// dry pass measured.  `impl` is an int(Ctx&) that calls the orchestrator with the entry point's operands.
+template <typename Impl>
+static Ctx dry_pass(Impl&& impl) {
+  Ctx dry(nullptr, 0, true, nullptr);
+  impl(dry);
+  return dry;
+}
+template <typename Impl>
+static size_t dry_total(Impl&& impl) { return dry_pass(impl).total(); }
+template <typename Impl>
+static int run_sized(const char* who, void* ws, size_t ws_bytes, void* stream, Impl&& impl) {
+  const Ctx dry = dry_pass(impl);
+  if (ws_bytes < dry.total()) {
+    cgat_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, dry.total());
+    return CGAT_ERR_WORKSPACE;
+  }
+  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
+  c.scratch_need = dry.scratch_need;
+  return impl(c);
+}
+
 // =======================================================================================
 // GATConvNodes message / softmax / aggregate
 // =======================================================================================
-// In-place-free edge backward: gZ[t, :] from Z[t, :], plus per-chunk partial column sums of
-// g_a * leaky(zA) for the gradient of MH_A.fc_out.weight.
-#define GZ_ROWS 64
-__global__ void edge_gz_kernel(const float* __restrict__ Z, float* __restrict__ gZ, const float* __restrict__ ga,
-                               const float* __restrict__ alpha, const float* __restrict__ gS,
-                               const int* __restrict__ dst, const float* __restrict__ wA_out, int E, int H, int Hd,
-                               float* __restrict__ partial, long gz_block) {
-  const int HHd = H * Hd, W2 = 2 * HHd;
-  const int chunk = blockIdx.x;
-  const int t0 = chunk * GZ_ROWS, t1 = min(E, t0 + GZ_ROWS);
-  for (int col = threadIdx.x; col < W2; col += blockDim.x) {
-    const bool isA = col < HHd;
-    const int cc = isA ? col : col - HHd;
-    const int h = cc / Hd;
-    const float wv = isA ? wA_out[cc] : 0.f;
-    float psum = 0.f;
-    for (int t = t0; t < t1; ++t) {
-      float z = Z[(long)t * W2 + col];
-      float d = z > 0.f ? 1.f : 0.01f;
-      float g;
-      if (isA) {
-        float gav = ga[(long)t * H + h];
-        g = gav * wv * d;
-        psum += gav * (z > 0.f ? z : 0.01f * z);
-      } else {
-        g = alpha[(long)t * H + h] * gS[(long)dst[t] * HHd + cc] * d;
-      }
-      if (gz_block) gZ[(long)(col >> 7) * gz_block + (long)t * 128 + (col & 127)] = g;  // column-block-major
-      else gZ[(long)t * W2 + col] = g;
-    }
-    if (isA) partial[(long)chunk * HHd + cc] = psum;
-  }
-}
-
-// Node-aligned fused edge backward.  One workgroup owns SEGB_NODES consecutive destination
-// segments (whole segments, CSR order), so everything that PyG's softmax/scatter backward needs
-// per destination is local: per node n
-//   1. g_alpha[t,h] = leaky(zM[t,h,:]) . gS[n,h,:] + gs[n,h]            (block reductions)
-//   2. g_a[t,h]     = alpha[t,h] * (g_alpha[t,h] - sum_seg alpha * g_alpha)   (softmax backward)
-//   3. gZ[t,:]      = [ g_a * wA_out * leaky'(zA) | alpha * gS[n] * leaky'(zM) ],
-//      Gi[n,:]      = sum_seg gZ[t,:]   (the x_i-side segment sum),  partial sums of g_a*leaky(zA)
-//      for the gradient of MH_A.fc_out.weight.
-// gS[n] is read once per node instead of gathered per edge; Z is read twice but the second
-// read of a 70 KB segment hits L2.  No atomics; fixed summation order.
-#define SEGB_NODES 8
-#define SEGB_LONG 256   // rows above which the softmax backward of a segment is done by the whole workgroup
-__device__ __forceinline__ float wave_sum_l(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// ZB (with VEC and mask): Z is read as bf16 (the "bf16" edge-storage mode; offsets count elements either way)
-template <bool VEC, bool ZB = false>
-__global__ __launch_bounds__(256) void edge_seg_bwd_kernel(const float* __restrict__ Z, float* __restrict__ gZ,
-                                                           long gz_block, const float* __restrict__ alpha,
-                                                           const float* __restrict__ gS, const float* __restrict__ gs,
-                                                           const int* __restrict__ rowptr,
-                                                           const float* __restrict__ wA_out, int N, int H, int Hd,
-                                                           float* __restrict__ tt, float* __restrict__ ga,
-                                                           float* __restrict__ Gi, float* __restrict__ partialW,
-                                                           float* __restrict__ gzmax, unsigned* __restrict__ mask,
-                                                           float* __restrict__ gimax) {
-  // gimax (optional, VEC path): max |Gi| is folded into gimax[0] the same way -- the scale of the node-side products
-  // mask (optional, VEC path, W2 % 256 == 0): gZ is NOT written; instead bit (col & 31) of mask[t][col >> 5] records
-  // Z[t, col] > 0, from which -- with ga, alpha, gS, wA -- the consumers rebuild the row (struct EdgeRC, kernels.h)
-  // gzmax (optional, VEC path): max |gZ| is folded into gzmax[0] (zeroed before) -- the per-tensor scale the fp16
-  // forms of the two kernels that consume gZ need (edgebwd.hip); a maximum does not depend on the order it is taken in
-  extern __shared__ float pw[];  // [HHd] per-column partial sums of g_a * leaky(zA)
-  float gm = 0.f, gim_max = 0.f;
-  const int HHd = H * Hd, W2 = 2 * HHd;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int c = tid; c < HHd; c += 256) pw[c] = 0.f;
-  const int n0 = blockIdx.x * SEGB_NODES, n1 = min(N, n0 + SEGB_NODES);
-  // The three steps run over ALL segments of the workgroup before the next one starts: two barriers per workgroup
-  // instead of three per node.
-  // With the sign-bit output and Hd = 256 (one float4 of a head per lane) step 1 also produces everything the MESSAGE
-  // half of gZ contributes -- its sign bits, its share of Gi, its maximum: they need alpha only, not the softmax
-  // backward -- so that step 3 reads only the attention half of Z (Z is then read once, not 1.5 times).  A wave owns
-  // head h = wave, wave + 4, ... of EVERY row of a segment, so its lanes accumulate Gi over the rows in the order
-  // step 3 used to (no cross-wave sum).
-  const bool fuse_m = VEC && mask != nullptr && Hd == 256;
-  // ---- 1. g_alpha: one wave per edge row, wave-level reductions only ----
-  if (fuse_m) {
-    for (int n = n0; n < n1; ++n) {
-      const int r0 = rowptr[n], r1 = rowptr[n + 1];
-      if (r1 == r0) continue;                    // (step 3 zero-fills the whole Gi row of an empty segment)
-      for (int h = wave; h < H; h += 4) {
-        const int wcol = HHd + h * Hd + 4 * lane;                            // this lane's four columns of the row
-        const float4 g = *reinterpret_cast<const float4*>(gS + (long)n * HHd + h * Hd + 4 * lane);
-        const float gsn = gs[(long)n * H + h];
-        float4 gim = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int tb = r0; tb < r1; tb += 4) {
-          float4 zv[4];
-          float al[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int t = tb + u < r1 ? tb + u : r1 - 1;
-            zv[u] = ZB ? load4_bf16(reinterpret_cast<const __bf16*>(Z) + (long)t * W2 + wcol)
-                       : *reinterpret_cast<const float4*>(Z + (long)t * W2 + wcol);
-            al[u] = alpha[(long)t * H + h];
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int t = tb + u;
-            if (t < r1) {
-              const float4 z = zv[u];
-              float part = (z.x > 0.f ? z.x : 0.01f * z.x) * g.x + (z.y > 0.f ? z.y : 0.01f * z.y) * g.y +
-                           (z.z > 0.f ? z.z : 0.01f * z.z) * g.z + (z.w > 0.f ? z.w : 0.01f * z.w) * g.w;
-              part = wave_sum_l(part);
-              if (lane == 0) tt[(long)t * H + h] = part + gsn;
-              const float a_ = al[u];
-              const float4 gz = make_float4(a_ * g.x * (z.x > 0.f ? 1.f : 0.01f), a_ * g.y * (z.y > 0.f ? 1.f : 0.01f),
-                                            a_ * g.z * (z.z > 0.f ? 1.f : 0.01f), a_ * g.w * (z.w > 0.f ? 1.f : 0.01f));
-              gm = fmaxf(fmaxf(gm, fmaxf(fabsf(gz.x), fabsf(gz.y))), fmaxf(fabsf(gz.z), fabsf(gz.w)));
-              gim.x += gz.x; gim.y += gz.y; gim.z += gz.z; gim.w += gz.w;
-              unsigned w = ((z.x > 0.f ? 1u : 0u) | (z.y > 0.f ? 2u : 0u) | (z.z > 0.f ? 4u : 0u) | (z.w > 0.f ? 8u : 0u))
-                           << (4 * (lane & 7));
-              w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-              w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-              w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x141, 0xF, 0xF, true);   // row_half_mirror
-              if ((lane & 7) == 0) mask[(long)t * (W2 >> 5) + (wcol >> 5)] = w;
-            }
-          }
-        }
-        *reinterpret_cast<float4*>(Gi + (long)n * W2 + wcol) = gim;
-        gim_max = fmaxf(fmaxf(gim_max, fmaxf(fabsf(gim.x), fabsf(gim.y))), fmaxf(fabsf(gim.z), fabsf(gim.w)));
-      }
-    }
-  } else
-  for (int n = n0; n < n1; ++n) {
-    const int r0 = rowptr[n], r1 = rowptr[n + 1];
-    const float* gSn = gS + (long)n * HHd;
-    for (int t = r0 + wave; t < r1; t += 4) {
-      const float* zM = Z + (long)t * W2 + HHd;
-      for (int h = 0; h < H; ++h) {
-        float part = 0.f;
-        if (VEC) {
-          const float4* z4 = reinterpret_cast<const float4*>(zM + h * Hd);
-          const __bf16* z16 = reinterpret_cast<const __bf16*>(Z) + (long)t * W2 + HHd + h * Hd;
-          const float4* g4 = reinterpret_cast<const float4*>(gSn + h * Hd);
-          for (int j = lane; j < Hd / 4; j += 64) {
-            float4 z = ZB ? load4_bf16(z16 + 4 * j) : z4[j], g = g4[j];
-            part += (z.x > 0.f ? z.x : 0.01f * z.x) * g.x + (z.y > 0.f ? z.y : 0.01f * z.y) * g.y +
-                    (z.z > 0.f ? z.z : 0.01f * z.z) * g.z + (z.w > 0.f ? z.w : 0.01f * z.w) * g.w;
-          }
-        } else {
-          for (int j = lane; j < Hd; j += 64) {
-            float z = zM[h * Hd + j];
-            part += (z > 0.f ? z : 0.01f * z) * gSn[h * Hd + j];
-          }
-        }
-        part = wave_sum_l(part);
-        if (lane == 0) tt[(long)t * H + h] = part + gs[(long)n * H + h];
-      }
-    }
-  }
-  __syncthreads();
-  // ---- 2. softmax backward, one thread per (segment, head) ----
-  if (tid < (n1 - n0) * H) {
-    const int n = n0 + tid / H, h = tid % H;
-    const int r0 = rowptr[n], r1 = rowptr[n + 1];
-    if (r1 - r0 <= SEGB_LONG) {
-      float dot = 0.f;
-      for (int t = r0; t < r1; ++t) dot += alpha[(long)t * H + h] * tt[(long)t * H + h];
-      for (int t = r0; t < r1; ++t) ga[(long)t * H + h] = alpha[(long)t * H + h] * (tt[(long)t * H + h] - dot);
-    }
-  }
-  // a long segment (a hub atom: 20 000 incoming edges in the test): the whole workgroup strides over its rows, the dot
-  // product through wavefront + LDS reductions in a fixed order -- one thread walking 2 x 20 000 dependent loads per
-  // head took milliseconds
-  for (int n = n0; n < n1; ++n) {                  // (uniform: every thread sees the same segment lengths)
-    const int r0 = rowptr[n], r1 = rowptr[n + 1];
-    if (r1 - r0 <= SEGB_LONG) continue;
-    __shared__ float red4[4];
-    for (int h = 0; h < H; ++h) {
-      float dot = 0.f;
-      for (int t = r0 + tid; t < r1; t += 256) dot += alpha[(long)t * H + h] * tt[(long)t * H + h];
-      dot = wave_sum_l(dot);
-      __syncthreads();
-      if (lane == 0) red4[wave] = dot;
-      __syncthreads();
-      dot = (red4[0] + red4[1]) + (red4[2] + red4[3]);
-      for (int t = r0 + tid; t < r1; t += 256) ga[(long)t * H + h] = alpha[(long)t * H + h] * (tt[(long)t * H + h] - dot);
-    }
-  }
-  __syncthreads();
-  // ---- 3. gZ rows, their segment sum, partial sums for grad wA_out (a thread keeps its columns for all segments) ----
-  for (int n = n0; n < n1; ++n) {
-    const int r0 = rowptr[n], r1 = rowptr[n + 1];
-    if (r1 == r0) {  // no incoming edge: zero row of the segment sum
-      for (int c = tid; c < W2; c += 256) Gi[(long)n * W2 + c] = 0.f;
-      continue;
-    }
-    const float* gSn = gS + (long)n * HHd;
-    if (VEC) {  // four consecutive columns per thread (a head boundary is a multiple of 4); rows four at a time
-      for (int c4 = tid; c4 < (fuse_m ? HHd : W2) / 4; c4 += 256) {   // (fuse_m: the message half is done)
-        const int col = 4 * c4;
-        const bool isA = col < HHd;
-        const int cc = isA ? col : col - HHd;
-        const int h = cc / Hd;
-        const float4 wv = isA ? *reinterpret_cast<const float4*>(wA_out + cc) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 gsv = isA ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(gSn + cc);
-        const float* coef = isA ? ga : alpha;
-        float4 gi = make_float4(0.f, 0.f, 0.f, 0.f), ps = gi;
-        // Rows four at a time, the NEXT four loaded before this batch's gZ stores are issued: vmcnt retires in order
-        // and counts stores, so a load issued after a store cannot be waited for without draining that store -- with
-        // load / store / load / ... every batch paid the full write latency.
-        float4 zn[4];
-        float cn[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = r0 + u < r1 ? r0 + u : r1 - 1;
-          zn[u] = ZB ? load4_bf16(reinterpret_cast<const __bf16*>(Z) + (long)t * W2 + col)
-                     : *reinterpret_cast<const float4*>(Z + (long)t * W2 + col);
-          cn[u] = coef[(long)t * H + h];
-        }
-        for (int tb = r0; tb < r1; tb += 4) {
-          float4 zv[4];
-          float cf[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) { zv[u] = zn[u]; cf[u] = cn[u]; }
-          if (tb + 4 < r1) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int t = tb + 4 + u < r1 ? tb + 4 + u : r1 - 1;
-              zn[u] = ZB ? load4_bf16(reinterpret_cast<const __bf16*>(Z) + (long)t * W2 + col)
-                         : *reinterpret_cast<const float4*>(Z + (long)t * W2 + col);
-              cn[u] = coef[(long)t * H + h];
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int t = tb + u;
-            if (t < r1) {
-              const float4 z = zv[u];
-              const float4 d = make_float4(z.x > 0.f ? 1.f : 0.01f, z.y > 0.f ? 1.f : 0.01f, z.z > 0.f ? 1.f : 0.01f,
-                                           z.w > 0.f ? 1.f : 0.01f);
-              float4 g;
-              if (isA) {
-                const float gav = cf[u];
-                g = make_float4(gav * wv.x * d.x, gav * wv.y * d.y, gav * wv.z * d.z, gav * wv.w * d.w);
-                ps.x += gav * z.x * d.x; ps.y += gav * z.y * d.y; ps.z += gav * z.z * d.z; ps.w += gav * z.w * d.w;
-              } else {
-                const float al = cf[u];
-                g = make_float4(al * gsv.x * d.x, al * gsv.y * d.y, al * gsv.z * d.z, al * gsv.w * d.w);
-              }
-              if (mask) {
-                // four sign bits per lane, eight lanes per 32-column word: OR across the eight lanes (two quad
-                // permutations and the half-row mirror), lane 0 of each group stores the word
-                unsigned w = ((z.x > 0.f ? 1u : 0u) | (z.y > 0.f ? 2u : 0u) | (z.z > 0.f ? 4u : 0u) | (z.w > 0.f ? 8u : 0u))
-                             << (4 * (lane & 7));
-                w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-                w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-                w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x141, 0xF, 0xF, true);   // row_half_mirror
-                if ((lane & 7) == 0) mask[(long)t * (W2 >> 5) + (col >> 5)] = w;
-              } else {
-                const long doff = gz_block ? (long)(col >> 7) * gz_block + (long)t * 128 + (col & 127) : (long)t * W2 + col;
-                *reinterpret_cast<float4*>(gZ + doff) = g;
-              }
-              gm = fmaxf(fmaxf(gm, fmaxf(fabsf(g.x), fabsf(g.y))), fmaxf(fabsf(g.z), fabsf(g.w)));
-              gi.x += g.x; gi.y += g.y; gi.z += g.z; gi.w += g.w;
-            }
-          }
-        }
-        *reinterpret_cast<float4*>(Gi + (long)n * W2 + col) = gi;
-        gim_max = fmaxf(fmaxf(gim_max, fmaxf(fabsf(gi.x), fabsf(gi.y))), fmaxf(fabsf(gi.z), fabsf(gi.w)));
-        if (isA) {
-          pw[cc] += ps.x; pw[cc + 1] += ps.y; pw[cc + 2] += ps.z; pw[cc + 3] += ps.w;
-        }
-      }
-    } else {
-      for (int col = tid; col < W2; col += 256) {
-        const bool isA = col < HHd;
-        const int cc = isA ? col : col - HHd;
-        const int h = cc / Hd;
-        const float wv = isA ? wA_out[cc] : 0.f;
-        const float gsv = isA ? 0.f : gSn[cc];
-        float gi = 0.f, ps = 0.f;
-        for (int t = r0; t < r1; ++t) {
-          const float z = Z[(long)t * W2 + col];
-          const float d = z > 0.f ? 1.f : 0.01f;
-          float g;
-          if (isA) {
-            const float gav = ga[(long)t * H + h];
-            g = gav * wv * d;
-            ps += gav * z * d;
-          } else {
-            g = alpha[(long)t * H + h] * gsv * d;
-          }
-          if (gz_block) gZ[(long)(col >> 7) * gz_block + (long)t * 128 + (col & 127)] = g;
-          else gZ[(long)t * W2 + col] = g;
-          gi += g;
-        }
-        Gi[(long)n * W2 + col] = gi;
-        if (isA) pw[cc] += ps;
-      }
-    }
-  }
-  __syncthreads();
-  for (int c = tid; c < HHd; c += 256) partialW[(long)blockIdx.x * HHd + c] = pw[c];
-  if (VEC && gzmax) block_absmax_commit(gm, gzmax);
-  if (VEC && gimax) {
-    __syncthreads();                               // (the commit's staging words are shared by the two calls)
-    block_absmax_commit(gim_max, gimax);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The same backward as THREE small kernels (round 3; sign-bit form at Hd = 256, fp32 Z): the three steps of
-// edge_seg_bwd_kernel talk through global memory anyway (tt, ga), and as one kernel it needs 106 VGPRs -- one wave per SIMD
-// beside the side stream's dT workgroups (2 x 192 VGPRs), i.e. a quarter of its occupancy when the two share a CU.  At
-// <= 64 VGPRs two waves per SIMD fit beside them: the HBM-bound passes over Z then run ON the CUs the matrix-bound
-// contraction occupies instead of beside them on the other half of the chip (DESIGN.md §5 Streams).  Same operations in
-// the same order per output element: results are bit-identical to the one-kernel form.
-//   seg_bwd_msg_kernel   step 1: one wave per (segment, head): g_alpha, the message half's sign bits, its share of Gi
-//   seg_bwd_soft_kernel  step 2: softmax backward per (segment, head)
-//   seg_bwd_att_kernel   step 3: the attention half: sign bits, Gi share, partial sums for grad fc_out_A
-template <bool ZB = false>   // ZB: Z is read as bf16 (the "bf16" edge-storage mode; offsets count elements either way)
-__global__ __launch_bounds__(256, 8) void seg_bwd_msg_kernel(const float* __restrict__ Z, const float* __restrict__ alpha,
-                                                             const float* __restrict__ gS, const float* __restrict__ gs,
-                                                             const int* __restrict__ rowptr, int N, int H,
-                                                             float* __restrict__ tt, float* __restrict__ Gi,
-                                                             float* __restrict__ gzmax, unsigned* __restrict__ mask,
-                                                             float* __restrict__ gimax) {
-  constexpr int Hd = 256;
-  const int HHd = H * Hd, W2 = 2 * HHd;
-  const int tid = threadIdx.x, lane = tid & 63;
-  // wave-uniform values are made SCALAR (readfirstlane): the row index, the segment bounds and every row base address then
-  // live in SGPRs -- as vector values they cost the 30 VGPRs that did not fit under the 64 this kernel is built for
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float gm = 0.f, gim_max = 0.f;
-  const long ntask = (long)N * H;
-  for (long task = (long)blockIdx.x * 4 + wave; task < ntask; task += (long)gridDim.x * 4) {
-    const int n = (int)(task / H), h = (int)(task - (long)n * H);
-    const int r0 = __builtin_amdgcn_readfirstlane(rowptr[n]), r1 = __builtin_amdgcn_readfirstlane(rowptr[n + 1]);
-    if (r1 == r0) continue;                        // (seg_bwd_att_kernel zero-fills the whole Gi row of an empty segment)
-    const int wcol = HHd + h * Hd + 4 * lane;
-    const float4 g = *reinterpret_cast<const float4*>(gS + (long)n * HHd + h * Hd + 4 * lane);
-    const float gsn = gs[(long)n * H + h];
-    float4 gim = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int tb = r0; tb < r1; tb += 4) {
-      float4 zv[4];
-      float al[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = tb + u < r1 ? tb + u : r1 - 1;
-        zv[u] = ZB ? load4_bf16(reinterpret_cast<const __bf16*>(Z) + (long)t * W2 + wcol)
-                   : *reinterpret_cast<const float4*>(Z + (long)t * W2 + wcol);
-        al[u] = alpha[(long)t * H + h];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = tb + u;
-        if (t < r1) {
-          const float4 z = zv[u];
-          float part = (z.x > 0.f ? z.x : 0.01f * z.x) * g.x + (z.y > 0.f ? z.y : 0.01f * z.y) * g.y +
-                       (z.z > 0.f ? z.z : 0.01f * z.z) * g.z + (z.w > 0.f ? z.w : 0.01f * z.w) * g.w;
-          part = wave_sum_l(part);
-          if (lane == 0) tt[(long)t * H + h] = part + gsn;
-          const float a_ = al[u];
-          const float4 gz = make_float4(a_ * g.x * (z.x > 0.f ? 1.f : 0.01f), a_ * g.y * (z.y > 0.f ? 1.f : 0.01f),
-                                        a_ * g.z * (z.z > 0.f ? 1.f : 0.01f), a_ * g.w * (z.w > 0.f ? 1.f : 0.01f));
-          gm = fmaxf(fmaxf(gm, fmaxf(fabsf(gz.x), fabsf(gz.y))), fmaxf(fabsf(gz.z), fabsf(gz.w)));
-          gim.x += gz.x; gim.y += gz.y; gim.z += gz.z; gim.w += gz.w;
-          unsigned w = ((z.x > 0.f ? 1u : 0u) | (z.y > 0.f ? 2u : 0u) | (z.z > 0.f ? 4u : 0u) | (z.w > 0.f ? 8u : 0u))
-                       << (4 * (lane & 7));
-          w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-          w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-          w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x141, 0xF, 0xF, true);   // row_half_mirror
-          if ((lane & 7) == 0) mask[(long)t * (W2 >> 5) + (wcol >> 5)] = w;
-        }
-      }
-    }
-    *reinterpret_cast<float4*>(Gi + (long)n * W2 + wcol) = gim;
-    gim_max = fmaxf(fmaxf(gim_max, fmaxf(fabsf(gim.x), fabsf(gim.y))), fmaxf(fabsf(gim.z), fabsf(gim.w)));
-  }
-  if (gzmax) block_absmax_commit(gm, gzmax);
-  if (gimax) {
-    __syncthreads();                               // (the commit's staging words are shared by the two calls)
-    block_absmax_commit(gim_max, gimax);
-  }
-}
-
-__global__ __launch_bounds__(256, 8) void seg_bwd_soft_kernel(const float* __restrict__ alpha, const float* __restrict__ tt,
-                                                              const int* __restrict__ rowptr, int N, int H,
-                                                              float* __restrict__ ga) {
-  __shared__ float red4[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n0 = blockIdx.x * SEGB_NODES, n1 = min(N, n0 + SEGB_NODES);
-  if (tid < (n1 - n0) * H) {
-    const int n = n0 + tid / H, h = tid % H;
-    const int r0 = rowptr[n], r1 = rowptr[n + 1];
-    if (r1 - r0 <= SEGB_LONG) {
-      float dot = 0.f;
-      for (int t = r0; t < r1; ++t) dot += alpha[(long)t * H + h] * tt[(long)t * H + h];
-      for (int t = r0; t < r1; ++t) ga[(long)t * H + h] = alpha[(long)t * H + h] * (tt[(long)t * H + h] - dot);
-    }
-  }
-  for (int n = n0; n < n1; ++n) {                  // long segments: the whole workgroup (see edge_seg_bwd_kernel)
-    const int r0 = rowptr[n], r1 = rowptr[n + 1];
-    if (r1 - r0 <= SEGB_LONG) continue;
-    for (int h = 0; h < H; ++h) {
-      float dot = 0.f;
-      for (int t = r0 + tid; t < r1; t += 256) dot += alpha[(long)t * H + h] * tt[(long)t * H + h];
-      dot = wave_sum_l(dot);
-      __syncthreads();
-      if (lane == 0) red4[wave] = dot;
-      __syncthreads();
-      dot = (red4[0] + red4[1]) + (red4[2] + red4[3]);
-      for (int t = r0 + tid; t < r1; t += 256) ga[(long)t * H + h] = alpha[(long)t * H + h] * (tt[(long)t * H + h] - dot);
-    }
-  }
-}
-
-template <bool ZB = false>
-__global__ __launch_bounds__(256, 8) void seg_bwd_att_kernel(const float* __restrict__ Z, const float* __restrict__ ga,
-                                                             const int* __restrict__ rowptr,
-                                                             const float* __restrict__ wA_out, int N, int H,
-                                                             float* __restrict__ Gi, float* __restrict__ partialW,
-                                                             float* __restrict__ gzmax, unsigned* __restrict__ mask,
-                                                             float* __restrict__ gimax) {
-  constexpr int Hd = 256;
-  extern __shared__ float pw[];                    // [HHd] per-column partial sums of g_a * leaky(zA)
-  const int HHd = H * Hd, W2 = 2 * HHd;
-  const int tid = threadIdx.x, lane = tid & 63;
-  float gm = 0.f, gim_max = 0.f;
-  for (int c = tid; c < HHd; c += 256) pw[c] = 0.f;
-  __syncthreads();
-  const int n0 = blockIdx.x * SEGB_NODES, n1 = min(N, n0 + SEGB_NODES);
-  for (int n = n0; n < n1; ++n) {
-    const int r0 = __builtin_amdgcn_readfirstlane(rowptr[n]), r1 = __builtin_amdgcn_readfirstlane(rowptr[n + 1]);
-    if (r1 == r0) {  // no incoming edge: zero row of the segment sum (both halves)
-      for (int c = tid; c < W2; c += 256) Gi[(long)n * W2 + c] = 0.f;
-      continue;
-    }
-    for (int c4 = tid; c4 < HHd / 4; c4 += 256) {
-      const int col = 4 * c4;
-      const int h = col / Hd;
-      const float4 wv = *reinterpret_cast<const float4*>(wA_out + col);
-      float4 gi = make_float4(0.f, 0.f, 0.f, 0.f), ps = gi;
-      for (int tb = r0; tb < r1; tb += 4) {
-        float4 zv[4];
-        float cf[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = tb + u < r1 ? tb + u : r1 - 1;
-          zv[u] = ZB ? load4_bf16(reinterpret_cast<const __bf16*>(Z) + (long)t * W2 + col)
-                     : *reinterpret_cast<const float4*>(Z + (long)t * W2 + col);
-          cf[u] = ga[(long)t * H + h];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = tb + u;
-          if (t < r1) {
-            const float4 z = zv[u];
-            const float4 d = make_float4(z.x > 0.f ? 1.f : 0.01f, z.y > 0.f ? 1.f : 0.01f, z.z > 0.f ? 1.f : 0.01f,
-                                         z.w > 0.f ? 1.f : 0.01f);
-            const float gav = cf[u];
-            const float4 g = make_float4(gav * wv.x * d.x, gav * wv.y * d.y, gav * wv.z * d.z, gav * wv.w * d.w);
-            ps.x += gav * z.x * d.x; ps.y += gav * z.y * d.y; ps.z += gav * z.z * d.z; ps.w += gav * z.w * d.w;
-            unsigned w = ((z.x > 0.f ? 1u : 0u) | (z.y > 0.f ? 2u : 0u) | (z.z > 0.f ? 4u : 0u) | (z.w > 0.f ? 8u : 0u))
-                         << (4 * (lane & 7));
-            w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-            w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-            w |= (unsigned)__builtin_amdgcn_mov_dpp((int)w, 0x141, 0xF, 0xF, true);   // row_half_mirror
-            if ((lane & 7) == 0) mask[(long)t * (W2 >> 5) + (col >> 5)] = w;
-            gm = fmaxf(fmaxf(gm, fmaxf(fabsf(g.x), fabsf(g.y))), fmaxf(fabsf(g.z), fabsf(g.w)));
-            gi.x += g.x; gi.y += g.y; gi.z += g.z; gi.w += g.w;
-          }
-        }
-      }
-      *reinterpret_cast<float4*>(Gi + (long)n * W2 + col) = gi;
-      gim_max = fmaxf(fmaxf(gim_max, fmaxf(fabsf(gi.x), fabsf(gi.y))), fmaxf(fabsf(gi.z), fabsf(gi.w)));
-      pw[col] += ps.x; pw[col + 1] += ps.y; pw[col + 2] += ps.z; pw[col + 3] += ps.w;
-    }
-  }
-  __syncthreads();
-  for (int c = tid; c < HHd; c += 256) partialW[(long)blockIdx.x * HHd + c] = pw[c];
-  if (gzmax) block_absmax_commit(gm, gzmax);
-  if (gimax) {
-    __syncthreads();
-    block_absmax_commit(gim_max, gimax);
-  }
-}
-
 struct AttnDims {
   int N, E, C, Ce, H, Hd, D, HHd, W2;
 };
@@ -970,7 +508,7 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
                               const float* saved, const float* g_aggr, float* g_x, float* g_e,
                               const cgat_attn_grads* gr) {
   const AttnDims d = attn_dims(plan, p);
-  const int chunks = cdiv(d.N > 0 ? d.N : 1, SEGB_NODES);  // workgroups of the fused segment kernel
+  const int chunks = edge_seg_bwd_chunks(d.N);  // workgroups of the fused segment kernel
   float* Wcat = c.take<float>((size_t)d.W2 * d.D);
   float* gWcat = c.take<float>((size_t)d.W2 * d.D);
   float* gbcat = c.take<float>((size_t)d.W2);
@@ -1068,13 +606,9 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
   // grad fc_out_A, all per whole destination segment in one pass (edge_seg_bwd_kernel)
   bool have_scales = false, zb = false;
   if (!c.dry && d.N > 0) {
-    CGAT_CHECK_ARG(d.H <= 16, "nodes_attention_backward: more than 16 heads");
-    CGAT_PROF("edge_seg_bwd", c.s);
-    size_t shm = (size_t)d.HHd * sizeof(float);
     const bool vec = (d.Hd % 4 == 0) && ((((uintptr_t)sv.Z) | ((uintptr_t)gZ) | ((uintptr_t)gS) | ((uintptr_t)Gi) |
                                           ((uintptr_t)p->A_out_w)) & 15) == 0;
     have_scales = vec && mode_f16() && d.Ce == 128 && (((uintptr_t)e) & 15) == 0;
-    if (have_scales) CGAT_TRY(fill_launch(scales, 0.f, 8, c.s));
     // the forward stored Z as bf16 under exactly this predicate (same tensors, same alignment)
     const bool zb_x = attn_bf16(d) && mode_f16() &&
                       edge_zx_fast(d.C, d.Ce, d.W2, d.H, d.Hd, d.W2, d.W2, e, x, Gi, sv.Z, p->A_out_w) &&
@@ -1090,41 +624,11 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
       CGAT_CHECK_ARG(vec && (((uintptr_t)e) & 15) == 0,
                      "nodes_attention_backward: saved, edge_attr and MH_A.fc_out.weight must be 16-byte aligned at these widths");
     unsigned* mask = rc_shape ? reinterpret_cast<unsigned*>(gZ) : nullptr;
-    float* gzmax = have_scales ? scales : (float*)nullptr;
+    float* gzmax = have_scales ? scales : nullptr;
     // [2] max |Gi|, [3] max |Gj|, [4] max |x|: with them the node-side products run in the fp16 form too (rebuilt path)
-    float* gimax = (have_scales && rc_shape) ? scales + 2 : (float*)nullptr;
-    if (zb_6) {
-      CGAT_CHECK_ARG(vec && mask && d.Hd == 256, "nodes_attention_backward: the bf16 edge storage needs the vector form");
-      const long tasks = (long)d.N * d.H;
-      hipLaunchKernelGGL(seg_bwd_msg_kernel<true>, dim3((unsigned)cdiv(tasks, 4)), dim3(256), 0, c.s, sv.Z, sv.alpha, gS, gs,
-                         plan->dst_rowptr, d.N, d.H, tt, Gi, gzmax, mask, gimax);
-      CGAT_LAUNCH_CHECK();
-      hipLaunchKernelGGL(seg_bwd_soft_kernel, dim3(chunks), dim3(256), 0, c.s, sv.alpha, tt, plan->dst_rowptr, d.N, d.H, ga);
-      CGAT_LAUNCH_CHECK();
-      hipLaunchKernelGGL(seg_bwd_att_kernel<true>, dim3(chunks), dim3(256), shm, c.s, sv.Z, ga, plan->dst_rowptr, p->A_out_w,
-                         d.N, d.H, Gi, partial, gzmax, mask, gimax);
-    } else if (zb) {
-      CGAT_CHECK_ARG(rc_shape && have_scales, "nodes_attention_backward: the bf16 edge storage needs the vector form");
-      hipLaunchKernelGGL((edge_seg_bwd_kernel<true, true>), dim3(chunks), dim3(256), shm, c.s, sv.Z, gZ, gzb, sv.alpha, gS, gs,
-                         plan->dst_rowptr, p->A_out_w, d.N, d.H, d.Hd, tt, ga, Gi, partial, gzmax, mask, gimax);
-    } else if (vec && mask && d.Hd == 256) {
-      // three small kernels (<= 64 VGPRs: they co-reside with the side stream's dT workgroups); bit-identical results
-      const long tasks = (long)d.N * d.H;
-      hipLaunchKernelGGL(seg_bwd_msg_kernel<false>, dim3((unsigned)cdiv(tasks, 4)), dim3(256), 0, c.s, sv.Z, sv.alpha, gS, gs,
-                         plan->dst_rowptr, d.N, d.H, tt, Gi, gzmax, mask, gimax);
-      CGAT_LAUNCH_CHECK();
-      hipLaunchKernelGGL(seg_bwd_soft_kernel, dim3(chunks), dim3(256), 0, c.s, sv.alpha, tt, plan->dst_rowptr, d.N, d.H, ga);
-      CGAT_LAUNCH_CHECK();
-      hipLaunchKernelGGL(seg_bwd_att_kernel<false>, dim3(chunks), dim3(256), shm, c.s, sv.Z, ga, plan->dst_rowptr, p->A_out_w, d.N,
-                         d.H, Gi, partial, gzmax, mask, gimax);
-    } else if (vec)
-      hipLaunchKernelGGL(edge_seg_bwd_kernel<true>, dim3(chunks), dim3(256), shm, c.s, sv.Z, gZ, gzb, sv.alpha, gS, gs,
-                         plan->dst_rowptr, p->A_out_w, d.N, d.H, d.Hd, tt, ga, Gi, partial, gzmax, mask, gimax);
-    else
-      hipLaunchKernelGGL(edge_seg_bwd_kernel<false>, dim3(chunks), dim3(256), shm, c.s, sv.Z, gZ, gzb, sv.alpha, gS, gs,
-                         plan->dst_rowptr, p->A_out_w, d.N, d.H, d.Hd, tt, ga, Gi, partial, (float*)nullptr,
-                         (unsigned*)nullptr, (float*)nullptr);
-    CGAT_LAUNCH_CHECK();
+    float* gimax = (have_scales && rc_shape) ? scales + 2 : nullptr;
+    CGAT_TRY(edge_seg_bwd_launch(sv.Z, gZ, gzb, sv.alpha, gS, gs, plan->dst_rowptr, p->A_out_w, d.N, d.H, d.Hd, tt, ga, Gi,
+                                 partial, gzmax, mask, gimax, vec, zb_6, zb, rc_shape, have_scales, c.s));
   }
   EdgeRC rc = {};
   if (rc_shape && !c.dry) {
@@ -1237,27 +741,24 @@ static int hidden_check(const cgat_plan* plan, int C, int Ce, int W2) {
   return CGAT_OK;
 }
 extern "C" size_t cgat_edge_hidden_forward_workspace_bytes(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2) {
-  Ctx c(nullptr, 0, true, nullptr);
-  edge_hidden_forward_impl(c, plan, hidden_dims(plan, C, Ce, W2), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  return c.total();
+  return dry_total([&](Ctx& c) {
+    return edge_hidden_forward_impl(c, plan, hidden_dims(plan, C, Ce, W2), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  });
 }
 extern "C" size_t cgat_edge_hidden_backward_workspace_bytes(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2) {
-  Ctx c(nullptr, 0, true, nullptr);
-  edge_hidden_backward_impl(c, plan, hidden_dims(plan, C, Ce, W2), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr);
-  return c.total();
+  return dry_total([&](Ctx& c) {
+    return edge_hidden_backward_impl(c, plan, hidden_dims(plan, C, Ce, W2), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, nullptr);
+  });
 }
 extern "C" int cgat_edge_hidden_forward(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, const float* w_in,
                                         const float* b_in, const float* x, const float* edge_attr, float* hidden,
                                         float* hidden_absmax, void* ws, size_t ws_bytes, void* stream) {
   CGAT_TRY(hidden_check(plan, C, Ce, W2));
   if (hidden_absmax) CGAT_TRY(fill_launch(hidden_absmax, 0.f, 1, (hipStream_t)stream));
-  if (ws_bytes < cgat_edge_hidden_forward_workspace_bytes(plan, C, Ce, W2)) {
-    cgat_set_error("edge_hidden_forward: workspace too small");
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  return edge_hidden_forward_impl(c, plan, hidden_dims(plan, C, Ce, W2), w_in, b_in, x, edge_attr, hidden, hidden_absmax);
+  return run_sized("edge_hidden_forward", ws, ws_bytes, stream, [&](Ctx& c) {
+    return edge_hidden_forward_impl(c, plan, hidden_dims(plan, C, Ce, W2), w_in, b_in, x, edge_attr, hidden, hidden_absmax);
+  });
 }
 extern "C" int cgat_edge_hidden_backward(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, const float* w_in,
                                          const float* x, const float* edge_attr, const float* hidden,
@@ -1265,13 +766,11 @@ extern "C" int cgat_edge_hidden_backward(const cgat_plan* plan, int32_t C, int32
                                          float* g_edge_attr, float* g_w_in, float* g_b_in, void* ws, size_t ws_bytes,
                                          void* stream) {
   CGAT_TRY(hidden_check(plan, C, Ce, W2));
-  if (ws_bytes < cgat_edge_hidden_backward_workspace_bytes(plan, C, Ce, W2)) {
-    cgat_set_error("edge_hidden_backward: workspace too small");
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  return edge_hidden_backward_impl(c, plan, hidden_dims(plan, C, Ce, W2), w_in, x, edge_attr, hidden, g_hidden, g_x,
-                                   g_edge_attr, g_w_in, g_b_in, g_is_pre, gpre_absmax);
+  // (sized as cgat_edge_hidden_backward_workspace_bytes sizes it, i.e. with a gZ buffer, whatever g_is_pre says)
+  return run_sized("edge_hidden_backward", ws, ws_bytes, stream, [&](Ctx& c) {
+    return edge_hidden_backward_impl(c, plan, hidden_dims(plan, C, Ce, W2), w_in, x, edge_attr, hidden, g_hidden, g_x,
+                                     g_edge_attr, g_w_in, g_b_in, c.dry ? 0 : g_is_pre, gpre_absmax);
+  });
 }
 
 static int attn_check(const cgat_plan* plan, const cgat_attn_params* p) {
@@ -1283,63 +782,33 @@ static int attn_check(const cgat_plan* plan, const cgat_attn_params* p) {
 }
 
 extern "C" size_t cgat_nodes_attention_forward_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p) {
-  Ctx c(nullptr, 0, true, nullptr);
-  attn_forward_impl(c, plan, p, nullptr, nullptr, nullptr, nullptr);
-  return c.total();
+  return dry_total([&](Ctx& c) { return attn_forward_impl(c, plan, p, nullptr, nullptr, nullptr, nullptr); });
 }
 extern "C" size_t cgat_nodes_attention_backward_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p) {
-  Ctx c(nullptr, 0, true, nullptr);
   cgat_attn_grads g = {};
-  attn_backward_impl(c, plan, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g);
-  return c.total();
+  return dry_total([&](Ctx& c) { return attn_backward_impl(c, plan, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g); });
 }
 extern "C" int cgat_nodes_attention_forward(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
                                             const float* edge_attr, float* aggr, float* saved, void* ws,
                                             size_t ws_bytes, void* stream) {
   CGAT_TRY(attn_check(plan, p));
-  {
-    Ctx dry(nullptr, 0, true, nullptr);
-    attn_forward_impl(dry, plan, p, nullptr, nullptr, nullptr, nullptr);
-    if (ws_bytes < dry.total()) {
-      cgat_set_error("nodes_attention_forward: workspace too small (%zu < %zu)", ws_bytes, dry.total());
-      return CGAT_ERR_WORKSPACE;
-    }
-    Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-    c.scratch_need = dry.scratch_need;
-    return attn_forward_impl(c, plan, p, x, edge_attr, aggr, saved);
-  }
+  return run_sized("nodes_attention_forward", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return attn_forward_impl(c, plan, p, x, edge_attr, aggr, saved); });
 }
 extern "C" int32_t cgat_nodes_attention_infer_fused(const cgat_plan* plan, const cgat_attn_params* p) {
   if (attn_check(plan, p) != CGAT_OK) return 0;
   return attn_infer_fused(attn_dims(plan, p)) ? 1 : 0;
 }
 extern "C" size_t cgat_nodes_attention_infer_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p) {
-  Ctx c(nullptr, 0, true, nullptr);
-  attn_forward_impl(c, plan, p, nullptr, nullptr, nullptr, nullptr, true);
-  return c.total();
+  return dry_total([&](Ctx& c) { return attn_forward_impl(c, plan, p, nullptr, nullptr, nullptr, nullptr, true); });
 }
 extern "C" int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
                                           const float* edge_attr, float* aggr, void* ws, size_t ws_bytes, void* stream) {
   CGAT_TRY(attn_check(plan, p));
-  Ctx dry(nullptr, 0, true, nullptr);
-  attn_forward_impl(dry, plan, p, nullptr, nullptr, nullptr, nullptr, true);
-  if (ws_bytes < dry.total()) {
-    cgat_set_error("nodes_attention_infer: workspace too small (%zu < %zu)", ws_bytes, dry.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  c.scratch_need = dry.scratch_need;
-  return attn_forward_impl(c, plan, p, x, edge_attr, aggr, nullptr, true);
+  return run_sized("nodes_attention_infer", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return attn_forward_impl(c, plan, p, x, edge_attr, aggr, nullptr, true); });
 }
 // ---- debug: the sign pattern of the saved pre-activations in original edge order (include/cgat_hip.h) ----
-__global__ void attn_signs_kernel(const float* __restrict__ Z, const int* __restrict__ perm, long E, int W2,
-                                  uint8_t* __restrict__ mask) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= E * W2) return;
-  const long t = i / W2;
-  const int c = (int)(i - t * W2);
-  mask[(long)perm[t] * W2 + c] = Z[i] > 0.f ? 1 : 0;
-}
 extern "C" int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cgat_attn_params* p, const float* saved,
                                                 uint8_t* mask, void* stream) {
   CGAT_TRY(attn_check(plan, p));
@@ -1349,12 +818,7 @@ extern "C" int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cga
     cgat_set_error("debug_nodes_attention_signs: fp32 edge storage only");
     return CGAT_ERR_UNSUPPORTED;
   }
-  const long n = (long)d.E * d.W2;
-  if (n == 0) return CGAT_OK;
-  hipLaunchKernelGGL(attn_signs_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, saved,
-                     plan->dst_perm, (long)d.E, d.W2, mask);
-  CGAT_LAUNCH_CHECK();
-  return CGAT_OK;
+  return attn_signs_launch(saved, plan->dst_perm, (long)d.E, d.W2, mask, (hipStream_t)stream);
 }
 
 // grad edge_attr's product alone, on caller-supplied ingredients of the rebuilt gZ rows (struct EdgeRC, kernels.h), through
@@ -1394,15 +858,9 @@ extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_a
                                              size_t ws_bytes, void* stream) {
   CGAT_TRY(attn_check(plan, p));
   CGAT_CHECK_ARG(g, "nodes_attention_backward: null grads");
-  Ctx dry(nullptr, 0, true, nullptr);
-  attn_backward_impl(dry, plan, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, g);
-  if (ws_bytes < dry.total()) {
-    cgat_set_error("nodes_attention_backward: workspace too small (%zu < %zu)", ws_bytes, dry.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  c.scratch_need = dry.scratch_need;
-  return attn_backward_impl(c, plan, p, x, edge_attr, saved, g_aggr, g_x, g_edge_attr, g);
+  return run_sized("nodes_attention_backward", ws, ws_bytes, stream, [&](Ctx& c) {
+    return attn_backward_impl(c, plan, p, x, edge_attr, saved, g_aggr, g_x, g_edge_attr, g);
+  });
 }
 
 // =======================================================================================
@@ -1432,118 +890,6 @@ static int hnet_check(int rows, const cgat_hnet_params* p) {
   return CGAT_OK;
 }
 
-static int hnet_forward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const float* h0, const float* v, float* y,
-                             float* saved) {
-  const int W = p->W;
-  const size_t WW = (size_t)W * W;
-  // the re-laid T of every predicted layer, prepared up front in two launches where the batched form exists (f16x3, f16x3c)
-  const size_t Tfl = bilinear_T_floats(W, W, W);
-  const bool batch_T = W == 128 && mode_f16_T() && p->n_hyper <= TPREP_MAX;
-  float* Tp = c.take<float>((batch_T ? (size_t)p->n_hyper : 1) * Tfl);
-  float* Tpart = c.take<float>(bilinear_prepare_T_batch_ws_floats(p->n_hyper));
-  const bool batch_w = W == 128 && p->n_hyper * (p->n_fc + 2) <= WPREP_MAX;
-  if (batch_w) { c.wprep_reserve(p->n_hyper * (p->n_fc + 2)); c.tprep_reserve(2 * p->n_hyper); }
-  c.seal();
-  bool T_ready = false;
-  if (batch_T && !c.dry) {
-    const float* tsrc[TPREP_MAX];
-    float* tdst[TPREP_MAX];
-    for (int l = 0; l < p->n_hyper; ++l) { tsrc[l] = p->layer[l].head_w; tdst[l] = Tp + (size_t)l * Tfl; }
-    const int rc_ = bilinear_prepare_T_batch(p->n_hyper, tsrc, tdst, W, W, W, 1, 2, 0, Tpart, c.s);
-    if (rc_ == CGAT_OK) T_ready = true;
-    else if (rc_ != CGAT_ERR_UNSUPPORTED) return rc_;
-  }
-  if (batch_w) {   // every dense-layer weight of the pass, prepared in one launch (forward orientation [out][in])
-    for (int l = 0; l < p->n_hyper; ++l) {
-      for (int s = 0; s < p->n_fc; ++s) c.wprep_add(p->layer[l].fc_w[s], W, 1);
-      if (mode_f16()) c.wprep_add(p->layer[l].head_b, W, 1);   // read by linear128_launch in that mode only
-      else c.tprep_add(p->layer[l].head_b, W, 1);                        // (the 24-bit modes: the dense-layer kernel's image)
-      c.wprep_add(p->layer[l].head_w + WW * W, W, 1);
-    }
-    CGAT_TRY(c.wprep_run());
-    CGAT_TRY(c.tprep_run());
-  }
-  HnetSaved sv = hnet_saved(saved, rows, p);
-  const float* hin = h0;
-  if (p->damping) {
-    RUN(mix_launch(h0, v, p->damping, sv.hin(), (long)rows * W, c.s));
-    hin = sv.hin();
-  }
-  // The trunk (n_fc x [Linear + Tanh]) and the trunk-side linear term of the head, u = z @ U^T + b0, as ONE chain per
-  // predicted layer (chain.hip) when the weights of the pass have been prepared in a batch (width 128, <= 4 trunk layers)
-  // -- and, since every predicted layer's trunk reads the same hyper input, the chains of ALL predicted layers as ONE
-  // launch (round 5); the remaining linear term u += vin @ Bm^T follows per layer.  Bm = head_b[:W*W] as [o,i],
-  // U = head_w[W*W:]
-  bool chained_all = false;
-  if (batch_w && !c.dry && wprep_image_floats() != 0 && p->n_fc + 1 <= CHAIN_MAX && p->n_hyper <= CGAT_MAX_HYPER) {
-    ChainDesc cds[CGAT_MAX_HYPER];
-    bool ok = true;
-    for (int l = 0; l < p->n_hyper; ++l) {
-      const cgat_hyperlinear_params& L = p->layer[l];
-      ChainDesc& cd = cds[l];
-      memset(&cd, 0, sizeof(cd));
-      cd.n_layers = p->n_fc + 1; cd.rows = rows; cd.x = hin; cd.ldx = W;
-      for (int s = 0; s < p->n_fc; ++s) {
-        ChainLayer& cl = cd.layer[s];
-        cl.W = (const uint4*)c.wprep_find(L.fc_w[s], W, 1);
-        cl.bias = L.fc_b[s]; cl.act = CGAT_ACT_TANH; cl.out = sv.act(l, s); cl.ld_out = W;
-        ok = ok && cl.W;
-      }
-      ChainLayer& cu = cd.layer[p->n_fc];
-      cu.W = (const uint4*)c.wprep_find(L.head_w + WW * W, W, 1);
-      cu.bias = L.head_b + WW; cu.act = CGAT_ACT_NONE; cu.out = (l == p->n_hyper - 1) ? y : sv.u(l); cu.ld_out = W;
-      ok = ok && cu.W && mlp_chain128_fast(cd);
-    }
-    if (ok) {
-      for (int l0 = 0; l0 < p->n_hyper; l0 += CHAIN_BATCH_MAX)
-        CGAT_TRY(mlp_chain128_batch_launch(cds + l0, p->n_hyper - l0 < CHAIN_BATCH_MAX ? p->n_hyper - l0 : CHAIN_BATCH_MAX, c.s));
-      chained_all = true;
-    }
-  }
-  const float* vin = v;
-  for (int l = 0; l < p->n_hyper; ++l) {
-    const cgat_hyperlinear_params& L = p->layer[l];
-    float* u = c.dry ? nullptr : ((l == p->n_hyper - 1) ? y : sv.u(l));
-    const float* z = c.dry ? nullptr : sv.act(l, p->n_fc - 1);
-    bool chained = false;
-    if (chained_all) {
-      GemmParams g = gemm_params(rows, W, W, vin, W, L.head_b, W, u, W);
-      g.beta = 1.f;
-      CGAT_TRY(c.gemm(g));
-      chained = true;
-    }
-    if (!chained) {
-      const float* t = hin;
-      for (int s = 0; s < p->n_fc; ++s) {  // trunk: Linear + Tanh
-        GemmParams g = gemm_params(rows, W, W, t, W, L.fc_w[s], W, c.dry ? nullptr : sv.act(l, s), W);
-        g.bias = L.fc_b[s];
-        g.act = CGAT_ACT_TANH;
-        CGAT_TRY(c.gemm(g));
-        t = c.dry ? nullptr : sv.act(l, s);
-      }
-      // bias-row terms of the head:  u = vin @ Bm^T + z @ U^T + b0
-      GemmParams g = gemm_params(rows, W, W, vin, W, L.head_b, W, u, W);
-      CGAT_TRY(c.gemm(g));
-      g = gemm_params(rows, W, W, z, W, L.head_w + WW * W, W, u, W);
-      g.bias = L.head_b + WW;
-      g.beta = 1.f;
-      CGAT_TRY(c.gemm(g));
-    }
-    // trilinear term with T[o,i,k] = head_w[(o*W+i)*W + k] re-laid as Tp[i,k,o]
-    float* Tl = Tp + (T_ready ? (size_t)l * Tfl : 0);
-    if (!T_ready) RUN(bilinear_prepare_T(L.head_w, Tl, W, W, W, 1, 2, 0, c.s));
-    // (+ LayerNorm + tanh of every layer but the last, fused into the contraction's slab sum at width 128)
-    const bool ln = l < p->n_hyper - 1;
-    const bool ln_fused = ln && W == 128;
-    CGAT_TRY(c.bilinear(vin, W, z, W, Tl, u, W, u, W, rows, W, W, W, (ln_fused && !c.dry) ? sv.vin(l + 1) : nullptr, 1e-5f));
-    if (ln) {
-      if (!ln_fused) RUN(layernorm_tanh_fwd_launch(u, sv.vin(l + 1), rows, W, 1e-5f, c.s));
-      vin = c.dry ? nullptr : sv.vin(l + 1);
-    }
-  }
-  return check_ws(c, "hnet_forward");
-}
-
 // `side`: optional second stream + workspace.  The four dT contractions (the weight-gradient kernel and its operand
 // preparation) feed nothing else in the backward pass, and they are matrix-core bound while what follows them (the
 // attention backward of the layer) is HBM bound: issued on the side stream they run beside it (measured in isolation:
@@ -1569,315 +915,482 @@ static HnetSideLayout hnet_side_layout(int rows, const cgat_hnet_params* p) {
   L.total = L.wgrad + bilinear_wgrad_batch_ws_bytes(p->n_hyper, rows, p->W, p->W, p->W) + 256;
   return L;
 }
-static size_t hnet_side_ws_bytes(int rows, const cgat_hnet_params* p) { return hnet_side_layout(rows, p).total; }
-static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const float* h0, const float* v,
-                              const float* saved, const float* g_y, float* g_h0, float* g_v,
-                              const cgat_hnet_grads* gr, const HnetSide* side = nullptr) {
+
+// Makes `waiter` wait for everything issued on `signaller` so far.  Events come from a small ring created lazily and
+// never destroyed: under a hipGraph capture (cgat_amd.GraphedStep) the captured dependency keeps referring to the event
+// object, and destroying it right after the wait -- legal in eager mode -- crashed hipStreamEndCapture on the second
+// capture of a process.
+static hipEvent_t g_wait_ring[64];
+static unsigned g_wait_next = 0, g_wait_made = 0;
+static int stream_wait_stream(hipStream_t waiter, hipStream_t signaller) {
+  const unsigned slot = g_wait_next++ % 64;
+  if (slot >= g_wait_made) {
+    CGAT_HIP(hipEventCreateWithFlags(&g_wait_ring[slot], hipEventDisableTiming));
+    g_wait_made = slot + 1;
+  }
+  CGAT_HIP(hipEventRecord(g_wait_ring[slot], signaller));
+  CGAT_HIP(hipStreamWaitEvent(waiter, g_wait_ring[slot], 0));
+  return CGAT_OK;
+}
+
+// The routing decisions and the carved buffers of one hypernetwork pass: made once by hnet_carve, read by every step.
+struct HnetPlan {
+  int rows, W;
+  size_t WW, rw, Tfl;    // W * W, rows * W, floats of one re-laid T
+  bool batch_T;          // the re-laid T of every predicted layer prepared up front in two launches (f16x3, f16x3c)
+  bool batch_w;          // every dense-layer weight image of the pass prepared in one launch
+  float *Tp, *Tpart;
+  // backward only: a trunk's backward as one chain launch; all dense-layer weight gradients in one batched launch at the
+  // end; at few rows the chains themselves in one batched launch; trunk layers with a g_pre buffer (at least one)
+  bool chain_ok, defer_dw, chain_batch;
+  int nfc1;
+  float *g_hin, *g_u, *gvin_buf[2], *g_t_all, *ghin_slabs, *g_pre_all;
+  HnetSideLayout SL;
+};
+
+// Carves the persistent buffers and seals the workspace.  The ORDER and sizes of the take / reserve calls are the
+// workspace layout, the same in the dry and the real pass.
+static HnetPlan hnet_carve(Ctx& c, int rows, const cgat_hnet_params* p, bool backward, const HnetSide* side) {
+  HnetPlan h = {};
   const int W = p->W;
-  const size_t WW = (size_t)W * W;
-  const size_t rw = (size_t)rows * W;
-  const size_t Tfl = bilinear_T_floats(W, W, W);
-  const bool batch_T = W == 128 && mode_f16_T() && p->n_hyper <= TPREP_MAX && bilinear_dual_fast(W, W, W);
-  float* Tp = c.take<float>((batch_T ? (size_t)p->n_hyper : 1) * Tfl);
-  float* Tpart = c.take<float>(bilinear_prepare_T_batch_ws_floats(p->n_hyper));
-  float* g_hin = c.take<float>(rw);
-  float* g_u = c.take<float>((size_t)p->n_hyper * rw);   // one per predicted layer: all dT run in ONE launch at the end
-  float* gvin_buf[2] = {c.take<float>(rw), c.take<float>(rw)};
-  const bool batch_w = W == 128 && p->n_hyper * (p->n_fc + 2) <= WPREP_MAX;
-  // the fused trunk chain (chain.hip) leaves every trunk layer's pre-activation gradient behind, so the weight
-  // gradients of all dense layers of all predicted layers can wait for ONE batched launch at the end (rowsdw.hip):
-  // they feed nothing else in the backward pass.  g_pre then needs a buffer per predicted layer.
-  const bool chain_ok = batch_w && wprep_image_floats() != 0 && p->n_fc >= 1 && p->n_fc <= CHAIN_MAX;
-  const bool defer_dw = chain_ok && p->n_hyper * (p->n_fc + 2) <= DW_BATCH_MAX;
-  const int nfc1 = p->n_fc > 0 ? p->n_fc : 1;
-  // At a few thousand rows (the harness' shipped batch: 1 280 atoms) a trunk chain is 10 workgroups, and the four chains of
-  // a backward pass -- one per predicted layer, each 57 us, none feeding another: they feed the weight gradients and the
-  // SUM g_hin -- were 1.1 ms of an 18-ms step.  There they wait for ONE batched launch behind the loop (round 6): every
-  // predicted layer keeps its own g_t and writes its g_hin term to a slab; the slabs are added in the order the
-  // accumulating chains ran in (bit-identical).
-  const bool chain_batch = chain_ok && defer_dw && rows <= 8192 && p->n_hyper > 1 && p->n_hyper <= CHAIN_BATCH_MAX &&
-                           !mode_f16();
-  float* g_t_all = c.take<float>((chain_batch ? (size_t)p->n_hyper : 1) * rw);
-  float* ghin_slabs = chain_batch ? c.take<float>((size_t)p->n_hyper * rw) : nullptr;
-  ChainDesc pending[CHAIN_BATCH_MAX];
-  int n_pending = 0, n_slabs = 0;
-  const HnetSideLayout SL = hnet_side_layout(rows, p);
-  float* g_pre_all = (side && defer_dw) ? (c.dry ? nullptr : (float*)((char*)side->ws + SL.gpre))
-                                        : c.take<float>((size_t)(defer_dw ? p->n_hyper : 1) * nfc1 * rw);
-  if (batch_w) { c.wprep_reserve(p->n_hyper * (p->n_fc + 2)); c.tprep_reserve(2 * p->n_hyper); }
+  h.rows = rows; h.W = W; h.WW = (size_t)W * W; h.rw = (size_t)rows * W; h.Tfl = bilinear_T_floats(W, W, W);
+  const size_t rw = h.rw;
+  h.batch_T = W == 128 && mode_f16_T() && p->n_hyper <= TPREP_MAX && (!backward || bilinear_dual_fast(W, W, W));
+  h.Tp = c.take<float>((h.batch_T ? (size_t)p->n_hyper : 1) * h.Tfl);
+  h.Tpart = c.take<float>(bilinear_prepare_T_batch_ws_floats(p->n_hyper));
+  h.batch_w = W == 128 && p->n_hyper * (p->n_fc + 2) <= WPREP_MAX;
+  if (backward) {
+    h.g_hin = c.take<float>(rw);
+    h.g_u = c.take<float>((size_t)p->n_hyper * rw);   // one per predicted layer: all dT run in ONE launch at the end
+    h.gvin_buf[0] = c.take<float>(rw);
+    h.gvin_buf[1] = c.take<float>(rw);
+    // the fused trunk chain (chain.hip) leaves every trunk layer's pre-activation gradient behind, so the weight
+    // gradients of all dense layers of all predicted layers can wait for ONE batched launch at the end (rowsdw.hip):
+    // they feed nothing else in the backward pass.  g_pre then needs a buffer per predicted layer.
+    h.chain_ok = h.batch_w && wprep_image_floats() != 0 && p->n_fc >= 1 && p->n_fc <= CHAIN_MAX;
+    h.defer_dw = h.chain_ok && p->n_hyper * (p->n_fc + 2) <= DW_BATCH_MAX;
+    h.nfc1 = p->n_fc > 0 ? p->n_fc : 1;
+    // At a few thousand rows (the harness' shipped batch: 1 280 atoms) a trunk chain is 10 workgroups, and the four chains of
+    // a backward pass -- one per predicted layer, each 57 us, none feeding another: they feed the weight gradients and the
+    // SUM g_hin -- were 1.1 ms of an 18-ms step.  There they wait for ONE batched launch behind the loop (round 6): every
+    // predicted layer keeps its own g_t and writes its g_hin term to a slab; the slabs are added in the order the
+    // accumulating chains ran in (bit-identical).
+    h.chain_batch = h.chain_ok && h.defer_dw && rows <= 8192 && p->n_hyper > 1 && p->n_hyper <= CHAIN_BATCH_MAX &&
+                    !mode_f16();
+    h.g_t_all = c.take<float>((h.chain_batch ? (size_t)p->n_hyper : 1) * rw);
+    h.ghin_slabs = h.chain_batch ? c.take<float>((size_t)p->n_hyper * rw) : nullptr;
+    h.SL = hnet_side_layout(rows, p);
+    h.g_pre_all = (side && h.defer_dw) ? (c.dry ? nullptr : (float*)((char*)side->ws + h.SL.gpre))
+                                       : c.take<float>((size_t)(h.defer_dw ? p->n_hyper : 1) * h.nfc1 * rw);
+  }
+  if (h.batch_w) { c.wprep_reserve(p->n_hyper * (p->n_fc + 2)); c.tprep_reserve(2 * p->n_hyper); }
   c.seal();
-  DwBatchDesc dwb;
-  memset(&dwb, 0, sizeof(dwb));
-  dwb.rows = rows; dwb.ldg = W; dwb.ldx = W; dwb.ldo = W;
-  if (defer_dw && !side) c.need(rows_dw128_batch_ws_bytes(p->n_hyper * (p->n_fc + 2), rows));
-  if (defer_dw) c.need(rows_dw128_ws_bytes(rows, 2));   // an operand off the 16-byte grid takes the per-layer launch
-  auto defer_item = [&](const float* G, const float* X, float* out, float* bsum) -> bool {
-    if (!defer_dw || c.dry || dwb.n >= DW_BATCH_MAX || !rows_dw128_fast(G, W, X, W, nullptr, 0)) return false;
-    dwb.it[dwb.n++] = {G, X, out, bsum};
-    return true;
-  };
-  if (batch_w) {   // the same weights in the transposed orientation (g_in = g_out W)
-    for (int l = 0; l < p->n_hyper; ++l) {
-      for (int s = 0; s < p->n_fc; ++s) c.wprep_add(p->layer[l].fc_w[s], 1, W);
-      if (mode_f16()) c.wprep_add(p->layer[l].head_b, 1, W);
-      else { c.tprep_add(p->layer[l].head_b, 1, W); c.tprep_add(p->layer[l].head_w + WW * W, 1, W); }
-      c.wprep_add(p->layer[l].head_w + WW * W, 1, W);
-    }
-    CGAT_TRY(c.wprep_run());
-    CGAT_TRY(c.tprep_run());
+  if (backward) {
+    if (h.defer_dw && !side) c.need(rows_dw128_batch_ws_bytes(p->n_hyper * (p->n_fc + 2), rows));
+    if (h.defer_dw) c.need(rows_dw128_ws_bytes(rows, 2));   // an operand off the 16-byte grid takes the per-layer launch
   }
-  bool T_ready = false;   // the [a = i][b = o][c = k] operands of all predicted layers in two launches
-  if (batch_T && !c.dry) {
-    const float* tsrc[TPREP_MAX];
-    float* tdst[TPREP_MAX];
-    for (int l = 0; l < p->n_hyper; ++l) { tsrc[l] = p->layer[l].head_w; tdst[l] = Tp + (size_t)l * Tfl; }
-    const int rc_ = bilinear_prepare_T_batch(p->n_hyper, tsrc, tdst, W, W, W, 1, 0, 2, Tpart, c.s);
-    if (rc_ == CGAT_OK) T_ready = true;
-    else if (rc_ != CGAT_ERR_UNSUPPORTED) return rc_;
-  }
-  HnetSaved sv = hnet_saved(const_cast<float*>(saved), rows, p);
-  const float* hin = p->damping ? sv.hin() : h0;
-  RUN(fill_launch(g_hin, 0.f, (long)rw, c.s));
-  struct { const float *gu, *vin, *z; float* out; } deferred[CGAT_MAX_HYPER];
-  int n_deferred = 0;
-  // makes the side stream wait for everything issued on the main stream so far.  Events come from a small ring created
-  // once and never destroyed: under a hipGraph capture (cgat_amd.GraphedStep) the captured dependency keeps referring to
-  // the event object, and destroying it right after the wait -- legal in eager mode -- crashed hipStreamEndCapture on
-  // the second capture of a process.
-  auto side_sync = [&]() -> int {
-    static hipEvent_t ring[64];
-    static unsigned next = 0, made = 0;
-    const unsigned slot = next++ % 64;
-    if (slot >= made) {
-      CGAT_HIP(hipEventCreateWithFlags(&ring[slot], hipEventDisableTiming));
-      made = slot + 1;
+  return h;
+}
+
+// The re-laid T operands of ALL predicted layers in two launches, T[o,i,k] = head_w[(o*W+i)*W + k] under the index
+// permutation the caller's contraction reads.  *ready stays false where the batched form does not exist: the caller
+// then prepares each layer's operand when it gets there.
+static int hnet_prepare_T_all(Ctx& c, const HnetPlan& h, const cgat_hnet_params* p, int perm0, int perm1, int perm2,
+                              bool* ready) {
+  *ready = false;
+  if (!h.batch_T || c.dry) return CGAT_OK;
+  const float* tsrc[TPREP_MAX];
+  float* tdst[TPREP_MAX];
+  for (int l = 0; l < p->n_hyper; ++l) { tsrc[l] = p->layer[l].head_w; tdst[l] = h.Tp + (size_t)l * h.Tfl; }
+  const int rc_ = bilinear_prepare_T_batch(p->n_hyper, tsrc, tdst, h.W, h.W, h.W, perm0, perm1, perm2, h.Tpart, c.s);
+  if (rc_ == CGAT_OK) *ready = true;
+  else if (rc_ != CGAT_ERR_UNSUPPORTED) return rc_;
+  return CGAT_OK;
+}
+
+// Every dense-layer weight of the pass, prepared in one launch per image kind: forward orientation [out][in], or
+// `transposed` for the backward's g_in = g_out W.  Bm = head_b[:W*W] as [o,i], U = head_w[W*W:].
+static int hnet_prepare_weights(Ctx& c, const HnetPlan& h, const cgat_hnet_params* p, bool transposed) {
+  if (!h.batch_w) return CGAT_OK;
+  const long so = transposed ? 1 : h.W, sk = transposed ? h.W : 1;
+  for (int l = 0; l < p->n_hyper; ++l) {
+    const float* U = p->layer[l].head_w + h.WW * h.W;
+    for (int s = 0; s < p->n_fc; ++s) c.wprep_add(p->layer[l].fc_w[s], so, sk);
+    if (mode_f16()) {
+      c.wprep_add(p->layer[l].head_b, so, sk);   // read by linear128_launch in that mode only
+    } else {                                     // (the 24-bit modes: the dense-layer kernel's image)
+      c.tprep_add(p->layer[l].head_b, so, sk);
+      if (transposed) c.tprep_add(U, so, sk);
     }
-    CGAT_HIP(hipEventRecord(ring[slot], c.s));
-    CGAT_HIP(hipStreamWaitEvent(side->s, ring[slot], 0));
-    return CGAT_OK;
-  };
+    c.wprep_add(U, so, sk);
+  }
+  CGAT_TRY(c.wprep_run());
+  CGAT_TRY(c.tprep_run());
+  return CGAT_OK;
+}
+
+// The trunk (n_fc x [Linear + Tanh]) and the trunk-side linear term of the head, u = z @ U^T + b0, as ONE chain per
+// predicted layer (chain.hip) when the weights of the pass have been prepared in a batch (width 128, <= 4 trunk layers)
+// -- and, since every predicted layer's trunk reads the same hyper input, the chains of ALL predicted layers as ONE
+// launch (round 5); the remaining linear term u += vin @ Bm^T follows per layer.  *chained stays false where a chain
+// cannot run: the caller then takes the per-layer products.
+static int hnet_forward_chains(Ctx& c, const HnetPlan& h, const cgat_hnet_params* p, const float* hin, const HnetSaved& sv,
+                               float* y, bool* chained) {
+  *chained = false;
+  if (!h.batch_w || c.dry || wprep_image_floats() == 0 || p->n_fc + 1 > CHAIN_MAX || p->n_hyper > CGAT_MAX_HYPER) return CGAT_OK;
+  const int W = h.W;
+  ChainDesc cds[CGAT_MAX_HYPER];
+  for (int l = 0; l < p->n_hyper; ++l) {
+    const cgat_hyperlinear_params& L = p->layer[l];
+    ChainDesc& cd = cds[l];
+    memset(&cd, 0, sizeof(cd));
+    cd.n_layers = p->n_fc + 1; cd.rows = h.rows; cd.x = hin; cd.ldx = W;
+    for (int s = 0; s < p->n_fc; ++s) {
+      ChainLayer& cl = cd.layer[s];
+      cl.W = (const uint4*)c.wprep_find(L.fc_w[s], W, 1);
+      cl.bias = L.fc_b[s]; cl.act = CGAT_ACT_TANH; cl.out = sv.act(l, s); cl.ld_out = W;
+      if (!cl.W) return CGAT_OK;
+    }
+    ChainLayer& cu = cd.layer[p->n_fc];
+    cu.W = (const uint4*)c.wprep_find(L.head_w + h.WW * W, W, 1);
+    cu.bias = L.head_b + h.WW; cu.act = CGAT_ACT_NONE; cu.out = (l == p->n_hyper - 1) ? y : sv.u(l); cu.ld_out = W;
+    if (!cu.W || !mlp_chain128_fast(cd)) return CGAT_OK;
+  }
+  for (int l0 = 0; l0 < p->n_hyper; l0 += CHAIN_BATCH_MAX)
+    CGAT_TRY(mlp_chain128_batch_launch(cds + l0, p->n_hyper - l0 < CHAIN_BATCH_MAX ? p->n_hyper - l0 : CHAIN_BATCH_MAX, c.s));
+  *chained = true;
+  return CGAT_OK;
+}
+
+static int hnet_forward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const float* h0, const float* v, float* y,
+                             float* saved) {
+  const HnetPlan h = hnet_carve(c, rows, p, /*backward=*/false, nullptr);
+  const int W = h.W;
+  bool T_ready = false, chained = false;
+  CGAT_TRY(hnet_prepare_T_all(c, h, p, 1, 2, 0, &T_ready));   // T re-laid as Tp[i,k,o]
+  CGAT_TRY(hnet_prepare_weights(c, h, p, /*transposed=*/false));
+  HnetSaved sv = hnet_saved(saved, rows, p);
+  const float* hin = h0;
+  if (p->damping) {
+    RUN(mix_launch(h0, v, p->damping, sv.hin(), (long)rows * W, c.s));
+    hin = sv.hin();
+  }
+  CGAT_TRY(hnet_forward_chains(c, h, p, hin, sv, y, &chained));
+  const float* vin = v;
+  for (int l = 0; l < p->n_hyper; ++l) {
+    const cgat_hyperlinear_params& L = p->layer[l];
+    float* u = c.dry ? nullptr : ((l == p->n_hyper - 1) ? y : sv.u(l));
+    const float* z = c.dry ? nullptr : sv.act(l, p->n_fc - 1);
+    if (chained) {   // u holds z @ U^T + b0
+      GemmParams g = gemm_params(rows, W, W, vin, W, L.head_b, W, u, W);
+      g.beta = 1.f;
+      CGAT_TRY(c.gemm(g));
+    } else {
+      const float* t = hin;
+      for (int s = 0; s < p->n_fc; ++s) {  // trunk: Linear + Tanh
+        GemmParams g = gemm_params(rows, W, W, t, W, L.fc_w[s], W, c.dry ? nullptr : sv.act(l, s), W);
+        g.bias = L.fc_b[s];
+        g.act = CGAT_ACT_TANH;
+        CGAT_TRY(c.gemm(g));
+        t = c.dry ? nullptr : sv.act(l, s);
+      }
+      // bias-row terms of the head:  u = vin @ Bm^T + z @ U^T + b0
+      GemmParams g = gemm_params(rows, W, W, vin, W, L.head_b, W, u, W);
+      CGAT_TRY(c.gemm(g));
+      g = gemm_params(rows, W, W, z, W, L.head_w + h.WW * W, W, u, W);
+      g.bias = L.head_b + h.WW;
+      g.beta = 1.f;
+      CGAT_TRY(c.gemm(g));
+    }
+    // trilinear term with T[o,i,k] = head_w[(o*W+i)*W + k] re-laid as Tp[i,k,o]
+    float* Tl = h.Tp + (T_ready ? (size_t)l * h.Tfl : 0);
+    if (!T_ready) RUN(bilinear_prepare_T(L.head_w, Tl, W, W, W, 1, 2, 0, c.s));
+    // (+ LayerNorm + tanh of every layer but the last, fused into the contraction's slab sum at width 128)
+    const bool ln = l < p->n_hyper - 1;
+    const bool ln_fused = ln && W == 128;
+    CGAT_TRY(c.bilinear(vin, W, z, W, Tl, u, W, u, W, rows, W, W, W, (ln_fused && !c.dry) ? sv.vin(l + 1) : nullptr, 1e-5f));
+    if (ln) {
+      if (!ln_fused) RUN(layernorm_tanh_fwd_launch(u, sv.vin(l + 1), rows, W, 1e-5f, c.s));
+      vin = c.dry ? nullptr : sv.vin(l + 1);
+    }
+  }
+  return check_ws(c, "hnet_forward");
+}
+
+// backward: what its steps share -- the plan, the operands and the three queues that wait for a batched launch in the tail
+struct HnetBwd {
+  HnetPlan h;
+  const cgat_hnet_params* p;
+  const cgat_hnet_grads* gr;
+  const HnetSide* side;
+  HnetSaved sv;
+  const float* hin;
+  bool T_ready;
+  DwBatchDesc dwb;                        // dense-layer weight gradients (rowsdw.hip)
+  ChainDesc pending[CHAIN_BATCH_MAX];     // trunk chains (chain_batch); chain i writes slab i of ghin_slabs
+  int n_pending;
+  const float *dT_gu[CGAT_MAX_HYPER], *dT_vin[CGAT_MAX_HYPER], *dT_z[CGAT_MAX_HYPER];   // dT: all predicted layers in one launch
+  float* dT_out[CGAT_MAX_HYPER];
+  int n_deferred;
   // dT operands are prepared (maxima, scaled transposes, fp16 planes: HBM-bound, 0.25 ms a layer) on the side stream as
   // soon as a layer's gu exists, beside that layer's matrix-bound contraction on the main stream, so that the dT launch
-  // itself can start the moment this function has issued its last kernel
-  bool early_prep = side && !c.dry && rows >= 16384;   // (small batches: 9 more launches cost more than they hide)
-  int n_prepped = 0;
-  const float* gout = g_y;  // gradient wrt the output of predicted layer l (post norm for l < last)
-  for (int l = p->n_hyper - 1; l >= 0; --l) {
-    const cgat_hyperlinear_params& L = p->layer[l];
-    const cgat_hyperlinear_grads& G = gr->layer[l];
-    const float* gu = gout;  // gradient wrt the pre-norm output u_l
-    if (l < p->n_hyper - 1) {
-      float* gu_buf = c.dry ? nullptr : ((side ? (float*)side->ws : g_u) + (size_t)l * rw);
-      RUN(layernorm_tanh_bwd_launch(sv.u(l), sv.vin(l + 1), gout, gu_buf, rows, W, 1e-5f, c.s));
-      gu = gu_buf;
-    }
-    float* g_vin = (l == 0) ? g_v : gvin_buf[l & 1];  // gradient wrt this layer's input
-    float* g_t = c.dry ? nullptr : g_t_all + (chain_batch ? (size_t)l * rw : 0);
-    const float* vin = (l == 0) ? v : sv.vin(l);
-    const float* z = c.dry ? nullptr : sv.act(l, p->n_fc - 1);
-    // ---- head parameter gradients ----
-    // dT[o][i][k] = sum_n gu[n,o] vin[n,i] z[n,k]: deferred, all predicted layers in one launch (end of this function)
-    deferred[n_deferred++] = {gu, vin, z, G.head_w};
-    if (early_prep) {
-      CGAT_TRY(side_sync());
-      const int rc_ = bilinear_wgrad_batch_prep(n_deferred - 1, p->n_hyper, gu, W, vin, W, z, W, rows, W, W, W,
-                                                (char*)side->ws + SL.wgrad, side->bytes - SL.wgrad, side->s);
-      if (rc_ == CGAT_OK) ++n_prepped;
-      else if (rc_ == CGAT_ERR_UNSUPPORTED) early_prep = false;
-      else return rc_;
-    }
-    // Bm grad [o][i] = gu^T vin, U grad [o][k] = gu^T z, bias grad = column sums of gu: one pass over the three operands
-    int fused = -1;
-    if (c.dry && defer_dw) fused = 0;
-    else if (defer_dw && dwb.n + 2 <= DW_BATCH_MAX && rows_dw128_fast(gu, W, vin, W, z, W) &&
-             defer_item(gu, vin, G.head_b, G.head_b + WW) && defer_item(gu, z, G.head_w + WW * W, nullptr)) fused = 0;
-    else if (W == 128) fused = c.dw128(gu, W, vin, W, G.head_b, W, z, W, G.head_w + WW * W, W, G.head_b + WW, rows);
-    if (fused > 0) return fused;
-    if (fused < 0) {
-      GemmParams g = gemm_params(W, W, rows, gu, W, vin, W, G.head_b, W);  // Bm grad [o][i]
+  // itself can start the moment the backward has issued its last kernel
+  bool early_prep;
+  int n_prepped;
+};
+
+// Weight (and bias) gradients of one dense layer: out1 = G^T X1 (and out2 = G^T X2 when X2 is given), bsum = column sums
+// of G.  In order of preference: queued for the batched launch of the tail (`may_wait`: G stays as it is until then),
+// the rows kernel now (rowsdw.hip), generic products + column sum.
+static int dense_wgrad(Ctx& c, HnetBwd& b, bool may_wait, const float* G, const float* X1, float* out1, const float* X2,
+                       float* out2, float* bsum) {
+  const int W = b.h.W, rows = b.h.rows;
+  const int nx = X2 ? 2 : 1;
+  if (may_wait && c.dry) return CGAT_OK;   // (hnet_carve has sized the batched launch and the per-layer one)
+  if (may_wait && b.dwb.n + nx <= DW_BATCH_MAX && rows_dw128_fast(G, W, X1, W, X2, X2 ? W : 0)) {
+    b.dwb.it[b.dwb.n++] = {G, X1, out1, bsum};
+    if (X2) b.dwb.it[b.dwb.n++] = {G, X2, out2, nullptr};
+    return CGAT_OK;
+  }
+  const int fused = W == 128 ? c.dw128(G, W, X1, W, out1, W, X2, X2 ? W : 0, out2, X2 ? W : 0, bsum, rows) : -1;
+  if (fused > 0) return fused;
+  if (fused < 0) {
+    GemmParams g = gemm_params(W, W, rows, G, W, X1, W, out1, W);
+    g.a_kmajor = 1; g.b_kmajor = 1;
+    CGAT_TRY(c.gemm(g, true));
+    if (X2) {
+      g = gemm_params(W, W, rows, G, W, X2, W, out2, W);
       g.a_kmajor = 1; g.b_kmajor = 1;
       CGAT_TRY(c.gemm(g, true));
-      g = gemm_params(W, W, rows, gu, W, z, W, G.head_w + WW * W, W);  // U grad [o][k]
-      g.a_kmajor = 1; g.b_kmajor = 1;
-      CGAT_TRY(c.gemm(g, true));
-      CGAT_TRY(c.colsum(gu, W, rows, W, G.head_b + WW, 1.f));
     }
-    // ---- g_z = gu @ U + sum_{o,i} gu[o] vin[i] T[o,i,k]  ----
-    {
-      GemmParams g = gemm_params(rows, W, W, gu, W, L.head_w + WW * W, W, g_t, W);
-      g.b_kmajor = 1;
-      CGAT_TRY(c.gemm(g));
-    }
-    // ---- g_vin = gu @ Bm + sum_{o,k} gu[o] z[k] T[o,i,k] ----
-    {
-      GemmParams g = gemm_params(rows, W, W, gu, W, L.head_b, W, g_vin, W);
-      g.b_kmajor = 1;
-      CGAT_TRY(c.gemm(g));
-    }
-    if (bilinear_dual_fast(W, W, W)) {
-      // both bilinear parts from one contraction: M[n,i,k] = sum_o gu[o] T[o,i,k];  g_z += vin . M,  g_vin += M . z
-      float* Tl = Tp + (T_ready ? (size_t)l * Tfl : 0);
-      if (!T_ready) RUN(bilinear_prepare_T(L.head_w, Tl, W, W, W, 1, 0, 2, c.s));   // operand [a = i][b = o][c = k]
-      CGAT_TRY(c.dual(vin, W, gu, W, z, W, Tl, g_t, W, g_t, W, g_vin, W, g_vin, W, rows));
-    } else {
-      RUN(bilinear_prepare_T(L.head_w, Tp, W, W, W, 0, 1, 2, c.s));
-      CGAT_TRY(c.bilinear(gu, W, vin, W, Tp, g_t, W, g_t, W, rows, W, W, W));
-      RUN(bilinear_prepare_T(L.head_w, Tp, W, W, W, 0, 2, 1, c.s));   // T re-laid as [o,k,i]
-      CGAT_TRY(c.bilinear(gu, W, z, W, Tp, g_vin, W, g_vin, W, rows, W, W, W));
-    }
-    // ---- trunk backward (g_t holds the gradient wrt the trunk output z) ----
-    // One chain launch on the transposed weights (chain.hip): rows = g_t * tanh'(t_last) = the last layer's
-    // pre-activation gradient, layer i multiplies by W_(n_fc-1-i) and by tanh' of the activation below it, every
-    // pre-activation gradient is stored for the weight-gradient kernel, the last product is added to g_hin.
-    bool chained = false;
-    float* g_pre = c.dry ? nullptr : g_pre_all + (defer_dw ? (size_t)l * nfc1 * rw : 0);
-    if (chain_ok && !c.dry) {
-      ChainDesc cd;
-      memset(&cd, 0, sizeof(cd));
-      const int nf = p->n_fc;
-      cd.n_layers = nf; cd.rows = rows; cd.x = g_t; cd.ldx = W;
-      cd.in_dact = sv.act(l, nf - 1); cd.ld_in_dact = W; cd.in_dact_type = CGAT_ACT_TANH;
-      cd.in_store = g_pre + (size_t)(nf - 1) * rw; cd.ld_in_store = W;
-      bool ok = true;
-      for (int i = 0; i < nf; ++i) {
-        const int sl = nf - 1 - i;                      // trunk layer whose weight this chain layer multiplies by
-        ChainLayer& cl = cd.layer[i];
-        cl.W = (const uint4*)c.wprep_find(L.fc_w[sl], 1, W);
-        cl.act = CGAT_ACT_NONE;
-        if (sl > 0) {
-          cl.dact = sv.act(l, sl - 1); cl.ld_dact = W; cl.dact_type = CGAT_ACT_TANH;
-          cl.out = g_pre + (size_t)(sl - 1) * rw; cl.ld_out = W;
-        } else if (chain_batch) {
-          cl.out = ghin_slabs + (size_t)n_slabs * rw; cl.ld_out = W;   // (summed behind the loop, in this order)
-        } else {
-          cl.out = g_hin; cl.ld_out = W; cl.accumulate = 1;   // every predicted layer's trunk reads the same hyper input
-        }
-        ok = ok && cl.W;
-      }
-      ok = ok && mlp_chain128_fast(cd);
-      // (batched: a weight gradient that cannot wait for the batched launch would read g_pre before the chain has run)
-      bool can_wait = chain_batch;
-      for (int s2 = nf - 1; s2 >= 0 && can_wait; --s2)
-        can_wait = rows_dw128_fast(g_pre + (size_t)s2 * rw, W, (s2 == 0) ? hin : sv.act(l, s2 - 1), W, nullptr, 0) &&
-                   dwb.n + nf <= DW_BATCH_MAX;
-      if (ok && chain_batch && !can_wait) {
-        cd.layer[nf - 1].out = g_hin; cd.layer[nf - 1].accumulate = 1;
-      }
-      if (ok) {
-        if (chain_batch && can_wait) { pending[n_pending++] = cd; ++n_slabs; }
-        else CGAT_TRY(mlp_chain128_launch(cd, c.s));
-        for (int s2 = nf - 1; s2 >= 0; --s2) {
-          const float* tin = (s2 == 0) ? hin : sv.act(l, s2 - 1);
-          const float* gp = g_pre + (size_t)s2 * rw;
-          if (defer_item(gp, tin, G.fc_w[s2], G.fc_b[s2])) continue;
-          int fz = W == 128 ? c.dw128(gp, W, tin, W, G.fc_w[s2], W, nullptr, 0, nullptr, 0, G.fc_b[s2], rows) : -1;
-          if (fz > 0) return fz;
-          if (fz < 0) {
-            GemmParams g = gemm_params(W, W, rows, gp, W, tin, W, G.fc_w[s2], W);
-            g.a_kmajor = 1; g.b_kmajor = 1;
-            CGAT_TRY(c.gemm(g, true));
-            CGAT_TRY(c.colsum(gp, W, rows, W, G.fc_b[s2], 1.f));
-          }
-        }
-        chained = true;
-      }
-    }
-    for (int s = p->n_fc - 1; s >= 0 && !chained; --s) {
-      const float* tout = c.dry ? nullptr : sv.act(l, s);
-      const float* tin = (s == 0) ? hin : (c.dry ? nullptr : sv.act(l, s - 1));
-      RUN(act_bwd_launch(tout, g_t, g_pre, (long)rw, CGAT_ACT_TANH, c.s));
-      GemmParams g = gemm_params(W, W, rows, g_pre, W, tin, W, G.fc_w[s], W);
-      fused = W == 128 ? c.dw128(g_pre, W, tin, W, G.fc_w[s], W, nullptr, 0, nullptr, 0, G.fc_b[s], rows) : -1;
-      if (fused > 0) return fused;
-      if (fused < 0) {
-        g.a_kmajor = 1; g.b_kmajor = 1;
-        CGAT_TRY(c.gemm(g, true));
-        CGAT_TRY(c.colsum(g_pre, W, rows, W, G.fc_b[s], 1.f));
-      }
-      g = gemm_params(rows, W, W, g_pre, W, L.fc_w[s], W, s == 0 ? g_hin : g_t, W);
-      g.b_kmajor = 1;
-      g.beta = (s == 0) ? 1.f : 0.f;  // every predicted layer's trunk reads the same hyper input
-      CGAT_TRY(c.gemm(g));
-    }
-    gout = g_vin;
+    CGAT_TRY(c.colsum(G, W, rows, W, bsum, 1.f));
   }
-  if (n_pending > 0) {
-    CGAT_TRY(mlp_chain128_batch_launch(pending, n_pending, c.s));
-    if (n_pending == p->n_hyper) {
-      RUN(sum_slabs_launch(ghin_slabs, n_slabs, (long)rw, g_hin, (long)rw, c.s));   // (g_hin was zero: 0.f + c_last + ... + c_0)
-    } else {      // some layer took the accumulating route: add the slabs to what it left
-      for (int z = 0; z < n_slabs; ++z) RUN(axpy_launch(g_hin, ghin_slabs + (size_t)z * rw, 1.f, (long)rw, c.s));
-    }
+  return CGAT_OK;
+}
+
+// ---- head parameter gradients of predicted layer l ----
+static int hnet_head_param_grads(Ctx& c, HnetBwd& b, int l, const float* gu, const float* vin, const float* z) {
+  const HnetPlan& h = b.h;
+  const int W = h.W;
+  const cgat_hyperlinear_grads& G = b.gr->layer[l];
+  // dT[o][i][k] = sum_n gu[n,o] vin[n,i] z[n,k]: deferred, all predicted layers in one launch (hnet_backward_tail)
+  b.dT_gu[b.n_deferred] = gu; b.dT_vin[b.n_deferred] = vin; b.dT_z[b.n_deferred] = z; b.dT_out[b.n_deferred++] = G.head_w;
+  if (b.early_prep) {
+    CGAT_TRY(stream_wait_stream(b.side->s, c.s));
+    const int rc_ = bilinear_wgrad_batch_prep(b.n_deferred - 1, b.p->n_hyper, gu, W, vin, W, z, W, h.rows, W, W, W,
+                                              (char*)b.side->ws + h.SL.wgrad, b.side->bytes - h.SL.wgrad, b.side->s);
+    if (rc_ == CGAT_OK) ++b.n_prepped;
+    else if (rc_ == CGAT_ERR_UNSUPPORTED) b.early_prep = false;
+    else return rc_;
   }
-  if (p->damping) {
-    CGAT_TRY(c.mix_bwd(g_hin, h0, v, p->damping, g_h0, g_v, gr->damping, (long)rw));
+  // Bm grad [o][i] = gu^T vin, U grad [o][k] = gu^T z, bias grad = column sums of gu: one pass over the three operands
+  return dense_wgrad(c, b, h.defer_dw, gu, vin, G.head_b, z, G.head_w + h.WW * W, G.head_b + h.WW);
+}
+
+// ---- the head's input gradients: g_t = g_z (wrt the trunk output), g_vin (wrt the layer's input) ----
+static int hnet_head_input_grads(Ctx& c, const HnetBwd& b, int l, const float* gu, const float* vin, const float* z,
+                                 float* g_t, float* g_vin) {
+  const HnetPlan& h = b.h;
+  const int W = h.W, rows = h.rows;
+  const cgat_hyperlinear_params& L = b.p->layer[l];
+  {  // g_z = gu @ U + sum_{o,i} gu[o] vin[i] T[o,i,k]
+    GemmParams g = gemm_params(rows, W, W, gu, W, L.head_w + h.WW * W, W, g_t, W);
+    g.b_kmajor = 1;
+    CGAT_TRY(c.gemm(g));
+  }
+  {  // g_vin = gu @ Bm + sum_{o,k} gu[o] z[k] T[o,i,k]
+    GemmParams g = gemm_params(rows, W, W, gu, W, L.head_b, W, g_vin, W);
+    g.b_kmajor = 1;
+    CGAT_TRY(c.gemm(g));
+  }
+  if (bilinear_dual_fast(W, W, W)) {
+    // both bilinear parts from one contraction: M[n,i,k] = sum_o gu[o] T[o,i,k];  g_z += vin . M,  g_vin += M . z
+    float* Tl = h.Tp + (b.T_ready ? (size_t)l * h.Tfl : 0);
+    if (!b.T_ready) RUN(bilinear_prepare_T(L.head_w, Tl, W, W, W, 1, 0, 2, c.s));   // operand [a = i][b = o][c = k]
+    CGAT_TRY(c.dual(vin, W, gu, W, z, W, Tl, g_t, W, g_t, W, g_vin, W, g_vin, W, rows));
   } else {
-    RUN(copy2d_launch(g_hin, W, g_h0, W, rows, W, c.s));
+    RUN(bilinear_prepare_T(L.head_w, h.Tp, W, W, W, 0, 1, 2, c.s));
+    CGAT_TRY(c.bilinear(gu, W, vin, W, h.Tp, g_t, W, g_t, W, rows, W, W, W));
+    RUN(bilinear_prepare_T(L.head_w, h.Tp, W, W, W, 0, 2, 1, c.s));   // T re-laid as [o,k,i]
+    CGAT_TRY(c.bilinear(gu, W, z, W, h.Tp, g_vin, W, g_vin, W, rows, W, W, W));
+  }
+  return CGAT_OK;
+}
+
+// ---- trunk backward of predicted layer l (g_t holds the gradient wrt the trunk output z) ----
+// One chain launch on the transposed weights (chain.hip): rows = g_t * tanh'(t_last) = the last layer's
+// pre-activation gradient, layer i multiplies by W_(n_fc-1-i) and by tanh' of the activation below it, every
+// pre-activation gradient is stored for the weight-gradient kernel, the last product is added to g_hin -- launched now,
+// or queued for the batched launch of the tail (chain_batch).  *chained stays false where the chain cannot run.
+static int hnet_trunk_backward_chain(Ctx& c, HnetBwd& b, int l, const float* g_t, float* g_pre, bool* chained) {
+  *chained = false;
+  const HnetPlan& h = b.h;
+  if (!h.chain_ok || c.dry) return CGAT_OK;
+  const int W = h.W, nf = b.p->n_fc;
+  const size_t rw = h.rw;
+  const cgat_hyperlinear_params& L = b.p->layer[l];
+  const cgat_hyperlinear_grads& G = b.gr->layer[l];
+  auto below = [&](int s) { return s == 0 ? b.hin : b.sv.act(l, s - 1); };   // input rows of trunk layer s
+  // (batched: a weight gradient that cannot wait for the batched launch would read g_pre before the chain has run)
+  bool can_wait = h.chain_batch;
+  for (int s = nf - 1; s >= 0 && can_wait; --s)
+    can_wait = rows_dw128_fast(g_pre + (size_t)s * rw, W, below(s), W, nullptr, 0) && b.dwb.n + nf <= DW_BATCH_MAX;
+  ChainDesc cd;
+  memset(&cd, 0, sizeof(cd));
+  cd.n_layers = nf; cd.rows = h.rows; cd.x = g_t; cd.ldx = W;
+  cd.in_dact = b.sv.act(l, nf - 1); cd.ld_in_dact = W; cd.in_dact_type = CGAT_ACT_TANH;
+  cd.in_store = g_pre + (size_t)(nf - 1) * rw; cd.ld_in_store = W;
+  for (int i = 0; i < nf; ++i) {
+    const int sl = nf - 1 - i;                      // trunk layer whose weight this chain layer multiplies by
+    ChainLayer& cl = cd.layer[i];
+    cl.W = (const uint4*)c.wprep_find(L.fc_w[sl], 1, W);
+    if (!cl.W) return CGAT_OK;
+    cl.act = CGAT_ACT_NONE;
+    cl.ld_out = W;
+    if (sl > 0) {
+      cl.dact = b.sv.act(l, sl - 1); cl.ld_dact = W; cl.dact_type = CGAT_ACT_TANH;
+      cl.out = g_pre + (size_t)(sl - 1) * rw;
+    } else if (can_wait) {
+      cl.out = h.ghin_slabs + (size_t)b.n_pending * rw;   // (summed in the tail, in this order)
+    } else {
+      cl.out = h.g_hin; cl.accumulate = 1;   // every predicted layer's trunk reads the same hyper input
+    }
+  }
+  if (!mlp_chain128_fast(cd)) return CGAT_OK;
+  if (can_wait) b.pending[b.n_pending++] = cd;
+  else CGAT_TRY(mlp_chain128_launch(cd, c.s));
+  for (int s = nf - 1; s >= 0; --s)
+    CGAT_TRY(dense_wgrad(c, b, h.defer_dw, g_pre + (size_t)s * rw, below(s), G.fc_w[s], nullptr, nullptr, G.fc_b[s]));
+  *chained = true;
+  return CGAT_OK;
+}
+
+// ... or layer by layer (what the dry pass sizes): g_pre is ONE buffer for all trunk layers, no weight gradient can wait
+static int hnet_trunk_backward_layers(Ctx& c, HnetBwd& b, int l, float* g_t, float* g_pre) {
+  const HnetPlan& h = b.h;
+  const int W = h.W, rows = h.rows;
+  const cgat_hyperlinear_params& L = b.p->layer[l];
+  const cgat_hyperlinear_grads& G = b.gr->layer[l];
+  for (int s = b.p->n_fc - 1; s >= 0; --s) {
+    const float* tout = c.dry ? nullptr : b.sv.act(l, s);
+    const float* tin = (s == 0) ? b.hin : (c.dry ? nullptr : b.sv.act(l, s - 1));
+    RUN(act_bwd_launch(tout, g_t, g_pre, (long)h.rw, CGAT_ACT_TANH, c.s));
+    CGAT_TRY(dense_wgrad(c, b, /*may_wait=*/false, g_pre, tin, G.fc_w[s], nullptr, nullptr, G.fc_b[s]));
+    GemmParams g = gemm_params(rows, W, W, g_pre, W, L.fc_w[s], W, s == 0 ? h.g_hin : g_t, W);
+    g.b_kmajor = 1;
+    g.beta = (s == 0) ? 1.f : 0.f;  // every predicted layer's trunk reads the same hyper input
+    CGAT_TRY(c.gemm(g));
+  }
+  return CGAT_OK;
+}
+
+// ---- behind the loop: the three queues, and the gradient of the hyper input ----
+static int hnet_backward_tail(Ctx& c, HnetBwd& b, const float* h0, const float* v, float* g_h0, float* g_v) {
+  const HnetPlan& h = b.h;
+  const HnetSide* side = b.side;
+  const int W = h.W, rows = h.rows;
+  if (b.n_pending > 0) {
+    CGAT_TRY(mlp_chain128_batch_launch(b.pending, b.n_pending, c.s));
+    if (b.n_pending == b.p->n_hyper) {   // (g_hin was zero: 0.f + c_last + ... + c_0)
+      RUN(sum_slabs_launch(h.ghin_slabs, b.n_pending, (long)h.rw, h.g_hin, (long)h.rw, c.s));
+    } else {      // some layer took the accumulating route: add the slabs to what it left
+      for (int z = 0; z < b.n_pending; ++z) RUN(axpy_launch(h.g_hin, h.ghin_slabs + (size_t)z * h.rw, 1.f, (long)h.rw, c.s));
+    }
+  }
+  if (b.p->damping) {
+    CGAT_TRY(c.mix_bwd(h.g_hin, h0, v, b.p->damping, g_h0, g_v, b.gr->damping, (long)h.rw));
+  } else {
+    RUN(copy2d_launch(h.g_hin, W, g_h0, W, rows, W, c.s));
   }
   bool side_waits = false;   // the side stream has been made to wait for everything issued above
   auto side_wait = [&]() -> int {
     if (side_waits) return CGAT_OK;
     side_waits = true;
-    return side_sync();
+    return stream_wait_stream(side->s, c.s);
   };
-  if (n_deferred > 0) {
-    const float *dp[CGAT_MAX_HYPER], *dq[CGAT_MAX_HYPER], *dr[CGAT_MAX_HYPER];
-    float* dout[CGAT_MAX_HYPER];
-    for (int i = 0; i < n_deferred; ++i) { dp[i] = deferred[i].gu; dq[i] = deferred[i].vin; dr[i] = deferred[i].z; dout[i] = deferred[i].out; }
+  if (b.n_deferred > 0) {
     if (side && !c.dry) {
       // On the side stream the dT launch starts when everything above has been issued on the main stream, i.e. together
       // with whatever the caller enqueues next (the HBM-bound attention backward), on `wgrad_wgs` workgroups.
       CGAT_TRY(side_wait());
-      CGAT_TRY(bilinear_wgrad_batch_launch(n_deferred, dp, W, dq, W, dr, W, dout, rows, W, W, W,
-                                           (char*)side->ws + SL.wgrad, side->bytes - SL.wgrad, side->s, side->wgrad_wgs,
-                                           early_prep && n_prepped == n_deferred));
+      CGAT_TRY(bilinear_wgrad_batch_launch(b.n_deferred, b.dT_gu, W, b.dT_vin, W, b.dT_z, W, b.dT_out, rows, W, W, W,
+                                           (char*)side->ws + h.SL.wgrad, side->bytes - h.SL.wgrad, side->s, side->wgrad_wgs,
+                                           b.early_prep && b.n_prepped == b.n_deferred));
     } else {
-      CGAT_TRY(c.wgrad_batch(n_deferred, dp, dq, dr, dout, rows, W));
+      CGAT_TRY(c.wgrad_batch(b.n_deferred, b.dT_gu, b.dT_vin, b.dT_z, b.dT_out, rows, W));
     }
   }
-  if (dwb.n > 0 && !c.dry) {
+  if (b.dwb.n > 0 && !c.dry) {
     // HBM-bound, 0.7 ms for 24 products at 83 340 rows; in f16x3 on the main stream, right here.  On the side stream
     // (f16x3c) it goes BEHIND the dT launch: that launch must be resident before the caller's next kernel floods
     // the chip with small workgroups (its 132-KB workgroups are not placed while those keep arriving -- measured: 9.5 ms
     // instead of 6.2 when it started 0.7 ms later), and there it ends up beside the matrix-bound edge_ge (1.3 -> 2.5 ms)
     if (side && side->dw_side) {
       CGAT_TRY(side_wait());
-      CGAT_TRY(rows_dw128_batch_launch(dwb, (char*)side->ws + SL.dw, SL.wgrad - SL.dw, side->s));
+      CGAT_TRY(rows_dw128_batch_launch(b.dwb, (char*)side->ws + h.SL.dw, h.SL.wgrad - h.SL.dw, side->s));
     } else if (side) {   // main stream; the operands live in the side workspace either way
-      CGAT_TRY(rows_dw128_batch_launch(dwb, (char*)side->ws + SL.dw, SL.wgrad - SL.dw, c.s));
+      CGAT_TRY(rows_dw128_batch_launch(b.dwb, (char*)side->ws + h.SL.dw, h.SL.wgrad - h.SL.dw, c.s));
     } else {
-      CGAT_TRY(rows_dw128_batch_launch(dwb, c.scratch, c.scratch_bytes, c.s));
+      CGAT_TRY(rows_dw128_batch_launch(b.dwb, c.scratch, c.scratch_bytes, c.s));
     }
   }
+  return CGAT_OK;
+}
+
+static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const float* h0, const float* v,
+                              const float* saved, const float* g_y, float* g_h0, float* g_v,
+                              const cgat_hnet_grads* gr, const HnetSide* side = nullptr) {
+  HnetBwd b = {};
+  b.h = hnet_carve(c, rows, p, /*backward=*/true, side);
+  b.p = p; b.gr = gr; b.side = side;
+  const HnetPlan& h = b.h;
+  const int W = h.W;
+  b.dwb.rows = rows; b.dwb.ldg = W; b.dwb.ldx = W; b.dwb.ldo = W;
+  CGAT_TRY(hnet_prepare_weights(c, h, p, /*transposed=*/true));
+  CGAT_TRY(hnet_prepare_T_all(c, h, p, 1, 0, 2, &b.T_ready));   // the [a = i][b = o][c = k] operands
+  b.sv = hnet_saved(const_cast<float*>(saved), rows, p);
+  b.hin = p->damping ? b.sv.hin() : h0;
+  RUN(fill_launch(h.g_hin, 0.f, (long)h.rw, c.s));
+  b.early_prep = side && !c.dry && rows >= 16384;   // (small batches: 9 more launches cost more than they hide)
+  const float* gout = g_y;  // gradient wrt the output of predicted layer l (post norm for l < last)
+  for (int l = p->n_hyper - 1; l >= 0; --l) {
+    const float* gu = gout;  // gradient wrt the pre-norm output u_l
+    if (l < p->n_hyper - 1) {
+      float* gu_buf = c.dry ? nullptr : ((side ? (float*)side->ws : h.g_u) + (size_t)l * h.rw);
+      RUN(layernorm_tanh_bwd_launch(b.sv.u(l), b.sv.vin(l + 1), gout, gu_buf, rows, W, 1e-5f, c.s));
+      gu = gu_buf;
+    }
+    float* g_vin = (l == 0) ? g_v : h.gvin_buf[l & 1];  // gradient wrt this layer's input
+    float* g_t = c.dry ? nullptr : h.g_t_all + (h.chain_batch ? (size_t)l * h.rw : 0);
+    float* g_pre = c.dry ? nullptr : h.g_pre_all + (h.defer_dw ? (size_t)l * h.nfc1 * h.rw : 0);
+    const float* vin = (l == 0) ? v : b.sv.vin(l);
+    const float* z = c.dry ? nullptr : b.sv.act(l, p->n_fc - 1);
+    CGAT_TRY(hnet_head_param_grads(c, b, l, gu, vin, z));
+    CGAT_TRY(hnet_head_input_grads(c, b, l, gu, vin, z, g_t, g_vin));
+    bool chained = false;
+    CGAT_TRY(hnet_trunk_backward_chain(c, b, l, g_t, g_pre, &chained));
+    if (!chained) CGAT_TRY(hnet_trunk_backward_layers(c, b, l, g_t, g_pre));
+    gout = g_vin;
+  }
+  CGAT_TRY(hnet_backward_tail(c, b, h0, v, g_h0, g_v));
   return check_ws(c, "hnet_backward");
 }
 
 extern "C" size_t cgat_hnet_forward_workspace_bytes(int32_t rows, const cgat_hnet_params* p) {
-  Ctx c(nullptr, 0, true, nullptr);
-  hnet_forward_impl(c, rows, p, nullptr, nullptr, nullptr, nullptr);
-  return c.total();
+  return dry_total([&](Ctx& c) { return hnet_forward_impl(c, rows, p, nullptr, nullptr, nullptr, nullptr); });
 }
 extern "C" size_t cgat_hnet_backward_workspace_bytes(int32_t rows, const cgat_hnet_params* p) {
-  Ctx c(nullptr, 0, true, nullptr);
   cgat_hnet_grads g = {};
-  hnet_backward_impl(c, rows, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g);
-  return c.total();
+  return dry_total([&](Ctx& c) { return hnet_backward_impl(c, rows, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g); });
 }
 extern "C" int cgat_hnet_forward(int32_t rows, const cgat_hnet_params* p, const float* h0, const float* v, float* y,
                                  float* saved, void* ws, size_t ws_bytes, void* stream) {
   CGAT_TRY(hnet_check(rows, p));
-  Ctx dry(nullptr, 0, true, nullptr);
-  hnet_forward_impl(dry, rows, p, nullptr, nullptr, nullptr, nullptr);
-  if (ws_bytes < dry.total()) {
-    cgat_set_error("hnet_forward: workspace too small (%zu < %zu)", ws_bytes, dry.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  c.scratch_need = dry.scratch_need;
-  return hnet_forward_impl(c, rows, p, h0, v, y, saved);
+  return run_sized("hnet_forward", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return hnet_forward_impl(c, rows, p, h0, v, y, saved); });
 }
 extern "C" size_t cgat_hnet_backward_side_workspace_bytes(int32_t rows, const cgat_hnet_params* p) {
-  return hnet_side_ws_bytes(rows, p);
+  return hnet_side_layout(rows, p).total;
 }
 extern "C" int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_params* p, const float* h0, const float* v,
                                              const float* saved, const float* g_y, float* g_h0, float* g_v,
@@ -1885,16 +1398,8 @@ extern "C" int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_param
                                              void* side_ws, size_t side_ws_bytes, void* side_stream) {
   CGAT_TRY(hnet_check(rows, p));
   CGAT_CHECK_ARG(g, "hnet_backward: null grads");
-  CGAT_CHECK_ARG(side_stream && side_ws && side_ws_bytes >= hnet_side_ws_bytes(rows, p),
+  CGAT_CHECK_ARG(side_stream && side_ws && side_ws_bytes >= hnet_side_layout(rows, p).total,
                  "hnet_backward_overlapped: side stream / workspace missing or too small");
-  Ctx dry(nullptr, 0, true, nullptr);
-  hnet_backward_impl(dry, rows, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, g);
-  if (ws_bytes < dry.total()) {
-    cgat_set_error("hnet_backward: workspace too small (%zu < %zu)", ws_bytes, dry.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  c.scratch_need = dry.scratch_need;
   // 128 workgroups: half of the chip stays free for the main stream's HBM-bound kernels
   const int side_wgs = 128;
   // the batched dense-layer weight gradients: f16x3 -- main stream (behind the dT launch on the side stream the batch
@@ -1902,21 +1407,17 @@ extern "C" int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_param
   // twice as long and still running when edge_ge starts either way: 29.0-29.4 vs 29.5 ms, serial order 29.9-30.0;
   // profiles/r05_side_stream_sweep.txt)
   const int dw_side = mode_f16c() ? 1 : 0;
-  HnetSide side = {(hipStream_t)side_stream, side_ws, side_ws_bytes, side_wgs, dw_side};
-  return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g, &side);
+  const HnetSide side = {(hipStream_t)side_stream, side_ws, side_ws_bytes, side_wgs, dw_side};
+  // (sized as cgat_hnet_backward_workspace_bytes sizes it: the main workspace of the serial backward)
+  return run_sized("hnet_backward", ws, ws_bytes, stream, [&](Ctx& c) {
+    return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g, c.dry ? nullptr : &side);
+  });
 }
 extern "C" int cgat_hnet_backward(int32_t rows, const cgat_hnet_params* p, const float* h0, const float* v,
                                   const float* saved, const float* g_y, float* g_h0, float* g_v,
                                   const cgat_hnet_grads* g, void* ws, size_t ws_bytes, void* stream) {
   CGAT_TRY(hnet_check(rows, p));
   CGAT_CHECK_ARG(g, "hnet_backward: null grads");
-  Ctx dry(nullptr, 0, true, nullptr);
-  hnet_backward_impl(dry, rows, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, g);
-  if (ws_bytes < dry.total()) {
-    cgat_set_error("hnet_backward: workspace too small (%zu < %zu)", ws_bytes, dry.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  c.scratch_need = dry.scratch_need;
-  return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g);
+  return run_sized("hnet_backward", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g); });
 }

@@ -224,6 +224,53 @@ def _attn_params(x, edge_attr, H, ws_):
     return p, Hd
 
 
+def _attn_forward(x, edge_attr, plan, H, weights, *, save):
+    """The scalar-attention forward behind NodesAttentionFn and NodeLayerFn (save=True: the training forward with its saved
+    buffer) and nodes_attention_infer (save=False).  Returns (aggr, saved or None, the prepared weights)."""
+    A_in_w, A_out_w, M_in_w = weights[0], weights[2], weights[4]
+    ws_ = [_f32c(w.detach()) for w in weights]
+    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
+        raise ValueError("_attn_forward handles scalar attention (MH_A output_dim == 1)")
+    N, E = plan.N, plan.E
+    if x.shape[0] != N or edge_attr.shape[0] != E:
+        raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, edge_attr {tuple(edge_attr.shape)}")
+    p, Hd = _attn_params(x, edge_attr, H, ws_)
+    dev = x.device
+    saved = _scratch(lib.cgat_nodes_attention_saved_floats(N, E, H, Hd), torch.float32, dev) if save else None
+    aggr = torch.empty(N, x.shape[1], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        if save:
+            ws = workspace(lib.cgat_nodes_attention_forward_workspace_bytes(C.byref(plan.c), C.byref(p)), dev)
+            check(lib.cgat_nodes_attention_forward(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(edge_attr), _ptr(aggr),
+                                                   _ptr(saved), _ptr(ws), ws.numel(), _stream()),
+                  "cgat_nodes_attention_forward")
+        else:
+            ws = workspace(lib.cgat_nodes_attention_infer_workspace_bytes(C.byref(plan.c), C.byref(p)), dev)
+            check(lib.cgat_nodes_attention_infer(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(edge_attr), _ptr(aggr), _ptr(ws),
+                                                 ws.numel(), _stream()), "cgat_nodes_attention_infer")
+    if save and debug.recording():
+        debug.note_attention(A_in_w, M_in_w, plan, p, saved, 2 * H * Hd)
+    return aggr, saved, ws_
+
+
+def _attn_backward(x, edge_attr, plan, H, weights, saved, g_aggr, storage, stream):
+    """cgat_nodes_attention_backward on `stream` (a raw handle) under the forward's edge-storage mode; the workspace is
+    taken here, after whatever the caller has issued before.  Returns (g_x, g_e, parameter grads)."""
+    g_aggr = _f32c(g_aggr)
+    p, _ = _attn_params(x, edge_attr, H, weights)
+    dev = x.device
+    g_x, g_e = torch.empty_like(x), torch.empty_like(edge_attr)
+    grads = [_param_grad(w) for w in weights]
+    g = _lib.AttnGrads(*[t.data_ptr() for t in grads])
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_nodes_attention_backward_workspace_bytes(C.byref(plan.c), C.byref(p)), dev)
+        with _storage_of(storage):
+            check(lib.cgat_nodes_attention_backward(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(edge_attr), _ptr(saved),
+                                                    _ptr(g_aggr), _ptr(g_x), _ptr(g_e), C.byref(g), _ptr(ws), ws.numel(),
+                                                    stream), "cgat_nodes_attention_backward")
+    return g_x, g_e, grads
+
+
 class NodesAttentionFn(torch.autograd.Function):
     """aggr[n] = mean_h sum_{e: dst(e)=n} softmax_dst(MH_A(m_e))[h] * MH_M(m_e)[h]
     (reference CGAT.py:319-329 + PyG aggregate), scalar attention."""
@@ -233,43 +280,15 @@ class NodesAttentionFn(torch.autograd.Function):
         weights = [A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b]
         _require_gpu(x, edge_attr, *weights)
         x, edge_attr = _f32c(x), _f32c(edge_attr)
-        weights = [_f32c(w.detach()) for w in weights]
-        if A_out_w.numel() != H * (A_in_w.shape[0] // H):
-            raise ValueError("NodesAttentionFn handles scalar attention (MH_A output_dim == 1)")
-        N, E = plan.N, plan.E
-        if x.shape[0] != N or edge_attr.shape[0] != E:
-            raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, edge_attr {tuple(edge_attr.shape)}")
-        p, Hd = _attn_params(x, edge_attr, H, weights)
-        dev = x.device
-        saved = _scratch(lib.cgat_nodes_attention_saved_floats(N, E, H, Hd), torch.float32, dev)
-        aggr = torch.empty(N, x.shape[1], dtype=torch.float32, device=dev)
-        ws = workspace(lib.cgat_nodes_attention_forward_workspace_bytes(C.byref(plan.c), C.byref(p)), dev)
-        with torch.cuda.device(dev):
-            check(lib.cgat_nodes_attention_forward(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(edge_attr), _ptr(aggr),
-                                                   _ptr(saved), _ptr(ws), ws.numel(), _stream()),
-                  "cgat_nodes_attention_forward")
+        aggr, saved, weights = _attn_forward(x, edge_attr, plan, H, weights, save=True)
         ctx.plan, ctx.H, ctx.storage = plan, H, lib.cgat_get_edge_storage()
         ctx.save_for_backward(x, edge_attr, saved, *weights)
-        if debug.recording():
-            debug.note_attention(A_in_w, M_in_w, plan, p, saved, 2 * H * Hd)
         return aggr
 
     @staticmethod
     def backward(ctx, g_aggr):
         x, edge_attr, saved, *weights = ctx.saved_tensors
-        plan, H = ctx.plan, ctx.H
-        g_aggr = _f32c(g_aggr)
-        p, Hd = _attn_params(x, edge_attr, H, weights)
-        dev = x.device
-        g_x = torch.empty_like(x)
-        g_e = torch.empty_like(edge_attr)
-        grads = [_param_grad(w) for w in weights]
-        g = _lib.AttnGrads(*[t.data_ptr() for t in grads])
-        ws = workspace(lib.cgat_nodes_attention_backward_workspace_bytes(C.byref(plan.c), C.byref(p)), dev)
-        with torch.cuda.device(dev), _storage_of(ctx.storage):
-            check(lib.cgat_nodes_attention_backward(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(edge_attr), _ptr(saved),
-                                                    _ptr(g_aggr), _ptr(g_x), _ptr(g_e), C.byref(g), _ptr(ws),
-                                                    ws.numel(), _stream()), "cgat_nodes_attention_backward")
+        g_x, g_e, grads = _attn_backward(x, edge_attr, ctx.plan, ctx.H, weights, saved, g_aggr, ctx.storage, _stream())
         return (g_x, g_e, None, None, *grads)
 
 
@@ -294,21 +313,7 @@ def nodes_attention_infer(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w, A_out_
     buffers from workspace(), nothing allocated but the result.  Never records a backward."""
     weights = [A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b]
     _require_gpu(x, edge_attr, *weights)
-    x, edge_attr = _f32c(x.detach()), _f32c(edge_attr.detach())
-    weights = [_f32c(w.detach()) for w in weights]
-    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
-        raise ValueError("nodes_attention_infer handles scalar attention (MH_A output_dim == 1)")
-    N, E = plan.N, plan.E
-    if x.shape[0] != N or edge_attr.shape[0] != E:
-        raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, edge_attr {tuple(edge_attr.shape)}")
-    p, Hd = _attn_params(x, edge_attr, H, weights)
-    dev = x.device
-    aggr = torch.empty(N, x.shape[1], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws = workspace(lib.cgat_nodes_attention_infer_workspace_bytes(C.byref(plan.c), C.byref(p)), dev)
-        check(lib.cgat_nodes_attention_infer(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(edge_attr), _ptr(aggr), _ptr(ws),
-                                             ws.numel(), _stream()), "cgat_nodes_attention_infer")
-    return aggr
+    return _attn_forward(_f32c(x.detach()), _f32c(edge_attr.detach()), plan, H, weights, save=False)[0]
 
 
 def infer_route(x, edge_attr, params):
@@ -321,6 +326,25 @@ def infer_route(x, edge_attr, params):
     return not any(t is not None and t.requires_grad for t in (x, edge_attr, *params))
 
 
+def _edge_hidden_forward(who, x, edge_attr, plan, w_in, b_in):
+    """cgat_edge_hidden_forward behind EdgeHiddenFn and EdgeHiddenHeadsFn.  Returns the prepared operands, hidden and
+    hmax = max |hidden| (the fp16 scale of the second layers)."""
+    x, edge_attr, w_in, b_in = _f32c(x), _f32c(edge_attr), _f32c(w_in.detach()), _f32c(b_in.detach())
+    N, E = plan.N, plan.E
+    Cn, Ce, W2 = x.shape[1], edge_attr.shape[1], w_in.shape[0]
+    if x.shape[0] != N or edge_attr.shape[0] != E or w_in.shape[1] != 2 * Cn + Ce or b_in.numel() != W2:
+        raise ValueError(f"{who}: shapes do not match the plan / the stacked first-layer weight")
+    dev = x.device
+    hidden = torch.empty(E, W2, dtype=torch.float32, device=dev)
+    hmax = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = workspace(lib.cgat_edge_hidden_forward_workspace_bytes(C.byref(plan.c), Cn, Ce, W2), dev)
+    with torch.cuda.device(dev):
+        check(lib.cgat_edge_hidden_forward(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(b_in), _ptr(x),
+                                           _ptr(edge_attr), _ptr(hidden), _ptr(hmax), _ptr(ws), ws.numel(), _stream()),
+              "cgat_edge_hidden_forward")
+    return x, edge_attr, w_in, hidden, hmax
+
+
 class EdgeHiddenFn(torch.autograd.Function):
     """hidden[t] = LeakyReLU(w_in [x_i ; edge_attr ; x_j] + b_in) in destination-sorted slot order t (plan.dst_perm):
     the first layer of both message networks (reference CGAT.py:96,105-108 on the concatenated message of 316-318)
@@ -329,19 +353,7 @@ class EdgeHiddenFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, edge_attr, plan, w_in, b_in):
         _require_gpu(x, edge_attr, w_in, b_in)
-        x, edge_attr, w_in, b_in = _f32c(x), _f32c(edge_attr), _f32c(w_in.detach()), _f32c(b_in.detach())
-        N, E = plan.N, plan.E
-        Cn, Ce, W2 = x.shape[1], edge_attr.shape[1], w_in.shape[0]
-        if x.shape[0] != N or edge_attr.shape[0] != E or w_in.shape[1] != 2 * Cn + Ce or b_in.numel() != W2:
-            raise ValueError("EdgeHiddenFn: shapes do not match the plan / the stacked first-layer weight")
-        dev = x.device
-        hidden = torch.empty(E, W2, dtype=torch.float32, device=dev)
-        hmax = torch.empty(1, dtype=torch.float32, device=dev)     # max |hidden|: the fp16 scale of the second layers
-        ws = workspace(lib.cgat_edge_hidden_forward_workspace_bytes(C.byref(plan.c), Cn, Ce, W2), dev)
-        with torch.cuda.device(dev):
-            check(lib.cgat_edge_hidden_forward(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(b_in), _ptr(x),
-                                               _ptr(edge_attr), _ptr(hidden), _ptr(hmax), _ptr(ws), ws.numel(), _stream()),
-                  "cgat_edge_hidden_forward")
+        x, edge_attr, w_in, hidden, hmax = _edge_hidden_forward("EdgeHiddenFn", x, edge_attr, plan, w_in, b_in)
         ctx.plan = plan
         ctx.save_for_backward(x, edge_attr, w_in, hidden)
         ctx.mark_non_differentiable(hmax)
@@ -449,6 +461,61 @@ def aux_streams():
     return list(_branch_streams.values()) + list(_side_streams.values())
 
 
+def _hnet_forward(h0, v, damping, n_fc, n_hyper, flat):
+    """cgat_hnet_forward behind HNetFn and NodeLayerFn.  Returns (y, saved, prepared damping or None, prepared flat)."""
+    _require_gpu(h0, v, *flat)
+    flat = [_f32c(t.detach()) for t in flat]
+    d = None if damping is None else _f32c(damping.detach())
+    rows, W = v.shape
+    if h0.shape != v.shape:
+        raise ValueError("hypernetwork: h0 and v must both be [rows, W]")
+    for l in range(n_hyper):
+        hw = flat[l * (2 * n_fc + 2) + 2 * n_fc]
+        if tuple(hw.shape) != (W * W + W, W):
+            raise ValueError(f"hypernetwork head weight must be [{W * W + W}, {W}] (all widths equal), got {tuple(hw.shape)}")
+    p = _hnet_struct(_lib.HnetParams, W, n_fc, n_hyper, flat, d)
+    dev = v.device
+    saved = _scratch(lib.cgat_hnet_saved_floats(rows, C.byref(p)), torch.float32, dev)
+    y = torch.empty_like(v)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_hnet_forward_workspace_bytes(rows, C.byref(p)), dev)
+        check(lib.cgat_hnet_forward(rows, C.byref(p), _ptr(h0), _ptr(v), _ptr(y), _ptr(saved), _ptr(ws), ws.numel(),
+                                    _stream()), "cgat_hnet_forward")
+    return y, saved, d, flat
+
+
+def _hnet_backward(h0, v, saved, d, flat, n_fc, n_hyper, g_y, side=None):
+    """cgat_hnet_backward, or -- side = (main stream, side stream) -- cgat_hnet_backward_overlapped, which leaves the
+    weight-gradient contractions on the side stream for the caller to join.  Returns (g_h0, g_v, g_d or None, grads,
+    side_ws): the caller MUST keep side_ws alive until the main stream has waited for the side stream."""
+    rows, W = v.shape
+    g_y = _f32c(g_y)
+    p = _hnet_struct(_lib.HnetParams, W, n_fc, n_hyper, flat, d)
+    grads = [_param_grad(t) for t in flat]
+    g_d = torch.empty_like(d) if d is not None else None
+    g = _hnet_struct(_lib.HnetGrads, W, n_fc, n_hyper, grads, g_d)
+    g_h0, g_v = torch.empty_like(h0), torch.empty_like(v)
+    dev = v.device
+    side_ws = None
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_hnet_backward_workspace_bytes(rows, C.byref(p)), dev)
+        if side is None:
+            check(lib.cgat_hnet_backward(rows, C.byref(p), _ptr(h0), _ptr(v), _ptr(saved), _ptr(g_y), _ptr(g_h0),
+                                         _ptr(g_v), C.byref(g), _ptr(ws), ws.numel(), _stream()), "cgat_hnet_backward")
+        else:
+            main, s2 = side
+            # side_ws (the side stream's inputs and scratch: g_u, g_pre, the dw slabs, the dT workspace) is its own
+            # allocation: the attention backward reuses the cached main workspace while the side stream is still running.
+            # It is allocated on the main stream and read and written on the side stream, so it has to outlive the join:
+            # dropped earlier, the allocator hands its block to the next main-stream allocation
+            side_ws = _scratch(lib.cgat_hnet_backward_side_workspace_bytes(rows, C.byref(p)), torch.uint8, dev)
+            check(lib.cgat_hnet_backward_overlapped(rows, C.byref(p), _ptr(h0), _ptr(v), _ptr(saved), _ptr(g_y),
+                                                    _ptr(g_h0), _ptr(g_v), C.byref(g), _ptr(ws), ws.numel(),
+                                                    main.cuda_stream, _ptr(side_ws), side_ws.numel(), s2.cuda_stream),
+                  "cgat_hnet_backward_overlapped")
+    return g_h0, g_v, g_d, grads, side_ws
+
+
 class HNetFn(torch.autograd.Function):
     """y = HyperFC(hyper_input)(v)  with hyper_input = h0 (H_Net_0) or d*h0 + (1-d)*v (H_Net);
     reference Hypernetworksmp.py:257-313.  `flat` = per predicted layer: n_fc trunk weights,
@@ -456,47 +523,17 @@ class HNetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h0, v, damping, n_fc, n_hyper, *flat):
-        _require_gpu(h0, v, *flat)
         h0, v = _f32c(h0), _f32c(v)
-        flat = [_f32c(t.detach()) for t in flat]
-        d = None if damping is None else _f32c(damping.detach())
-        rows, W = v.shape
-        if h0.shape != v.shape:
-            raise ValueError("hypernetwork: h0 and v must both be [rows, W]")
-        for l in range(n_hyper):
-            hw = flat[l * (2 * n_fc + 2) + 2 * n_fc]
-            if tuple(hw.shape) != (W * W + W, W):
-                raise ValueError(f"hypernetwork head weight must be [{W * W + W}, {W}] (all widths equal), got {tuple(hw.shape)}")
-        p = _hnet_struct(_lib.HnetParams, W, n_fc, n_hyper, flat, d)
-        dev = v.device
-        saved = _scratch(lib.cgat_hnet_saved_floats(rows, C.byref(p)), torch.float32, dev)
-        y = torch.empty_like(v)
-        ws = workspace(lib.cgat_hnet_forward_workspace_bytes(rows, C.byref(p)), dev)
-        with torch.cuda.device(dev):
-            check(lib.cgat_hnet_forward(rows, C.byref(p), _ptr(h0), _ptr(v), _ptr(y), _ptr(saved), _ptr(ws), ws.numel(),
-                                        _stream()), "cgat_hnet_forward")
+        y, saved, d, flat = _hnet_forward(h0, v, damping, n_fc, n_hyper, flat)
         ctx.n_fc, ctx.n_hyper, ctx.has_d = n_fc, n_hyper, d is not None
-        ctx.save_for_backward(h0, v, saved, *( [d] if d is not None else []), *flat)
+        ctx.save_for_backward(h0, v, saved, *([d] if d is not None else []), *flat)
         return y
 
     @staticmethod
     def backward(ctx, g_y):
         h0, v, saved, *rest = ctx.saved_tensors
         d = rest.pop(0) if ctx.has_d else None
-        flat = rest
-        n_fc, n_hyper = ctx.n_fc, ctx.n_hyper
-        rows, W = v.shape
-        g_y = _f32c(g_y)
-        p = _hnet_struct(_lib.HnetParams, W, n_fc, n_hyper, flat, d)
-        grads = [_param_grad(t) for t in flat]
-        g_d = torch.empty_like(d) if d is not None else None
-        g = _hnet_struct(_lib.HnetGrads, W, n_fc, n_hyper, grads, g_d)
-        g_h0, g_v = torch.empty_like(h0), torch.empty_like(v)
-        dev = v.device
-        ws = workspace(lib.cgat_hnet_backward_workspace_bytes(rows, C.byref(p)), dev)
-        with torch.cuda.device(dev):
-            check(lib.cgat_hnet_backward(rows, C.byref(p), _ptr(h0), _ptr(v), _ptr(saved), _ptr(g_y), _ptr(g_h0),
-                                         _ptr(g_v), C.byref(g), _ptr(ws), ws.numel(), _stream()), "cgat_hnet_backward")
+        g_h0, g_v, g_d, grads, _ = _hnet_backward(h0, v, saved, d, rest, ctx.n_fc, ctx.n_hyper, g_y)
         return (g_h0, g_v, g_d, None, None, *grads)
 
 
@@ -509,35 +546,15 @@ class NodeLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, edge_attr, h0, plan, H, damping, n_fc, n_hyper, *params):
-        attn_w, flat = list(params[:8]), list(params[8:])
-        _require_gpu(x, edge_attr, h0, *attn_w, *flat)
+        _require_gpu(x, edge_attr, h0, *params)
         x, edge_attr, h0 = _f32c(x), _f32c(edge_attr), _f32c(h0)
-        attn_w = [_f32c(w.detach()) for w in attn_w]
-        flat = [_f32c(t.detach()) for t in flat]
-        d = None if damping is None else _f32c(damping.detach())
-        N, E = plan.N, plan.E
-        if x.shape[0] != N or edge_attr.shape[0] != E or h0.shape != x.shape:
+        if x.shape[0] != plan.N or edge_attr.shape[0] != plan.E or h0.shape != x.shape:
             raise ValueError("NodeLayerFn: shapes do not match the plan")
-        dev = x.device
-        pa, Hd = _attn_params(x, edge_attr, H, attn_w)
-        W = x.shape[1]
-        ph = _hnet_struct(_lib.HnetParams, W, n_fc, n_hyper, flat, d)
-        saved_a = _scratch(lib.cgat_nodes_attention_saved_floats(N, E, H, Hd), torch.float32, dev)
-        saved_h = _scratch(lib.cgat_hnet_saved_floats(N, C.byref(ph)), torch.float32, dev)
-        aggr, y = torch.empty(N, W, dtype=torch.float32, device=dev), torch.empty(N, W, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws = workspace(lib.cgat_nodes_attention_forward_workspace_bytes(C.byref(plan.c), C.byref(pa)), dev)
-            check(lib.cgat_nodes_attention_forward(C.byref(plan.c), C.byref(pa), _ptr(x), _ptr(edge_attr), _ptr(aggr),
-                                                   _ptr(saved_a), _ptr(ws), ws.numel(), _stream()),
-                  "cgat_nodes_attention_forward")
-            ws = workspace(lib.cgat_hnet_forward_workspace_bytes(N, C.byref(ph)), dev)
-            check(lib.cgat_hnet_forward(N, C.byref(ph), _ptr(h0), _ptr(aggr), _ptr(y), _ptr(saved_h), _ptr(ws), ws.numel(),
-                                        _stream()), "cgat_hnet_forward")
+        aggr, saved_a, attn_w = _attn_forward(x, edge_attr, plan, H, params[:8], save=True)
+        y, saved_h, d, flat = _hnet_forward(h0, aggr, damping, n_fc, n_hyper, params[8:])
         ctx.plan, ctx.H, ctx.n_fc, ctx.n_hyper, ctx.has_d = plan, H, n_fc, n_hyper, d is not None
         ctx.storage = lib.cgat_get_edge_storage()
         ctx.save_for_backward(x, edge_attr, h0, aggr, saved_a, saved_h, *([d] if d is not None else []), *attn_w, *flat)
-        if debug.recording():
-            debug.note_attention(params[0], params[4], plan, pa, saved_a, 2 * H * Hd)
         return y
 
     @staticmethod
@@ -545,36 +562,18 @@ class NodeLayerFn(torch.autograd.Function):
         x, edge_attr, h0, aggr, saved_a, saved_h, *rest = ctx.saved_tensors
         d = rest.pop(0) if ctx.has_d else None
         attn_w, flat = rest[:8], rest[8:]
-        plan, H, n_fc, n_hyper = ctx.plan, ctx.H, ctx.n_fc, ctx.n_hyper
-        N, W = x.shape
         dev = x.device
-        g_y = _f32c(g_y)
-        ph = _hnet_struct(_lib.HnetParams, W, n_fc, n_hyper, flat, d)
-        g_flat = [_param_grad(t) for t in flat]
-        g_d = torch.empty_like(d) if d is not None else None
-        gh = _hnet_struct(_lib.HnetGrads, W, n_fc, n_hyper, g_flat, g_d)
-        g_h0, g_aggr = torch.empty_like(h0), torch.empty_like(aggr)
-        pa, Hd = _attn_params(x, edge_attr, H, attn_w)
-        g_x, g_e = torch.empty_like(x), torch.empty_like(edge_attr)
-        g_attn = [_param_grad(w) for w in attn_w]
-        ga = _lib.AttnGrads(*[t.data_ptr() for t in g_attn])
         main = torch.cuda.current_stream(dev)
         s2 = side_stream(dev)
+        # the hypernetwork's workspace is taken and its overlapped call issued first, then the attention backward takes
+        # its workspace from the same cache (main-stream order; what the side stream reads is its own allocation)
+        g_h0, g_aggr, g_d, g_flat, side_ws = _hnet_backward(h0, aggr, saved_h, d, flat, ctx.n_fc, ctx.n_hyper, g_y,
+                                                            side=(main, s2))
+        g_x, g_e, g_attn = _attn_backward(x, edge_attr, ctx.plan, ctx.H, attn_w, saved_a, g_aggr, ctx.storage,
+                                          main.cuda_stream)
         with torch.cuda.device(dev):
-            # side_ws (the side stream's inputs and scratch) is its own allocation: the attention backward reuses the
-            # cached main workspace while the side stream is still running
-            ws_h = workspace(lib.cgat_hnet_backward_workspace_bytes(N, C.byref(ph)), dev)
-            side_ws = _scratch(lib.cgat_hnet_backward_side_workspace_bytes(N, C.byref(ph)), torch.uint8, dev)
-            check(lib.cgat_hnet_backward_overlapped(N, C.byref(ph), _ptr(h0), _ptr(aggr), _ptr(saved_h), _ptr(g_y),
-                                                    _ptr(g_h0), _ptr(g_aggr), C.byref(gh), _ptr(ws_h), ws_h.numel(),
-                                                    main.cuda_stream, _ptr(side_ws), side_ws.numel(), s2.cuda_stream),
-                  "cgat_hnet_backward_overlapped")
-            ws_a = workspace(lib.cgat_nodes_attention_backward_workspace_bytes(C.byref(plan.c), C.byref(pa)), dev)
-            with _storage_of(ctx.storage):
-                check(lib.cgat_nodes_attention_backward(C.byref(plan.c), C.byref(pa), _ptr(x), _ptr(edge_attr), _ptr(saved_a),
-                                                        _ptr(g_aggr), _ptr(g_x), _ptr(g_e), C.byref(ga), _ptr(ws_a),
-                                                        ws_a.numel(), main.cuda_stream), "cgat_nodes_attention_backward")
             main.wait_stream(s2)     # every gradient is complete, in stream order, when this node returns
+        del side_ws                  # (held until here: the side stream was using it)
         return (g_x, g_e, g_h0, None, None, g_d, None, None, *g_attn, *g_flat)
 
 
@@ -723,19 +722,8 @@ class EdgeHiddenHeadsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, edge_attr, plan, w_in, b_in, wa, ba, wm, bm, H, Hd, Co):
         _require_gpu(x, edge_attr, w_in, b_in, wa, wm)
-        x, edge_attr, w_in, b_in = _f32c(x), _f32c(edge_attr), _f32c(w_in.detach()), _f32c(b_in.detach())
-        N, E = plan.N, plan.E
-        Cn, Ce, W2 = x.shape[1], edge_attr.shape[1], w_in.shape[0]
-        if x.shape[0] != N or edge_attr.shape[0] != E or w_in.shape[1] != 2 * Cn + Ce or b_in.numel() != W2:
-            raise ValueError("EdgeHiddenHeadsFn: shapes do not match the plan / the stacked first-layer weight")
-        dev = x.device
-        hidden = torch.empty(E, W2, dtype=torch.float32, device=dev)
-        hmax = torch.empty(1, dtype=torch.float32, device=dev)
-        ws = workspace(lib.cgat_edge_hidden_forward_workspace_bytes(C.byref(plan.c), Cn, Ce, W2), dev)
-        with torch.cuda.device(dev):
-            check(lib.cgat_edge_hidden_forward(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(b_in), _ptr(x),
-                                               _ptr(edge_attr), _ptr(hidden), _ptr(hmax), _ptr(ws), ws.numel(), _stream()),
-                  "cgat_edge_hidden_forward")
+        x, edge_attr, w_in, hidden, hmax = _edge_hidden_forward("EdgeHiddenHeadsFn", x, edge_attr, plan, w_in, b_in)
+        E = plan.E
         cos = _cos(Co, 2)
         ws_ = [_f32c(w.detach().reshape(H * co, Hd)) for w, co in zip((wa, wm), cos)]
         bs_ = [None if b is None else _f32c(b.detach()) for b in (ba, bm)]

@@ -199,6 +199,36 @@ def test_nodes_layer_other_widths_vs_oracle(C, vector):
                          lambda: O.GATConvNodes(C, C, C, 3, concat=True, vector_attention=vector), inputs, call)
 
 
+def test_single_predicted_layer_vs_oracle():
+    """A hypernetwork of ONE predicted layer (n_hyper == 1; the module API never builds fewer than two): nothing is
+    batched across predicted layers, no LayerNorm, the last layer's gradient is the first's.  HNetFn on one HyperLinear
+    against the oracle's predict + apply, same parameters through the shared state_dict layout."""
+    import cgat_amd as P
+    from cgat_amd import hypernet, ops
+    from oracle import cgat_oracle as O
+    W, rows, hidden_layers = 128, 130, 3
+
+    class Prod(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.hl = hypernet.HyperLinear(W, W, W, hidden_layers, W)
+
+        def forward(self, h0, v):
+            return ops.HNetFn.apply(h0, v, None, 1 + hidden_layers, 1, *self.hl.flat_params())
+
+    class Orac(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.hl = O.HyperLinear(W, W, W, hidden_layers, W)
+
+        def forward(self, h0, v):
+            Wp, bp = self.hl.predict(h0)
+            return O.HyperLinear.apply_predicted(Wp, bp, v.view(v.shape[0], 1, W)).view(v.shape[0], W)
+    g = torch.Generator().manual_seed(31)
+    inputs = {"h0": torch.randn(rows, W, generator=g), "v": torch.randn(rows, W, generator=g)}
+    _compare_with_oracle(Prod, Orac, inputs, lambda m, i: m(i["h0"], i["v"]))
+
+
 @pytest.mark.parametrize("first", [True, False])
 def test_nodes_layer_vs_oracle_random_init(first):
     """Config 1 -> 2 of BASELINE.json at a size the oracle finishes in seconds: 60 crystals
@@ -587,27 +617,31 @@ def test_side_stream_equals_serial():
     weight-gradient sums differs): 1e-5 max-norm relative on every gradient."""
     import cgat_amd as P
     from cgat_amd import ops
-    b, _ = P.synthetic_batch(300, 20, 12, seed=4)
-    dev = "cuda:0"
-    torch.manual_seed(3)
-    m = P.GATConvNodes(128, 128, 128, 3, concat=True).to(dev)
-    g = torch.Generator().manual_seed(9)
-    N, E = b.num_nodes, b.edge_index.shape[1]
-    x, e, x0 = (torch.randn(s, 128, generator=g).to(dev) for s in (N, E, N))
-    ei = b.edge_index.to(dev)
-    was = ops.get_overlap_wgrad()                       # the raw tri-state, so that the per-mode default survives (ADVICE r4)
-    res = {}
-    try:
-        for mode in (True, False):
-            ops.set_overlap_wgrad(mode)
-            xx, ee = x.clone().requires_grad_(True), e.clone().requires_grad_(True)
-            y = m(xx, ei, ee, x0)
-            gr = torch.autograd.grad(y.square().sum(), [xx, ee] + list(m.parameters()))
-            res[mode] = [y.detach().cpu().numpy()] + [t.detach().cpu().numpy() for t in gr]
-    finally:
-        ops.set_overlap_wgrad(was)
-    for a, bb in zip(res[True], res[False]):
-        assert maxnorm_rel(a, bb) <= 1e-5
+    # 6 000 atoms: below the row count at which the overlapped backward prepares the dT operands early on the side
+    # stream; 16 400 atoms: above it
+    for crystals in (300, 820):
+        b, _ = P.synthetic_batch(crystals, 20, 12, seed=4)
+        dev = "cuda:0"
+        torch.manual_seed(3)
+        m = P.GATConvNodes(128, 128, 128, 3, concat=True).to(dev)
+        g = torch.Generator().manual_seed(9)
+        N, E = b.num_nodes, b.edge_index.shape[1]
+        assert (N >= 16384) == (crystals == 820)
+        x, e, x0 = (torch.randn(s, 128, generator=g).to(dev) for s in (N, E, N))
+        ei = b.edge_index.to(dev)
+        was = ops.get_overlap_wgrad()                   # the raw tri-state, so that the per-mode default survives (ADVICE r4)
+        res = {}
+        try:
+            for mode in (True, False):
+                ops.set_overlap_wgrad(mode)
+                xx, ee = x.clone().requires_grad_(True), e.clone().requires_grad_(True)
+                y = m(xx, ei, ee, x0)
+                gr = torch.autograd.grad(y.square().sum(), [xx, ee] + list(m.parameters()))
+                res[mode] = [y.detach().cpu().numpy()] + [t.detach().cpu().numpy() for t in gr]
+        finally:
+            ops.set_overlap_wgrad(was)
+        for a, bb in zip(res[True], res[False]):
+            assert maxnorm_rel(a, bb) <= 1e-5
 
 
 def _determinism_body(P):
