@@ -136,6 +136,10 @@ PROTOTYPES = {
     "cgat_debug_edge_ge_rebuilt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "cgat_debug_edge_ge_rebuilt": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                              C.c_size_t, vp]),
+    "cgat_debug_edge_gw_force_six": (C.c_int32, [C.c_int32]),
+    "cgat_debug_edge_gw_rebuilt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "cgat_debug_edge_gw_rebuilt": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             vp, C.POINTER(C.c_int32), vp, C.c_size_t, vp]),
     "cgat_hnet_saved_floats": (C.c_size_t, [C.c_int32, C.POINTER(HnetParams)]),
     "cgat_hnet_forward_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(HnetParams)]),
     "cgat_hnet_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(HnetParams)]),

@@ -399,12 +399,28 @@ __global__ __launch_bounds__(512, 2) void edge_ge_kernel(const float* __restrict
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-template <int PASSES, bool RC = false>   // RC: the gZ tile is rebuilt from its ingredients (struct EdgeRC), not read
+// BP (with RC, six passes: scalar attention in the 24-bit modes at Hd = 256; edge_gw_bitplane below): the ATTENTION half
+// of the columns runs on the stored bit alone.  There gZ[t, (h, c)] = ga[t, h] wA[h, c] d, d = 1 or 0.01 by the bit m, so
+// with the coefficient moved onto the OTHER operand, e'_h[t, :] = fl(ga[t, h] e[perm[t], :]),
+//     g_W_e[(h, c), :] = wA[h, c] (P + 0.01 (cs_h - P)),   P[(h, c), :] = sum_t m[t, (h, c)] e'_h[t, :],   cs_h = sum_t e'_h[t, :].
+// m is exact in ONE bf16 plane: P takes three passes (the planes of e') instead of six, the Gs image holds one plane of
+// shifted bits -- no coefficient, no wA, no multiply, no split --, and wA and the 0.01 fold are applied once per output by
+// the reducer (edge_gw_bit_reduce_kernel).  A head's 256 columns are one column-block pair, so an attention workgroup
+// needs e' of ONE head: it builds the planes itself from 32 gathered fp32 rows of e per k-step (8 elements per thread)
+// and writes them to Es in the order the MFMA loop reads; it does not read Eq.  cs_h: per-thread partial sums of the
+// rounded e' (one per wave's slot quad and output), added to the workgroup's cs rows at every flush.
+// One launch holds both halves: workgroups [0, S * message pairs) are the message pairs on S ranges (the body below,
+// XCD-aware order as before), the SA * H behind them the attention pairs on SA longer ranges (same order: the H
+// workgroups of a range share the gathered e rows from one L2).  SA : S follows the measured cost per k-step.
+template <int PASSES, bool RC = false, bool BP = false>   // RC: the gZ tile is rebuilt from its ingredients (struct EdgeRC)
 __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict__ gZ, long ldg, long gzb,
                                                          const uint4* __restrict__ Eq, float* __restrict__ slab,
                                                          int E, int ncb, int nsteps, int S,
                                                          const float* __restrict__ gmax, const float* __restrict__ emax,
-                                                         const EdgeRC rc) {
+                                                         const EdgeRC rc, const float* __restrict__ erows, long lde,
+                                                         const int* __restrict__ perm, int SA,
+                                                         float* __restrict__ slabA, float* __restrict__ csl) {
+  static_assert(!BP || (RC && PASSES == 6), "the bit-plane body belongs to the six-pass rebuilt form");
   // PASSES == 2: two fp16 planes, three passes; both operands are indexed by the reduction index (the edge slot), so
   // both scales are per tensor: gmax[0] = max |gZ| (from its producer), emax[0] = max |e| (the planes carry 2^k e)
   // PASSES == 1 (edge storage "bf16-mma"): one bf16 pass on the leading planes of both operands (see edge_ge_kernel)
@@ -425,30 +441,35 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n16 = lane & 15, kg = lane >> 4;
   const int grp = wave >> 2, wq = wave & 3;              // column block of the pair, 32-column slice in it
-  const int npair = ncb / 2;
+  const int cbA = BP ? rc.HHd / 128 : 0;                // BP: the attention half's column blocks are not this body's
+  const int npair = (ncb - cbA) / 2;
   // XCD-aware order: consecutive workgroup ids go to different XCDs (own L2 each), and the npair workgroups of one range
   // read the same e planes.  The first 8 * floor(S / 8) ranges are dealt out so that a range's workgroups sit on ONE XCD,
   // next to each other in its dispatch order (the planes then come from HBM once and from that L2 afterwards; in plain
   // order every column-block pair fetched them into its own XCD: 6.5 GB of FETCH_SIZE for 0.77 GB of planes at
   // W2 = 1536); the remaining S % 8 ranges keep the plain order.  Same number of workgroups either way.
   int pair, split;
+  const bool attn = BP && (int)blockIdx.x >= S * npair;  // (workgroup-uniform)
   {
-    const int s8 = S >> 3, body = 8 * s8 * npair;
-    if ((int)blockIdx.x < body) {
-      const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-      pair = j % npair;
-      split = xcd * s8 + j / npair;
+    const int wg = attn ? blockIdx.x - S * npair : blockIdx.x;   // (a multiple of 8 apart or not: equal wg & 7 = one XCD)
+    const int Sx = attn ? SA : S, np = attn ? rc.H : npair;
+    const int s8 = Sx >> 3, body = 8 * s8 * np;
+    if (wg < body) {
+      const int xcd = wg & 7, j = wg >> 3;
+      pair = j % np;
+      split = xcd * s8 + j / np;
     } else {
-      const int r = blockIdx.x - body;
-      pair = r % npair;
-      split = 8 * s8 + r / npair;
+      const int r = wg - body;
+      pair = r % np;
+      split = 8 * s8 + r / np;
     }
   }
+  const int Sr = attn ? SA : S;                          // ranges this workgroup's half is dealt over
   // ranges in units of two k-steps (the loop is unrolled by two without a tail); a k-step past nsteps holds slots >= E,
   // which contribute zeros, and its e planes are the zero padding of the last 128-slot block
   const int npairs = (nsteps + 1) / 2;
-  const int ks0 = 2 * (int)((long)npairs * split / S), ks1 = 2 * (int)((long)npairs * (split + 1) / S);
-  const int cb128 = pair * 2 + grp;
+  const int ks0 = 2 * (int)((long)npairs * split / Sr), ks1 = 2 * (int)((long)npairs * (split + 1) / Sr);
+  const int cb128 = (attn ? 0 : cbA) + pair * 2 + grp;
   const float* gblk = gZ + (long)cb128 * gzb;
   const int gt = tid & 255;                              // thread within the column block's group
   // RC: this thread's four columns 128 cb128 + 4 (gt & 31) never change: head, half, mask word and bit offset are fixed
@@ -602,7 +623,9 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
     P_ = mma16<F16>(F1_, Q1_, P_);                                                                       \
   }
   // the workgroup's slab tile: rows = its 256 columns of gZ, 128 outputs each
-  float* tile = slab + ((long)split * ncb * 128 + (long)cb128 * 128 + 32 * wq) * 128;
+  // (BP: message slabs hold the message columns only, [S][W2 - HHd][128]; attention slabs [SA][HHd][128] at slabA)
+  float* tile = attn ? slabA + ((long)split * cbA * 128 + (long)cb128 * 128 + 32 * wq) * 128
+                     : slab + ((long)split * (ncb - cbA) * 128 + (long)(cb128 - cbA) * 128 + 32 * wq) * 128;
 #define GW_FLUSH(first_, sg_)                                                                            \
   {                                                                                                      \
     _Pragma("unroll") for (int g = 0; g < 8; ++g)                                                        \
@@ -615,6 +638,151 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
       *o = w;                                                                                            \
       acc[2 * g + nb] = f32x4{0.f, 0.f, 0.f, 0.f};                                                       \
     }                                                                                                    \
+  }
+  if constexpr (BP) {
+    if (attn) {
+      // e' role: thread (op, sq) holds outputs op and op + 64 of the k-step's slots 4 sq ... 4 sq + 3 (a wave's loads
+      // cover 256 contiguous bytes of one gathered row; its coefficient and row index are wave-uniform)
+      const int op = tid & 63, sq = wave, head = pair;
+      unsigned char* const esb = reinterpret_cast<unsigned char*>(&Es[0][0]) +
+                                 16 * ((op >> 4) * 64 + (sq >> 1) * 16 + (op & 15)) + 8 * (sq & 1);
+      // bit role: thread (slot, word, half) expands 16 bits of the head's eight mask words of one slot
+      const int gslot = tid >> 4, gw = (tid >> 1) & 7, ghs = tid & 1, ggrp = gw >> 2;
+      const int gch = 4 * (gw & 3) + 2 * ghs, gsw = ((gslot & 3) << 2) | ((gslot >> 2) & 3);
+      const int goff0 = 256 * gslot + 16 * (gch ^ gsw), goff1 = 256 * gslot + 16 * ((gch + 1) ^ gsw);
+      const unsigned* mbase = rc.mask + head * 8 + gw;
+      const float* kbase = rc.ga + head;
+      float* csrow = csl + (((long)split * rc.H + head) * 8 + sq) * 128 + op;
+      // (pe*: the sums of the k-step split LAST -- it is multiplied one iteration later and may open the next flush group)
+      float cs0 = 0.f, cs1 = 0.f, pe0 = 0.f, pe1 = 0.f;
+      if (ks1 <= ks0) {   // empty range: the reducer still sums this slab and these cs rows
+        GW_FLUSH(true, 1.f);
+        csrow[0] = 0.f; csrow[64] = 0.f;
+        return;
+      }
+      int pn0 = 0, pn1 = 0, pn2 = 0, pn3 = 0;            // rows of e for the k-step after the one being loaded
+      float rv[8], sv[8], rk[4], sk[4];                  // raw e values / coefficients: next k-step's, the one after
+      unsigned rm = 0, sm = 0;
+#define AT_D1(ks_, j_, D_)                                                                               \
+      {                                                                                                  \
+        const long t = (long)(ks_) * 32 + 4 * sq + (j_);                                                 \
+        D_ = perm[t < E ? t : last_row];                                                                 \
+      }
+#define AT_DLOAD(ks_) { AT_D1(ks_, 0, pn0) AT_D1(ks_, 1, pn1) AT_D1(ks_, 2, pn2) AT_D1(ks_, 3, pn3) }
+#define AT_K1(ks_, j_, K_)                                                                               \
+      {                                                                                                  \
+        const long t = (long)(ks_) * 32 + 4 * sq + (j_);                                                 \
+        const float kk_ = kbase[(t < E ? t : last_row) * rc.H];   /* unconditional load, then the select */ \
+        K_[j_] = t < E ? kk_ : 0.f;                                                                      \
+      }
+      // same order inside one group of loads as GW_LOADS below: the row indices of the k-step AFTER this one first
+#define AT_LOADS(ks_, V_, K_, M_)                                                                        \
+      {                                                                                                  \
+        const float* q0 = erows + (long)pn0 * lde + op;                                                  \
+        const float* q1 = erows + (long)pn1 * lde + op;                                                  \
+        const float* q2 = erows + (long)pn2 * lde + op;                                                  \
+        const float* q3 = erows + (long)pn3 * lde + op;                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        AT_DLOAD((ks_) + 1)                                                                              \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        V_[0] = q0[0]; V_[1] = q0[64]; V_[2] = q1[0]; V_[3] = q1[64];                                    \
+        V_[4] = q2[0]; V_[5] = q2[64]; V_[6] = q3[0]; V_[7] = q3[64];                                    \
+        AT_K1(ks_, 0, K_) AT_K1(ks_, 1, K_) AT_K1(ks_, 2, K_) AT_K1(ks_, 3, K_)                          \
+        {                                                                                                \
+          const long t = (long)(ks_) * 32 + gslot;                                                       \
+          M_ = mbase[(t < E ? t : last_row) * rc.nw];                                                    \
+        }                                                                                                \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+      }
+      // e' = fl(+-ga e) (the flush group's sign rides on the coefficient: exact), its column sum, its three planes:
+      // 8 bytes (four slots) per plane and output into the fragment-ordered tile
+#define AT_SPLIT_E(V_, K_, buf_, sg_)                                                                    \
+      {                                                                                                  \
+        float v_[8];                                                                                     \
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                               \
+          const float k_ = K_[j_] * (sg_);                                                               \
+          v_[2 * j_] = __fmul_rn(k_, V_[2 * j_]); v_[2 * j_ + 1] = __fmul_rn(k_, V_[2 * j_ + 1]);        \
+        }                                                                                                \
+        pe0 = __fadd_rn(__fadd_rn(v_[0], v_[2]), __fadd_rn(v_[4], v_[6]));                               \
+        pe1 = __fadd_rn(__fadd_rn(v_[1], v_[3]), __fadd_rn(v_[5], v_[7]));                               \
+        uint2 a1, a2, a3, b1, b2, b3;                                                                    \
+        split3_pair(v_[0], v_[2], a1.x, a2.x, a3.x); split3_pair(v_[4], v_[6], a1.y, a2.y, a3.y);        \
+        split3_pair(v_[1], v_[3], b1.x, b2.x, b3.x); split3_pair(v_[5], v_[7], b1.y, b2.y, b3.y);        \
+        unsigned char* d_ = esb + (buf_) * (2 * HP * 16);                                                \
+        *reinterpret_cast<uint2*>(d_) = a1;                                                              \
+        *reinterpret_cast<uint2*>(d_ + 4096) = a2;                                                       \
+        *reinterpret_cast<uint2*>(d_ + 8192) = a3;                                                       \
+        *reinterpret_cast<uint2*>(d_ + HP * 16) = b1;                                                    \
+        *reinterpret_cast<uint2*>(d_ + HP * 16 + 4096) = b2;                                             \
+        *reinterpret_cast<uint2*>(d_ + HP * 16 + 8192) = b3;                                             \
+      }
+#define AT_SPLIT_G(M_, buf_)                                                                             \
+      {                                                                                                  \
+        const unsigned mb_ = (M_) >> (16 * ghs);                                                         \
+        *reinterpret_cast<uint4*>(&Gs[buf_][ggrp][0][goff0]) = __builtin_bit_cast(uint4, bits8_bf16(mb_));      \
+        *reinterpret_cast<uint4*>(&Gs[buf_][ggrp][0][goff1]) = __builtin_bit_cast(uint4, bits8_bf16(mb_ >> 8)); \
+      }
+      AT_DLOAD(ks0);
+      AT_LOADS(ks0, rv, rk, rm);
+      AT_SPLIT_E(rv, rk, 0, 1.f)
+      AT_SPLIT_G(rm, 0)
+      AT_LOADS(ks0 + 1, rv, rk, rm);                     // ranges are even
+      __syncthreads();
+      bool firstA = true;
+      // the pipeline of GW_ITER below: loads of k-step ks + 2 into the S set, the R set split into the other buffer
+#define AT_ITER(ks_, buf_, RV, RK, RM, SV, SK, SM)                                                       \
+      {                                                                                                  \
+        const int rel = (ks_) - ks0;                                                                     \
+        const float sgn_next = (((rel + 1) / FLUSH) & 1) ? -1.f : 1.f;                                   \
+        const int kl_ = (ks_) + 2 < ks1 ? (ks_) + 2 : ks1 - 1;                                           \
+        AT_LOADS(kl_, SV, SK, SM);                                                                       \
+        cs0 = __fadd_rn(cs0, pe0); cs1 = __fadd_rn(cs1, pe1);        /* this k-step's e' */                \
+        const bf16x8* es = reinterpret_cast<const bf16x8*>(&Es[buf_][lane]);                             \
+        const bf16x8 qa = GW_TRREAD(buf_, 0, tr00, tr01), qb = GW_TRREAD(buf_, 0, tr10, tr11);           \
+        bf16x8 f1 = es[0], f2 = es[256], f3 = es[512];                                                   \
+        _Pragma("unroll") for (int g = 0; g < 8; ++g) {                                                  \
+          bf16x8 n1, n2, n3;                                                                             \
+          if (g < 7) {                                                                                   \
+            const int o = ((g + 1) >> 2) * HP + ((g + 1) & 3) * 64;                                      \
+            n1 = es[o]; n2 = es[o + 256]; n3 = es[o + 512];                                              \
+          }                                                                                              \
+          /* smallest plane first; columns a and b alternate so that no pass waits for the one before it */ \
+          acc[2 * g + 0] = mma16<false>(f3, qa, acc[2 * g + 0]);                                         \
+          acc[2 * g + 1] = mma16<false>(f3, qb, acc[2 * g + 1]);                                         \
+          acc[2 * g + 0] = mma16<false>(f2, qa, acc[2 * g + 0]);                                         \
+          acc[2 * g + 1] = mma16<false>(f2, qb, acc[2 * g + 1]);                                         \
+          acc[2 * g + 0] = mma16<false>(f1, qa, acc[2 * g + 0]);                                         \
+          acc[2 * g + 1] = mma16<false>(f1, qb, acc[2 * g + 1]);                                         \
+          if (g == 1) AT_SPLIT_E(RV, RK, (buf_) ^ 1, sgn_next)                                           \
+          if (g == 4) AT_SPLIT_G(RM, (buf_) ^ 1)                                                         \
+          if (g < 7) { f1 = n1; f2 = n2; f3 = n3; }                                                      \
+        }                                                                                                \
+        if ((rel + 1) % FLUSH == 0 || (ks_) + 1 == ks1) {                                                \
+          const float sg = ((rel / FLUSH) & 1) ? -1.f : 1.f;                                             \
+          GW_FLUSH(firstA, sg);                                                                          \
+          float c0 = cs0 * sg, c1 = cs1 * sg;                                                            \
+          if (!firstA) { c0 = __fadd_rn(c0, csrow[0]); c1 = __fadd_rn(c1, csrow[64]); }                  \
+          csrow[0] = c0; csrow[64] = c1;                                                                 \
+          cs0 = cs1 = 0.f;                                                                               \
+          firstA = false;                                                                                \
+        }                                                                                                \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                               \
+        __builtin_amdgcn_s_barrier();                                                                    \
+        asm volatile("" ::: "memory");                                                                   \
+      }
+      for (int ks = ks0; ks < ks1; ks += 2) {
+        AT_ITER(ks, 0, rv, rk, rm, sv, sk, sm)
+        AT_ITER(ks + 1, 1, sv, sk, sm, rv, rk, rm)
+      }
+#undef AT_ITER
+#undef AT_SPLIT_G
+#undef AT_SPLIT_E
+#undef AT_LOADS
+#undef AT_K1
+#undef AT_DLOAD
+#undef AT_D1
+      return;
+    }
   }
   if (ks1 <= ks0) {   // empty range: the reducer still sums this slab
     GW_FLUSH(true, 1.f);
@@ -879,17 +1047,82 @@ static int edge_gw_splits(int W2) {   // ranges x column-block pairs ~ one workg
   if (npair <= 0) return 1;
   return 256 / npair > 0 ? 256 / npair : 1;
 }
-// workspace floats: e planes (zero-padded to a multiple of 128 slots) + slabs
+// Bit-plane form (edge_gw_kernel<6, true, true>): the per-edge launch over rebuilt rows in the 24-bit modes, scalar
+// attention with heads of exactly one column-block pair.  Both halves share one wave of workgroups and the launch lasts
+// as long as its slowest one, so the k-ranges are dealt per half: H * SA + (message pairs) * SM <= 256 with
+// SA : SM = (cost of an attention k-step) : (cost of a message k-step) = GW_BIT_COST_A : GW_BIT_COST_M, measured on an
+// MI355X.
+#define GW_BIT_COST_A 3
+#define GW_BIT_COST_M 4
+static bool g_gw_force_six = false;    // debug, process-wide: keep the six-pass form (cgat_debug_edge_gw_force_six)
+bool edge_gw_force_six(bool on) { const bool was = g_gw_force_six; g_gw_force_six = on; return was; }
+static bool edge_gw_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six, int* SA, int* SM) {
+  if (!rc || !perm || force_six || g_gw_force_six || !mode_24bit() || edge_mma_bf16() || mode_bf16x3()) return false;
+  if (rc->Hd != 256 || rc->H < 1 || rc->HHd != rc->H * rc->Hd || rc->nw * 32 != W2 || W2 <= rc->HHd ||
+      (W2 - rc->HHd) % 256 != 0)
+    return false;
+  const int H = rc->H, npm = (W2 - rc->HHd) / 256;
+  // SA (H + npm * COST_M / COST_A) <= 256
+  const int sa = 256 * GW_BIT_COST_A / (H * GW_BIT_COST_A + npm * GW_BIT_COST_M);
+  if (sa < 1 || 256 - H * sa < npm) return false;
+  *SA = sa;
+  *SM = (256 - H * sa) / npm;
+  return true;
+}
+bool edge_gw_takes_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six) {
+  int sa, sm;
+  return edge_gw_bitplane(rc, W2, perm, force_six, &sa, &sm);
+}
+// workspace floats: e planes (zero-padded to a multiple of 128 slots) + slabs.  The slab part is the MAXIMUM over both
+// forms on purpose (the bit-plane form: at most 256 workgroup tiles of 256 x 128 and 256 x 8 rows of column sums, 35 MB;
+// the plain form needs 33 MB at W2 = 1536), also for launches that never take the bit-plane route: the size then does not
+// depend on the route or on the debug switch, and the dry and the real pass of a layer agree whatever either decides.
 size_t edge_gw_ws_floats(int E, int W2) {
   const size_t planes = ((size_t)cdiv(E, 128) * 128 * 128 * 3 + 1) / 2;
-  return planes + (size_t)edge_gw_splits(W2) * W2 * 128 + 64;
+  const size_t plain = (size_t)edge_gw_splits(W2) * W2 * 128, bit = (size_t)256 * 256 * 128 + (size_t)256 * 8 * 128;
+  return planes + (plain > bit ? plain : bit) + 64;
+}
+
+// The reducer of the bit-plane form: one workgroup per 32 outputs of one column, eight threads per output.
+// The slabs are added in fp64 and rounded once (the ranges are shorter than the six-pass form's: more slabs per output,
+// and their fp32 sum was most of the product's error at few edges) -- fixed order, deterministic.
+//   message column:   out = sum over the SM slabs (eight contiguous groups summed in order, then the groups in order)
+//   attention column: P likewise over the SA slabs; cs_h[j] = the SA x 8 partial rows, thread q the rows of slot quad q
+//                     in range order, then q in order;  out = wA (P + 0.01 (cs - P)) on the rounded P and cs as
+//                     d = cs - P;  u = fma(0.01, d, P);  out = wA * u, each one fp32 rounding, in this order
+__global__ __launch_bounds__(256) void edge_gw_bit_reduce_kernel(const float* __restrict__ slabM, int SM,
+                                                                 const float* __restrict__ slabA, int SA,
+                                                                 const float* __restrict__ csl, const float* __restrict__ wA,
+                                                                 int H, int HHd, int W2, float* __restrict__ out, long ldo) {
+  __shared__ double part[8][32], cpart[8][32];
+  const int o = threadIdx.x & 31, zg = threadIdx.x >> 5;
+  const int col = blockIdx.x >> 2, j = 32 * (blockIdx.x & 3) + o;
+  const bool isA = col < HHd;
+  const int splits = isA ? SA : SM, per = (splits + 7) / 8;
+  const int z0 = zg * per, z1 = min(splits, z0 + per);
+  const long rows = isA ? HHd : W2 - HHd;
+  const float* src = (isA ? slabA : slabM) + (long)(isA ? col : col - HHd) * 128 + j;
+  double sd = 0., cd = 0.;
+  for (int z = z0; z < z1; ++z) sd += (double)src[(long)z * rows * 128];
+  if (isA) {
+    const float* cr = csl + ((long)(col / 256) * 8 + zg) * 128 + j;
+    for (int z = 0; z < SA; ++z) cd += (double)cr[(long)z * H * 8 * 128];
+  }
+  part[zg][o] = sd; cpart[zg][o] = cd;
+  __syncthreads();
+  if (zg != 0) return;
+#pragma unroll
+  for (int g = 1; g < 8; ++g) { sd += part[g][o]; cd += cpart[g][o]; }
+  float s = (float)sd;
+  if (isA) s = __fmul_rn(wA[col], __fmaf_rn(0.01f, __fsub_rn((float)cd, s), s));
+  out[(long)col * ldo + j] = s;
 }
 
 // out[col * ldo + k] = sum_t G[t, col] * e[perm[t] * lde + k],   G[t, 128 a + j] at gZ[t * ldg + a * gzb + j]
 // gmax, emax (f16x3 mode only): device pointers to max |gZ| and max |e|; without them the bf16x6 form runs.
 int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde, const int* perm, int E, int W2,
                    float* ws, float* out, long ldo, hipStream_t stream, const float* gmax, const float* emax,
-                   const EdgeRC* rc) {
+                   const EdgeRC* rc, bool force_six) {
   if (E <= 0) {
     GemmParams z = gemm_params(W2, 128, 0, nullptr, 1, nullptr, 1, out, ldo);
     return gemm_launch(z, nullptr, 0, stream);   // K = 0: zero fill
@@ -900,13 +1133,30 @@ int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde
   // operand (a = slot block, b = slot in block, c = k) = e[perm[128 a + b] * lde + c], zero past E
   const bool f16 = mode_f16() && gmax && emax;
   CGAT_TRY(prepare_T_bf16_rows_launch(e, lde, perm, E, planes, na, stream, f16 ? emax : nullptr));
+  const int nsteps = cdiv(E, 32);
+  int SA = 0, SM = 0;
+  if (!f16 && edge_gw_bitplane(rc, W2, perm, force_six, &SA, &SM)) {
+    const int H = rc->H, HHd = rc->HHd, npm = (W2 - HHd) / 256;
+    float* slabA = slab + (size_t)SM * (W2 - HHd) * 128;
+    float* csl = slabA + (size_t)SA * HHd * 128;
+    {
+      CGAT_PROF("edge_gw", stream);
+      hipLaunchKernelGGL((edge_gw_kernel<6, true, true>), dim3(SM * npm + SA * H), dim3(512), 0, stream, gZ, ldg, gzb,
+                         (const uint4*)planes, slab, E, ncb, nsteps, SM, gmax, emax, *rc, e, lde, perm, SA, slabA, csl);
+      CGAT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(edge_gw_bit_reduce_kernel, dim3(W2 * 4), dim3(256), 0, stream, slab, SM, slabA, SA, csl, rc->wA, H,
+                       HHd, W2, out, ldo);
+    CGAT_LAUNCH_CHECK();
+    return CGAT_OK;
+  }
   {
     CGAT_PROF(perm ? "edge_gw" : "rows_gw", stream);
-    const int nsteps = cdiv(E, 32);
     const EdgeRC none = {};
 #define GW_GO(P_, R_)                                                                                                  \
   hipLaunchKernelGGL((edge_gw_kernel<P_, R_>), dim3(S * (ncb / 2)), dim3(512), 0, stream, gZ, ldg, gzb,                \
-                     (const uint4*)planes, slab, E, ncb, nsteps, S, gmax, emax, R_ ? *rc : none)
+                     (const uint4*)planes, slab, E, ncb, nsteps, S, gmax, emax, R_ ? *rc : none, (const float*)nullptr,   \
+                     0l, (const int*)nullptr, 0, (float*)nullptr, (float*)nullptr)
     const bool one = rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
     if (one) GW_GO(1, true);
     else if (rc) { if (f16) GW_GO(2, true); else if (!mode_bf16x3()) GW_GO(6, true); else GW_GO(3, true); }

@@ -300,7 +300,11 @@ size_t edge_gw_ws_floats(int E, int W2);
 int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde, const int* perm, int E, int W2,
                    float* ws, float* out, long ldo, hipStream_t stream, const float* gmax = nullptr,
                    const float* emax = nullptr,            // device maxima of |gZ| and |e| -> fp16 form in the f16x3 mode
-                   const EdgeRC* rc = nullptr);
+                   const EdgeRC* rc = nullptr,
+                   bool force_six = false);                // debug: this launch keeps the six-pass form on every column
+// the bit-plane form of the attention half (edge_gw_kernel<6, true, true>): would this launch take it / debug: never take it
+bool edge_gw_takes_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six = false);
+bool edge_gw_force_six(bool on);   // the process-wide switch; returns the previous setting
 bool edge_ge_fast(int Ce, int W2, long ldg, long gzb, long ldo, const void* gZ, const void* out);
 size_t edge_ge_heads_image_floats(int W2);
 bool edge_ge_heads_fast(int heads, int W2, long ldx, long ldy, long ldw, const void* x, const void* w, const void* y,

@@ -852,6 +852,35 @@ extern "C" int cgat_debug_edge_ge_rebuilt(const uint32_t* mask, const float* ga,
   return edge_ge_launch(nullptr, 128, (long)E * 128, We, 128, 1, Wq, W2, out, 128, nullptr, E, 0, nullptr, s, nullptr, &rc);
 }
 
+// grad W_e's product alone on caller-supplied ingredients of the rebuilt gZ rows, through edge_gw_launch as
+// attn_backward_impl calls it; force_six: THIS launch keeps the six-pass form whatever the route would be (an argument of
+// the launch, no shared state); cgat_debug_edge_gw_force_six: the one process-wide switch (edgebwd.hip)
+extern "C" int32_t cgat_debug_edge_gw_force_six(int32_t on) { return edge_gw_force_six(on != 0) ? 1 : 0; }
+extern "C" size_t cgat_debug_edge_gw_rebuilt_workspace_bytes(int32_t E, int32_t H, int32_t Hd) {
+  return (edge_gw_ws_floats(E, 2 * H * Hd) + 64) * sizeof(float);
+}
+extern "C" int cgat_debug_edge_gw_rebuilt(const uint32_t* mask, const float* ga, const float* alpha, const float* gS,
+                                          const float* wA, const float* e, const int32_t* perm, const int32_t* dst,
+                                          int32_t H, int32_t Hd, int32_t E, int32_t force_six, float* out,
+                                          int32_t* took_bitplane, void* ws, size_t ws_bytes, void* stream) {
+  const int W2 = 2 * H * Hd;
+  CGAT_CHECK_ARG(mask && ga && alpha && gS && wA && e && perm && dst && out && ws, "debug_edge_gw_rebuilt: null pointer");
+  if (!mode_split()) {   // the f32 mode has no such launch: its layers run the generic GEMM on a stored gZ
+    cgat_set_error("debug_edge_gw_rebuilt: split arithmetic modes only");
+    return CGAT_ERR_UNSUPPORTED;
+  }
+  CGAT_CHECK_ARG(E > 0 && edge_rc_shape(128, H, Hd) && W2 % 256 == 0, "debug_edge_gw_rebuilt: H = %d, Hd = %d", H, Hd);
+  CGAT_CHECK_ARG(ws_bytes >= cgat_debug_edge_gw_rebuilt_workspace_bytes(E, H, Hd) &&
+                 ((((uintptr_t)gS) | ((uintptr_t)wA) | ((uintptr_t)e) | ((uintptr_t)out) | ((uintptr_t)ws)) & 15) == 0,
+                 "debug_edge_gw_rebuilt: workspace too small or operands not 16-byte aligned");
+  EdgeRC rc = {};
+  rc.mask = mask; rc.ga = ga; rc.alpha = alpha; rc.gS = gS; rc.wA = wA; rc.dst = dst;
+  rc.H = H; rc.Hd = Hd; rc.HHd = H * Hd; rc.nw = W2 / 32;
+  if (took_bitplane) *took_bitplane = edge_gw_takes_bitplane(&rc, W2, perm, force_six != 0) ? 1 : 0;
+  return edge_gw_launch(nullptr, 128, (long)E * 128, e, 128, perm, E, W2, (float*)ws, out, 128, (hipStream_t)stream, nullptr,
+                        nullptr, &rc, force_six != 0);
+}
+
 extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
                                              const float* edge_attr, const float* saved, const float* g_aggr,
                                              float* g_x, float* g_edge_attr, const cgat_attn_grads* g, void* ws,

@@ -107,3 +107,30 @@ def edge_ge_rebuilt(mask, ga, alpha, gS, wA, dst, We, H, Hd):
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)),
               "cgat_debug_edge_ge_rebuilt")
     return out
+
+
+def edge_gw_rebuilt(mask, ga, alpha, gS, wA, e, perm, dst, H, Hd, force_six=False):
+    """grad W_e's product alone on caller-supplied ingredients of the rebuilt rows (cgat_debug_edge_gw_rebuilt,
+    include/cgat_hip.h): mask int32 [E, 2 H Hd / 32], ga / alpha [E, H], gS [N, H Hd], wA [H Hd], e [E, 128] in original
+    edge order, perm int32 [E] (slot -> edge), dst int32 [E].  Returns (out [2 H Hd, 128], took_bitplane)."""
+    E, dev = ga.shape[0], ga.device
+    t = [mask.contiguous(), ga.contiguous(), alpha.contiguous(), gS.contiguous(), wA.contiguous(), e.contiguous(),
+         perm.contiguous(), dst.contiguous()]
+    assert all(v.dtype == torch.int32 for v in (t[0], t[6], t[7])) and all(v.dtype == torch.float32 for v in t[1:6])
+    out = torch.empty(2 * H * Hd, 128, dtype=torch.float32, device=dev)
+    from . import ops
+    ws = ops.workspace(lib.cgat_debug_edge_gw_rebuilt_workspace_bytes(E, H, Hd), dev)
+    took = C.c_int32(0)
+    with torch.cuda.device(dev):
+        check(lib.cgat_debug_edge_gw_rebuilt(*[C.c_void_p(v.data_ptr()) for v in t], H, Hd, E, 1 if force_six else 0,
+                                             C.c_void_p(out.data_ptr()), C.byref(took), C.c_void_p(ws.data_ptr()),
+                                             ws.numel() * ws.element_size(),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              "cgat_debug_edge_gw_rebuilt")
+    return out, bool(took.value)
+
+
+def edge_gw_force_six(flag):
+    """Process-wide: grad W_e keeps its six-pass form on every column (the A/B reference of the bit-plane route).  Returns
+    the previous setting."""
+    return bool(lib.cgat_debug_edge_gw_force_six(1 if flag else 0))

@@ -202,6 +202,19 @@ int cgat_debug_edge_ge_rebuilt(const uint32_t* mask, const float* ga, const floa
                                const float* wA, const int32_t* dst, const float* We, int32_t H, int32_t Hd, int32_t E,
                                float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* Debug / parity instrumentation (tests only): grad W_e's product  out[col, :] = sum_t gZ[t, col] e[perm[t], :]  ALONE, with
+ * gZ rebuilt from the same caller-supplied ingredients as above, through the launch the backward takes for it.
+ * e [E, 128] (original edge order), perm [E] (slot -> edge), out [2*H*Hd, 128].  force_six != 0: the six-pass form on
+ * every column, whatever the route would be; *took_bitplane (host, may be null) = 1 when the attention half ran on the
+ * stored bit (24-bit modes, fp32 / bf16 edge storage, Hd == 256).  Every split arithmetic mode, Hd a multiple of 128.
+ * cgat_debug_edge_gw_force_six: the same switch for every later launch of the process (returns the previous value). */
+int32_t cgat_debug_edge_gw_force_six(int32_t on);
+size_t cgat_debug_edge_gw_rebuilt_workspace_bytes(int32_t E, int32_t H, int32_t Hd);
+int cgat_debug_edge_gw_rebuilt(const uint32_t* mask, const float* ga, const float* alpha, const float* gS,
+                               const float* wA, const float* e, const int32_t* perm, const int32_t* dst, int32_t H,
+                               int32_t Hd, int32_t E, int32_t force_six, float* out, int32_t* took_bitplane, void* ws,
+                               size_t ws_bytes, void* stream);
+
 /* ---- first layer of the message networks alone (vector-attention variants) ---------------
  * hidden[t, :] = LeakyReLU(w_in [x_i ; edge_attr ; x_j] + b_in), t = destination-sorted edge slot (plan.dst_perm),
  * for the stacked first-layer weights w_in [W2, 2C+Ce] of any number of heads / networks: MultiHeadNetwork's
