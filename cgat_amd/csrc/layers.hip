@@ -3,6 +3,8 @@
 // stream -- no allocation, no synchronisation.
 #include <string.h>
 
+#include <initializer_list>
+
 #include "../../include/cgat_hip.h"
 #include "common.h"
 #include "kernels.h"
@@ -240,6 +242,36 @@ static int stack_in_weights(Ctx& c, const cgat_attn_params* p, const AttnDims& d
   return CGAT_OK;
 }
 
+// ---- routes: which launches a pass takes, decided once from the dims, the arithmetic mode, the edge-storage mode and
+// the alignment of the operands, and read by every step below.  A dry pass takes no route that depends on an operand:
+// it measures the generic steps, and the scratch a fast route needs is asked for by dims alone where that route runs
+// (so the real pass tests no scratch size: run_sized has refused a workspace smaller than the dry pass measured).
+// `ws` stands for the pass' workspace carve-outs in the kernels' 16-byte tests: Workspace::take places every one a
+// multiple of 256 bytes behind the caller's base, so any of them passes exactly when all do.
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
+}
+
+// How the forward forms and stores Z [E, W2] -- and therefore how the backward finds it: both passes call this with the
+// same x, e, saved buffer and fc_out_A weight (Z = saved; nullptr where the fused inference forms no Z).
+struct ZForm {
+  bool zx;        // f16x3 mode at the benchmark widths: the x_j projection is folded into the per-edge kernel
+                  // (edge_zx_kernel), so Pj is never formed
+  bool fused_z;   // Z and the attention logits from one fused split-bf16 per-edge launch (else: generic GEMM + row-dot)
+  bool bf16;      // Z stored as bf16 (edge-storage mode "bf16"): by edge_zx in the f16x3 mode, ...
+  bool bf16_six;  // ... by the six-pass per-edge kernel otherwise
+};
+static ZForm attn_z_form(const AttnDims& d, const float* e, const float* x, const float* Z, const float* wA, const void* ws) {
+  ZForm z;
+  z.zx = d.N > 0 && edge_zx_fast(d.C, d.Ce, d.W2, d.H, d.Hd, d.W2, d.W2, e, x, ws, Z, wA) &&
+         edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, ws, ws, ws, ws);
+  const bool per_edge = edge_z_fast(d.Ce, d.W2, d.H, d.Hd, d.Ce, d.W2, d.W2, e, ws, ws, Z, wA);
+  z.fused_z = per_edge && !z.zx;
+  z.bf16_six = attn_bf16(d) && per_edge && !mode_f16();
+  z.bf16 = (attn_bf16(d) && z.zx) || z.bf16_six;
+  return z;
+}
+
 // The forward without grad (infer): at the shapes edge_infer_fused takes (edgez.hip: the 24-bit modes at width 128, up to
 // 2048 columns per half and 8 heads -- the harness' H = 5 -- at any number of edges, its few-row batches included) the
 // logits launch and the fused
@@ -249,408 +281,582 @@ static int stack_in_weights(Ctx& c, const cgat_attn_params* p, const AttnDims& d
 static bool attn_infer_fused(const AttnDims& d) {
   return edge_infer_fused(d.N, d.E, d.C, d.Ce, d.H, d.Hd) && (!edge_bf16_storage() || attn_bf16(d));
 }
-static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x, const float* e,
-                             float* aggr, float* saved, bool infer = false) {
-  const AttnDims d = attn_dims(plan, p);
-  float* Wcat = c.take<float>((size_t)d.W2 * d.D);
-  float* bcat = c.take<float>((size_t)d.W2);
-  float* Pi = c.take<float>((size_t)d.N * d.W2);
-  float* Pj = c.take<float>((size_t)d.N * d.W2);
-  float* a = c.take<float>((size_t)d.E * d.H);
-  float* Wq = c.take<float>(edge_z_wq_floats(d.W2) > edge_zx_wq_floats(d.W2) ? edge_z_wq_floats(d.W2)
-                                                                              : edge_zx_wq_floats(d.W2));
-  const bool fused_inf = infer && attn_infer_fused(d);
-  AttnSaved inf = {};
-  if (fused_inf) {
-    inf.alpha = c.take<float>((size_t)d.E * d.H);
-    inf.S = c.take<float>((size_t)d.N * d.HHd);
-    inf.ssum = c.take<float>((size_t)d.N * d.H);
-  } else if (infer) {
-    saved = c.take<float>(cgat_nodes_attention_saved_floats(d.N, d.E, d.H, d.Hd));
-  }
-  c.seal();
-  AttnSaved sv = c.dry ? AttnSaved{} : fused_inf ? inf : attn_saved(saved, d);
-  // f16x3 mode at the benchmark widths: the x_j projection is folded into the per-edge kernel (edge_zx_kernel), so
-  // Pj is never formed
-  const bool zx = !c.dry && d.N > 0 &&
-                  edge_zx_fast(d.C, d.Ce, d.W2, d.H, d.Hd, d.W2, d.W2, e, x, Pi, sv.Z, p->A_out_w) &&
-                  edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, Pi, Pj, Pi, bcat);
+// Round 6: fc_out_M as ONE K = H * Hd launch (the 24-bit modes, more rows than the small-row programs take): the H per-head
+// weights are not one affine operand, but their six-pass images -- one batched image launch, head h's blocks behind
+// head h - 1's -- are exactly the contiguous operand of the K = W2 -> 128 kernel (edgebwd.hip).  Saves five passes over
+// aggr (42 MB read + written each at 83 340 atoms) and four launches.
+static bool attn_out_one_shape(const AttnDims& d) {
+  return mode_24bit() && d.C == 128 && d.Hd % 128 == 0 && d.N > rowprog_max_rows() && d.H <= TPREP_MAX &&
+         ((d.Hd / 128) % 2) == 0;      // (even: the per-head block parity is the global one)
+}
 
-  CGAT_TRY(stack_in_weights(c, p, d, Wcat, bcat));
-  // first conv layer split by operand: W_in [x_i;e;x_j] = W_i x_i + W_e e + W_j x_j
+struct AttnFwdRoute {
+  bool fused_infer;   // the no-grad forward on the logits launch + the fused message / weighted-sum launch
+  bool zx, fused_z;   // the per-edge phase of the training forward (ZForm)
+  bool z_bf16;
+  bool proj_fast;     // the node projections on the per-edge kernel (else: the GEMM pair)
+  bool out_fast;      // fc_out_M as H * Hd / 128 accumulating K = 128 launches of the dense-layer kernel
+  bool out_one;       // ... as one K = H * Hd launch (attn_out_one_shape)
+};
+// saved: where Z / alpha / S / ssum of this pass live (nullptr: the fused inference, whose S is a carve-out)
+static AttnFwdRoute attn_fwd_route(bool dry, const AttnDims& d, bool infer, const cgat_attn_params* p, const float* x,
+                                   const float* e, const float* saved, const float* S, const float* aggr, const void* ws) {
+  AttnFwdRoute r = {};
+  r.fused_infer = infer && attn_infer_fused(d);
+  r.out_fast = mode_split() && d.C == 128 && d.Hd % 128 == 0;
+  if (dry) return r;
+  const ZForm z = attn_z_form(d, e, x, saved, p->A_out_w, ws);
+  r.zx = z.zx; r.fused_z = z.fused_z; r.z_bf16 = z.bf16;
   // (a few hundred atoms: the generic branch, whose products run as 16 x 16 wave tiles -- rowprog.hip -- instead of
   // five 256-row workgroups streaming the whole weight image: 86 -> ~10 us per projection at 1 280 atoms)
-  if (!c.dry && d.N > rowprog_max_rows() && edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, Pi, Pj, Pi, bcat)) {
-    RUN(edge_z_launch(x, d.C, nullptr, Wcat, d.D, Wq, d.W2, bcat, nullptr, nullptr, nullptr, 0, Pi, d.W2, d.N, nullptr,
-                      nullptr, d.H, d.Hd, nullptr, c.s));
-    if (!zx)
-      RUN(edge_z_launch(x, d.C, nullptr, Wcat + d.C + d.Ce, d.D, Wq, d.W2, nullptr, nullptr, nullptr, nullptr, 0, Pj, d.W2,
-                        d.N, nullptr, nullptr, d.H, d.Hd, nullptr, c.s));
+  r.proj_fast = d.N > rowprog_max_rows() && edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, ws, ws, ws, ws);
+  r.out_one = attn_out_one_shape(d) && edge_ge_fast(128, d.HHd, d.HHd, 128, d.C, S, aggr) && aligned16(p->M_out_w);
+  return r;
+}
+
+// fc_out_M's backward at the benchmark widths (C = 128, Hd a multiple of 128, at most DW_BATCH_MAX weight-gradient blocks)
+static bool attn_bwd_out_shape(const AttnDims& d) {
+  return mode_split() && d.C == 128 && d.Hd % 128 == 0 && d.H * (d.Hd / 128) <= DW_BATCH_MAX;
+}
+struct AttnBwdRoute {
+  bool rc;             // gZ is not stored: one bit per element, the consumers rebuild the rows (struct EdgeRC, kernels.h)
+  bool vec;            // the segment kernel's 16-byte loads
+  bool have_scales;    // f16x3: maxima of gZ and edge_attr -> the per-edge products on two fp16 planes
+  bool z_bf16, z_bf16_six;   // how the forward stored Z (ZForm)
+  bool out_fast;       // fc_out_M's input gradients on the dense-layer kernel, its weight gradients in one batched launch
+  bool out_heads_one;  // ... the input gradients of all heads in one launch pair (round 6)
+};
+static AttnBwdRoute attn_bwd_route(bool dry, const AttnDims& d, const cgat_attn_params* p, const float* x, const float* e,
+                                   const float* saved, const float* S, const void* ws) {
+  AttnBwdRoute r = {};
+  // At the benchmark widths gZ [E, W2] is never stored: edge_seg_bwd_kernel leaves one bit per element behind and the
+  // three consumers rebuild the rows (struct EdgeRC, kernels.h) -- E * W2 / 8 bytes of workspace instead of 4 E * W2
+  // (edge storage mode 2 keeps the stored-gZ backward of round 1 at these widths too: the A/B reference of the tests)
+  r.rc = mode_split() && edge_rc_shape(d.Ce, d.H, d.Hd) && d.W2 % 256 == 0 && d.N > 0 && d.E > 0 && edge_storage() != 2;
+  r.out_fast = attn_bwd_out_shape(d);     // (a dry pass measures this route's per-head form)
+  if (dry || d.N <= 0) { r.out_fast = r.out_fast && dry; return r; }
+  r.out_fast = r.out_fast && linear128_fast(d.C, d.Hd, d.C, d.HHd, ws, ws) &&
+               rows_dw128_fast((const float*)ws, d.C, S, d.HHd, nullptr, 0);   // (every S block starts 512 bytes further)
+  r.out_heads_one = r.out_fast && mode_24bit() && d.N > rowprog_max_rows() && d.H > 1 && aligned16(p->M_out_w);
+  r.vec = (d.Hd % 4 == 0) && aligned16(saved, ws, p->A_out_w);
+  r.have_scales = r.vec && mode_f16() && d.Ce == 128 && aligned16(e);
+  const ZForm z = attn_z_form(d, e, x, saved, p->A_out_w, ws);
+  r.z_bf16 = z.bf16; r.z_bf16_six = z.bf16_six;
+  return r;
+}
+
+// ---- forward ----
+struct AttnFwd {
+  AttnDims d;
+  const cgat_plan* plan;
+  const cgat_attn_params* p;
+  const float *x, *e;
+  float* aggr;
+  float *Wcat, *bcat, *Pi, *Pj, *a, *Wq;
+  AttnSaved sv;       // the caller's saved buffer, or (infer) carve-outs
+  AttnFwdRoute r;
+};
+static AttnFwd attn_fwd_carve(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x, const float* e,
+                              float* aggr, float* saved, bool infer) {
+  AttnFwd f = {};
+  const AttnDims d = f.d = attn_dims(plan, p);
+  f.plan = plan; f.p = p; f.x = x; f.e = e; f.aggr = aggr;
+  f.Wcat = c.take<float>((size_t)d.W2 * d.D);
+  f.bcat = c.take<float>((size_t)d.W2);
+  f.Pi = c.take<float>((size_t)d.N * d.W2);
+  f.Pj = c.take<float>((size_t)d.N * d.W2);
+  f.a = c.take<float>((size_t)d.E * d.H);
+  f.Wq = c.take<float>(edge_z_wq_floats(d.W2) > edge_zx_wq_floats(d.W2) ? edge_z_wq_floats(d.W2)
+                                                                        : edge_zx_wq_floats(d.W2));
+  if (infer && attn_infer_fused(d)) {
+    f.sv.alpha = c.take<float>((size_t)d.E * d.H);
+    f.sv.S = c.take<float>((size_t)d.N * d.HHd);
+    f.sv.ssum = c.take<float>((size_t)d.N * d.H);
   } else {
-    GemmParams g = gemm_params(d.N, d.W2, d.C, x, d.C, Wcat, d.D, Pi, d.W2);
-    g.bias = bcat;
-    CGAT_TRY(c.gemm(g));
-    g = gemm_params(d.N, d.W2, d.C, x, d.C, Wcat + d.C + d.Ce, d.D, Pj, d.W2);
-    CGAT_TRY(c.gemm(g));
+    if (infer) saved = c.take<float>(cgat_nodes_attention_saved_floats(d.N, d.E, d.H, d.Hd));
+    if (!c.dry) f.sv = attn_saved(saved, d);
   }
-  if (fused_inf) {   // logits, softmax (the same launch as below), message columns summed straight into S
-    CGAT_CHECK_ARG(((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)p->A_out_w)) & 15) == 0,
-                   "nodes_attention_infer: edge_attr and MH_A.fc_out.weight must be 16-byte aligned");
-    RUN(edge_logits_launch(e, d.Ce, plan->dst_perm, Wcat + d.C, d.D, Wq, d.W2, Pi, plan->dst_sorted, Pj, plan->src_sorted,
-                           d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, a, c.s));
-    RUN(seg_softmax_fwd_launch(a, nullptr, plan->dst_rowptr, d.N, d.H, 1e-16f, sv.alpha, sv.ssum, c.s));
-    RUN(edge_msg_wsum_launch(e, d.Ce, plan->dst_perm, Wq, d.W2, Pi, plan->dst_sorted, Pj, plan->src_sorted, d.N, d.E, d.H,
-                             d.Hd, sv.alpha, plan->dst_rowptr, sv.S, attn_bf16(d) ? 1 : 0, c.s));
-  } else {
-  // Z[t] = W_e e[perm[t]] + Pi[dst[t]] + Pj[src[t]]      (x_i = x[edge_index[1]], x_j = x[edge_index[0]])
-  // and the attention logits a[t,h] = fc_out_A(leaky(zA)): one fused split-bf16 kernel at the benchmark widths,
-  // the generic GEMM + row-dot otherwise (and in the f32 arithmetic mode)
-  const bool fused_z = !c.dry && edge_z_fast(d.Ce, d.W2, d.H, d.Hd, d.Ce, d.W2, d.W2, e, Pi, Pj, sv.Z, p->A_out_w);
-  // Z stored as bf16 (edge-storage mode "bf16"): by edge_zx in the f16x3 mode, by the six-pass per-edge kernel otherwise
-  const bool zb = attn_bf16(d) && (zx || (fused_z && !mode_f16()));
-  if (!c.dry && edge_bf16_storage() && !zb && d.N > 0 && d.E > 0) {
+  c.seal();
+  f.r = attn_fwd_route(c.dry, d, infer, p, x, e, f.sv.Z, f.sv.S, aggr, f.Pi);
+  return f;
+}
+
+// first conv layer split by operand: W_in [x_i;e;x_j] = W_i x_i + W_e e + W_j x_j.  The two node projections
+// Pi = x W_i^T + bias, Pj = x W_j^T of the stacked weight W [W2, D]: two launches of the per-edge kernel, or the GEMM pair
+// (which forms Pj whether or not the per-edge phase reads it)
+struct NodeProj { float *Pi, *Pj, *Wq; };
+static int node_projections(Ctx& c, const AttnDims& d, bool fast, bool need_Pj, const float* x, const float* W,
+                            const float* bias, const NodeProj& o) {
+  float *Pi = o.Pi, *Pj = o.Pj, *Wq = o.Wq;
+  if (fast) {
+    RUN(edge_z_launch(x, d.C, nullptr, W, d.D, Wq, d.W2, bias, nullptr, nullptr, nullptr, 0, Pi, d.W2, d.N, nullptr,
+                      nullptr, d.H, d.Hd, nullptr, c.s));
+    if (need_Pj)
+      RUN(edge_z_launch(x, d.C, nullptr, W + d.C + d.Ce, d.D, Wq, d.W2, nullptr, nullptr, nullptr, nullptr, 0, Pj, d.W2,
+                        d.N, nullptr, nullptr, d.H, d.Hd, nullptr, c.s));
+    return CGAT_OK;
+  }
+  GemmParams g = gemm_params(d.N, d.W2, d.C, x, d.C, W, d.D, Pi, d.W2);
+  g.bias = bias;
+  CGAT_TRY(c.gemm(g));
+  g = gemm_params(d.N, d.W2, d.C, x, d.C, W + d.C + d.Ce, d.D, Pj, d.W2);
+  return c.gemm(g);
+}
+
+// logits, softmax (the same launch as the training forward's), message columns summed straight into S
+static int attn_fwd_edges_infer(Ctx& c, const AttnFwd& f) {
+  const AttnDims& d = f.d;
+  const cgat_plan* plan = f.plan;
+  CGAT_CHECK_ARG(aligned16(f.e, f.Pi, f.Pj) && aligned16(f.p->A_out_w),
+                 "nodes_attention_infer: edge_attr and MH_A.fc_out.weight must be 16-byte aligned");
+  RUN(edge_logits_launch(f.e, d.Ce, plan->dst_perm, f.Wcat + d.C, d.D, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj,
+                         plan->src_sorted, d.E, f.p->A_out_w, f.p->A_out_b, d.H, d.Hd, f.a, c.s));
+  RUN(seg_softmax_fwd_launch(f.a, nullptr, plan->dst_rowptr, d.N, d.H, 1e-16f, f.sv.alpha, f.sv.ssum, c.s));
+  RUN(edge_msg_wsum_launch(f.e, d.Ce, plan->dst_perm, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj, plan->src_sorted, d.N, d.E,
+                           d.H, d.Hd, f.sv.alpha, plan->dst_rowptr, f.sv.S, attn_bf16(d) ? 1 : 0, c.s));
+  return CGAT_OK;
+}
+
+// Z[t] = W_e e[perm[t]] + Pi[dst[t]] + Pj[src[t]]      (x_i = x[edge_index[1]], x_j = x[edge_index[0]])
+// and the attention logits a[t,h] = fc_out_A(leaky(zA)): one fused split-bf16 kernel at the benchmark widths,
+// the generic GEMM + row-dot otherwise (and in the f32 arithmetic mode); then softmax and the weighted sum
+static int attn_fwd_edges_train(Ctx& c, const AttnFwd& f) {
+  const AttnDims& d = f.d;
+  const cgat_plan* plan = f.plan;
+  const cgat_attn_params* p = f.p;
+  const AttnFwdRoute& r = f.r;
+  const AttnSaved& sv = f.sv;
+  if (!c.dry && edge_bf16_storage() && !r.z_bf16 && d.N > 0 && d.E > 0) {
     cgat_set_error("nodes_attention_forward: edge storage \"bf16\" is set but this layer (C %d, Ce %d, H %d, Hd %d, arithmetic "
                    "mode %d) has no bf16 form -- refusing to run it in fp32 storage under that label", d.C, d.Ce, d.H, d.Hd,
                    bilinear_mode());
     return CGAT_ERR_UNSUPPORTED;
   }
-  if (zx) {
-    RUN(edge_zx_launch(e, d.Ce, plan->dst_perm, x, d.C, Wcat + d.C, Wcat + d.C + d.Ce, d.D, Wq, d.W2, Pi, plan->dst_sorted,
-                       plan->src_sorted, d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, a, c.s, zb ? 1 : 0));
-  } else if (fused_z) {
-    RUN(edge_z_launch(e, d.Ce, plan->dst_perm, Wcat + d.C, d.D, Wq, d.W2, Pi, plan->dst_sorted, Pj, plan->src_sorted,
-                      d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, a, c.s, CGAT_ACT_NONE, nullptr, zb ? 1 : 0, d.N));
+  const int zb = r.z_bf16 ? 1 : 0;
+  if (r.zx) {
+    RUN(edge_zx_launch(f.e, d.Ce, plan->dst_perm, f.x, d.C, f.Wcat + d.C, f.Wcat + d.C + d.Ce, d.D, f.Wq, d.W2, f.Pi,
+                       plan->dst_sorted, plan->src_sorted, d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, f.a, c.s,
+                       zb));
+  } else if (r.fused_z) {
+    RUN(edge_z_launch(f.e, d.Ce, plan->dst_perm, f.Wcat + d.C, d.D, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj,
+                      plan->src_sorted, d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, f.a, c.s, CGAT_ACT_NONE,
+                      nullptr, zb, d.N));
   } else {
-    GemmParams g = gemm_params(d.E, d.W2, d.Ce, e, d.Ce, Wcat + d.C, d.D, sv.Z, d.W2);
+    GemmParams g = gemm_params(d.E, d.W2, d.Ce, f.e, d.Ce, f.Wcat + d.C, d.D, sv.Z, d.W2);
     g.a_rgather = plan->dst_perm;
-    g.add1 = Pi; g.add1_idx = plan->dst_sorted;
-    g.add2 = Pj; g.add2_idx = plan->src_sorted;
+    g.add1 = f.Pi; g.add1_idx = plan->dst_sorted;
+    g.add2 = f.Pj; g.add2_idx = plan->src_sorted;
     g.ld_add = d.W2;
     CGAT_TRY(c.gemm(g));
+    RUN(rowdot_launch(sv.Z, d.W2, CGAT_ACT_LEAKY, p->A_out_w, 0, nullptr, p->A_out_b, nullptr, d.E, d.H, d.Hd, f.a, c.s));
   }
-  if (!fused_z && !zx)
-    RUN(rowdot_launch(sv.Z, d.W2, CGAT_ACT_LEAKY, p->A_out_w, 0, nullptr, p->A_out_b, nullptr, d.E, d.H, d.Hd, a, c.s));
-  RUN(seg_softmax_fwd_launch(a, nullptr, plan->dst_rowptr, d.N, d.H, 1e-16f, sv.alpha, sv.ssum, c.s));
+  RUN(seg_softmax_fwd_launch(f.a, nullptr, plan->dst_rowptr, d.N, d.H, 1e-16f, sv.alpha, sv.ssum, c.s));
   // S[n,h,:] = sum_{t -> n} alpha[t,h] leaky(zM[t,h,:])  -- fc_out of MH_M commutes with the weighted sum
   RUN(seg_wsum_launch(zb ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(sv.Z) + d.HHd) : sv.Z + d.HHd, d.W2,
-                      nullptr, sv.alpha, d.H, d.Hd, plan->dst_rowptr, d.N, d.HHd, CGAT_ACT_LEAKY, sv.S, d.HHd, c.s, 0,
-                      zb ? 1 : 0));
-  }
-  // aggr = (1/H) [ sum_h S[:,h,:] fc_out_M[h]^T + ssum b ].  At the benchmark widths the H products run as
-  // H * Hd / 128 accumulating launches of the dense-layer kernel (K = 128 each; the generic f32 GEMM tile took 0.1 ms
-  // per head) and 1/H is applied by the bias product that closes the sum.
-  const bool out_fast = mode_split() && d.C == 128 && d.Hd % 128 == 0;
-  // Round 6: ONE K = H * Hd launch instead (the 24-bit modes, more rows than the small-row programs take): the H per-head
-  // weights are not one affine operand, but their six-pass images -- one batched image launch, head h's blocks behind
-  // head h - 1's -- are exactly the contiguous operand of the K = W2 -> 128 kernel (edgebwd.hip).  Saves five passes over
-  // aggr (42 MB read + written each at 83 340 atoms) and four launches.
+                      nullptr, sv.alpha, d.H, d.Hd, plan->dst_rowptr, d.N, d.HHd, CGAT_ACT_LEAKY, sv.S, d.HHd, c.s, 0, zb));
+  return CGAT_OK;
+}
+
+// aggr = (1/H) [ sum_h S[:,h,:] fc_out_M[h]^T + ssum b ].  At the benchmark widths the H products run as
+// H * Hd / 128 accumulating launches of the dense-layer kernel (K = 128 each; the generic f32 GEMM tile took 0.1 ms
+// per head) -- or as one launch (attn_out_one_shape) -- and 1/H is applied by the bias product that closes the sum.
+static int attn_fwd_out(Ctx& c, const AttnFwd& f) {
+  const AttnDims& d = f.d;
+  const cgat_attn_params* p = f.p;
+  const AttnSaved& sv = f.sv;
   const int ncb_h = d.Hd / 128;
-  const bool out_one = out_fast && mode_24bit() && d.N > rowprog_max_rows() &&
-                       d.H <= TPREP_MAX && (ncb_h % 2) == 0;      // (even: the per-head block parity is the global one)
-  const size_t out_img_bytes = (size_t)d.H * ncb_h * 24576 * sizeof(float);
-  if (out_one) c.need(out_img_bytes);
-  bool out_done = false;
-  if (out_one && !c.dry && c.scratch_bytes >= out_img_bytes &&
-      edge_ge_fast(128, d.HHd, d.HHd, 128, d.C, sv.S, aggr) && (((uintptr_t)p->M_out_w) & 15) == 0) {
+  if (attn_out_one_shape(d)) c.need((size_t)d.H * ncb_h * 24576 * sizeof(float));
+  if (f.r.out_one) {
     // operand (a = block of head h, b = column in block, c = output) = M_out_w[h * C * Hd + c * Hd + 128 a + b]
     CGAT_TRY(prepare_T_bf16_heads_launch(p->M_out_w, c.scratch, ncb_h, 128, 1, d.Hd, /*alternate=*/1, d.H, (long)d.C * d.Hd,
                                          (long)ncb_h * 24576, c.s));
-    CGAT_TRY(edge_ge_prepared_launch(sv.S, d.HHd, c.scratch, d.H * ncb_h, aggr, d.C, d.N, 0, c.s));
-    out_done = true;
-  }
-  for (int h = 0; h < d.H && !out_done; ++h) {
-    if (out_fast) {
-      for (int j = 0; j < d.Hd / 128; ++j) {
+    CGAT_TRY(edge_ge_prepared_launch(sv.S, d.HHd, c.scratch, d.H * ncb_h, f.aggr, d.C, d.N, 0, c.s));
+  } else if (f.r.out_fast) {
+    for (int h = 0; h < d.H; ++h)
+      for (int j = 0; j < ncb_h; ++j) {
         GemmParams g = gemm_params(d.N, d.C, 128, sv.S + (size_t)h * d.Hd + 128 * j, d.HHd,
-                                   p->M_out_w + (size_t)h * d.C * d.Hd + 128 * j, d.Hd, aggr, d.C);
+                                   p->M_out_w + (size_t)h * d.C * d.Hd + 128 * j, d.Hd, f.aggr, d.C);
         g.beta = (h > 0 || j > 0) ? 1.f : 0.f;
         CGAT_TRY(c.gemm(g));
       }
-      continue;
+  } else {
+    for (int h = 0; h < d.H; ++h) {
+      GemmParams g = gemm_params(d.N, d.C, d.Hd, sv.S + (size_t)h * d.Hd, d.HHd, p->M_out_w + (size_t)h * d.C * d.Hd,
+                                 d.Hd, f.aggr, d.C);
+      g.alpha = 1.f / d.H;
+      g.beta = h > 0 ? 1.f : 0.f;
+      CGAT_TRY(c.gemm(g));
     }
-    GemmParams g = gemm_params(d.N, d.C, d.Hd, sv.S + (size_t)h * d.Hd, d.HHd, p->M_out_w + (size_t)h * d.C * d.Hd,
-                               d.Hd, aggr, d.C);
-    g.alpha = 1.f / d.H;
-    g.beta = h > 0 ? 1.f : 0.f;
-    CGAT_TRY(c.gemm(g));
   }
-  {  // + (1/H) sum_h ssum[n,h] * fc_out bias
-    GemmParams g = gemm_params(d.N, d.C, d.H, sv.ssum, d.H, p->M_out_b, d.C, aggr, d.C);
-    g.b_kmajor = 1;
-    g.alpha = 1.f / d.H;
-    g.beta = out_fast ? 1.f / d.H : 1.f;
-    CGAT_TRY(c.gemm(g));
-  }
+  // + (1/H) sum_h ssum[n,h] * fc_out bias
+  GemmParams g = gemm_params(d.N, d.C, d.H, sv.ssum, d.H, p->M_out_b, d.C, f.aggr, d.C);
+  g.b_kmajor = 1;
+  g.alpha = 1.f / d.H;
+  g.beta = f.r.out_fast ? 1.f / d.H : 1.f;
+  return c.gemm(g);
+}
+
+static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x, const float* e,
+                             float* aggr, float* saved, bool infer = false) {
+  const AttnFwd f = attn_fwd_carve(c, plan, p, x, e, aggr, saved, infer);
+  CGAT_TRY(stack_in_weights(c, p, f.d, f.Wcat, f.bcat));
+  CGAT_TRY(node_projections(c, f.d, f.r.proj_fast, !f.r.zx, x, f.Wcat, f.bcat, NodeProj{f.Pi, f.Pj, f.Wq}));
+  CGAT_TRY(f.r.fused_infer ? attn_fwd_edges_infer(c, f) : attn_fwd_edges_train(c, f));
+  CGAT_TRY(attn_fwd_out(c, f));
   return check_ws(c, "nodes_attention_forward");
 }
 
-// Everything downstream of the pre-activation gradient gZ[t, :] (destination-sorted slots; element (t, 128 a + j) at
-// gZ[t * gz_ld + a * gzb + j]) of the operand-split first layer: gradients wrt edge_attr, x, the stacked weight
-// [W2, D] = [W_i | W_e | W_j] and its bias.  Shared by the scalar-attention backward (gZ from the fused segment
-// kernel, column-blocked, Gi already summed) and the edge_hidden op (gZ row-major from autograd).
-static int edge_first_layer_backward_tail(Ctx& c, const cgat_plan* plan, const AttnDims& d, const float* Wcat,
-                                          float* gWcat, float* gbcat, const float* gZ, long gz_ld, long gzb, float* Gi,
-                                          float* Gj, bool have_Gi, const float* x, const float* e, float* g_x, float* g_e,
-                                          float* Wq, float* gw_ws, const float* scales = nullptr,
-                                          const EdgeRC* rc = nullptr, bool node_scales = false) {
-  // rc: gZ was not stored; the per-edge launches and the source-side sum rebuild its rows (struct EdgeRC, kernels.h)
-  // scales (f16x3 mode, optional): device {max |gZ|, max |e|} -> the per-edge products run on two fp16 planes
-  const long xb = (gz_ld == d.W2) ? 0 : gzb;   // block stride for the segment sums; 0 = plain row-major gZ
-  // Order: the HBM-bound kernels (segment sums, node-side products over the 0.5-GB Gi / Gj) first, the two matrix-bound
-  // per-edge products last -- the caller's side stream runs the matrix-bound dT launch on half of the chip meanwhile,
-  // and a matrix-bound kernel beside it takes 2.9x as long (edge_ge 1.3 -> 3.7 ms) where an HBM-bound one loses little.
-  // segment sums of gZ: by destination (x_i side) unless the caller already has them, by source (x_j side)
-  if (!have_Gi)
-    RUN(seg_wsum_launch(gZ, d.W2, nullptr, nullptr, 0, 1, plan->dst_rowptr, d.N, d.W2, CGAT_ACT_NONE, Gi, d.W2, c.s, xb));
-  // node-side scales {max |Gi|, max |Gj|, max |x|} at scales[2..4] (rebuilt path in the f16x3 mode, see the caller)
-  const float* ns = ((rc || node_scales) && scales && d.C == 128 && (((uintptr_t)x) & 15) == 0) ? scales + 2 : nullptr;
-  if (rc) {
-    RUN(edge_gj_launch(*rc, plan->src_rowptr, plan->src_pos, d.N, d.W2, Gj, d.W2, c.s,
-                       ns ? const_cast<float*>(ns) + 1 : nullptr));
-  } else {
-    RUN(seg_wsum_launch(gZ, d.W2, plan->src_pos, nullptr, 0, 1, plan->src_rowptr, d.N, d.W2, CGAT_ACT_NONE, Gj, d.W2,
-                        c.s, xb));
-    if (ns && node_scales && !c.dry && d.N > 0 && d.W2 % 128 == 0 && ((((uintptr_t)Gi) | ((uintptr_t)Gj)) & 15) == 0) {
-      // stored-gZ path with scales (vector attention): the segment sums carry no maxima, three passes over [N, .] rows
-      float* w = const_cast<float*>(ns);
-      RUN(absmax_rows128_launch(Gi, 128, (int)((long)d.N * d.W2 / 128), w, c.s));
-      RUN(absmax_rows128_launch(Gj, 128, (int)((long)d.N * d.W2 / 128), w + 1, c.s));
-      RUN(absmax_rows128_launch(x, d.C, d.N, w + 2, c.s));
-    } else if (node_scales) {
-      ns = nullptr;
-    }
-  }
-  // node-side products of the operand split: g_x = Gi W_i + Gj W_j,  grad W_i = Gi^T x,  grad W_j = Gj^T x.
-  // Same shapes as the two edge kernels (K = 1536 -> 128 outputs per row; K = rows -> 1536 x 128): reuse them on
-  // the row-major Gi/Gj when the node width is 128, generic GEMMs otherwise
+// ---- the operand-split first layer's backward tail ----
+// Everything downstream of the pre-activation gradient gZ[t, :] (destination-sorted slots) of the operand-split first
+// layer: gradients wrt edge_attr, x, the stacked weight [W2, D] = [W_i | W_e | W_j] and its bias.  Shared by the
+// scalar-attention backward (gZ from the fused segment kernel, column-blocked, Gi already summed) and the edge_hidden
+// op (gZ row-major from autograd).
+struct GzView {
+  const float* ptr;   // element (t, 128 a + j) at ptr[t * ld + a * block + j]; nullptr: not stored, rebuilt from *rc
+  long ld, block;
+};
+static EdgeRC edge_rc_make(const unsigned* mask, const float* ga, const float* alpha, const float* gS, const float* wA,
+                           const int* dst, int H, int Hd) {
+  EdgeRC rc = {};
+  rc.mask = mask; rc.ga = ga; rc.alpha = alpha; rc.gS = gS; rc.wA = wA; rc.dst = dst;
+  rc.H = H; rc.Hd = Hd; rc.HHd = H * Hd; rc.nw = 2 * H * Hd / 32;
+  return rc;
+}
+struct EdgeTail {
+  GzView gZ;
+  float *Gi, *Gj;        // [N, W2] segment sums of gZ by destination / by source
+  bool have_Gi;          // the caller has summed Gi already
+  const float* Wcat;     // the stacked weight [W2, D]
+  float *gWcat, *gbcat;
+  float *Wq, *gw_ws;     // edge_z_wq_floats(W2) / edge_gw_ws_floats(E, W2) floats of workspace
+  const float* scales;   // f16x3 mode, optional: device {max |gZ|, max |e|} -> the per-edge products run on two fp16 planes;
+                         // [2..4] then take the node-side maxima {max |Gi|, max |Gj|, max |x|}
+  const EdgeRC* rc;      // gZ was not stored; the per-edge launches and the source-side sum rebuild its rows (kernels.h)
+  bool node_scales;      // stored gZ: form the node-side maxima by three passes (the rebuilt path's kernels fold them in)
+  bool gw_force_six;     // debug entry only: grad W_e's launch keeps its six-pass form
+  const float *x, *e;
+  float *g_x, *g_e;
+};
+
+enum NodeSide { NODE_KSPLIT, NODE_SMALL_ROWS, NODE_LAUNCHES, NODE_GEMM };
+enum EdgeProduct { PRODUCT_KSPLIT, PRODUCT_LAUNCH, PRODUCT_GEMM };
+struct TailRoute {
+  // node-side products g_x = Gi W_i + Gj W_j, grad W_i = Gi^T x, grad W_j = Gj^T x.  Same shapes as the two edge kernels
+  // (K = 1536 -> 128 outputs per row; K = rows -> 1536 x 128): reuse them on the row-major Gi / Gj when the node width is
+  // 128 -- g_x as K-split slabs at few row tiles, as the small-row GEMM pair at a few hundred atoms -- generic GEMMs otherwise
+  NodeSide node;
+  int Sx, Se;           // K groups of the node-side / edge-side K = W2 -> 128 product (1: no split)
+  bool node_scales;     // the node-side launches run on {max |Gi|, max |Gj|, max |x|} at scales[2..4] (f16x3)
+  EdgeProduct ge, gw;   // grad edge_attr (K-split, per-edge launch or GEMM) and grad W_e (launch or GEMM)
+};
+static TailRoute tail_route(bool dry, const AttnDims& d, const EdgeTail& t) {
+  TailRoute r = {};
+  const bool maxima = t.scales && d.C == 128 && aligned16(t.x);
+  r.node_scales = t.rc ? maxima
+                       : maxima && t.node_scales && !dry && d.N > 0 && d.W2 % 128 == 0 && aligned16(t.Gi, t.Gj);
   // (K-split forms of the two K = W2 -> 128 products at few row tiles, edgebwd.hip: slabs in the scratch region)
-  const int Sx = (!ns && d.C == 128) ? edge_ge_ksplit_groups(d.N, d.W2) : 1;
-  const int Se = (!scales && d.Ce == 128 && !(rc && edge_mma_bf16())) ? edge_ge_ksplit_groups(d.E, d.W2) : 1;
-  if (Sx > 1) c.need((size_t)2 * Sx * d.N * 128 * sizeof(float));
-  if (Se > 1) c.need((size_t)Se * d.E * 128 * sizeof(float));
-  if (!c.dry && d.N > 0 && edge_ge_fast(d.C, d.W2, d.W2, 128, d.C, Gi, g_x) && edge_gw_fast(d.C, d.W2, d.W2, 128, Gi) &&
-      ((((uintptr_t)Gj) | ((uintptr_t)x)) & 15) == 0 && d.N <= d.E) {
-    if (Sx > 1 && c.scratch_bytes >= (size_t)2 * Sx * d.N * 128 * sizeof(float)) {
-      // g_x = Gi W_i + Gj W_j as 2 Sx slabs, added in order (round 6: 2 x 100 us of fp64 small-row products -> 3 launches)
-      float* sl = (float*)c.scratch;
-      RUN(edge_ge_ksplit_launch(Gi, d.W2, 128, Wcat, d.D, 1, Wq, d.W2, sl, nullptr, d.N, Sx, c.s));
-      RUN(edge_ge_ksplit_launch(Gj, d.W2, 128, Wcat + d.C + d.Ce, d.D, 1, Wq, d.W2, sl + (size_t)Sx * d.N * 128, nullptr, d.N,
-                                Sx, c.s));
-      RUN(sum_slabs_launch(sl, 2 * Sx, (long)d.N * 128, g_x, (long)d.N * 128, c.s));
-    } else if (d.N <= rowprog_max_rows()) {
-      // a few hundred atoms: the 256-row tiles of the per-edge kernel are 5 workgroups walking K = 1536 (91 us a launch
-      // at 1 280 atoms); as 16 x 16 wave tiles with the k range dealt over a workgroup's waves the chip is full
-      GemmParams g = gemm_params(d.N, d.C, d.W2, Gi, d.W2, Wcat, d.D, g_x, d.C);
-      g.b_kmajor = 1;
-      CGAT_TRY(c.gemm(g));
-      g = gemm_params(d.N, d.C, d.W2, Gj, d.W2, Wcat + d.C + d.Ce, d.D, g_x, d.C);
-      g.b_kmajor = 1;
-      g.beta = 1.f;
-      CGAT_TRY(c.gemm(g));
-    } else {
-      RUN(edge_ge_launch(Gi, d.W2, 128, Wcat, d.D, 1, Wq, d.W2, g_x, d.C, nullptr, d.N, 0, nullptr, c.s, ns));
-      RUN(edge_ge_launch(Gj, d.W2, 128, Wcat + d.C + d.Ce, d.D, 1, Wq, d.W2, g_x, d.C, nullptr, d.N, 1, nullptr, c.s,
-                         ns ? ns + 1 : nullptr));
-    }
-    RUN(edge_gw_launch(Gi, d.W2, 128, x, d.C, nullptr, d.N, d.W2, gw_ws, gWcat, d.D, c.s, ns, ns ? ns + 2 : nullptr));
-    RUN(edge_gw_launch(Gj, d.W2, 128, x, d.C, nullptr, d.N, d.W2, gw_ws, gWcat + d.C + d.Ce, d.D, c.s,
-                       ns ? ns + 1 : nullptr, ns ? ns + 2 : nullptr));
-  } else {
-    GemmParams g = gemm_params(d.N, d.C, d.W2, Gi, d.W2, Wcat, d.D, g_x, d.C);
-    g.b_kmajor = 1;
-    CGAT_TRY(c.gemm(g));
-    g = gemm_params(d.N, d.C, d.W2, Gj, d.W2, Wcat + d.C + d.Ce, d.D, g_x, d.C);
-    g.b_kmajor = 1;
-    g.beta = 1.f;
-    CGAT_TRY(c.gemm(g));
-    g = gemm_params(d.W2, d.C, d.N, Gi, d.W2, x, d.C, gWcat, d.D);
-    g.a_kmajor = 1; g.b_kmajor = 1;
-    CGAT_TRY(c.gemm(g, true));
-    g = gemm_params(d.W2, d.C, d.N, Gj, d.W2, x, d.C, gWcat + d.C + d.Ce, d.D);
-    g.a_kmajor = 1; g.b_kmajor = 1;
-    CGAT_TRY(c.gemm(g, true));
+  r.Sx = (!r.node_scales && d.C == 128) ? edge_ge_ksplit_groups(d.N, d.W2) : 1;
+  r.Se = (!t.scales && d.Ce == 128 && !(t.rc && edge_mma_bf16())) ? edge_ge_ksplit_groups(d.E, d.W2) : 1;
+  const bool node_fast = !dry && d.N > 0 && edge_ge_fast(d.C, d.W2, d.W2, 128, d.C, t.Gi, t.g_x) &&
+                         edge_gw_fast(d.C, d.W2, d.W2, 128, t.Gi) && aligned16(t.Gj, t.x) && d.N <= d.E;
+  r.node = !node_fast ? NODE_GEMM : r.Sx > 1 ? NODE_KSPLIT : d.N <= rowprog_max_rows() ? NODE_SMALL_ROWS : NODE_LAUNCHES;
+  const bool ge_fast = !dry && edge_ge_fast(d.Ce, d.W2, t.gZ.ld, t.gZ.block, d.Ce, t.gZ.ptr, t.g_e);
+  r.ge = !ge_fast ? PRODUCT_GEMM : r.Se > 1 ? PRODUCT_KSPLIT : PRODUCT_LAUNCH;
+  r.gw = (!dry && edge_gw_fast(d.Ce, d.W2, t.gZ.ld, t.gZ.block, t.gZ.ptr)) ? PRODUCT_LAUNCH : PRODUCT_GEMM;
+  return r;
+}
+static long tail_xblock(const AttnDims& d, const EdgeTail& t) {   // block stride of a stored gZ; 0 = plain row-major
+  return (t.gZ.ld == d.W2) ? 0 : t.gZ.block;
+}
+
+// segment sums of gZ: by destination (x_i side) unless the caller already has them, by source (x_j side)
+static int tail_segment_sums(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
+  const long xb = tail_xblock(d, t);
+  float* ns = r.node_scales ? const_cast<float*>(t.scales) + 2 : nullptr;
+  if (!t.have_Gi)
+    RUN(seg_wsum_launch(t.gZ.ptr, d.W2, nullptr, nullptr, 0, 1, plan->dst_rowptr, d.N, d.W2, CGAT_ACT_NONE, t.Gi, d.W2, c.s,
+                        xb));
+  if (t.rc) {
+    RUN(edge_gj_launch(*t.rc, plan->src_rowptr, plan->src_pos, d.N, d.W2, t.Gj, d.W2, c.s, ns ? ns + 1 : nullptr));
+    return CGAT_OK;
   }
-  CGAT_TRY(c.colsum(Gi, d.W2, d.N, d.W2, gbcat, 1.f));
-  // grad edge_attr[perm[t]] = gZ[t] @ W_e: split-bf16 kernel at the benchmark widths, generic GEMM otherwise
-  if (!c.dry && rc)
-    CGAT_CHECK_ARG(edge_ge_fast(d.Ce, d.W2, gz_ld, gzb, d.Ce, gZ, g_e) && edge_gw_fast(d.Ce, d.W2, gz_ld, gzb, gZ) && have_Gi,
-                   "nodes_attention_backward: the rebuilt-gZ path needs the split per-edge kernels");
-  if (!c.dry && Se > 1 && edge_ge_fast(d.Ce, d.W2, gz_ld, gzb, d.Ce, gZ, g_e) &&
-      c.scratch_bytes >= (size_t)Se * d.E * 128 * sizeof(float)) {
+  RUN(seg_wsum_launch(t.gZ.ptr, d.W2, plan->src_pos, nullptr, 0, 1, plan->src_rowptr, d.N, d.W2, CGAT_ACT_NONE, t.Gj, d.W2,
+                      c.s, xb));
+  if (ns) {
+    // stored-gZ path with scales (vector attention): the segment sums carry no maxima, three passes over [N, .] rows
+    RUN(absmax_rows128_launch(t.Gi, 128, (int)((long)d.N * d.W2 / 128), ns, c.s));
+    RUN(absmax_rows128_launch(t.Gj, 128, (int)((long)d.N * d.W2 / 128), ns + 1, c.s));
+    RUN(absmax_rows128_launch(t.x, d.C, d.N, ns + 2, c.s));
+  }
+  return CGAT_OK;
+}
+
+static int tail_gx_gemm_pair(Ctx& c, const AttnDims& d, const EdgeTail& t) {   // g_x = Gi W_i + Gj W_j
+  GemmParams g = gemm_params(d.N, d.C, d.W2, t.Gi, d.W2, t.Wcat, d.D, t.g_x, d.C);
+  g.b_kmajor = 1;
+  CGAT_TRY(c.gemm(g));
+  g = gemm_params(d.N, d.C, d.W2, t.Gj, d.W2, t.Wcat + d.C + d.Ce, d.D, t.g_x, d.C);
+  g.b_kmajor = 1;
+  g.beta = 1.f;
+  return c.gemm(g);
+}
+static int tail_node_products(Ctx& c, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
+  const float* ns = r.node_scales ? t.scales + 2 : nullptr;
+  const float* Wj = t.Wcat + d.C + d.Ce;
+  if (r.Sx > 1) c.need((size_t)2 * r.Sx * d.N * 128 * sizeof(float));
+  if (r.node == NODE_GEMM) {
+    CGAT_TRY(tail_gx_gemm_pair(c, d, t));
+    GemmParams g = gemm_params(d.W2, d.C, d.N, t.Gi, d.W2, t.x, d.C, t.gWcat, d.D);
+    g.a_kmajor = 1; g.b_kmajor = 1;
+    CGAT_TRY(c.gemm(g, true));
+    g = gemm_params(d.W2, d.C, d.N, t.Gj, d.W2, t.x, d.C, t.gWcat + d.C + d.Ce, d.D);
+    g.a_kmajor = 1; g.b_kmajor = 1;
+    CGAT_TRY(c.gemm(g, true));
+    return c.colsum(t.Gi, d.W2, d.N, d.W2, t.gbcat, 1.f);
+  }
+  if (r.node == NODE_KSPLIT) {
+    // g_x = Gi W_i + Gj W_j as 2 Sx slabs, added in order (round 6: 2 x 100 us of fp64 small-row products -> 3 launches)
     float* sl = (float*)c.scratch;
-    RUN(edge_ge_ksplit_launch(gZ, gz_ld, gzb, Wcat + d.C, d.D, 1, Wq, d.W2, sl, plan->dst_perm, d.E, Se, c.s, rc));
-    RUN(sum_slabs_launch(sl, Se, (long)d.E * 128, g_e, (long)d.E * 128, c.s));
-  } else if (!c.dry && edge_ge_fast(d.Ce, d.W2, gz_ld, gzb, d.Ce, gZ, g_e)) {
-    RUN(edge_ge_launch(gZ, gz_ld, gzb, Wcat + d.C, d.D, 1, Wq, d.W2, g_e, d.Ce, plan->dst_perm, d.E, 0, nullptr, c.s,
-                       scales, rc));
+    RUN(edge_ge_ksplit_launch(t.Gi, d.W2, 128, t.Wcat, d.D, 1, t.Wq, d.W2, sl, nullptr, d.N, r.Sx, c.s));
+    RUN(edge_ge_ksplit_launch(t.Gj, d.W2, 128, Wj, d.D, 1, t.Wq, d.W2, sl + (size_t)r.Sx * d.N * 128, nullptr, d.N, r.Sx, c.s));
+    RUN(sum_slabs_launch(sl, 2 * r.Sx, (long)d.N * 128, t.g_x, (long)d.N * 128, c.s));
+  } else if (r.node == NODE_SMALL_ROWS) {
+    // a few hundred atoms: the 256-row tiles of the per-edge kernel are 5 workgroups walking K = 1536 (91 us a launch
+    // at 1 280 atoms); as 16 x 16 wave tiles with the k range dealt over a workgroup's waves the chip is full
+    CGAT_TRY(tail_gx_gemm_pair(c, d, t));
   } else {
-    GemmParams g = gemm_params(d.E, d.Ce, d.W2, gZ, gz_ld, Wcat + d.C, d.D, g_e, d.Ce);
-    g.a_block = xb;
+    RUN(edge_ge_launch(t.Gi, d.W2, 128, t.Wcat, d.D, 1, t.Wq, d.W2, t.g_x, d.C, nullptr, d.N, 0, nullptr, c.s, ns));
+    RUN(edge_ge_launch(t.Gj, d.W2, 128, Wj, d.D, 1, t.Wq, d.W2, t.g_x, d.C, nullptr, d.N, 1, nullptr, c.s,
+                       ns ? ns + 1 : nullptr));
+  }
+  RUN(edge_gw_launch(t.Gi, d.W2, 128, t.x, d.C, nullptr, d.N, d.W2, t.gw_ws, t.gWcat, d.D, c.s, ns, ns ? ns + 2 : nullptr));
+  RUN(edge_gw_launch(t.Gj, d.W2, 128, t.x, d.C, nullptr, d.N, d.W2, t.gw_ws, t.gWcat + d.C + d.Ce, d.D, c.s,
+                     ns ? ns + 1 : nullptr, ns ? ns + 2 : nullptr));
+  return c.colsum(t.Gi, d.W2, d.N, d.W2, t.gbcat, 1.f);
+}
+
+// grad edge_attr[perm[t]] = gZ[t] @ W_e: split-bf16 kernel at the benchmark widths, generic GEMM otherwise
+static int tail_edge_ge(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
+  if (r.Se > 1) c.need((size_t)r.Se * d.E * 128 * sizeof(float));
+  if (r.ge == PRODUCT_KSPLIT) {
+    float* sl = (float*)c.scratch;
+    RUN(edge_ge_ksplit_launch(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.Wcat + d.C, d.D, 1, t.Wq, d.W2, sl, plan->dst_perm, d.E, r.Se,
+                              c.s, t.rc));
+    RUN(sum_slabs_launch(sl, r.Se, (long)d.E * 128, t.g_e, (long)d.E * 128, c.s));
+  } else if (r.ge == PRODUCT_LAUNCH) {
+    RUN(edge_ge_launch(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.Wcat + d.C, d.D, 1, t.Wq, d.W2, t.g_e, d.Ce, plan->dst_perm, d.E, 0,
+                       nullptr, c.s, t.scales, t.rc));
+  } else {
+    GemmParams g = gemm_params(d.E, d.Ce, d.W2, t.gZ.ptr, t.gZ.ld, t.Wcat + d.C, d.D, t.g_e, d.Ce);
+    g.a_block = tail_xblock(d, t);
     g.b_kmajor = 1;
     g.c_scatter = plan->dst_perm;
     CGAT_TRY(c.gemm(g));
   }
-  // grad W_e = gZ^T @ e[perm]
-  if (!c.dry && edge_gw_fast(d.Ce, d.W2, gz_ld, gzb, gZ)) {
-    RUN(edge_gw_launch(gZ, gz_ld, gzb, e, d.Ce, plan->dst_perm, d.E, d.W2, gw_ws, gWcat + d.C, d.D, c.s, scales,
-                       scales ? scales + 1 : nullptr, rc));
-  } else {
-    GemmParams g = gemm_params(d.W2, d.Ce, d.E, gZ, gz_ld, e, d.Ce, gWcat + d.C, d.D);
-    g.a_block = xb;
-    g.a_kmajor = 1; g.b_kmajor = 1;
-    g.b_kgather = plan->dst_perm;
-    CGAT_TRY(c.gemm(g, true));
+  return CGAT_OK;
+}
+// grad W_e = gZ^T @ e[perm]
+static int tail_edge_gw(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
+  if (r.gw == PRODUCT_LAUNCH) {
+    RUN(edge_gw_launch(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.e, d.Ce, plan->dst_perm, d.E, d.W2, t.gw_ws, t.gWcat + d.C, d.D, c.s,
+                       t.scales, t.scales ? t.scales + 1 : nullptr, t.rc, t.gw_force_six));
+    return CGAT_OK;
   }
+  GemmParams g = gemm_params(d.W2, d.Ce, d.E, t.gZ.ptr, t.gZ.ld, t.e, d.Ce, t.gWcat + d.C, d.D);
+  g.a_block = tail_xblock(d, t);
+  g.a_kmajor = 1; g.b_kmajor = 1;
+  g.b_kgather = plan->dst_perm;
+  return c.gemm(g, true);
+}
+static int tail_edge_products(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
+  if (!c.dry && t.rc)
+    CGAT_CHECK_ARG(r.ge != PRODUCT_GEMM && r.gw != PRODUCT_GEMM && t.have_Gi,
+                   "nodes_attention_backward: the rebuilt-gZ path needs the split per-edge kernels");
+  CGAT_TRY(tail_edge_ge(c, plan, d, t, r));
+  return tail_edge_gw(c, plan, d, t, r);
+}
+
+static int edge_first_layer_backward_tail(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t) {
+  const TailRoute r = tail_route(c.dry, d, t);
+  // Order: the HBM-bound kernels (segment sums, node-side products over the 0.5-GB Gi / Gj) first, the two matrix-bound
+  // per-edge products last -- the caller's side stream runs the matrix-bound dT launch on half of the chip meanwhile,
+  // and a matrix-bound kernel beside it takes 2.9x as long (edge_ge 1.3 -> 3.7 ms) where an HBM-bound one loses little.
+  CGAT_TRY(tail_segment_sums(c, plan, d, t, r));
+  CGAT_TRY(tail_node_products(c, d, t, r));
+  return tail_edge_products(c, plan, d, t, r);
+}
+
+// ---- backward ----
+struct AttnBwd {
+  AttnDims d;
+  const cgat_plan* plan;
+  const cgat_attn_params* p;
+  const cgat_attn_grads* gr;
+  const float *x, *e, *g_aggr;
+  float *g_x, *g_e;
+  float *Wcat, *gWcat, *gbcat, *gS, *gs, *gas, *tt, *ga, *gZ, *partial, *Gi, *Gj, *Wq, *gw_ws;
+  float* scales;      // [0] max |gZ|, [1] max |edge_attr| (f16x3 mode), [2..4] max |Gi|, |Gj|, |x|
+  int chunks;         // workgroups of the fused segment kernel
+  long gzb, gz_ld;    // gZ is stored in 128-column blocks [W2/128][E][128] when the width allows: the weight-gradient
+                      // product gZ^T @ e then streams each block contiguously instead of 512-byte pieces at a 6 KB stride
+  AttnSaved sv;
+  EdgeRC rc;
+  AttnBwdRoute r;
+};
+static AttnBwd attn_bwd_carve(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x, const float* e,
+                              const float* saved, const float* g_aggr, float* g_x, float* g_e, const cgat_attn_grads* gr) {
+  AttnBwd b = {};
+  const AttnDims d = b.d = attn_dims(plan, p);
+  b.plan = plan; b.p = p; b.gr = gr; b.x = x; b.e = e; b.g_aggr = g_aggr; b.g_x = g_x; b.g_e = g_e;
+  b.chunks = edge_seg_bwd_chunks(d.N);
+  if (!c.dry) b.sv = attn_saved(const_cast<float*>(saved), d);
+  b.Wcat = c.take<float>((size_t)d.W2 * d.D);
+  b.r = attn_bwd_route(c.dry, d, p, x, e, saved, b.sv.S, b.Wcat);
+  b.gWcat = c.take<float>((size_t)d.W2 * d.D);
+  b.gbcat = c.take<float>((size_t)d.W2);
+  b.gS = c.take<float>((size_t)d.N * d.HHd);
+  b.gs = c.take<float>((size_t)d.N * d.H);
+  b.gas = mode_split() ? c.take<float>((size_t)d.N * d.C) : nullptr;   // g_aggr / H (fast fc_out path)
+  b.tt = c.take<float>((size_t)d.E * d.H);
+  b.ga = c.take<float>((size_t)d.E * d.H);
+  b.gZ = c.take<float>(b.r.rc ? (size_t)d.E * (d.W2 / 32) : (size_t)d.E * d.W2);
+  b.partial = c.take<float>((size_t)b.chunks * d.HHd);
+  b.Gi = c.take<float>((size_t)d.N * d.W2);
+  b.Gj = c.take<float>((size_t)d.N * d.W2);
+  b.Wq = c.take<float>(edge_z_wq_floats(d.W2));
+  b.gw_ws = c.take<float>(edge_gw_ws_floats(d.E, d.W2));
+  b.scales = c.take<float>(64);
+  c.seal();
+  b.gzb = (d.W2 % 128 == 0) ? (long)d.E * 128 : 0;
+  b.gz_ld = b.gzb ? 128 : d.W2;
+  if (b.r.rc && !c.dry)
+    b.rc = edge_rc_make(reinterpret_cast<const unsigned*>(b.gZ), b.ga, b.sv.alpha, b.gS, p->A_out_w, plan->dst_sorted, d.H, d.Hd);
+  return b;
+}
+
+// The per-head second layer of the message network: gS = (1/H) g_aggr fc_out_M[h], grad fc_out_M, gs and grad bias_M.
+// At the benchmark widths (C = 128, Hd a multiple of 128): the input gradients on the dense-layer kernel (K = 128 -> Hd
+// outputs per head), the H * Hd / 128 weight-gradient blocks in one batched launch of the rows kernel (rowsdw.hip); 1/H
+// is folded into one scaled copy of g_aggr.
+static int attn_bwd_out_layer(Ctx& c, const AttnBwd& b) {
+  const AttnDims& d = b.d;
+  const cgat_attn_params* p = b.p;
+  const float invH = 1.f / d.H;
+  if (attn_bwd_out_shape(d)) {
+    c.need(rows_dw128_batch_ws_bytes(d.H * (d.Hd / 128), d.N));
+    c.need(linear128_ws_bytes(d.Hd));
+    c.need((size_t)d.H * linear128_heads_image_floats(d.Hd) * sizeof(float));
+  }
+  if (b.r.out_fast) {
+    RUN(scale_launch(b.g_aggr, invH, b.gas, (long)d.N * d.C, c.s));
+    if (b.r.out_heads_one) {
+      // all heads in one launch pair (round 6): head h reads the same gas, its weight at + h * C * Hd, writes gS + h * Hd
+      CGAT_TRY(linear128_heads_launch(d.H, b.gas, d.C, 0, p->M_out_w, 1, d.Hd, (long)d.C * d.Hd, nullptr, 0, CGAT_ACT_NONE, 0,
+                                      b.gS, d.HHd, d.Hd, d.N, c.scratch, c.s, d.Hd, nullptr, 0, 0, nullptr));
+    } else {
+      for (int h = 0; h < d.H; ++h) {   // gS[:,h,:] = gas @ fc_out_M[h]
+        GemmParams g = gemm_params(d.N, d.Hd, d.C, b.gas, d.C, p->M_out_w + (size_t)h * d.C * d.Hd, d.Hd,
+                                   b.gS + (size_t)h * d.Hd, d.HHd);
+        g.b_kmajor = 1;
+        CGAT_TRY(c.gemm(g));
+      }
+    }
+    if (!c.dry) {   // grad fc_out_M[h] = gas^T S[:,h,:]
+      DwBatchDesc w;
+      memset(&w, 0, sizeof(w));
+      w.rows = d.N; w.ldg = d.C; w.ldx = d.HHd; w.ldo = d.Hd;
+      for (int h = 0; h < d.H; ++h)
+        for (int j = 0; j < d.Hd / 128; ++j)
+          w.it[w.n++] = {b.gas, b.sv.S + (size_t)h * d.Hd + 128 * j, b.gr->M_out_w + (size_t)h * d.C * d.Hd + 128 * j, nullptr};
+      CGAT_TRY(rows_dw128_batch_launch(w, c.scratch, c.scratch_bytes, c.s));
+    }
+  } else {
+    for (int h = 0; h < d.H; ++h) {
+      const float* Wo = p->M_out_w + (size_t)h * d.C * d.Hd;
+      // gS[:,h,:] = (1/H) g_aggr @ fc_out_M[h]
+      GemmParams g = gemm_params(d.N, d.Hd, d.C, b.g_aggr, d.C, Wo, d.Hd, b.gS + (size_t)h * d.Hd, d.HHd);
+      g.b_kmajor = 1;
+      g.alpha = invH;
+      CGAT_TRY(c.gemm(g));
+      // grad fc_out_M[h] = (1/H) g_aggr^T S[:,h,:]
+      g = gemm_params(d.C, d.Hd, d.N, b.g_aggr, d.C, b.sv.S + (size_t)h * d.Hd, d.HHd,
+                      b.gr->M_out_w + (size_t)h * d.C * d.Hd, d.Hd);
+      g.a_kmajor = 1; g.b_kmajor = 1;
+      g.alpha = invH;
+      CGAT_TRY(c.gemm(g, true));
+    }
+  }
+  // gs[n,h] = (1/H) g_aggr[n,:] . bias_M[h,:]
+  GemmParams g = gemm_params(d.N, d.H, d.C, b.g_aggr, d.C, p->M_out_b, d.C, b.gs, d.H);
+  g.alpha = invH;
+  CGAT_TRY(c.gemm(g));
+  // grad bias_M[h,c] = (1/H) sum_n ssum[n,h] g_aggr[n,c]
+  g = gemm_params(d.H, d.C, d.N, b.sv.ssum, d.H, b.g_aggr, d.C, b.gr->M_out_b, d.C);
+  g.a_kmajor = 1; g.b_kmajor = 1;
+  g.alpha = invH;
+  return c.gemm(g, true);
+}
+
+// g_alpha, softmax backward, gZ, the destination-side segment sum Gi and the partial sums for
+// grad fc_out_A, all per whole destination segment in one pass (edge_seg_bwd_kernel); then the f16x3 maxima and grad fc_out_A
+static int attn_bwd_segments(Ctx& c, const AttnBwd& b) {
+  const AttnDims& d = b.d;
+  const AttnBwdRoute& r = b.r;
+  if (!c.dry && d.N > 0) {
+    if (edge_bf16_storage() && !r.z_bf16) {
+      cgat_set_error("nodes_attention_backward: edge storage \"bf16\" is set but this layer has no bf16 form");
+      return CGAT_ERR_UNSUPPORTED;
+    }
+    if (r.rc)
+      CGAT_CHECK_ARG(r.vec && aligned16(b.e),
+                     "nodes_attention_backward: saved, edge_attr and MH_A.fc_out.weight must be 16-byte aligned at these widths");
+    unsigned* mask = r.rc ? reinterpret_cast<unsigned*>(b.gZ) : nullptr;
+    float* gzmax = r.have_scales ? b.scales : nullptr;
+    // [2] max |Gi|, [3] max |Gj|, [4] max |x|: with them the node-side products run in the fp16 form too (rebuilt path)
+    float* gimax = (r.have_scales && r.rc) ? b.scales + 2 : nullptr;
+    CGAT_TRY(edge_seg_bwd_launch(b.sv.Z, b.gZ, b.gzb, b.sv.alpha, b.gS, b.gs, b.plan->dst_rowptr, b.p->A_out_w, d.N, d.H, d.Hd,
+                                 b.tt, b.ga, b.Gi, b.partial, gzmax, mask, gimax, r.vec, r.z_bf16_six, r.z_bf16, r.rc,
+                                 r.have_scales, c.s));
+  }
+  if (r.have_scales) RUN(absmax_rows128_launch(b.e, d.Ce, d.E, b.scales + 1, c.s));
+  if (r.have_scales && r.rc && d.C == 128 && aligned16(b.x)) RUN(absmax_rows128_launch(b.x, d.C, d.N, b.scales + 4, c.s));
+  CGAT_TRY(c.colsum(b.ga, d.H, d.E, d.H, b.gr->A_out_b, 1.f));
+  return c.colsum(b.partial, d.HHd, d.N > 0 ? b.chunks : 0, d.HHd, b.gr->A_out_w, 1.f);
+}
+
+static EdgeTail attn_bwd_tail(const AttnBwd& b) {
+  EdgeTail t = {};
+  t.gZ = {b.r.rc ? nullptr : b.gZ, b.gz_ld, b.gzb};
+  t.Gi = b.Gi; t.Gj = b.Gj; t.have_Gi = true;
+  t.Wcat = b.Wcat; t.gWcat = b.gWcat; t.gbcat = b.gbcat;
+  t.Wq = b.Wq; t.gw_ws = b.gw_ws;
+  t.scales = b.r.have_scales ? b.scales : nullptr;
+  t.rc = b.r.rc ? &b.rc : nullptr;
+  t.x = b.x; t.e = b.e; t.g_x = b.g_x; t.g_e = b.g_e;
+  return t;
+}
+
+static int attn_bwd_scatter_grads(Ctx& c, const AttnBwd& b) {
+  const AttnDims& d = b.d;
+  Copy2DJobs j;
+  j.n = 4;
+  j.job[0] = {b.gWcat, d.D, b.gr->A_in_w, d.D, d.HHd, d.D};
+  j.job[1] = {b.gWcat + (size_t)d.HHd * d.D, d.D, b.gr->M_in_w, d.D, d.HHd, d.D};
+  j.job[2] = {b.gbcat, d.HHd, b.gr->A_in_b, d.HHd, 1, d.HHd};
+  j.job[3] = {b.gbcat + d.HHd, d.HHd, b.gr->M_in_b, d.HHd, 1, d.HHd};
+  RUN(copy2d_multi_launch(j, c.s));
   return CGAT_OK;
 }
 
 static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x, const float* e,
                               const float* saved, const float* g_aggr, float* g_x, float* g_e,
                               const cgat_attn_grads* gr) {
-  const AttnDims d = attn_dims(plan, p);
-  const int chunks = edge_seg_bwd_chunks(d.N);  // workgroups of the fused segment kernel
-  float* Wcat = c.take<float>((size_t)d.W2 * d.D);
-  float* gWcat = c.take<float>((size_t)d.W2 * d.D);
-  float* gbcat = c.take<float>((size_t)d.W2);
-  float* gS = c.take<float>((size_t)d.N * d.HHd);
-  float* gs = c.take<float>((size_t)d.N * d.H);
-  float* gas = mode_split() ? c.take<float>((size_t)d.N * d.C) : nullptr;   // g_aggr / H (fast fc_out path)
-  float* tt = c.take<float>((size_t)d.E * d.H);
-  float* ga = c.take<float>((size_t)d.E * d.H);
-  // At the benchmark widths gZ [E, W2] is never stored: edge_seg_bwd_kernel leaves one bit per element behind and the
-  // three consumers rebuild the rows (struct EdgeRC, kernels.h) -- E * W2 / 8 bytes of workspace instead of 4 E * W2
-  // (edge storage mode 2 keeps the stored-gZ backward of round 1 at these widths too: the A/B reference of the tests)
-  const bool rc_shape = mode_split() && edge_rc_shape(d.Ce, d.H, d.Hd) && d.W2 % 256 == 0 && d.N > 0 && d.E > 0 &&
-                        edge_storage() != 2;
-  float* gZ = c.take<float>(rc_shape ? (size_t)d.E * (d.W2 / 32) : (size_t)d.E * d.W2);
-  float* partial = c.take<float>((size_t)chunks * d.HHd);
-  float* Gi = c.take<float>((size_t)d.N * d.W2);
-  float* Gj = c.take<float>((size_t)d.N * d.W2);
-  float* Wq = c.take<float>(edge_z_wq_floats(d.W2));
-  float* gw_ws = c.take<float>(edge_gw_ws_floats(d.E, d.W2));
-  float* scales = c.take<float>(64);   // [0] max |gZ|, [1] max |edge_attr| (f16x3 mode)
-  c.seal();
-  AttnSaved sv = c.dry ? AttnSaved{} : attn_saved(const_cast<float*>(saved), d);
-  const float invH = 1.f / d.H;
-  // gZ is stored in 128-column blocks [W2/128][E][128] when the width allows: the weight-gradient
-  // product gZ^T @ e then streams each block contiguously instead of 512-byte pieces at a 6 KB stride
-  const long gzb = (d.W2 % 128 == 0) ? (long)d.E * 128 : 0;
-  const long gz_ld = gzb ? 128 : d.W2;
-
-  CGAT_TRY(stack_in_weights(c, p, d, Wcat, nullptr));
-  // The per-head second layer of the message network at the benchmark widths (C = 128, Hd a multiple of 128): the input
-  // gradients on the dense-layer kernel (K = 128 -> Hd outputs per head), the H * Hd / 128 weight-gradient blocks in one
-  // batched launch of the rows kernel (rowsdw.hip); 1/H is folded into one scaled copy of g_aggr.
-  const bool out_fast = mode_split() && d.C == 128 && d.Hd % 128 == 0 && d.H * (d.Hd / 128) <= DW_BATCH_MAX;
-  bool out_done = false;
-  if (out_fast) {
-    c.need(rows_dw128_batch_ws_bytes(d.H * (d.Hd / 128), d.N));
-    c.need(linear128_ws_bytes(d.Hd));
-    c.need((size_t)d.H * linear128_heads_image_floats(d.Hd) * sizeof(float));
-    DwBatchDesc b;
-    memset(&b, 0, sizeof(b));
-    b.rows = d.N; b.ldg = d.C; b.ldx = d.HHd; b.ldo = d.Hd;
-    if (!c.dry) {
-      for (int h = 0; h < d.H; ++h)
-        for (int j = 0; j < d.Hd / 128; ++j)
-          b.it[b.n++] = {gas, sv.S + (size_t)h * d.Hd + 128 * j, gr->M_out_w + (size_t)h * d.C * d.Hd + 128 * j, nullptr};
-    }
-    if (c.dry || (d.N > 0 && linear128_fast(d.C, d.Hd, d.C, d.HHd, gas, gS) && rows_dw128_batch_fast(b) &&
-                  c.scratch_bytes >= rows_dw128_batch_ws_bytes(b.n, d.N))) {
-      RUN(scale_launch(g_aggr, invH, gas, (long)d.N * d.C, c.s));
-      const size_t gs_img_bytes = (size_t)d.H * linear128_heads_image_floats(d.Hd) * sizeof(float);
-      if (!c.dry && mode_24bit() && d.N > rowprog_max_rows() && d.H > 1 &&
-          c.scratch_bytes >= gs_img_bytes && (((uintptr_t)p->M_out_w) & 15) == 0) {
-        // all heads in one launch pair (round 6): head h reads the same gas, its weight at + h * C * Hd, writes gS + h * Hd
-        CGAT_TRY(linear128_heads_launch(d.H, gas, d.C, 0, p->M_out_w, 1, d.Hd, (long)d.C * d.Hd, nullptr, 0, CGAT_ACT_NONE, 0, gS,
-                                        d.HHd, d.Hd, d.N, c.scratch, c.s, d.Hd, nullptr, 0, 0, nullptr));
-      } else {
-        for (int h = 0; h < d.H; ++h) {   // gS[:,h,:] = gas @ fc_out_M[h]
-          GemmParams g = gemm_params(d.N, d.Hd, d.C, gas, d.C, p->M_out_w + (size_t)h * d.C * d.Hd, d.Hd,
-                                     gS + (size_t)h * d.Hd, d.HHd);
-          g.b_kmajor = 1;
-          CGAT_TRY(c.gemm(g));
-        }
-      }
-      RUN(rows_dw128_batch_launch(b, c.scratch, c.scratch_bytes, c.s));   // grad fc_out_M[h] = gas^T S[:,h,:]
-      out_done = true;
-    }
-  }
-  for (int h = 0; h < d.H && !out_done; ++h) {
-    const float* Wo = p->M_out_w + (size_t)h * d.C * d.Hd;
-    {  // gS[:,h,:] = (1/H) g_aggr @ fc_out_M[h]
-      GemmParams g = gemm_params(d.N, d.Hd, d.C, g_aggr, d.C, Wo, d.Hd, gS + (size_t)h * d.Hd, d.HHd);
-      g.b_kmajor = 1;
-      g.alpha = invH;
-      CGAT_TRY(c.gemm(g));
-    }
-    {  // grad fc_out_M[h] = (1/H) g_aggr^T S[:,h,:]
-      GemmParams g = gemm_params(d.C, d.Hd, d.N, g_aggr, d.C, sv.S + (size_t)h * d.Hd, d.HHd,
-                                 gr->M_out_w + (size_t)h * d.C * d.Hd, d.Hd);
-      g.a_kmajor = 1; g.b_kmajor = 1;
-      g.alpha = invH;
-      CGAT_TRY(c.gemm(g, true));
-    }
-  }
-  {  // gs[n,h] = (1/H) g_aggr[n,:] . bias_M[h,:]
-    GemmParams g = gemm_params(d.N, d.H, d.C, g_aggr, d.C, p->M_out_b, d.C, gs, d.H);
-    g.alpha = invH;
-    CGAT_TRY(c.gemm(g));
-    // grad bias_M[h,c] = (1/H) sum_n ssum[n,h] g_aggr[n,c]
-    g = gemm_params(d.H, d.C, d.N, sv.ssum, d.H, g_aggr, d.C, gr->M_out_b, d.C);
-    g.a_kmajor = 1; g.b_kmajor = 1;
-    g.alpha = invH;
-    CGAT_TRY(c.gemm(g, true));
-  }
-  // g_alpha, softmax backward, gZ, the destination-side segment sum Gi and the partial sums for
-  // grad fc_out_A, all per whole destination segment in one pass (edge_seg_bwd_kernel)
-  bool have_scales = false, zb = false;
-  if (!c.dry && d.N > 0) {
-    const bool vec = (d.Hd % 4 == 0) && ((((uintptr_t)sv.Z) | ((uintptr_t)gZ) | ((uintptr_t)gS) | ((uintptr_t)Gi) |
-                                          ((uintptr_t)p->A_out_w)) & 15) == 0;
-    have_scales = vec && mode_f16() && d.Ce == 128 && (((uintptr_t)e) & 15) == 0;
-    // the forward stored Z as bf16 under exactly this predicate (same tensors, same alignment)
-    const bool zb_x = attn_bf16(d) && mode_f16() &&
-                      edge_zx_fast(d.C, d.Ce, d.W2, d.H, d.Hd, d.W2, d.W2, e, x, Gi, sv.Z, p->A_out_w) &&
-                      edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, Gi, Gj, Gi, gbcat);
-    const bool zb_6 = attn_bf16(d) && !mode_f16() &&
-                      edge_z_fast(d.Ce, d.W2, d.H, d.Hd, d.Ce, d.W2, d.W2, e, Gi, Gj, sv.Z, p->A_out_w);
-    zb = zb_x || zb_6;
-    if (edge_bf16_storage() && !zb) {
-      cgat_set_error("nodes_attention_backward: edge storage \"bf16\" is set but this layer has no bf16 form");
-      return CGAT_ERR_UNSUPPORTED;
-    }
-    if (rc_shape)
-      CGAT_CHECK_ARG(vec && (((uintptr_t)e) & 15) == 0,
-                     "nodes_attention_backward: saved, edge_attr and MH_A.fc_out.weight must be 16-byte aligned at these widths");
-    unsigned* mask = rc_shape ? reinterpret_cast<unsigned*>(gZ) : nullptr;
-    float* gzmax = have_scales ? scales : nullptr;
-    // [2] max |Gi|, [3] max |Gj|, [4] max |x|: with them the node-side products run in the fp16 form too (rebuilt path)
-    float* gimax = (have_scales && rc_shape) ? scales + 2 : nullptr;
-    CGAT_TRY(edge_seg_bwd_launch(sv.Z, gZ, gzb, sv.alpha, gS, gs, plan->dst_rowptr, p->A_out_w, d.N, d.H, d.Hd, tt, ga, Gi,
-                                 partial, gzmax, mask, gimax, vec, zb_6, zb, rc_shape, have_scales, c.s));
-  }
-  EdgeRC rc = {};
-  if (rc_shape && !c.dry) {
-    rc.mask = reinterpret_cast<const unsigned*>(gZ); rc.ga = ga; rc.alpha = sv.alpha; rc.gS = gS; rc.wA = p->A_out_w;
-    rc.dst = plan->dst_sorted; rc.H = d.H; rc.Hd = d.Hd; rc.HHd = d.HHd; rc.nw = d.W2 / 32;
-  }
-  if (have_scales) RUN(absmax_rows128_launch(e, d.Ce, d.E, scales + 1, c.s));
-  if (have_scales && rc_shape && d.C == 128 && (((uintptr_t)x) & 15) == 0) RUN(absmax_rows128_launch(x, d.C, d.N, scales + 4, c.s));
-  CGAT_TRY(c.colsum(ga, d.H, d.E, d.H, gr->A_out_b, 1.f));
-  CGAT_TRY(c.colsum(partial, d.HHd, d.N > 0 ? chunks : 0, d.HHd, gr->A_out_w, 1.f));
-  CGAT_TRY(edge_first_layer_backward_tail(c, plan, d, Wcat, gWcat, gbcat, rc_shape ? nullptr : gZ, gz_ld, gzb, Gi, Gj, true,
-                                          x, e, g_x, g_e, Wq, gw_ws, have_scales ? scales : nullptr,
-                                          rc_shape ? &rc : nullptr));
-  {
-    Copy2DJobs j;
-    j.n = 4;
-    j.job[0] = {gWcat, d.D, gr->A_in_w, d.D, d.HHd, d.D};
-    j.job[1] = {gWcat + (size_t)d.HHd * d.D, d.D, gr->M_in_w, d.D, d.HHd, d.D};
-    j.job[2] = {gbcat, d.HHd, gr->A_in_b, d.HHd, 1, d.HHd};
-    j.job[3] = {gbcat + d.HHd, d.HHd, gr->M_in_b, d.HHd, 1, d.HHd};
-    RUN(copy2d_multi_launch(j, c.s));
-  }
+  const AttnBwd b = attn_bwd_carve(c, plan, p, x, e, saved, g_aggr, g_x, g_e, gr);
+  CGAT_TRY(stack_in_weights(c, p, b.d, b.Wcat, nullptr));
+  CGAT_TRY(attn_bwd_out_layer(c, b));
+  CGAT_TRY(attn_bwd_segments(c, b));
+  CGAT_TRY(edge_first_layer_backward_tail(c, plan, b.d, attn_bwd_tail(b)));
+  CGAT_TRY(attn_bwd_scatter_grads(c, b));
   return check_ws(c, "nodes_attention_backward");
 }
 
@@ -673,22 +879,13 @@ static int edge_hidden_forward_impl(Ctx& c, const cgat_plan* plan, const AttnDim
   float* Wq = c.take<float>(edge_z_wq_floats(d.W2));
   c.seal();
   const bool fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 && d.C == 128 &&
-                    edge_z_fast(d.Ce, d.W2, 1, d.W2 / 2, d.Ce, d.W2, d.W2, e, Pi, Pj, Hout, b_in) &&
-                    (((uintptr_t)x) & 15) == 0;
+                    edge_z_fast(d.Ce, d.W2, 1, d.W2 / 2, d.Ce, d.W2, d.W2, e, Pi, Pj, Hout, b_in) && aligned16(x);
+  CGAT_TRY(node_projections(c, d, fast, true, x, w_in, b_in, NodeProj{Pi, Pj, Wq}));
   if (fast) {
-    RUN(edge_z_launch(x, d.C, nullptr, w_in, d.D, Wq, d.W2, b_in, nullptr, nullptr, nullptr, 0, Pi, d.W2, d.N, nullptr,
-                      nullptr, 1, d.W2 / 2, nullptr, c.s));
-    RUN(edge_z_launch(x, d.C, nullptr, w_in + d.C + d.Ce, d.D, Wq, d.W2, nullptr, nullptr, nullptr, nullptr, 0, Pj, d.W2,
-                      d.N, nullptr, nullptr, 1, d.W2 / 2, nullptr, c.s));
     RUN(edge_z_launch(e, d.Ce, plan->dst_perm, w_in + d.C, d.D, Wq, d.W2, Pi, plan->dst_sorted, Pj, plan->src_sorted, d.W2,
                       Hout, d.W2, d.E, nullptr, nullptr, 1, d.W2 / 2, nullptr, c.s, CGAT_ACT_LEAKY, hmax));
   } else {
-    GemmParams g = gemm_params(d.N, d.W2, d.C, x, d.C, w_in, d.D, Pi, d.W2);
-    g.bias = b_in;
-    CGAT_TRY(c.gemm(g));
-    g = gemm_params(d.N, d.W2, d.C, x, d.C, w_in + d.C + d.Ce, d.D, Pj, d.W2);
-    CGAT_TRY(c.gemm(g));
-    g = gemm_params(d.E, d.W2, d.Ce, e, d.Ce, w_in + d.C, d.D, Hout, d.W2);
+    GemmParams g = gemm_params(d.E, d.W2, d.Ce, e, d.Ce, w_in + d.C, d.D, Hout, d.W2);
     g.a_rgather = plan->dst_perm;
     g.add1 = Pi; g.add1_idx = plan->dst_sorted;
     g.add2 = Pj; g.add2_idx = plan->src_sorted;
@@ -706,17 +903,19 @@ static int edge_hidden_backward_impl(Ctx& c, const cgat_plan* plan, const AttnDi
   // g_is_pre: g_H already is the gradient of the PRE-activation (cgat_linear_backward_dact folded LeakyReLU' into the
   // product that made it) and gpre_absmax[0] its maximum: no elementwise pass, no copy -- the tail reads g_H itself
   float* gZ = g_is_pre ? const_cast<float*>(g_H) : c.take<float>((size_t)d.E * d.W2);
-  float* Gi = c.take<float>((size_t)d.N * d.W2);
-  float* Gj = c.take<float>((size_t)d.N * d.W2);
-  float* Wq = c.take<float>(edge_z_wq_floats(d.W2));
-  float* gw_ws = c.take<float>(edge_gw_ws_floats(d.E, d.W2));
+  EdgeTail t = {};
+  t.gZ = {gZ, d.W2, 128};
+  t.Gi = c.take<float>((size_t)d.N * d.W2);
+  t.Gj = c.take<float>((size_t)d.N * d.W2);
+  t.Wq = c.take<float>(edge_z_wq_floats(d.W2));
+  t.gw_ws = c.take<float>(edge_gw_ws_floats(d.E, d.W2));
   float* scales = c.take<float>(8);       // f16x3: [0] max |gZ|, [1] max |e|, [2..4] max |Gi|, |Gj|, |x| (set by the tail)
   c.seal();
   // f16x3 mode: the LeakyReLU backward also yields max |gZ| and one pass over edge_attr max |e| -- with them the per-edge
   // products of the tail (K = W2 -> 128 and K = E) run on two fp16 planes (three passes) instead of the six-pass bf16
   // form they fell back to without scales: 43 + 22 ms of the harness-default network's 252-ms step
   bool have_scales = false;
-  const bool f16_ok = !c.dry && mode_f16() && d.Ce == 128 && (((uintptr_t)e) & 15) == 0 && d.E > 0;
+  const bool f16_ok = !c.dry && mode_f16() && d.Ce == 128 && aligned16(e) && d.E > 0;
   if (g_is_pre) {
     if (f16_ok && gpre_absmax) {
       CGAT_TRY(fill_launch(scales, 0.f, 8, c.s));
@@ -730,8 +929,11 @@ static int edge_hidden_backward_impl(Ctx& c, const cgat_plan* plan, const AttnDi
     RUN(act_bwd_launch(Hsaved, g_H, gZ, (long)d.E * d.W2, CGAT_ACT_LEAKY, c.s));
   }
   if (have_scales) RUN(absmax_rows128_launch(e, d.Ce, d.E, scales + 1, c.s));
-  CGAT_TRY(edge_first_layer_backward_tail(c, plan, d, w_in, g_w_in, g_b_in, gZ, d.W2, 128, Gi, Gj, false, x, e, g_x, g_e, Wq,
-                                          gw_ws, have_scales ? scales : nullptr, nullptr, /*node_scales=*/have_scales));
+  t.Wcat = w_in; t.gWcat = g_w_in; t.gbcat = g_b_in;
+  t.scales = have_scales ? scales : nullptr;
+  t.node_scales = have_scales;
+  t.x = x; t.e = e; t.g_x = g_x; t.g_e = g_e;
+  CGAT_TRY(edge_first_layer_backward_tail(c, plan, d, t));
   return check_ws(c, "edge_hidden_backward");
 }
 
@@ -808,6 +1010,39 @@ extern "C" int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn
   return run_sized("nodes_attention_infer", ws, ws_bytes, stream,
                    [&](Ctx& c) { return attn_forward_impl(c, plan, p, x, edge_attr, aggr, nullptr, true); });
 }
+extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                             const float* edge_attr, const float* saved, const float* g_aggr,
+                                             float* g_x, float* g_edge_attr, const cgat_attn_grads* g, void* ws,
+                                             size_t ws_bytes, void* stream) {
+  CGAT_TRY(attn_check(plan, p));
+  CGAT_CHECK_ARG(g, "nodes_attention_backward: null grads");
+  return run_sized("nodes_attention_backward", ws, ws_bytes, stream, [&](Ctx& c) {
+    return attn_backward_impl(c, plan, p, x, edge_attr, saved, g_aggr, g_x, g_edge_attr, g);
+  });
+}
+
+// ---- debug: the routes of a layer as bit masks (include/cgat_hip.h), for 16-byte aligned operands: the carve and route
+// functions of the real pass over a null, unbounded workspace ----
+static uint32_t route_bits(std::initializer_list<bool> on) {
+  uint32_t m = 0, i = 0;
+  for (bool b : on) m |= (uint32_t)b << i++;
+  return m;
+}
+extern "C" uint32_t cgat_debug_nodes_attention_route(const cgat_plan* plan, const cgat_attn_params* p, int32_t backward) {
+  if (attn_check(plan, p) != CGAT_OK) return 0;
+  Ctx c(nullptr, (size_t)-1 / 2, false, nullptr);
+  if (!backward) {
+    const AttnFwdRoute r = attn_fwd_carve(c, plan, p, nullptr, nullptr, nullptr, nullptr, false).r;
+    return route_bits({attn_infer_fused(attn_dims(plan, p)), r.zx, r.fused_z, r.z_bf16, r.proj_fast, r.out_fast, r.out_one});
+  }
+  const AttnBwd b = attn_bwd_carve(c, plan, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const TailRoute t = tail_route(false, b.d, attn_bwd_tail(b));
+  return route_bits({b.r.rc, b.r.vec, b.r.have_scales, b.r.z_bf16, b.r.z_bf16_six, b.r.out_fast, b.r.out_heads_one,
+                     t.node == NODE_KSPLIT, t.node == NODE_SMALL_ROWS, t.node == NODE_LAUNCHES, t.node == NODE_GEMM,
+                     t.node_scales, t.ge == PRODUCT_KSPLIT, t.ge == PRODUCT_LAUNCH, t.ge == PRODUCT_GEMM,
+                     t.gw == PRODUCT_LAUNCH, t.gw == PRODUCT_GEMM});
+}
+
 // ---- debug: the sign pattern of the saved pre-activations in original edge order (include/cgat_hip.h) ----
 extern "C" int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cgat_attn_params* p, const float* saved,
                                                 uint8_t* mask, void* stream) {
@@ -821,12 +1056,36 @@ extern "C" int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cga
   return attn_signs_launch(saved, plan->dst_perm, (long)d.E, d.W2, mask, (hipStream_t)stream);
 }
 
-// grad edge_attr's product alone, on caller-supplied ingredients of the rebuilt gZ rows (struct EdgeRC, kernels.h), through
-// the launches attn_backward_impl takes for it: the K-group form at few row tiles, the plain launch otherwise
+// ---- debug: one per-edge product of the tail alone, on caller-supplied ingredients of the rebuilt gZ rows (struct EdgeRC,
+// kernels.h), through the step attn_backward_impl takes for it.  The "layer" is the W_e slice alone: no node columns
+// (C = 0, D = 128), the weight / its gradient [W2, 128], gZ column-blocked as the backward's.
+struct EdgeProductDebug {
+  AttnDims d;
+  cgat_plan plan;    // dst_perm alone is read
+  EdgeRC rc;
+  EdgeTail t;
+};
+static void edge_product_debug(EdgeProductDebug& q, const EdgeRC& rc, const int32_t* perm, int32_t E) {
+  memset(&q, 0, sizeof(q));
+  q.d.E = E; q.d.Ce = 128; q.d.H = rc.H; q.d.Hd = rc.Hd; q.d.D = 128; q.d.HHd = rc.HHd; q.d.W2 = 2 * rc.HHd;
+  q.plan.E = E; q.plan.dst_perm = perm;
+  q.rc = rc;
+  q.t.gZ = {nullptr, 128, (long)E * 128};
+  q.t.rc = &q.rc;
+  q.t.have_Gi = true;
+}
+// grad edge_attr's product: the K-group form at few row tiles, the plain launch otherwise
+static int debug_edge_ge_impl(Ctx& c, const EdgeRC& rc, const float* We, int32_t E, float* out) {
+  EdgeProductDebug q;
+  edge_product_debug(q, rc, nullptr, E);
+  q.t.Wq = c.take<float>(edge_z_wq_floats(q.d.W2));
+  c.seal();
+  q.t.Wcat = We; q.t.g_e = out;
+  CGAT_TRY(tail_edge_ge(c, &q.plan, q.d, q.t, tail_route(c.dry, q.d, q.t)));
+  return check_ws(c, "debug_edge_ge_rebuilt");
+}
 extern "C" size_t cgat_debug_edge_ge_rebuilt_workspace_bytes(int32_t E, int32_t H, int32_t Hd) {
-  const int W2 = 2 * H * Hd;
-  const int S = edge_ge_ksplit_groups(E, W2);
-  return (edge_z_wq_floats(W2) + 64 + (S > 1 ? (size_t)S * E * 128 : 0)) * sizeof(float);
+  return dry_total([&](Ctx& c) { return debug_edge_ge_impl(c, edge_rc_make(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H, Hd), nullptr, E, nullptr); });
 }
 extern "C" int cgat_debug_edge_ge_rebuilt(const uint32_t* mask, const float* ga, const float* alpha, const float* gS,
                                           const float* wA, const int32_t* dst, const float* We, int32_t H, int32_t Hd,
@@ -835,29 +1094,28 @@ extern "C" int cgat_debug_edge_ge_rebuilt(const uint32_t* mask, const float* ga,
   CGAT_CHECK_ARG(mask && ga && alpha && gS && wA && dst && We && out && ws, "debug_edge_ge_rebuilt: null pointer");
   CGAT_CHECK_ARG(E > 0 && edge_rc_shape(128, H, Hd) && W2 % 256 == 0 && mode_24bit() && !edge_mma_bf16(),
                  "debug_edge_ge_rebuilt: H = %d, Hd = %d in a 24-bit mode with fp32 edge storage", H, Hd);
-  CGAT_CHECK_ARG(ws_bytes >= cgat_debug_edge_ge_rebuilt_workspace_bytes(E, H, Hd) &&
-                 ((((uintptr_t)gS) | ((uintptr_t)wA) | ((uintptr_t)We) | ((uintptr_t)out) | ((uintptr_t)ws)) & 15) == 0,
+  CGAT_CHECK_ARG(ws_bytes >= cgat_debug_edge_ge_rebuilt_workspace_bytes(E, H, Hd) && aligned16(gS, wA, We) && aligned16(out, ws),
                  "debug_edge_ge_rebuilt: workspace too small or operands not 16-byte aligned");
-  EdgeRC rc = {};
-  rc.mask = mask; rc.ga = ga; rc.alpha = alpha; rc.gS = gS; rc.wA = wA; rc.dst = dst;
-  rc.H = H; rc.Hd = Hd; rc.HHd = H * Hd; rc.nw = W2 / 32;
-  hipStream_t s = (hipStream_t)stream;
-  float* Wq = (float*)ws;
-  float* slabs = Wq + (edge_z_wq_floats(W2) + 63) / 64 * 64;
-  const int S = edge_ge_ksplit_groups(E, W2);
-  if (S > 1) {
-    CGAT_TRY(edge_ge_ksplit_launch(nullptr, 128, (long)E * 128, We, 128, 1, Wq, W2, slabs, nullptr, E, S, s, &rc));
-    return sum_slabs_launch(slabs, S, (long)E * 128, out, (long)E * 128, s);
-  }
-  return edge_ge_launch(nullptr, 128, (long)E * 128, We, 128, 1, Wq, W2, out, 128, nullptr, E, 0, nullptr, s, nullptr, &rc);
+  const EdgeRC rc = edge_rc_make(mask, ga, alpha, gS, wA, dst, H, Hd);
+  return run_sized("debug_edge_ge_rebuilt", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return debug_edge_ge_impl(c, rc, We, E, out); });
 }
 
-// grad W_e's product alone on caller-supplied ingredients of the rebuilt gZ rows, through edge_gw_launch as
-// attn_backward_impl calls it; force_six: THIS launch keeps the six-pass form whatever the route would be (an argument of
+// grad W_e's product; force_six: THIS launch keeps the six-pass form whatever the route would be (an argument of
 // the launch, no shared state); cgat_debug_edge_gw_force_six: the one process-wide switch (edgebwd.hip)
 extern "C" int32_t cgat_debug_edge_gw_force_six(int32_t on) { return edge_gw_force_six(on != 0) ? 1 : 0; }
+static int debug_edge_gw_impl(Ctx& c, const EdgeRC& rc, const float* e, const int32_t* perm, int32_t E, bool force_six,
+                              float* out) {
+  EdgeProductDebug q;
+  edge_product_debug(q, rc, perm, E);
+  q.t.gw_ws = c.take<float>(edge_gw_ws_floats(E, q.d.W2));
+  c.seal();
+  q.t.e = e; q.t.gWcat = out; q.t.gw_force_six = force_six;
+  CGAT_TRY(tail_edge_gw(c, &q.plan, q.d, q.t, tail_route(c.dry, q.d, q.t)));
+  return check_ws(c, "debug_edge_gw_rebuilt");
+}
 extern "C" size_t cgat_debug_edge_gw_rebuilt_workspace_bytes(int32_t E, int32_t H, int32_t Hd) {
-  return (edge_gw_ws_floats(E, 2 * H * Hd) + 64) * sizeof(float);
+  return dry_total([&](Ctx& c) { return debug_edge_gw_impl(c, edge_rc_make(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H, Hd), nullptr, nullptr, E, false, nullptr); });
 }
 extern "C" int cgat_debug_edge_gw_rebuilt(const uint32_t* mask, const float* ga, const float* alpha, const float* gS,
                                           const float* wA, const float* e, const int32_t* perm, const int32_t* dst,
@@ -870,26 +1128,12 @@ extern "C" int cgat_debug_edge_gw_rebuilt(const uint32_t* mask, const float* ga,
     return CGAT_ERR_UNSUPPORTED;
   }
   CGAT_CHECK_ARG(E > 0 && edge_rc_shape(128, H, Hd) && W2 % 256 == 0, "debug_edge_gw_rebuilt: H = %d, Hd = %d", H, Hd);
-  CGAT_CHECK_ARG(ws_bytes >= cgat_debug_edge_gw_rebuilt_workspace_bytes(E, H, Hd) &&
-                 ((((uintptr_t)gS) | ((uintptr_t)wA) | ((uintptr_t)e) | ((uintptr_t)out) | ((uintptr_t)ws)) & 15) == 0,
+  CGAT_CHECK_ARG(ws_bytes >= cgat_debug_edge_gw_rebuilt_workspace_bytes(E, H, Hd) && aligned16(gS, wA, e) && aligned16(out, ws),
                  "debug_edge_gw_rebuilt: workspace too small or operands not 16-byte aligned");
-  EdgeRC rc = {};
-  rc.mask = mask; rc.ga = ga; rc.alpha = alpha; rc.gS = gS; rc.wA = wA; rc.dst = dst;
-  rc.H = H; rc.Hd = Hd; rc.HHd = H * Hd; rc.nw = W2 / 32;
+  const EdgeRC rc = edge_rc_make(mask, ga, alpha, gS, wA, dst, H, Hd);
   if (took_bitplane) *took_bitplane = edge_gw_takes_bitplane(&rc, W2, perm, force_six != 0) ? 1 : 0;
-  return edge_gw_launch(nullptr, 128, (long)E * 128, e, 128, perm, E, W2, (float*)ws, out, 128, (hipStream_t)stream, nullptr,
-                        nullptr, &rc, force_six != 0);
-}
-
-extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
-                                             const float* edge_attr, const float* saved, const float* g_aggr,
-                                             float* g_x, float* g_edge_attr, const cgat_attn_grads* g, void* ws,
-                                             size_t ws_bytes, void* stream) {
-  CGAT_TRY(attn_check(plan, p));
-  CGAT_CHECK_ARG(g, "nodes_attention_backward: null grads");
-  return run_sized("nodes_attention_backward", ws, ws_bytes, stream, [&](Ctx& c) {
-    return attn_backward_impl(c, plan, p, x, edge_attr, saved, g_aggr, g_x, g_edge_attr, g);
-  });
+  return run_sized("debug_edge_gw_rebuilt", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return debug_edge_gw_impl(c, rc, e, perm, E, force_six != 0, out); });
 }
 
 // =======================================================================================

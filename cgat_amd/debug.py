@@ -89,6 +89,24 @@ def note_sorted_hidden(weights, plan, hidden):
         note(w, m[:, k * share:(k + 1) * share])
 
 
+# bit i of cgat_debug_nodes_attention_route's mask (include/cgat_hip.h; the route structs of csrc/layers.hip)
+ROUTE_BITS = {
+    "forward": ("fused_infer", "zx", "fused_z", "z_bf16", "proj_fast", "out_fast", "out_one"),
+    "backward": ("rc", "vec", "have_scales", "z_bf16", "z_bf16_six", "out_fast", "out_heads_one", "node_ksplit",
+                 "node_small_rows", "node_launches", "node_gemm", "node_scales", "ge_ksplit", "ge_launch", "ge_gemm",
+                 "gw_launch", "gw_gemm"),
+}
+
+
+def nodes_attention_route(N, E, C_, Ce, H, Hd, backward=False):
+    """The names of the routes the scalar-attention layer takes at these shapes in the current arithmetic and
+    edge-storage modes, for 16-byte aligned operands (host only, no GPU needed)."""
+    plan = _lib.Plan(N, E, None, None, None, None, None, None)
+    p = _lib.AttnParams(C_, Ce, H, Hd, *([None] * 8))
+    mask = lib.cgat_debug_nodes_attention_route(C.byref(plan), C.byref(p), 1 if backward else 0)
+    return {n for i, n in enumerate(ROUTE_BITS["backward" if backward else "forward"]) if mask >> i & 1}
+
+
 def edge_ge_rebuilt(mask, ga, alpha, gS, wA, dst, We, H, Hd):
     """grad edge_attr's product alone on caller-supplied ingredients of the rebuilt rows (cgat_debug_edge_ge_rebuilt,
     include/cgat_hip.h): mask int32 [E, 2 H Hd / 32] bit words, ga / alpha [E, H], gS [N, H Hd], wA [H Hd], dst int32 [E],

@@ -180,6 +180,17 @@ int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn_params* p,
                                const float* edge_attr /* [E,Ce], original edge order */, float* aggr /* out [N,C] */,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* Debug (tests only): the routes cgat_nodes_attention_forward (backward == 0) or cgat_nodes_attention_backward
+ * (backward != 0) takes for this layer in the current arithmetic and edge-storage modes, for 16-byte aligned operands --
+ * host only, a predicate of the shapes like cgat_nodes_attention_infer_fused.  One bit per route, from bit 0:
+ *   forward:  fused_infer (what cgat_nodes_attention_infer would take; the others describe the training forward),
+ *             zx, fused_z, z_bf16, proj_fast, out_fast, out_one
+ *   backward: rc, vec, have_scales, z_bf16, z_bf16_six, out_fast, out_heads_one,
+ *             node_ksplit, node_small_rows, node_launches, node_gemm (exactly one), node_scales,
+ *             ge_ksplit, ge_launch, ge_gemm (exactly one), gw_launch, gw_gemm (exactly one)
+ * named as the route structs of csrc/layers.hip, which say what each stands for.  0 for a layer attn_check refuses. */
+uint32_t cgat_debug_nodes_attention_route(const cgat_plan* plan, const cgat_attn_params* p, int32_t backward);
+
 /* Debug / parity instrumentation (tests only, not on the hot path): the LeakyReLU derivative pattern the backward of
  * cgat_nodes_attention_forward will use -- mask[e, c] = (Z[slot(e), c] > 0) for the pre-activations of MH_A (columns
  * [0, H*Hd)) and MH_M ([H*Hd, 2*H*Hd)) of CGAT/CGAT.py:96,105-108, in ORIGINAL edge order.  LeakyReLU's derivative

@@ -264,6 +264,39 @@ def test_nodes_layer_vs_oracle_above_small_row_limit():
                          lambda: O.GATConvNodes(128, 128, 128, 3, concat=True), inputs, call)
 
 
+def _runnable_route_rows():
+    """The rows of test_attn_workspace.ROUTES that run here: fp32 edge storage, the default mode and f32, at the two
+    batches P.synthetic_batch makes (25 / 192 crystals of 12 atoms: 300 atoms, and 2 304 -- the smallest whole batch
+    past the small-row programs' 2 048 rows)."""
+    from test_attn_workspace import ABOVE, BENCH, ROUTES, SMALL
+    return [r[:4] for r in ROUTES if r[0] in ("f16x3c", "f32") and r[1] == "f32" and r[2] in (SMALL, ABOVE) and r[3] == BENCH]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,storage,batch,layer", _runnable_route_rows(),
+                         ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
+def test_nodes_layer_vs_oracle_on_the_named_route(mode, storage, batch, layer):
+    """One layer forward + every gradient against the oracle on each route of the table in tests/test_attn_workspace.py
+    that can run, and the route itself: cgat_debug_nodes_attention_route must name what the table says for this shape."""
+    import cgat_amd as P
+    from cgat_amd import ops
+    from oracle import cgat_oracle as O
+    from test_attn_workspace import _modes, route_row
+    b, _ = P.synthetic_batch(batch[0] // 12, 12, 12, seed=5)
+    g = torch.Generator().manual_seed(6)
+    N, E = b.num_nodes, b.edge_index.shape[1]
+    assert (N, E) == batch and layer == (128, 128, 3, 256)
+    inputs = {"x": torch.randn(N, 128, generator=g), "edge_index": b.edge_index,
+              "edge_attr": torch.randn(E, 128, generator=g), "x_0": torch.randn(N, 128, generator=g)}
+    call = lambda m, i: m(i["x"], i["edge_index"], i["edge_attr"], i["x_0"])
+    fwd, bwd = route_row(mode, storage, batch, layer)
+    with _modes(mode, storage):
+        assert P.debug.nodes_attention_route(N, E, *layer, backward=False) == fwd
+        assert P.debug.nodes_attention_route(N, E, *layer, backward=True) == bwd
+        _compare_with_oracle(lambda: P.GATConvNodes(128, 128, 128, 3, concat=True),
+                             lambda: O.GATConvNodes(128, 128, 128, 3, concat=True), inputs, call)
+
+
 @pytest.mark.gpu
 def test_vector_attention_layer_vs_oracle_random_init():
     """vector_attention=True (the reference harness' shipped default) at the BASELINE widths: the
