@@ -906,12 +906,12 @@ int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_
     if (out_contig) CGAT_TRY(absmax_rows128_launch(We, s_col, W2, wmax, stream));
     else
       for (int j = 0; j < ncb; ++j) CGAT_TRY(absmax_rows128_launch(We + 128 * j, s_out, 128, wmax, stream));
-    CGAT_TRY(prepare_T_f16_scaled_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, wmax, stream, /*alternate=*/1));
+    CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream, wmax));
   } else if (bp) {
     CGAT_TRY(prepare_T_bf16_attn_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, rcv.wA, rcv.H, rcv.Hd,
                                         const_cast<float*>(rcv.cs), stream));
   } else {
-    CGAT_TRY(prepare_T_bf16_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
+    CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
   }
   CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);   // the per-edge launch / node-side and dense-layer uses
   const int grid = cdiv(E, 256);
@@ -961,7 +961,7 @@ int edge_ge_ksplit_launch(const float* gZ, long ldg, long gzb, const float* We, 
     CGAT_TRY(prepare_T_bf16_attn_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, rcv.wA, rcv.H, rcv.Hd,
                                         const_cast<float*>(rcv.cs), stream));
   else
-    CGAT_TRY(prepare_T_bf16_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
+    CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
   CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);
   const HeadBatch hb = {(long)ncb_g * gzb, (long)ncb_g * 6144, 0, (long)E * 128, 0, 0, (long)ncb_g * 4};
   if (bp)
@@ -979,7 +979,7 @@ int edge_ge_ksplit_launch(const float* gZ, long ldg, long gzb, const float* We, 
 }
 
 // out[t, :] (+)= sum over the ncb 128-column blocks of x[t, :] times an ALREADY prepared six-pass image (block a at
-// Wq + a * 24576 floats, odd blocks negated: prepare_T_bf16_launch / _heads_launch with alternate = 1) -- the per-node
+// Wq + a * 24576 floats, odd blocks negated: prepare_T_planes_launch with alternate = 1) -- the per-node
 // second layer of the message network, whose H per-head weights are not one affine operand (layers.hip)
 int edge_ge_prepared_launch(const float* x, long ldx, const void* Wq, int ncb, float* out, long ldo, int rows,
                             int accumulate, hipStream_t stream) {
@@ -995,7 +995,7 @@ int edge_ge_prepared_launch(const float* x, long ldx, const void* Wq, int ncb, f
 
 // `heads` products y_h = x_h W_h^T + b_h (x_h = x + h * s_x: W2 columns of a wider matrix; W_h = W + h * s_w: [128, W2]
 // row-major with leading dimension W2, contiguous; y_h = y + h * s_y) in three launches instead of 4-5 per head: the
-// heads' weight maxima and fp16 planes through the batched preparation of the contraction kernels (bilinear.hip), then
+// heads' weight maxima and fp16 planes through the batched preparation of the contraction kernels (opimage.hip), then
 // ONE launch of the kernel above with grid.y = head.  f16x3 mode with max |x| known (amax), heads <= TPREP_MAX.
 // ws: heads * edge_ge_heads_image_floats(W2) + bilinear_prepare_T_batch_ws_floats(heads) floats.
 // (the six-pass image is the larger one: three bf16 planes per 128 x 128 block)
@@ -1017,7 +1017,7 @@ int edge_ge_heads_launch(int heads, const float* x, long ldx, long s_x, const fl
   const EdgeRC none = {};
   if (!mode_f16()) {
     // operand (a = column block, b = column in block, c = output k) = W_h[c * W2 + 128 a + b], as edge_ge_launch's
-    CGAT_TRY(prepare_T_bf16_heads_launch(W, ws, ncb, 128, 1, W2, /*alternate=*/1, heads, s_w, (long)img, stream));
+    CGAT_TRY(prepare_T_planes_launch(W, ws, ncb, 128, 1, W2, /*alternate=*/1, stream, nullptr, heads, s_w, (long)img));
     CGAT_PROF("rows_ge", stream);
     hipLaunchKernelGGL((edge_ge_kernel<6, false>), dim3(cdiv(E, 256), heads), dim3(512), 0, stream, x, ldx, 128l,
                        (const uint4*)ws, ncb, y, ldy, (const int*)nullptr, E, 0, bias, (const float*)nullptr, none, hb);

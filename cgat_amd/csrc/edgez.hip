@@ -1066,7 +1066,7 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
                  "edge_z: bf16 storage is the per-edge launch of the six-pass form only");
   // operand (a = column block, b = k, c = column in block) = We[(128 a + c) * ldw + b]
   if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(We, Wq, ncb, 128 * ldw, 1, ldw, stream));
-  else CGAT_TRY(prepare_T_bf16_launch(We, Wq, ncb, 128 * ldw, 1, ldw, 0, stream));
+  else CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * ldw, 1, ldw, 0, stream));
   CGAT_PROF(Pj ? "edge_z" : "edge_proj", stream);   // the per-edge launch / the per-node projections
   // the six-pass per-edge launch on 256-row workgroups (edge_z6w_kernel: same arithmetic, bit-identical results)
   // (below 128 of its 256-row tiles -- the harness' shipped batch: 60 workgroups walking 12 blocks, 119 us -- the 128-row
@@ -1142,7 +1142,7 @@ int edge_logits_launch(const float* e, long lde, const int* perm, const float* W
   CGAT_CHECK_ARG(W2 == 2 * H * Hd && Hd % 128 == 0 && H * Hd <= 2048 && (lde % 4) == 0 && wA && a_out && perm &&
                  ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)wA)) & 15) == 0,
                  "edge_logits: needs Hd %% 128 == 0, H * Hd <= 2048, 16-byte aligned rows and fc_out_A's weight");
-  CGAT_TRY(prepare_T_bf16_launch(We, Wq, W2 / 128, 128 * ldw, 1, ldw, 0, stream));   // (the whole W2 image: edge_msg_wsum's too)
+  CGAT_TRY(prepare_T_planes_launch(We, Wq, W2 / 128, 128 * ldw, 1, ldw, 0, stream));   // (the whole W2 image: edge_msg_wsum's too)
   const int G = infer_few_rows(E) ? z_groups(cdiv(E, 256), ncb, Hd / 128) : 1;       // groups of whole heads
   CGAT_PROF("edge_logits", stream);
   hipLaunchKernelGGL((edge_z6w_kernel<false, 1>), dim3(cdiv(E, 256), G), dim3(512), 0, stream, e, lde, perm,
@@ -1201,7 +1201,7 @@ int linear128_launch(const float* in, long ldi, const float* W, long so, long sk
   // prepare_T_bf16_batch_launch), n_out == 128 only
   if (prepared && n_out == 128) ws = const_cast<void*>(prepared);
   else if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(W, ws, ncb, 128 * so, sk, so, stream));
-  else CGAT_TRY(prepare_T_bf16_launch(W, ws, ncb, 128 * so, sk, so, 0, stream));
+  else CGAT_TRY(prepare_T_planes_launch(W, ws, ncb, 128 * so, sk, so, 0, stream));
   CGAT_PROF("linear128", stream);
   const int grid = cdiv(rows, 128);
   // (column blocks over grid.y when the row tiles leave CUs idle: edge_z_launch above)
@@ -1236,7 +1236,7 @@ int linear128_heads_launch(int heads, const float* in, long ldi, long s_in, cons
   const int ncb = n_out / 128;
   const long img = (long)linear128_heads_image_floats(n_out);
   if (!mode_f16()) {     // the 24-bit modes (round 6): one image launch for all heads, one six-pass product launch
-    CGAT_TRY(prepare_T_bf16_heads_launch(W, ws, ncb, 128 * so, sk, so, 0, heads, s_w, img, stream));
+    CGAT_TRY(prepare_T_planes_launch(W, ws, ncb, 128 * so, sk, so, 0, stream, nullptr, heads, s_w, img));
     CGAT_PROF("linear128", stream);
     const HeadBatch hb6 = {s_in, img / 4, s_bias, s_out, s_dact};
     hipLaunchKernelGGL((edge_z_kernel<6, false>), dim3(cdiv(rows, 128), heads), dim3(256), 0, stream, in, ldi,
@@ -1246,7 +1246,7 @@ int linear128_heads_launch(int heads, const float* in, long ldi, long s_in, cons
     CGAT_LAUNCH_CHECK();
     return CGAT_OK;
   }
-  CGAT_TRY(prepare_W_f16_heads_launch(W, ws, ncb, 128 * so, sk, so, heads, s_w, img, stream));
+  CGAT_TRY(prepare_W_f16_launch(W, ws, ncb, 128 * so, sk, so, stream, heads, s_w, img));
   CGAT_PROF("linear128", stream);
   const HeadBatch hb = {s_in, img / 4, s_bias, s_out, s_dact};
   hipLaunchKernelGGL((edge_z_kernel<2, false>), dim3(cdiv(rows, 128), heads), dim3(256), 0, stream, in, ldi,

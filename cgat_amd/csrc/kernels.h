@@ -72,10 +72,9 @@ bool rowprog_gemm_ok(const GemmParams& p);    // plain strided product of at mos
 int rowprog_gemm(const GemmParams& p, hipStream_t s);
 int rowprog_launch(const cgat_rowprog_op* ops, int n_ops, uint32_t* sync_words, hipStream_t s);
 
-// ---- bilinear (hypernetwork) contractions, bilinear.hip ----
-// out[n,c] = init[n,c] + sum_{a<NA,b<NB} p[n,a] q[n,b] T3[a,b,c], with T = bilinear_prepare_T(T3 source):
+// ---- the hypernetwork contractions, bilinear.hip ----
+// out[n,c] = init[n,c] + sum_{a<NA,b<NB} p[n,a] q[n,b] T3[a,b,c], with T = bilinear_prepare_T(T3 source) (opimage.hip):
 // a permuted copy whose columns are interleaved for the MFMA kernel when NB == NC == 128.
-bool bilinear_T_interleaved(int NB, int NC);
 // The arithmetic mode of the matrix-core kernels (values: the C ABI's cgat_set/get_bilinear_mode).
 //   F32     f32-input MFMA (exact fp32)
 //   F16X3   two fp16 planes per operand, three passes (22-bit operands, scaled per row / per tensor)
@@ -98,30 +97,18 @@ inline bool mode_24bit() { const int m = bilinear_mode(); return m == MODE_F16X3
 // T operands as fp16-plane images (prepared and differentiated in batches): f16x3 and f16x3c
 inline bool mode_f16_T() { const int m = bilinear_mode(); return m == MODE_F16X3 || m == MODE_F16X3C; }
 void bilinear_set_mode(int m);
-size_t bilinear_T_floats(int NA, int NB, int NC);  // workspace floats of the prepared T
-size_t bilinear_T_floats_max(int NA, int NB, int NC);   // ... in whichever arithmetic mode needs most (size queries)
-// several tensors in two launches (f16x3 mode at width 128; CGAT_ERR_UNSUPPORTED otherwise -> prepare one by one)
-#define TPREP_MAX 8
-struct TPrepBatch {
-  int n;
-  const float* src[TPREP_MAX];
-  void* dst[TPREP_MAX];
-};
-size_t bilinear_prepare_T_batch_ws_floats(int n);
-int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, int n0, int n1, int n2, int perm0,
-                             int perm1, int perm2, float* part, hipStream_t stream, int alternate = 1);
-int bilinear_prepare_T(const float* src, float* dst, int n0, int n1, int n2, int perm0, int perm1, int perm2,
-                       hipStream_t stream);
 size_t bilinear_rows_ws_bytes(int nrows, int NA, int NB, int NC);
 int bilinear_rows_launch(const float* p, long ldp, const float* q, long ldq, const float* T, const float* init,
                          long ldi, float* out, long ldo, int nrows, int NA, int NB, int NC, void* ws, size_t ws_bytes,
                          hipStream_t stream, float* ln_out = nullptr, float ln_eps = 0.f);   // ln_out: tanh(LayerNorm(out))
-// fused pair (bilinear.hip, bilinear_rows128_dual_kernel): T = bilinear_prepare_T of the [128,128,128] operand
+// fused pair (bilinear_rows128_dual_kernel): T = bilinear_prepare_T of the [128,128,128] operand
 bool bilinear_dual_fast(int NA, int NB, int NC);
 size_t bilinear_dual_ws_bytes(int nrows);
 int bilinear_dual_launch(const float* p, long ldp, const float* q, long ldq, const float* zz, long ldz, const float* T,
                          const float* init1, long ldi1, float* out1, long ldo1, const float* init2, long ldi2,
                          float* out2, long ldo2, int nrows, void* ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- the contractions' weight gradient, bilwgrad.hip ----
 // out[(a*NB+b)*NC + c] = sum_n p[n,a] q[n,b] r[n,c]      (workspace: slabs)
 size_t bilinear_wgrad_ws_bytes(int nrows, int NA, int NB, int NC);
 int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, const float* r, long ldr, float* out,
@@ -137,15 +124,48 @@ int bilinear_wgrad_batch_launch(int n_layers, const float* const* p, long ldp, c
 // stream; CGAT_ERR_UNSUPPORTED when the batched form does not take the operands
 int bilinear_wgrad_batch_prep(int slot, int n_layers, const float* p, long ldp, const float* q, long ldq, const float* r,
                               long ldr, int nrows, int NA, int NB, int NC, void* ws, size_t ws_bytes, hipStream_t stream);
-// three bf16 planes of sgn(a) * src[a*sa + b*sb + c*sc] (a < NA; b, c < 128) in the ring kernels' fragment order
-int prepare_T_bf16_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, int alternate,
-                          hipStream_t stream);
-int prepare_T_bf16_heads_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, int alternate, int heads,
-                                long s_head, long image_floats, hipStream_t stream);
+
+// ---- operand images, opimage.hip ----
+// The B operand of bilinear_rows for a [n0,n1,n2] tensor viewed with permuted indices
+bool bilinear_T_interleaved(int NB, int NC);
+size_t bilinear_T_floats(int NA, int NB, int NC);  // workspace floats of the prepared T
+size_t bilinear_T_floats_max(int NA, int NB, int NC);   // ... in whichever arithmetic mode needs most (size queries)
+// several tensors in two launches (f16x3 mode at width 128; CGAT_ERR_UNSUPPORTED otherwise -> prepare one by one)
+#define TPREP_MAX 8
+struct TPrepBatch {
+  int n;
+  const float* src[TPREP_MAX];
+  void* dst[TPREP_MAX];
+};
+size_t bilinear_prepare_T_batch_ws_floats(int n);
+int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, int n0, int n1, int n2, int perm0,
+                             int perm1, int perm2, float* part, hipStream_t stream, int alternate = 1);
+int bilinear_prepare_T(const float* src, float* dst, int n0, int n1, int n2, int perm0, int perm1, int perm2,
+                       hipStream_t stream);
+// Planes of sgn(a) * src[a*sa + b*sb + c*sc] (a < NA; b, c < 128) in the ring kernels' fragment order: three bf16 planes,
+// or with tmax (device memory, tmax[0] = max |src|) the two fp16 planes of 2^k src.  heads > 1: head h of a multi-head
+// layer reads src + h * s_head and writes (float*)dst + h * image_floats, all in one launch.
+int prepare_T_planes_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, int alternate,
+                            hipStream_t stream, const float* tmax = nullptr, int heads = 1, long s_head = 0,
+                            long image_floats = 0);
 // the alternate = 1 image whose first H * Hd / 128 blocks hold wA[b] * src[b][c], and cs[h][c] = the signed column sums
 // of head h's scaled rows (the bit-plane form of edge_ge_kernel, edgebwd.hip); one launch
 int prepare_T_bf16_attn_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, const float* wA, int H,
                                int Hd, float* cs, hipStream_t stream);
+int absmax_launch(const float* src, long n, float* out, hipStream_t stream);   // zeroes out[0] first
+int absmax_rows128_launch(const float* t, long ld, int rows, float* out, hipStream_t stream);  // folds into out[0]
+// ... on `wgs` workgroups, operands unchecked (t 16-byte aligned, ld % 4 == 0, rows > 0)
+int absmax_rows128_wgs_launch(const float* t, long ld, int rows, float* out, int wgs, hipStream_t stream);
+// fp16 form for weight operands: planes of 2^k(a) W[a], max |W[a]| in ((float*)dst)[NA * 16384 + a].  heads > 1: that
+// many weights of NA blocks each in ONE launch, head h reads src + h * s_head and writes the image (NA planes blocks,
+// then NA maxima) at (float*)dst + h * image_floats
+int prepare_W_f16_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, hipStream_t stream, int heads = 1,
+                         long s_head = 0, long image_floats = 0);
+// dst[(a*d1 + b)*d2 + c] = src[...] under an index permutation of a [n0,n1,n2] tensor
+int permute3_launch(const float* src, float* dst, int n0, int n1, int n2, int perm0, int perm1, int perm2,
+                    int interleave, hipStream_t stream);
+// (the batched weight images of the dense layers: below, beside WPrepBatch)
+
 // ---- fused edge pre-activations + attention logits, edgez.hip ----
 bool edge_z_fast(int Ce, int W2, int H, int Hd, long lde, long ld_add, long ldz, const void* e, const void* Pi,
                  const void* Pj, const void* Z, const void* wA);
@@ -164,14 +184,6 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
                   int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream,
                   int act = CGAT_ACT_NONE, float* omax = nullptr, int z_bf16 = 0,   // z_bf16: as edge_zx_launch
                   int n_add_rows = 0);   // rows of Pi / Pj (0 = unknown: the f16x3c kernel addresses them by 32-bit offsets)
-int absmax_launch(const float* src, long n, float* out, hipStream_t stream);   // zeroes out[0] first
-int absmax_rows128_launch(const float* t, long ld, int rows, float* out, hipStream_t stream);  // folds into out[0]
-// fp16 form for weight operands: planes of 2^k(a) W[a], max |W[a]| in ((float*)dst)[NA * 16384 + a]
-int prepare_W_f16_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, hipStream_t stream);
-// the same for `heads` weights of NA blocks each in ONE launch: head h reads src + h * s_head and writes the image
-// (NA planes blocks, then NA maxima) at (float*)dst + h * image_floats
-int prepare_W_f16_heads_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, int heads, long s_head,
-                               long image_floats, hipStream_t stream);
 // Per-head offsets of a launch whose grid.y runs over the heads of a multi-head second layer (elements of each operand;
 // w in 16-byte pieces): all zero = the single-operand launch
 struct HeadBatch {
@@ -221,8 +233,6 @@ int prepare_W_f16_batch_launch(const WPrepBatch& b, float* dst, hipStream_t stre
 int prepare_T_bf16_batch_launch(const WPrepBatch& b, float* dst, hipStream_t stream);
 int prepare_T_bf16_rows_launch(const float* rows, long ld, const int* gather, int nrows, void* dst, int NA,
                                hipStream_t stream, const float* emax = nullptr);   // emax: fp16 form scaled by max |rows|
-int prepare_T_f16_scaled_launch(const float* src, void* dst, int NA, long sa, long sb, long sc, const float* tmax,
-                                hipStream_t stream, int alternate = 0);
 // dense layer at width 128 on the split-bf16 kernel: out = act(in W^T + bias) (+ out),  W(o, k) = W[o*so + k*sk]
 bool linear128_fast(int K, int N, long ldi, long ldo, const void* in, const void* out);
 size_t linear128_ws_bytes(int n_out = 128);
@@ -326,9 +336,6 @@ int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_
 // Gj[n, :] = sum over the edges leaving n of the rebuilt gZ rows (src_rowptr / src_pos: slots grouped by source)
 int edge_gj_launch(const EdgeRC& rc, const int* src_rowptr, const int* src_pos, int N, int W2, float* Gj, long ldo,
                    hipStream_t stream, float* gjmax = nullptr);   // gjmax: max |Gj| folded in (zeroed by the caller)
-// dst[(a*d1 + b)*d2 + c] = src[...] under an index permutation of a [n0,n1,n2] tensor
-int permute3_launch(const float* src, float* dst, int n0, int n1, int n2, int perm0, int perm1, int perm2,
-                    int interleave, hipStream_t stream);
 
 // ---- width-128 weight gradients over rows, rowsdw.hip: out_k[o][i] = sum_n G[n,o] X_k[n,i], bsum[o] = sum_n G[n,o] ----
 bool rows_dw128_fast(const float* G, long ldg, const float* X1, long ldx1, const float* X2, long ldx2);

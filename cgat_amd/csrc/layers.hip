@@ -468,8 +468,8 @@ static int attn_fwd_out(Ctx& c, const AttnFwd& f) {
   if (attn_out_one_shape(d)) c.need((size_t)d.H * ncb_h * 24576 * sizeof(float));
   if (f.r.out_one) {
     // operand (a = block of head h, b = column in block, c = output) = M_out_w[h * C * Hd + c * Hd + 128 a + b]
-    CGAT_TRY(prepare_T_bf16_heads_launch(p->M_out_w, c.scratch, ncb_h, 128, 1, d.Hd, /*alternate=*/1, d.H, (long)d.C * d.Hd,
-                                         (long)ncb_h * 24576, c.s));
+    CGAT_TRY(prepare_T_planes_launch(p->M_out_w, c.scratch, ncb_h, 128, 1, d.Hd, /*alternate=*/1, c.s, nullptr, d.H,
+                                     (long)d.C * d.Hd, (long)ncb_h * 24576));
     CGAT_TRY(edge_ge_prepared_launch(sv.S, d.HHd, c.scratch, d.H * ncb_h, f.aggr, d.C, d.N, 0, c.s));
   } else if (f.r.out_fast) {
     for (int h = 0; h < d.H; ++h)

@@ -114,7 +114,7 @@ __device__ __forceinline__ i32x8 frag6_as8(const frag6& f) {   // the builtin ta
 // of two pieces carries the scale 1, so the instruction needs no E8M0 scale operands (zero scale arguments select the
 // unscaled v_mfma_f32_16x16x128_f8f6f4: no scale VGPRs).  bf6 spans 0.0625 .. 28: t (a power of two) is exact for every
 // element within 2^-7 of its block's maximum, h keeps three bits within 2^-4 of it.
-// prepared-T image of the contraction kernels in this form (bilinear.hip, prepare_T_f16c_kernel)
+// prepared-T image of the contraction kernels in this form (opimage.hip, prepare_T_f16c_kernel)
 #define F16C_CHUNK16 1600                       // 16-byte pieces per chunk (a, column half, column-block pair): 25 KB
 #define F16C_A_FLOATS (4 * F16C_CHUNK16 * 4)    // floats per `a` (four chunks)
 // the three 6-bit images of 32 scaled values (the lane's K elements in ANY order: both operands of a product use this

@@ -1,4 +1,4 @@
-// Descriptors shared by the batched weight-gradient contractions (bilinear.hip: f16x3 form; wgradc.hip: f16x3c form).
+// Descriptors shared by the batched weight-gradient contractions (bilwgrad.hip: f16x3 form; wgradc.hip: f16x3c form).
 #pragma once
 #include "common.h"
 
@@ -15,7 +15,7 @@ struct WgradPrepDesc {
   const float* r[WGB_MAX];
 };
 
-// mx[4 * (l0 + l) + which] = max |p, q, r of layer l| for l < n (mx zeroed before), wgs workgroups per tensor (bilinear.hip)
+// mx[4 * (l0 + l) + which] = max |p, q, r of layer l| for l < n (mx zeroed before), wgs workgroups per tensor (bilwgrad.hip)
 int absmax_rows_batch_launch(const WgradPrepDesc& d, int l0, int n, long ldp, long ldq, long ldr, int rows, int NA,
                              float* mx, int wgs, hipStream_t stream);
 

@@ -1,7 +1,7 @@
 // Hypernetwork weight gradient  out[l][a,b,c] = sum_n p[l][n,a] q[l][n,b] r[l][n,c]  (the autograd of the predicted
 // Linear(C -> C*C + C) head, reference Hypernetworksmp.py:206-208, 236-240) in the f16x3c arithmetic: 24-bit operands
 // as x = h + l + t (mfma_bf16.h), 3 fp16 passes + 3 six-bit correction passes = 3.75 pass-equivalents, where the
-// bf16 form of the same contraction (bilinear.hip, bilinear_wgrad128_bf16_kernel<6>) pays six.  One launch covers every
+// bf16 form of the same contraction (bilwgrad.hip, bilinear_wgrad128_bf16_kernel<6>) pays six.  One launch covers every
 // predicted layer of a hypernetwork, with no row split when the units fill the chip (round 5).
 //
 // The reduction runs over the ROWS n, and the row operand of the matrix instruction is the product p[n,a] * q[n,b]:
@@ -43,7 +43,7 @@ typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
 #endif
 
 // ------------------------------- operand preparation -------------------------------
-// (the maxima: absmax_rows_batch_launch, bilinear.hip)
+// (the maxima: absmax_rows_batch_launch, bilwgrad.hip)
 
 // One 64-row chunk of one operand of one layer per workgroup (256 threads; blockIdx.z = operand):
 //  pT [128][rows_pad]      = (p * 2^k * sign(n))^T: 2^k from max|p| max|q| (the products must fit fp16), sign(n) = -1 in the
