@@ -185,6 +185,8 @@ PROTOTYPES = {
                                            C.c_size_t, vp]),
     "cgat_edge_hidden_backward": (C.c_int, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32,
                                             vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "cgat_debug_edge_hidden_route": (C.c_uint32, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32]),
     "cgat_linear_backward_dact": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp,
                                             vp, C.c_int64, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_size_t, vp]),
     "cgat_heads_linear_forward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -365,7 +365,8 @@ int layernorm_tanh_fwd_launch(const float* u, float* y, int rows, int W, float e
 int layernorm_tanh_bwd_launch(const float* u, const float* y, const float* gy, float* gu, int rows, int W, float eps,
                               hipStream_t s);
 int act_bwd_launch(const float* y, const float* gy, float* gpre, long n, int act, hipStream_t s);  // in terms of post-activation y
-int act_bwd_leaky_max_launch(const float* y, const float* gy, float* gpre, long n, float* gmax, hipStream_t s, bool* used);
+bool act_bwd_leaky_max_fast(const void* y, const void* gy, const void* gpre, long n);   // the vector form applies
+int act_bwd_leaky_max_launch(const float* y, const float* gy, float* gpre, long n, float* gmax, hipStream_t s);
 int colsum_launch(const float* x, long ldx, int rows, int cols, float* out, float alpha, void* ws, size_t ws_bytes,
                   hipStream_t s);
 size_t colsum_ws_bytes(int rows, int cols);

@@ -872,23 +872,36 @@ static AttnDims hidden_dims(const cgat_plan* plan, int C, int Ce, int W2) {
   return d;
 }
 
+// ---- routes of the two passes: decided once from the dims, the arithmetic mode and the alignment of the operands, by
+// the carve functions that the real pass, its dry pass and cgat_debug_edge_hidden_route all go through ----
+struct HiddenFwd {
+  float *Pi, *Pj, *Wq;
+  bool fast;          // the node projections and the per-edge phase on the split per-edge kernel (else: the GEMM engine)
+};
+static HiddenFwd hidden_fwd_carve(Ctx& c, const AttnDims& d, const float* b_in, const float* x, const float* e,
+                                  const float* Hout) {
+  HiddenFwd f = {};
+  f.Pi = c.take<float>((size_t)d.N * d.W2);
+  f.Pj = c.take<float>((size_t)d.N * d.W2);
+  f.Wq = c.take<float>(edge_z_wq_floats(d.W2));
+  c.seal();
+  f.fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 && d.C == 128 &&
+           edge_z_fast(d.Ce, d.W2, 1, d.W2 / 2, d.Ce, d.W2, d.W2, e, f.Pi, f.Pj, Hout, b_in) && aligned16(x);
+  return f;
+}
+
 static int edge_hidden_forward_impl(Ctx& c, const cgat_plan* plan, const AttnDims& d, const float* w_in,
                                     const float* b_in, const float* x, const float* e, float* Hout, float* hmax) {
-  float* Pi = c.take<float>((size_t)d.N * d.W2);
-  float* Pj = c.take<float>((size_t)d.N * d.W2);
-  float* Wq = c.take<float>(edge_z_wq_floats(d.W2));
-  c.seal();
-  const bool fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 && d.C == 128 &&
-                    edge_z_fast(d.Ce, d.W2, 1, d.W2 / 2, d.Ce, d.W2, d.W2, e, Pi, Pj, Hout, b_in) && aligned16(x);
-  CGAT_TRY(node_projections(c, d, fast, true, x, w_in, b_in, NodeProj{Pi, Pj, Wq}));
-  if (fast) {
-    RUN(edge_z_launch(e, d.Ce, plan->dst_perm, w_in + d.C, d.D, Wq, d.W2, Pi, plan->dst_sorted, Pj, plan->src_sorted, d.W2,
-                      Hout, d.W2, d.E, nullptr, nullptr, 1, d.W2 / 2, nullptr, c.s, CGAT_ACT_LEAKY, hmax));
+  const HiddenFwd f = hidden_fwd_carve(c, d, b_in, x, e, Hout);
+  CGAT_TRY(node_projections(c, d, f.fast, true, x, w_in, b_in, NodeProj{f.Pi, f.Pj, f.Wq}));
+  if (f.fast) {
+    RUN(edge_z_launch(e, d.Ce, plan->dst_perm, w_in + d.C, d.D, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj, plan->src_sorted,
+                      d.W2, Hout, d.W2, d.E, nullptr, nullptr, 1, d.W2 / 2, nullptr, c.s, CGAT_ACT_LEAKY, hmax));
   } else {
     GemmParams g = gemm_params(d.E, d.W2, d.Ce, e, d.Ce, w_in + d.C, d.D, Hout, d.W2);
     g.a_rgather = plan->dst_perm;
-    g.add1 = Pi; g.add1_idx = plan->dst_sorted;
-    g.add2 = Pj; g.add2_idx = plan->src_sorted;
+    g.add1 = f.Pi; g.add1_idx = plan->dst_sorted;
+    g.add2 = f.Pj; g.add2_idx = plan->src_sorted;
     g.ld_add = d.W2;
     g.act = CGAT_ACT_LEAKY;
     CGAT_TRY(c.gemm(g));
@@ -897,43 +910,54 @@ static int edge_hidden_forward_impl(Ctx& c, const cgat_plan* plan, const AttnDim
   return check_ws(c, "edge_hidden_forward");
 }
 
-static int edge_hidden_backward_impl(Ctx& c, const cgat_plan* plan, const AttnDims& d, const float* w_in, const float* x,
-                                     const float* e, const float* Hsaved, const float* g_H, float* g_x, float* g_e,
-                                     float* g_w_in, float* g_b_in, int g_is_pre = 0, const float* gpre_absmax = nullptr) {
-  // g_is_pre: g_H already is the gradient of the PRE-activation (cgat_linear_backward_dact folded LeakyReLU' into the
-  // product that made it) and gpre_absmax[0] its maximum: no elementwise pass, no copy -- the tail reads g_H itself
-  float* gZ = g_is_pre ? const_cast<float*>(g_H) : c.take<float>((size_t)d.E * d.W2);
-  EdgeTail t = {};
-  t.gZ = {gZ, d.W2, 128};
+struct HiddenBwd {
+  EdgeTail t;
+  float* gZ;          // the pre-activation gradient the tail reads: a carve-out, or (g_is_pre) g_H itself
+  float* scales;      // f16x3: [0] max |gZ|, [1] max |e|, [2..4] max |Gi|, |Gj|, |x| (set by the tail)
+  // f16x3 mode: the LeakyReLU backward also yields max |gZ| and one pass over edge_attr max |e| -- with them the per-edge
+  // products of the tail (K = W2 -> 128 and K = E) run on two fp16 planes (three passes) instead of the six-pass bf16
+  // form they fell back to without scales: 43 + 22 ms of the harness-default network's 252-ms step
+  bool have_scales;
+};
+// g_is_pre: g_H already is the gradient of the PRE-activation (cgat_linear_backward_dact folded LeakyReLU' into the
+// product that made it) and, if has_absmax, the caller holds its maximum: no elementwise pass, no copy -- the tail reads
+// g_H itself
+static HiddenBwd hidden_bwd_carve(Ctx& c, const AttnDims& d, const float* w_in, const float* x, const float* e,
+                                  const float* Hsaved, const float* g_H, float* g_x, float* g_e, float* g_w_in,
+                                  float* g_b_in, int g_is_pre, bool has_absmax) {
+  HiddenBwd b = {};
+  b.gZ = g_is_pre ? const_cast<float*>(g_H) : c.take<float>((size_t)d.E * d.W2);
+  EdgeTail& t = b.t;
+  t.gZ = {b.gZ, d.W2, 128};
   t.Gi = c.take<float>((size_t)d.N * d.W2);
   t.Gj = c.take<float>((size_t)d.N * d.W2);
   t.Wq = c.take<float>(edge_z_wq_floats(d.W2));
   t.gw_ws = c.take<float>(edge_gw_ws_floats(d.E, d.W2));
-  float* scales = c.take<float>(8);       // f16x3: [0] max |gZ|, [1] max |e|, [2..4] max |Gi|, |Gj|, |x| (set by the tail)
+  b.scales = c.take<float>(8);
   c.seal();
-  // f16x3 mode: the LeakyReLU backward also yields max |gZ| and one pass over edge_attr max |e| -- with them the per-edge
-  // products of the tail (K = W2 -> 128 and K = E) run on two fp16 planes (three passes) instead of the six-pass bf16
-  // form they fell back to without scales: 43 + 22 ms of the harness-default network's 252-ms step
-  bool have_scales = false;
   const bool f16_ok = !c.dry && mode_f16() && d.Ce == 128 && aligned16(e) && d.E > 0;
-  if (g_is_pre) {
-    if (f16_ok && gpre_absmax) {
-      CGAT_TRY(fill_launch(scales, 0.f, 8, c.s));
-      CGAT_TRY(copy2d_launch(gpre_absmax, 1, scales, 1, 1, 1, c.s));   // (a kernel node, like every fill: rowops.hip)
-      have_scales = true;
-    }
-  } else if (f16_ok) {
-    CGAT_TRY(fill_launch(scales, 0.f, 8, c.s));
-    RUN(act_bwd_leaky_max_launch(Hsaved, g_H, gZ, (long)d.E * d.W2, scales, c.s, &have_scales));
-  } else {
-    RUN(act_bwd_launch(Hsaved, g_H, gZ, (long)d.E * d.W2, CGAT_ACT_LEAKY, c.s));
-  }
-  if (have_scales) RUN(absmax_rows128_launch(e, d.Ce, d.E, scales + 1, c.s));
+  b.have_scales = f16_ok && (g_is_pre ? has_absmax : act_bwd_leaky_max_fast(Hsaved, g_H, b.gZ, (long)d.E * d.W2));
   t.Wcat = w_in; t.gWcat = g_w_in; t.gbcat = g_b_in;
-  t.scales = have_scales ? scales : nullptr;
-  t.node_scales = have_scales;
+  t.scales = b.have_scales ? b.scales : nullptr;
+  t.node_scales = b.have_scales;
   t.x = x; t.e = e; t.g_x = g_x; t.g_e = g_e;
-  CGAT_TRY(edge_first_layer_backward_tail(c, plan, d, t));
+  return b;
+}
+
+static int edge_hidden_backward_impl(Ctx& c, const cgat_plan* plan, const AttnDims& d, const float* w_in, const float* x,
+                                     const float* e, const float* Hsaved, const float* g_H, float* g_x, float* g_e,
+                                     float* g_w_in, float* g_b_in, int g_is_pre = 0, const float* gpre_absmax = nullptr) {
+  const HiddenBwd b = hidden_bwd_carve(c, d, w_in, x, e, Hsaved, g_H, g_x, g_e, g_w_in, g_b_in, g_is_pre,
+                                       gpre_absmax != nullptr);
+  if (b.have_scales) CGAT_TRY(fill_launch(b.scales, 0.f, 8, c.s));
+  if (!g_is_pre && !b.have_scales)
+    RUN(act_bwd_launch(Hsaved, g_H, b.gZ, (long)d.E * d.W2, CGAT_ACT_LEAKY, c.s));
+  else if (!g_is_pre)
+    RUN(act_bwd_leaky_max_launch(Hsaved, g_H, b.gZ, (long)d.E * d.W2, b.scales, c.s));
+  else if (b.have_scales)   // (a kernel node, like every fill: rowops.hip)
+    CGAT_TRY(copy2d_launch(gpre_absmax, 1, b.scales, 1, 1, 1, c.s));
+  if (b.have_scales) RUN(absmax_rows128_launch(e, d.Ce, d.E, b.scales + 1, c.s));
+  CGAT_TRY(edge_first_layer_backward_tail(c, plan, d, b.t));
   return check_ws(c, "edge_hidden_backward");
 }
 
@@ -1041,6 +1065,21 @@ extern "C" uint32_t cgat_debug_nodes_attention_route(const cgat_plan* plan, cons
                      t.node == NODE_KSPLIT, t.node == NODE_SMALL_ROWS, t.node == NODE_LAUNCHES, t.node == NODE_GEMM,
                      t.node_scales, t.ge == PRODUCT_KSPLIT, t.ge == PRODUCT_LAUNCH, t.ge == PRODUCT_GEMM,
                      t.gw == PRODUCT_LAUNCH, t.gw == PRODUCT_GEMM});
+}
+
+extern "C" uint32_t cgat_debug_edge_hidden_route(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, int32_t backward,
+                                                 int32_t g_is_pre, int32_t has_absmax) {
+  if (hidden_check(plan, C, Ce, W2) != CGAT_OK) return 0;
+  const AttnDims d = hidden_dims(plan, C, Ce, W2);
+  // (a non-null aligned base: no carve-out is a null pointer, as none is in a real pass; nothing is dereferenced)
+  Ctx c((void*)256, (size_t)-1 / 2, false, nullptr);
+  if (!backward) return route_bits({hidden_fwd_carve(c, d, nullptr, nullptr, nullptr, nullptr).fast});
+  const HiddenBwd b = hidden_bwd_carve(c, d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       g_is_pre, has_absmax != 0);
+  const TailRoute t = tail_route(false, d, b.t);
+  return route_bits({b.have_scales, t.node == NODE_KSPLIT, t.node == NODE_SMALL_ROWS, t.node == NODE_LAUNCHES,
+                     t.node == NODE_GEMM, t.node_scales, t.ge == PRODUCT_KSPLIT, t.ge == PRODUCT_LAUNCH,
+                     t.ge == PRODUCT_GEMM, t.gw == PRODUCT_LAUNCH, t.gw == PRODUCT_GEMM});
 }
 
 // ---- debug: the sign pattern of the saved pre-activations in original edge order (include/cgat_hip.h) ----

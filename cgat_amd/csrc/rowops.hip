@@ -121,20 +121,19 @@ static inline int grid_for(long n) {
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
 
-// LeakyReLU backward + max |gpre| (gmax zeroed by the caller); falls back to the plain kernel (gmax untouched, returns
-// CGAT_ERR_UNSUPPORTED-free: the caller checks `*used`) when the vector form does not apply
-int act_bwd_leaky_max_launch(const float* y, const float* gy, float* gpre, long n, float* gmax, hipStream_t s, bool* used) {
-  *used = false;
-  if (n <= 0) return CGAT_OK;
-  if ((n % 4) != 0 || ((((uintptr_t)y) | ((uintptr_t)gy) | ((uintptr_t)gpre)) & 15) != 0)
-    return act_bwd_launch(y, gy, gpre, n, CGAT_ACT_LEAKY, s);
+// LeakyReLU backward + max |gpre| (gmax zeroed by the caller): the vector form alone.  act_bwd_leaky_max_fast says whether
+// it applies; where it does not the caller runs act_bwd_launch and has no maximum
+bool act_bwd_leaky_max_fast(const void* y, const void* gy, const void* gpre, long n) {
+  return n > 0 && (n % 4) == 0 && ((((uintptr_t)y) | ((uintptr_t)gy) | ((uintptr_t)gpre)) & 15) == 0;
+}
+int act_bwd_leaky_max_launch(const float* y, const float* gy, float* gpre, long n, float* gmax, hipStream_t s) {
+  CGAT_CHECK_ARG(act_bwd_leaky_max_fast(y, gy, gpre, n), "act_bwd_leaky_max: n = %ld or operands not 16-byte aligned", n);
   const long n4 = n / 4;
   long b = (n4 + 255) / 256;
   const int grid = (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
   hipLaunchKernelGGL(act_bwd_max_kernel, dim3(grid), dim3(256), 0, s, (const float4*)y, (const float4*)gy, (float4*)gpre, n4,
                      gmax);
   CGAT_LAUNCH_CHECK();
-  *used = true;
   return CGAT_OK;
 }
 

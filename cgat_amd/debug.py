@@ -107,6 +107,24 @@ def nodes_attention_route(N, E, C_, Ce, H, Hd, backward=False):
     return {n for i, n in enumerate(ROUTE_BITS["backward" if backward else "forward"]) if mask >> i & 1}
 
 
+# bit i of cgat_debug_edge_hidden_route's mask (include/cgat_hip.h)
+EDGE_HIDDEN_ROUTE_BITS = {
+    "forward": ("fast",),
+    "backward": ("have_scales", "node_ksplit", "node_small_rows", "node_launches", "node_gemm", "node_scales", "ge_ksplit",
+                 "ge_launch", "ge_gemm", "gw_launch", "gw_gemm"),
+}
+
+
+def edge_hidden_route(N, E, C_, Ce, W2, backward=False, g_is_pre=False, has_absmax=False):
+    """The names of the routes cgat_edge_hidden_forward / _backward (the operand-split first layer of the vector-attention
+    variants) take at these shapes in the current arithmetic mode, for 16-byte aligned operands (host only, no GPU
+    needed).  g_is_pre / has_absmax: the backward's arguments of those names."""
+    plan = _lib.Plan(N, E, None, None, None, None, None, None)
+    mask = lib.cgat_debug_edge_hidden_route(C.byref(plan), C_, Ce, W2, 1 if backward else 0, 1 if g_is_pre else 0,
+                                            1 if has_absmax else 0)
+    return {n for i, n in enumerate(EDGE_HIDDEN_ROUTE_BITS["backward" if backward else "forward"]) if mask >> i & 1}
+
+
 def edge_ge_rebuilt(mask, ga, alpha, gS, wA, dst, We, H, Hd):
     """grad edge_attr's product alone on caller-supplied ingredients of the rebuilt rows (cgat_debug_edge_ge_rebuilt,
     include/cgat_hip.h): mask int32 [E, 2 H Hd / 32] bit words, ga / alpha [E, H], gS [N, H Hd], wA [H Hd], dst int32 [E],

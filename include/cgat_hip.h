@@ -245,6 +245,17 @@ int cgat_edge_hidden_backward(const cgat_plan* plan, int32_t C, int32_t Ce, int3
                               const float* gpre_absmax, float* g_x, float* g_edge_attr, float* g_w_in, float* g_b_in,
                               void* ws, size_t ws_bytes, void* stream);
 
+/* Debug (tests only): the routes cgat_edge_hidden_forward (backward == 0) or cgat_edge_hidden_backward (backward != 0;
+ * g_is_pre as passed to it, has_absmax != 0: with a gpre_absmax) takes at these shapes in the current arithmetic mode, for
+ * 16-byte aligned operands -- host only, like cgat_debug_nodes_attention_route.  One bit per route, from bit 0:
+ *   forward:  fast (the node projections and the per-edge phase on the split per-edge kernel; else the GEMM engine)
+ *   backward: have_scales (the fp16 per-tensor scales of the f16x3 mode),
+ *             node_ksplit, node_small_rows, node_launches, node_gemm (exactly one), node_scales,
+ *             ge_ksplit, ge_launch, ge_gemm (exactly one), gw_launch, gw_gemm (exactly one)
+ * named as the route structs of csrc/layers.hip.  0 for arguments the two calls refuse. */
+uint32_t cgat_debug_edge_hidden_route(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, int32_t backward,
+                                      int32_t g_is_pre, int32_t has_absmax);
+
 /* ---- H_Net_0 / H_Net: hypernetwork Pooling_NN -------------------------------------------
  * replaces CGAT/Hypernetworksmp.py:257-313 (HyperFC of n_hyper predicted layers, each with its
  * own FCBlock trunk of n_fc Linear+Tanh and a Linear(W -> W*W+W) head; LayerNorm(no affine,
