@@ -12,7 +12,7 @@ from .nets import CGAtNet, GATConvEdges, GATConvNodes, MHAttention, MultiHeadNet
 from .roost import MessageLayer, Roost, WeightedAttention
 from .graph import GraphBatch, synthetic_batch
 from .collate import PackedDataset
-from .optim import FusedAdamW, FusedLamb, RobustL1, RobustL2, cyclical_lr
+from .optim import FusedAdam, FusedAdamW, FusedLamb, FusedSGD, L1Loss, MSELoss, RobustL1, RobustL2, criterion_with_metrics, cyclical_lr
 from .ops import get_bilinear_mode, set_bilinear_mode, set_validate_indices, set_edge_storage, get_edge_storage
 from .ops import set_fused_inference, get_fused_inference
 from .trainer import DataParallelTrainer, Normalizer
@@ -22,6 +22,7 @@ from . import debug
 
 __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAttention", "H_Net", "H_Net_0",
            "HyperFC", "SimpleNetwork", "ResidualNetwork", "Rezero", "Roost", "MessageLayer", "WeightedAttention",
-           "GraphBatch", "synthetic_batch", "PackedDataset", "FusedAdamW", "FusedLamb", "RobustL1", "RobustL2", "cyclical_lr", "set_bilinear_mode", "get_bilinear_mode",
+           "GraphBatch", "synthetic_batch", "PackedDataset", "FusedAdamW", "FusedLamb", "RobustL1", "RobustL2", "cyclical_lr",
+           "FusedSGD", "FusedAdam", "L1Loss", "MSELoss", "criterion_with_metrics", "set_bilinear_mode", "get_bilinear_mode",
            "set_validate_indices", "DataParallelTrainer", "Normalizer", "set_max_edges_per_pass",
            "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "GraphedStep", "debug"]

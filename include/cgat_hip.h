@@ -104,18 +104,34 @@ size_t cgat_embedding_backward_workspace_bytes(int32_t K, int32_t C);
 int cgat_embedding_backward(const float* g, int64_t ldg, const int64_t* idx, int64_t rows, int32_t K, int32_t C,
                             float* g_table, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- fused optimiser steps and robust losses (after the hot path) ------------
+/* ---- fused optimiser steps and losses (after the hot path) -------------------
  * One launch over all parameter tensors.  `table[n_tensors]` (device) holds the tensors; the chunk list cuts them
  * into pieces of cgat_mt_chunk_elems() elements: chunk c covers table[chunk_tensor[c]] from element chunk_off[c];
  * the chunks of a tensor are consecutive and first_chunk[n_tensors+1] indexes them (LAMB's per-tensor norms).
  *   cgat_adamw_step : torch.optim.AdamW as the reference constructs it (CGAT/lightning_module.py:328-331):
  *                     p *= 1 - lr*wd;  m = lerp(m, g, 1-b1);  v = b2 v + (1-b2) g^2;
  *                     p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+ *   cgat_adam_step  : torch.optim.Adam as the reference constructs it (CGAT/lightning_module.py:325-327), coupled
+ *                     (L2) decay: g' = g + wd*p; moments and bias corrections as cgat_adamw_step, on g'; no p *= ...
+ *   cgat_sgd_step   : torch.optim.SGD(lr, weight_decay, momentum) as at CGAT/lightning_module.py:320-323 (dampening
+ *                     0, no Nesterov): g' = g + wd*p;  buf = momentum*buf + g';  p -= lr*buf.  table[i].m is the
+ *                     momentum buffer (zero-initialised: torch's first-step buf = clone(g') has the same bits),
+ *                     table[i].v is unused and may be null.  momentum == 0: p -= lr*g', no buffer is read or
+ *                     written and m may be null.
  *   cgat_lamb_step  : CGAT/lambs.py:155-181 lamb_kernel (JITLamb.step 226-262): no bias correction, weight norm
  *                     clamped to [0,10], trust ratio |w|/(|s|+eps) (1 when either norm is 0), p -= lr*ratio*s,
  *                     s = m/(sqrt(v)+eps) + wd*p.  ws: 2*n_chunks + n_tensors floats.
  *   cgat_robust_loss: CGAT/utils.py:30-47 RobustL1 (kind 1) / RobustL2 (kind 2): per-row terms and the gradients
- *                     of the terms wrt output and log_std (the caller takes the mean). */
+ *                     of the terms wrt output and log_std (the caller takes the mean).
+ *   cgat_loss_metrics: criterion, its gradients and the step metrics of CGAT/lightning_module.py:240-243 (276-277,
+ *                     297-298) in ONE launch of one 256-thread workgroup (deterministic, no atomics).  `target` is
+ *                     the raw target: t_n = (target - mean)/std and pred = output*std + mean (lines 153, 159).
+ *                     kind 1 / 2: RobustL1 / RobustL2 on (output, log_std, t_n); kind 3: nn.L1Loss |output - t_n|
+ *                     (gradient sign(output - t_n), 0 at equality); kind 4: nn.MSELoss (output - t_n)^2 (lines
+ *                     131-142).  g_output[n] / g_log_std[n]: gradients of the MEAN loss (divided by n); for kinds 3
+ *                     and 4 log_std and g_log_std may be null and are not touched.  out3 = {mean loss,
+ *                     mean |pred - target|, sqrt(mean (pred - target)^2)}, summed in double, rounded to fp32 once.
+ *                     n >= 1. */
 typedef struct cgat_mt_tensor {
   float* p;
   const float* g;
@@ -126,11 +142,17 @@ typedef struct cgat_mt_tensor {
 int32_t cgat_mt_chunk_elems(void);
 int cgat_adamw_step(const cgat_mt_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t n_chunks,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream);
+int cgat_adam_step(const cgat_mt_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t n_chunks,
+                   float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream);
+int cgat_sgd_step(const cgat_mt_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t n_chunks,
+                  float lr, float momentum, float weight_decay, void* stream);
 int cgat_lamb_step(const cgat_mt_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t n_chunks,
                    const int32_t* first_chunk, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
                    float weight_decay, float* ws, void* stream);
 int cgat_robust_loss(const float* output, const float* log_std, const float* target, int32_t n, int32_t kind,
                      float* loss_terms, float* g_output, float* g_log_std, void* stream);
+int cgat_loss_metrics(const float* output, const float* log_std, const float* target, int32_t n, int32_t kind, float mean,
+                      float std, float* g_output, float* g_log_std, float* out3, void* stream);
 
 /* ---- GATConvNodes message + softmax + aggregate (scalar attention) ----------------------
  * replaces CGAT/CGAT.py:319-329: m=cat[x_i,edge_attr,x_j]; alpha=softmax_dst(MH_A(m));
