@@ -15,6 +15,7 @@ from .collate import PackedDataset
 from .optim import FusedAdam, FusedAdamW, FusedLamb, FusedSGD, L1Loss, MSELoss, RobustL1, RobustL2, criterion_with_metrics, cyclical_lr
 from .ops import get_bilinear_mode, set_bilinear_mode, set_validate_indices, set_edge_storage, get_edge_storage
 from .ops import set_fused_inference, get_fused_inference
+from .ops import set_fused_edge_combine, get_fused_edge_combine
 from .trainer import DataParallelTrainer, Normalizer
 from .chunked import set_max_edges_per_pass
 from .capture import GraphedStep
@@ -25,4 +26,5 @@ __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAtt
            "GraphBatch", "synthetic_batch", "PackedDataset", "FusedAdamW", "FusedLamb", "RobustL1", "RobustL2", "cyclical_lr",
            "FusedSGD", "FusedAdam", "L1Loss", "MSELoss", "criterion_with_metrics", "set_bilinear_mode", "get_bilinear_mode",
            "set_validate_indices", "DataParallelTrainer", "Normalizer", "set_max_edges_per_pass",
-           "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "GraphedStep", "debug"]
+           "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "set_fused_edge_combine",
+           "get_fused_edge_combine", "GraphedStep", "debug"]

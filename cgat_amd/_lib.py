@@ -164,6 +164,9 @@ PROTOTYPES = {
                                                       vp, vp, vp, vp, vp]),
     "cgat_segment_attention_pool_backward": (C.c_int, [vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp, vp,
                                                        vp, vp, vp, vp, C.c_int64, vp, vp]),
+    "cgat_edge_head_combine_forward": (C.c_int, [vp, C.c_int32, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp]),
+    "cgat_edge_head_combine_backward": (C.c_int, [vp, C.c_int32, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp,
+                                                  vp]),
     "cgat_mlp_chain_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgat_mlp_chain": (C.c_int, [C.POINTER(ChainDesc), vp, C.c_size_t, vp]),
     "cgat_rowprog_run": (C.c_int, [C.POINTER(RowProg), vp, vp]),

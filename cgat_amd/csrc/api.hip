@@ -351,6 +351,18 @@ extern "C" int cgat_segment_attention_pool_backward(const float* a, int32_t aF, 
                                  (hipStream_t)stream, out_lo);
 }
 
+// ---- head combination of the edge update ----
+extern "C" int cgat_edge_head_combine_forward(const float* sa, int32_t aF, const float* sm, const float* keep,
+                                              const int32_t* perm, int64_t E, int32_t H, int32_t Co, float* out,
+                                              void* stream) {
+  return edge_combine_fwd_launch(sa, aF, sm, keep, perm, E, H, Co, out, (hipStream_t)stream);
+}
+extern "C" int cgat_edge_head_combine_backward(const float* sa, int32_t aF, const float* sm, const float* keep,
+                                               const int32_t* perm, const float* g_out, int64_t E, int32_t H, int32_t Co,
+                                               float* g_sa, float* g_sm, void* stream) {
+  return edge_combine_bwd_launch(sa, aF, sm, keep, perm, g_out, E, H, Co, g_sa, g_sm, (hipStream_t)stream);
+}
+
 // ---- dense-layer chain ----
 extern "C" size_t cgat_mlp_chain_workspace_bytes(int32_t n_layers) {
   return (size_t)(n_layers > 0 ? n_layers : 0) * WPREP_IMAGE_FLOATS_MAX * sizeof(float) + 256;

@@ -408,6 +408,16 @@ int seg_attnpool_bwd_launch(const float* a, int aF, const float* mult, const flo
 int rowdot_launch(const float* x, long ldx, int act, const float* v, long ldv, const int* vrow, const float* bias,
                   const float* addv, int rows, int H, int Hd, float* out, hipStream_t s);
 
+// ---- head combination of the per-edge hypernetwork edge update, edgecomb.hip ----
+// out[perm ? perm[t] : t, c] = (sum_h softmax_h(sa[t, ., c'])[h] * keep[t,h,c'] * sm[t,h,c]) / H with c' = c (aF == Co)
+// or 0 (aF == 1); the softmax over the heads has no max-subtraction (CGAT.py:214-223).  keep / perm may be null; backward
+// recomputes the softmax from sa, g_sa / g_sm may be null.  No workspace, no atomics.
+bool edge_combine_ok(int H, int aF, int Co);   // Co % 4 == 0, Co <= 256, 1 <= H <= 8, aF in {1, Co}
+int edge_combine_fwd_launch(const float* sa, int aF, const float* sm, const float* keep, const int* perm, long E, int H,
+                            int Co, float* out, hipStream_t s);
+int edge_combine_bwd_launch(const float* sa, int aF, const float* sm, const float* keep, const int* perm,
+                            const float* g_out, long E, int H, int Co, float* g_sa, float* g_sm, hipStream_t s);
+
 // ---- CSR plan, plan.hip ----
 size_t plan_ws_bytes(int E, int N);
 int plan_build_launch(const int64_t* edge_index, int E, int N, int* dst_rowptr, int* dst_perm, int* dst_sorted,

@@ -22,6 +22,7 @@ from .ops import (AttentionPoolFn, attention_pool, EdgeHiddenFn, EdgeHiddenHeads
                   segment_softmax, segment_sum)
 from .ops import overlap_enabled as ops_overlap_enabled
 from .ops import HNetFn, infer_route, nodes_attention_infer
+from .ops import EdgeHeadCombineFn, edge_combine_route
 from .ops import branch_stream
 from .roost import Roost
 
@@ -123,6 +124,22 @@ class GATConvEdges(nn.Module):
         self.first = first
         self.no_hyper = no_hyper
 
+    def _combine(self, sa, sm, drop):
+        """Generic route: logits and messages [E, H, .] in the caller's edge order -> [E, Co] (CGAT.py:214-223)."""
+        if edge_combine_route(sa, sm):
+            keep = None
+            if drop:
+                keep = _dropout_keep(sa, drop)                # CGAT.py:221
+                debug.note_dropout(keep)
+            return EdgeHeadCombineFn.apply(sa, sm, keep, None)
+        alpha = sa.exp()
+        alpha = alpha / alpha.sum(dim=1, keepdim=True)        # normalised over heads, no max-subtraction
+        if drop:
+            keep = _dropout_keep(alpha, drop)                 # CGAT.py:221
+            debug.note_dropout(keep)
+            alpha = alpha * keep
+        return (sm * alpha).mean(dim=1)
+
     def forward(self, x, edge_index, edge_attr, x_0, size=None):
         if self.no_hyper:
             return self.Pooling_NN(edge_attr)     # (the discarded attention's dropout mask is discarded with it)
@@ -137,14 +154,7 @@ class GATConvEdges(nn.Module):
         x_i = gather_rows(x, edge_index[0], splan0)           # note: opposite naming to GATConvNodes (209-210)
         x_j = gather_rows(x, edge_index[1], splan1)
         m = torch.cat([x_i, edge_attr, x_j], dim=-1)
-        alpha = self.MH_A(m).exp()
-        m = self.MH_M(m)
-        alpha = alpha / alpha.sum(dim=1, keepdim=True)        # normalised over heads, no max-subtraction
-        if drop:
-            keep = _dropout_keep(alpha, drop)                 # CGAT.py:221
-            debug.note_dropout(keep)
-            alpha = alpha * keep
-        aggr_out = (m * alpha).mean(dim=1)
+        aggr_out = self._combine(self.MH_A(m), self.MH_M(m), drop)
         if self.first:
             return self.Pooling_NN(edge_attr, aggr_out)
         return self.Pooling_NN(x_0, edge_attr, aggr_out)
@@ -174,6 +184,14 @@ def _gatconvedges_message_fast(self, x, edge_attr, plan, drop=0.0):
             debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, hid)
         sa, sm = HeadsLinearFn.apply(hid, a.fc_out.weight, a.fc_out.bias, m.fc_out.weight, m.fc_out.bias, H, Hd,
                                      (a.output_dim, Co), hmax)
+    if edge_combine_route(sa, sm):
+        # exp, head sum, division, dropout, product, head mean and the permutation back as one kernel per direction
+        keep = None
+        if drop:
+            keep = _dropout_keep(sa, drop)                    # CGAT.py:221; rows are destination-sorted slots here
+            if debug.recording():
+                debug.note_dropout(torch.empty_like(keep).index_copy(0, plan.dst_perm.long(), keep))
+        return EdgeHeadCombineFn.apply(sa, sm, keep, plan.dst_perm)
     alpha = sa.exp()
     alpha = alpha / alpha.sum(dim=1, keepdim=True)        # normalised over heads, no max-subtraction (CGAT.py:219-221)
     if drop:

@@ -1067,6 +1067,83 @@ def attention_pool(a, m, index_plan, index, mult=None, eps=1e-16):
     return segment_sum(w * m2, index_plan, index)
 
 
+_fused_edge_combine = os.environ.get("CGAT_FUSED_EDGE_COMBINE", "1") != "0"
+
+
+def set_fused_edge_combine(flag):
+    """The one-kernel head combination of GATConvEdges(no_hyper=False) (default on; env CGAT_FUSED_EDGE_COMBINE=0 starts
+    it off): EdgeHeadCombineFn instead of the exp / sum / division / dropout / product / mean / index_copy sequence of
+    torch ops on [E, H, Co] tensors.  Off: that sequence runs (the A/B reference)."""
+    global _fused_edge_combine
+    _fused_edge_combine = bool(flag)
+
+
+def get_fused_edge_combine():
+    return _fused_edge_combine
+
+
+class EdgeHeadCombineFn(torch.autograd.Function):
+    """out[perm[t]] = mean_h softmax over the heads(sa[t])[h] * keep[t, h] * sm[t, h] -- the reference's exp -> sum over
+    heads -> division -> dropout -> times the message -> mean (CGAT.py:214-223; no max-subtraction) as one kernel per
+    direction (csrc/edgecomb.hip).  `sa` [E, H, 1 | Co], `sm` [E, H, Co], `keep` the dropout keep-mask of sa's shape or
+    None, `perm` int32 [E] (rows are destination-sorted slots: plan.dst_perm) or None.  Backward recomputes the softmax
+    from sa: nothing but the inputs is saved."""
+
+    @staticmethod
+    def supported(sa, sm):
+        if sa.dim() != 3 or sm.dim() != 3 or sa.shape[:2] != sm.shape[:2]:
+            return False
+        if sa.dtype != torch.float32 or sm.dtype != torch.float32:
+            return False
+        H, aF, Co = sm.shape[1], sa.shape[2], sm.shape[2]
+        return Co % 4 == 0 and 0 < Co <= 256 and 1 <= H <= 8 and aF in (1, Co)
+
+    @staticmethod
+    def forward(ctx, sa, sm, keep, perm):
+        _require_gpu(sa, sm, keep, perm)
+        if not EdgeHeadCombineFn.supported(sa, sm):
+            raise ValueError(f"EdgeHeadCombineFn: unsupported shapes {tuple(sa.shape)}, {tuple(sm.shape)}")
+        sa, sm = _f32c(sa), _f32c(sm)
+        E, H, Co = sm.shape
+        aF = sa.shape[2]
+        if keep is not None:
+            if keep.shape != sa.shape:
+                raise ValueError("EdgeHeadCombineFn: the keep-mask must have the logits' shape")
+            keep = _f32c(keep)
+        if perm is not None:
+            if perm.dtype != torch.int32 or perm.numel() != E:
+                raise TypeError("EdgeHeadCombineFn: perm must be int32 [E]")
+            perm = perm.contiguous()
+        out = torch.empty(E, Co, dtype=torch.float32, device=sm.device)
+        with torch.cuda.device(sm.device):
+            check(lib.cgat_edge_head_combine_forward(_ptr(sa), aF, _ptr(sm), _ptr(keep), _ptr(perm), E, H, Co, _ptr(out),
+                                                     _stream()), "cgat_edge_head_combine_forward")
+        ctx.has_keep, ctx.has_perm = keep is not None, perm is not None
+        ctx.save_for_backward(sa, sm, *([keep] if keep is not None else []), *([perm] if perm is not None else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        sa, sm, *rest = ctx.saved_tensors
+        keep = rest.pop(0) if ctx.has_keep else None
+        perm = rest.pop(0) if ctx.has_perm else None
+        g_out = _f32c(g_out)
+        E, H, Co = sm.shape
+        g_sa = torch.empty_like(sa) if ctx.needs_input_grad[0] else None
+        g_sm = torch.empty_like(sm) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(sm.device):
+            check(lib.cgat_edge_head_combine_backward(_ptr(sa), sa.shape[2], _ptr(sm), _ptr(keep), _ptr(perm), _ptr(g_out),
+                                                      E, H, Co, _ptr(g_sa), _ptr(g_sm), _stream()),
+                  "cgat_edge_head_combine_backward")
+        return g_sa, g_sm, None, None
+
+
+def edge_combine_route(sa, sm):
+    """True when GATConvEdges hands its head combination to EdgeHeadCombineFn: the switch is on, the tensors are on the
+    GPU and the shape is one the kernels take.  Everything else keeps the sequence of torch ops."""
+    return _fused_edge_combine and sa.is_cuda and sm.is_cuda and EdgeHeadCombineFn.supported(sa, sm)
+
+
 class GatherRowsFn(torch.autograd.Function):
     """x[index] whose backward is an atomics-free segment sum over the index's CSR plan
     (deterministic, unlike index_add)."""

@@ -401,6 +401,27 @@ int cgat_segment_attention_pool_backward(const float* a, int32_t aF, const float
                                          const float* inv, const float* out_lo, const float* g_out, float* g_a, float* g_m,
                                          int64_t ldgm, float* g_mult, void* stream);
 
+/* Head combination of the per-edge hypernetwork edge update, GATConvEdges(no_hyper=False) (reference CGAT.py:214-223:
+ * exp -> sum over the heads -> division -> attention dropout -> times the message -> mean over the heads), one kernel
+ * per direction.  sa [E, H, aF] logits, sm [E, H, Co] messages, aF == Co (vector attention, c' = c) or aF == 1 (c' = 0):
+ *   alpha[t,h,c']            = exp(sa[t,h,c']) / sum_h' exp(sa[t,h',c'])     (no max-subtraction, ONE division: as the reference)
+ *   out[perm ? perm[t] : t, c] = (sum_h alpha[t,h,c'] * keep[t,h,c'] * sm[t,h,c]) / H
+ * keep [E, H, aF] is the dropout keep-mask scaled by 1 / (1 - p), NULL = no dropout; perm [E] (the plan's dst_perm when
+ * the rows are destination-sorted slots), NULL = rows already in output order.  Needs Co % 4 == 0, Co <= 256,
+ * 1 <= H <= 8, 16-byte aligned operands; E == 0 launches nothing.  No workspace, no atomics (bitwise reproducible). */
+int cgat_edge_head_combine_forward(const float* sa, int32_t aF, const float* sm, const float* keep, const int32_t* perm,
+                                   int64_t E, int32_t H, int32_t Co, float* out /* [E, Co] */, void* stream);
+/* alpha is recomputed from sa (nothing but the inputs is saved).  With g = g_out[perm ? perm[t] : t, :] / H:
+ *   g_sm[t,h,c]  = g[c] * alpha[t,h,c'] * keep[t,h,c']
+ *   q_h[c']      = sum over the channels c that share c' of g[c] * sm[t,h,c] * keep[t,h,c']
+ *   g_sa[t,h,c'] = alpha_h * (q_h - sum_h' alpha_h' * q_h')
+ * g_sa / g_sm may be NULL when that gradient is not needed.  With aF == 1 the sums over the Co channels run in a fixed
+ * order inside the row's lane group, and g_sa (E * H values) is formed in fp64 and rounded once; where the forward's
+ * fp32 denominator is not finite or zero, the row's g_sa is NaN as the row of `out` is. */
+int cgat_edge_head_combine_backward(const float* sa, int32_t aF, const float* sm, const float* keep, const int32_t* perm,
+                                    const float* g_out /* [E, Co] */, int64_t E, int32_t H, int32_t Co, float* g_sa,
+                                    float* g_sm, void* stream);
+
 /* A chain of up to 5 dense layers of width 128 in ONE launch (the split arithmetic modes f16x3, f16x3c, bf16x6;
  * CGAT_ERR_UNSUPPORTED in the f32 mode; the workspace holds one prepared weight image of 24576 floats per layer):
  *   r_0 = x                      (times act'(in_dact) if in_dact != NULL; stored to in_store if != NULL)
