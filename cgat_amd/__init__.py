@@ -16,6 +16,7 @@ from .optim import FusedAdam, FusedAdamW, FusedLamb, FusedSGD, L1Loss, MSELoss, 
 from .ops import get_bilinear_mode, set_bilinear_mode, set_validate_indices, set_edge_storage, get_edge_storage
 from .ops import set_fused_inference, get_fused_inference
 from .ops import set_fused_edge_combine, get_fused_edge_combine
+from .ops import set_fused_attention_dropout, get_fused_attention_dropout
 from .trainer import DataParallelTrainer, Normalizer
 from .chunked import set_max_edges_per_pass
 from .capture import GraphedStep
@@ -27,4 +28,4 @@ __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAtt
            "FusedSGD", "FusedAdam", "L1Loss", "MSELoss", "criterion_with_metrics", "set_bilinear_mode", "get_bilinear_mode",
            "set_validate_indices", "DataParallelTrainer", "Normalizer", "set_max_edges_per_pass",
            "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "set_fused_edge_combine",
-           "get_fused_edge_combine", "GraphedStep", "debug"]
+           "get_fused_edge_combine", "set_fused_attention_dropout", "get_fused_attention_dropout", "GraphedStep", "debug"]

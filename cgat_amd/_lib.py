@@ -164,6 +164,10 @@ PROTOTYPES = {
                                                       vp, vp, vp, vp, vp]),
     "cgat_segment_attention_pool_backward": (C.c_int, [vp, C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp, vp,
                                                        vp, vp, vp, vp, C.c_int64, vp, vp]),
+    "cgat_segment_attention_pool_dropout_forward": (C.c_int, [vp, C.c_int32, vp, vp, vp, C.c_int64, vp, vp, C.c_int32,
+                                                              C.c_int32, C.c_float, vp, vp, vp, vp, vp]),
+    "cgat_segment_attention_pool_dropout_backward": (C.c_int, [vp, C.c_int32, vp, vp, vp, C.c_int64, vp, vp, C.c_int32,
+                                                               C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "cgat_edge_head_combine_forward": (C.c_int, [vp, C.c_int32, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp]),
     "cgat_edge_head_combine_backward": (C.c_int, [vp, C.c_int32, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp,
                                                   vp]),

@@ -351,6 +351,24 @@ extern "C" int cgat_segment_attention_pool_backward(const float* a, int32_t aF, 
                                  (hipStream_t)stream, out_lo);
 }
 
+extern "C" int cgat_segment_attention_pool_dropout_forward(const float* a, int32_t aF, const float* keep,
+                                                           const int32_t* keep_idx, const float* m, int64_t ldm,
+                                                           const int32_t* rowptr, const int32_t* ridx, int32_t S,
+                                                           int32_t F, float eps, float* out, float* mx, float* inv,
+                                                           float* out_lo, void* stream) {
+  return seg_attnpool_drop_fwd_launch(a, aF, nullptr, keep, keep_idx, m, ldm, rowptr, ridx, S, F, eps, out, mx, inv, out_lo,
+                                      (hipStream_t)stream);
+}
+extern "C" int cgat_segment_attention_pool_dropout_backward(const float* a, int32_t aF, const float* keep,
+                                                            const int32_t* keep_idx, const float* m, int64_t ldm,
+                                                            const int32_t* rowptr, const int32_t* ridx, int32_t S,
+                                                            int32_t F, const float* out, const float* mx,
+                                                            const float* inv, const float* out_lo, const float* g_out,
+                                                            float* g_a, float* g_m, int64_t ldgm, void* stream) {
+  return seg_attnpool_drop_bwd_launch(a, aF, nullptr, keep, keep_idx, m, ldm, rowptr, ridx, S, F, out, mx, inv, out_lo, g_out,
+                                      g_a, g_m, ldgm, (hipStream_t)stream);
+}
+
 // ---- head combination of the edge update ----
 extern "C" int cgat_edge_head_combine_forward(const float* sa, int32_t aF, const float* sm, const float* keep,
                                               const int32_t* perm, int64_t E, int32_t H, int32_t Co, float* out,

@@ -404,6 +404,15 @@ int seg_attnpool_fwd_launch(const float* a, int aF, const float* mult, const flo
 int seg_attnpool_bwd_launch(const float* a, int aF, const float* mult, const float* m, long ldm, const int* rowptr,
                             const int* ridx, int S, int F, const float* out, const float* mx, const float* inv, const float* g_out, float* g_a,
                             float* g_m, long ldgm, float* g_mult, hipStream_t s, const float* out_lo = nullptr);
+// the same with an attention-dropout keep-mask: m' = keep * m, keep [R, aF] scaled by 1 / (1 - p); the keep row of CSR
+// position t is keep_idx[t] (nullable: the operand row).  `mult` must be null: the combination is refused, not built.
+int seg_attnpool_drop_fwd_launch(const float* a, int aF, const float* mult, const float* keep, const int* keep_idx,
+                                 const float* m, long ldm, const int* rowptr, const int* ridx, int S, int F, float eps,
+                                 float* out, float* mx, float* inv, float* out_lo, hipStream_t s);
+int seg_attnpool_drop_bwd_launch(const float* a, int aF, const float* mult, const float* keep, const int* keep_idx,
+                                 const float* m, long ldm, const int* rowptr, const int* ridx, int S, int F,
+                                 const float* out, const float* mx, const float* inv, const float* out_lo,
+                                 const float* g_out, float* g_a, float* g_m, long ldgm, hipStream_t s);
 // per-row, per-head dot:  out[r,h] = sum_j act(x[r, h*Hd+j]) * v[(vrow(r)) * ldv + h*Hd + j] + bias[h] (+ addv[vrow(r)*H + h])
 int rowdot_launch(const float* x, long ldx, int act, const float* v, long ldv, const int* vrow, const float* bias,
                   const float* addv, int rows, int H, int Hd, float* out, hipStream_t s);

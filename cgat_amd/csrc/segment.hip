@@ -611,21 +611,143 @@ __global__ __launch_bounds__(1024) void seg_attnpool_fwd_kernel(const float* __r
   }
 }
 
-// PER_F as above; otherwise the fw / 4 threads of a logit column are `grp` consecutive lanes of one wave (grp a power of
-// two <= 64) and their partial sums of g_a meet in a shuffle reduction
+// The forward with an attention-dropout keep-mask (CGAT.py:325: the reference masks the NORMALISED coefficients, and
+// sum_r keep alpha m = sum_r alpha (keep m)): the kernel above on the message m' = keep * m, without a multiplier.
+// keep [R, aF] is the mask scaled by 1 / (1 - p), laid out as the logits; the keep row of CSR position t is keep_idx[t]
+// when given (a mask drawn in the caller's edge order for operands in sorted slot order), else the operand row.  The
+// maximum, the normaliser and the coefficients' own sum do not see the mask.  A kernel of its own, not a template
+// parameter of the one above: moving that kernel's body into a shared __device__ template changed its register
+// allocation; the same statements in the same order here, so keep == 1 reproduces it bit for bit (tested).
 template <bool PER_F>
-__global__ __launch_bounds__(1024) void seg_attnpool_bwd_kernel(const float* __restrict__ a, int aF, int fw, int grp,
-                                                                const float* __restrict__ mult,
-                                                                const float* __restrict__ m, long ldm,
-                                                                const int* __restrict__ rowptr,
-                                                                const int* __restrict__ ridx, int F,
-                                                                const float* __restrict__ out,
-                                                                const float* __restrict__ mxs,
-                                                                const float* __restrict__ invs,
-                                                                const float* __restrict__ g_out,
-                                                                float* __restrict__ g_a, float* __restrict__ g_m,
-                                                                long ldgm, float* __restrict__ g_mult,
-                                                                const float* __restrict__ out_lo) {
+__global__ __launch_bounds__(1024) void seg_attnpool_drop_fwd_kernel(const float* __restrict__ a, int aF, int fw,
+                                                                     const float* __restrict__ keep,
+                                                                     const int* __restrict__ keep_idx,
+                                                                     const float* __restrict__ m, long ldm,
+                                                                     const int* __restrict__ rowptr,
+                                                                     const int* __restrict__ ridx, int F, float eps,
+                                                                     float* __restrict__ out, float* __restrict__ mx_out,
+                                                                     float* __restrict__ inv_out,
+                                                                     float* __restrict__ out_lo) {
+  const int s = blockIdx.x;
+  const int r0 = rowptr[s], r1 = rowptr[s + 1];
+  for (int f = 4 * threadIdx.x; f < F; f += 4 * blockDim.x) {
+    const int ac = PER_F ? f : f / fw;
+    float4 mx = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    for (int r = r0; r < r1; r += AP_W) {
+      float4 v[AP_W];
+#pragma unroll
+      for (int u = 0; u < AP_W; ++u) {
+        const int rs = r + u < r1 ? r + u : r1 - 1;
+        const long row = ridx ? (long)ridx[rs] : (long)rs;
+        if (PER_F) v[u] = *reinterpret_cast<const float4*>(a + row * aF + ac);
+        else v[u].x = a[row * aF + ac];
+      }
+#pragma unroll
+      for (int u = 0; u < AP_W; ++u) {
+        mx.x = fmaxf(mx.x, v[u].x);
+        if (PER_F) { mx.y = fmaxf(mx.y, v[u].y); mx.z = fmaxf(mx.z, v[u].z); mx.w = fmaxf(mx.w, v[u].w); }
+      }
+    }
+    if (!PER_F) mx.y = mx.z = mx.w = mx.x;
+    float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r = r0; r < r1; r += AP_W) {
+      float4 v[AP_W];
+#pragma unroll
+      for (int u = 0; u < AP_W; ++u) {
+        const int rs = r + u < r1 ? r + u : r1 - 1;
+        const long rr = ridx ? (long)ridx[rs] : (long)rs;
+        if (PER_F) v[u] = *reinterpret_cast<const float4*>(a + rr * aF + ac);
+        else v[u].x = a[rr * aF + ac];
+      }
+#pragma unroll
+      for (int u = 0; u < AP_W; ++u) {
+        if (r + u < r1) {
+          if (PER_F) {
+            z.x += expf(v[u].x - mx.x); z.y += expf(v[u].y - mx.y);
+            z.z += expf(v[u].z - mx.z); z.w += expf(v[u].w - mx.w);
+          } else {
+            z.x += expf(v[u].x - mx.x);
+          }
+        }
+      }
+    }
+    if (!PER_F) z.y = z.z = z.w = z.x;
+    const float4 den = make_float4(z.x + eps, z.y + eps, z.z + eps, z.w + eps);
+    double accd[4] = {0.0, 0.0, 0.0, 0.0};
+    double asum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int r = r0; r < r1; r += AP_U) {
+      float4 av[AP_U], mv[AP_U], kv[AP_U];
+#pragma unroll
+      for (int u = 0; u < AP_U; ++u) {
+        const int rs = r + u < r1 ? r + u : r1 - 1;
+        const long rr = ridx ? (long)ridx[rs] : (long)rs;
+        const long kr = keep_idx ? (long)keep_idx[rs] : rr;
+        if (PER_F) {
+          av[u] = *reinterpret_cast<const float4*>(a + rr * aF + ac);
+          kv[u] = *reinterpret_cast<const float4*>(keep + kr * aF + ac);
+        } else {
+          av[u].x = a[rr * aF + ac];
+          kv[u].x = keep[kr * aF + ac];
+        }
+        mv[u] = *reinterpret_cast<const float4*>(m + rr * ldm + f);
+      }
+#pragma unroll
+      for (int u = 0; u < AP_U; ++u) {
+        if (r + u < r1) {
+          float4 al;
+          al.x = expf(av[u].x - mx.x) / den.x;
+          if (PER_F) {
+            al.y = expf(av[u].y - mx.y) / den.y; al.z = expf(av[u].z - mx.z) / den.z;
+            al.w = expf(av[u].w - mx.w) / den.w;
+          } else {
+            al.y = al.z = al.w = al.x;
+            kv[u].y = kv[u].z = kv[u].w = kv[u].x;
+          }
+          // the masked message keep * m, rounded to fp32 as backward forms it
+          const float4 mk = make_float4(mv[u].x * kv[u].x, mv[u].y * kv[u].y, mv[u].z * kv[u].z, mv[u].w * kv[u].w);
+          accd[0] += (double)al.x * (double)mk.x; accd[1] += (double)al.y * (double)mk.y;
+          accd[2] += (double)al.z * (double)mk.z; accd[3] += (double)al.w * (double)mk.w;
+          asum[0] += (double)al.x; asum[1] += (double)al.y; asum[2] += (double)al.z; asum[3] += (double)al.w;
+        }
+      }
+    }
+    const float4 oh = make_float4((float)accd[0], (float)accd[1], (float)accd[2], (float)accd[3]);
+    *reinterpret_cast<float4*>(out + (long)s * F + f) = oh;
+    if (out_lo) {                                  // the centre accd / asum minus out, accd the MASKED sum
+      double c[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[j] = asum[j] > 0.0 ? accd[j] / asum[j] : accd[j];
+      *reinterpret_cast<float4*>(out_lo + (long)s * F + f) =
+          make_float4((float)(c[0] - (double)oh.x), (float)(c[1] - (double)oh.y), (float)(c[2] - (double)oh.z),
+                      (float)(c[3] - (double)oh.w));
+    }
+    if (PER_F) {
+      *reinterpret_cast<float4*>(mx_out + (long)s * aF + ac) = mx;
+      *reinterpret_cast<float4*>(inv_out + (long)s * aF + ac) = den;
+    } else if (f % fw == 0) {
+      mx_out[(long)s * aF + ac] = mx.x;
+      inv_out[(long)s * aF + ac] = den.x;
+    }
+  }
+}
+
+// PER_F as above; otherwise the fw / 4 threads of a logit column are `grp` consecutive lanes of one wave (grp a power of
+// two <= 64) and their partial sums of g_a meet in a shuffle reduction.  DROP (keep / keep_idx as in the forward):
+// g_m = keep alpha g_out, and the row is centred as the masked message, dm = (keep m - out) - out_lo.
+template <bool PER_F, bool DROP>
+__device__ __forceinline__ void seg_attnpool_bwd_body(const float* __restrict__ a, int aF, int fw, int grp,
+                                                      const float* __restrict__ mult,
+                                                      const float* __restrict__ keep, const int* __restrict__ keep_idx,
+                                                      const float* __restrict__ m, long ldm,
+                                                      const int* __restrict__ rowptr,
+                                                      const int* __restrict__ ridx, int F,
+                                                      const float* __restrict__ out,
+                                                      const float* __restrict__ mxs,
+                                                      const float* __restrict__ invs,
+                                                      const float* __restrict__ g_out,
+                                                      float* __restrict__ g_a, float* __restrict__ g_m,
+                                                      long ldgm, float* __restrict__ g_mult,
+                                                      const float* __restrict__ out_lo) {
   const int s = blockIdx.x;
   const int r0 = rowptr[s], r1 = rowptr[s + 1];
   // every thread of a wave runs the same number of iterations (F rounded up to whole groups by the launch), so the
@@ -648,7 +770,7 @@ __global__ __launch_bounds__(1024) void seg_attnpool_bwd_kernel(const float* __r
     const float4 go = *reinterpret_cast<const float4*>(g_out + (long)s * F + f);
     for (int rb = r0; rb < r1; rb += AP_U) {
      // (the operands of AP_U rows requested together, round 6: one row per round trip before; same operations per row)
-     float4 avv[AP_U], mvv[AP_U];
+     float4 avv[AP_U], mvv[AP_U], kvv[AP_U];
      float wvv[AP_U];
      long rrv[AP_U];
 #pragma unroll
@@ -659,6 +781,11 @@ __global__ __launch_bounds__(1024) void seg_attnpool_bwd_kernel(const float* __r
        if (PER_F) avv[u] = *reinterpret_cast<const float4*>(a + rrv[u] * aF + ac);
        else avv[u].x = a[rrv[u] * aF + ac];
        mvv[u] = *reinterpret_cast<const float4*>(m + rrv[u] * ldm + f);
+       if (DROP) {
+         const long kr = keep_idx ? (long)keep_idx[rc_] : rrv[u];
+         if (PER_F) kvv[u] = *reinterpret_cast<const float4*>(keep + kr * aF + ac);
+         else kvv[u].x = keep[kr * aF + ac];
+       }
      }
 #pragma unroll
      for (int u = 0; u < AP_U; ++u) {
@@ -667,7 +794,13 @@ __global__ __launch_bounds__(1024) void seg_attnpool_bwd_kernel(const float* __r
       const float w = wvv[u];
       float4 av = avv[u];
       if (!PER_F) av.y = av.z = av.w = av.x;
-      const float4 mv = mvv[u];
+      float4 mv = mvv[u];
+      float4 kv = make_float4(1.f, 1.f, 1.f, 1.f);
+      if (DROP) {                                // the masked message, as in the forward
+        kv = kvv[u];
+        if (!PER_F) kv.y = kv.z = kv.w = kv.x;
+        mv.x *= kv.x; mv.y *= kv.y; mv.z *= kv.z; mv.w *= kv.w;
+      }
       float4 al;
       al.x = (expf(av.x - mx.x) * w) / inv.x;    // `inv` holds the segment's denominator sum + eps (see the forward)
       if (PER_F) { al.y = (expf(av.y - mx.y) * w) / inv.y; al.z = (expf(av.z - mx.z) * w) / inv.z; al.w = (expf(av.w - mx.w) * w) / inv.w; }
@@ -675,7 +808,9 @@ __global__ __launch_bounds__(1024) void seg_attnpool_bwd_kernel(const float* __r
       const float4 gm = make_float4(al.x * go.x, al.y * go.y, al.z * go.z, al.w * go.w);
       const float4 dm = make_float4((mv.x - o4.x) - ol.x, (mv.y - o4.y) - ol.y, (mv.z - o4.z) - ol.z, (mv.w - o4.w) - ol.w);
       const float4 t = make_float4(gm.x * dm.x, gm.y * dm.y, gm.z * dm.z, gm.w * dm.w);
-      if (live && g_m) *reinterpret_cast<float4*>(g_m + r * ldgm + f) = gm;
+      if (live && g_m)
+        *reinterpret_cast<float4*>(g_m + r * ldgm + f) =
+            DROP ? make_float4(gm.x * kv.x, gm.y * kv.y, gm.z * kv.z, gm.w * kv.w) : gm;
       if (PER_F) {
         if (live) *reinterpret_cast<float4*>(g_a + r * aF + ac) = t;
       } else {
@@ -697,6 +832,39 @@ __global__ __launch_bounds__(1024) void seg_attnpool_bwd_kernel(const float* __r
      }
     }
   }
+}
+
+template <bool PER_F>
+__global__ __launch_bounds__(1024) void seg_attnpool_bwd_kernel(const float* __restrict__ a, int aF, int fw, int grp,
+                                                                const float* __restrict__ mult,
+                                                                const float* __restrict__ m, long ldm,
+                                                                const int* __restrict__ rowptr,
+                                                                const int* __restrict__ ridx, int F,
+                                                                const float* __restrict__ out,
+                                                                const float* __restrict__ mxs,
+                                                                const float* __restrict__ invs,
+                                                                const float* __restrict__ g_out,
+                                                                float* __restrict__ g_a, float* __restrict__ g_m,
+                                                                long ldgm, float* __restrict__ g_mult,
+                                                                const float* __restrict__ out_lo) {
+  seg_attnpool_bwd_body<PER_F, false>(a, aF, fw, grp, mult, nullptr, nullptr, m, ldm, rowptr, ridx, F, out, mxs, invs, g_out,
+                                      g_a, g_m, ldgm, g_mult, out_lo);
+}
+template <bool PER_F>   // with the keep-mask, without a multiplier
+__global__ __launch_bounds__(1024) void seg_attnpool_drop_bwd_kernel(const float* __restrict__ a, int aF, int fw, int grp,
+                                                                     const float* __restrict__ keep,
+                                                                     const int* __restrict__ keep_idx,
+                                                                     const float* __restrict__ m, long ldm,
+                                                                     const int* __restrict__ rowptr,
+                                                                     const int* __restrict__ ridx, int F,
+                                                                     const float* __restrict__ out,
+                                                                     const float* __restrict__ mxs,
+                                                                     const float* __restrict__ invs,
+                                                                     const float* __restrict__ g_out,
+                                                                     float* __restrict__ g_a, float* __restrict__ g_m,
+                                                                     long ldgm, const float* __restrict__ out_lo) {
+  seg_attnpool_bwd_body<PER_F, true>(a, aF, fw, grp, nullptr, keep, keep_idx, m, ldm, rowptr, ridx, F, out, mxs, invs, g_out,
+                                     g_a, g_m, ldgm, nullptr, out_lo);
 }
 
 static bool attnpool_ok(int aF, int F, long ldm, const void* a, const void* m, const void* out) {
@@ -746,6 +914,50 @@ int seg_attnpool_bwd_launch(const float* a, int aF, const float* mult, const flo
   else
     hipLaunchKernelGGL(seg_attnpool_bwd_kernel<false>, dim3(S), dim3(attnpool_threads(F)), 0, s, a, aF, fw, fw / 4, mult, m,
                        ldm, rowptr, ridx, F, out, mx, inv, g_out, g_a, g_m, ldgm, g_mult, out_lo);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+
+// The two launches with the attention-dropout keep-mask (see the kernel bodies).  A multiplier is refused: no caller
+// combines the two (Roost's weighted pooling has no dropout), and the variant is not built.
+int seg_attnpool_drop_fwd_launch(const float* a, int aF, const float* mult, const float* keep, const int* keep_idx,
+                                 const float* m, long ldm, const int* rowptr, const int* ridx, int S, int F, float eps,
+                                 float* out, float* mx, float* inv, float* out_lo, hipStream_t s) {
+  CGAT_CHECK_ARG(!mult, "segment_attention_pool_dropout: a keep-mask together with a multiplier is not supported");
+  CGAT_CHECK_ARG(keep != nullptr, "segment_attention_pool_dropout: keep is NULL");
+  if (S <= 0) return CGAT_OK;
+  CGAT_CHECK_ARG(attnpool_ok(aF, F, ldm, a, m, out), "segment_attention_pool_dropout: unsupported shape (F=%d, aF=%d)", F, aF);
+  CGAT_CHECK_ARG((((uintptr_t)out_lo) & 15) == 0, "segment_attention_pool_dropout: out_lo must be 16-byte aligned");
+  const int fw = F / aF;
+  CGAT_CHECK_ARG(fw != 1 || (((uintptr_t)keep) & 15) == 0, "segment_attention_pool_dropout: keep must be 16-byte aligned");
+  CGAT_PROF("seg_attnpool_drop_fwd", s);
+  if (fw == 1)
+    hipLaunchKernelGGL(seg_attnpool_drop_fwd_kernel<true>, dim3(S), dim3(attnpool_threads(F)), 0, s, a, aF, fw, keep,
+                       keep_idx, m, ldm, rowptr, ridx, F, eps, out, mx, inv, out_lo);
+  else
+    hipLaunchKernelGGL(seg_attnpool_drop_fwd_kernel<false>, dim3(S), dim3(attnpool_threads(F)), 0, s, a, aF, fw, keep,
+                       keep_idx, m, ldm, rowptr, ridx, F, eps, out, mx, inv, out_lo);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+int seg_attnpool_drop_bwd_launch(const float* a, int aF, const float* mult, const float* keep, const int* keep_idx,
+                                 const float* m, long ldm, const int* rowptr, const int* ridx, int S, int F,
+                                 const float* out, const float* mx, const float* inv, const float* out_lo,
+                                 const float* g_out, float* g_a, float* g_m, long ldgm, hipStream_t s) {
+  CGAT_CHECK_ARG(!mult, "segment_attention_pool_dropout backward: a keep-mask together with a multiplier is not supported");
+  CGAT_CHECK_ARG(keep != nullptr, "segment_attention_pool_dropout backward: keep is NULL");
+  if (S <= 0) return CGAT_OK;
+  CGAT_CHECK_ARG(attnpool_ok(aF, F, ldm, a, m, out) && ldgm % 4 == 0 && (((uintptr_t)out_lo) & 15) == 0 && (!g_m || (((uintptr_t)g_m) & 15) == 0),
+                 "segment_attention_pool_dropout backward: unsupported shape (F=%d, aF=%d)", F, aF);
+  const int fw = F / aF;
+  CGAT_CHECK_ARG(fw != 1 || (((uintptr_t)keep) & 15) == 0, "segment_attention_pool_dropout backward: keep must be 16-byte aligned");
+  CGAT_PROF("seg_attnpool_drop_bwd", s);
+  if (fw == 1)
+    hipLaunchKernelGGL(seg_attnpool_drop_bwd_kernel<true>, dim3(S), dim3(attnpool_threads(F)), 0, s, a, aF, fw, 1, keep,
+                       keep_idx, m, ldm, rowptr, ridx, F, out, mx, inv, g_out, g_a, g_m, ldgm, out_lo);
+  else
+    hipLaunchKernelGGL(seg_attnpool_drop_bwd_kernel<false>, dim3(S), dim3(attnpool_threads(F)), 0, s, a, aF, fw, fw / 4,
+                       keep, keep_idx, m, ldm, rowptr, ridx, F, out, mx, inv, g_out, g_a, g_m, ldgm, out_lo);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }

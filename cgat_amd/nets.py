@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import _lib, chunked, debug, rowprog
 from .hypernet import H_Net, H_Net_0
 from .mlp import ResidualNetwork, SimpleNetwork
-from .ops import (AttentionPoolFn, attention_pool, EdgeHiddenFn, EdgeHiddenHeadsFn, HeadsLinear1Fn, HeadsLinearFn, NodeLayerFn, NodesAttentionFn, SegmentPlan, SegmentSoftmaxFn, SegmentSumFn, gather_rows, get_plan, get_segment_plan, linear, small_embedding,
+from .ops import (AttentionPoolFn, attention_pool, get_fused_attention_dropout, EdgeHiddenFn, EdgeHiddenHeadsFn, HeadsLinear1Fn, HeadsLinearFn, NodeLayerFn, NodesAttentionFn, SegmentPlan, SegmentSoftmaxFn, SegmentSumFn, gather_rows, get_plan, get_segment_plan, linear, small_embedding,
                   segment_softmax, segment_sum)
 from .ops import overlap_enabled as ops_overlap_enabled
 from .ops import HNetFn, infer_route, nodes_attention_infer
@@ -262,19 +262,23 @@ class GATConvNodes(nn.Module):
 
     # -- vector attention (CGAT.py:286-290: MH_A emits one logit per head AND channel): the shared first layer of both
     #    networks runs as one operand-split op in destination-sorted order, so the concatenated message [E, 2C+Ce],
-    #    its K = 2C+Ce products and the two permutations of the generic path disappear --------------------------------
-    def _aggregate_vector(self, x, edge_attr, plan, edge_index):
+    #    its K = 2C+Ce products and the two permutations of the generic path disappear.  With `keep` (training-mode
+    #    attention dropout, CGAT.py:325: the keep-mask of the coefficients, [E, H, Co | 1] in ORIGINAL edge order) also
+    #    the scalar-attention layer runs here, MH_A's second layers emitting one logit per head: the pooling kernels
+    #    take the mask as an operand and reach its rows through plan.dst_perm ----------------------------------------
+    def _aggregate_vector(self, x, edge_attr, plan, edge_index, keep=None):
         a, m = self.MH_A, self.MH_M
         H, Hd, Co = self.heads, a.hidden_layer_dim, self.out_channels
         D = a.input_dim
+        cos = Co if a.output_dim == Co else (a.output_dim, Co)
         w_in = torch.cat([a.fc_in.weight.reshape(H * Hd, D), m.fc_in.weight.reshape(H * Hd, D)], dim=0)
         b_in = torch.cat([a.fc_in.bias, m.fc_in.bias])
         E = plan.E
-        if EdgeHiddenHeadsFn.eligible(w_in.shape[0], H, Hd, (Co, Co)):
+        if EdgeHiddenHeadsFn.eligible(w_in.shape[0], H, Hd, (a.output_dim, Co)):
             # first layers + the 2H second layers as ONE autograd node: its backward folds LeakyReLU' into the second
             # layers' input-gradient products instead of an elementwise pass over [E, 2 H Hd] (ops.EdgeHiddenHeadsFn)
             sa, sm = EdgeHiddenHeadsFn.apply(x, edge_attr, plan, w_in, b_in, a.fc_out.weight, a.fc_out.bias,
-                                             m.fc_out.weight, m.fc_out.bias, H, Hd, Co)
+                                             m.fc_out.weight, m.fc_out.bias, H, Hd, cos)
             if debug.recording():
                 debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, debug.last_hidden)
         else:
@@ -282,9 +286,12 @@ class GATConvNodes(nn.Module):
             if debug.recording():
                 debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, hid)
             # second layers of all 2H heads as one autograd node (ops.HeadsLinearFn): [E,H,Co] each
-            sa, sm = HeadsLinearFn.apply(hid, a.fc_out.weight, a.fc_out.bias, m.fc_out.weight, m.fc_out.bias, H, Hd, Co, hmax)
+            sa, sm = HeadsLinearFn.apply(hid, a.fc_out.weight, a.fc_out.bias, m.fc_out.weight, m.fc_out.bias, H, Hd, cos, hmax)
         sa2, sm2 = sa.reshape(E, -1), sm.reshape(E, -1)
-        if E > 0 and AttentionPoolFn.supported(sa2, sm2):
+        if keep is not None:
+            # (_attn_dropout_route has checked the shape) softmax, mask, product and sum as one kernel per direction
+            agg = AttentionPoolFn.apply(sa2, None, sm2, plan.dst_rowptr, None, 1e-16, keep.reshape(E, -1), plan.dst_perm)
+        elif E > 0 and AttentionPoolFn.supported(sa2, sm2):
             # channel-wise softmax over each atom's incoming edges, times the message, summed per atom: one kernel per
             # direction (csrc/segment.hip), no alpha / alpha*message tensors of [E, H*C]
             agg = AttentionPoolFn.apply(sa2, None, sm2, plan.dst_rowptr, None, 1e-16)
@@ -292,6 +299,16 @@ class GATConvNodes(nn.Module):
             alpha = SegmentSoftmaxFn.apply(sa2, None, plan.dst_rowptr, 1e-16)
             agg = SegmentSumFn.apply(sm2 * alpha, plan.dst_rowptr, plan.dst_sorted.long())
         return agg.reshape(plan.N, H, Co).mean(dim=1)
+
+    def _attn_dropout_route(self, x, edge_attr, plan):
+        """True when training-mode attention dropout runs on the operand-split route with the keep-mask pooling kernels:
+        the switch is on (ops.set_fused_attention_dropout), message() is the layer's own, the tensors are on the GPU and
+        the pooling shape is one the kernels take.  Everything else keeps the MessagePassing-style route."""
+        if not (get_fused_attention_dropout() and type(self).message is GATConvNodes.message and x.is_cuda and
+                edge_attr.is_cuda and x.dtype == torch.float32 and plan.E > 0):
+            return False
+        H = self.heads
+        return AttentionPoolFn.supported(x.new_empty(0, H * self.MH_A.output_dim), x.new_empty(0, H * self.out_channels))
 
     # -- MessagePassing-style surface (subclasses overriding message) --
     def message(self, x_i, x_j, edge_attr, edge_index_i, plan=None):
@@ -345,11 +362,12 @@ class GATConvNodes(nn.Module):
                     agg = lambda xs, ei, es: self._aggregate_fused(xs, es, get_plan(ei, xs.shape[0]))
                     upd = lambda aggr, x0s, xs: self.update(aggr, x_0=x0s, x=xs, _mean_done=True)
                     return chunked.ChunkedSplitLayerFn.apply(agg, upd, chunks, x, edge_attr, x_0, *self.parameters())
-                run = lambda xs, ei, es, x0s: self._propagate_one(ei, xs, es, x0s)
+                run = lambda xs, ei, es, x0s: self._propagate_one(ei, xs, es, x0s, fused_dropout=False)
                 return chunked.ChunkedLayerFn.apply(run, chunks, x, edge_attr, x_0, *self.parameters())
         return self._propagate_one(edge_index, x, edge_attr, x_0)
 
-    def _propagate_one(self, edge_index, x, edge_attr, x_0):
+    def _propagate_one(self, edge_index, x, edge_attr, x_0, fused_dropout=True):
+        """`fused_dropout=False` (the chunked pass): training-mode attention dropout keeps the MessagePassing-style route."""
         plan = get_plan(edge_index, x.shape[0])
         drop = bool(self.dropout and self.training)       # F.dropout(..., training=self.training): identity in eval mode
         if (ops_overlap_enabled() and not self.vector_attention and not self.final and not drop and
@@ -360,9 +378,14 @@ class GATConvNodes(nn.Module):
             aggr = self._aggregate_fused(x, edge_attr, plan)
         elif self.vector_attention and type(self).message is GATConvNodes.message and not drop:
             aggr = self._aggregate_vector(x, edge_attr, plan, edge_index)
+        elif drop and fused_dropout and self._attn_dropout_route(x, edge_attr, plan):
+            # drawn on the shape and in the edge order of the MessagePassing-style route's alpha: one seed, one mask
+            keep = _dropout_keep(x.new_empty(plan.E, self.heads, self.MH_A.output_dim), self.dropout)   # CGAT.py:325
+            debug.note_dropout(keep)
+            aggr = self._aggregate_vector(x, edge_attr, plan, edge_index, keep=keep)
         else:
-            # the MessagePassing-style route: subclasses overriding message(), and training-mode attention dropout
-            # (the mask multiplies the normalised coefficients, so the fused softmax x message kernels do not apply)
+            # the MessagePassing-style route: subclasses overriding message(), and training-mode attention dropout where
+            # the route above does not apply (switched off, CPU tensors, a shape the pooling kernels do not take, chunks)
             splan0, splan1 = _endpoint_plans(plan, edge_index)
             x_j = gather_rows(x, edge_index[0], splan0)
             x_i = gather_rows(x, edge_index[1], splan1)

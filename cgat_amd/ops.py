@@ -1000,7 +1000,12 @@ class AttentionPoolFn(torch.autograd.Function):
     """out[s, f] = sum_{r in seg s} alpha[r, f // fw] * m[r, f] with alpha = mult * exp(a - segmax) / (segsum + eps) -- the
     reference's softmax -> multiply -> scatter_add (CGAT.py:323-329, 59-61; roost_message.py:305-317) as one kernel per
     direction.  `a` [R, aF], `m` [R, F] (fw = F // aF), `mult` [R] or None; `perm` = rows of each segment in CSR order
-    (None: the rows already are), so nothing is gathered or permuted."""
+    (None: the rows already are), so nothing is gathered or permuted.
+
+    apply(a, mult, m, rowptr, perm, eps, keep, keep_idx) is the same with training-mode attention dropout between the
+    softmax and the product (CGAT.py:325): out = sum_r keep * alpha * m.  `keep` [R, aF] is the keep-mask scaled by
+    1 / (1 - p); the keep row of CSR position t is keep_idx[t] (int32 [R]) or, with keep_idx None, the operand row.  The
+    mask gets no gradient, and a mask together with `mult` is refused (no layer combines them; it is not built)."""
 
     @staticmethod
     def supported(a, m):
@@ -1011,14 +1016,27 @@ class AttentionPoolFn(torch.autograd.Function):
         return (fw == 1 and aF % 4 == 0) or (fw % 4 == 0 and fw // 4 <= 64 and (fw // 4) & (fw // 4 - 1) == 0)
 
     @staticmethod
-    def forward(ctx, a, mult, m, rowptr, perm, eps):
-        _require_gpu(a, m, rowptr)
+    def forward(ctx, a, mult, m, rowptr, perm, eps, *drop):
+        keep, keep_idx = drop if drop else (None, None)
+        _require_gpu(a, m, rowptr, keep, keep_idx)
         a, m = _f32c(a), _f32c(m)
         mu = None if mult is None else _f32c(mult.reshape(-1))
         R, aF = a.shape
         F = m.shape[1]
         S = rowptr.numel() - 1
         dev = a.device
+        if keep is not None:
+            if mu is not None:
+                raise ValueError("AttentionPoolFn: a keep-mask together with a multiplier is not supported")
+            if keep.shape != a.shape:
+                raise ValueError("AttentionPoolFn: the keep-mask must have the logits' shape")
+            keep = _f32c(keep)
+            if keep_idx is not None:
+                if keep_idx.dtype != torch.int32 or keep_idx.numel() != R:
+                    raise TypeError("AttentionPoolFn: keep_idx must be int32 [R]")
+                keep_idx = keep_idx.contiguous()
+        elif keep_idx is not None:
+            raise ValueError("AttentionPoolFn: keep_idx without a keep-mask")
         out = torch.empty(S, F, dtype=torch.float32, device=dev)
         mx = torch.empty(S, aF, dtype=torch.float32, device=dev)
         inv = torch.empty(S, aF, dtype=torch.float32, device=dev)
@@ -1026,12 +1044,19 @@ class AttentionPoolFn(torch.autograd.Function):
         need_lo = any(ctx.needs_input_grad[:3])
         out_lo = torch.empty(S, F, dtype=torch.float32, device=dev) if need_lo else None
         with torch.cuda.device(dev):
-            check(lib.cgat_segment_attention_pool_forward(_ptr(a), aF, _ptr(mu), _ptr(m), F, _ptr(rowptr), _ptr(perm), S, F,
-                                                          eps, _ptr(out), _ptr(mx), _ptr(inv), _ptr(out_lo), _stream()),
-                  "cgat_segment_attention_pool_forward")
+            if keep is not None:
+                check(lib.cgat_segment_attention_pool_dropout_forward(
+                    _ptr(a), aF, _ptr(keep), _ptr(keep_idx), _ptr(m), F, _ptr(rowptr), _ptr(perm), S, F, eps, _ptr(out),
+                    _ptr(mx), _ptr(inv), _ptr(out_lo), _stream()), "cgat_segment_attention_pool_dropout_forward")
+            else:
+                check(lib.cgat_segment_attention_pool_forward(_ptr(a), aF, _ptr(mu), _ptr(m), F, _ptr(rowptr), _ptr(perm), S, F,
+                                                              eps, _ptr(out), _ptr(mx), _ptr(inv), _ptr(out_lo), _stream()),
+                      "cgat_segment_attention_pool_forward")
         ctx.has_mu, ctx.has_perm, ctx.mshape = mu is not None, perm is not None, None if mult is None else mult.shape
+        ctx.has_keep, ctx.has_kidx, ctx.n_drop = keep is not None, keep_idx is not None, len(drop)
         ctx.save_for_backward(a, m, out, mx, inv, out_lo, rowptr, *([mu] if mu is not None else []),
-                              *([perm] if perm is not None else []))
+                              *([perm] if perm is not None else []), *([keep] if keep is not None else []),
+                              *([keep_idx] if keep_idx is not None else []))
         return out
 
     @staticmethod
@@ -1039,6 +1064,8 @@ class AttentionPoolFn(torch.autograd.Function):
         a, m, out, mx, inv, out_lo, rowptr, *rest = ctx.saved_tensors
         mu = rest.pop(0) if ctx.has_mu else None
         perm = rest.pop(0) if ctx.has_perm else None
+        keep = rest.pop(0) if ctx.has_keep else None
+        keep_idx = rest.pop(0) if ctx.has_kidx else None
         g_out = _f32c(g_out)
         R, aF = a.shape
         F = m.shape[1]
@@ -1047,11 +1074,17 @@ class AttentionPoolFn(torch.autograd.Function):
         g_m = torch.empty_like(m) if ctx.needs_input_grad[2] else None
         g_mu = torch.empty_like(mu) if (mu is not None and ctx.needs_input_grad[1]) else None
         with torch.cuda.device(a.device):
-            check(lib.cgat_segment_attention_pool_backward(_ptr(a), aF, _ptr(mu), _ptr(m), F, _ptr(rowptr), _ptr(perm), S, F,
-                                                           _ptr(out), _ptr(mx), _ptr(inv), _ptr(out_lo), _ptr(g_out), _ptr(g_a),
-                                                           _ptr(g_m), F, _ptr(g_mu), _stream()),
-                  "cgat_segment_attention_pool_backward")
-        return g_a, (None if g_mu is None else g_mu.reshape(ctx.mshape)), g_m, None, None, None
+            if keep is not None:
+                check(lib.cgat_segment_attention_pool_dropout_backward(
+                    _ptr(a), aF, _ptr(keep), _ptr(keep_idx), _ptr(m), F, _ptr(rowptr), _ptr(perm), S, F, _ptr(out), _ptr(mx),
+                    _ptr(inv), _ptr(out_lo), _ptr(g_out), _ptr(g_a), _ptr(g_m), F, _stream()),
+                    "cgat_segment_attention_pool_dropout_backward")
+            else:
+                check(lib.cgat_segment_attention_pool_backward(_ptr(a), aF, _ptr(mu), _ptr(m), F, _ptr(rowptr), _ptr(perm), S, F,
+                                                               _ptr(out), _ptr(mx), _ptr(inv), _ptr(out_lo), _ptr(g_out), _ptr(g_a),
+                                                               _ptr(g_m), F, _ptr(g_mu), _stream()),
+                      "cgat_segment_attention_pool_backward")
+        return (g_a, (None if g_mu is None else g_mu.reshape(ctx.mshape)), g_m, None, None, None) + (None,) * ctx.n_drop
 
 
 def attention_pool(a, m, index_plan, index, mult=None, eps=1e-16):
@@ -1080,6 +1113,22 @@ def set_fused_edge_combine(flag):
 
 def get_fused_edge_combine():
     return _fused_edge_combine
+
+
+_fused_attn_dropout = os.environ.get("CGAT_FUSED_ATTN_DROPOUT", "1") != "0"
+
+
+def set_fused_attention_dropout(flag):
+    """Training-mode attention dropout of GATConvNodes on the operand-split first layer and the keep-mask attention-pool
+    kernels (default on; env CGAT_FUSED_ATTN_DROPOUT=0 starts it off).  Off: the MessagePassing-style route runs --
+    concatenated [E, 2C+Ce] rows, generic networks, segment softmax, mask, product, segment sum (the A/B reference).
+    The mask is drawn the same way on both routes: one seed gives one mask per edge."""
+    global _fused_attn_dropout
+    _fused_attn_dropout = bool(flag)
+
+
+def get_fused_attention_dropout():
+    return _fused_attn_dropout
 
 
 class EdgeHeadCombineFn(torch.autograd.Function):

@@ -401,6 +401,28 @@ int cgat_segment_attention_pool_backward(const float* a, int32_t aF, const float
                                          const float* inv, const float* out_lo, const float* g_out, float* g_a, float* g_m,
                                          int64_t ldgm, float* g_mult, void* stream);
 
+/* Attention pooling with training-mode attention dropout (reference CGAT.py:323-329: softmax -> F.dropout on the
+ * normalised coefficients -> times the message -> scatter_add), one pass per direction:
+ *   out[s,f] = sum_{r in seg s} keep[k(r), f/fw] * alpha[r, f/fw] * m[r,f] = sum_r alpha * (keep * m),
+ * alpha as above without a multiplier; the maximum, the denominator (mx / inv) and the centre's normalisation do not see
+ * the mask.  keep [R, aF] is the keep-mask already scaled by 1 / (1 - p) (values 0 or 1 / (1 - p)), laid out as the
+ * logits; the keep row of CSR position t is k = keep_idx[t] (int32 [R]) when keep_idx != NULL -- a mask drawn in the
+ * caller's edge order for operands in destination-sorted slot order -- and the operand row (ridx[t], or t) otherwise.
+ * Same shape rule as cgat_segment_attention_pool_forward; keep must be 16-byte aligned when aF == F; S == 0 launches
+ * nothing.  The mask is an explicit operand (no random numbers are drawn in the kernel).  No atomics, fixed summation
+ * order: bitwise reproducible; with keep == 1 everywhere every output equals cgat_segment_attention_pool_* bit for bit. */
+int cgat_segment_attention_pool_dropout_forward(const float* a, int32_t aF, const float* keep, const int32_t* keep_idx,
+                                                const float* m, int64_t ldm, const int32_t* rowptr, const int32_t* ridx,
+                                                int32_t S, int32_t F, float eps, float* out, float* mx, float* inv,
+                                                float* out_lo, void* stream);
+/* g_m[r,f] = keep * alpha * g_out[s,f];  g_a[r,c] = sum_{f in c} alpha * g_out * ((keep * m - out) - out_lo)
+ * (g_m / out_lo may be NULL; keep receives no gradient) */
+int cgat_segment_attention_pool_dropout_backward(const float* a, int32_t aF, const float* keep, const int32_t* keep_idx,
+                                                 const float* m, int64_t ldm, const int32_t* rowptr, const int32_t* ridx,
+                                                 int32_t S, int32_t F, const float* out, const float* mx, const float* inv,
+                                                 const float* out_lo, const float* g_out, float* g_a, float* g_m,
+                                                 int64_t ldgm, void* stream);
+
 /* Head combination of the per-edge hypernetwork edge update, GATConvEdges(no_hyper=False) (reference CGAT.py:214-223:
  * exp -> sum over the heads -> division -> attention dropout -> times the message -> mean over the heads), one kernel
  * per direction.  sa [E, H, aF] logits, sm [E, H, Co] messages, aF == Co (vector attention, c' = c) or aF == 1 (c' = 0):
