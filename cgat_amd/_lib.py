@@ -130,6 +130,7 @@ PROTOTYPES = {
     "cgat_nodes_attention_backward": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(AttnGrads), vp, C.c_size_t, vp]),
     "cgat_nodes_attention_infer_fused": (C.c_int32, [C.POINTER(Plan), C.POINTER(AttnParams)]),
+    "cgat_nodes_attention_bit_form": (C.c_int32, [C.POINTER(Plan), C.POINTER(AttnParams)]),
     "cgat_nodes_attention_infer_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.POINTER(AttnParams)]),
     "cgat_nodes_attention_infer": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, vp, vp, C.c_size_t, vp]),
     "cgat_debug_nodes_attention_route": (C.c_uint32, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),

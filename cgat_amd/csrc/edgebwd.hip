@@ -1056,18 +1056,25 @@ static int edge_gw_splits(int W2) {   // ranges x column-block pairs ~ one workg
 #define GW_BIT_COST_M 4
 static bool g_gw_force_six = false;    // debug, process-wide: keep the six-pass form (cgat_debug_edge_gw_force_six)
 bool edge_gw_force_six(bool on) { const bool was = g_gw_force_six; g_gw_force_six = on; return was; }
-static bool edge_gw_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six, int* SA, int* SM) {
-  if (!rc || !perm || force_six || g_gw_force_six || !mode_24bit() || edge_mma_bf16() || mode_bf16x3()) return false;
-  if (rc->Hd != 256 || rc->H < 1 || rc->HHd != rc->H * rc->Hd || rc->nw * 32 != W2 || W2 <= rc->HHd ||
-      (W2 - rc->HHd) % 256 != 0)
-    return false;
-  const int H = rc->H, npm = (W2 - rc->HHd) / 256;
+// (mode and shape alone: what the debug switches cannot change)
+static bool gw_bitplane_shape(int H, int Hd, int HHd, int W2, int* SA, int* SM) {
+  if (!mode_24bit() || edge_mma_bf16() || mode_bf16x3()) return false;
+  if (Hd != 256 || H < 1 || HHd != H * Hd || W2 <= HHd || (W2 - HHd) % 256 != 0) return false;
+  const int npm = (W2 - HHd) / 256;
   // SA (H + npm * COST_M / COST_A) <= 256
   const int sa = 256 * GW_BIT_COST_A / (H * GW_BIT_COST_A + npm * GW_BIT_COST_M);
   if (sa < 1 || 256 - H * sa < npm) return false;
   *SA = sa;
   *SM = (256 - H * sa) / npm;
   return true;
+}
+static bool edge_gw_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six, int* SA, int* SM) {
+  if (!rc || !perm || force_six || g_gw_force_six || rc->nw * 32 != W2) return false;
+  return gw_bitplane_shape(rc->H, rc->Hd, rc->HHd, W2, SA, SM);
+}
+bool edge_gw_bitplane_layer(int H, int Hd) {
+  int sa, sm;
+  return gw_bitplane_shape(H, Hd, H * Hd, 2 * H * Hd, &sa, &sm);
 }
 bool edge_gw_takes_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six) {
   int sa, sm;
@@ -1090,10 +1097,14 @@ size_t edge_gw_ws_floats(int E, int W2) {
 //   attention column: P likewise over the SA slabs; cs_h[j] = the SA x 8 partial rows, thread q the rows of slot quad q
 //                     in range order, then q in order;  out = wA (P + 0.01 (cs - P)) on the rounded P and cs as
 //                     d = cs - P;  u = fma(0.01, d, P);  out = wA * u, each one fp32 rounding, in this order
+// te (the bit form of the layer's saved buffer): an attention workgroup also leaves
+//   te.part[4 col + quarter] = sum over its 32 outputs j of We[col, j] * u[col, j]     (fp64, a fixed tree over the lanes)
+// the edge part of grad fc_out_A; gw_te_add_kernel adds the four quarters to te.out[col].  out == nullptr: nothing else.
 __global__ __launch_bounds__(256) void edge_gw_bit_reduce_kernel(const float* __restrict__ slabM, int SM,
                                                                  const float* __restrict__ slabA, int SA,
                                                                  const float* __restrict__ csl, const float* __restrict__ wA,
-                                                                 int H, int HHd, int W2, float* __restrict__ out, long ldo) {
+                                                                 int H, int HHd, int W2, float* __restrict__ out, long ldo,
+                                                                 const GwTe te) {
   __shared__ double part[8][32], cpart[8][32];
   const int o = threadIdx.x & 31, zg = threadIdx.x >> 5;
   const int col = blockIdx.x >> 2, j = 32 * (blockIdx.x & 3) + o;
@@ -1114,15 +1125,30 @@ __global__ __launch_bounds__(256) void edge_gw_bit_reduce_kernel(const float* __
 #pragma unroll
   for (int g = 1; g < 8; ++g) { sd += part[g][o]; cd += cpart[g][o]; }
   float s = (float)sd;
-  if (isA) s = __fmul_rn(wA[col], __fmaf_rn(0.01f, __fsub_rn((float)cd, s), s));
-  out[(long)col * ldo + j] = s;
+  if (isA) {
+    const float u = __fmaf_rn(0.01f, __fsub_rn((float)cd, s), s);
+    s = __fmul_rn(wA[col], u);
+    if (te.part) {   // (uniform per workgroup; lanes 0..31 of wave 0 are the only threads left)
+      double p = (double)te.We[(long)col * te.ldw + j] * (double)u;
+#pragma unroll
+      for (int w = 16; w > 0; w >>= 1) p += __shfl_xor(p, w, 64);
+      if (o == 0) te.part[(long)col * 4 + (blockIdx.x & 3)] = p;
+    }
+  }
+  if (out) out[(long)col * ldo + j] = s;
+}
+__global__ void gw_te_add_kernel(const double* __restrict__ part, int HHd, float* __restrict__ out) {
+  const int col = blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= HHd) return;
+  const double* p = part + (long)col * 4;
+  out[col] = (float)(((p[0] + p[1]) + (p[2] + p[3])) + (double)out[col]);
 }
 
 // out[col * ldo + k] = sum_t G[t, col] * e[perm[t] * lde + k],   G[t, 128 a + j] at gZ[t * ldg + a * gzb + j]
 // gmax, emax (f16x3 mode only): device pointers to max |gZ| and max |e|; without them the bf16x6 form runs.
 int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde, const int* perm, int E, int W2,
                    float* ws, float* out, long ldo, hipStream_t stream, const float* gmax, const float* emax,
-                   const EdgeRC* rc, bool force_six) {
+                   const EdgeRC* rc, bool force_six, const GwTe* te) {
   if (E <= 0) {
     GemmParams z = gemm_params(W2, 128, 0, nullptr, 1, nullptr, 1, out, ldo);
     return gemm_launch(z, nullptr, 0, stream);   // K = 0: zero fill
@@ -1135,7 +1161,18 @@ int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde
   CGAT_TRY(prepare_T_bf16_rows_launch(e, lde, perm, E, planes, na, stream, f16 ? emax : nullptr));
   const int nsteps = cdiv(E, 32);
   int SA = 0, SM = 0;
-  if (!f16 && edge_gw_bitplane(rc, W2, perm, force_six, &SA, &SM)) {
+  const bool bitplane = !f16 && edge_gw_bitplane(rc, W2, perm, force_six, &SA, &SM);
+  // The edge part of grad fc_out_A comes from the bit-plane form's column sums.  With that form switched off for this
+  // launch (the debug switches) it still runs first, for that sum alone, and the six-pass form below writes `out`: on
+  // that debug route the whole bit-plane launch and its reducer are paid on top of the six-pass launch (about twice the
+  // work of either), and the six-pass launch then reuses the same slab workspace, behind them on the same stream.  It
+  // keeps grad fc_out_A's bits independent of the switch (tests/test_edge_gw_bitplane.py compares a layer step with the
+  // switch on and off bit for bit in everything but the two W_e blocks).
+  const bool te_only = te && !bitplane;
+  if (te_only)
+    CGAT_CHECK_ARG(!f16 && rc && perm && rc->nw * 32 == W2 && gw_bitplane_shape(rc->H, rc->Hd, rc->HHd, W2, &SA, &SM),
+                   "edge_gw: the edge part of grad fc_out_A needs the shape of the bit-plane form");
+  if (bitplane || te_only) {
     const int H = rc->H, HHd = rc->HHd, npm = (W2 - HHd) / 256;
     float* slabA = slab + (size_t)SM * (W2 - HHd) * 128;
     float* csl = slabA + (size_t)SA * HHd * 128;
@@ -1146,9 +1183,13 @@ int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde
       CGAT_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(edge_gw_bit_reduce_kernel, dim3(W2 * 4), dim3(256), 0, stream, slab, SM, slabA, SA, csl, rc->wA, H,
-                       HHd, W2, out, ldo);
+                       HHd, W2, te_only ? nullptr : out, ldo, te ? *te : GwTe{});
     CGAT_LAUNCH_CHECK();
-    return CGAT_OK;
+    if (te) {
+      hipLaunchKernelGGL(gw_te_add_kernel, dim3(cdiv(HHd, 256)), dim3(256), 0, stream, te->part, HHd, te->out);
+      CGAT_LAUNCH_CHECK();
+    }
+    if (!te_only) return CGAT_OK;
   }
   {
     CGAT_PROF(perm ? "edge_gw" : "rows_gw", stream);

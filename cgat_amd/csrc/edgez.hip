@@ -361,10 +361,17 @@ __global__ __launch_bounds__(256, 2) void edge_z_kernel(const float* __restrict_
 //   2  the message column blocks: each 32-column slice of z = part + Pi[dst] + Pj[src] is staged in LDS (rounded to bf16
 //      first under bf16 edge storage, as mode 0 stores it), and red(a, ch) reduces it into the weighted segment sums
 //      (edge_msg_wsum_kernel).  Nothing per edge reaches memory.
+//   3  the bit form of the training forward: as mode 0, but an attention chunk stores no Z -- a chunk
+//      is one 32-column word of the sign mask (bit i of word w = Z[t, 32 w + i] > 0, seg_bwd_att_kernel's meaning); the words
+//      of rows 32 g .. 32 g + 31 go to zbits + g * ldz, word-major [word][row & 31]: one 128-byte line per wave and chunk.
+//      Logits by the same statements; the message chunks are mode 0's.
 // The logits of head h (of the H heads this tile computes) go to a_out[row * lda + h].
 // Rows >= row_lim are clamped to row_lim - 1 (their results are discarded).  The counted wait below allows for the
 // stores of mode 0 only; modes 1 and 2 wait for the gathers of the current slice with 4 fewer younger operations (in
-// mode 2 the weighted sums' stores of the previous slice are older still: waited for too, never overtaken).
+// mode 2 the weighted sums' stores of the previous slice are older still: waited for too, never overtaken).  In mode 3 an
+// attention chunk issues ONE store (every wave: a wave of clamped rows rewrites row E - 1's word with the identical value),
+// so behind an attention chunk the wait counts 1 + 3 + 8 = 12 younger operations, behind a message chunk mode 0's 15: the
+// count never includes an operation that was not issued (the logits' stores, where a head ends, only make it wait longer).
 // ---------------------------------------------------------------------------------------
 constexpr int Z6_CH = 24 * 64;                        // 16-byte pieces per ring chunk (24 KB)
 constexpr int Z6_SLOTS = 4;
@@ -379,7 +386,7 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
                                          float* Z, long ldz, int row0, int row_lim,
                                          const float* wA, const float* bA, int H,
                                          int cb_per_head, float* a_out, int lda, int act, float* omax,
-                                         const Red& red) {
+                                         const Red& red, unsigned* zbits = nullptr) {
   constexpr int CH = Z6_CH;
   constexpr int SLOTS = Z6_SLOTS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -494,6 +501,7 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
     asm volatile("" : "+v"(ra_), "+v"(rb_), "+v"(lk_));                                        \
     const int col0 = (a_) * 128 + ((ch_) >> 1) * 64 + ((ch_) & 1) * 32 + 4 * (lk_ >> 4);       \
     const bool isA = (a_) < ncbA;                                                              \
+    unsigned wa_ = 0u, wb_ = 0u;                                                               \
     _Pragma("unroll") for (int cb2 = 0; cb2 < 2; ++cb2) {                                      \
       const int col = col0 + 16 * cb2;                                                         \
       const f32x4 pa = part[2 * cb2 + 0] - partn[2 * cb2 + 0], pb = part[2 * cb2 + 1] - partn[2 * cb2 + 1]; \
@@ -525,6 +533,16 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
           *reinterpret_cast<float4*>(Z + (long)rb_ * ldz + col) = vb;                          \
         }                                                                                      \
       }                                                                                        \
+      if constexpr (MODE == 3) {                                                               \
+        if (isA) {   /* four sign bits of each row at the columns' place in the chunk's word */ \
+          const int sh_ = 16 * cb2 + 4 * (lk_ >> 4);                                           \
+          wa_ |= ((va.x > 0.f ? 1u : 0u) | (va.y > 0.f ? 2u : 0u) | (va.z > 0.f ? 4u : 0u) | (va.w > 0.f ? 8u : 0u)) << sh_; \
+          wb_ |= ((vb.x > 0.f ? 1u : 0u) | (vb.y > 0.f ? 2u : 0u) | (vb.z > 0.f ? 4u : 0u) | (vb.w > 0.f ? 8u : 0u)) << sh_; \
+        } else {                                                                               \
+          *reinterpret_cast<float4*>(Z + (long)ra_ * ldz + col) = va;                          \
+          *reinterpret_cast<float4*>(Z + (long)rb_ * ldz + col) = vb;                          \
+        }                                                                                      \
+      }                                                                                        \
       if (MODE == 0 && omax) {   /* (kernel argument: uniform) max |stored value|; dot_b is free in a launch without logits */ \
         dot_b = fmaxf(fmaxf(dot_b, fmaxf(fabsf(va.x), fabsf(va.y))), fmaxf(fabsf(va.z), fabsf(va.w))); \
         dot_b = fmaxf(fmaxf(dot_b, fmaxf(fabsf(vb.x), fabsf(vb.y))), fmaxf(fabsf(vb.z), fabsf(vb.w))); \
@@ -537,6 +555,17 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
         dot_b += (vb.x > 0.f ? vb.x : 0.01f * vb.x) * w.x + (vb.y > 0.f ? vb.y : 0.01f * vb.y) * w.y + \
                  (vb.z > 0.f ? vb.z : 0.01f * vb.z) * w.z + (vb.w > 0.f ? vb.w : 0.01f * vb.w) * w.w; \
         asm volatile("" : "+v"(dot_b));                                                        \
+      }                                                                                        \
+    }                                                                                          \
+    if constexpr (MODE == 3) if (isA) {                                                        \
+      /* OR over the four lane groups in two exchanges: even groups end with row a's word, odd groups with row b's; \
+         groups 0 and 1 store them -- lanes 0..31 = rows 0..31 of the wave */                  \
+      const bool odd_ = (lk_ >> 4) & 1;                                                        \
+      unsigned keep_ = (odd_ ? wb_ : wa_) | (unsigned)__shfl_xor((int)(odd_ ? wa_ : wb_), 16, 64); \
+      keep_ |= (unsigned)__shfl_xor((int)keep_, 32, 64);                                       \
+      if (lk_ < 32) {                                                                          \
+        const int rs_ = odd_ ? rb_ : ra_;                                                      \
+        zbits[(long)(rs_ >> 5) * ldz + ((a_) * 4 + (ch_)) * 32 + (rs_ & 31)] = keep_;          \
       }                                                                                        \
     }                                                                                          \
     if (isA && (ch_) == 3 && ((a_) + 1) % cb_per_head == 0) {   /* a head is complete: reduce over the 4 lane groups */ \
@@ -572,6 +601,10 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
     __builtin_amdgcn_sched_barrier(0);                                                         \
     /* gathers of THIS chunk (issued one iteration ago): younger are the 4 stores of the previous chunk and this       \
        iteration's 3 pieces + 8 gathers; the ring needs nothing more (chunk i + 2's pieces are older still) */          \
+    if constexpr (MODE == 3) {   /* (uniform) was the previous chunk an attention chunk: one store, or four */ \
+      if ((a_) * 4 + (ch_) <= 4 * ncbA) wait_vmcnt<12>();                                      \
+      else wait_vmcnt<15>();                                                                   \
+    } else                                                                                     \
     wait_vmcnt<MODE == 0 ? 15 : 11>();                                                         \
     if constexpr (MODE == 2) {   /* every wave is done reducing the previous slice */          \
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                       \
@@ -603,7 +636,8 @@ __device__ __forceinline__ void z6w_tile(uint4* smem, float* zst, const float* e
 #undef Z6_CHUNK
 }
 
-// MODE 0 (the training forward) and MODE 1 (logits only: Z, ZB, act and omax unused).
+// MODE 0 (the training forward), MODE 3 (its bit form: zbits = the first sign-bit hole) and MODE 1 (logits only: Z, ZB,
+// act and omax unused).
 // In MODE 1 the heads are dealt to grid.y groups (few row tiles): group y computes heads [y H / gy, (y + 1) H / gy) from
 // its ncb = (H / gy) * cb_per_head column blocks; each head's logit is the sum over its own blocks, as in one group.
 template <bool ZB, int MODE = 0>
@@ -614,7 +648,7 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
                                                           long ld_add, float* __restrict__ Z, long ldz, int E,
                                                           const float* __restrict__ wA, const float* __restrict__ bA,
                                                           int H, int cb_per_head, float* __restrict__ a_out, int act,
-                                                          float* __restrict__ omax) {
+                                                          float* __restrict__ omax, unsigned* __restrict__ zbits) {
   __shared__ uint4 smem[Z6_SLOTS * Z6_CH + 512];      // the ring + fc_out_A's weight (<= 2048 floats)
   if constexpr (MODE == 1) {
     const int hg = H / (int)gridDim.y, h0 = (int)blockIdx.y * hg;
@@ -624,7 +658,7 @@ __global__ __launch_bounds__(512, 2) void edge_z6w_kernel(const float* __restric
                     Z6NoRed{});
   } else {
     z6w_tile<MODE, ZB>(smem, nullptr, e, lde, perm, Wq, ncb, Pi, dsti, Pj, srci, ld_add, Z, ldz, blockIdx.x * 256, E, wA, bA,
-                       H, cb_per_head, a_out, H, act, omax, Z6NoRed{});
+                       H, cb_per_head, a_out, H, act, omax, Z6NoRed{}, zbits);
   }
 }
 
@@ -1053,13 +1087,31 @@ static int z_groups(int row_tiles, int ncb, int unit = 1) {
   return on ? z_col_groups(row_tiles, ncb, unit) : 1;
 }
 
+// Does the per-edge launch of these dims run edge_z6w_kernel (given gathered addends, a slot permutation and an activation
+// it has): the 24-bit modes, not the few-row form (below 128 of its 256-row tiles -- the harness' shipped batch: 60
+// workgroups walking 12 blocks, 119 us -- the 128-row kernel with its column blocks dealt to grid.y groups fills the chip
+// instead), fc_out_A's weight within the kernel's LDS, 32-bit gather offsets.  hhd_logits: H * Hd of a launch that forms
+// logits, else 0.
+static bool z6w_shape(int E, int ncb, int unit_z, bool z_bf16, long hhd_logits, int n_add_rows, long ld_add) {
+  const bool few_rows = !z_bf16 && cdiv(E, 256) < 128 && z_groups(cdiv(E, 128), ncb, unit_z) > 1;
+  return mode_24bit() && edge_z6w_on() && !few_rows && hhd_logits <= 2048 && n_add_rows > 0 &&
+         (long)n_add_rows * 4 * ld_add < (1l << 32);
+}
+// ... the fp32 training forward of a scalar-attention layer [E, 2 H Hd] over N nodes, at 128 row tiles or more -- where no
+// switch (CGAT_Z_COL_GROUPS) decides between this kernel and the few-row form (layers.hip: the bit form's predicate)
+bool edge_z6w_takes(int N, int E, int H, int Hd) {
+  const long W2 = 2l * H * Hd;
+  return E > 0 && Hd % 128 == 0 && cdiv(E, 256) >= 128 &&
+         z6w_shape(E, (int)(W2 / 128), Hd / 128, false, (long)H * Hd, N, W2);
+}
+
 // We: the edge_attr slice of the stacked first-layer weight, element (out, k) at We[out * ldw + k].
 // With Pj == nullptr the kernel computes the plain product Z = e We^T + bias (Pi = bias vector or nullptr, no logits):
 // the per-node projections of the operand split.
 int edge_z_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
                   const float* Pi, const int* dsti, const float* Pj, const int* srci, long ld_add, float* Z, long ldz,
                   int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream, int act,
-                  float* omax, int z_bf16, int n_add_rows) {
+                  float* omax, int z_bf16, int n_add_rows, int z_bits) {
   if (E <= 0) return CGAT_OK;
   const int ncb = W2 / 128;
   CGAT_CHECK_ARG(!z_bf16 || (Pj != nullptr && mode_24bit() && act == CGAT_ACT_NONE && !omax),
@@ -1068,20 +1120,25 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
   if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(We, Wq, ncb, 128 * ldw, 1, ldw, stream));
   else CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * ldw, 1, ldw, 0, stream));
   CGAT_PROF(Pj ? "edge_z" : "edge_proj", stream);   // the per-edge launch / the per-node projections
-  // the six-pass per-edge launch on 256-row workgroups (edge_z6w_kernel: same arithmetic, bit-identical results)
-  // (below 128 of its 256-row tiles -- the harness' shipped batch: 60 workgroups walking 12 blocks, 119 us -- the 128-row
-  // kernel with its column blocks dealt to grid.y groups fills the chip instead: bit-identical arithmetic, see below)
-  const int unit_z = a_out ? Hd / 128 : 1;
-  const bool few_rows = !z_bf16 && cdiv(E, 256) < 128 && z_groups(cdiv(E, 128), ncb, unit_z) > 1;
-  if (mode_24bit() && Pj != nullptr && perm && (act == CGAT_ACT_NONE || act == CGAT_ACT_LEAKY) &&
-      !(omax && a_out) && edge_z6w_on() && !few_rows &&   // (the running maximum shares a register with the logits)
-      (!a_out || (long)H * Hd <= 2048) && n_add_rows > 0 && (long)n_add_rows * 4 * ld_add < (1l << 32)) {
-    if (z_bf16)
+  // the six-pass per-edge launch on 256-row workgroups (edge_z6w_kernel: same arithmetic, bit-identical results; the
+  // few-row launches take the 128-row kernel below instead: z6w_shape)
+  const bool z6w = z6w_shape(E, ncb, a_out ? Hd / 128 : 1, z_bf16 != 0, a_out ? (long)H * Hd : 0, n_add_rows, ld_add);
+  CGAT_CHECK_ARG(!z_bits || (z6w && !z_bf16 && Pj && perm && a_out && wA && act == CGAT_ACT_NONE && !omax && ld_add == ldz &&
+                             2l * n_add_rows + cdiv(E, 32) <= (long)E && (long)H * Hd == W2 / 2),
+                 "edge_z: the bit form of the training forward is edge_z6w_kernel's, with logits (edge_z6w_takes)");
+  if (z6w && Pj != nullptr && perm && (act == CGAT_ACT_NONE || act == CGAT_ACT_LEAKY) &&
+      !(omax && a_out)) {   // (the running maximum shares a register with the logits)
+    unsigned* none = nullptr;
+    if (z_bits)   // the holes behind the two half projections: rows 2 N + g of Z
+      hipLaunchKernelGGL((edge_z6w_kernel<false, 3>), dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq, ncb,
+                         Pi, dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax,
+                         reinterpret_cast<unsigned*>(Z + 2l * n_add_rows * ldz));
+    else if (z_bf16)
       hipLaunchKernelGGL(edge_z6w_kernel<true>, dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq, ncb, Pi,
-                         dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax);
+                         dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax, none);
     else
       hipLaunchKernelGGL(edge_z6w_kernel<false>, dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq, ncb, Pi,
-                         dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax);
+                         dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax, none);
     CGAT_LAUNCH_CHECK();
     return CGAT_OK;
   }
@@ -1147,7 +1204,7 @@ int edge_logits_launch(const float* e, long lde, const int* perm, const float* W
   CGAT_PROF("edge_logits", stream);
   hipLaunchKernelGGL((edge_z6w_kernel<false, 1>), dim3(cdiv(E, 256), G), dim3(512), 0, stream, e, lde, perm,
                      (const uint4*)Wq, ncb / G, Pi, dsti, Pj, srci, (long)W2, (float*)nullptr, 0l, E, wA, bA, H, Hd / 128,
-                     a_out, CGAT_ACT_NONE, (float*)nullptr);
+                     a_out, CGAT_ACT_NONE, (float*)nullptr, (unsigned*)nullptr);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }

@@ -183,7 +183,11 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
                   const float* Pi, const int* dsti, const float* Pj, const int* srci, long ld_add, float* Z, long ldz,
                   int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream,
                   int act = CGAT_ACT_NONE, float* omax = nullptr, int z_bf16 = 0,   // z_bf16: as edge_zx_launch
-                  int n_add_rows = 0);   // rows of Pi / Pj (0 = unknown: the f16x3c kernel addresses them by 32-bit offsets)
+                  int n_add_rows = 0,    // rows of Pi / Pj (0 = unknown: the f16x3c kernel addresses them by 32-bit offsets)
+                  int z_bits = 0);       // the bit form (edge_z6w_kernel<false, 3>): the attention columns leave sign words in
+                                         // the holes of rows 2 N + g of Z instead of values (layers.hip attn_z_form)
+// would the fp32 training forward of a scalar-attention layer run edge_z6w_kernel (mode, switches, shape; host only)
+bool edge_z6w_takes(int N, int E, int H, int Hd);
 // Per-head offsets of a launch whose grid.y runs over the heads of a multi-head second layer (elements of each operand;
 // w in 16-byte pieces): all zero = the single-operand launch
 struct HeadBatch {
@@ -279,9 +283,13 @@ int edge_seg_bwd_chunks(int N);
 int edge_seg_bwd_launch(const float* Z, float* gZ, long gz_block, const float* alpha, const float* gS, const float* gs,
                         const int* rowptr, const float* wA_out, int N, int H, int Hd, float* tt, float* ga, float* Gi,
                         float* partialW, float* gzmax, unsigned* mask, float* gimax, bool vec, bool zb_6, bool zb,
-                        bool rc_shape, bool have_scales, hipStream_t stream);
+                        bool rc_shape, bool have_scales, hipStream_t stream,
+                        const int* bits_src = nullptr);   // the bit form of the saved buffer (segbwd.hip seg_bwd_attb_kernel):
+                                                          // the source node of every slot; Z holds no attention values
 // debug: mask[perm[t]][c] = (Z[t][c] > 0), the saved pre-activations' signs in original edge order
-int attn_signs_launch(const float* Z, const int* perm, long E, int W2, uint8_t* mask, hipStream_t stream);
+// (zbits: the attention half from the stored sign words of the bit form)
+int attn_signs_launch(const float* Z, const int* perm, long E, int W2, uint8_t* mask, hipStream_t stream,
+                      const unsigned* zbits = nullptr);
 // ---- split-bf16 backward products over gZ, edgebwd.hip ----
 // The pre-activation gradient of the scalar-attention layer is never stored when its consumers can rebuild it
 // (edge_seg_bwd_kernel step 3, segbwd.hip): for destination-sorted slot t and column col of the stacked hidden layer
@@ -305,13 +313,24 @@ bool edge_mma_bf16();
 static inline bool edge_rc_shape(int Ce, int H, int Hd) { return Ce == 128 && H > 0 && Hd > 0 && Hd % 128 == 0; }
 // operand element (t, 128 a + j) at gZ[t * ldg + a * gzb + j]: (128, E*128) = column-blocked, (W2, 128) = row-major;
 // with rc != null the operand is rebuilt from *rc instead (gZ, ldg, gzb unused)
+// The edge part of grad fc_out_A under the bit form of the saved buffer: the reducer of the
+// bit-plane form adds sum_k We[col, k] u[col, k] (We: the edge_attr slice of the stacked weight, leading dimension ldw)
+// to out[col] -- through part, 4 H Hd doubles of scratch, in a fixed order
+struct GwTe {
+  const float* We;
+  long ldw;
+  double* part;
+  float* out;
+};
+bool edge_gw_bitplane_layer(int H, int Hd);   // mode and shape of the bit-plane form for a scalar-attention layer
 bool edge_gw_fast(int Ce, int W2, long ldg, long gzb, const void* gZ);
 size_t edge_gw_ws_floats(int E, int W2);
 int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde, const int* perm, int E, int W2,
                    float* ws, float* out, long ldo, hipStream_t stream, const float* gmax = nullptr,
                    const float* emax = nullptr,            // device maxima of |gZ| and |e| -> fp16 form in the f16x3 mode
                    const EdgeRC* rc = nullptr,
-                   bool force_six = false);                // debug: this launch keeps the six-pass form on every column
+                   bool force_six = false,                 // debug: this launch keeps the six-pass form on every column
+                   const GwTe* te = nullptr);
 // the bit-plane form of the attention half (edge_gw_kernel<6, true, true>): would this launch take it / debug: never take it
 bool edge_gw_takes_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six = false);
 bool edge_gw_force_six(bool on);   // the process-wide switch; returns the previous setting

@@ -202,11 +202,14 @@ static int g_edge_storage = -1;
 static int edge_storage() {
   if (g_edge_storage < 0) {
     const char* e = getenv("CGAT_EDGE_STORAGE");
-    g_edge_storage = (e && !strcmp(e, "bf16")) ? 1 : (e && !strcmp(e, "f32+gz")) ? 2 : (e && !strcmp(e, "bf16-mma")) ? 3 : 0;
+    g_edge_storage = (e && !strcmp(e, "bf16")) ? 1 : (e && !strcmp(e, "f32+gz")) ? 2 : (e && !strcmp(e, "bf16-mma")) ? 3 :
+                     (e && !strcmp(e, "f32+za")) ? 4 : 0;
   }
   return g_edge_storage;
 }
-extern "C" void cgat_set_edge_storage(int32_t mode) { g_edge_storage = (mode >= 1 && mode <= 3) ? mode : 0; }
+extern "C" void cgat_set_edge_storage(int32_t mode) { g_edge_storage = (mode >= 1 && mode <= 4) ? mode : 0; }
+// mode 4 ("f32+za"): fp32 with the attention pre-activations stored at every shape -- mode 0 without the bit form of the
+// saved buffer (attn_z_form), the A/B reference of its tests as "f32+gz" is for the stored gZ
 // mode 3 ("bf16-mma"): bf16 storage of Z AND one-pass bf16 operands in the two per-edge backward products (edgebwd.hip)
 static bool edge_bf16_storage() { return edge_storage() == 1 || edge_storage() == 3; }
 bool edge_mma_bf16() { return edge_storage() == 3; }
@@ -260,7 +263,19 @@ struct ZForm {
   bool fused_z;   // Z and the attention logits from one fused split-bf16 per-edge launch (else: generic GEMM + row-dot)
   bool bf16;      // Z stored as bf16 (edge-storage mode "bf16"): by edge_zx in the f16x3 mode, ...
   bool bf16_six;  // ... by the six-pass per-edge kernel otherwise
+  bool bits;      // the bit form of the saved buffer (attn_bit_form_dims below, on 16-byte aligned operands)
 };
+// The bit form: the forward keeps no attention pre-activations Z_A.  The attention columns of the
+// saved buffer's rows -- one hole of H * Hd floats per row, row stride W2 as ever -- hold instead
+//   rows n < N: Pi_A[n, :] (bias included) | rows N + n: Pj_A[n, :] | rows 2 N + g: the sign words of edge rows 32 g .. 32 g + 31
+// from which the backward forms everything it took from Z_A.  Taken where the forward runs
+// edge_z6w_kernel in fp32 storage and the backward rebuilds gZ with the bit-plane form of grad W_e (whose column sums give
+// the edge part of grad fc_out_A), and the 2 N + ceil(E / 32) holes exist.  Dims, mode and storage alone:
+static bool attn_bit_form_dims(const AttnDims& d) {
+  return mode_24bit() && edge_storage() == 0 && d.N > 0 && d.E > 0 && d.C == 128 && edge_rc_shape(d.Ce, d.H, d.Hd) &&
+         d.Hd == 256 && edge_z6w_takes(d.N, d.E, d.H, d.Hd) && edge_gw_bitplane_layer(d.H, d.Hd) &&
+         2l * d.N + cdiv(d.E, 32) <= (long)d.E;
+}
 static ZForm attn_z_form(const AttnDims& d, const float* e, const float* x, const float* Z, const float* wA, const void* ws) {
   ZForm z;
   z.zx = d.N > 0 && edge_zx_fast(d.C, d.Ce, d.W2, d.H, d.Hd, d.W2, d.W2, e, x, ws, Z, wA) &&
@@ -269,6 +284,9 @@ static ZForm attn_z_form(const AttnDims& d, const float* e, const float* x, cons
   z.fused_z = per_edge && !z.zx;
   z.bf16_six = attn_bf16(d) && per_edge && !mode_f16();
   z.bf16 = (attn_bf16(d) && z.zx) || z.bf16_six;
+  // (fused_z: e, the workspace, the saved buffer and fc_out_A's weight are 16-byte aligned -- what the backward's vector
+  // form asks of the same four)
+  z.bits = z.fused_z && !z.bf16 && attn_bit_form_dims(d);
   return z;
 }
 
@@ -294,6 +312,7 @@ struct AttnFwdRoute {
   bool fused_infer;   // the no-grad forward on the logits launch + the fused message / weighted-sum launch
   bool zx, fused_z;   // the per-edge phase of the training forward (ZForm)
   bool z_bf16;
+  bool z_bits;        // the bit form of the saved buffer (ZForm)
   bool proj_fast;     // the node projections on the per-edge kernel (else: the GEMM pair)
   bool out_fast;      // fc_out_M as H * Hd / 128 accumulating K = 128 launches of the dense-layer kernel
   bool out_one;       // ... as one K = H * Hd launch (attn_out_one_shape)
@@ -306,7 +325,7 @@ static AttnFwdRoute attn_fwd_route(bool dry, const AttnDims& d, bool infer, cons
   r.out_fast = mode_split() && d.C == 128 && d.Hd % 128 == 0;
   if (dry) return r;
   const ZForm z = attn_z_form(d, e, x, saved, p->A_out_w, ws);
-  r.zx = z.zx; r.fused_z = z.fused_z; r.z_bf16 = z.bf16;
+  r.zx = z.zx; r.fused_z = z.fused_z; r.z_bf16 = z.bf16; r.z_bits = z.bits;
   // (a few hundred atoms: the generic branch, whose products run as 16 x 16 wave tiles -- rowprog.hip -- instead of
   // five 256-row workgroups streaming the whole weight image: 86 -> ~10 us per projection at 1 280 atoms)
   r.proj_fast = d.N > rowprog_max_rows() && edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, ws, ws, ws, ws);
@@ -323,6 +342,7 @@ struct AttnBwdRoute {
   bool vec;            // the segment kernel's 16-byte loads
   bool have_scales;    // f16x3: maxima of gZ and edge_attr -> the per-edge products on two fp16 planes
   bool z_bf16, z_bf16_six;   // how the forward stored Z (ZForm)
+  bool z_bits;         // ... in the bit form: no attention values, the sign words and the two half projections
   bool out_fast;       // fc_out_M's input gradients on the dense-layer kernel, its weight gradients in one batched launch
   bool out_heads_one;  // ... the input gradients of all heads in one launch pair (round 6)
 };
@@ -342,6 +362,7 @@ static AttnBwdRoute attn_bwd_route(bool dry, const AttnDims& d, const cgat_attn_
   r.have_scales = r.vec && mode_f16() && d.Ce == 128 && aligned16(e);
   const ZForm z = attn_z_form(d, e, x, saved, p->A_out_w, ws);
   r.z_bf16 = z.bf16; r.z_bf16_six = z.bf16_six;
+  r.z_bits = z.bits;   // (implies rc and vec: the same shapes, modes and aligned operands)
   return r;
 }
 
@@ -420,12 +441,17 @@ static int attn_fwd_edges_infer(Ctx& c, const AttnFwd& f) {
 // Z[t] = W_e e[perm[t]] + Pi[dst[t]] + Pj[src[t]]      (x_i = x[edge_index[1]], x_j = x[edge_index[0]])
 // and the attention logits a[t,h] = fc_out_A(leaky(zA)): one fused split-bf16 kernel at the benchmark widths,
 // the generic GEMM + row-dot otherwise (and in the f32 arithmetic mode); then softmax and the weighted sum
+// The form the last training forward left its saved buffer in, for the debug reader of the signs: that entry sees the
+// buffer alone, not the operands whose alignment decided the form.
+static const float* g_fwd_saved = nullptr;
+static bool g_fwd_saved_bits = false;
 static int attn_fwd_edges_train(Ctx& c, const AttnFwd& f) {
   const AttnDims& d = f.d;
   const cgat_plan* plan = f.plan;
   const cgat_attn_params* p = f.p;
   const AttnFwdRoute& r = f.r;
   const AttnSaved& sv = f.sv;
+  if (!c.dry) { g_fwd_saved = sv.Z; g_fwd_saved_bits = r.z_bits; }
   if (!c.dry && edge_bf16_storage() && !r.z_bf16 && d.N > 0 && d.E > 0) {
     cgat_set_error("nodes_attention_forward: edge storage \"bf16\" is set but this layer (C %d, Ce %d, H %d, Hd %d, arithmetic "
                    "mode %d) has no bf16 form -- refusing to run it in fp32 storage under that label", d.C, d.Ce, d.H, d.Hd,
@@ -438,9 +464,16 @@ static int attn_fwd_edges_train(Ctx& c, const AttnFwd& f) {
                        plan->dst_sorted, plan->src_sorted, d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, f.a, c.s,
                        zb));
   } else if (r.fused_z) {
+    if (r.z_bits) {   // the attention halves of the two projections into the holes of rows 0 .. 2 N - 1 (ZForm)
+      Copy2DJobs j;
+      j.n = 2;
+      j.job[0] = {f.Pi, d.W2, sv.Z, d.W2, d.N, d.HHd};
+      j.job[1] = {f.Pj, d.W2, sv.Z + (size_t)d.N * d.W2, d.W2, d.N, d.HHd};
+      RUN(copy2d_multi_launch(j, c.s));
+    }
     RUN(edge_z_launch(f.e, d.Ce, plan->dst_perm, f.Wcat + d.C, d.D, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj,
                       plan->src_sorted, d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, f.a, c.s, CGAT_ACT_NONE,
-                      nullptr, zb, d.N));
+                      nullptr, zb, d.N, r.z_bits ? 1 : 0));
   } else {
     GemmParams g = gemm_params(d.E, d.W2, d.Ce, f.e, d.Ce, f.Wcat + d.C, d.D, sv.Z, d.W2);
     g.a_rgather = plan->dst_perm;
@@ -534,6 +567,8 @@ struct EdgeTail {
   const EdgeRC* rc;      // gZ was not stored; the per-edge launches and the source-side sum rebuild its rows (kernels.h)
   bool node_scales;      // stored gZ: form the node-side maxima by three passes (the rebuilt path's kernels fold them in)
   bool gw_force_six;     // debug entry only: grad W_e's launch keeps its six-pass form
+  GwTe te;               // te.out != nullptr (the bit form of the saved buffer): grad W_e's reducer adds the edge part of
+                         // grad fc_out_A to te.out (edgebwd.hip)
   const float *x, *e;
   float *g_x, *g_e;
 };
@@ -659,9 +694,10 @@ static int tail_edge_ge(Ctx& c, const cgat_plan* plan, const AttnDims& d, const 
 static int tail_edge_gw(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
   if (r.gw == PRODUCT_LAUNCH) {
     RUN(edge_gw_launch(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.e, d.Ce, plan->dst_perm, d.E, d.W2, t.gw_ws, t.gWcat + d.C, d.D, c.s,
-                       t.scales, t.scales ? t.scales + 1 : nullptr, t.rc, t.gw_force_six));
+                       t.scales, t.scales ? t.scales + 1 : nullptr, t.rc, t.gw_force_six, t.te.out ? &t.te : nullptr));
     return CGAT_OK;
   }
+  CGAT_CHECK_ARG(!t.te.out, "nodes_attention_backward: the bit form of the saved buffer needs grad W_e's per-edge launch");
   GemmParams g = gemm_params(d.W2, d.Ce, d.E, t.gZ.ptr, t.gZ.ld, t.e, d.Ce, t.gWcat + d.C, d.D);
   g.a_block = tail_xblock(d, t);
   g.a_kmajor = 1; g.b_kmajor = 1;
@@ -807,6 +843,11 @@ static int attn_bwd_segments(Ctx& c, const AttnBwd& b) {
       cgat_set_error("nodes_attention_backward: edge storage \"bf16\" is set but this layer has no bf16 form");
       return CGAT_ERR_UNSUPPORTED;
     }
+    CGAT_CHECK_ARG(!r.z_bits || (r.rc && r.vec), "nodes_attention_backward: the bit form of the saved buffer without its route");
+    // (attn_bwd_tail lends tt to grad W_e's reducer as 4 H Hd doubles)
+    CGAT_CHECK_ARG(!r.z_bits || ((size_t)d.E * d.H * sizeof(float) >= (size_t)4 * d.HHd * sizeof(double) &&
+                                 (((uintptr_t)b.tt) & 7) == 0),
+                   "nodes_attention_backward: the bit form needs %d doubles of scratch in tt", 4 * d.HHd);
     if (r.rc)
       CGAT_CHECK_ARG(r.vec && aligned16(b.e),
                      "nodes_attention_backward: saved, edge_attr and MH_A.fc_out.weight must be 16-byte aligned at these widths");
@@ -816,7 +857,7 @@ static int attn_bwd_segments(Ctx& c, const AttnBwd& b) {
     float* gimax = (r.have_scales && r.rc) ? b.scales + 2 : nullptr;
     CGAT_TRY(edge_seg_bwd_launch(b.sv.Z, b.gZ, b.gzb, b.sv.alpha, b.gS, b.gs, b.plan->dst_rowptr, b.p->A_out_w, d.N, d.H, d.Hd,
                                  b.tt, b.ga, b.Gi, b.partial, gzmax, mask, gimax, r.vec, r.z_bf16_six, r.z_bf16, r.rc,
-                                 r.have_scales, c.s));
+                                 r.have_scales, c.s, r.z_bits ? b.plan->src_sorted : nullptr));
   }
   if (r.have_scales) RUN(absmax_rows128_launch(b.e, d.Ce, d.E, b.scales + 1, c.s));
   if (r.have_scales && r.rc && d.C == 128 && aligned16(b.x)) RUN(absmax_rows128_launch(b.x, d.C, d.N, b.scales + 4, c.s));
@@ -833,6 +874,9 @@ static EdgeTail attn_bwd_tail(const AttnBwd& b) {
   t.scales = b.r.have_scales ? b.scales : nullptr;
   t.rc = b.r.rc ? &b.rc : nullptr;
   t.x = b.x; t.e = b.e; t.g_x = b.g_x; t.g_e = b.g_e;
+  // (tt, E * H floats on a 256-byte boundary, is dead behind the softmax backward: the 4 H Hd doubles of the reducer's
+  // quarter sums fit from E = 2048 on -- attn_bwd_segments checks both)
+  if (b.r.z_bits && b.gr) t.te = {b.Wcat + b.d.C, b.d.D, reinterpret_cast<double*>(b.tt), b.gr->A_out_w};   // (no gr: the route query)
   return t;
 }
 
@@ -1092,7 +1136,18 @@ extern "C" int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cga
     cgat_set_error("debug_nodes_attention_signs: fp32 edge storage only");
     return CGAT_ERR_UNSUPPORTED;
   }
-  return attn_signs_launch(saved, plan->dst_perm, (long)d.E, d.W2, mask, (hipStream_t)stream);
+  // The bit form: as the forward that filled THIS buffer decided it on its real operands (recorded there); for any other
+  // buffer, as a forward on 16-byte aligned x and edge_attr with this buffer and this fc_out_A weight decides it.
+  const bool bits = saved == g_fwd_saved ? g_fwd_saved_bits : attn_z_form(d, saved, saved, saved, p->A_out_w, saved).bits;
+  return attn_signs_launch(saved, plan->dst_perm, (long)d.E, d.W2, mask, (hipStream_t)stream,
+                           bits ? reinterpret_cast<const unsigned*>(saved + 2 * (size_t)d.N * d.W2) : nullptr);
+}
+
+// Does the training forward of this layer keep its saved buffer in the bit form (16-byte aligned operands assumed)
+extern "C" int32_t cgat_nodes_attention_bit_form(const cgat_plan* plan, const cgat_attn_params* p) {
+  if (attn_check(plan, p) != CGAT_OK) return 0;
+  const void* al = (const void*)256;
+  return attn_z_form(attn_dims(plan, p), (const float*)al, (const float*)al, (const float*)al, (const float*)al, al).bits ? 1 : 0;
 }
 
 // ---- debug: one per-edge product of the tail alone, on caller-supplied ingredients of the rebuilt gZ rows (struct EdgeRC,

@@ -456,19 +456,111 @@ __global__ __launch_bounds__(256, 8) void seg_bwd_att_kernel(const float* __rest
   }
 }
 
+// The attention half under the bit form of the saved buffer (the forward is edge_z6w_kernel<false, 3>):
+// no Z_A exists.  The attention columns of the buffer's rows hold, instead,
+//   rows n < N        Pi_A[n, :]   the attention half of the x_i projection, bias included   (leading dimension W2)
+//   rows N + n        Pj_A[n, :]   ... of the x_j projection
+//   rows 2 N + g      the sign words of edge rows 32 g .. 32 g + 31, word-major: word w of row t at [w * 32 + (t & 31)],
+//                     bit i of word w = (Z_A[t, 32 w + i] > 0)
+// Per (node, four columns) wA and Pi_A[n] are loaded once; per edge of the segment, in ascending order, the mask word,
+// g_a[t, h], the source node and four floats of its Pj_A row (a crystal's rows: L2, as in the forward's gathers).
+//   * mask: the attention words of the backward's sign mask, in the layout EdgeRC expects -- the loaded word as it is;
+//   * Gi: seg_bwd_att_kernel's operations in its order, g = gav * wv * d; gi += g: the same bits;
+//   * partialW: sum_t (gav d) (Pi_A + Pj_A), the node part T_ij of grad fc_out_A; the edge part
+//     T_e = sum_k W_e u is added by edge_gw_bit_reduce_kernel from the column sums it holds.  LeakyReLU(z) = d z and
+//     z = W_e e + Pi + Pj; no division by wA anywhere, so a zero entry of wA keeps its true gradient.
+__global__ __launch_bounds__(256, 8) void seg_bwd_attb_kernel(const float* __restrict__ saved, const float* __restrict__ ga,
+                                                              const int* __restrict__ rowptr, const int* __restrict__ srcs,
+                                                              const float* __restrict__ wA_out, int N, int H,
+                                                              float* __restrict__ Gi, float* __restrict__ partialW,
+                                                              unsigned* __restrict__ mask) {
+  constexpr int Hd = 256;
+  extern __shared__ float pw[];                    // [HHd] per-column partial sums
+  const int HHd = H * Hd, W2 = 2 * HHd;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const float* PiA = saved;
+  const float* PjA = saved + (long)N * W2;
+  const unsigned* zb = reinterpret_cast<const unsigned*>(saved + 2l * N * W2);
+  for (int c = tid; c < HHd; c += 256) pw[c] = 0.f;
+  __syncthreads();
+  const int n0 = blockIdx.x * SEGB_NODES, n1 = min(N, n0 + SEGB_NODES);
+  for (int n = n0; n < n1; ++n) {
+    const int r0 = __builtin_amdgcn_readfirstlane(rowptr[n]), r1 = __builtin_amdgcn_readfirstlane(rowptr[n + 1]);
+    if (r1 == r0) {  // no incoming edge: zero row of the segment sum (both halves)
+      for (int c = tid; c < W2; c += 256) Gi[(long)n * W2 + c] = 0.f;
+      continue;
+    }
+    for (int c4 = tid; c4 < HHd / 4; c4 += 256) {
+      const int col = 4 * c4;
+      const int h = col / Hd;
+      const int bit = col & 31;
+      const unsigned* zw = zb + (col >> 5) * 32;
+      const unsigned woff = (unsigned)(col >> 5) * 4u;
+      const float4 wv = *reinterpret_cast<const float4*>(wA_out + col);
+      const float4 pi = *reinterpret_cast<const float4*>(PiA + (long)n * W2 + col);
+      float4 gi = make_float4(0.f, 0.f, 0.f, 0.f), ps = gi;
+      for (int tb = r0; tb < r1; tb += 4) {
+        unsigned m[4];
+        float cf[4];
+        int sn[4];
+        float4 pj[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int t = tb + u < r1 ? tb + u : r1 - 1;
+          m[u] = zw[(long)(t >> 5) * W2 + (t & 31)];
+          cf[u] = ga[(long)t * H + h];
+          sn[u] = srcs[t];   // (wave-uniform address: t is)
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)   // (32-bit byte offsets: N * W2 * 4 < 2^32 where the forward takes this form)
+          pj[u] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(PjA) +
+                                                   ((unsigned)sn[u] * (unsigned)W2 + (unsigned)col) * 4u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int t = tb + u;
+          if (t < r1) {
+            const unsigned mb = m[u] >> bit;
+            const float4 d = make_float4((mb & 1u) ? 1.f : 0.01f, (mb & 2u) ? 1.f : 0.01f, (mb & 4u) ? 1.f : 0.01f,
+                                         (mb & 8u) ? 1.f : 0.01f);
+            const float gav = cf[u];
+            const float4 g = make_float4(gav * wv.x * d.x, gav * wv.y * d.y, gav * wv.z * d.z, gav * wv.w * d.w);
+            ps.x += (gav * d.x) * (pi.x + pj[u].x); ps.y += (gav * d.y) * (pi.y + pj[u].y);
+            ps.z += (gav * d.z) * (pi.z + pj[u].z); ps.w += (gav * d.w) * (pi.w + pj[u].w);
+            // (a wave-uniform row base and a 32-bit lane offset, laundered so that no 64-bit lane address per unrolled
+            // row is kept across the loop: those spilled to scratch)
+            if ((lane & 7) == 0) {
+              unsigned wo = woff;
+              asm volatile("" : "+v"(wo));
+              *reinterpret_cast<unsigned*>(reinterpret_cast<char*>(mask + (long)t * (W2 >> 5)) + wo) = m[u];
+            }
+            gi.x += g.x; gi.y += g.y; gi.z += g.z; gi.w += g.w;
+          }
+        }
+      }
+      *reinterpret_cast<float4*>(Gi + (long)n * W2 + col) = gi;
+      pw[col] += ps.x; pw[col + 1] += ps.y; pw[col + 2] += ps.z; pw[col + 3] += ps.w;
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < HHd; c += 256) partialW[(long)blockIdx.x * HHd + c] = pw[c];
+}
+
 // ---- debug: the sign pattern of the saved pre-activations in original edge order (include/cgat_hip.h) ----
+// zbits (the bit form of the saved buffer): the attention columns' signs are the stored words (see seg_bwd_attb_kernel)
 __global__ void attn_signs_kernel(const float* __restrict__ Z, const int* __restrict__ perm, long E, int W2,
-                                  uint8_t* __restrict__ mask) {
+                                  uint8_t* __restrict__ mask, const unsigned* __restrict__ zbits) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= E * W2) return;
   const long t = i / W2;
   const int c = (int)(i - t * W2);
-  mask[(long)perm[t] * W2 + c] = Z[i] > 0.f ? 1 : 0;
+  if (zbits && c < W2 / 2) mask[(long)perm[t] * W2 + c] = (zbits[(t >> 5) * W2 + (c >> 5) * 32 + (t & 31)] >> (c & 31)) & 1u;
+  else mask[(long)perm[t] * W2 + c] = Z[i] > 0.f ? 1 : 0;
 }
-int attn_signs_launch(const float* Z, const int* perm, long E, int W2, uint8_t* mask, hipStream_t stream) {
+int attn_signs_launch(const float* Z, const int* perm, long E, int W2, uint8_t* mask, hipStream_t stream,
+                      const unsigned* zbits) {
   const long n = E * W2;
   if (n == 0) return CGAT_OK;
-  hipLaunchKernelGGL(attn_signs_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, Z, perm, E, W2, mask);
+  hipLaunchKernelGGL(attn_signs_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, Z, perm, E, W2, mask, zbits);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
@@ -479,13 +571,18 @@ int edge_seg_bwd_chunks(int N) { return cdiv(N > 0 ? N : 1, SEGB_NODES); }
 template <bool ZB>
 static int seg_bwd_three_launch(const float* Z, const float* alpha, const float* gS, const float* gs, const int* rowptr,
                                 const float* wA_out, int N, int H, float* tt, float* ga, float* Gi, float* partialW,
-                                float* gzmax, unsigned* mask, float* gimax, hipStream_t stream) {
+                                float* gzmax, unsigned* mask, float* gimax, hipStream_t stream,
+                                const int* srcs = nullptr) {   // srcs: the bit form of the saved buffer (seg_bwd_attb_kernel)
   const int chunks = edge_seg_bwd_chunks(N);
   hipLaunchKernelGGL(seg_bwd_msg_kernel<ZB>, dim3((unsigned)cdiv((long)N * H, 4)), dim3(256), 0, stream, Z, alpha, gS, gs, rowptr,
                      N, H, tt, Gi, gzmax, mask, gimax);
   CGAT_LAUNCH_CHECK();
   hipLaunchKernelGGL(seg_bwd_soft_kernel, dim3(chunks), dim3(256), 0, stream, alpha, tt, rowptr, N, H, ga);
   CGAT_LAUNCH_CHECK();
+  if (srcs)
+    hipLaunchKernelGGL(seg_bwd_attb_kernel, dim3(chunks), dim3(256), (size_t)H * 256 * sizeof(float), stream, Z, ga, rowptr,
+                       srcs, wA_out, N, H, Gi, partialW, mask);
+  else
   hipLaunchKernelGGL(seg_bwd_att_kernel<ZB>, dim3(chunks), dim3(256), (size_t)H * 256 * sizeof(float), stream, Z, ga, rowptr,
                      wA_out, N, H, Gi, partialW, gzmax, mask, gimax);
   CGAT_LAUNCH_CHECK();
@@ -495,8 +592,10 @@ static int seg_bwd_three_launch(const float* Z, const float* alpha, const float*
 int edge_seg_bwd_launch(const float* Z, float* gZ, long gz_block, const float* alpha, const float* gS, const float* gs,
                         const int* rowptr, const float* wA_out, int N, int H, int Hd, float* tt, float* ga, float* Gi,
                         float* partialW, float* gzmax, unsigned* mask, float* gimax, bool vec, bool zb_6, bool zb,
-                        bool rc_shape, bool have_scales, hipStream_t stream) {
+                        bool rc_shape, bool have_scales, hipStream_t stream, const int* bits_src) {
   CGAT_CHECK_ARG(H <= 16, "nodes_attention_backward: more than 16 heads");
+  CGAT_CHECK_ARG(!bits_src || (vec && mask && Hd == 256 && !zb && !zb_6 && !have_scales),
+                 "nodes_attention_backward: the bit form of the saved buffer is the three-kernel fp32 route's");
   CGAT_PROF("edge_seg_bwd", stream);
   if (have_scales) CGAT_TRY(fill_launch(gzmax, 0.f, 8, stream));   // the maxima gzmax[0..7] the kernels and the caller fold into
   const int chunks = edge_seg_bwd_chunks(N);
@@ -510,7 +609,8 @@ int edge_seg_bwd_launch(const float* Z, float* gZ, long gz_block, const float* a
     hipLaunchKernelGGL((edge_seg_bwd_kernel<true, true>), dim3(chunks), dim3(256), shm, stream, Z, gZ, gz_block, alpha, gS,
                        gs, rowptr, wA_out, N, H, Hd, tt, ga, Gi, partialW, gzmax, mask, gimax);
   } else if (vec && mask && Hd == 256) {
-    return seg_bwd_three_launch<false>(Z, alpha, gS, gs, rowptr, wA_out, N, H, tt, ga, Gi, partialW, gzmax, mask, gimax, stream);
+    return seg_bwd_three_launch<false>(Z, alpha, gS, gs, rowptr, wA_out, N, H, tt, ga, Gi, partialW, gzmax, mask, gimax, stream,
+                                       bits_src);
   } else if (vec)
     hipLaunchKernelGGL(edge_seg_bwd_kernel<true>, dim3(chunks), dim3(256), shm, stream, Z, gZ, gz_block, alpha, gS, gs,
                        rowptr, wA_out, N, H, Hd, tt, ga, Gi, partialW, gzmax, mask, gimax);

@@ -107,6 +107,15 @@ def nodes_attention_route(N, E, C_, Ce, H, Hd, backward=False):
     return {n for i, n in enumerate(ROUTE_BITS["backward" if backward else "forward"]) if mask >> i & 1}
 
 
+def nodes_attention_bit_form(N, E, C_, Ce, H, Hd):
+    """Does the training forward of the scalar-attention layer keep its saved buffer in the bit form at these shapes, in
+    the current arithmetic and edge-storage modes, for 16-byte aligned operands (cgat_nodes_attention_bit_form; host only):
+    sign words and the two half projections in place of the attention pre-activations."""
+    plan = _lib.Plan(N, E, None, None, None, None, None, None)
+    p = _lib.AttnParams(C_, Ce, H, Hd, *([None] * 8))
+    return bool(lib.cgat_nodes_attention_bit_form(C.byref(plan), C.byref(p)))
+
+
 # bit i of cgat_debug_edge_hidden_route's mask (include/cgat_hip.h)
 EDGE_HIDDEN_ROUTE_BITS = {
     "forward": ("fast",),

@@ -1275,12 +1275,14 @@ def set_edge_storage(mode):
     tolerance 1e-2.  The forward product keeps its six passes: on bf16 operands the pre-activations move by ~3e-3 of
     their scale, 0.3 % of the LeakyReLU derivatives land on the other side, and the gradients of edge_attr and of the
     attention network's first layer came out 1.6 % ... 5.7 % off (tools/bf16mma_probe.py; measured 775 ms instead of 830
-    per 64 M-edge step) -- outside the mode's stated tolerance."""
-    lib.cgat_set_edge_storage({"f32": 0, "bf16": 1, "f32+gz": 2, "bf16-mma": 3}[mode])
+    per 64 M-edge step) -- outside the mode's stated tolerance.
+    "f32+gz" / "f32+za": fp32 with the backward's gZ stored / with the attention pre-activations stored at every shape --
+    the A/B references of the rebuilt-gZ route and of the bit form of the saved buffer (debug.nodes_attention_bit_form)."""
+    lib.cgat_set_edge_storage({"f32": 0, "bf16": 1, "f32+gz": 2, "bf16-mma": 3, "f32+za": 4}[mode])
 
 
 def get_edge_storage():
-    return {0: "f32", 1: "bf16", 2: "f32+gz", 3: "bf16-mma"}[lib.cgat_get_edge_storage()]
+    return {0: "f32", 1: "bf16", 2: "f32+gz", 3: "bf16-mma", 4: "f32+za"}[lib.cgat_get_edge_storage()]
 
 
 class _storage_of:

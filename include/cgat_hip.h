@@ -218,9 +218,21 @@ uint32_t cgat_debug_nodes_attention_route(const cgat_plan* plan, const cgat_attn
  * [0, H*Hd)) and MH_M ([H*Hd, 2*H*Hd)) of CGAT/CGAT.py:96,105-108, in ORIGINAL edge order.  LeakyReLU's derivative
  * jumps at 0 (CGAT.py:95, slope 0.01), so two correct fp32 evaluations can disagree on elements with |z| ~ 1e-7 max|z|
  * and then differ in every upstream gradient by a finite amount; the parity tests force the oracle's derivative
- * pattern to THIS one and compare at the flat tolerance.  fp32 edge storage only. */
+ * pattern to THIS one and compare at the flat tolerance.  fp32 edge storage only.  Under the bit form of the saved buffer
+ * (cgat_nodes_attention_bit_form) the attention half is read from the stored sign words, the message half from Z_M; which
+ * form `saved` is in is what the last cgat_nodes_attention_forward recorded if it filled this buffer, else what a forward
+ * on 16-byte aligned x and edge_attr would choose. */
 int cgat_debug_nodes_attention_signs(const cgat_plan* plan, const cgat_attn_params* p, const float* saved,
                                      uint8_t* mask /* out [E, 2*H*Hd] */, void* stream);
+
+/* 1 if cgat_nodes_attention_forward keeps this layer's saved buffer in the BIT FORM (for 16-byte aligned operands; host
+ * only): no attention pre-activations are stored.  The buffer keeps its size and the places of Z_M, alpha, S and ssum; the
+ * H*Hd attention columns of its rows hold the attention halves of the two per-node projections (rows [0, N) and
+ * [N, 2N)) and, from row 2N on, the sign words of 32 edge rows each.  Taken in the 24-bit arithmetic modes under edge
+ * storage 0 where the forward runs its 256-row per-edge kernel (at least 128 row tiles, H*Hd <= 2048), Hd == 256 and
+ * 2N + ceil(E/32) <= E; the backward then forms grad MH_A.fc_out.weight from those and the column sums of grad W_e's
+ * product.  Everything else the layer returns keeps its bits.  0 everywhere else, where nothing changes. */
+int32_t cgat_nodes_attention_bit_form(const cgat_plan* plan, const cgat_attn_params* p);
 
 /* Debug / parity instrumentation (tests only): grad edge_attr's product  out[t, :] = gZ[t, :] W_e  ALONE, with the rows of
  * gZ rebuilt from caller-supplied ingredients exactly as the backward of cgat_nodes_attention_forward rebuilds them,
@@ -545,8 +557,10 @@ int cgat_rowprog_run(const cgat_rowprog* prog, uint32_t* sync_words, void* strea
  *       CGAT_ERR_UNSUPPORTED for a layer without that form (other widths, the f32 mode) instead of running it in fp32
  *       storage under the bf16 label (round 4's library ignored the switch there);
  *   2 = fp32 Z with gZ stored in backward (round 1's path, 6 KB more workspace per edge): the A/B reference of the tests.
- * A backward call must run under the mode its forward ran under.  Env CGAT_EDGE_STORAGE = bf16 | f32+gz sets the start
- * value. */
+ *   4 = fp32 with the attention pre-activations stored at every shape ("f32+za"): mode 0 without the bit form of the saved
+ *       buffer (cgat_nodes_attention_bit_form), its A/B reference; identical to mode 0 wherever that form is not taken.
+ * A backward call must run under the mode its forward ran under.  Env CGAT_EDGE_STORAGE = bf16 | f32+gz | bf16-mma |
+ * f32+za sets the start value. */
 void cgat_set_edge_storage(int32_t mode);
 int32_t cgat_get_edge_storage(void);
 
