@@ -17,6 +17,7 @@ from .ops import get_bilinear_mode, set_bilinear_mode, set_validate_indices, set
 from .ops import set_fused_inference, get_fused_inference
 from .ops import set_fused_edge_combine, get_fused_edge_combine
 from .ops import set_fused_attention_dropout, get_fused_attention_dropout
+from .ops import IndexedEdgeAttr, set_indexed_edge_attr, get_indexed_edge_attr
 from .trainer import DataParallelTrainer, Normalizer
 from .chunked import set_max_edges_per_pass
 from .capture import GraphedStep
@@ -28,4 +29,5 @@ __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAtt
            "FusedSGD", "FusedAdam", "L1Loss", "MSELoss", "criterion_with_metrics", "set_bilinear_mode", "get_bilinear_mode",
            "set_validate_indices", "DataParallelTrainer", "Normalizer", "set_max_edges_per_pass",
            "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "set_fused_edge_combine",
-           "get_fused_edge_combine", "set_fused_attention_dropout", "get_fused_attention_dropout", "GraphedStep", "debug"]
+           "get_fused_edge_combine", "set_fused_attention_dropout", "get_fused_attention_dropout", "IndexedEdgeAttr", "set_indexed_edge_attr",
+           "get_indexed_edge_attr", "GraphedStep", "debug"]

@@ -133,6 +133,10 @@ PROTOTYPES = {
     "cgat_nodes_attention_bit_form": (C.c_int32, [C.POINTER(Plan), C.POINTER(AttnParams)]),
     "cgat_nodes_attention_infer_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.POINTER(AttnParams)]),
     "cgat_nodes_attention_infer": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, vp, vp, C.c_size_t, vp]),
+    "cgat_nodes_attention_infer_indexed_ok": (C.c_int32, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
+    "cgat_nodes_attention_infer_indexed_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
+    "cgat_nodes_attention_infer_indexed": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, C.c_int32, vp, vp, vp,
+                                                     C.c_size_t, vp]),
     "cgat_debug_nodes_attention_route": (C.c_uint32, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
     "cgat_debug_nodes_attention_signs": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, vp]),
     "cgat_debug_edge_ge_rebuilt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -1117,7 +1117,9 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
   CGAT_CHECK_ARG(!z_bf16 || (Pj != nullptr && mode_24bit() && act == CGAT_ACT_NONE && !omax),
                  "edge_z: bf16 storage is the per-edge launch of the six-pass form only");
   // operand (a = column block, b = k, c = column in block) = We[(128 a + c) * ldw + b]
-  if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(We, Wq, ncb, 128 * ldw, 1, ldw, stream));
+  // (We == nullptr: the caller has prepared that image in Wq already, e.g. several slices in one launch)
+  if (!We) {}
+  else if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(We, Wq, ncb, 128 * ldw, 1, ldw, stream));
   else CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * ldw, 1, ldw, 0, stream));
   CGAT_PROF(Pj ? "edge_z" : "edge_proj", stream);   // the per-edge launch / the per-node projections
   // the six-pass per-edge launch on 256-row workgroups (edge_z6w_kernel: same arithmetic, bit-identical results; the

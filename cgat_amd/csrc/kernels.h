@@ -179,6 +179,8 @@ int edge_zx_launch(const float* e, long lde, const int* perm, const float* x, lo
                    long ldw, float* Wq, int W2, const float* Pi, const int* dsti, const int* srci, long ld_add, float* Z,
                    long ldz, int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream,
                    int z_bf16 = 0);   // z_bf16: Z stored as bf16 (ldz in elements either way)
+// (We == nullptr: Wq already holds the image of the current mode -- prepare_T_planes_launch / prepare_W_f16_launch with
+// this function's strides -- and is only read)
 int edge_z_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
                   const float* Pi, const int* dsti, const float* Pj, const int* srci, long ld_add, float* Z, long ldz,
                   int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream,
@@ -216,6 +218,17 @@ int edge_logits_launch(const float* e, long lde, const int* perm, const float* W
 int edge_msg_wsum_launch(const float* e, long lde, const int* perm, const float* Wq, int W2, const float* Pi,
                          const int* dsti, const float* Pj, const int* srci, int N, int E, int H, int Hd, const float* alpha,
                          const int* rowptr, float* S, int z_bf16, hipStream_t stream);
+// ---- the same per-edge phase for edge_attr = table[idx] of R rows (shell-indexed edge features), edgeidx.hip ----
+// Te [R, W2] = table W_e^T (no bias); idx [E] int64 in original edge order, reached through perm; Pi / Pj [N, W2].
+// Gathers and fp32 VALU only: any arithmetic mode, any E.  edge_idx_ok: the host-only predicate of the shapes.
+#define EDGE_IDX_MAX_ROWS 256
+bool edge_idx_ok(int H, int Hd, int R);
+int edge_idx_logits_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
+                           const int* srci, int W2, const float* wA, const float* bA, int H, int Hd, const int* rowptr,
+                           int N, int E, float* a_out, hipStream_t stream);
+int edge_idx_wsum_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
+                         const int* srci, int W2, const float* alpha, int H, int Hd, const int* rowptr, int N, int E,
+                         float* S, hipStream_t stream);
 size_t linear128_heads_image_floats(int n_out);
 int linear128_heads_launch(int heads, const float* in, long ldi, long s_in, const float* W, long so, long sk, long s_w,
                            const float* bias, long s_bias, int act, int accumulate, float* out, long ldo, long s_out, int rows,

@@ -539,6 +539,111 @@ static int attn_forward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_para
   return check_ws(c, "nodes_attention_forward");
 }
 
+// ---- the forward without grad on shell-indexed edge features: edge_attr[e] = table[index[e]], R rows ----
+// W_e edge_attr[e] takes R distinct values, so Te = table W_e^T [R, W2] is formed once and the per-edge phase adds three
+// gathered rows (edgeidx.hip): no per-edge product.  fp32 edge storage only -- the dense route rounds z to bf16 under
+// edge storage "bf16" and this one would not, so the caller densifies there.  Every arithmetic mode: the per-edge phase
+// has no matrix instruction, and the node-side products are the ones of attn_forward_impl.
+static bool attn_infer_indexed_ok(const AttnDims& d, int R) {
+  return !edge_bf16_storage() && d.N > 0 && d.E > 0 && edge_idx_ok(d.H, d.Hd, R);
+}
+struct AttnFwdIndexed {
+  AttnFwd f;          // e == nullptr; a, sv.alpha, sv.S, sv.ssum: carve-outs, as in the fused inference
+  const float* table;
+  const int64_t* index;
+  int R;
+  float* Te;
+};
+static AttnFwdIndexed attn_fwd_indexed_carve(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                             const float* table, int R, const int64_t* index, float* aggr) {
+  AttnFwdIndexed g = {};
+  AttnFwd& f = g.f;
+  const AttnDims d = f.d = attn_dims(plan, p);
+  f.plan = plan; f.p = p; f.x = x; f.aggr = aggr;
+  g.table = table; g.index = index; g.R = R;
+  f.Wcat = c.take<float>((size_t)d.W2 * d.D);
+  f.bcat = c.take<float>((size_t)d.W2);
+  f.Pi = c.take<float>((size_t)d.N * d.W2);
+  f.Pj = c.take<float>((size_t)d.N * d.W2);
+  g.Te = c.take<float>((size_t)R * d.W2);
+  f.Wq = c.take<float>(2 * edge_z_wq_floats(d.W2));   // the images of W_i and W_j, made in one launch
+  f.a = c.take<float>((size_t)d.E * d.H);            // the logits and alpha: all that grows with E
+  f.sv.alpha = c.take<float>((size_t)d.E * d.H);
+  f.sv.S = c.take<float>((size_t)d.N * d.HHd);
+  f.sv.ssum = c.take<float>((size_t)d.N * d.H);
+  c.seal();
+  f.r = attn_fwd_route(c.dry, d, true, p, x, nullptr, nullptr, f.sv.S, aggr, f.Pi);   // proj_fast, out_fast, out_one
+  return g;
+}
+// node_projections with the images of both weight slices from ONE preparation launch (the per-edge kernel's launches then
+// only read them): the same products, one launch fewer per layer
+static int node_projections_indexed(Ctx& c, const AttnFwdIndexed& g) {
+  const AttnFwd& f = g.f;
+  const AttnDims& d = f.d;
+  if (!f.r.proj_fast) return node_projections(c, d, false, true, f.x, f.Wcat, f.bcat, NodeProj{f.Pi, f.Pj, f.Wq});
+  const int ncb = d.W2 / 128;
+  const long img = (long)edge_z_wq_floats(d.W2);
+  // operand (a = column block, b = k, c = column in block) = W[(128 a + c) * D + b]; slice 1 starts C + Ce columns further
+  if (mode_f16()) RUN(prepare_W_f16_launch(f.Wcat, f.Wq, ncb, 128l * d.D, 1, d.D, c.s, 2, d.C + d.Ce, img));
+  else RUN(prepare_T_planes_launch(f.Wcat, f.Wq, ncb, 128l * d.D, 1, d.D, 0, c.s, nullptr, 2, d.C + d.Ce, img));
+  RUN(edge_z_launch(f.x, d.C, nullptr, nullptr, d.D, f.Wq, d.W2, f.bcat, nullptr, nullptr, nullptr, 0, f.Pi, d.W2, d.N,
+                    nullptr, nullptr, d.H, d.Hd, nullptr, c.s));
+  RUN(edge_z_launch(f.x, d.C, nullptr, nullptr, d.D, f.Wq + img, d.W2, nullptr, nullptr, nullptr, nullptr, 0, f.Pj, d.W2,
+                    d.N, nullptr, nullptr, d.H, d.Hd, nullptr, c.s));
+  return CGAT_OK;
+}
+// Te = table W_e^T (no bias: Pi carries it) on whichever engine takes R rows: a single-op small-row program below
+// rowprog_max_rows(), the generic product of node_projections otherwise
+static int indexed_edge_table(Ctx& c, const AttnFwdIndexed& g) {
+  const AttnDims& d = g.f.d;
+  return c.gemm(gemm_params(g.R, d.W2, d.Ce, g.table, d.Ce, g.f.Wcat + d.C, d.D, g.Te, d.W2));
+}
+// logits, softmax (the launch of every other forward: eps 1e-16, one rounded division), message columns summed into S
+static int attn_fwd_edges_indexed(Ctx& c, const AttnFwdIndexed& g) {
+  const AttnFwd& f = g.f;
+  const AttnDims& d = f.d;
+  const cgat_plan* plan = f.plan;
+  CGAT_CHECK_ARG(aligned16(f.p->A_out_w), "nodes_attention_infer_indexed: MH_A.fc_out.weight must be 16-byte aligned");
+  RUN(edge_idx_logits_launch(g.Te, g.R, g.index, plan->dst_perm, f.Pi, f.Pj, plan->src_sorted, d.W2, f.p->A_out_w,
+                             f.p->A_out_b, d.H, d.Hd, plan->dst_rowptr, d.N, d.E, f.a, c.s));
+  RUN(seg_softmax_fwd_launch(f.a, nullptr, plan->dst_rowptr, d.N, d.H, 1e-16f, f.sv.alpha, f.sv.ssum, c.s));
+  RUN(edge_idx_wsum_launch(g.Te, g.R, g.index, plan->dst_perm, f.Pi, f.Pj, plan->src_sorted, d.W2, f.sv.alpha, d.H, d.Hd,
+                           plan->dst_rowptr, d.N, d.E, f.sv.S, c.s));
+  return CGAT_OK;
+}
+// fc_out_M for this route.  Where attn_fwd_out would take its one K = H * Hd launch, the same kernel runs once per head
+// over that head's blocks of the same image (K = Hd each, accumulating into aggr): the accumulation chain of the one
+// launch is the largest error of the whole forward, and the dense route leaves it wherever its
+// own S is misaligned.  Everything else is attn_fwd_out.
+static int attn_fwd_out_indexed(Ctx& c, const AttnFwd& f) {
+  const AttnDims& d = f.d;
+  if (!f.r.out_one) return attn_fwd_out(c, f);
+  const int ncb_h = d.Hd / 128;
+  c.need((size_t)d.H * ncb_h * 24576 * sizeof(float));
+  CGAT_TRY(prepare_T_planes_launch(f.p->M_out_w, c.scratch, ncb_h, 128, 1, d.Hd, /*alternate=*/1, c.s, nullptr, d.H,
+                                   (long)d.C * d.Hd, (long)ncb_h * 24576));
+  for (int h = 0; h < d.H; ++h)
+    CGAT_TRY(edge_ge_prepared_launch(f.sv.S + (size_t)h * d.Hd, d.HHd,
+                                     reinterpret_cast<const float*>(c.scratch) + (size_t)h * ncb_h * 24576, ncb_h, f.aggr,
+                                     d.C, d.N, h > 0 ? 1 : 0, c.s));
+  GemmParams g = gemm_params(d.N, d.C, d.H, f.sv.ssum, d.H, f.p->M_out_b, d.C, f.aggr, d.C);
+  g.b_kmajor = 1;
+  g.alpha = 1.f / d.H;
+  g.beta = 1.f / d.H;
+  return c.gemm(g);
+}
+static int attn_infer_indexed_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                   const float* table, int R, const int64_t* index, float* aggr) {
+  const AttnFwdIndexed g = attn_fwd_indexed_carve(c, plan, p, x, table, R, index, aggr);
+  const AttnFwd& f = g.f;
+  CGAT_TRY(stack_in_weights(c, p, f.d, f.Wcat, f.bcat));
+  CGAT_TRY(node_projections_indexed(c, g));
+  CGAT_TRY(indexed_edge_table(c, g));
+  CGAT_TRY(attn_fwd_edges_indexed(c, g));
+  CGAT_TRY(attn_fwd_out_indexed(c, f));
+  return check_ws(c, "nodes_attention_infer_indexed");
+}
+
 // ---- the operand-split first layer's backward tail ----
 // Everything downstream of the pre-activation gradient gZ[t, :] (destination-sorted slots) of the operand-split first
 // layer: gradients wrt edge_attr, x, the stacked weight [W2, D] = [W_i | W_e | W_j] and its bias.  Shared by the
@@ -1077,6 +1182,29 @@ extern "C" int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn
   CGAT_TRY(attn_check(plan, p));
   return run_sized("nodes_attention_infer", ws, ws_bytes, stream,
                    [&](Ctx& c) { return attn_forward_impl(c, plan, p, x, edge_attr, aggr, nullptr, true); });
+}
+extern "C" int32_t cgat_nodes_attention_infer_indexed_ok(const cgat_plan* plan, const cgat_attn_params* p, int32_t R) {
+  if (attn_check(plan, p) != CGAT_OK) return 0;
+  return attn_infer_indexed_ok(attn_dims(plan, p), R) ? 1 : 0;
+}
+extern "C" size_t cgat_nodes_attention_infer_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p,
+                                                                     int32_t R) {
+  if (R < 1) R = 1;
+  return dry_total([&](Ctx& c) { return attn_infer_indexed_impl(c, plan, p, nullptr, nullptr, R, nullptr, nullptr); });
+}
+extern "C" int cgat_nodes_attention_infer_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                                  const float* table, int32_t R, const int64_t* index, float* aggr,
+                                                  void* ws, size_t ws_bytes, void* stream) {
+  CGAT_TRY(attn_check(plan, p));
+  if (!attn_infer_indexed_ok(attn_dims(plan, p), R)) {
+    cgat_set_error("nodes_attention_infer_indexed: not taken for N %d, E %d, H %d, Hd %d, R %d under edge storage %d "
+                   "(cgat_nodes_attention_infer_indexed_ok); densify and call cgat_nodes_attention_infer", plan->N, plan->E,
+                   p->H, p->Hd, R, edge_storage());
+    return CGAT_ERR_UNSUPPORTED;
+  }
+  CGAT_CHECK_ARG(x && table && index && aggr, "nodes_attention_infer_indexed: null operand");
+  return run_sized("nodes_attention_infer_indexed", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return attn_infer_indexed_impl(c, plan, p, x, table, R, index, aggr); });
 }
 extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
                                              const float* edge_attr, const float* saved, const float* g_aggr,

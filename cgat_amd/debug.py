@@ -53,6 +53,19 @@ def note(weight, mask):
         _active.masks.setdefault(name, []).append(mask.detach().to("cpu", torch.bool))
 
 
+def expand_last(weights, index):
+    """Shell-indexed edge features (ops.IndexedEdgeAttr): the layers with these weights have just run on the table's rows;
+    the pattern each recorded last becomes that of the dense rows, mask[index] -- the reference's activation has one row
+    per edge."""
+    if _active is None:
+        return
+    idx = index.detach().to("cpu")
+    for w in weights:
+        lst = _active.masks.get(_active.names.get(w.data_ptr()))
+        if lst:
+            lst[-1] = lst[-1][idx]
+
+
 def note_dropout(keep):
     if _active is not None:
         _active.dropout.append(keep.detach().to("cpu"))

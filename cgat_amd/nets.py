@@ -22,6 +22,7 @@ from .ops import (AttentionPoolFn, attention_pool, get_fused_attention_dropout, 
                   segment_softmax, segment_sum)
 from .ops import overlap_enabled as ops_overlap_enabled
 from .ops import HNetFn, infer_route, nodes_attention_infer
+from .ops import IndexedEdgeAttr, get_indexed_edge_attr, indexed_route, nodes_attention_infer_indexed
 from .ops import EdgeHeadCombineFn, edge_combine_route
 from .ops import branch_stream
 from .roost import Roost
@@ -141,6 +142,12 @@ class GATConvEdges(nn.Module):
         return (sm * alpha).mean(dim=1)
 
     def forward(self, x, edge_index, edge_attr, x_0, size=None):
+        if isinstance(edge_attr, IndexedEdgeAttr):
+            # shell-indexed edge features: the shipped form is row-wise, so it runs on the table's rows and the result is
+            # a lookup again; the per-edge hypernetwork form needs the rows themselves
+            if self.no_hyper:
+                return edge_attr.with_table(self.Pooling_NN(edge_attr.table))
+            edge_attr = edge_attr.dense()
         if self.no_hyper:
             return self.Pooling_NN(edge_attr)     # (the discarded attention's dropout mask is discarded with it)
         drop = self.dropout if (self.dropout and self.training) else 0.0
@@ -256,9 +263,22 @@ class GATConvNodes(nn.Module):
 
     def _aggregate_fused(self, x, edge_attr, plan):
         params = self._attn_params()
+        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route)
+            return nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *params)
         if infer_route(x, edge_attr, params):
             return nodes_attention_infer(x, edge_attr, plan, self.heads, *params)
         return NodesAttentionFn.apply(x, edge_attr, plan, self.heads, *params)
+
+    def _indexed_route(self, x, edge_index, edge_attr):
+        """True when this call, given an IndexedEdgeAttr, runs ops.nodes_attention_infer_indexed in place of
+        nodes_attention_infer: scalar attention, one unchunked pass, no training-mode dropout, message / update the
+        layer's own, no backward to follow and no debug recording (ops.infer_route), and a shape the library takes in
+        the current arithmetic and edge-storage modes.  Everything else densifies and runs as it always has."""
+        if (self.vector_attention or not torch.is_tensor(x) or (self.dropout and self.training) or
+                type(self).message is not GATConvNodes.message or type(self).update is not GATConvNodes.update or
+                edge_index.shape[1] > chunked.max_edges_per_pass() or not x.is_cuda):
+            return False
+        return indexed_route(x, edge_attr, get_plan(edge_index, x.shape[0]), self.heads, self._attn_params())
 
     # -- vector attention (CGAT.py:286-290: MH_A emits one logit per head AND channel): the shared first layer of both
     #    networks runs as one operand-split op in destination-sorted order, so the concatenated message [E, 2C+Ce],
@@ -340,6 +360,9 @@ class GATConvNodes(nn.Module):
             with torch.no_grad():
                 pool.damping.data = pool.damping.data.clamp(0.0, 1.0)      # Hypernetworksmp.py:307, as H_Net.forward
             h0, damping = x_0, pool.damping
+        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route, infer_route included)
+            aggr = nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *self._attn_params())
+            return HNetFn.apply(h0, aggr, damping, hyper.n_fc, len(hyper.layers), *flat)
         if infer_route(x, edge_attr, self._attn_params()):
             # the attention half without grad; the hypernetwork as its own node (NodeLayerFn's forward runs the same call)
             aggr = nodes_attention_infer(x, edge_attr, plan, self.heads, *self._attn_params())
@@ -429,6 +452,8 @@ class GATConvNodes(nn.Module):
         return agg.reshape(plan.N, self.heads, self.out_channels).mean(dim=1)[:n_dst]
 
     def forward(self, x, edge_index, edge_attr, x_0, size=None):
+        if isinstance(edge_attr, IndexedEdgeAttr) and not self._indexed_route(x, edge_index, edge_attr):
+            edge_attr = edge_attr.dense()
         if not torch.is_tensor(x):
             x_src, x_dst = x[0], x[1]
             if x_src is None or x_dst is None or not self.final:
@@ -492,9 +517,15 @@ class CGAtNet(nn.Module):
             branch.wait_stream(main)
             with torch.cuda.stream(branch):
                 crys_comp = self.roost(*roost, num_crystals=G)
-        edge_attr = small_embedding(batch.edge_attr, self.nbr_embedding.weight)  # [E] int64 -> [E,Ce]
+        indexed = self._indexed_edges(batch)                                    # (opt-in: ops.set_indexed_edge_attr)
+        if not indexed:
+            edge_attr = small_embedding(batch.edge_attr, self.nbr_embedding.weight)  # [E] int64 -> [E,Ce]
         elem_fea = linear(batch.x, self.embedding.weight, None)                 # [N,200] -> [N,C]
         elem_fea_0 = elem_fea
+        if indexed:
+            elem_fea = self._graphs_indexed(batch, elem_fea)
+            return self._readout(batch, roost, elem_fea, G, main, branch, crys_comp if branch is not None else None,
+                                 last_layer, return_graph_embedding)
         edge_attr_0 = edge_attr
         # (per-layer fork / join: worth it inside a hipGraph, where it is a graph edge -- 13.76 -> 13.45 ms per replayed
         # 64-crystal step; in eager mode the eight extra stream switches cost more host time than the overlap returns)
@@ -524,6 +555,74 @@ class CGAtNet(nn.Module):
             else:
                 edge_attr = edge_attr + edge(elem_fea, edge_index, edge_attr, edge_attr_0)
             elem_fea = elem_fea + node_update
+        return self._readout(batch, roost, elem_fea, G, main, branch, crys_comp if branch is not None else None,
+                             last_layer, return_graph_embedding)
+
+    def _indexed_edges(self, batch):
+        """The shell-indexed form of the edge features applies (ops.set_indexed_edge_attr): the switch is on, every Edge
+        layer is the shipped row-wise form, and batch.edge_attr holds integer ids on the GPU.  One layer that fails
+        sends the whole forward down the dense path."""
+        ea = batch.edge_attr
+        return (get_indexed_edge_attr() and torch.is_tensor(ea) and ea.is_cuda and ea.dim() == 1 and
+                not ea.is_floating_point() and not ea.is_complex() and ea.dtype != torch.bool and
+                self.nbr_embedding.weight.is_cuda and self.nbr_embedding.weight.dtype == torch.float32 and
+                all(g['Edge'].no_hyper and type(g['Edge']).forward is GATConvEdges.forward for g in self.graphs))
+
+    def _graphs_indexed(self, batch, elem_fea):
+        """The graph layers on edge_attr_l[e] = T_l[shell[e]]: the edge update and its residual run
+        on the R = neighbor_number + 1 rows of the table -- a small-row program on the main stream, no edge branch -- and
+        the node layers take the lookup (without grad: no per-edge product; with grad: one gather per layer, whose
+        backward is the deterministic per-class row sum)."""
+        elem_fea_0 = elem_fea
+        index = batch.edge_attr if batch.edge_attr.dtype == torch.int64 else batch.edge_attr.long()
+        ea = IndexedEdgeAttr(self.nbr_embedding.weight, index)
+        if self._edge_tables_ahead(ea.table):
+            # no grad: T_l depends on the edge networks alone, so every layer's table comes from ONE small-row launch
+            # issued ahead of the node layers (the same products as below, bit for bit; the last update feeds nothing)
+            tables = self._edge_tables(ea.table)
+            for graph_func, table in zip(self.graphs, tables):
+                elem_fea = elem_fea + graph_func['Node'](elem_fea, batch.edge_index, ea.with_table(table), elem_fea_0)
+            return elem_fea
+        for graph_func in self.graphs:
+            node_update = graph_func['Node'](elem_fea, batch.edge_index, ea, elem_fea_0)
+            pool = graph_func['Edge'].Pooling_NN
+            ea = ea.with_table(pool(ea.table, residual=ea.table))
+            if debug.recording():
+                debug.expand_last([fc.weight for fc in pool.fcs], ea.index)
+            elem_fea = elem_fea + node_update
+        return elem_fea
+
+    def _edge_tables_ahead(self, table):
+        pools = [g['Edge'].Pooling_NN for g in self.graphs]
+        return (not torch.is_grad_enabled() and not debug.recording() and rowprog.eligible(table) and
+                2 * (len(pools) - 1) <= _lib.ROWPROG_MAX_OPS and
+                all(type(p) is SimpleNetwork and len(p.fcs) == 1 and p.fcs[0].bias is not None and
+                    p.fc_out.bias is not None and p.fc_out.weight.shape[0] == table.shape[1] and
+                    p.fcs[0].weight.shape[1] == table.shape[1] for p in pools))
+
+    def _edge_tables(self, table):
+        """[T_0, ..., T_{L-1}] with T_{l+1} = T_l + Edge_l.Pooling_NN(T_l) as one small-row program: per layer the two
+        ops SimpleNetwork.forward(T_l, residual=T_l) runs, phases in sequence."""
+        R, dev = table.shape[0], table.device
+        cur = table.detach()
+        tables, prog = [cur], []
+        for g in list(self.graphs)[:-1]:
+            pool = g['Edge'].Pooling_NN
+            w1, wo = pool.fcs[0].weight.detach(), pool.fc_out.weight.detach()
+            hid = torch.empty(R, w1.shape[0], dtype=torch.float32, device=dev)
+            out = torch.empty(R, wo.shape[0], dtype=torch.float32, device=dev)
+            prog.append(rowprog.op(len(prog), R, w1.shape[0], w1.shape[1], cur, w1, hid, bias=pool.fcs[0].bias.detach(),
+                                   act=_lib.ACT_LEAKY))
+            prog.append(rowprog.op(len(prog), R, wo.shape[0], wo.shape[1], hid, wo, out, bias=pool.fc_out.bias.detach(),
+                                   resid=cur))
+            tables.append(out)
+            cur = out
+        if prog:
+            rowprog.run(prog, dev)
+        return tables
+
+    def _readout(self, batch, roost, elem_fea, G, main, branch, crys_comp, last_layer, return_graph_embedding):
+        crystal_elem_idx = batch.batch
         if branch is not None:
             main.wait_stream(branch)
             crys_comp.record_stream(main)

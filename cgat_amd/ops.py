@@ -326,6 +326,133 @@ def infer_route(x, edge_attr, params):
     return not any(t is not None and t.requires_grad for t in (x, edge_attr, *params))
 
 
+# ----------------------------------------------------------------------------------------
+# shell-indexed edge features: edge_attr[e] = table[index[e]]
+# ----------------------------------------------------------------------------------------
+_indexed_edge_attr = os.environ.get("CGAT_INDEXED_EDGE_ATTR", "0") == "1"
+
+
+def set_indexed_edge_attr(flag):
+    """CGAtNet carries its edge features as an IndexedEdgeAttr (default off; env CGAT_INDEXED_EDGE_ATTR=1 starts it on)
+    where that is exact: every Edge layer is the shipped no_hyper form and batch.edge_attr holds integer shell ids.  The
+    edge update then runs on the table's rows, and scalar-attention node layers without grad take
+    nodes_attention_infer_indexed.  Off: the dense edge features of every earlier release, bit for bit."""
+    global _indexed_edge_attr
+    _indexed_edge_attr = bool(flag)
+
+
+def get_indexed_edge_attr():
+    return _indexed_edge_attr
+
+
+_index_checked = {}
+
+
+class IndexedEdgeAttr:
+    """Edge features as a lookup: edge_attr[e] = table[index[e]].
+
+    table  [R, Ce] float32 on the GPU; may require grad
+    index  [E] int64 in original edge order, values in [0, R)
+
+    In the shipped network nbr_embedding's lookup and every row-wise edge update keep the edge features in this form
+    with R = neighbor_number + 1.  `dense()` returns small_embedding(index, table), cached on the
+    object: the gradient reaches `table` through the deterministic per-class row sum of that op, which it has while
+    R * Ce <= 8192 (small_embedding's limit; beyond it torch's embedding backward runs, which is not deterministic).
+    The index values are validated once per index tensor (one host round trip, under ops.set_validate_indices like the
+    plans; skipped during a hipGraph capture): `with_table` keeps the index and its validation."""
+
+    def __init__(self, table, index, _checked=False):
+        if not torch.is_tensor(table) or not torch.is_tensor(index):
+            raise TypeError("IndexedEdgeAttr(table, index) takes two tensors")
+        _require_gpu(table, index)
+        if table.dtype != torch.float32 or table.dim() != 2:
+            raise TypeError(f"IndexedEdgeAttr: table must be float32 [R, Ce], got {table.dtype} {tuple(table.shape)}")
+        if index.dtype != torch.int64 or index.dim() != 1:
+            raise TypeError(f"IndexedEdgeAttr: index must be int64 [E], got {index.dtype} {tuple(index.shape)}")
+        if table.shape[0] < 1:
+            raise ValueError("IndexedEdgeAttr: the table has no rows")
+        self.table, self.index = table, index
+        self._dense = None
+        if not _checked:
+            self._validate()
+
+    def _validate(self):
+        idx, R = self.index, int(self.table.shape[0])
+        if not _validate_indices or idx.numel() == 0 or torch.cuda.is_current_stream_capturing():
+            return
+        key = (idx.data_ptr(), idx.numel(), idx._version, idx.device.index)
+        if _index_checked.get(key, (1 << 62, None))[0] <= R:   # this index has passed for a table of no more rows
+            return
+        lo, hi = (int(v) for v in torch.aminmax(idx))
+        if lo < 0 or hi >= R:
+            raise IndexError(f"cgat_amd: IndexedEdgeAttr index values span [{lo}, {hi}], outside [0, {R})")
+        if len(_index_checked) >= 16:
+            _index_checked.pop(next(iter(_index_checked)))
+        _index_checked[key] = (hi + 1, idx)              # (the tensor is kept alive: its address is the key)
+
+    @property
+    def shape(self):
+        return (self.index.shape[0], self.table.shape[1])
+
+    def with_table(self, table):
+        """The same lookup over another table of as many rows (a row-wise function of this one's)."""
+        if table.shape[0] != self.table.shape[0]:
+            raise ValueError("IndexedEdgeAttr.with_table: the row count must not change")
+        return IndexedEdgeAttr(table, self.index, _checked=True)
+
+    def dense(self):
+        if self._dense is None:
+            self._dense = small_embedding(self.index, self.table)
+        return self._dense
+
+
+def infer_indexed_ok(plan_c, C_, Ce, H, Hd, R):
+    """cgat_nodes_attention_infer_indexed_ok for a layer of these dims (host only; plan_c: the C struct of a plan)."""
+    p = _lib.AttnParams(int(C_), int(Ce), int(H), int(Hd), *([None] * 8))
+    return bool(lib.cgat_nodes_attention_infer_indexed_ok(C.byref(plan_c), C.byref(p), int(R)))
+
+
+def indexed_route(x, edge_attr, plan, H, params):
+    """True when a scalar-attention node layer given an IndexedEdgeAttr takes nodes_attention_infer_indexed: infer_route
+    holds (no backward can follow, no debug recording) and the library takes the shape in the current modes."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        return False
+    if not infer_route(x, edge_attr.table, params):
+        return False
+    A_in_w, A_out_w = params[0], params[2]
+    HHd = A_in_w.shape[0]
+    if HHd % H or A_out_w.numel() != HHd:                 # vector attention
+        return False
+    return infer_indexed_ok(plan.c, x.shape[1], edge_attr.table.shape[1], H, HHd // H, edge_attr.table.shape[0])
+
+
+def nodes_attention_infer_indexed(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b):
+    """nodes_attention_infer for an IndexedEdgeAttr (or a (table, index) pair) without forming table[index]
+    (cgat_nodes_attention_infer_indexed): Te = table W_e^T once, the per-edge phase a gather of three rows.  Equal to the
+    dense call up to fp32 summation order.  Raises where the library does not take the shape (infer_indexed_ok)."""
+    if not isinstance(edge_attr, IndexedEdgeAttr):
+        edge_attr = IndexedEdgeAttr(*edge_attr)
+    weights = [A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b]
+    table, index = edge_attr.table, edge_attr.index
+    _require_gpu(x, *weights)
+    x, table, index = _f32c(x.detach()), _f32c(table.detach()), index.contiguous()
+    ws_ = [_f32c(w.detach()) for w in weights]
+    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
+        raise ValueError("nodes_attention_infer_indexed handles scalar attention (MH_A output_dim == 1)")
+    N, E, R = plan.N, plan.E, int(table.shape[0])
+    if x.shape[0] != N or index.shape[0] != E:
+        raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, index {tuple(index.shape)}")
+    p, Hd = _attn_params(x, table, H, ws_)
+    dev = x.device
+    aggr = torch.empty(N, x.shape[1], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_nodes_attention_infer_indexed_workspace_bytes(C.byref(plan.c), C.byref(p), R), dev)
+        check(lib.cgat_nodes_attention_infer_indexed(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(table), R, _ptr(index),
+                                                     _ptr(aggr), _ptr(ws), ws.numel(), _stream()),
+              "cgat_nodes_attention_infer_indexed")
+    return aggr
+
+
 def _edge_hidden_forward(who, x, edge_attr, plan, w_in, b_in):
     """cgat_edge_hidden_forward behind EdgeHiddenFn and EdgeHiddenHeadsFn.  Returns the prepared operands, hidden and
     hmax = max |hidden| (the fp16 scale of the second layers)."""

@@ -202,6 +202,24 @@ int cgat_nodes_attention_infer(const cgat_plan* plan, const cgat_attn_params* p,
                                const float* edge_attr /* [E,Ce], original edge order */, float* aggr /* out [N,C] */,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* The same forward without grad for shell-indexed edge features: edge_attr[e] = table[index[e]] with R rows (replaces
+ * CGAT/CGAT.py:319-329 together with the edge features of 569 and 583: in the shipped network nbr_embedding's lookup and
+ * every row-wise edge update keep edge_attr a lookup of at most neighbor_number + 1 rows).  Te = table W_e^T [R, 2*H*Hd] is
+ * formed once and the per-edge pre-activation is the sum of three gathered rows, Te[index[e]] + Pi[dst] + Pj[src]: no
+ * per-edge product, nothing of size E*H*Hd formed; the workspace grows with E by the logits and alpha alone.  Equal to
+ * cgat_nodes_attention_infer on table[index] up to fp32 summation order; bitwise deterministic; no allocation, no host
+ * synchronisation.  index values must lie in [0, R) (the caller validates; the kernels clamp).
+ * cgat_nodes_attention_infer_indexed_ok -- a host-only predicate -- says 1 for fp32 edge storage, every arithmetic mode,
+ * N, E > 0, H <= 8, Hd % 4 == 0, H*Hd <= 2048, 1 <= R <= 256 (any C, Ce; any E; 64-bit row offsets); 0 under edge storage
+ * "bf16", where the dense route rounds the pre-activations and this one would not.  Where it says 0 the call returns
+ * CGAT_ERR_UNSUPPORTED: the caller densifies and calls cgat_nodes_attention_infer. */
+int32_t cgat_nodes_attention_infer_indexed_ok(const cgat_plan* plan, const cgat_attn_params* p, int32_t R);
+size_t cgat_nodes_attention_infer_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p, int32_t R);
+int cgat_nodes_attention_infer_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x /* [N,C] */,
+                                       const float* table /* [R,Ce] */, int32_t R,
+                                       const int64_t* index /* [E], original edge order, values in [0,R) */,
+                                       float* aggr /* out [N,C] */, void* ws, size_t ws_bytes, void* stream);
+
 /* Debug (tests only): the routes cgat_nodes_attention_forward (backward == 0) or cgat_nodes_attention_backward
  * (backward != 0) takes for this layer in the current arithmetic and edge-storage modes, for 16-byte aligned operands --
  * host only, a predicate of the shapes like cgat_nodes_attention_infer_fused.  One bit per route, from bit 0:
