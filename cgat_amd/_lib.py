@@ -137,6 +137,21 @@ PROTOTYPES = {
     "cgat_nodes_attention_infer_indexed_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
     "cgat_nodes_attention_infer_indexed": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, C.c_int32, vp, vp, vp,
                                                      C.c_size_t, vp]),
+    "cgat_nodes_attention_train_indexed_ok": (C.c_int32, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
+    "cgat_nodes_attention_indexed_saved_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cgat_nodes_attention_forward_indexed_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
+    "cgat_nodes_attention_forward_indexed": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, C.c_int32, vp, vp, vp,
+                                                       vp, C.c_size_t, vp]),
+    "cgat_nodes_attention_backward_indexed_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
+    "cgat_nodes_attention_backward_indexed": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, C.c_int32, vp, vp, vp,
+                                                        vp, vp, vp, vp, vp, C.POINTER(AttnGrads), vp, C.c_size_t, vp]),
+    "cgat_indexed_class_pieces": (C.c_int32, [C.c_int32, C.c_int32]),
+    "cgat_indexed_class_plan_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cgat_indexed_class_plan": (C.c_int, [C.POINTER(Plan), vp, C.c_int32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "cgat_debug_nodes_attention_signs_indexed_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.POINTER(AttnParams),
+                                                                              C.c_int32]),
+    "cgat_debug_nodes_attention_signs_indexed": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, C.c_int32, vp, vp,
+                                                           vp, C.c_size_t, vp]),
     "cgat_debug_nodes_attention_route": (C.c_uint32, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
     "cgat_debug_nodes_attention_signs": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, vp]),
     "cgat_debug_edge_ge_rebuilt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

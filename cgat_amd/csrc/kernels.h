@@ -229,6 +229,32 @@ int edge_idx_logits_launch(const float* Te, int R, const int64_t* idx, const int
 int edge_idx_wsum_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
                          const int* srci, int W2, const float* alpha, int H, int Hd, const int* rowptr, int N, int E,
                          float* S, hipStream_t stream);
+// ---- the training form of that route, edgeidx.hip: no Z is stored, the backward forms z again from the three rows ----
+// edge_idx_train_ok: edge_idx_ok plus whole 32-column mask words per half (H * Hd % 32 == 0).  Host only.
+bool edge_idx_train_ok(int H, int Hd, int R);
+int edge_idx_bwd_chunks(int N);                 // rows of partialW [chunks][H * Hd]
+// the segment backward (segbwd.hip's three steps on recomputed z): tt, ga [E, H]; mask [E][W2 / 32] in EdgeRC's layout;
+// Gi [N, W2]; partialW: the partial rows of grad fc_out_A.weight = sum ga leaky(z_A)
+int edge_idx_bwd_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
+                        const int* srci, int W2, const float* alpha, const float* gS, const float* gs, const float* wA,
+                        int H, int Hd, const int* rowptr, int N, int E, float* tt, float* ga, unsigned* mask, float* Gi,
+                        float* partialW, hipStream_t stream);
+int seg_bwd_soft_launch(const float* alpha, const float* tt, const int* rowptr, int N, int H, float* ga,
+                        hipStream_t stream);    // segbwd.hip: seg_bwd_soft_kernel alone
+// the class sum gT [R, W2] of the rebuilt gZ rows: slots grouped by class in ascending slot order (cls_pos [E]), classes
+// cut into fixed pieces (piece_start [R + 1], piece_rowptr [edge_idx_class_pieces(E, R) + 1]) -- all three made by
+// edge_idx_class_plan_launch from index and the plan's slot order, once per batch;
+// partials: [edge_idx_class_pieces(E, R)][W2] floats of workspace
+struct EdgeRC;
+int edge_idx_class_pieces(int E, int R);
+size_t edge_idx_class_plan_ws_bytes(int E, int R);
+int edge_idx_class_plan_launch(const int64_t* idx, const int* perm, int E, int R, int* cls_pos, int* piece_start,
+                               int* piece_rowptr, void* ws, size_t ws_bytes, hipStream_t stream);
+int edge_idx_class_sum_launch(const EdgeRC& rc, const int* piece_rowptr, const int* piece_start, const int* cls_pos, int R,
+                              int E, int W2, float* partials, float* gT, hipStream_t stream);
+// debug: mask[perm[t]][c] = (z[t][c] > 0) for z formed as the route forms it (uint8 [E, W2], original edge order)
+int edge_idx_signs_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
+                          const int* srci, const int* dsti, int W2, long E, uint8_t* mask, hipStream_t stream);
 size_t linear128_heads_image_floats(int n_out);
 int linear128_heads_launch(int heads, const float* in, long ldi, long s_in, const float* W, long so, long sk, long s_w,
                            const float* bias, long s_bias, int act, int accumulate, float* out, long ldo, long s_out, int rows,

@@ -554,8 +554,27 @@ struct AttnFwdIndexed {
   int R;
   float* Te;
 };
+// The saved buffer of the indexed training forward: alpha [E, H] | ssum [N, H], each on a 256-byte boundary of a 256-byte
+// aligned buffer.  No Z and no S: the backward forms z again from the three rows, and S [N, H Hd] -- 4 % of the dense
+// route's saved buffer by itself -- again with the forward's own launch of edge_idx_wsum on the same inputs (the same bits).
+static size_t idx_round64(size_t n) { return (n + 63) / 64 * 64; }
+extern "C" size_t cgat_nodes_attention_indexed_saved_floats(int32_t N, int32_t E, int32_t H, int32_t Hd) {
+  (void)Hd;
+  return idx_round64((size_t)E * H) + (size_t)N * H;
+}
+static AttnSaved attn_saved_indexed(float* saved, const AttnDims& d, float* S) {
+  AttnSaved s;
+  s.Z = nullptr;
+  s.alpha = saved;
+  s.S = S;           // a workspace carve-out of the pass
+  s.ssum = s.alpha + idx_round64((size_t)d.E * d.H);
+  return s;
+}
+// train: alpha and ssum live in the caller's saved buffer (`saved`; a dry pass has none) instead of the workspace; S stays
+// a carve-out at the place the forward without grad has it (the same fc_out_M route, the same bits)
 static AttnFwdIndexed attn_fwd_indexed_carve(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x,
-                                             const float* table, int R, const int64_t* index, float* aggr) {
+                                             const float* table, int R, const int64_t* index, float* aggr,
+                                             bool train = false, float* saved = nullptr) {
   AttnFwdIndexed g = {};
   AttnFwd& f = g.f;
   const AttnDims d = f.d = attn_dims(plan, p);
@@ -568,9 +587,14 @@ static AttnFwdIndexed attn_fwd_indexed_carve(Ctx& c, const cgat_plan* plan, cons
   g.Te = c.take<float>((size_t)R * d.W2);
   f.Wq = c.take<float>(2 * edge_z_wq_floats(d.W2));   // the images of W_i and W_j, made in one launch
   f.a = c.take<float>((size_t)d.E * d.H);            // the logits and alpha: all that grows with E
-  f.sv.alpha = c.take<float>((size_t)d.E * d.H);
-  f.sv.S = c.take<float>((size_t)d.N * d.HHd);
-  f.sv.ssum = c.take<float>((size_t)d.N * d.H);
+  if (train) {
+    float* S = c.take<float>((size_t)d.N * d.HHd);
+    if (!c.dry) f.sv = attn_saved_indexed(saved, d, S);
+  } else {
+    f.sv.alpha = c.take<float>((size_t)d.E * d.H);
+    f.sv.S = c.take<float>((size_t)d.N * d.HHd);
+    f.sv.ssum = c.take<float>((size_t)d.N * d.H);
+  }
   c.seal();
   f.r = attn_fwd_route(c.dry, d, true, p, x, nullptr, nullptr, f.sv.S, aggr, f.Pi);   // proj_fast, out_fast, out_one
   return g;
@@ -632,16 +656,18 @@ static int attn_fwd_out_indexed(Ctx& c, const AttnFwd& f) {
   g.beta = 1.f / d.H;
   return c.gemm(g);
 }
+// (train: the training forward -- the same steps, alpha and ssum kept for the backward)
 static int attn_infer_indexed_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x,
-                                   const float* table, int R, const int64_t* index, float* aggr) {
-  const AttnFwdIndexed g = attn_fwd_indexed_carve(c, plan, p, x, table, R, index, aggr);
+                                   const float* table, int R, const int64_t* index, float* aggr, bool train = false,
+                                   float* saved = nullptr) {
+  const AttnFwdIndexed g = attn_fwd_indexed_carve(c, plan, p, x, table, R, index, aggr, train, saved);
   const AttnFwd& f = g.f;
   CGAT_TRY(stack_in_weights(c, p, f.d, f.Wcat, f.bcat));
   CGAT_TRY(node_projections_indexed(c, g));
   CGAT_TRY(indexed_edge_table(c, g));
   CGAT_TRY(attn_fwd_edges_indexed(c, g));
   CGAT_TRY(attn_fwd_out_indexed(c, f));
-  return check_ws(c, "nodes_attention_infer_indexed");
+  return check_ws(c, train ? "nodes_attention_forward_indexed" : "nodes_attention_infer_indexed");
 }
 
 // ---- the operand-split first layer's backward tail ----
@@ -1009,6 +1035,124 @@ static int attn_backward_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_par
   return check_ws(c, "nodes_attention_backward");
 }
 
+// ---- the backward of the indexed training forward (reference CGAT.py:319-329 + PyG aggregate, on edge_attr = table[index]) ----
+// No Z and no S were stored: Pi, Pj, Te and then S are formed again by the forward's launches on the forward's inputs (the
+// same bits) and the segment backward forms z from them (edgeidx.hip).  grad edge_attr and grad W_e are linear in e, and e takes R
+// values: with gT[r, :] = the sum of the gZ rows of class r, grad table = gT W_e and grad W_e = gT^T table -- two products
+// over R rows in place of the two per-edge products.  The node-side products run without the f16x3 maxima (this segment
+// backward folds none): in that mode they take the form that needs none, bf16x6.
+static bool attn_train_indexed_ok(const AttnDims& d, int R) {
+  return edge_storage() == 0 && d.N > 0 && d.E > 0 && edge_idx_train_ok(d.H, d.Hd, R);
+}
+struct AttnClassPlan {          // built once per (index, plan) by cgat_indexed_class_plan
+  const int32_t *cls_pos, *piece_rowptr, *piece_start;
+};
+struct AttnBwdIndexed {
+  AttnBwd b;                    // e == nullptr, g_e == nullptr; gZ: the mask words
+  AttnFwdIndexed g;             // the recomputation: Wcat, bcat, Pi, Pj, Te, Wq
+  AttnClassPlan cls;
+  float *g_table, *gT, *cpart;
+};
+static AttnBwdIndexed attn_bwd_indexed_carve(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                             const float* table, int R, const int64_t* index, const AttnClassPlan& cls,
+                                             const float* saved, const float* g_aggr, float* g_x, float* g_table,
+                                             const cgat_attn_grads* gr) {
+  AttnBwdIndexed q = {};
+  AttnBwd& b = q.b;
+  AttnFwd& f = q.g.f;
+  const AttnDims d = b.d = f.d = attn_dims(plan, p);
+  b.plan = f.plan = plan; b.p = f.p = p; b.gr = gr; b.x = f.x = x; b.g_aggr = g_aggr; b.g_x = g_x;
+  q.g.table = table; q.g.index = index; q.g.R = R; q.cls = cls; q.g_table = g_table;
+  b.chunks = edge_idx_bwd_chunks(d.N);
+  b.Wcat = f.Wcat = c.take<float>((size_t)d.W2 * d.D);
+  float* S = c.take<float>((size_t)d.N * d.HHd);                      // formed again by the forward's launch
+  if (!c.dry) b.sv = attn_saved_indexed(const_cast<float*>(saved), d, S);
+  f.bcat = c.take<float>((size_t)d.W2);
+  b.gWcat = c.take<float>((size_t)d.W2 * d.D);
+  b.gbcat = c.take<float>((size_t)d.W2);
+  b.gS = c.take<float>((size_t)d.N * d.HHd);
+  b.gs = c.take<float>((size_t)d.N * d.H);
+  b.gas = mode_split() ? c.take<float>((size_t)d.N * d.C) : nullptr;
+  b.tt = c.take<float>((size_t)d.E * d.H);
+  b.ga = c.take<float>((size_t)d.E * d.H);
+  b.gZ = c.take<float>((size_t)d.E * (d.W2 / 32));                    // the sign words, EdgeRC's layout
+  b.partial = c.take<float>((size_t)b.chunks * d.HHd);
+  b.Gi = c.take<float>((size_t)d.N * d.W2);
+  b.Gj = c.take<float>((size_t)d.N * d.W2);
+  f.Pi = c.take<float>((size_t)d.N * d.W2);
+  f.Pj = c.take<float>((size_t)d.N * d.W2);
+  q.g.Te = c.take<float>((size_t)R * d.W2);
+  b.Wq = f.Wq = c.take<float>(2 * edge_z_wq_floats(d.W2));            // the projections' images, then the tail's
+  b.gw_ws = c.take<float>(edge_gw_ws_floats(d.N, d.W2));              // (the node-side weight gradients: N rows)
+  q.gT = c.take<float>((size_t)R * d.W2);
+  q.cpart = c.take<float>((size_t)edge_idx_class_pieces(d.E, R) * d.W2);
+  c.seal();
+  b.r = attn_bwd_route(c.dry, d, p, x, nullptr, saved, b.sv.S, b.Wcat);   // out_fast, out_heads_one
+  f.r = attn_fwd_route(c.dry, d, true, p, x, nullptr, nullptr, b.sv.S, nullptr, f.Pi);   // proj_fast, as the forward
+  if (!c.dry)
+    b.rc = edge_rc_make(reinterpret_cast<const unsigned*>(b.gZ), b.ga, b.sv.alpha, b.gS, p->A_out_w, plan->dst_sorted, d.H, d.Hd);
+  return q;
+}
+// tt, ga, the sign words, Gi and the partial rows of grad fc_out_A.weight on recomputed z; then grad fc_out_A
+static int attn_bwd_segments_indexed(Ctx& c, const AttnBwdIndexed& q) {
+  const AttnBwd& b = q.b;
+  const AttnFwd& f = q.g.f;
+  const AttnDims& d = b.d;
+  CGAT_CHECK_ARG(c.dry || aligned16(b.p->A_out_w, b.sv.alpha),
+                 "nodes_attention_backward_indexed: saved and MH_A.fc_out.weight must be 16-byte aligned");
+  RUN(edge_idx_bwd_launch(q.g.Te, q.g.R, q.g.index, b.plan->dst_perm, f.Pi, f.Pj, b.plan->src_sorted, d.W2, b.sv.alpha, b.gS,
+                          b.gs, b.p->A_out_w, d.H, d.Hd, b.plan->dst_rowptr, d.N, d.E, b.tt, b.ga,
+                          reinterpret_cast<unsigned*>(b.gZ), b.Gi, b.partial, c.s));
+  CGAT_TRY(c.colsum(b.ga, d.H, d.E, d.H, b.gr->A_out_b, 1.f));
+  return c.colsum(b.partial, d.HHd, b.chunks, d.HHd, b.gr->A_out_w, 1.f);
+}
+static EdgeTail attn_bwd_tail_indexed(const AttnBwdIndexed& q) {
+  const AttnBwd& b = q.b;
+  EdgeTail t = {};
+  t.gZ = {nullptr, b.d.W2, 0};
+  t.Gi = b.Gi; t.Gj = b.Gj; t.have_Gi = true;
+  t.Wcat = b.Wcat; t.gWcat = b.gWcat; t.gbcat = b.gbcat;
+  t.Wq = b.Wq; t.gw_ws = b.gw_ws;
+  t.scales = nullptr;            // no maxima on this route: the node-side products in the form that needs none
+  t.rc = &b.rc;
+  t.x = b.x; t.g_x = b.g_x;
+  return t;
+}
+// gT, then grad table = gT W_e and grad W_e = gT^T table (into the W_e columns of gWcat)
+static int attn_bwd_class_products(Ctx& c, const AttnBwdIndexed& q) {
+  const AttnBwd& b = q.b;
+  const AttnDims& d = b.d;
+  RUN(edge_idx_class_sum_launch(b.rc, q.cls.piece_rowptr, q.cls.piece_start, q.cls.cls_pos, q.g.R, d.E, d.W2, q.cpart, q.gT,
+                                c.s));
+  GemmParams g = gemm_params(q.g.R, d.Ce, d.W2, q.gT, d.W2, b.Wcat + d.C, d.D, q.g_table, d.Ce);
+  g.b_kmajor = 1;
+  CGAT_TRY(c.gemm(g));
+  g = gemm_params(d.W2, d.Ce, q.g.R, q.gT, d.W2, q.g.table, d.Ce, b.gWcat + d.C, d.D);
+  g.a_kmajor = 1; g.b_kmajor = 1;
+  return c.gemm(g);
+}
+static int attn_backward_indexed_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                      const float* table, int R, const int64_t* index, const AttnClassPlan& cls,
+                                      const float* saved, const float* g_aggr, float* g_x, float* g_table,
+                                      const cgat_attn_grads* gr) {
+  const AttnBwdIndexed q = attn_bwd_indexed_carve(c, plan, p, x, table, R, index, cls, saved, g_aggr, g_x, g_table, gr);
+  const AttnBwd& b = q.b;
+  CGAT_TRY(stack_in_weights(c, p, b.d, b.Wcat, q.g.f.bcat));
+  CGAT_TRY(node_projections_indexed(c, q.g));
+  CGAT_TRY(indexed_edge_table(c, q.g));
+  RUN(edge_idx_wsum_launch(q.g.Te, R, index, plan->dst_perm, q.g.f.Pi, q.g.f.Pj, plan->src_sorted, b.d.W2, b.sv.alpha, b.d.H,
+                           b.d.Hd, plan->dst_rowptr, b.d.N, b.d.E, b.sv.S, c.s));   // S, not saved: the forward's bits
+  CGAT_TRY(attn_bwd_out_layer(c, b));
+  CGAT_TRY(attn_bwd_segments_indexed(c, q));
+  const EdgeTail t = attn_bwd_tail_indexed(q);
+  const TailRoute r = tail_route(c.dry, b.d, t);
+  RUN(edge_gj_launch(b.rc, plan->src_rowptr, plan->src_pos, b.d.N, b.d.W2, b.Gj, b.d.W2, c.s, nullptr));
+  CGAT_TRY(tail_node_products(c, b.d, t, r));
+  CGAT_TRY(attn_bwd_class_products(c, q));
+  CGAT_TRY(attn_bwd_scatter_grads(c, b));
+  return check_ws(c, "nodes_attention_backward_indexed");
+}
+
 // =======================================================================================
 // edge_hidden: H[t, :] = LeakyReLU( W_in [x_i ; edge_attr ; x_j] + b ) for all heads of any number of message networks
 // stacked in W_in [W2, D], rows in destination-sorted slot order t (plan->dst_perm).  The first layer of
@@ -1205,6 +1349,95 @@ extern "C" int cgat_nodes_attention_infer_indexed(const cgat_plan* plan, const c
   CGAT_CHECK_ARG(x && table && index && aggr, "nodes_attention_infer_indexed: null operand");
   return run_sized("nodes_attention_infer_indexed", ws, ws_bytes, stream,
                    [&](Ctx& c) { return attn_infer_indexed_impl(c, plan, p, x, table, R, index, aggr); });
+}
+// ---- the indexed training route (include/cgat_hip.h) ----
+extern "C" int32_t cgat_nodes_attention_train_indexed_ok(const cgat_plan* plan, const cgat_attn_params* p, int32_t R) {
+  if (attn_check(plan, p) != CGAT_OK) return 0;
+  return attn_train_indexed_ok(attn_dims(plan, p), R) ? 1 : 0;
+}
+static int train_indexed_refuse(const char* who, const cgat_plan* plan, const cgat_attn_params* p, int R) {
+  cgat_set_error("%s: not taken for N %d, E %d, H %d, Hd %d, R %d under edge storage %d "
+                 "(cgat_nodes_attention_train_indexed_ok); densify and call the dense entry", who, plan->N, plan->E, p->H, p->Hd,
+                 R, edge_storage());
+  return CGAT_ERR_UNSUPPORTED;
+}
+extern "C" size_t cgat_nodes_attention_forward_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p,
+                                                                       int32_t R) {
+  if (R < 1) R = 1;
+  return dry_total([&](Ctx& c) { return attn_infer_indexed_impl(c, plan, p, nullptr, nullptr, R, nullptr, nullptr, true); });
+}
+extern "C" int cgat_nodes_attention_forward_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                                    const float* table, int32_t R, const int64_t* index, float* aggr,
+                                                    float* saved, void* ws, size_t ws_bytes, void* stream) {
+  CGAT_TRY(attn_check(plan, p));
+  if (!attn_train_indexed_ok(attn_dims(plan, p), R)) return train_indexed_refuse("nodes_attention_forward_indexed", plan, p, R);
+  CGAT_CHECK_ARG(x && table && index && aggr && saved && (((uintptr_t)saved) & 255) == 0,
+                 "nodes_attention_forward_indexed: null operand, or saved not on a 256-byte boundary");
+  return run_sized("nodes_attention_forward_indexed", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return attn_infer_indexed_impl(c, plan, p, x, table, R, index, aggr, true, saved); });
+}
+extern "C" size_t cgat_nodes_attention_backward_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p,
+                                                                        int32_t R) {
+  if (R < 1) R = 1;
+  cgat_attn_grads g = {};
+  const AttnClassPlan cls = {};
+  return dry_total([&](Ctx& c) {
+    return attn_backward_indexed_impl(c, plan, p, nullptr, nullptr, R, nullptr, cls, nullptr, nullptr, nullptr, nullptr, &g);
+  });
+}
+extern "C" int cgat_nodes_attention_backward_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                                     const float* table, int32_t R, const int64_t* index,
+                                                     const int32_t* cls_pos, const int32_t* piece_rowptr,
+                                                     const int32_t* piece_start, const float* saved, const float* g_aggr,
+                                                     float* g_x, float* g_table, const cgat_attn_grads* g, void* ws,
+                                                     size_t ws_bytes, void* stream) {
+  CGAT_TRY(attn_check(plan, p));
+  if (!attn_train_indexed_ok(attn_dims(plan, p), R)) return train_indexed_refuse("nodes_attention_backward_indexed", plan, p, R);
+  CGAT_CHECK_ARG(x && table && index && cls_pos && piece_rowptr && piece_start && saved && g_aggr && g_x && g_table && g &&
+                 (((uintptr_t)saved) & 255) == 0,
+                 "nodes_attention_backward_indexed: null operand, or saved not on a 256-byte boundary");
+  const AttnClassPlan cls = {cls_pos, piece_rowptr, piece_start};
+  return run_sized("nodes_attention_backward_indexed", ws, ws_bytes, stream, [&](Ctx& c) {
+    return attn_backward_indexed_impl(c, plan, p, x, table, R, index, cls, saved, g_aggr, g_x, g_table, g);
+  });
+}
+// the class grouping of the slots (edgeidx.hip): cls_pos [E] = the slots of class 0, 1, ... in ascending slot order,
+// piece_start [R + 1], piece_rowptr [cgat_indexed_class_pieces(E, R) + 1]; once per (index, plan), outside the hot path
+extern "C" int32_t cgat_indexed_class_pieces(int32_t E, int32_t R) { return edge_idx_class_pieces(E, R); }
+extern "C" size_t cgat_indexed_class_plan_workspace_bytes(int32_t E, int32_t R) { return edge_idx_class_plan_ws_bytes(E, R) + 256; }
+extern "C" int cgat_indexed_class_plan(const cgat_plan* plan, const int64_t* index, int32_t R, int32_t* cls_pos,
+                                       int32_t* piece_start, int32_t* piece_rowptr, void* ws, size_t ws_bytes, void* stream) {
+  CGAT_CHECK_ARG(plan && plan->E > 0, "indexed_class_plan: null plan or no edges");
+  return edge_idx_class_plan_launch(index, plan->dst_perm, plan->E, R, cls_pos, piece_start, piece_rowptr, ws, ws_bytes,
+                                    (hipStream_t)stream);
+}
+// debug: the signs of z as this route forms it, uint8 [E, W2] in original edge order: the projections and Te by the
+// forward's launches, z by idx_z
+static int debug_signs_indexed_impl(Ctx& c, const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                    const float* table, int R, const int64_t* index, uint8_t* mask) {
+  const AttnFwdIndexed g = attn_fwd_indexed_carve(c, plan, p, x, table, R, index, nullptr);
+  const AttnFwd& f = g.f;
+  CGAT_TRY(stack_in_weights(c, p, f.d, f.Wcat, f.bcat));
+  CGAT_TRY(node_projections_indexed(c, g));
+  CGAT_TRY(indexed_edge_table(c, g));
+  RUN(edge_idx_signs_launch(g.Te, R, index, plan->dst_perm, f.Pi, f.Pj, plan->src_sorted, plan->dst_sorted, f.d.W2, (long)f.d.E,
+                            mask, c.s));
+  return check_ws(c, "debug_nodes_attention_signs_indexed");
+}
+extern "C" size_t cgat_debug_nodes_attention_signs_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p,
+                                                                           int32_t R) {
+  if (R < 1) R = 1;
+  return dry_total([&](Ctx& c) { return debug_signs_indexed_impl(c, plan, p, nullptr, nullptr, R, nullptr, nullptr); });
+}
+extern "C" int cgat_debug_nodes_attention_signs_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                                        const float* table, int32_t R, const int64_t* index, uint8_t* mask,
+                                                        void* ws, size_t ws_bytes, void* stream) {
+  CGAT_TRY(attn_check(plan, p));
+  if (!attn_train_indexed_ok(attn_dims(plan, p), R))
+    return train_indexed_refuse("debug_nodes_attention_signs_indexed", plan, p, R);
+  CGAT_CHECK_ARG(x && table && index && mask, "debug_nodes_attention_signs_indexed: null operand");
+  return run_sized("debug_nodes_attention_signs_indexed", ws, ws_bytes, stream,
+                   [&](Ctx& c) { return debug_signs_indexed_impl(c, plan, p, x, table, R, index, mask); });
 }
 extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
                                              const float* edge_attr, const float* saved, const float* g_aggr,

@@ -567,6 +567,16 @@ int attn_signs_launch(const float* Z, const int* perm, long E, int W2, uint8_t* 
 
 int edge_seg_bwd_chunks(int N) { return cdiv(N > 0 ? N : 1, SEGB_NODES); }
 
+// step 2 alone, for the indexed training route (edgeidx.hip), whose steps 1 and 3 form z instead of reading Z
+int seg_bwd_soft_launch(const float* alpha, const float* tt, const int* rowptr, int N, int H, float* ga, hipStream_t stream) {
+  CGAT_CHECK_ARG(H >= 1 && H <= 16, "seg_bwd_soft: more than 16 heads");
+  if (N <= 0) return CGAT_OK;
+  CGAT_PROF("edge_idx_bwd_soft", stream);
+  hipLaunchKernelGGL(seg_bwd_soft_kernel, dim3(edge_seg_bwd_chunks(N)), dim3(256), 0, stream, alpha, tt, rowptr, N, H, ga);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+
 // the three small kernels (<= 64 VGPRs: they co-reside with the side stream's dT workgroups); bit-identical results
 template <bool ZB>
 static int seg_bwd_three_launch(const float* Z, const float* alpha, const float* gS, const float* gs, const int* rowptr,

@@ -87,6 +87,29 @@ def note_attention(a_in_w, m_in_w, plan, attn_params, saved, W2):
     note(m_in_w, mask[:, half:] != 0)
 
 
+def note_attention_indexed(a_in_w, m_in_w, plan, attn_params, x, table, index):
+    """The scalar-attention layer on the indexed training route (ops.NodesAttentionIndexedFn), which stores no
+    pre-activations: their signs from x, table, index and the parameters through the forward's projections and the one
+    function that forms z for the forward and the backward (cgat_debug_nodes_attention_signs_indexed), original edge
+    order; noted as note_attention notes them."""
+    if _active is None:
+        return
+    from . import ops
+    R, W2 = int(table.shape[0]), 2 * attn_params.H * attn_params.Hd
+    mask = torch.empty(plan.E, W2, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = ops.workspace(lib.cgat_debug_nodes_attention_signs_indexed_workspace_bytes(C.byref(plan.c), C.byref(attn_params),
+                                                                                        R), x.device)
+        check(lib.cgat_debug_nodes_attention_signs_indexed(C.byref(plan.c), C.byref(attn_params), C.c_void_p(x.data_ptr()),
+                                                           C.c_void_p(table.data_ptr()), R, C.c_void_p(index.data_ptr()),
+                                                           C.c_void_p(mask.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              "cgat_debug_nodes_attention_signs_indexed")
+    half = W2 // 2
+    note(a_in_w, mask[:, :half] != 0)
+    note(m_in_w, mask[:, half:] != 0)
+
+
 def note_sorted_hidden(weights, plan, hidden):
     """EdgeHiddenFn's output (post-activation, destination-sorted slots) -> per-network masks in original edge order.
     `weights`: the first-layer weights of the stacked networks, equal column shares of `hidden`."""

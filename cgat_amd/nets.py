@@ -23,6 +23,7 @@ from .ops import (AttentionPoolFn, attention_pool, get_fused_attention_dropout, 
 from .ops import overlap_enabled as ops_overlap_enabled
 from .ops import HNetFn, infer_route, nodes_attention_infer
 from .ops import IndexedEdgeAttr, get_indexed_edge_attr, indexed_route, nodes_attention_infer_indexed
+from .ops import NodesAttentionIndexedFn, NodeLayerIndexedFn, train_indexed_route
 from .ops import EdgeHeadCombineFn, edge_combine_route
 from .ops import branch_stream
 from .roost import Roost
@@ -263,22 +264,27 @@ class GATConvNodes(nn.Module):
 
     def _aggregate_fused(self, x, edge_attr, plan):
         params = self._attn_params()
-        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route)
-            return nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *params)
+        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route: one of the two holds)
+            if infer_route(x, edge_attr.table, params):
+                return nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *params)
+            return NodesAttentionIndexedFn.apply(x, edge_attr.table, edge_attr.index, plan, self.heads, *params)
         if infer_route(x, edge_attr, params):
             return nodes_attention_infer(x, edge_attr, plan, self.heads, *params)
         return NodesAttentionFn.apply(x, edge_attr, plan, self.heads, *params)
 
     def _indexed_route(self, x, edge_index, edge_attr):
-        """True when this call, given an IndexedEdgeAttr, runs ops.nodes_attention_infer_indexed in place of
-        nodes_attention_infer: scalar attention, one unchunked pass, no training-mode dropout, message / update the
-        layer's own, no backward to follow and no debug recording (ops.infer_route), and a shape the library takes in
-        the current arithmetic and edge-storage modes.  Everything else densifies and runs as it always has."""
+        """True when this call, given an IndexedEdgeAttr, keeps it: scalar attention, one unchunked pass, no training-mode
+        dropout, message / update the layer's own, and either no backward to follow and no debug recording
+        (ops.infer_route: ops.nodes_attention_infer_indexed runs) or a backward to follow under
+        ops.set_indexed_edge_training (ops.NodesAttentionIndexedFn / NodeLayerIndexedFn run), at a shape the library takes
+        for that route in the current arithmetic and edge-storage modes.  Everything else densifies and runs as it
+        always has."""
         if (self.vector_attention or not torch.is_tensor(x) or (self.dropout and self.training) or
                 type(self).message is not GATConvNodes.message or type(self).update is not GATConvNodes.update or
                 edge_index.shape[1] > chunked.max_edges_per_pass() or not x.is_cuda):
             return False
-        return indexed_route(x, edge_attr, get_plan(edge_index, x.shape[0]), self.heads, self._attn_params())
+        plan, params = get_plan(edge_index, x.shape[0]), self._attn_params()
+        return indexed_route(x, edge_attr, plan, self.heads, params) or train_indexed_route(x, edge_attr, plan, self.heads, params)
 
     # -- vector attention (CGAT.py:286-290: MH_A emits one logit per head AND channel): the shared first layer of both
     #    networks runs as one operand-split op in destination-sorted order, so the concatenated message [E, 2C+Ce],
@@ -360,9 +366,12 @@ class GATConvNodes(nn.Module):
             with torch.no_grad():
                 pool.damping.data = pool.damping.data.clamp(0.0, 1.0)      # Hypernetworksmp.py:307, as H_Net.forward
             h0, damping = x_0, pool.damping
-        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route, infer_route included)
-            aggr = nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *self._attn_params())
-            return HNetFn.apply(h0, aggr, damping, hyper.n_fc, len(hyper.layers), *flat)
+        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route: one of the two holds)
+            if infer_route(x, edge_attr.table, self._attn_params()):
+                aggr = nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *self._attn_params())
+                return HNetFn.apply(h0, aggr, damping, hyper.n_fc, len(hyper.layers), *flat)
+            return NodeLayerIndexedFn.apply(x, edge_attr.table, edge_attr.index, h0, plan, self.heads, damping, hyper.n_fc,
+                                            len(hyper.layers), *self._attn_params(), *flat)
         if infer_route(x, edge_attr, self._attn_params()):
             # the attention half without grad; the hypernetwork as its own node (NodeLayerFn's forward runs the same call)
             aggr = nodes_attention_infer(x, edge_attr, plan, self.heads, *self._attn_params())

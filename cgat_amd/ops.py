@@ -453,6 +453,161 @@ def nodes_attention_infer_indexed(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w
     return aggr
 
 
+_indexed_edge_training = os.environ.get("CGAT_INDEXED_EDGE_TRAIN", "0") == "1"
+
+
+def set_indexed_edge_training(flag):
+    """The training route of shell-indexed edge features (default off; env CGAT_INDEXED_EDGE_TRAIN=1 starts it on): a
+    scalar-attention node layer given an IndexedEdgeAttr WITH a backward to follow runs NodesAttentionIndexedFn -- no
+    [E, Ce] edge features, no stored pre-activations, grad table and grad W_e from a per-class sum -- where the library
+    takes the shape (train_indexed_ok).  It matters only where an IndexedEdgeAttr reaches the layer: through CGAtNet that
+    needs set_indexed_edge_attr(True) too.  Off: such a layer densifies and runs the dense training launches, bit for bit."""
+    global _indexed_edge_training
+    _indexed_edge_training = bool(flag)
+
+
+def get_indexed_edge_training():
+    return _indexed_edge_training
+
+
+def train_indexed_ok(plan_c, C_, Ce, H, Hd, R):
+    """cgat_nodes_attention_train_indexed_ok for a layer of these dims in the current arithmetic and edge-storage modes
+    (host only; plan_c: the C struct of a plan)."""
+    p = _lib.AttnParams(int(C_), int(Ce), int(H), int(Hd), *([None] * 8))
+    return bool(lib.cgat_nodes_attention_train_indexed_ok(C.byref(plan_c), C.byref(p), int(R)))
+
+
+def train_indexed_route(x, edge_attr, plan, H, params):
+    """True when a scalar-attention node layer given an IndexedEdgeAttr takes NodesAttentionIndexedFn: the switch is on, a
+    backward can follow (grad mode on and something involved requires grad), and the library takes the shape in the
+    current modes.  A debug recording does not leave this route (debug.note_attention_indexed)."""
+    if not _indexed_edge_training or not torch.is_grad_enabled():
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        return False
+    table, index = edge_attr.table, edge_attr.index
+    # (what _attn_forward_indexed would refuse densifies instead, like every other ineligible call; a non-contiguous index
+    # would be copied per call and never find its class plan again)
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and
+            torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int64 and index.dim() == 1 and
+            index.is_contiguous() and index.shape[0] == plan.E and x.shape[0] == plan.N):
+        return False
+    if not any(t is not None and t.requires_grad for t in (x, table, *params)):
+        return False
+    A_in_w, A_out_w = params[0], params[2]
+    HHd = A_in_w.shape[0]
+    if HHd % H or A_out_w.numel() != HHd:                 # vector attention
+        return False
+    return train_indexed_ok(plan.c, x.shape[1], edge_attr.table.shape[1], H, HHd // H, edge_attr.table.shape[0])
+
+
+def _class_plan(index, plan, R):
+    """The grouping of a plan's destination-sorted slots by class for the class sum of the indexed backward: (cls_pos [E],
+    piece_rowptr, piece_start [R + 1]) -- a stable counting sort of the slots by index[dst_perm] (clamped as the kernels
+    clamp) and the fixed 256-row pieces of every class (cgat_indexed_class_plan).  Built once per (index, plan), in a forward outside any capture; shared by all
+    layers and by IndexedEdgeAttr.with_table copies (the key is the index tensor)."""
+    cache = plan.__dict__.setdefault("_class_plans", {})
+    key = (index.data_ptr(), index._version, int(index.numel()), int(R))
+    cp = cache.get(key)
+    if cp is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("cgat_amd: the class plan of an IndexedEdgeAttr must be built before a capture "
+                               "(run one eager forward of the layer first)")
+        dev, E = index.device, plan.E
+        i32 = dict(dtype=torch.int32, device=dev)
+        cls_pos = torch.empty(E, **i32)
+        n_pieces = lib.cgat_indexed_class_pieces(E, R)
+        piece_start, piece_rowptr = torch.empty(R + 1, **i32), torch.empty(n_pieces + 1, **i32)
+        with torch.cuda.device(dev):
+            ws = workspace(lib.cgat_indexed_class_plan_workspace_bytes(E, R), dev)
+            check(lib.cgat_indexed_class_plan(C.byref(plan.c), _ptr(index), R, _ptr(cls_pos), _ptr(piece_start),
+                                              _ptr(piece_rowptr), _ptr(ws), ws.numel(), _stream()), "cgat_indexed_class_plan")
+        cp = (cls_pos, piece_rowptr, piece_start, index)          # (the index is kept alive: its address is the key)
+        if len(cache) >= 4:
+            cache.pop(next(iter(cache)))
+        cache[key] = cp
+    return cp[:3]
+
+
+def _attn_forward_indexed(x, table, index, plan, H, weights):
+    """cgat_nodes_attention_forward_indexed behind NodesAttentionIndexedFn and NodeLayerIndexedFn.  Everything is checked
+    before the first launch.  Returns (aggr, saved, the prepared operands x, table, index, weights, the class plan)."""
+    if not (torch.is_tensor(table) and torch.is_tensor(index)):
+        raise TypeError("NodesAttentionIndexedFn(x, table, index, ...) takes tensors")
+    _require_gpu(x, table, index, *weights)
+    if table.dtype != torch.float32 or table.dim() != 2:
+        raise TypeError(f"indexed attention: table must be float32 [R, Ce], got {table.dtype} {tuple(table.shape)}")
+    if index.dtype != torch.int64 or index.dim() != 1:
+        raise TypeError(f"indexed attention: index must be int64 [E], got {index.dtype} {tuple(index.shape)}")
+    A_in_w, A_out_w, M_in_w = weights[0], weights[2], weights[4]
+    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
+        raise ValueError("NodesAttentionIndexedFn handles scalar attention (MH_A output_dim == 1)")
+    N, E, R = plan.N, plan.E, int(table.shape[0])
+    if x.shape[0] != N or index.shape[0] != E:
+        raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, index {tuple(index.shape)}")
+    if not index.is_contiguous():                         # (a copy per call would never find its class plan again)
+        raise ValueError("indexed attention: index must be contiguous")
+    x, table = _f32c(x.detach()), _f32c(table.detach())
+    ws_ = [_f32c(w.detach()) for w in weights]
+    p, Hd = _attn_params(x, table, H, ws_)
+    if not lib.cgat_nodes_attention_train_indexed_ok(C.byref(plan.c), C.byref(p), R):
+        raise ValueError(f"NodesAttentionIndexedFn: H {H}, Hd {Hd}, R {R} is not taken in the current arithmetic / "
+                         "edge-storage modes (ops.train_indexed_ok); densify")
+    dev = x.device
+    cls = _class_plan(index, plan, R)
+    # (its exact size: E * H + N * H floats and padding -- alpha and ssum, all a layer keeps for its backward)
+    saved = torch.empty(lib.cgat_nodes_attention_indexed_saved_floats(N, E, H, Hd), dtype=torch.float32, device=dev)
+    aggr = torch.empty(N, x.shape[1], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_nodes_attention_forward_indexed_workspace_bytes(C.byref(plan.c), C.byref(p), R), dev)
+        check(lib.cgat_nodes_attention_forward_indexed(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(table), R, _ptr(index),
+                                                       _ptr(aggr), _ptr(saved), _ptr(ws), ws.numel(), _stream()),
+              "cgat_nodes_attention_forward_indexed")
+    if debug.recording():
+        debug.note_attention_indexed(A_in_w, M_in_w, plan, p, x, table, index)
+    return aggr, saved, x, table, index, ws_, cls
+
+
+def _attn_backward_indexed(x, table, index, cls, plan, H, weights, saved, g_aggr, stream):
+    """cgat_nodes_attention_backward_indexed on `stream` (a raw handle).  Builds and validates nothing.  Returns (g_x,
+    g_table, parameter grads)."""
+    g_aggr = _f32c(g_aggr)
+    p, _ = _attn_params(x, table, H, weights)
+    dev, R = x.device, int(table.shape[0])
+    g_x, g_t = torch.empty_like(x), torch.empty_like(table)
+    grads = [_param_grad(w) for w in weights]
+    g = _lib.AttnGrads(*[t.data_ptr() for t in grads])
+    cls_pos, piece_rowptr, piece_start = cls
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_nodes_attention_backward_indexed_workspace_bytes(C.byref(plan.c), C.byref(p), R), dev)
+        check(lib.cgat_nodes_attention_backward_indexed(C.byref(plan.c), C.byref(p), _ptr(x), _ptr(table), R, _ptr(index),
+                                                        _ptr(cls_pos), _ptr(piece_rowptr), _ptr(piece_start), _ptr(saved),
+                                                        _ptr(g_aggr), _ptr(g_x), _ptr(g_t), C.byref(g), _ptr(ws), ws.numel(),
+                                                        stream), "cgat_nodes_attention_backward_indexed")
+    return g_x, g_t, grads
+
+
+class NodesAttentionIndexedFn(torch.autograd.Function):
+    """NodesAttentionFn for edge_attr = table[index] (reference CGAT.py:319-329 on the lookup of 569 / 583) without the
+    [E, Ce] edge features and without stored pre-activations: the forward is nodes_attention_infer_indexed's, bit for bit,
+    keeping alpha and ssum; the backward forms S and z again from three gathered rows and returns g_x, g_table (the embedding
+    backward included) and the eight parameter gradients."""
+
+    @staticmethod
+    def forward(ctx, x, table, index, plan, H, A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b):
+        weights = [A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b]
+        aggr, saved, x, table, index, weights, cls = _attn_forward_indexed(x, table, index, plan, H, weights)
+        ctx.plan, ctx.H, ctx.cls = plan, H, cls
+        ctx.save_for_backward(x, table, index, saved, *weights)
+        return aggr
+
+    @staticmethod
+    def backward(ctx, g_aggr):
+        x, table, index, saved, *weights = ctx.saved_tensors
+        g_x, g_t, grads = _attn_backward_indexed(x, table, index, ctx.cls, ctx.plan, ctx.H, weights, saved, g_aggr, _stream())
+        return (g_x, g_t, None, None, None, *grads)
+
+
 def _edge_hidden_forward(who, x, edge_attr, plan, w_in, b_in):
     """cgat_edge_hidden_forward behind EdgeHiddenFn and EdgeHiddenHeadsFn.  Returns the prepared operands, hidden and
     hmax = max |hidden| (the fp16 scale of the second layers)."""
@@ -702,6 +857,58 @@ class NodeLayerFn(torch.autograd.Function):
             main.wait_stream(s2)     # every gradient is complete, in stream order, when this node returns
         del side_ws                  # (held until here: the side stream was using it)
         return (g_x, g_e, g_h0, None, None, g_d, None, None, *g_attn, *g_flat)
+
+
+def _overlapped_hnet_keeps_bits(v):
+    """True where cgat_hnet_backward_overlapped gives the bits of cgat_hnet_backward: the batched fp16 forms of the
+    weight-gradient contraction ("f16x3", "f16x3c" at width 128), whose row split does not follow the grid.  Under the
+    six-pass plane forms ("bf16x6", "bf16x3") the side stream's half-chip grid halves the split and the sums differ in the
+    last bits (test_hip_golden.py::test_side_stream_equals_serial holds NodeLayerFn to 1e-5 there)."""
+    return get_bilinear_mode() in ("f16x3", "f16x3c") and v.shape[1] == 128
+
+
+class NodeLayerIndexedFn(torch.autograd.Function):
+    """NodeLayerFn for edge_attr = table[index]: aggr = NodesAttentionIndexedFn, y = HyperFC(h0)(aggr) as ONE autograd node
+    with the same schedule -- the hypernetwork's weight-gradient contractions on the side stream beside the attention
+    backward, joined before returning -- wherever that schedule keeps the bits of the two separate nodes
+    (_overlapped_hnet_keeps_bits); elsewhere the two backward calls run one after the other.  Bit-equal to
+    NodesAttentionIndexedFn + HNetFn in every arithmetic mode."""
+
+    @staticmethod
+    def forward(ctx, x, table, index, h0, plan, H, damping, n_fc, n_hyper, *params):
+        _require_gpu(h0)
+        h0 = _f32c(h0)
+        if h0.shape != x.shape:
+            raise ValueError("NodeLayerIndexedFn: shapes do not match the plan")
+        aggr, saved_a, x, table, index, attn_w, cls = _attn_forward_indexed(x, table, index, plan, H, list(params[:8]))
+        y, saved_h, d, flat = _hnet_forward(h0, aggr, damping, n_fc, n_hyper, params[8:])
+        ctx.plan, ctx.H, ctx.n_fc, ctx.n_hyper, ctx.has_d, ctx.cls = plan, H, n_fc, n_hyper, d is not None, cls
+        ctx.save_for_backward(x, table, index, h0, aggr, saved_a, saved_h, *([d] if d is not None else []), *attn_w, *flat)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, table, index, h0, aggr, saved_a, saved_h, *rest = ctx.saved_tensors
+        d = rest.pop(0) if ctx.has_d else None
+        attn_w, flat = rest[:8], rest[8:]
+        dev = x.device
+        main = torch.cuda.current_stream(dev)
+        if not _overlapped_hnet_keeps_bits(aggr):
+            # the overlapped hypernetwork backward caps the grid of its weight-gradient launches; where that cap moves the
+            # row split of their sums (the six-pass plane forms, other widths) the serial call runs: HNetFn's bits
+            g_h0, g_aggr, g_d, g_flat, _ = _hnet_backward(h0, aggr, saved_h, d, flat, ctx.n_fc, ctx.n_hyper, g_y)
+            g_x, g_t, g_attn = _attn_backward_indexed(x, table, index, ctx.cls, ctx.plan, ctx.H, attn_w, saved_a, g_aggr,
+                                                      main.cuda_stream)
+            return (g_x, g_t, None, g_h0, None, None, g_d, None, None, *g_attn, *g_flat)
+        s2 = side_stream(dev)
+        g_h0, g_aggr, g_d, g_flat, side_ws = _hnet_backward(h0, aggr, saved_h, d, flat, ctx.n_fc, ctx.n_hyper, g_y,
+                                                            side=(main, s2))
+        g_x, g_t, g_attn = _attn_backward_indexed(x, table, index, ctx.cls, ctx.plan, ctx.H, attn_w, saved_a, g_aggr,
+                                                  main.cuda_stream)
+        with torch.cuda.device(dev):
+            main.wait_stream(s2)     # every gradient is complete, in stream order, when this node returns
+        del side_ws                  # (held until here: the side stream was using it)
+        return (g_x, g_t, None, g_h0, None, None, g_d, None, None, *g_attn, *g_flat)
 
 
 # ----------------------------------------------------------------------------------------

@@ -220,6 +220,51 @@ int cgat_nodes_attention_infer_indexed(const cgat_plan* plan, const cgat_attn_pa
                                        const int64_t* index /* [E], original edge order, values in [0,R) */,
                                        float* aggr /* out [N,C] */, void* ws, size_t ws_bytes, void* stream);
 
+/* The TRAINING form of the same route (replaces CGAT/CGAT.py:319-329 and its autograd backward on edge_attr =
+ * table[index], with the embedding backward of 569 / 583 folded in).  The forward runs the launches of
+ * cgat_nodes_attention_infer_indexed -- bit-identical aggr -- and keeps alpha [E,H] and ssum [N,H] in `saved`
+ * (cgat_nodes_attention_indexed_saved_floats floats, on a 256-byte boundary): E*H + N*H floats plus alignment padding, no
+ * pre-activations and no S.  The backward forms Pi, Pj, Te and S [N,H*Hd] again with the forward's launches on the same
+ * inputs (the same bits), forms z[t] = Te[index[perm[t]]] + Pi[dst[t]] + Pj[src[t]] where the dense backward reads Z, and
+ * replaces grad edge_attr / grad W_e by the class sum gT[r,:] = sum of the pre-activation gradients of class r:
+ * g_table = gT W_e [R,Ce] (the gradient wrt table, embedding backward included), grad W_e = gT^T table.  No g_edge_attr
+ * [E,Ce] exists.  The class grouping is the caller's, built once per (index, plan) by cgat_indexed_class_plan: cls_pos [E]
+ * lists the destination-sorted slots of class 0, 1, ... in ascending slot order (a stable counting sort for few classes of
+ * many rows) and every class is cut into pieces of 256 rows: piece_start [R+1], piece_rowptr
+ * [cgat_indexed_class_pieces(E,R) + 1], where cgat_indexed_class_pieces(E,R) = ceil(E/256) + R bounds the piece count.  Pieces are summed in ascending order, the
+ * partial rows of a class in piece order in fp64, rounded once: bitwise deterministic, no atomics.
+ * cgat_nodes_attention_train_indexed_ok -- host only -- says 1 where cgat_nodes_attention_infer_indexed_ok does and
+ * H*Hd % 32 == 0 (whole mask words per half), in every arithmetic mode, under fp32 edge storage ("f32") alone; where it says
+ * 0 the calls return CGAT_ERR_UNSUPPORTED and the caller densifies.  Under "f16x3" the node-side products of the backward
+ * run in the bf16x6 form (this route folds no tensor maxima).  No allocation, no host synchronisation; workspace sizes
+ * from N, E, R and the dims alone. */
+int32_t cgat_nodes_attention_train_indexed_ok(const cgat_plan* plan, const cgat_attn_params* p, int32_t R);
+size_t cgat_nodes_attention_indexed_saved_floats(int32_t N, int32_t E, int32_t H, int32_t Hd);
+size_t cgat_nodes_attention_forward_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p, int32_t R);
+int cgat_nodes_attention_forward_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x /* [N,C] */,
+                                         const float* table /* [R,Ce] */, int32_t R, const int64_t* index /* [E] */,
+                                         float* aggr /* out [N,C] */, float* saved, void* ws, size_t ws_bytes,
+                                         void* stream);
+size_t cgat_nodes_attention_backward_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p, int32_t R);
+int cgat_nodes_attention_backward_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                          const float* table, int32_t R, const int64_t* index, const int32_t* cls_pos,
+                                          const int32_t* piece_rowptr, const int32_t* piece_start, const float* saved,
+                                          const float* g_aggr /* [N,C] */, float* g_x /* out [N,C] */,
+                                          float* g_table /* out [R,Ce] */, const cgat_attn_grads* g, void* ws,
+                                          size_t ws_bytes, void* stream);
+int32_t cgat_indexed_class_pieces(int32_t E, int32_t R);
+size_t cgat_indexed_class_plan_workspace_bytes(int32_t E, int32_t R);
+int cgat_indexed_class_plan(const cgat_plan* plan, const int64_t* index /* [E] */, int32_t R, int32_t* cls_pos /* out [E] */,
+                            int32_t* piece_start /* out */, int32_t* piece_rowptr /* out */, void* ws, size_t ws_bytes,
+                            void* stream);
+/* Debug (tests only): the derivative pattern of that route, mask[e, c] = (z[slot(e), c] > 0) as uint8 [E, 2*H*Hd] in
+ * original edge order, from x, table, index and the parameters through the forward's projections and the one function
+ * that forms z for the forward and the backward (CGAT/CGAT.py:95-96,105-108). */
+size_t cgat_debug_nodes_attention_signs_indexed_workspace_bytes(const cgat_plan* plan, const cgat_attn_params* p, int32_t R);
+int cgat_debug_nodes_attention_signs_indexed(const cgat_plan* plan, const cgat_attn_params* p, const float* x,
+                                             const float* table, int32_t R, const int64_t* index,
+                                             uint8_t* mask /* out [E, 2*H*Hd] */, void* ws, size_t ws_bytes, void* stream);
+
 /* Debug (tests only): the routes cgat_nodes_attention_forward (backward == 0) or cgat_nodes_attention_backward
  * (backward != 0) takes for this layer in the current arithmetic and edge-storage modes, for 16-byte aligned operands --
  * host only, a predicate of the shapes like cgat_nodes_attention_infer_fused.  One bit per route, from bit 0:

@@ -9,9 +9,19 @@ warm-up then `--reps` repetitions per sample, median and spread (min .. max of t
   (d) the 4-layer training step (forward + backward), on against off
   (e) peak allocation of one call of (a)
 
-Writes profiles/indexed_edges_bench.json (or --out) and prints the same JSON line.
+With --train-route, the training route (cgat_amd.set_indexed_edge_training) instead, three columns alternated in one
+process: "indexed" (the route on), "densified" (the lookup densified per layer, as without the switch) and "dense" (a dense
+edge_attr tensor / set_indexed_edge_attr off):
 
-    python tools/indexed_edges_bench.py [--reps 10] [--quick] [--out PATH]
+  (f) one layer forward + backward at 1 M edges, H = 3
+  (g) the 4-layer training step at 1 M edges, 240 000 edges and 64 crystals
+  (h) peak allocation of (g) at 1 M edges
+  (i) per-kernel times of the new launches by CGAT_PROF tag next to edge_z, seg_wsum, edge_seg_bwd, edge_ge, edge_gw
+
+Writes profiles/indexed_edges_bench.json (profiles/indexed_train_bench.json with --train-route; or --out) and prints the
+same JSON line.
+
+    python tools/indexed_edges_bench.py [--reps 10] [--quick] [--train-route] [--out PATH]
 """
 import argparse
 import json
@@ -176,17 +186,144 @@ def train_case(crystals, reps):
     return {"crystals": crystals, "E": int(b.edge_index.shape[1]), "train_step": _alternate(step, reps)}
 
 
+TRAIN_TAGS = ("edge_idx_logits", "edge_idx_wsum", "edge_idx_bwd_msg", "edge_idx_bwd_soft", "edge_idx_bwd_att", "edge_gj",
+              "edge_idx_class_sum", "edge_z", "seg_wsum", "edge_seg_bwd", "edge_ge", "edge_gw")
+
+
+def _alternate3(fns, reps, samples=3):
+    """{column: {"median_ms", "min_ms", "max_ms", "spread_ms"}} for {column: callable}, the columns alternated."""
+    ms = {k: [] for k in fns}
+    for f in fns.values():
+        f()
+        f()
+    for _ in range(samples):
+        for k, f in fns.items():
+            ms[k].append(_median_ms(f, reps))
+    out = {}
+    for k, v in ms.items():
+        v = sorted(v)
+        out[k] = {"median_ms": round(v[len(v) // 2], 4), "min_ms": round(v[0], 4), "max_ms": round(v[-1], 4),
+                  "spread_ms": round(v[-1] - v[0], 4)}
+    return out
+
+
+def _train_tags(fn):
+    from cgat_amd import ops
+    ops.prof_reset()
+    ops.prof_enable(True)
+    fn()
+    torch.cuda.synchronize()
+    ops.prof_enable(False)
+    out = {}
+    for t in TRAIN_TAGS:
+        n, ms = ops.prof_get(t)
+        if n:
+            out[t] = {"launches": n, "ms": round(ms, 4)}
+    return out
+
+
+class _switches:
+    def __init__(self, attr, train):
+        self.v = (attr, train)
+
+    def __enter__(self):
+        import cgat_amd as P
+        self.prev = (P.get_indexed_edge_attr(), P.get_indexed_edge_training())
+        P.set_indexed_edge_attr(self.v[0])
+        P.set_indexed_edge_training(self.v[1])
+
+    def __exit__(self, *a):
+        import cgat_amd as P
+        P.set_indexed_edge_attr(self.prev[0])
+        P.set_indexed_edge_training(self.prev[1])
+
+
+def train_layer_case(crystals, reps, H=3, K=12):
+    """(f), (i): one node layer forward + backward on the same lookup, three ways."""
+    import cgat_amd as P
+    b, _ = P.synthetic_batch(crystals, 20, K, seed=0)
+    g = torch.Generator().manual_seed(1)
+    N, E = b.num_nodes, b.edge_index.shape[1]
+    x, x0 = torch.randn(N, 128, generator=g).to(DEV).requires_grad_(True), torch.randn(N, 128, generator=g).to(DEV)
+    cot = torch.randn(N, 128, generator=g).to(DEV)
+    table = torch.randn(K + 1, 128, generator=g).to(DEV).requires_grad_(True)
+    index, ei = b.edge_attr.to(DEV), b.edge_index.to(DEV)
+    dense = table.detach()[index].clone().requires_grad_(True)
+    torch.manual_seed(1)
+    layer = P.GATConvNodes(128, 128, 128, H, concat=True).to(DEV)
+    leaves = [x, table] + list(layer.parameters())
+
+    def run(ea, train):
+        def f():
+            with _switches(False, train):
+                y = layer(x, ei, ea() if callable(ea) else ea, x0)
+                torch.autograd.grad((y * cot).sum(), leaves + ([dense] if ea is dense else []), allow_unused=True)
+        return f
+    fns = {"indexed": run(lambda: P.IndexedEdgeAttr(table, index), True),
+           "densified": run(lambda: P.IndexedEdgeAttr(table, index), False), "dense": run(dense, False)}
+    res = {"crystals": crystals, "N": N, "E": E, "H": H, "R": K + 1, "layer_fwd_bwd": _alternate3(fns, reps)}
+    res["tags"] = {k: _train_tags(f) for k, f in fns.items()}
+    res["peak_alloc_bytes"] = {k: _peak(f) for k, f in fns.items()}
+    return res
+
+
+def train_net_case(crystals, reps, peak=False):
+    """(g), (h): forward + backward of the 4-layer network in train mode (no optimiser step)."""
+    b, roost = _batch(crystals, 12)
+    net = _net(False).train()
+    cot = torch.randn(crystals, 2, generator=torch.Generator().manual_seed(2)).to(DEV)
+
+    def run(attr, train):
+        def f():
+            with _switches(attr, train):
+                for p in net.parameters():
+                    p.grad = None
+                (net(b, roost) * cot).sum().backward()
+        return f
+    fns = {"indexed": run(True, True), "densified": run(True, False), "dense": run(False, False)}
+    res = {"crystals": crystals, "E": int(b.edge_index.shape[1]), "train_step": _alternate3(fns, reps)}
+    if peak:
+        res["peak_alloc_bytes"] = {k: _peak(f) for k, f in fns.items()}
+        res["tags"] = {k: _train_tags(f) for k, f in fns.items()}
+    return res
+
+
+def train_route_main(args, reps):
+    import cgat_amd as P
+    out = {"tool": "indexed_edges_bench --train-route", "mode": P.get_bilinear_mode(),
+           "device": torch.cuda.get_device_name(0), "reps": reps, "samples": 3}
+    big = 1000 if args.quick else 4167
+    out["f_i_layer"] = {str(big): train_layer_case(big, reps)}
+    torch.cuda.empty_cache()
+    out["g_h_train"] = {}
+    for c in ((1000, 64) if args.quick else (4167, 1000, 64)):
+        out["g_h_train"][str(c)] = train_net_case(c, reps, peak=c == big)
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--quick", action="store_true", help="64 and 1 000 crystals only (a rehearsal of the tool)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "indexed_edges_bench.json"))
+    ap.add_argument("--train-route", action="store_true", help="rows (f)-(i): the training route, three columns")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "indexed_train_bench.json" if args.train_route else "indexed_edges_bench.json")
     if not torch.cuda.is_available():
         sys.exit("indexed_edges_bench: needs an MI355X; nothing is measured without one")
     import cgat_amd as P
     reps = max(10, args.reps)
     sizes = (64, 1000) if args.quick else (4167, 1000, 64)
+    if args.train_route:
+        out = train_route_main(args, reps)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
     out = {"tool": "indexed_edges_bench", "mode": P.get_bilinear_mode(), "device": torch.cuda.get_device_name(0),
            "reps": reps, "samples": 3}
     out["a_eval_scalar"] = {str(c): eval_case(c, reps, peak=True) for c in sizes}
