@@ -19,6 +19,7 @@ from .ops import set_fused_edge_combine, get_fused_edge_combine
 from .ops import set_fused_attention_dropout, get_fused_attention_dropout
 from .ops import IndexedEdgeAttr, set_indexed_edge_attr, get_indexed_edge_attr
 from .ops import set_indexed_edge_training, get_indexed_edge_training
+from .ops import set_indexed_vector_attention, get_indexed_vector_attention
 from .trainer import DataParallelTrainer, Normalizer
 from .chunked import set_max_edges_per_pass
 from .capture import GraphedStep
@@ -31,4 +32,5 @@ __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAtt
            "set_validate_indices", "DataParallelTrainer", "Normalizer", "set_max_edges_per_pass",
            "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "set_fused_edge_combine",
            "get_fused_edge_combine", "set_fused_attention_dropout", "get_fused_attention_dropout", "IndexedEdgeAttr", "set_indexed_edge_attr",
-           "get_indexed_edge_attr", "set_indexed_edge_training", "get_indexed_edge_training", "GraphedStep", "debug"]
+           "get_indexed_edge_attr", "set_indexed_edge_training", "get_indexed_edge_training", "set_indexed_vector_attention",
+           "get_indexed_vector_attention", "GraphedStep", "debug"]

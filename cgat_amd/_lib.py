@@ -212,6 +212,16 @@ PROTOTYPES = {
                                            C.c_size_t, vp]),
     "cgat_edge_hidden_backward": (C.c_int, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32,
                                             vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "cgat_edge_hidden_indexed_ok": (C.c_int32, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cgat_edge_hidden_forward_indexed_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32,
+                                                                      C.c_int32]),
+    "cgat_edge_hidden_forward_indexed": (C.c_int, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32,
+                                                   vp, vp, vp, vp, C.c_size_t, vp]),
+    "cgat_edge_hidden_backward_indexed_workspace_bytes": (C.c_size_t, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32,
+                                                                       C.c_int32]),
+    "cgat_edge_hidden_backward_indexed": (C.c_int, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32,
+                                                    vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_size_t,
+                                                    vp]),
     "cgat_debug_edge_hidden_route": (C.c_uint32, [C.POINTER(Plan), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32]),
     "cgat_linear_backward_dact": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp,

@@ -18,8 +18,13 @@
 //   edge_idx_bwd_msg  g_alpha, the message half's sign bits and its share of Gi        (seg_bwd_msg_kernel's step on z)
 //   edge_idx_bwd_att  the attention half: sign bits, Gi share, partial sums of grad fc_out_A  (seg_bwd_att_kernel's)
 //   edge_idx_class_sum  gT[r, :] = sum of the rebuilt gZ rows of class r: grad table = gT W_e, grad W_e = gT^T table
+//
+// The vector-attention first layer on the same lookup (last part of this file) stores what its second layers read:
+//   edge_idx_hidden   hidden[t, :] = leaky(z[t, :]) over all W2 columns, max |hidden| folded in; its backward takes gT
+//                     from a STORED gZ (the second form of edge_idx_class_sum)
 #include "common.h"
 #include "kernels.h"
+#include "mfma_bf16.h"   // block_absmax_commit
 
 #define IDX_THREADS 1024
 #define IDX_WAVES 16      // waves per workgroup = segments per ordinary workgroup = row groups of a long segment
@@ -649,6 +654,110 @@ int edge_idx_class_sum_launch(const EdgeRC& rc, const int* piece_rowptr, const i
   CGAT_TRY(edge_gj_launch(rc, piece_rowptr, cls_pos, n_max, W2, partials, W2, stream));
   hipLaunchKernelGGL(edge_idx_class_reduce_kernel, dim3(cdiv(W2 / 4, 256), R), dim3(256), 0, stream, partials, piece_start,
                      n_max, W2, gT);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+
+// ... over a STORED gZ [E, W2] (row-major, destination-sorted slots: the vector-attention first layer, whose gZ autograd
+// hands over).  Level 1: one workgroup per piece, a thread per column quad, the piece's rows gathered through cls_pos four
+// at a time and added in ascending order in fp64, rounded once per piece; level 2 the reduction above.  (seg_wsum_launch
+// with cls_pos as its row gather -- the launch that forms Gj from a stored gZ -- computes the same partial rows by an
+// fp32 chain of up to IDX_PIECE_ROWS terms; with every slot in one class that chain left grad W_e 2.7 x the dense
+// product's error, outside the ratio rule of the tests.  The adds hide behind the gather either way.)
+__global__ __launch_bounds__(256) void edge_idx_class_piece_kernel(const float* __restrict__ gZ, long ld,
+                                                                   const int* __restrict__ cls_pos,
+                                                                   const int* __restrict__ piece_rowptr, int W2,
+                                                                   float* __restrict__ part) {
+  const int p = blockIdx.x;
+  const int r0 = piece_rowptr[p], r1 = piece_rowptr[p + 1];
+  for (int f = 4 * threadIdx.x; f < W2; f += 4 * blockDim.x) {
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;       // (an empty piece: zeros)
+    for (int r = r0; r < r1; r += 4) {
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = idx_ld4(gZ + (size_t)cls_pos[r + u < r1 ? r + u : r1 - 1] * ld + f);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (r + u < r1) { a0 += (double)v[u].x; a1 += (double)v[u].y; a2 += (double)v[u].z; a3 += (double)v[u].w; }
+    }
+    *reinterpret_cast<float4*>(part + (size_t)p * W2 + f) = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
+  }
+}
+int edge_idx_class_sum_launch(const float* gZ, const int* piece_rowptr, const int* piece_start, const int* cls_pos, int R,
+                              int E, int W2, float* partials, float* gT, hipStream_t stream) {
+  CGAT_CHECK_ARG(R >= 1 && R <= EDGE_IDX_MAX_ROWS && W2 > 0 && W2 % 4 == 0 && E > 0 && gZ && piece_rowptr && piece_start &&
+                 cls_pos && partials && gT && idx_aligned16(partials, gT, gZ, gZ),
+                 "edge_idx_class_sum: 1 <= R <= %d, E > 0, W2 %% 4 == 0, 16-byte aligned rows", EDGE_IDX_MAX_ROWS);
+  const int n_max = edge_idx_class_pieces(E, R);
+  CGAT_PROF("edge_idx_class_sum", stream);
+  const int threads = W2 / 4 >= 256 ? 256 : cdiv(W2 / 4, 64) * 64;
+  hipLaunchKernelGGL(edge_idx_class_piece_kernel, dim3(n_max), dim3(threads), 0, stream, gZ, (long)W2, cls_pos, piece_rowptr,
+                     W2, partials);
+  CGAT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(edge_idx_class_reduce_kernel, dim3(cdiv(W2 / 4, 256), R), dim3(256), 0, stream, partials, piece_start,
+                     n_max, W2, gT);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+
+// =====================================================================================================================
+// The vector-attention first layer on the same lookup: hidden[t, :] = leaky(z[t, :]) over ALL W2 columns, stored (the second
+// layers need every row), and max |hidden| folded into the launch (their fp16 scale, as edge_z_launch gives it to the
+// dense op).  A flat decomposition: a workgroup takes IDX_HID_ROWS consecutive slots and its threads walk the
+// IDX_HID_ROWS x W2 / 4 column quads of the tile row by row, IDX_HID_U quads in flight per thread.  Nothing is summed over
+// a segment here, so a segment per wave would only buy Pi[n] in registers -- which the L2 serves anyway (the slots of a
+// destination are neighbours) -- at the price of the long-segment split; flat, every workgroup has the same work whatever
+// the degrees are, and the stores of a tile are one contiguous stream.  Column-wise: no bound on W2.
+// =====================================================================================================================
+#define IDX_HID_THREADS 256
+#define IDX_HID_ROWS 8
+#define IDX_HID_U 4
+
+__global__ __launch_bounds__(IDX_HID_THREADS) void edge_idx_hidden_kernel(const IdxSrc src, const float* __restrict__ Pi,
+                                                                          const int* __restrict__ dsti, int E, int Q,
+                                                                          float* __restrict__ hidden,
+                                                                          float* __restrict__ hmax) {
+  const int t0 = blockIdx.x * IDX_HID_ROWS;
+  const int rows = min(IDX_HID_ROWS, E - t0);
+  const int items = rows * Q;                        // (<= 8 * W2 / 4: an int)
+  float m = 0.f;
+  for (int j0 = threadIdx.x; j0 < items; j0 += IDX_HID_U * IDX_HID_THREADS) {
+    float4 z[IDX_HID_U];
+    int tt[IDX_HID_U], ff[IDX_HID_U];
+#pragma unroll
+    for (int u = 0; u < IDX_HID_U; ++u) {
+      const int j = j0 + u * IDX_HID_THREADS < items ? j0 + u * IDX_HID_THREADS : j0;   // (clamped: a valid item)
+      const int r = j / Q;
+      tt[u] = t0 + r;
+      ff[u] = 4 * (j - r * Q);
+      z[u] = idx_z(src, tt[u], ff[u], idx_ld4(Pi + (size_t)dsti[tt[u]] * src.W2 + ff[u]));
+    }
+#pragma unroll
+    for (int u = 0; u < IDX_HID_U; ++u)
+      if (j0 + u * IDX_HID_THREADS < items) {
+        const float4 h = make_float4(idx_leaky(z[u].x), idx_leaky(z[u].y), idx_leaky(z[u].z), idx_leaky(z[u].w));
+        *reinterpret_cast<float4*>(hidden + (size_t)tt[u] * src.W2 + ff[u]) = h;
+        m = fmaxf(m, fmaxf(fmaxf(fabsf(h.x), fabsf(h.y)), fmaxf(fabsf(h.z), fabsf(h.w))));
+      }
+  }
+  // one integer atomic max per workgroup on the bit image of a non-negative float: order-free
+  if (hmax) block_absmax_commit(m, hmax);
+}
+
+// Shapes the launch takes: whole column quads, 1 <= R <= EDGE_IDX_MAX_ROWS; 64-bit row offsets.  Host only.
+bool edge_idx_hidden_ok(int W2, int R) { return W2 >= 4 && W2 % 4 == 0 && R >= 1 && R <= EDGE_IDX_MAX_ROWS; }
+
+int edge_idx_hidden_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
+                           const int* srci, const int* dsti, int W2, int E, float* hidden, float* hmax,
+                           hipStream_t stream) {
+  CGAT_CHECK_ARG(edge_idx_hidden_ok(W2, R) && Te && Pi && Pj && idx && perm && srci && dsti && hidden &&
+                 idx_aligned16(Te, Pi, Pj, hidden),
+                 "edge_idx_hidden: needs W2 %% 4 == 0, 1 <= R <= %d and 16-byte aligned rows", EDGE_IDX_MAX_ROWS);
+  if (E <= 0) return CGAT_OK;
+  const IdxSrc src = {Te, Pj, idx, perm, srci, (long)W2, R};
+  CGAT_PROF("edge_idx_hidden", stream);
+  hipLaunchKernelGGL(edge_idx_hidden_kernel, dim3(cdiv(E, IDX_HID_ROWS)), dim3(IDX_HID_THREADS), 0, stream, src, Pi, dsti, E,
+                     W2 / 4, hidden, hmax);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }

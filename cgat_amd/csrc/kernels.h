@@ -252,6 +252,17 @@ int edge_idx_class_plan_launch(const int64_t* idx, const int* perm, int E, int R
                                int* piece_rowptr, void* ws, size_t ws_bytes, hipStream_t stream);
 int edge_idx_class_sum_launch(const EdgeRC& rc, const int* piece_rowptr, const int* piece_start, const int* cls_pos, int R,
                               int E, int W2, float* partials, float* gT, hipStream_t stream);
+// ... over a STORED gZ [E, W2] (row-major, destination-sorted slots): level 1 sums each piece's rows, gathered through
+// cls_pos, in ascending order in fp64 and rounds once; level 2 is the same fp64 reduction in piece order.  Same tag.
+int edge_idx_class_sum_launch(const float* gZ, const int* piece_rowptr, const int* piece_start, const int* cls_pos, int R,
+                              int E, int W2, float* partials, float* gT, hipStream_t stream);
+// ---- the vector-attention first layer on the lookup: hidden[t, :] = leaky(Te[idx[perm[t]]] + Pi[dst[t]] + Pj[src[t]]) over
+// all W2 columns, z through the same idx_z; hmax (optional, zeroed by a fill kernel before): max |hidden| by one integer
+// atomic max per workgroup (order-free).  Flat over the E * W2 / 4 column quads: any W2 % 4 == 0, any degree.  Tag
+// "edge_idx_hidden".  edge_idx_hidden_ok: the host-only predicate of the shapes.
+bool edge_idx_hidden_ok(int W2, int R);
+int edge_idx_hidden_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
+                           const int* srci, const int* dsti, int W2, int E, float* hidden, float* hmax, hipStream_t stream);
 // debug: mask[perm[t]][c] = (z[t][c] > 0) for z formed as the route forms it (uint8 [E, W2], original edge order)
 int edge_idx_signs_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
                           const int* srci, const int* dsti, int W2, long E, uint8_t* mask, hipStream_t stream);

@@ -1292,6 +1292,146 @@ extern "C" int cgat_edge_hidden_backward(const cgat_plan* plan, int32_t C, int32
   });
 }
 
+// ---- edge_hidden on shell-indexed edge features: edge_attr[e] = table[index[e]], R rows (reference CGAT.py:96,105-108 on
+// the message of 316-318 with the lookups of 569 / 583; include/cgat_hip.h).  `hidden` stays; what goes is everything the
+// layer does per edge with edge_attr: Te = table W_e^T over R rows and a gather of three rows forward; backward the class
+// sum gT of the stored gZ and two R-row products in place of grad edge_attr = gZ W_e and grad W_e = gZ^T e -- the algebra
+// of attn_backward_indexed_impl.  No tensor maxima on this route: under f16x3 the node-side products run in the form that
+// needs none (bf16x6), as the scalar indexed route's do.
+static bool hidden_indexed_ok(const AttnDims& d, int R) {
+  return edge_storage() == 0 && d.N > 0 && d.E > 0 && d.C > 0 && d.Ce > 0 && edge_idx_hidden_ok(d.W2, R);
+}
+struct HiddenFwdIndexed {
+  float *Pi, *Pj, *Te, *Wq;
+  bool fast;          // the node projections on the split per-edge kernel (else: the GEMM engine), as hidden_fwd_carve
+};
+static HiddenFwdIndexed hidden_fwd_indexed_carve(Ctx& c, const AttnDims& d, int R, const float* b_in, const float* x,
+                                                 const float* Hout) {
+  HiddenFwdIndexed f = {};
+  f.Pi = c.take<float>((size_t)d.N * d.W2);
+  f.Pj = c.take<float>((size_t)d.N * d.W2);
+  f.Te = c.take<float>((size_t)R * d.W2);
+  f.Wq = c.take<float>(edge_z_wq_floats(d.W2));
+  c.seal();
+  f.fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 &&
+           edge_z_fast(d.C, d.W2, 1, d.W2 / 2, d.C, d.W2, d.W2, x, f.Pi, f.Pj, Hout, b_in);
+  return f;
+}
+static int edge_hidden_forward_indexed_impl(Ctx& c, const cgat_plan* plan, const AttnDims& d, const float* w_in,
+                                            const float* b_in, const float* x, const float* table, int R,
+                                            const int64_t* index, float* Hout, float* hmax) {
+  const HiddenFwdIndexed f = hidden_fwd_indexed_carve(c, d, R, b_in, x, Hout);
+  if (hmax) RUN(fill_launch(hmax, 0.f, 1, c.s));
+  CGAT_TRY(node_projections(c, d, f.fast, true, x, w_in, b_in, NodeProj{f.Pi, f.Pj, f.Wq}));
+  CGAT_TRY(c.gemm(gemm_params(R, d.W2, d.Ce, table, d.Ce, w_in + d.C, d.D, f.Te, d.W2)));   // (no bias: Pi carries it)
+  RUN(edge_idx_hidden_launch(f.Te, R, index, plan->dst_perm, f.Pi, f.Pj, plan->src_sorted, plan->dst_sorted, d.W2, d.E, Hout,
+                             hmax, c.s));
+  return check_ws(c, "edge_hidden_forward_indexed");
+}
+
+struct HiddenBwdIndexed {
+  EdgeTail t;         // e == nullptr, g_e == nullptr, rc == nullptr: the segment sums and the node-side products alone
+  float *gZ, *gT, *cpart;
+};
+static HiddenBwdIndexed hidden_bwd_indexed_carve(Ctx& c, const AttnDims& d, int R, const float* w_in, const float* x,
+                                                 const float* g_H, float* g_x, float* g_w_in, float* g_b_in, int g_is_pre) {
+  HiddenBwdIndexed b = {};
+  b.gZ = g_is_pre ? const_cast<float*>(g_H) : c.take<float>((size_t)d.E * d.W2);
+  EdgeTail& t = b.t;
+  t.gZ = {b.gZ, d.W2, 128};
+  t.Gi = c.take<float>((size_t)d.N * d.W2);
+  t.Gj = c.take<float>((size_t)d.N * d.W2);
+  t.Wq = c.take<float>(edge_z_wq_floats(d.W2));
+  t.gw_ws = c.take<float>(edge_gw_ws_floats(d.N, d.W2));              // (the node-side weight gradients: N rows)
+  b.gT = c.take<float>((size_t)R * d.W2);
+  b.cpart = c.take<float>((size_t)edge_idx_class_pieces(d.E, R) * d.W2);
+  c.seal();
+  t.Wcat = w_in; t.gWcat = g_w_in; t.gbcat = g_b_in;
+  t.scales = nullptr;            // no maxima on this route
+  t.x = x; t.g_x = g_x;
+  return b;
+}
+static int edge_hidden_backward_indexed_impl(Ctx& c, const cgat_plan* plan, const AttnDims& d, const float* w_in,
+                                             const float* x, const float* table, int R, const AttnClassPlan& cls,
+                                             const float* Hsaved, const float* g_H, int g_is_pre, float* g_x,
+                                             float* g_table, float* g_w_in, float* g_b_in) {
+  const HiddenBwdIndexed b = hidden_bwd_indexed_carve(c, d, R, w_in, x, g_H, g_x, g_w_in, g_b_in, g_is_pre);
+  if (!g_is_pre) RUN(act_bwd_launch(Hsaved, g_H, b.gZ, (long)d.E * d.W2, CGAT_ACT_LEAKY, c.s));
+  const TailRoute r = tail_route(c.dry, d, b.t);
+  CGAT_TRY(tail_segment_sums(c, plan, d, b.t, r));
+  CGAT_TRY(tail_node_products(c, d, b.t, r));
+  // gT, then grad table = gT W_e and grad W_e = gT^T table (into the W_e columns of g_w_in): attn_bwd_class_products' pair
+  RUN(edge_idx_class_sum_launch(b.gZ, cls.piece_rowptr, cls.piece_start, cls.cls_pos, R, d.E, d.W2, b.cpart, b.gT, c.s));
+  GemmParams g = gemm_params(R, d.Ce, d.W2, b.gT, d.W2, w_in + d.C, d.D, g_table, d.Ce);
+  g.b_kmajor = 1;
+  CGAT_TRY(c.gemm(g));
+  g = gemm_params(d.W2, d.Ce, R, b.gT, d.W2, table, d.Ce, g_w_in + d.C, d.D);
+  g.a_kmajor = 1; g.b_kmajor = 1;
+  CGAT_TRY(c.gemm(g));
+  return check_ws(c, "edge_hidden_backward_indexed");
+}
+static int hidden_indexed_refuse(const char* who, const cgat_plan* plan, int C, int Ce, int W2, int R) {
+  cgat_set_error("%s: not taken for N %d, E %d, C %d, Ce %d, W2 %d, R %d under edge storage %d "
+                 "(cgat_edge_hidden_indexed_ok); densify and call the dense entry", who, plan->N, plan->E, C, Ce, W2, R,
+                 edge_storage());
+  return CGAT_ERR_UNSUPPORTED;
+}
+extern "C" int32_t cgat_edge_hidden_indexed_ok(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, int32_t R) {
+  if (hidden_check(plan, C, Ce, W2) != CGAT_OK) return 0;
+  return hidden_indexed_ok(hidden_dims(plan, C, Ce, W2), R) ? 1 : 0;
+}
+extern "C" size_t cgat_edge_hidden_forward_indexed_workspace_bytes(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2,
+                                                                   int32_t R) {
+  if (R < 1) R = 1;
+  return dry_total([&](Ctx& c) {
+    return edge_hidden_forward_indexed_impl(c, plan, hidden_dims(plan, C, Ce, W2), nullptr, nullptr, nullptr, nullptr, R,
+                                            nullptr, nullptr, nullptr);
+  });
+}
+extern "C" int cgat_edge_hidden_forward_indexed(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, const float* w_in,
+                                                const float* b_in, const float* x, const float* table, int32_t R,
+                                                const int64_t* index, float* hidden, float* hidden_absmax, void* ws,
+                                                size_t ws_bytes, void* stream) {
+  CGAT_TRY(hidden_check(plan, C, Ce, W2));
+  if (!hidden_indexed_ok(hidden_dims(plan, C, Ce, W2), R))
+    return hidden_indexed_refuse("edge_hidden_forward_indexed", plan, C, Ce, W2, R);
+  CGAT_CHECK_ARG(w_in && b_in && x && table && index && hidden && aligned16(hidden),
+                 "edge_hidden_forward_indexed: null operand, or hidden not 16-byte aligned");
+  return run_sized("edge_hidden_forward_indexed", ws, ws_bytes, stream, [&](Ctx& c) {
+    return edge_hidden_forward_indexed_impl(c, plan, hidden_dims(plan, C, Ce, W2), w_in, b_in, x, table, R, index, hidden,
+                                            hidden_absmax);
+  });
+}
+extern "C" size_t cgat_edge_hidden_backward_indexed_workspace_bytes(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2,
+                                                                    int32_t R) {
+  if (R < 1) R = 1;
+  const AttnClassPlan cls = {};
+  return dry_total([&](Ctx& c) {
+    return edge_hidden_backward_indexed_impl(c, plan, hidden_dims(plan, C, Ce, W2), nullptr, nullptr, nullptr, R, cls, nullptr,
+                                             nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+  });
+}
+extern "C" int cgat_edge_hidden_backward_indexed(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, const float* w_in,
+                                                 const float* x, const float* table, int32_t R, const int64_t* index,
+                                                 const int32_t* cls_pos, const int32_t* piece_rowptr,
+                                                 const int32_t* piece_start, const float* hidden, const float* g_hidden,
+                                                 int32_t g_is_pre, const float* gpre_absmax, float* g_x, float* g_table,
+                                                 float* g_w_in, float* g_b_in, void* ws, size_t ws_bytes, void* stream) {
+  (void)gpre_absmax;   // (the dense entry's call shape: no product of this route takes maxima)
+  CGAT_TRY(hidden_check(plan, C, Ce, W2));
+  if (!hidden_indexed_ok(hidden_dims(plan, C, Ce, W2), R))
+    return hidden_indexed_refuse("edge_hidden_backward_indexed", plan, C, Ce, W2, R);
+  CGAT_CHECK_ARG(w_in && x && table && index && cls_pos && piece_rowptr && piece_start && g_hidden && (g_is_pre || hidden) &&
+                 g_x && g_table && g_w_in && g_b_in && aligned16(g_hidden),
+                 "edge_hidden_backward_indexed: null operand, or g_hidden not 16-byte aligned");
+  const AttnClassPlan cls = {cls_pos, piece_rowptr, piece_start};
+  // (sized as cgat_edge_hidden_backward_indexed_workspace_bytes sizes it, i.e. with a gZ buffer, whatever g_is_pre says)
+  return run_sized("edge_hidden_backward_indexed", ws, ws_bytes, stream, [&](Ctx& c) {
+    return edge_hidden_backward_indexed_impl(c, plan, hidden_dims(plan, C, Ce, W2), w_in, x, table, R, cls, hidden, g_hidden,
+                                             c.dry ? 0 : g_is_pre, g_x, g_table, g_w_in, g_b_in);
+  });
+}
+
 static int attn_check(const cgat_plan* plan, const cgat_attn_params* p) {
   CGAT_CHECK_ARG(plan && p, "nodes_attention: null plan/params");
   CGAT_CHECK_ARG(plan->N >= 0 && plan->E >= 0, "nodes_attention: negative N/E");

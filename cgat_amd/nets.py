@@ -24,6 +24,7 @@ from .ops import overlap_enabled as ops_overlap_enabled
 from .ops import HNetFn, infer_route, nodes_attention_infer
 from .ops import IndexedEdgeAttr, get_indexed_edge_attr, indexed_route, nodes_attention_infer_indexed
 from .ops import NodesAttentionIndexedFn, NodeLayerIndexedFn, train_indexed_route
+from .ops import EdgeHiddenIndexedFn, EdgeHiddenHeadsIndexedFn, vector_indexed_route
 from .ops import EdgeHeadCombineFn, edge_combine_route
 from .ops import branch_stream
 from .roost import Roost
@@ -273,16 +274,22 @@ class GATConvNodes(nn.Module):
         return NodesAttentionFn.apply(x, edge_attr, plan, self.heads, *params)
 
     def _indexed_route(self, x, edge_index, edge_attr):
-        """True when this call, given an IndexedEdgeAttr, keeps it: scalar attention, one unchunked pass, no training-mode
-        dropout, message / update the layer's own, and either no backward to follow and no debug recording
-        (ops.infer_route: ops.nodes_attention_infer_indexed runs) or a backward to follow under
+        """True when this call, given an IndexedEdgeAttr, keeps it: one unchunked pass, no training-mode dropout, message /
+        update the layer's own, and -- vector attention -- ops.vector_indexed_route holds (the opt-in switch
+        ops.set_indexed_vector_attention, with grad and without), or -- scalar attention -- either no backward to follow
+        and no debug recording (ops.infer_route: ops.nodes_attention_infer_indexed runs) or a backward to follow under
         ops.set_indexed_edge_training (ops.NodesAttentionIndexedFn / NodeLayerIndexedFn run), at a shape the library takes
         for that route in the current arithmetic and edge-storage modes.  Everything else densifies and runs as it
         always has."""
-        if (self.vector_attention or not torch.is_tensor(x) or (self.dropout and self.training) or
+        if (not torch.is_tensor(x) or (self.dropout and self.training) or
                 type(self).message is not GATConvNodes.message or type(self).update is not GATConvNodes.update or
                 edge_index.shape[1] > chunked.max_edges_per_pass() or not x.is_cuda):
             return False
+        if self.vector_attention:
+            # under ops.set_indexed_vector_attention, with grad and without: the first layer of both networks on the lookup
+            # (ops.EdgeHiddenIndexedFn / EdgeHiddenHeadsIndexedFn); everything behind `hidden` is unchanged
+            W2 = 2 * self.heads * self.MH_A.hidden_layer_dim
+            return vector_indexed_route(x, edge_attr, get_plan(edge_index, x.shape[0]), W2)
         plan, params = get_plan(edge_index, x.shape[0]), self._attn_params()
         return indexed_route(x, edge_attr, plan, self.heads, params) or train_indexed_route(x, edge_attr, plan, self.heads, params)
 
@@ -300,15 +307,20 @@ class GATConvNodes(nn.Module):
         w_in = torch.cat([a.fc_in.weight.reshape(H * Hd, D), m.fc_in.weight.reshape(H * Hd, D)], dim=0)
         b_in = torch.cat([a.fc_in.bias, m.fc_in.bias])
         E = plan.E
+        # (an IndexedEdgeAttr here: forward has checked _indexed_route; the same two forms on the lookup, no [E, Ce] tensor)
+        indexed = isinstance(edge_attr, IndexedEdgeAttr)
+        first = (edge_attr.table, edge_attr.index) if indexed else (edge_attr,)
         if EdgeHiddenHeadsFn.eligible(w_in.shape[0], H, Hd, (a.output_dim, Co)):
             # first layers + the 2H second layers as ONE autograd node: its backward folds LeakyReLU' into the second
             # layers' input-gradient products instead of an elementwise pass over [E, 2 H Hd] (ops.EdgeHiddenHeadsFn)
-            sa, sm = EdgeHiddenHeadsFn.apply(x, edge_attr, plan, w_in, b_in, a.fc_out.weight, a.fc_out.bias,
-                                             m.fc_out.weight, m.fc_out.bias, H, Hd, cos)
+            heads_fn = EdgeHiddenHeadsIndexedFn if indexed else EdgeHiddenHeadsFn
+            sa, sm = heads_fn.apply(x, *first, plan, w_in, b_in, a.fc_out.weight, a.fc_out.bias,
+                                    m.fc_out.weight, m.fc_out.bias, H, Hd, cos)
             if debug.recording():
                 debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, debug.last_hidden)
         else:
-            hid, hmax = EdgeHiddenFn.apply(x, edge_attr, plan, w_in, b_in)                   # [E, 2*H*Hd], sorted slots
+            hidden_fn = EdgeHiddenIndexedFn if indexed else EdgeHiddenFn
+            hid, hmax = hidden_fn.apply(x, *first, plan, w_in, b_in)                         # [E, 2*H*Hd], sorted slots
             if debug.recording():
                 debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, hid)
             # second layers of all 2H heads as one autograd node (ops.HeadsLinearFn): [E,H,Co] each

@@ -627,6 +627,21 @@ def _edge_hidden_forward(who, x, edge_attr, plan, w_in, b_in):
     return x, edge_attr, w_in, hidden, hmax
 
 
+def _edge_hidden_backward(x, edge_attr, plan, w_in, hidden, g, g_is_pre, gmax):
+    """cgat_edge_hidden_backward behind EdgeHiddenFn (g: the gradient of hidden) and EdgeHiddenHeadsFn (g_is_pre = 1: of
+    the pre-activations, gmax its maximum).  Returns g_x, g_edge_attr, g_w_in, g_b_in."""
+    Cn, Ce, W2 = x.shape[1], edge_attr.shape[1], w_in.shape[0]
+    dev = x.device
+    g_x, g_e = torch.empty_like(x), torch.empty_like(edge_attr)
+    g_w, g_b = torch.empty_like(w_in), torch.empty(W2, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_edge_hidden_backward_workspace_bytes(C.byref(plan.c), Cn, Ce, W2), dev)
+        check(lib.cgat_edge_hidden_backward(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(x), _ptr(edge_attr),
+                                            _ptr(hidden), _ptr(g), g_is_pre, _ptr(gmax), _ptr(g_x), _ptr(g_e), _ptr(g_w),
+                                            _ptr(g_b), _ptr(ws), ws.numel(), _stream()), "cgat_edge_hidden_backward")
+    return g_x, g_e, g_w, g_b
+
+
 class EdgeHiddenFn(torch.autograd.Function):
     """hidden[t] = LeakyReLU(w_in [x_i ; edge_attr ; x_j] + b_in) in destination-sorted slot order t (plan.dst_perm):
     the first layer of both message networks (reference CGAT.py:96,105-108 on the concatenated message of 316-318)
@@ -644,18 +659,122 @@ class EdgeHiddenFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_hidden, _g_hmax=None):
         x, edge_attr, w_in, hidden = ctx.saved_tensors
-        plan = ctx.plan
-        g_hidden = _f32c(g_hidden)
-        Cn, Ce, W2 = x.shape[1], edge_attr.shape[1], w_in.shape[0]
-        dev = x.device
-        g_x, g_e = torch.empty_like(x), torch.empty_like(edge_attr)
-        g_w, g_b = torch.empty_like(w_in), torch.empty(W2, dtype=torch.float32, device=dev)
-        ws = workspace(lib.cgat_edge_hidden_backward_workspace_bytes(C.byref(plan.c), Cn, Ce, W2), dev)
-        with torch.cuda.device(dev):
-            check(lib.cgat_edge_hidden_backward(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(x), _ptr(edge_attr),
-                                                _ptr(hidden), _ptr(g_hidden), 0, None, _ptr(g_x), _ptr(g_e), _ptr(g_w),
-                                                _ptr(g_b), _ptr(ws), ws.numel(), _stream()), "cgat_edge_hidden_backward")
+        g_x, g_e, g_w, g_b = _edge_hidden_backward(x, edge_attr, ctx.plan, w_in, hidden, _f32c(g_hidden), 0, None)
         return g_x, g_e, None, g_w, g_b
+
+
+# ---- the same first layer on shell-indexed edge features (cgat_edge_hidden_forward_indexed / _backward_indexed) ----
+_indexed_vector_attention = os.environ.get("CGAT_INDEXED_VECTOR_ATTN", "0") == "1"
+
+
+def set_indexed_vector_attention(flag):
+    """The shell-indexed route of VECTOR-attention node layers (default off; env CGAT_INDEXED_VECTOR_ATTN=1 starts it on):
+    such a layer given an IndexedEdgeAttr keeps it, with grad and without, and runs EdgeHiddenIndexedFn /
+    EdgeHiddenHeadsIndexedFn -- Te = table W_e^T over R rows and a three-row gather in place of the per-edge K = Ce
+    product, no [E, Ce] edge features (none saved either), grad table and grad W_e from a per-class row sum -- where the
+    library takes the shape (edge_hidden_indexed_ok).  `hidden` [E, 2 H Hd] and everything behind it are unchanged.  It
+    matters only where an IndexedEdgeAttr reaches the layer: through CGAtNet that needs set_indexed_edge_attr(True) too.
+    Off: such a layer densifies and runs the dense launches, bit for bit."""
+    global _indexed_vector_attention
+    _indexed_vector_attention = bool(flag)
+
+
+def get_indexed_vector_attention():
+    return _indexed_vector_attention
+
+
+def edge_hidden_indexed_ok(plan_c, C_, Ce, W2, R):
+    """cgat_edge_hidden_indexed_ok for a first layer of these dims in the current edge-storage mode (host only; plan_c:
+    the C struct of a plan)."""
+    return bool(lib.cgat_edge_hidden_indexed_ok(C.byref(plan_c), int(C_), int(Ce), int(W2), int(R)))
+
+
+def _indexed_operands_ok(x, table, index, plan):
+    """What the indexed autograd functions demand of x, table and index (train_indexed_route's conditions)."""
+    return (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and
+            torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and
+            torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int64 and index.dim() == 1 and
+            index.is_contiguous() and index.shape[0] == plan.E and x.shape[0] == plan.N)
+
+
+def vector_indexed_route(x, edge_attr, plan, W2):
+    """True when a vector-attention node layer given an IndexedEdgeAttr takes the indexed first layer: the switch is on,
+    the operands are as train_indexed_route demands (a contiguous index of plan.E entries among them) and the library
+    takes the shape under the current edge storage.  With grad and without; a debug recording stays on this route
+    (debug.note_sorted_hidden needs `hidden` alone)."""
+    if not _indexed_vector_attention:
+        return False
+    table, index = edge_attr.table, edge_attr.index
+    if not _indexed_operands_ok(x, table, index, plan):
+        return False
+    return edge_hidden_indexed_ok(plan.c, x.shape[1], table.shape[1], W2, table.shape[0])
+
+
+def _edge_hidden_forward_indexed(who, x, table, index, plan, w_in, b_in):
+    """cgat_edge_hidden_forward_indexed behind EdgeHiddenIndexedFn and EdgeHiddenHeadsIndexedFn.  Everything is checked
+    before the first launch.  Returns the prepared operands, hidden, hmax and the class plan of the backward."""
+    _require_gpu(x, table, index, w_in, b_in)
+    if not _indexed_operands_ok(x, table, index, plan):
+        raise ValueError(f"{who}: x float32 [N, C], table float32 [R, Ce] and a contiguous int64 index [E] matching the "
+                         "plan are required")
+    x, table, w_in, b_in = _f32c(x), _f32c(table), _f32c(w_in.detach()), _f32c(b_in.detach())
+    N, E, R = plan.N, plan.E, int(table.shape[0])
+    Cn, Ce, W2 = x.shape[1], table.shape[1], w_in.shape[0]
+    if w_in.shape[1] != 2 * Cn + Ce or b_in.numel() != W2:
+        raise ValueError(f"{who}: shapes do not match the stacked first-layer weight")
+    if not edge_hidden_indexed_ok(plan.c, Cn, Ce, W2, R):
+        raise ValueError(f"{who}: N {N}, E {E}, W2 {W2}, R {R} is not taken in the current edge-storage mode "
+                         "(ops.edge_hidden_indexed_ok); densify")
+    dev = x.device
+    cls = _class_plan(index, plan, R)
+    hidden = torch.empty(E, W2, dtype=torch.float32, device=dev)
+    hmax = torch.empty(1, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_edge_hidden_forward_indexed_workspace_bytes(C.byref(plan.c), Cn, Ce, W2, R), dev)
+        check(lib.cgat_edge_hidden_forward_indexed(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(b_in), _ptr(x), _ptr(table),
+                                                   R, _ptr(index), _ptr(hidden), _ptr(hmax), _ptr(ws), ws.numel(),
+                                                   _stream()), "cgat_edge_hidden_forward_indexed")
+    return x, table, w_in, hidden, hmax, cls
+
+
+def _edge_hidden_backward_indexed(x, table, index, cls, plan, w_in, hidden, g, g_is_pre, gmax):
+    """cgat_edge_hidden_backward_indexed.  Builds and validates nothing.  Returns g_x, g_table, g_w_in, g_b_in."""
+    Cn, Ce, W2, R = x.shape[1], table.shape[1], w_in.shape[0], int(table.shape[0])
+    dev = x.device
+    g_x, g_t = torch.empty_like(x), torch.empty_like(table)
+    g_w, g_b = torch.empty_like(w_in), torch.empty(W2, dtype=torch.float32, device=dev)
+    cls_pos, piece_rowptr, piece_start = cls
+    with torch.cuda.device(dev):
+        ws = workspace(lib.cgat_edge_hidden_backward_indexed_workspace_bytes(C.byref(plan.c), Cn, Ce, W2, R), dev)
+        check(lib.cgat_edge_hidden_backward_indexed(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(x), _ptr(table), R,
+                                                    _ptr(index), _ptr(cls_pos), _ptr(piece_rowptr), _ptr(piece_start),
+                                                    _ptr(hidden), _ptr(g), g_is_pre, _ptr(gmax), _ptr(g_x), _ptr(g_t),
+                                                    _ptr(g_w), _ptr(g_b), _ptr(ws), ws.numel(), _stream()),
+              "cgat_edge_hidden_backward_indexed")
+    return g_x, g_t, g_w, g_b
+
+
+class EdgeHiddenIndexedFn(torch.autograd.Function):
+    """EdgeHiddenFn for edge_attr = table[index] (reference CGAT.py:96,105-108 on the message of 316-318 with the lookups
+    of 569 / 583) without the [E, Ce] edge features: hidden from three gathered rows, and a backward that returns g_x,
+    g_table (the embedding backward included), g_w_in and g_b_in from segment sums and a per-class row sum.  Saves x, table,
+    index, w_in and hidden."""
+
+    @staticmethod
+    def forward(ctx, x, table, index, plan, w_in, b_in):
+        x, table, w_in, hidden, hmax, cls = _edge_hidden_forward_indexed("EdgeHiddenIndexedFn", x, table, index, plan,
+                                                                         w_in, b_in)
+        ctx.plan, ctx.cls = plan, cls
+        ctx.save_for_backward(x, table, index, w_in, hidden)
+        ctx.mark_non_differentiable(hmax)
+        return hidden, hmax
+
+    @staticmethod
+    def backward(ctx, g_hidden, _g_hmax=None):
+        x, table, index, w_in, hidden = ctx.saved_tensors
+        g_x, g_t, g_w, g_b = _edge_hidden_backward_indexed(x, table, index, ctx.cls, ctx.plan, w_in, hidden,
+                                                           _f32c(g_hidden), 0, None)
+        return g_x, g_t, None, None, g_w, g_b
 
 
 # ----------------------------------------------------------------------------------------
@@ -1039,6 +1158,45 @@ class HeadsLinearFn(torch.autograd.Function):
         return (g_hid, g_w[0].reshape(ctx.shapes[0]), g_b[0], g_w[1].reshape(ctx.shapes[1]), g_b[1], None, None, None, None)
 
 
+def _hidden_heads_forward(ctx, hidden, hmax, wa, ba, wm, bm, H, Hd, Co):
+    """The second-layer half of EdgeHiddenHeadsFn / EdgeHiddenHeadsIndexedFn's forward on a fresh `hidden`: sets ctx.dims,
+    .shapes, .has_b and returns (out_A [E, H, Co_A], out_M [E, H, Co_M], the two prepared head weights to save)."""
+    E = hidden.shape[0]
+    cos = _cos(Co, 2)
+    ws_ = [_f32c(w.detach().reshape(H * co, Hd)) for w, co in zip((wa, wm), cos)]
+    bs_ = [None if b is None else _f32c(b.detach()) for b in (ba, bm)]
+    outs = _heads_forward(hidden, list(zip(ws_, bs_)), H, Hd, cos, hmax)
+    ctx.dims = (H, Hd, cos)
+    ctx.shapes = (wa.shape, wm.shape)
+    ctx.has_b = (ba is not None, bm is not None)
+    if debug.recording():
+        debug.last_hidden = hidden             # the calling module records the derivative pattern under its weights' names
+    return outs[0].reshape(E, H, cos[0]), outs[1].reshape(E, H, cos[1]), ws_[0], ws_[1]
+
+
+def _hidden_heads_backward(ctx, hidden, w0, w1, g_a, g_m):
+    """The second layers' backward with LeakyReLU' folded in (cgat_heads_linear_backward_dact): returns gpre (the gradient of
+    the PRE-activations, written head by head), its device maximum and the head weights' / biases' gradients."""
+    H, Hd, cos = ctx.dims
+    E, W2 = hidden.shape
+    dev = hidden.device
+    gs = [_f32c(g.reshape(E, H * co)) for g, co in zip((g_a, g_m), cos)]
+    gpre = torch.empty_like(hidden)
+    gmax = torch.zeros(1, dtype=torch.float32, device=dev)
+    g_w = [torch.empty(H * co, Hd, dtype=torch.float32, device=dev) for co in cos]
+    g_b = [torch.empty(H * co, dtype=torch.float32, device=dev) if hb else None for hb, co in zip(ctx.has_b, cos)]
+    ws = workspace(max(lib.cgat_heads_linear_backward_dact_workspace_bytes(E, Hd, co, H) for co in cos), dev)
+    with torch.cuda.device(dev):
+        for net, w in enumerate((w0, w1)):
+            Co = cos[net]
+            col = net * H * Hd
+            check(lib.cgat_heads_linear_backward_dact(
+                _ptr(hidden[:, col:]), W2, Hd, _ptr(w), Hd, Co * Hd, _ptr(gs[net]), H * Co, Co,
+                _ptr(gpre[:, col:]), W2, Hd, _ptr(hidden[:, col:]), W2, Hd, _ptr(gmax), _ptr(g_w[net]), Hd, Co * Hd,
+                _ptr(g_b[net]), Co, E, Hd, Co, H, _ptr(ws), ws.numel(), _stream()), "cgat_heads_linear_backward_dact")
+    return gpre, gmax, g_w, g_b
+
+
 class EdgeHiddenHeadsFn(torch.autograd.Function):
     """EdgeHiddenFn followed by HeadsLinearFn as ONE autograd node (vector attention: both networks' first layers on
     [x_i; edge_attr; x_j], then the 2H per-head second layers; reference CGAT.py:96-109 on the message of 316-318).
@@ -1057,49 +1215,45 @@ class EdgeHiddenHeadsFn(torch.autograd.Function):
     def forward(ctx, x, edge_attr, plan, w_in, b_in, wa, ba, wm, bm, H, Hd, Co):
         _require_gpu(x, edge_attr, w_in, b_in, wa, wm)
         x, edge_attr, w_in, hidden, hmax = _edge_hidden_forward("EdgeHiddenHeadsFn", x, edge_attr, plan, w_in, b_in)
-        E = plan.E
-        cos = _cos(Co, 2)
-        ws_ = [_f32c(w.detach().reshape(H * co, Hd)) for w, co in zip((wa, wm), cos)]
-        bs_ = [None if b is None else _f32c(b.detach()) for b in (ba, bm)]
-        outs = _heads_forward(hidden, list(zip(ws_, bs_)), H, Hd, cos, hmax)
-        ctx.plan, ctx.dims = plan, (H, Hd, cos)
-        ctx.shapes = (wa.shape, wm.shape)
-        ctx.has_b = (ba is not None, bm is not None)
-        ctx.save_for_backward(x, edge_attr, w_in, hidden, ws_[0], ws_[1])
-        if debug.recording():
-            debug.last_hidden = hidden             # the calling module records the derivative pattern under its weights' names
-        return outs[0].reshape(E, H, cos[0]), outs[1].reshape(E, H, cos[1])
+        ctx.plan = plan
+        sa, sm, w0, w1 = _hidden_heads_forward(ctx, hidden, hmax, wa, ba, wm, bm, H, Hd, Co)
+        ctx.save_for_backward(x, edge_attr, w_in, hidden, w0, w1)
+        return sa, sm
 
     @staticmethod
     def backward(ctx, g_a, g_m):
         x, edge_attr, w_in, hidden, w0, w1 = ctx.saved_tensors
-        plan = ctx.plan
-        H, Hd, cos = ctx.dims
-        E, W2 = hidden.shape
-        Cn, Ce = x.shape[1], edge_attr.shape[1]
-        dev = x.device
-        gs = [_f32c(g.reshape(E, H * co)) for g, co in zip((g_a, g_m), cos)]
-        gpre = torch.empty_like(hidden)             # gradient of the PRE-activations, written head by head
-        gmax = torch.zeros(1, dtype=torch.float32, device=dev)
-        g_w = [torch.empty(H * co, Hd, dtype=torch.float32, device=dev) for co in cos]
-        g_b = [torch.empty(H * co, dtype=torch.float32, device=dev) if hb else None for hb, co in zip(ctx.has_b, cos)]
-        ws = workspace(max(lib.cgat_heads_linear_backward_dact_workspace_bytes(E, Hd, co, H) for co in cos), dev)
-        with torch.cuda.device(dev):
-            for net, w in enumerate((w0, w1)):
-                Co = cos[net]
-                col = net * H * Hd
-                check(lib.cgat_heads_linear_backward_dact(
-                    _ptr(hidden[:, col:]), W2, Hd, _ptr(w), Hd, Co * Hd, _ptr(gs[net]), H * Co, Co,
-                    _ptr(gpre[:, col:]), W2, Hd, _ptr(hidden[:, col:]), W2, Hd, _ptr(gmax), _ptr(g_w[net]), Hd, Co * Hd,
-                    _ptr(g_b[net]), Co, E, Hd, Co, H, _ptr(ws), ws.numel(), _stream()), "cgat_heads_linear_backward_dact")
-            g_x, g_e = torch.empty_like(x), torch.empty_like(edge_attr)
-            g_win, g_bin = torch.empty_like(w_in), torch.empty(W2, dtype=torch.float32, device=dev)
-            ws2 = workspace(lib.cgat_edge_hidden_backward_workspace_bytes(C.byref(plan.c), Cn, Ce, W2), dev)
-            check(lib.cgat_edge_hidden_backward(C.byref(plan.c), Cn, Ce, W2, _ptr(w_in), _ptr(x), _ptr(edge_attr),
-                                                _ptr(hidden), _ptr(gpre), 1, _ptr(gmax), _ptr(g_x), _ptr(g_e), _ptr(g_win),
-                                                _ptr(g_bin), _ptr(ws2), ws2.numel(), _stream()), "cgat_edge_hidden_backward")
+        gpre, gmax, g_w, g_b = _hidden_heads_backward(ctx, hidden, w0, w1, g_a, g_m)
+        g_x, g_e, g_win, g_bin = _edge_hidden_backward(x, edge_attr, ctx.plan, w_in, hidden, gpre, 1, gmax)
         return (g_x, g_e, None, g_win, g_bin, g_w[0].reshape(ctx.shapes[0]), g_b[0], g_w[1].reshape(ctx.shapes[1]), g_b[1],
                 None, None, None)
+
+
+class EdgeHiddenHeadsIndexedFn(torch.autograd.Function):
+    """EdgeHiddenHeadsFn for edge_attr = table[index]: EdgeHiddenIndexedFn's first layer, the same second layers, and the
+    backward's g_is_pre = 1 form (cgat_heads_linear_backward_dact, then cgat_edge_hidden_backward_indexed) -- the form the
+    harness-default shape takes.  Saves x, table, index, w_in, hidden and the head weights: no [E, Ce] tensor."""
+
+    eligible = staticmethod(EdgeHiddenHeadsFn.eligible)
+
+    @staticmethod
+    def forward(ctx, x, table, index, plan, w_in, b_in, wa, ba, wm, bm, H, Hd, Co):
+        _require_gpu(wa, wm)
+        x, table, w_in, hidden, hmax, cls = _edge_hidden_forward_indexed("EdgeHiddenHeadsIndexedFn", x, table, index,
+                                                                         plan, w_in, b_in)
+        ctx.plan, ctx.cls = plan, cls
+        sa, sm, w0, w1 = _hidden_heads_forward(ctx, hidden, hmax, wa, ba, wm, bm, H, Hd, Co)
+        ctx.save_for_backward(x, table, index, w_in, hidden, w0, w1)
+        return sa, sm
+
+    @staticmethod
+    def backward(ctx, g_a, g_m):
+        x, table, index, w_in, hidden, w0, w1 = ctx.saved_tensors
+        gpre, gmax, g_w, g_b = _hidden_heads_backward(ctx, hidden, w0, w1, g_a, g_m)
+        g_x, g_t, g_win, g_bin = _edge_hidden_backward_indexed(x, table, index, ctx.cls, ctx.plan, w_in, hidden, gpre, 1,
+                                                               gmax)
+        return (g_x, g_t, None, None, g_win, g_bin, g_w[0].reshape(ctx.shapes[0]), g_b[0], g_w[1].reshape(ctx.shapes[1]),
+                g_b[1], None, None, None)
 
 
 class HeadsLinear1Fn(torch.autograd.Function):

@@ -342,6 +342,40 @@ int cgat_edge_hidden_backward(const cgat_plan* plan, int32_t C, int32_t Ce, int3
                               const float* gpre_absmax, float* g_x, float* g_edge_attr, float* g_w_in, float* g_b_in,
                               void* ws, size_t ws_bytes, void* stream);
 
+/* The same first layer on SHELL-INDEXED edge features, edge_attr[e] = table[index[e]] with R rows (CGAT/CGAT.py:96,105-108
+ * on the message of 316-318 with the lookups of 569 / 583): Te = table W_e^T [R,W2] once, then
+ *     hidden[t, :] = LeakyReLU(Te[index[perm[t]], :] + Pi[dst[t], :] + Pj[src[t], :])
+ * by a gather of three rows, with max |hidden| folded into the same launch -- no [E,Ce] tensor and no per-edge product.
+ * `hidden` [E,W2] is stored as ever: the second layers read every row.  The backward takes the pre-activation gradient gZ
+ * as cgat_edge_hidden_backward does (g_is_pre as there; gpre_absmax is accepted for the same call shape and not read:
+ * this route runs no product that takes tensor maxima, and under "f16x3" its node-side products run in the bf16x6 form,
+ * like cgat_nodes_attention_backward_indexed's), sums it by destination and by source for g_x / grad W_i / grad W_j /
+ * g_b_in, and by CLASS -- gT[r,:] = sum of the gZ rows of class r, over the class plan of cgat_indexed_class_plan, every
+ * piece's rows in ascending order in fp64 and rounded once, a class' partial rows in fp64 in piece order -- for g_table = gT W_e [R,Ce] (embedding backward
+ * included) and grad W_e = gT^T table: the two per-edge products of the dense backward and its g_edge_attr do not exist.
+ * Rows of g_table for classes no edge uses are exactly 0.  Bitwise deterministic; the one atomic on memory is the integer
+ * maximum behind hidden_absmax.  cgat_edge_hidden_indexed_ok -- host only -- says 1 under fp32 edge storage ("f32") for
+ * N > 0, E > 0, W2 % 4 == 0 and 1 <= R <= 256, at any width (the launch is column-wise) and in every arithmetic mode; where
+ * it says 0 the calls return CGAT_ERR_UNSUPPORTED before any launch and the caller densifies.  The forward workspace holds
+ * Pi, Pj, Te and the weight images: it does not grow with E.  The backward reads the class plan that was built from
+ * `index` (cls_pos, piece_rowptr, piece_start), not `index` itself, which only has to be the same non-null array.  No
+ * allocation, no host synchronisation. */
+int32_t cgat_edge_hidden_indexed_ok(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, int32_t R);
+size_t cgat_edge_hidden_forward_indexed_workspace_bytes(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, int32_t R);
+int cgat_edge_hidden_forward_indexed(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2,
+                                     const float* w_in /* [W2,2C+Ce] */, const float* b_in /* [W2] */,
+                                     const float* x /* [N,C] */, const float* table /* [R,Ce] */, int32_t R,
+                                     const int64_t* index /* [E] */, float* hidden /* out [E,W2] */,
+                                     float* hidden_absmax /* out [1], optional */, void* ws, size_t ws_bytes, void* stream);
+size_t cgat_edge_hidden_backward_indexed_workspace_bytes(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, int32_t R);
+int cgat_edge_hidden_backward_indexed(const cgat_plan* plan, int32_t C, int32_t Ce, int32_t W2, const float* w_in,
+                                      const float* x, const float* table, int32_t R, const int64_t* index,
+                                      const int32_t* cls_pos, const int32_t* piece_rowptr, const int32_t* piece_start,
+                                      const float* hidden, const float* g_hidden, int32_t g_is_pre,
+                                      const float* gpre_absmax, float* g_x /* out [N,C] */, float* g_table /* out [R,Ce] */,
+                                      float* g_w_in /* out [W2,2C+Ce] */, float* g_b_in /* out [W2] */, void* ws,
+                                      size_t ws_bytes, void* stream);
+
 /* Debug (tests only): the routes cgat_edge_hidden_forward (backward == 0) or cgat_edge_hidden_backward (backward != 0;
  * g_is_pre as passed to it, has_absmax != 0: with a gpre_absmax) takes at these shapes in the current arithmetic mode, for
  * 16-byte aligned operands -- host only, like cgat_debug_nodes_attention_route.  One bit per route, from bit 0:
