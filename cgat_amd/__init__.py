@@ -23,6 +23,8 @@ from .ops import set_indexed_vector_attention, get_indexed_vector_attention
 from .trainer import DataParallelTrainer, Normalizer
 from .chunked import set_max_edges_per_pass
 from .capture import GraphedStep
+from . import neighbors
+from .neighbors import NeighborTables, neighbor_tables, dataset_dict_from_structures, synthetic_structures
 from . import debug
 
 __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAttention", "H_Net", "H_Net_0",
@@ -33,4 +35,5 @@ __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAtt
            "set_edge_storage", "get_edge_storage", "set_fused_inference", "get_fused_inference", "set_fused_edge_combine",
            "get_fused_edge_combine", "set_fused_attention_dropout", "get_fused_attention_dropout", "IndexedEdgeAttr", "set_indexed_edge_attr",
            "get_indexed_edge_attr", "set_indexed_edge_training", "get_indexed_edge_training", "set_indexed_vector_attention",
-           "get_indexed_vector_attention", "GraphedStep", "debug"]
+           "get_indexed_vector_attention", "GraphedStep", "debug", "neighbors", "NeighborTables", "neighbor_tables",
+           "dataset_dict_from_structures", "synthetic_structures"]

@@ -248,6 +248,9 @@ PROTOTYPES = {
     "cgat_loss_metrics": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp, vp, vp]),
     "cgat_collate_batch": (C.c_int, [C.POINTER(PackedDatasetStruct), vp, vp, vp, vp, C.c_int32, C.c_int64, C.c_int64,
                                      C.POINTER(CollatedStruct), vp]),
+    "cgat_neighbor_tables": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "cgat_debug_neighbor_tables": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double,
+                                             vp, vp, vp, vp, vp, vp, vp]),
     "cgat_bilinear_dual_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgat_bilinear_dual": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp,
                                      C.c_int64, vp, C.c_int64, C.c_int32, vp, C.c_size_t, vp]),

@@ -106,6 +106,21 @@ class PackedDataset:
         dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in arrays.items()}
         return cls(dev, host, torch.device(device))
 
+    @classmethod
+    def from_structures(cls, structures, targets, embedding, max_neighbor_number=12, stored_neighbors=24,
+                        target="e_above_hull", radius=18.0, device="cuda:0"):
+        """From raw structures -- (lattice 3x3, frac_coords n x 3, species symbols) tuples or objects of pymatgen's shape
+        -- without the reference's offline stage (prepare_data.py:146-169): the neighbour tables are built on the device
+        (csrc/neighbors.hip) with `stored_neighbors` columns, sliced to `max_neighbor_number` and packed.  Equal to
+        `from_dict(neighbors.dataset_dict_from_structures(...)[0], ...)`; crystals with too few neighbours within `radius`
+        are dropped with a warning, `kept` holds the indices of the others into `structures`."""
+        from .neighbors import dataset_dict_from_structures
+        data, kept = dataset_dict_from_structures(structures, {target: targets[target]}, stored_neighbors, radius,
+                                                  device=device)
+        ds = cls.from_dict(data, embedding, max_neighbor_number, target, device)
+        ds.kept = kept
+        return ds
+
     def __len__(self):
         return self.host["n_graphs"]
 

@@ -215,3 +215,12 @@ def edge_gw_force_six(flag):
     """Process-wide: grad W_e keeps its six-pass form on every column (the A/B reference of the bit-plane route).  Returns
     the previous setting."""
     return bool(lib.cgat_debug_edge_gw_force_six(1 if flag else 0))
+
+
+def neighbor_tables_with(lattice, frac_coords, atom_ptr, max_neighbor_number, radius, cap, first_radius=0.0):
+    """neighbors.neighbor_tables with the candidate capacity (K .. 2048) and the first working radius (0 = from the number
+    density) chosen by the caller (cgat_debug_neighbor_tables): drives the kernel's shrink / grow / does-not-fit paths.
+    Returns the tables with distances and pass counts; status 2 is reported in `.status`, not raised."""
+    from . import neighbors
+    return neighbors._run(lattice, frac_coords, atom_ptr, max_neighbor_number, radius, True, True, cap=cap,
+                          first_radius=first_radius)

@@ -97,6 +97,32 @@ int cgat_collate_batch(const cgat_packed_dataset* ds, const int32_t* ids, const 
                        const int32_t* comp_off, const int32_t* cedge_off, int32_t B, int64_t E_total, int64_t Ec_total,
                        const cgat_collated* out, void* stream);
 
+/* ---- neighbour tables from lattice + fractional coordinates (the stage before packing) -----------
+ * replaces CGAT/prepare_data.py:146-169 (pymatgen's get_all_neighbors(radius), a Python sort and a Python loop per
+ * atom): the tables a cgat_packed_dataset is packed from.  All geometry in fp64.  For every crystal g (atoms
+ * atom_ptr[g] .. atom_ptr[g+1], lattice rows a, b, c in lattice[g]): f_j = frac_j - floor(frac_j), r_j = f_j . L; the
+ * candidates of atom i are all (j, R in Z^3) with 1e-8 < d = |r_j + R.L - r_i| <= radius; sorted by d, shell ids by the
+ * reference's chain rule (a candidate opens the next shell iff d exceeds the FIRST distance of the current shell by more
+ * than 1e-8); the row keeps the first K, the shell holding the K-th place taken in ascending j, and is ordered by
+ * (shell, j).  status[g]: 0 built; 1 some atom has fewer than K candidates within radius (the reference drops the
+ * crystal); 2 beyond the kernel's limits (more than 1024 atoms in the crystal, a lattice without volume, more than 2^26
+ * (image, j) pairs in one search, or a shell holding the K-th place that does not fit the 2048-entry candidate list).
+ * Rows of crystals with status != 0 are zero-filled; no wrong row is ever written.  Outputs: shell (1..K), self_idx
+ * (crystal-local i), nbr_idx (crystal-local j), all int32 [N, K]; dist fp64 [N, K] or NULL; passes int32 [N] or NULL
+ * (searches the atom needed: 1 = the first working radius was accepted).  1 <= K <= 64, N * K < 2^31, atom_ptr
+ * non-decreasing from 0 to N.  All pointers are device pointers; bitwise deterministic; caller's stream, no allocation,
+ * no synchronisation. */
+int cgat_neighbor_tables(const double* lattice /* [G,3,3] */, const double* frac /* [N,3] */,
+                         const int32_t* atom_ptr /* [G+1] */, int32_t G, int32_t N, int32_t K, double radius, int32_t* shell,
+                         int32_t* self_idx, int32_t* nbr_idx, double* dist, int32_t* status /* [G] */, int32_t* passes,
+                         void* stream);
+/* The same with the candidate capacity (K .. 2048) and the first working radius (0 = from the number density) given by
+ * the caller: the tests drive the shrink / grow / does-not-fit paths with it. */
+int cgat_debug_neighbor_tables(const double* lattice, const double* frac, const int32_t* atom_ptr, int32_t G, int32_t N,
+                               int32_t K, double radius, int32_t cap, double first_radius, int32_t* shell,
+                               int32_t* self_idx, int32_t* nbr_idx, double* dist, int32_t* status, int32_t* passes,
+                               void* stream);
+
 /* Gradient of a small embedding table looked up once per edge (reference CGAT/CGAT.py: nbr_embedding =
  * nn.Embedding(neighbor_number + 1, nbr_embedding_size), CGAtNet.forward): g_table[k, :] = sum_{t: idx[t] == k} g[t, :].
  * Deterministic (no atomics).  idx: int64 [rows]; C <= 128, K * C <= 8192. */
