@@ -11,6 +11,7 @@ x[edge_index[1]], softmax and aggregation keyed by edge_index[1].
 """
 import itertools
 import os
+from typing import Callable, NamedTuple, Union
 
 import torch
 import torch.nn as nn
@@ -21,13 +22,122 @@ from .mlp import ResidualNetwork, SimpleNetwork
 from .ops import (AttentionPoolFn, attention_pool, get_fused_attention_dropout, EdgeHiddenFn, EdgeHiddenHeadsFn, HeadsLinear1Fn, HeadsLinearFn, NodeLayerFn, NodesAttentionFn, SegmentPlan, SegmentSoftmaxFn, SegmentSumFn, gather_rows, get_plan, get_segment_plan, linear, small_embedding,
                   segment_softmax, segment_sum)
 from .ops import overlap_enabled as ops_overlap_enabled
-from .ops import HNetFn, infer_route, nodes_attention_infer
-from .ops import IndexedEdgeAttr, get_indexed_edge_attr, indexed_route, nodes_attention_infer_indexed
-from .ops import NodesAttentionIndexedFn, NodeLayerIndexedFn, train_indexed_route
-from .ops import EdgeHiddenIndexedFn, EdgeHiddenHeadsIndexedFn, vector_indexed_route
-from .ops import EdgeHeadCombineFn, edge_combine_route
+from .ops import HNetFn, get_fused_inference, nodes_attention_infer
+from .ops import IndexedEdgeAttr, get_indexed_edge_attr, infer_indexed_ok, nodes_attention_infer_indexed
+from .ops import NodesAttentionIndexedFn, NodeLayerIndexedFn, get_indexed_edge_training, train_indexed_ok
+from .ops import EdgeHiddenIndexedFn, EdgeHiddenHeadsIndexedFn, edge_hidden_indexed_ok, get_indexed_vector_attention
+from .ops import EdgeHeadCombineFn, edge_combine_route, _indexed_operands_ok
 from .ops import branch_stream
 from .roost import Roost
+
+
+# ----------------------------------------------------------------------------------------
+# routes: which of the library's entries a layer call reaches, decided once per call
+# ----------------------------------------------------------------------------------------
+class Route(NamedTuple):
+    """What one layer call runs.  `kind`: GATConvNodes -- pair, layer_fused, scalar, vector, vector_dropout, message;
+    GATConvEdges -- rowwise, fast, generic.  `indexed`: an IndexedEdgeAttr is kept (False: forward densifies one that
+    arrives).  `no_grad`: the scalar attention half runs nodes_attention_infer[_indexed] (kinds scalar, layer_fused)."""
+    kind: str
+    indexed: bool = False
+    no_grad: bool = False
+
+
+_Lazy = Union[bool, Callable[[], bool]]     # an answer that costs a call: asked only by the route that depends on it
+
+
+def _ask(answer):
+    return answer() if callable(answer) else answer
+
+
+class NodeFacts(NamedTuple):
+    """Everything nodes_route reads of one GATConvNodes call (GATConvNodes._facts gathers it)."""
+    x_is_tensor: bool = True
+    x_cuda: bool = True
+    x_f32: bool = True
+    x_2d: bool = True
+    edge_attr_cuda: bool = True
+    N: int = 0
+    E: int = 0
+    C: int = 0
+    Ce: int = 0
+    H: int = 0
+    Hd: int = 0
+    R: int = 0                          # rows of the table of an IndexedEdgeAttr (0: a dense tensor arrived)
+    vector: bool = False
+    final: bool = False
+    first: bool = False
+    pooling: type = type(None)          # type(Pooling_NN)
+    message_own: bool = True            # type(layer).message is GATConvNodes.message
+    update_own: bool = True
+    drop: bool = False                  # dropout and training
+    grad_enabled: bool = True
+    requires_grad: bool = True          # any of x, edge_attr (its table) and the attention parameters
+    recording: bool = False             # debug.recording()
+    over_budget: bool = False           # E > chunked.max_edges_per_pass()
+    inner_pass: bool = False            # one chunk of a chunked pass
+    overlap: bool = False               # ops.overlap_enabled()
+    fused_infer: bool = True            # the switches
+    fused_dropout: bool = True
+    indexed_training: bool = False
+    indexed_vector: bool = False
+    indexed_input: bool = False         # an IndexedEdgeAttr arrived
+    operands_ok: bool = False           # ops._indexed_operands_ok of x, table, index
+    pool_supported: _Lazy = False       # AttentionPoolFn.supported at the layer's widths
+    infer_indexed_ok: _Lazy = False     # the library's answers at (N, E) and the layer's dims
+    train_indexed_ok: _Lazy = False
+    edge_hidden_indexed_ok: _Lazy = False
+
+
+def nodes_route(f):
+    """The route of a GATConvNodes call from its facts alone: no tensor, plan, library call or global is touched here
+    (the lazy answers are asked last, and only where everything else already holds)."""
+    if not f.x_is_tensor:
+        return Route("pair")
+    own = f.message_own and f.update_own
+    # no backward can follow (grad mode off, or nothing involved requires grad) and no debug recording wants the saved buffer
+    no_grad = f.fused_infer and not f.recording and (not f.grad_enabled or not f.requires_grad)
+    if f.overlap and not f.vector and not f.final and not f.drop and own and f.pooling in (H_Net, H_Net_0):
+        kind = "layer_fused"
+    elif not f.vector and f.message_own and not f.drop:
+        kind = "scalar"
+    elif f.vector and f.message_own and not f.drop:
+        kind = "vector"
+    elif (f.drop and not f.inner_pass and f.fused_dropout and f.message_own and f.x_cuda and f.edge_attr_cuda and f.x_f32
+          and f.E > 0 and _ask(f.pool_supported)):
+        kind = "vector_dropout"
+    else:
+        # subclasses overriding message(), and training-mode attention dropout where vector_dropout does not apply
+        # (switched off, CPU tensors, a shape the pooling kernels do not take, chunks)
+        kind = "message"
+    # an IndexedEdgeAttr survives one unchunked pass without training-mode dropout through the layer's own message / update
+    indexed = f.indexed_input and f.x_cuda and not f.drop and own and not f.over_budget
+    if indexed and f.vector:
+        # with grad and without; a debug recording stays (debug.note_sorted_hidden needs `hidden` alone)
+        indexed = f.indexed_vector and f.operands_ok and _ask(f.edge_hidden_indexed_ok)
+    elif indexed:
+        x_ok = f.x_f32 and f.x_2d
+        # either nodes_attention_infer_indexed, or -- a backward follows, under the training switch; a debug recording
+        # does not leave it (debug.note_attention_indexed) -- NodesAttentionIndexedFn / NodeLayerIndexedFn
+        indexed = ((x_ok and no_grad and _ask(f.infer_indexed_ok)) or
+                   (f.indexed_training and f.grad_enabled and x_ok and f.operands_ok and f.requires_grad and
+                    _ask(f.train_indexed_ok)))
+    return Route(kind, bool(indexed), no_grad and kind in ("scalar", "layer_fused"))
+
+
+class EdgeFacts(NamedTuple):
+    """Everything edges_route reads of one GATConvEdges call."""
+    indexed_input: bool = False
+    no_hyper: bool = True
+    x_cuda: bool = True
+    networks_own: bool = True           # MH_A and MH_M are MultiHeadNetwork itself
+
+
+def edges_route(f):
+    if f.no_hyper:
+        # the shipped form is row-wise: on an IndexedEdgeAttr it runs on the table's rows and the result is a lookup again
+        return Route("rowwise", f.indexed_input)
+    return Route("fast" if f.x_cuda and f.networks_own else "generic")     # (the per-edge form needs the rows themselves)
 
 
 class MultiHeadNetwork(nn.Module):
@@ -127,92 +237,94 @@ class GATConvEdges(nn.Module):
         self.first = first
         self.no_hyper = no_hyper
 
-    def _combine(self, sa, sm, drop):
-        """Generic route: logits and messages [E, H, .] in the caller's edge order -> [E, Co] (CGAT.py:214-223)."""
-        if edge_combine_route(sa, sm):
-            keep = None
-            if drop:
-                keep = _dropout_keep(sa, drop)                # CGAT.py:221
-                debug.note_dropout(keep)
-            return EdgeHeadCombineFn.apply(sa, sm, keep, None)
-        alpha = sa.exp()
-        alpha = alpha / alpha.sum(dim=1, keepdim=True)        # normalised over heads, no max-subtraction
-        if drop:
-            keep = _dropout_keep(alpha, drop)                 # CGAT.py:221
-            debug.note_dropout(keep)
-            alpha = alpha * keep
-        return (sm * alpha).mean(dim=1)
+    def _facts(self, x, edge_attr):
+        return EdgeFacts(indexed_input=isinstance(edge_attr, IndexedEdgeAttr), no_hyper=self.no_hyper,
+                         x_cuda=torch.is_tensor(x) and x.is_cuda,
+                         networks_own=type(self.MH_A) is MultiHeadNetwork and type(self.MH_M) is MultiHeadNetwork)
+
+    def route(self, x, edge_index, edge_attr):
+        """The Route `forward` takes for these arguments, without running anything."""
+        return edges_route(self._facts(x, edge_attr))
 
     def forward(self, x, edge_index, edge_attr, x_0, size=None):
-        if isinstance(edge_attr, IndexedEdgeAttr):
-            # shell-indexed edge features: the shipped form is row-wise, so it runs on the table's rows and the result is
-            # a lookup again; the per-edge hypernetwork form needs the rows themselves
-            if self.no_hyper:
-                return edge_attr.with_table(self.Pooling_NN(edge_attr.table))
+        route = self.route(x, edge_index, edge_attr)
+        if isinstance(edge_attr, IndexedEdgeAttr) and not route.indexed:
             edge_attr = edge_attr.dense()
-        if self.no_hyper:
-            return self.Pooling_NN(edge_attr)     # (the discarded attention's dropout mask is discarded with it)
+        if route.kind == "rowwise":           # (the discarded attention's dropout mask is discarded with it)
+            if route.indexed:
+                return edge_attr.with_table(self.Pooling_NN(edge_attr.table))
+            return self.Pooling_NN(edge_attr)
         drop = self.dropout if (self.dropout and self.training) else 0.0
         plan = get_plan(edge_index, x.shape[0])
-        if x.is_cuda and type(self.MH_A) is MultiHeadNetwork and type(self.MH_M) is MultiHeadNetwork:
+        if route.kind == "fast":
             aggr_out = self._message_fast(x, edge_attr, plan, drop)
-            if self.first:
-                return self.Pooling_NN(edge_attr, aggr_out)
-            return self.Pooling_NN(x_0, edge_attr, aggr_out)
-        splan0, splan1 = _endpoint_plans(plan, edge_index)
-        x_i = gather_rows(x, edge_index[0], splan0)           # note: opposite naming to GATConvNodes (209-210)
-        x_j = gather_rows(x, edge_index[1], splan1)
-        m = torch.cat([x_i, edge_attr, x_j], dim=-1)
-        aggr_out = self._combine(self.MH_A(m), self.MH_M(m), drop)
+        else:
+            splan0, splan1 = _endpoint_plans(plan, edge_index)
+            x_i = gather_rows(x, edge_index[0], splan0)           # note: opposite naming to GATConvNodes (209-210)
+            x_j = gather_rows(x, edge_index[1], splan1)
+            m = torch.cat([x_i, edge_attr, x_j], dim=-1)
+            # logits and messages [E, H, .] in the caller's edge order -> [E, Co] (CGAT.py:214-223)
+            aggr_out = _head_softmax_mean(self.MH_A(m), self.MH_M(m), drop)
         if self.first:
             return self.Pooling_NN(edge_attr, aggr_out)
         return self.Pooling_NN(x_0, edge_attr, aggr_out)
 
+    def _message_fast(self, x, edge_attr, plan, drop=0.0):
+        """The attention / message networks of the edge update without the concatenated [E, 2C+Ce] rows: first layers of
+        both networks as ONE operand-split op in destination-sorted slot order (EdgeHiddenFn, the op of the
+        vector-attention node layer), the 2H second layers as one autograd node, the head softmax and mean on [E, H, .]
+        tensors, and one permutation back to the caller's edge order at the end."""
+        a, m = self.MH_A, self.MH_M
+        H, Hd, D, C, Ce = self.heads, a.hidden_layer_dim, a.input_dim, self.in_channels, self.nbr_channels
+        w = torch.cat([a.fc_in.weight.reshape(H * Hd, D), m.fc_in.weight.reshape(H * Hd, D)], dim=0)
+        # the edge update names the endpoints the other way round (CGAT.py:209-210: x_i = x[edge_index[0]]); the op
+        # multiplies its first column block with x[edge_index[1]] and its last with x[edge_index[0]]: swap the blocks
+        w = torch.cat([w[:, C + Ce:], w[:, C:C + Ce], w[:, :C]], dim=1)
+        sa, sm = _two_layers(a, m, x, edge_attr, plan, w, torch.cat([a.fc_in.bias, m.fc_in.bias]))
+        return _head_softmax_mean(sa, sm, drop, plan.dst_perm)
 
-def _gatconvedges_message_fast(self, x, edge_attr, plan, drop=0.0):
-    """The attention / message networks of the edge update without the concatenated [E, 2C+Ce] rows: first layers of
-    both networks as ONE operand-split op in destination-sorted slot order (EdgeHiddenFn, the op of the vector-attention
-    node layer), the 2H second layers as one autograd node, the head softmax and mean on [E, H, .] tensors, and one
-    permutation back to the caller's edge order at the end."""
-    a, m = self.MH_A, self.MH_M
-    H, Hd, Co = self.heads, a.hidden_layer_dim, self.out_channels
-    D, C, Ce = a.input_dim, self.in_channels, self.nbr_channels
-    w = torch.cat([a.fc_in.weight.reshape(H * Hd, D), m.fc_in.weight.reshape(H * Hd, D)], dim=0)
-    # the edge update names the endpoints the other way round (CGAT.py:209-210: x_i = x[edge_index[0]]); the op
-    # multiplies its first column block with x[edge_index[1]] and its last with x[edge_index[0]]: swap the blocks
-    w = torch.cat([w[:, C + Ce:], w[:, C:C + Ce], w[:, :C]], dim=1)
-    b_in = torch.cat([a.fc_in.bias, m.fc_in.bias])
-    if EdgeHiddenHeadsFn.eligible(w.shape[0], H, Hd, (a.output_dim, Co)):
-        sa, sm = EdgeHiddenHeadsFn.apply(x, edge_attr, plan, w, b_in, a.fc_out.weight, a.fc_out.bias, m.fc_out.weight,
-                                         m.fc_out.bias, H, Hd, (a.output_dim, Co))
-        if debug.recording():
-            debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, debug.last_hidden)
+
+def _two_layers(a, m, x, edge_attr, plan, w_in, b_in, indexed=False):
+    """First layers of both networks of a layer (MH_A, MH_M; w_in, b_in their stacked first-layer parameters) on the
+    operand split, then the 2H second layers: logits and messages [E, H, .] in destination-sorted slot order.  On a
+    dense edge_attr or (indexed) on a lookup: the same two forms, no [E, Ce] tensor."""
+    H, Hd = a.nb_heads, a.hidden_layer_dim
+    first = (edge_attr.table, edge_attr.index) if indexed else (edge_attr,)
+    second = (a.fc_out.weight, a.fc_out.bias, m.fc_out.weight, m.fc_out.bias, H, Hd, (a.output_dim, m.output_dim))
+    if EdgeHiddenHeadsFn.eligible(w_in.shape[0], H, Hd, (a.output_dim, m.output_dim)):
+        # first layers + the 2H second layers as ONE autograd node: its backward folds LeakyReLU' into the second
+        # layers' input-gradient products instead of an elementwise pass over [E, 2 H Hd] (ops.EdgeHiddenHeadsFn)
+        heads_fn = EdgeHiddenHeadsIndexedFn if indexed else EdgeHiddenHeadsFn
+        sa, sm = heads_fn.apply(x, *first, plan, w_in, b_in, *second)
+        hid = debug.last_hidden
     else:
-        hid, hmax = EdgeHiddenFn.apply(x, edge_attr, plan, w, b_in)                      # [E, 2*H*Hd], sorted slots
-        if debug.recording():
-            debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, hid)
-        sa, sm = HeadsLinearFn.apply(hid, a.fc_out.weight, a.fc_out.bias, m.fc_out.weight, m.fc_out.bias, H, Hd,
-                                     (a.output_dim, Co), hmax)
+        hidden_fn = EdgeHiddenIndexedFn if indexed else EdgeHiddenFn
+        hid, hmax = hidden_fn.apply(x, *first, plan, w_in, b_in)                         # [E, 2*H*Hd], sorted slots
+        # second layers of all 2H heads as one autograd node (ops.HeadsLinearFn): [E,H,Co] each
+        sa, sm = HeadsLinearFn.apply(hid, *second, hmax)
+    if debug.recording():
+        debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, hid)
+    return sa, sm
+
+
+def _head_softmax_mean(sa, sm, drop, perm=None):
+    """Softmax over the heads (no max-subtraction), dropout, times the message, head mean (CGAT.py:214-223): logits and
+    messages [E, H, .] -> [E, Co].  `perm` (plan.dst_perm): the rows are destination-sorted slots and the result goes
+    back to the caller's edge order; None: they are in that order already."""
+    keep = None
+    if drop:
+        keep = _dropout_keep(sa, drop)                        # CGAT.py:221
+        if debug.recording():                                 # (recorded in the caller's edge order)
+            debug.note_dropout(keep if perm is None else torch.empty_like(keep).index_copy(0, perm.long(), keep))
     if edge_combine_route(sa, sm):
         # exp, head sum, division, dropout, product, head mean and the permutation back as one kernel per direction
-        keep = None
-        if drop:
-            keep = _dropout_keep(sa, drop)                    # CGAT.py:221; rows are destination-sorted slots here
-            if debug.recording():
-                debug.note_dropout(torch.empty_like(keep).index_copy(0, plan.dst_perm.long(), keep))
-        return EdgeHeadCombineFn.apply(sa, sm, keep, plan.dst_perm)
+        return EdgeHeadCombineFn.apply(sa, sm, keep, perm)
     alpha = sa.exp()
-    alpha = alpha / alpha.sum(dim=1, keepdim=True)        # normalised over heads, no max-subtraction (CGAT.py:219-221)
-    if drop:
-        keep = _dropout_keep(alpha, drop)                 # CGAT.py:221; rows are destination-sorted slots here
-        if debug.recording():
-            debug.note_dropout(torch.empty_like(keep).index_copy(0, plan.dst_perm.long(), keep))
+    alpha = alpha / alpha.sum(dim=1, keepdim=True)
+    if keep is not None:
         alpha = alpha * keep
-    aggr = (sm * alpha).mean(dim=1)                       # [E, Co] in sorted slot order
-    return torch.empty_like(aggr).index_copy(0, plan.dst_perm.long(), aggr)
-
-
-GATConvEdges._message_fast = _gatconvedges_message_fast
+    out = (sm * alpha).mean(dim=1)
+    return out if perm is None else torch.empty_like(out).index_copy(0, perm.long(), out)
 
 
 class _RowPlan:
@@ -255,79 +367,81 @@ class GATConvNodes(nn.Module):
         elif not final:
             self.Pooling_NN = H_Net(out_channels, 3, out_channels, out_channels, 2, out_channels, out_channels)
 
-    # -- fused scalar-attention path: one call into cgat_nodes_attention_forward ---------
-    #    (no backward can follow -- torch.no_grad(), inference_mode(), nothing requires grad --: the forward without
-    #    grad, ops.nodes_attention_infer: same results, no saved buffer, no per-edge activations at the benchmark widths)
+    # -- the route of one call: gathered facts -> nodes_route.  `forward` asks once; the runners below receive the answer
+    #    and decide nothing (handed a combination they cannot run, they raise) ----------------------------------------
+    def _facts(self, x, edge_index, edge_attr, inner_pass=False):
+        if not torch.is_tensor(x):
+            return NodeFacts(x_is_tensor=False)
+        indexed = isinstance(edge_attr, IndexedEdgeAttr)
+        ea = edge_attr.table if indexed else edge_attr
+        N, E, H, Hd = x.shape[0], edge_index.shape[1], self.heads, self.MH_A.hidden_layer_dim
+        C, Ce, R = (x.shape[1] if x.dim() == 2 else 0), edge_attr.shape[1], (ea.shape[0] if indexed else 0)
+        plan_c = lambda: _lib.Plan(N, E, 0, 0, 0, 0, 0, 0)           # (the library's answers read N and E of a plan)
+        return NodeFacts(
+            x_cuda=x.is_cuda, x_f32=x.dtype == torch.float32, x_2d=x.dim() == 2, edge_attr_cuda=ea.is_cuda,
+            N=N, E=E, C=C, Ce=Ce, H=H, Hd=Hd, R=R, vector=bool(self.vector_attention), final=bool(self.final),
+            first=bool(self.first), pooling=type(getattr(self, "Pooling_NN", None)),
+            message_own=type(self).message is GATConvNodes.message, update_own=type(self).update is GATConvNodes.update,
+            drop=bool(self.dropout and self.training),      # F.dropout(..., training=self.training): identity in eval mode
+            grad_enabled=torch.is_grad_enabled(),
+            requires_grad=x.requires_grad or ea.requires_grad or any(t is not None and t.requires_grad
+                                                                   for t in self._attn_params()),
+            recording=debug.recording(), over_budget=E > chunked.max_edges_per_pass(), inner_pass=inner_pass,
+            overlap=ops_overlap_enabled(), fused_infer=get_fused_inference(), fused_dropout=get_fused_attention_dropout(),
+            indexed_training=get_indexed_edge_training(), indexed_vector=get_indexed_vector_attention(),
+            indexed_input=indexed, operands_ok=indexed and _indexed_operands_ok(x, ea, edge_attr.index, N, E),
+            pool_supported=lambda: AttentionPoolFn.supported(x.new_empty(0, H * self.MH_A.output_dim),
+                                                             x.new_empty(0, H * self.out_channels)),
+            infer_indexed_ok=lambda: infer_indexed_ok(plan_c(), C, Ce, H, Hd, R),
+            train_indexed_ok=lambda: train_indexed_ok(plan_c(), C, Ce, H, Hd, R),
+            edge_hidden_indexed_ok=lambda: edge_hidden_indexed_ok(plan_c(), C, Ce, 2 * H * Hd, R))
+
+    def route(self, x, edge_index, edge_attr, inner_pass=False):
+        """The Route of one pass of `forward` over these arguments, without running anything (no launch, no plan).
+        inner_pass: as one chunk of a chunked pass (E beyond chunked.max_edges_per_pass()) is routed."""
+        return nodes_route(self._facts(x, edge_index, edge_attr, inner_pass))
+
     def _attn_params(self):
         a, m = self.MH_A, self.MH_M
         return (a.fc_in.weight, a.fc_in.bias, a.fc_out.weight, a.fc_out.bias, m.fc_in.weight, m.fc_in.bias,
                 m.fc_out.weight, m.fc_out.bias)
 
-    def _aggregate_fused(self, x, edge_attr, plan):
+    # -- fused scalar-attention path: one call into cgat_nodes_attention_forward, or -- route.no_grad: no backward can
+    #    follow -- the forward without grad (ops.nodes_attention_infer: same results, no saved buffer, no per-edge
+    #    activations at the benchmark widths); route.indexed: the same two on the lookup -----------------------------
+    def _aggregate_fused(self, x, edge_attr, plan, route):
+        if route.kind not in ("scalar", "layer_fused"):
+            raise ValueError(f"GATConvNodes: the fused scalar-attention path cannot run {route}")
         params = self._attn_params()
-        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route: one of the two holds)
-            if infer_route(x, edge_attr.table, params):
-                return nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *params)
+        if route.indexed and route.no_grad:
+            return nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *params)
+        if route.indexed:
             return NodesAttentionIndexedFn.apply(x, edge_attr.table, edge_attr.index, plan, self.heads, *params)
-        if infer_route(x, edge_attr, params):
+        if route.no_grad:
             return nodes_attention_infer(x, edge_attr, plan, self.heads, *params)
         return NodesAttentionFn.apply(x, edge_attr, plan, self.heads, *params)
 
-    def _indexed_route(self, x, edge_index, edge_attr):
-        """True when this call, given an IndexedEdgeAttr, keeps it: one unchunked pass, no training-mode dropout, message /
-        update the layer's own, and -- vector attention -- ops.vector_indexed_route holds (the opt-in switch
-        ops.set_indexed_vector_attention, with grad and without), or -- scalar attention -- either no backward to follow
-        and no debug recording (ops.infer_route: ops.nodes_attention_infer_indexed runs) or a backward to follow under
-        ops.set_indexed_edge_training (ops.NodesAttentionIndexedFn / NodeLayerIndexedFn run), at a shape the library takes
-        for that route in the current arithmetic and edge-storage modes.  Everything else densifies and runs as it
-        always has."""
-        if (not torch.is_tensor(x) or (self.dropout and self.training) or
-                type(self).message is not GATConvNodes.message or type(self).update is not GATConvNodes.update or
-                edge_index.shape[1] > chunked.max_edges_per_pass() or not x.is_cuda):
-            return False
-        if self.vector_attention:
-            # under ops.set_indexed_vector_attention, with grad and without: the first layer of both networks on the lookup
-            # (ops.EdgeHiddenIndexedFn / EdgeHiddenHeadsIndexedFn); everything behind `hidden` is unchanged
-            W2 = 2 * self.heads * self.MH_A.hidden_layer_dim
-            return vector_indexed_route(x, edge_attr, get_plan(edge_index, x.shape[0]), W2)
-        plan, params = get_plan(edge_index, x.shape[0]), self._attn_params()
-        return indexed_route(x, edge_attr, plan, self.heads, params) or train_indexed_route(x, edge_attr, plan, self.heads, params)
-
     # -- vector attention (CGAT.py:286-290: MH_A emits one logit per head AND channel): the shared first layer of both
     #    networks runs as one operand-split op in destination-sorted order, so the concatenated message [E, 2C+Ce],
-    #    its K = 2C+Ce products and the two permutations of the generic path disappear.  With `keep` (training-mode
-    #    attention dropout, CGAT.py:325: the keep-mask of the coefficients, [E, H, Co | 1] in ORIGINAL edge order) also
-    #    the scalar-attention layer runs here, MH_A's second layers emitting one logit per head: the pooling kernels
+    #    its K = 2C+Ce products and the two permutations of the generic path disappear.  With training-mode attention
+    #    dropout (route vector_dropout; CGAT.py:325: a keep-mask of the coefficients, [E, H, Co | 1] in ORIGINAL edge order)
+    #    also the scalar-attention layer runs here, MH_A's second layers emitting one logit per head: the pooling kernels
     #    take the mask as an operand and reach its rows through plan.dst_perm ----------------------------------------
-    def _aggregate_vector(self, x, edge_attr, plan, edge_index, keep=None):
+    def _aggregate_vector(self, x, edge_attr, plan, route):
+        if route.kind not in ("vector", "vector_dropout"):
+            raise ValueError(f"GATConvNodes: the operand-split path cannot run {route}")
         a, m = self.MH_A, self.MH_M
-        H, Hd, Co = self.heads, a.hidden_layer_dim, self.out_channels
-        D = a.input_dim
-        cos = Co if a.output_dim == Co else (a.output_dim, Co)
+        H, Hd, Co, D, E = self.heads, a.hidden_layer_dim, self.out_channels, a.input_dim, plan.E
+        keep = None
+        if route.kind == "vector_dropout":
+            # drawn on the shape and in the edge order of the MessagePassing-style route's alpha: one seed, one mask
+            keep = _dropout_keep(x.new_empty(E, H, a.output_dim), self.dropout)                      # CGAT.py:325
+            debug.note_dropout(keep)
         w_in = torch.cat([a.fc_in.weight.reshape(H * Hd, D), m.fc_in.weight.reshape(H * Hd, D)], dim=0)
-        b_in = torch.cat([a.fc_in.bias, m.fc_in.bias])
-        E = plan.E
-        # (an IndexedEdgeAttr here: forward has checked _indexed_route; the same two forms on the lookup, no [E, Ce] tensor)
-        indexed = isinstance(edge_attr, IndexedEdgeAttr)
-        first = (edge_attr.table, edge_attr.index) if indexed else (edge_attr,)
-        if EdgeHiddenHeadsFn.eligible(w_in.shape[0], H, Hd, (a.output_dim, Co)):
-            # first layers + the 2H second layers as ONE autograd node: its backward folds LeakyReLU' into the second
-            # layers' input-gradient products instead of an elementwise pass over [E, 2 H Hd] (ops.EdgeHiddenHeadsFn)
-            heads_fn = EdgeHiddenHeadsIndexedFn if indexed else EdgeHiddenHeadsFn
-            sa, sm = heads_fn.apply(x, *first, plan, w_in, b_in, a.fc_out.weight, a.fc_out.bias,
-                                    m.fc_out.weight, m.fc_out.bias, H, Hd, cos)
-            if debug.recording():
-                debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, debug.last_hidden)
-        else:
-            hidden_fn = EdgeHiddenIndexedFn if indexed else EdgeHiddenFn
-            hid, hmax = hidden_fn.apply(x, *first, plan, w_in, b_in)                         # [E, 2*H*Hd], sorted slots
-            if debug.recording():
-                debug.note_sorted_hidden((a.fc_in.weight, m.fc_in.weight), plan, hid)
-            # second layers of all 2H heads as one autograd node (ops.HeadsLinearFn): [E,H,Co] each
-            sa, sm = HeadsLinearFn.apply(hid, a.fc_out.weight, a.fc_out.bias, m.fc_out.weight, m.fc_out.bias, H, Hd, cos, hmax)
+        sa, sm = _two_layers(a, m, x, edge_attr, plan, w_in, torch.cat([a.fc_in.bias, m.fc_in.bias]), route.indexed)
         sa2, sm2 = sa.reshape(E, -1), sm.reshape(E, -1)
         if keep is not None:
-            # (_attn_dropout_route has checked the shape) softmax, mask, product and sum as one kernel per direction
+            # (the route has checked the shape) softmax, mask, product and sum as one kernel per direction
             agg = AttentionPoolFn.apply(sa2, None, sm2, plan.dst_rowptr, None, 1e-16, keep.reshape(E, -1), plan.dst_perm)
         elif E > 0 and AttentionPoolFn.supported(sa2, sm2):
             # channel-wise softmax over each atom's incoming edges, times the message, summed per atom: one kernel per
@@ -337,16 +451,6 @@ class GATConvNodes(nn.Module):
             alpha = SegmentSoftmaxFn.apply(sa2, None, plan.dst_rowptr, 1e-16)
             agg = SegmentSumFn.apply(sm2 * alpha, plan.dst_rowptr, plan.dst_sorted.long())
         return agg.reshape(plan.N, H, Co).mean(dim=1)
-
-    def _attn_dropout_route(self, x, edge_attr, plan):
-        """True when training-mode attention dropout runs on the operand-split route with the keep-mask pooling kernels:
-        the switch is on (ops.set_fused_attention_dropout), message() is the layer's own, the tensors are on the GPU and
-        the pooling shape is one the kernels take.  Everything else keeps the MessagePassing-style route."""
-        if not (get_fused_attention_dropout() and type(self).message is GATConvNodes.message and x.is_cuda and
-                edge_attr.is_cuda and x.dtype == torch.float32 and plan.E > 0):
-            return False
-        H = self.heads
-        return AttentionPoolFn.supported(x.new_empty(0, H * self.MH_A.output_dim), x.new_empty(0, H * self.out_channels))
 
     # -- MessagePassing-style surface (subclasses overriding message) --
     def message(self, x_i, x_j, edge_attr, edge_index_i, plan=None):
@@ -363,10 +467,24 @@ class GATConvNodes(nn.Module):
             alpha = alpha * keep
         return m * alpha
 
+    def _aggregate_message(self, x_src, x_dst, edge_index, edge_attr, plan, splans):
+        """The MessagePassing-style route: gather both endpoints (x_j from x_src with edge_index[0], x_i from x_dst with
+        edge_index[1]; splans: their row plans), message(), sum per destination, head mean -> [plan.N, Co]."""
+        x_j = gather_rows(x_src, edge_index[0], splans[0])
+        x_i = gather_rows(x_dst, edge_index[1], splans[1])
+        msg = self.message(x_i, x_j, edge_attr, edge_index[1], plan=plan)                 # [E,H,C]
+        E = msg.shape[0]
+        perm = plan.dst_perm.long()
+        agg = SegmentSumFn.apply(msg.reshape(E, -1).index_select(0, perm), plan.dst_rowptr,
+                                 edge_index[1].index_select(0, perm))
+        return agg.reshape(plan.N, self.heads, self.out_channels).mean(dim=1)
+
     # -- whole layer as one autograd node (scalar attention + H_Net update): lets the backward overlap the
     #    hypernetwork's weight-gradient contractions with the attention backward (ops.NodeLayerFn) -----------------
-    def _layer_fused(self, x, edge_attr, x_0, plan):
-        a, m, pool = self.MH_A, self.MH_M, self.Pooling_NN
+    def _layer_fused(self, x, edge_attr, x_0, plan, route):
+        if route.kind != "layer_fused":
+            raise ValueError(f"GATConvNodes: the whole-layer node cannot run {route}")
+        pool = self.Pooling_NN
         hyper = pool.Hyper
         flat = []
         for layer in hyper.layers:
@@ -378,21 +496,19 @@ class GATConvNodes(nn.Module):
             with torch.no_grad():
                 pool.damping.data = pool.damping.data.clamp(0.0, 1.0)      # Hypernetworksmp.py:307, as H_Net.forward
             h0, damping = x_0, pool.damping
-        if isinstance(edge_attr, IndexedEdgeAttr):        # (forward has checked _indexed_route: one of the two holds)
-            if infer_route(x, edge_attr.table, self._attn_params()):
-                aggr = nodes_attention_infer_indexed(x, edge_attr, plan, self.heads, *self._attn_params())
-                return HNetFn.apply(h0, aggr, damping, hyper.n_fc, len(hyper.layers), *flat)
+        if route.no_grad:
+            # the attention half without grad; the hypernetwork as its own node (NodeLayerFn's forward runs the same call)
+            aggr = self._aggregate_fused(x, edge_attr, plan, route)
+            return HNetFn.apply(h0, aggr, damping, hyper.n_fc, len(hyper.layers), *flat)
+        if route.indexed:
             return NodeLayerIndexedFn.apply(x, edge_attr.table, edge_attr.index, h0, plan, self.heads, damping, hyper.n_fc,
                                             len(hyper.layers), *self._attn_params(), *flat)
-        if infer_route(x, edge_attr, self._attn_params()):
-            # the attention half without grad; the hypernetwork as its own node (NodeLayerFn's forward runs the same call)
-            aggr = nodes_attention_infer(x, edge_attr, plan, self.heads, *self._attn_params())
-            return HNetFn.apply(h0, aggr, damping, hyper.n_fc, len(hyper.layers), *flat)
         return NodeLayerFn.apply(x, edge_attr, h0, plan, self.heads, damping, hyper.n_fc, len(hyper.layers),
-                                 a.fc_in.weight, a.fc_in.bias, a.fc_out.weight, a.fc_out.bias,
-                                 m.fc_in.weight, m.fc_in.bias, m.fc_out.weight, m.fc_out.bias, *flat)
+                                 *self._attn_params(), *flat)
 
-    def propagate(self, edge_index, x, edge_attr, x_0):
+    def propagate(self, edge_index, x, edge_attr, x_0, route=None):
+        """One pass on `route` (None: asked here), or -- beyond the per-pass budget -- chunk by chunk, each chunk's inner
+        pass on its own route."""
         if edge_index.shape[1] > chunked.max_edges_per_pass():
             # beyond the per-pass budget (BASELINE configs[4]: 64 M edges): closed chunks of the graph, one at a time
             chunks = chunked.closed_chunks(edge_index, x.shape[0], chunked.max_edges_per_pass())
@@ -403,42 +519,26 @@ class GATConvNodes(nn.Module):
                         os.environ.get("CGAT_CHUNK_SPLIT", "1") != "0"):
                     # aggregate (6 KB of saved state per edge) is recomputed per chunk in backward, update (the
                     # hypernetwork: small state) is not: 2 + 1 passes instead of 2 + 2
-                    agg = lambda xs, ei, es: self._aggregate_fused(xs, es, get_plan(ei, xs.shape[0]))
+                    agg = lambda xs, ei, es: self._aggregate_fused(xs, es, get_plan(ei, xs.shape[0]),
+                                                                   self.route(xs, ei, es, inner_pass=True))
                     upd = lambda aggr, x0s, xs: self.update(aggr, x_0=x0s, x=xs, _mean_done=True)
                     return chunked.ChunkedSplitLayerFn.apply(agg, upd, chunks, x, edge_attr, x_0, *self.parameters())
-                run = lambda xs, ei, es, x0s: self._propagate_one(ei, xs, es, x0s, fused_dropout=False)
+                run = lambda xs, ei, es, x0s: self._propagate_one(ei, xs, es, x0s, self.route(xs, ei, es, inner_pass=True))
                 return chunked.ChunkedLayerFn.apply(run, chunks, x, edge_attr, x_0, *self.parameters())
-        return self._propagate_one(edge_index, x, edge_attr, x_0)
+        return self._propagate_one(edge_index, x, edge_attr, x_0, route or self.route(x, edge_index, edge_attr))
 
-    def _propagate_one(self, edge_index, x, edge_attr, x_0, fused_dropout=True):
-        """`fused_dropout=False` (the chunked pass): training-mode attention dropout keeps the MessagePassing-style route."""
+    def _propagate_one(self, edge_index, x, edge_attr, x_0, route):
         plan = get_plan(edge_index, x.shape[0])
-        drop = bool(self.dropout and self.training)       # F.dropout(..., training=self.training): identity in eval mode
-        if (ops_overlap_enabled() and not self.vector_attention and not self.final and not drop and
-                type(self).message is GATConvNodes.message and type(self).update is GATConvNodes.update and
-                type(self.Pooling_NN) in (H_Net, H_Net_0)):
-            return self._layer_fused(x, edge_attr, x_0, plan)
-        if not self.vector_attention and type(self).message is GATConvNodes.message and not drop:
-            aggr = self._aggregate_fused(x, edge_attr, plan)
-        elif self.vector_attention and type(self).message is GATConvNodes.message and not drop:
-            aggr = self._aggregate_vector(x, edge_attr, plan, edge_index)
-        elif drop and fused_dropout and self._attn_dropout_route(x, edge_attr, plan):
-            # drawn on the shape and in the edge order of the MessagePassing-style route's alpha: one seed, one mask
-            keep = _dropout_keep(x.new_empty(plan.E, self.heads, self.MH_A.output_dim), self.dropout)   # CGAT.py:325
-            debug.note_dropout(keep)
-            aggr = self._aggregate_vector(x, edge_attr, plan, edge_index, keep=keep)
+        if route.kind == "layer_fused":
+            return self._layer_fused(x, edge_attr, x_0, plan, route)
+        if route.kind == "scalar":
+            aggr = self._aggregate_fused(x, edge_attr, plan, route)
+        elif route.kind in ("vector", "vector_dropout"):
+            aggr = self._aggregate_vector(x, edge_attr, plan, route)
+        elif route.kind == "message" and not route.indexed:
+            aggr = self._aggregate_message(x, x, edge_index, edge_attr, plan, _endpoint_plans(plan, edge_index))
         else:
-            # the MessagePassing-style route: subclasses overriding message(), and training-mode attention dropout where
-            # the route above does not apply (switched off, CPU tensors, a shape the pooling kernels do not take, chunks)
-            splan0, splan1 = _endpoint_plans(plan, edge_index)
-            x_j = gather_rows(x, edge_index[0], splan0)
-            x_i = gather_rows(x, edge_index[1], splan1)
-            msg = self.message(x_i, x_j, edge_attr, edge_index[1], plan=plan)             # [E,H,C]
-            E = msg.shape[0]
-            perm = plan.dst_perm.long()
-            agg = SegmentSumFn.apply(msg.reshape(E, -1).index_select(0, perm), plan.dst_rowptr,
-                                     edge_index[1].index_select(0, perm))
-            aggr = agg.reshape(plan.N, self.heads, self.out_channels).mean(dim=1)
+            raise ValueError(f"GATConvNodes: one pass over a node tensor cannot run {route}")
         return self.update(aggr, x_0=x_0, x=x, _mean_done=True)
 
     def update(self, aggr_out, x_0, x, _mean_done=False):
@@ -462,20 +562,13 @@ class GATConvNodes(nn.Module):
             if edge_index.shape[1] and int(edge_index[1].max()) >= n_dst:
                 raise IndexError(f"cgat_amd: edge_index[1] reaches beyond the {n_dst} target rows")
             plan._pair_plans[key] = (SegmentPlan(edge_index[0], n_src), _RowPlan(plan.dst_rowptr, plan.dst_perm, n_dst))
-        splan0, splan1 = plan._pair_plans[key]
-        x_j = gather_rows(x_src, edge_index[0], splan0)
-        x_i = gather_rows(x_dst, edge_index[1], splan1)
-        msg = self.message(x_i, x_j, edge_attr, edge_index[1], plan=plan)                 # [E,H,C]
-        E = msg.shape[0]
-        perm = plan.dst_perm.long()
-        agg = SegmentSumFn.apply(msg.reshape(E, -1).index_select(0, perm), plan.dst_rowptr,
-                                 edge_index[1].index_select(0, perm))
-        return agg.reshape(plan.N, self.heads, self.out_channels).mean(dim=1)[:n_dst]
+        return self._aggregate_message(x_src, x_dst, edge_index, edge_attr, plan, plan._pair_plans[key])[:n_dst]
 
     def forward(self, x, edge_index, edge_attr, x_0, size=None):
-        if isinstance(edge_attr, IndexedEdgeAttr) and not self._indexed_route(x, edge_index, edge_attr):
+        route = self.route(x, edge_index, edge_attr)
+        if isinstance(edge_attr, IndexedEdgeAttr) and not route.indexed:
             edge_attr = edge_attr.dense()
-        if not torch.is_tensor(x):
+        if route.kind == "pair":
             x_src, x_dst = x[0], x[1]
             if x_src is None or x_dst is None or not self.final:
                 # the reference's update() hands `x` to the hypernetwork (CGAT.py:328-335), which needs a tensor, and its
@@ -483,7 +576,7 @@ class GATConvNodes(nn.Module):
                 raise TypeError("GATConvNodes: x = (x_source, x_target) needs two tensors and final=True "
                                 "(the hypernetwork update takes a single node tensor, as in the reference)")
             return self._propagate_pair(edge_index, x_src, x_dst, edge_attr)
-        return self.propagate(edge_index, x=x, edge_attr=edge_attr, x_0=x_0)
+        return self.propagate(edge_index, x, edge_attr, x_0, route)
 
     def __repr__(self):
         return '{}({}, {}, heads={})'.format(self.__class__.__name__, self.in_channels, self.out_channels, self.heads)

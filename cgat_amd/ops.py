@@ -14,11 +14,14 @@ from ._lib import lib, check
 # ----------------------------------------------------------------------------------------
 # plumbing
 # ----------------------------------------------------------------------------------------
+_NO_CPU = ("cgat_amd: the HIP path needs tensors on an MI355X device (cuda:N); "
+           "there is no CPU fallback -- use oracle/ only for checking")
+
+
 def _require_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
-            raise RuntimeError("cgat_amd: the HIP path needs tensors on an MI355X device (cuda:N); "
-                               "there is no CPU fallback -- use oracle/ only for checking")
+            raise RuntimeError(_NO_CPU)
 
 
 def _f32c(t):
@@ -90,6 +93,18 @@ def _param_grad(w):
         if t is not None:
             return t
     return torch.empty_like(w)
+
+
+class _Switch:
+    """One on/off switch of the package: its value, the env variable a fresh process reads it from ("0" / "1"; anything
+    else leaves the default) and its default.  A default of None makes it a tri-state: None stays None until set."""
+
+    def __init__(self, env, default):
+        self.env, self.default = env, default
+        self.value = {"0": False, "1": True}.get(os.environ.get(env), default)
+
+    def set(self, flag):
+        self.value = None if (flag is None and self.default is None) else bool(flag)
 
 
 _validate_indices = os.environ.get("CGAT_VALIDATE_INDICES", "1") != "0"
@@ -224,13 +239,19 @@ def _attn_params(x, edge_attr, H, ws_):
     return p, Hd
 
 
+def _require_scalar_attention(who, H, weights):
+    """MH_A's second layers emit one logit per head (the fused attention entries take nothing else)."""
+    A_in_w, A_out_w = weights[0], weights[2]
+    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
+        raise ValueError(f"{who} handles scalar attention (MH_A output_dim == 1)")
+
+
 def _attn_forward(x, edge_attr, plan, H, weights, *, save):
     """The scalar-attention forward behind NodesAttentionFn and NodeLayerFn (save=True: the training forward with its saved
     buffer) and nodes_attention_infer (save=False).  Returns (aggr, saved or None, the prepared weights)."""
-    A_in_w, A_out_w, M_in_w = weights[0], weights[2], weights[4]
+    A_in_w, M_in_w = weights[0], weights[4]
     ws_ = [_f32c(w.detach()) for w in weights]
-    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
-        raise ValueError("_attn_forward handles scalar attention (MH_A output_dim == 1)")
+    _require_scalar_attention("_attn_forward", H, weights)
     N, E = plan.N, plan.E
     if x.shape[0] != N or edge_attr.shape[0] != E:
         raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, edge_attr {tuple(edge_attr.shape)}")
@@ -292,7 +313,7 @@ class NodesAttentionFn(torch.autograd.Function):
         return (g_x, g_e, None, None, *grads)
 
 
-_fused_infer = os.environ.get("CGAT_FUSED_INFER", "1") != "0"
+_fused_infer = _Switch("CGAT_FUSED_INFER", True)
 
 
 def set_fused_inference(flag):
@@ -300,12 +321,11 @@ def set_fused_inference(flag):
     off): under torch.no_grad() / inference_mode(), or when nothing of a layer requires grad, GATConvNodes runs
     nodes_attention_infer instead of the autograd node -- same results bit for bit, no saved buffer, and at the
     benchmark widths no per-edge activations at all.  Off: the training forward runs (the A/B reference)."""
-    global _fused_infer
-    _fused_infer = bool(flag)
+    _fused_infer.set(flag)
 
 
 def get_fused_inference():
-    return _fused_infer
+    return _fused_infer.value
 
 
 def nodes_attention_infer(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b):
@@ -316,20 +336,10 @@ def nodes_attention_infer(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w, A_out_
     return _attn_forward(_f32c(x.detach()), _f32c(edge_attr.detach()), plan, H, weights, save=False)[0]
 
 
-def infer_route(x, edge_attr, params):
-    """True when a scalar-attention node layer takes nodes_attention_infer: the route is on, no backward can follow
-    (grad mode off, or nothing involved requires grad) and no debug recording wants the saved buffer."""
-    if not _fused_infer or debug.recording():
-        return False
-    if not torch.is_grad_enabled():
-        return True
-    return not any(t is not None and t.requires_grad for t in (x, edge_attr, *params))
-
-
 # ----------------------------------------------------------------------------------------
 # shell-indexed edge features: edge_attr[e] = table[index[e]]
 # ----------------------------------------------------------------------------------------
-_indexed_edge_attr = os.environ.get("CGAT_INDEXED_EDGE_ATTR", "0") == "1"
+_indexed_edge_attr = _Switch("CGAT_INDEXED_EDGE_ATTR", False)
 
 
 def set_indexed_edge_attr(flag):
@@ -337,12 +347,11 @@ def set_indexed_edge_attr(flag):
     where that is exact: every Edge layer is the shipped no_hyper form and batch.edge_attr holds integer shell ids.  The
     edge update then runs on the table's rows, and scalar-attention node layers without grad take
     nodes_attention_infer_indexed.  Off: the dense edge features of every earlier release, bit for bit."""
-    global _indexed_edge_attr
-    _indexed_edge_attr = bool(flag)
+    _indexed_edge_attr.set(flag)
 
 
 def get_indexed_edge_attr():
-    return _indexed_edge_attr
+    return _indexed_edge_attr.value
 
 
 _index_checked = {}
@@ -406,24 +415,14 @@ class IndexedEdgeAttr:
         return self._dense
 
 
+def _attn_indexed_ok(entry, plan_c, C_, Ce, H, Hd, R):
+    p = _lib.AttnParams(int(C_), int(Ce), int(H), int(Hd), *([None] * 8))
+    return bool(entry(C.byref(plan_c), C.byref(p), int(R)))
+
+
 def infer_indexed_ok(plan_c, C_, Ce, H, Hd, R):
     """cgat_nodes_attention_infer_indexed_ok for a layer of these dims (host only; plan_c: the C struct of a plan)."""
-    p = _lib.AttnParams(int(C_), int(Ce), int(H), int(Hd), *([None] * 8))
-    return bool(lib.cgat_nodes_attention_infer_indexed_ok(C.byref(plan_c), C.byref(p), int(R)))
-
-
-def indexed_route(x, edge_attr, plan, H, params):
-    """True when a scalar-attention node layer given an IndexedEdgeAttr takes nodes_attention_infer_indexed: infer_route
-    holds (no backward can follow, no debug recording) and the library takes the shape in the current modes."""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
-        return False
-    if not infer_route(x, edge_attr.table, params):
-        return False
-    A_in_w, A_out_w = params[0], params[2]
-    HHd = A_in_w.shape[0]
-    if HHd % H or A_out_w.numel() != HHd:                 # vector attention
-        return False
-    return infer_indexed_ok(plan.c, x.shape[1], edge_attr.table.shape[1], H, HHd // H, edge_attr.table.shape[0])
+    return _attn_indexed_ok(lib.cgat_nodes_attention_infer_indexed_ok, plan_c, C_, Ce, H, Hd, R)
 
 
 def nodes_attention_infer_indexed(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w, A_out_b, M_in_w, M_in_b, M_out_w, M_out_b):
@@ -437,8 +436,7 @@ def nodes_attention_infer_indexed(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w
     _require_gpu(x, *weights)
     x, table, index = _f32c(x.detach()), _f32c(table.detach()), index.contiguous()
     ws_ = [_f32c(w.detach()) for w in weights]
-    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
-        raise ValueError("nodes_attention_infer_indexed handles scalar attention (MH_A output_dim == 1)")
+    _require_scalar_attention("nodes_attention_infer_indexed", H, weights)
     N, E, R = plan.N, plan.E, int(table.shape[0])
     if x.shape[0] != N or index.shape[0] != E:
         raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, index {tuple(index.shape)}")
@@ -453,7 +451,7 @@ def nodes_attention_infer_indexed(x, edge_attr, plan, H, A_in_w, A_in_b, A_out_w
     return aggr
 
 
-_indexed_edge_training = os.environ.get("CGAT_INDEXED_EDGE_TRAIN", "0") == "1"
+_indexed_edge_training = _Switch("CGAT_INDEXED_EDGE_TRAIN", False)
 
 
 def set_indexed_edge_training(flag):
@@ -462,43 +460,42 @@ def set_indexed_edge_training(flag):
     [E, Ce] edge features, no stored pre-activations, grad table and grad W_e from a per-class sum -- where the library
     takes the shape (train_indexed_ok).  It matters only where an IndexedEdgeAttr reaches the layer: through CGAtNet that
     needs set_indexed_edge_attr(True) too.  Off: such a layer densifies and runs the dense training launches, bit for bit."""
-    global _indexed_edge_training
-    _indexed_edge_training = bool(flag)
+    _indexed_edge_training.set(flag)
 
 
 def get_indexed_edge_training():
-    return _indexed_edge_training
+    return _indexed_edge_training.value
 
 
 def train_indexed_ok(plan_c, C_, Ce, H, Hd, R):
     """cgat_nodes_attention_train_indexed_ok for a layer of these dims in the current arithmetic and edge-storage modes
     (host only; plan_c: the C struct of a plan)."""
-    p = _lib.AttnParams(int(C_), int(Ce), int(H), int(Hd), *([None] * 8))
-    return bool(lib.cgat_nodes_attention_train_indexed_ok(C.byref(plan_c), C.byref(p), int(R)))
+    return _attn_indexed_ok(lib.cgat_nodes_attention_train_indexed_ok, plan_c, C_, Ce, H, Hd, R)
 
 
-def train_indexed_route(x, edge_attr, plan, H, params):
-    """True when a scalar-attention node layer given an IndexedEdgeAttr takes NodesAttentionIndexedFn: the switch is on, a
-    backward can follow (grad mode on and something involved requires grad), and the library takes the shape in the
-    current modes.  A debug recording does not leave this route (debug.note_attention_indexed)."""
-    if not _indexed_edge_training or not torch.is_grad_enabled():
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
-        return False
-    table, index = edge_attr.table, edge_attr.index
-    # (what _attn_forward_indexed would refuse densifies instead, like every other ineligible call; a non-contiguous index
-    # would be copied per call and never find its class plan again)
-    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and
-            torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int64 and index.dim() == 1 and
-            index.is_contiguous() and index.shape[0] == plan.E and x.shape[0] == plan.N):
-        return False
-    if not any(t is not None and t.requires_grad for t in (x, table, *params)):
-        return False
-    A_in_w, A_out_w = params[0], params[2]
-    HHd = A_in_w.shape[0]
-    if HHd % H or A_out_w.numel() != HHd:                 # vector attention
-        return False
-    return train_indexed_ok(plan.c, x.shape[1], edge_attr.table.shape[1], H, HHd // H, edge_attr.table.shape[0])
+def _indexed_operands_error(x, table, index, N, E):
+    """What the indexed autograd functions demand of x, table and index for a plan of N nodes and E edges: None, or the
+    exception that names the first operand that fails.  The layers' route facts read it too: what these functions would
+    refuse densifies instead, like every other ineligible call."""
+    if not (torch.is_tensor(x) and torch.is_tensor(table) and torch.is_tensor(index)):
+        return TypeError("indexed edge features: x, table and index must be tensors")
+    if not (x.is_cuda and table.is_cuda and index.is_cuda):
+        return RuntimeError(_NO_CPU)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        return TypeError(f"indexed edge features: x must be float32 [N, C], got {x.dtype} {tuple(x.shape)}")
+    if table.dtype != torch.float32 or table.dim() != 2:
+        return TypeError(f"indexed edge features: table must be float32 [R, Ce], got {table.dtype} {tuple(table.shape)}")
+    if index.dtype != torch.int64 or index.dim() != 1:
+        return TypeError(f"indexed edge features: index must be int64 [E], got {index.dtype} {tuple(index.shape)}")
+    if x.shape[0] != N or index.shape[0] != E:
+        return ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, index {tuple(index.shape)}")
+    if not index.is_contiguous():                         # (a copy per call would never find its class plan again)
+        return ValueError("indexed edge features: index must be contiguous")
+    return None
+
+
+def _indexed_operands_ok(x, table, index, N, E):
+    return _indexed_operands_error(x, table, index, N, E) is None
 
 
 def _class_plan(index, plan, R):
@@ -532,21 +529,14 @@ def _class_plan(index, plan, R):
 def _attn_forward_indexed(x, table, index, plan, H, weights):
     """cgat_nodes_attention_forward_indexed behind NodesAttentionIndexedFn and NodeLayerIndexedFn.  Everything is checked
     before the first launch.  Returns (aggr, saved, the prepared operands x, table, index, weights, the class plan)."""
-    if not (torch.is_tensor(table) and torch.is_tensor(index)):
-        raise TypeError("NodesAttentionIndexedFn(x, table, index, ...) takes tensors")
-    _require_gpu(x, table, index, *weights)
-    if table.dtype != torch.float32 or table.dim() != 2:
-        raise TypeError(f"indexed attention: table must be float32 [R, Ce], got {table.dtype} {tuple(table.shape)}")
-    if index.dtype != torch.int64 or index.dim() != 1:
-        raise TypeError(f"indexed attention: index must be int64 [E], got {index.dtype} {tuple(index.shape)}")
-    A_in_w, A_out_w, M_in_w = weights[0], weights[2], weights[4]
-    if A_out_w.numel() != H * (A_in_w.shape[0] // H):
-        raise ValueError("NodesAttentionIndexedFn handles scalar attention (MH_A output_dim == 1)")
-    N, E, R = plan.N, plan.E, int(table.shape[0])
-    if x.shape[0] != N or index.shape[0] != E:
-        raise ValueError(f"plan is for N={N}, E={E}; got x {tuple(x.shape)}, index {tuple(index.shape)}")
-    if not index.is_contiguous():                         # (a copy per call would never find its class plan again)
-        raise ValueError("indexed attention: index must be contiguous")
+    N, E = plan.N, plan.E
+    err = _indexed_operands_error(x, table, index, N, E)
+    if err is not None:
+        raise err
+    _require_gpu(*weights)
+    A_in_w, M_in_w = weights[0], weights[4]
+    _require_scalar_attention("NodesAttentionIndexedFn", H, weights)
+    R = int(table.shape[0])
     x, table = _f32c(x.detach()), _f32c(table.detach())
     ws_ = [_f32c(w.detach()) for w in weights]
     p, Hd = _attn_params(x, table, H, ws_)
@@ -664,7 +654,7 @@ class EdgeHiddenFn(torch.autograd.Function):
 
 
 # ---- the same first layer on shell-indexed edge features (cgat_edge_hidden_forward_indexed / _backward_indexed) ----
-_indexed_vector_attention = os.environ.get("CGAT_INDEXED_VECTOR_ATTN", "0") == "1"
+_indexed_vector_attention = _Switch("CGAT_INDEXED_VECTOR_ATTN", False)
 
 
 def set_indexed_vector_attention(flag):
@@ -675,12 +665,11 @@ def set_indexed_vector_attention(flag):
     library takes the shape (edge_hidden_indexed_ok).  `hidden` [E, 2 H Hd] and everything behind it are unchanged.  It
     matters only where an IndexedEdgeAttr reaches the layer: through CGAtNet that needs set_indexed_edge_attr(True) too.
     Off: such a layer densifies and runs the dense launches, bit for bit."""
-    global _indexed_vector_attention
-    _indexed_vector_attention = bool(flag)
+    _indexed_vector_attention.set(flag)
 
 
 def get_indexed_vector_attention():
-    return _indexed_vector_attention
+    return _indexed_vector_attention.value
 
 
 def edge_hidden_indexed_ok(plan_c, C_, Ce, W2, R):
@@ -689,34 +678,13 @@ def edge_hidden_indexed_ok(plan_c, C_, Ce, W2, R):
     return bool(lib.cgat_edge_hidden_indexed_ok(C.byref(plan_c), int(C_), int(Ce), int(W2), int(R)))
 
 
-def _indexed_operands_ok(x, table, index, plan):
-    """What the indexed autograd functions demand of x, table and index (train_indexed_route's conditions)."""
-    return (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and
-            torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and
-            torch.is_tensor(index) and index.is_cuda and index.dtype == torch.int64 and index.dim() == 1 and
-            index.is_contiguous() and index.shape[0] == plan.E and x.shape[0] == plan.N)
-
-
-def vector_indexed_route(x, edge_attr, plan, W2):
-    """True when a vector-attention node layer given an IndexedEdgeAttr takes the indexed first layer: the switch is on,
-    the operands are as train_indexed_route demands (a contiguous index of plan.E entries among them) and the library
-    takes the shape under the current edge storage.  With grad and without; a debug recording stays on this route
-    (debug.note_sorted_hidden needs `hidden` alone)."""
-    if not _indexed_vector_attention:
-        return False
-    table, index = edge_attr.table, edge_attr.index
-    if not _indexed_operands_ok(x, table, index, plan):
-        return False
-    return edge_hidden_indexed_ok(plan.c, x.shape[1], table.shape[1], W2, table.shape[0])
-
-
 def _edge_hidden_forward_indexed(who, x, table, index, plan, w_in, b_in):
     """cgat_edge_hidden_forward_indexed behind EdgeHiddenIndexedFn and EdgeHiddenHeadsIndexedFn.  Everything is checked
     before the first launch.  Returns the prepared operands, hidden, hmax and the class plan of the backward."""
-    _require_gpu(x, table, index, w_in, b_in)
-    if not _indexed_operands_ok(x, table, index, plan):
-        raise ValueError(f"{who}: x float32 [N, C], table float32 [R, Ce] and a contiguous int64 index [E] matching the "
-                         "plan are required")
+    err = _indexed_operands_error(x, table, index, plan.N, plan.E)
+    if err is not None:
+        raise err
+    _require_gpu(w_in, b_in)
     x, table, w_in, b_in = _f32c(x), _f32c(table), _f32c(w_in.detach()), _f32c(b_in.detach())
     N, E, R = plan.N, plan.E, int(table.shape[0])
     Cn, Ce, W2 = x.shape[1], table.shape[1], w_in.shape[0]
@@ -808,23 +776,22 @@ def _hnet_struct(cls, W, n_fc, n_hyper, flat, damping):
 # kernel alone on the chip.  "bf16x6" (four six-pass dT launches, two to four times as long as the kernels they would
 # run beside) gains nothing: 33.13 / 33.12 ms with, 33.04 / 33.08 without.
 _side_streams = {}
-_overlap_wgrad = {"0": False, "1": True}.get(os.environ.get("CGAT_OVERLAP_WGRAD", ""), None)
+_overlap_wgrad = _Switch("CGAT_OVERLAP_WGRAD", None)
 
 
 def set_overlap_wgrad(flag):
-    global _overlap_wgrad
-    _overlap_wgrad = None if flag is None else bool(flag)
+    _overlap_wgrad.set(flag)
 
 
 def get_overlap_wgrad():
     """The raw setting (None = decided per arithmetic mode): what a caller that changes it temporarily must restore."""
-    return _overlap_wgrad
+    return _overlap_wgrad.value
 
 
 def overlap_enabled():
-    if _overlap_wgrad is None:
+    if _overlap_wgrad.value is None:
         return get_bilinear_mode() == "f16x3"
-    return _overlap_wgrad
+    return _overlap_wgrad.value
 
 
 def side_stream(device, create=True):
@@ -938,6 +905,25 @@ class HNetFn(torch.autograd.Function):
         return (g_h0, g_v, g_d, None, None, *grads)
 
 
+def _layer_backward(ctx, h0, aggr, saved_h, d, flat, g_y, attn_backward, overlap):
+    """The backward schedule of a whole-layer node (NodeLayerFn, NodeLayerIndexedFn): the hypernetwork backward first --
+    overlap: cgat_hnet_backward_overlapped, its weight-gradient contractions left on the side stream --, then
+    `attn_backward(g_aggr, raw main stream)` on the main stream, then the join.  Returns (g_h0, g_d, the hypernetwork's
+    parameter grads, what attn_backward returned)."""
+    dev = aggr.device
+    main = torch.cuda.current_stream(dev)
+    side = (main, side_stream(dev)) if overlap else None
+    # the hypernetwork's workspace is taken and its call issued first, then the attention backward takes its workspace
+    # from the same cache (main-stream order; what the side stream reads is its own allocation)
+    g_h0, g_aggr, g_d, g_flat, side_ws = _hnet_backward(h0, aggr, saved_h, d, flat, ctx.n_fc, ctx.n_hyper, g_y, side=side)
+    g_attn = attn_backward(g_aggr, main.cuda_stream)
+    if overlap:
+        with torch.cuda.device(dev):
+            main.wait_stream(side[1])    # every gradient is complete, in stream order, when this node returns
+    del side_ws                          # (held until here: the side stream was using it)
+    return g_h0, g_d, g_flat, g_attn
+
+
 class NodeLayerFn(torch.autograd.Function):
     """One whole GATConvNodes layer: aggr = attention(x, edge_attr) (NodesAttentionFn), y = HyperFC(h0)(aggr) (HNetFn) --
     reference CGAT.py:307-340 -- as ONE autograd node, so that its backward can run the hypernetwork's four
@@ -963,18 +949,9 @@ class NodeLayerFn(torch.autograd.Function):
         x, edge_attr, h0, aggr, saved_a, saved_h, *rest = ctx.saved_tensors
         d = rest.pop(0) if ctx.has_d else None
         attn_w, flat = rest[:8], rest[8:]
-        dev = x.device
-        main = torch.cuda.current_stream(dev)
-        s2 = side_stream(dev)
-        # the hypernetwork's workspace is taken and its overlapped call issued first, then the attention backward takes
-        # its workspace from the same cache (main-stream order; what the side stream reads is its own allocation)
-        g_h0, g_aggr, g_d, g_flat, side_ws = _hnet_backward(h0, aggr, saved_h, d, flat, ctx.n_fc, ctx.n_hyper, g_y,
-                                                            side=(main, s2))
-        g_x, g_e, g_attn = _attn_backward(x, edge_attr, ctx.plan, ctx.H, attn_w, saved_a, g_aggr, ctx.storage,
-                                          main.cuda_stream)
-        with torch.cuda.device(dev):
-            main.wait_stream(s2)     # every gradient is complete, in stream order, when this node returns
-        del side_ws                  # (held until here: the side stream was using it)
+        attn = lambda g_aggr, stream: _attn_backward(x, edge_attr, ctx.plan, ctx.H, attn_w, saved_a, g_aggr, ctx.storage,
+                                                     stream)
+        g_h0, g_d, g_flat, (g_x, g_e, g_attn) = _layer_backward(ctx, h0, aggr, saved_h, d, flat, g_y, attn, overlap=True)
         return (g_x, g_e, g_h0, None, None, g_d, None, None, *g_attn, *g_flat)
 
 
@@ -1010,23 +987,12 @@ class NodeLayerIndexedFn(torch.autograd.Function):
         x, table, index, h0, aggr, saved_a, saved_h, *rest = ctx.saved_tensors
         d = rest.pop(0) if ctx.has_d else None
         attn_w, flat = rest[:8], rest[8:]
-        dev = x.device
-        main = torch.cuda.current_stream(dev)
-        if not _overlapped_hnet_keeps_bits(aggr):
-            # the overlapped hypernetwork backward caps the grid of its weight-gradient launches; where that cap moves the
-            # row split of their sums (the six-pass plane forms, other widths) the serial call runs: HNetFn's bits
-            g_h0, g_aggr, g_d, g_flat, _ = _hnet_backward(h0, aggr, saved_h, d, flat, ctx.n_fc, ctx.n_hyper, g_y)
-            g_x, g_t, g_attn = _attn_backward_indexed(x, table, index, ctx.cls, ctx.plan, ctx.H, attn_w, saved_a, g_aggr,
-                                                      main.cuda_stream)
-            return (g_x, g_t, None, g_h0, None, None, g_d, None, None, *g_attn, *g_flat)
-        s2 = side_stream(dev)
-        g_h0, g_aggr, g_d, g_flat, side_ws = _hnet_backward(h0, aggr, saved_h, d, flat, ctx.n_fc, ctx.n_hyper, g_y,
-                                                            side=(main, s2))
-        g_x, g_t, g_attn = _attn_backward_indexed(x, table, index, ctx.cls, ctx.plan, ctx.H, attn_w, saved_a, g_aggr,
-                                                  main.cuda_stream)
-        with torch.cuda.device(dev):
-            main.wait_stream(s2)     # every gradient is complete, in stream order, when this node returns
-        del side_ws                  # (held until here: the side stream was using it)
+        attn = lambda g_aggr, stream: _attn_backward_indexed(x, table, index, ctx.cls, ctx.plan, ctx.H, attn_w, saved_a,
+                                                             g_aggr, stream)
+        # the overlapped hypernetwork backward caps the grid of its weight-gradient launches; where that cap moves the row
+        # split of their sums (the six-pass plane forms, other widths) the serial call runs: HNetFn's bits
+        g_h0, g_d, g_flat, (g_x, g_t, g_attn) = _layer_backward(ctx, h0, aggr, saved_h, d, flat, g_y, attn,
+                                                                overlap=_overlapped_hnet_keeps_bits(aggr))
         return (g_x, g_t, None, g_h0, None, None, g_d, None, None, *g_attn, *g_flat)
 
 
@@ -1588,22 +1554,21 @@ def attention_pool(a, m, index_plan, index, mult=None, eps=1e-16):
     return segment_sum(w * m2, index_plan, index)
 
 
-_fused_edge_combine = os.environ.get("CGAT_FUSED_EDGE_COMBINE", "1") != "0"
+_fused_edge_combine = _Switch("CGAT_FUSED_EDGE_COMBINE", True)
 
 
 def set_fused_edge_combine(flag):
     """The one-kernel head combination of GATConvEdges(no_hyper=False) (default on; env CGAT_FUSED_EDGE_COMBINE=0 starts
     it off): EdgeHeadCombineFn instead of the exp / sum / division / dropout / product / mean / index_copy sequence of
     torch ops on [E, H, Co] tensors.  Off: that sequence runs (the A/B reference)."""
-    global _fused_edge_combine
-    _fused_edge_combine = bool(flag)
+    _fused_edge_combine.set(flag)
 
 
 def get_fused_edge_combine():
-    return _fused_edge_combine
+    return _fused_edge_combine.value
 
 
-_fused_attn_dropout = os.environ.get("CGAT_FUSED_ATTN_DROPOUT", "1") != "0"
+_fused_attn_dropout = _Switch("CGAT_FUSED_ATTN_DROPOUT", True)
 
 
 def set_fused_attention_dropout(flag):
@@ -1611,12 +1576,11 @@ def set_fused_attention_dropout(flag):
     kernels (default on; env CGAT_FUSED_ATTN_DROPOUT=0 starts it off).  Off: the MessagePassing-style route runs --
     concatenated [E, 2C+Ce] rows, generic networks, segment softmax, mask, product, segment sum (the A/B reference).
     The mask is drawn the same way on both routes: one seed gives one mask per edge."""
-    global _fused_attn_dropout
-    _fused_attn_dropout = bool(flag)
+    _fused_attn_dropout.set(flag)
 
 
 def get_fused_attention_dropout():
-    return _fused_attn_dropout
+    return _fused_attn_dropout.value
 
 
 class EdgeHeadCombineFn(torch.autograd.Function):
@@ -1678,7 +1642,7 @@ class EdgeHeadCombineFn(torch.autograd.Function):
 def edge_combine_route(sa, sm):
     """True when GATConvEdges hands its head combination to EdgeHeadCombineFn: the switch is on, the tensors are on the
     GPU and the shape is one the kernels take.  Everything else keeps the sequence of torch ops."""
-    return _fused_edge_combine and sa.is_cuda and sm.is_cuda and EdgeHeadCombineFn.supported(sa, sm)
+    return _fused_edge_combine.value and sa.is_cuda and sm.is_cuda and EdgeHeadCombineFn.supported(sa, sm)
 
 
 class GatherRowsFn(torch.autograd.Function):

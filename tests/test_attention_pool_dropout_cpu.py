@@ -65,7 +65,7 @@ def test_no_cpu_fallback():
         ops.AttentionPoolFn.apply(torch.zeros(R, 3), None, torch.zeros(R, 48), rowptr, None, 1e-16, torch.ones(R, 3), None)
     import cgat_amd as P
     layer = P.GATConvNodes(16, 16, 16, 3, concat=True, dropout=0.3)           # CPU tensors keep the MessagePassing route,
-    assert not layer._attn_dropout_route(torch.zeros(4, 16), torch.zeros(8, 16), type("Plan", (), {"E": 8})())
+    assert layer.route(torch.zeros(4, 16), torch.zeros(2, 8, dtype=torch.long), torch.zeros(8, 16)).kind == "message"
 
 
 def test_switch_round_trip_and_reexport():

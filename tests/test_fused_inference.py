@@ -144,9 +144,13 @@ def test_route_by_grad_mode():
     layer = _layer(False)
     with torch.no_grad():
         _, t = _tags(lambda: layer(x, ei, e, x0))
+        route = layer.route(x, ei, e)
     assert t["edge_logits"] > 0 and t["edge_msg_wsum"] > 0 and t["edge_z"] == 0 and t["seg_wsum"] == 0, t
+    assert route.kind in ("scalar", "layer_fused") and route.no_grad and not route.indexed, route
     _, t = _tags(lambda: layer(x.clone().requires_grad_(True), ei, e, x0))
     assert t["edge_logits"] == 0 and t["edge_msg_wsum"] == 0 and t["edge_z"] > 0 and t["seg_wsum"] > 0, t
+    route = layer.route(x.clone().requires_grad_(True), ei, e)
+    assert route.kind in ("scalar", "layer_fused") and not route.no_grad and not route.indexed, route
 
 
 def _check_layer_bits(kind, mode, storage="f32", fused=True):
@@ -158,6 +162,7 @@ def _check_layer_bits(kind, mode, storage="f32", fused=True):
             want = layer(x.clone().requires_grad_(True), ei, e.clone().requires_grad_(True), x0).detach()
             with torch.no_grad():
                 got, t = _tags(lambda: layer(x, ei, e, x0))
+                assert layer.route(x, ei, e).no_grad      # (fused or not: the library's choice behind the no-grad entry)
             assert (t["edge_msg_wsum"] > 0) == fused and t["edge_z"] == (0 if fused else t["edge_z"]), t
             assert torch.equal(got, want), (kind, mode, storage, first, float((got - want).abs().max()))
 

@@ -147,7 +147,9 @@ def _check_layer_bits(kind, mode, storage="f32", H=5):
             want = layer(x.clone().requires_grad_(True), ei, e.clone().requires_grad_(True), x0).detach()
             with torch.no_grad():
                 got, t = _tags(lambda: layer(x, ei, e, x0))
+                route = layer.route(x, ei, e)
             assert t["edge_logits"] > 0 and t["edge_msg_wsum"] > 0 and t["edge_z"] == 0 and t["seg_wsum"] == 0, t
+            assert route.kind in ("scalar", "layer_fused") and route.no_grad, route
             assert torch.equal(got, want), (kind, mode, storage, first, float((got - want).abs().max()))
 
 
@@ -194,6 +196,7 @@ def test_h5_no_grad_peak_below_quarter_of_opt_out():
                 base = torch.cuda.memory_allocated()
                 _, t = _tags(lambda: layer(x, ei, e, x0))
                 rise[on] = torch.cuda.max_memory_allocated() - base
+                assert layer.route(x, ei, e).no_grad == on
             assert (t["edge_msg_wsum"] > 0) == on, t
             torch.cuda.empty_cache()
     finally:

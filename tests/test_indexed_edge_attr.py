@@ -150,8 +150,12 @@ def test_layer_no_grad_takes_indexed_route(first):
     with torch.no_grad():
         got, t = _tags(lambda: pm(x, ei, P.IndexedEdgeAttr(table, index), x0))
         assert t["edge_idx_logits"] > 0 and t["edge_idx_wsum"] > 0 and all(t[k] == 0 for k in DENSE_TAGS), t
+        route = pm.route(x, ei, P.IndexedEdgeAttr(table, index))
+        assert route.indexed and route.no_grad and route.kind in ("scalar", "layer_fused"), route
         dense, t = _tags(lambda: pm(x, ei, table[index], x0))
         assert t["edge_idx_logits"] == 0 and t["edge_idx_wsum"] == 0 and t["edge_msg_wsum"] + t["seg_wsum"] > 0, t
+        route = pm.route(x, ei, table[index])
+        assert not route.indexed and route.no_grad and route.kind in ("scalar", "layer_fused"), route
     _check_both(f"layer first={first}", got, dense, *refs())
 
 
@@ -169,6 +173,8 @@ def test_layer_with_grad_densifies_same_bits(first):
         ea = P.IndexedEdgeAttr(tb, index) if indexed else ops.small_embedding(index, tb)
         y, t = _tags(lambda: pm(x, ei, ea, x0))
         assert t["seg_wsum"] > 0 and t["edge_idx_logits"] == 0 and t["edge_idx_wsum"] == 0, t     # the training forward
+        route = pm.route(x, ei, ea)
+        assert not route.indexed and not route.no_grad and route.kind in ("scalar", "layer_fused"), route
         (gt,) = torch.autograd.grad((y * cot).sum(), [tb])
         res.append((y.detach(), gt))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
@@ -180,7 +186,9 @@ def test_layer_recording_keeps_dense_route():
     _, pm, x, ei, table, index, x0 = _layer_case(False)
     with torch.no_grad(), P.debug.record_masks(pm):
         _, t = _tags(lambda: pm(x, ei, P.IndexedEdgeAttr(table, index), x0))
+        route = pm.route(x, ei, P.IndexedEdgeAttr(table, index))
     assert t["edge_idx_logits"] == 0 and t["edge_idx_wsum"] == 0 and t["seg_wsum"] > 0, t
+    assert not route.indexed and not route.no_grad and route.kind in ("scalar", "layer_fused"), route
 
 
 def test_edges_layer_accepts_indexed():
@@ -196,6 +204,7 @@ def test_edges_layer_accepts_indexed():
     with torch.no_grad():
         out = shipped(x, ei, ea, ea.dense())
         assert isinstance(out, P.IndexedEdgeAttr) and out.index is ea.index
+        assert shipped.route(x, ei, ea) == ("rowwise", True, False) and hyper.route(x, ei, ea) == ("fast", False, False)
         assert torch.equal(out.table, shipped.Pooling_NN(table))
         assert _maxerr(out.dense(), shipped(x, ei, ea.dense(), ea.dense())) <= 1e-5 * float(out.table.abs().max())
         got = hyper(x, ei, ea, ea.dense())
@@ -394,6 +403,7 @@ def test_indexed_deterministic_and_captured():
     with torch.no_grad():
         y1, t = _tags(lambda: layer(x, ei, ea, x0))
         y2 = layer(x, ei, ea, x0)
+        assert layer.route(x, ei, ea).indexed and layer.route(x, ei, ea).no_grad
     assert t["edge_idx_wsum"] > 0, t
     assert torch.equal(y1, y2)
     _, pm, b, roost = _net_pair(60, **KW3)

@@ -44,13 +44,16 @@ def _tags(fn):
     return out, t
 
 
-def _assert_indexed_tags(t):
+def _assert_indexed_tags(t, route=None):
+    """`route`: layer.route(...) of the call the tags were counted over (_step.route); it names the same route."""
     assert all(t[k] > 0 for k in NEW_TAGS + KEPT_TAGS), t
     assert all(t[k] == 0 for k in GONE_TAGS), t
+    assert route is None or (route.indexed and not route.no_grad and route.kind in ("scalar", "layer_fused")), route
 
 
-def _assert_dense_tags(t):
+def _assert_dense_tags(t, route=None):
     assert all(t[k] == 0 for k in NEW_TAGS + ("edge_idx_logits", "edge_idx_wsum")), t
+    assert route is None or not route.indexed, route
 
 
 class _train:
@@ -99,6 +102,7 @@ def _step(pm, x, ei, table, index, cot, indexed=True, x0=None):
     from cgat_amd import ops
     xg, tg = x.clone().requires_grad_(True), table.clone().requires_grad_(True)
     ea = P.IndexedEdgeAttr(tg, index) if indexed else ops.small_embedding(index, tg)
+    _step.route = pm.route(xg, ei, ea)                # (what the call below takes: asserted beside its launch tags)
     y = pm(xg, ei, ea, x0)
     names = [n for n, _ in pm.named_parameters()]
     gs = torch.autograd.grad((y * cot).sum(), [xg, tg] + list(pm.parameters()), allow_unused=True)
@@ -130,7 +134,7 @@ def test_layer_gradients_vs_oracle(kind, H, R, C_, mode):
         cot = torch.randn(N, C_, generator=torch.Generator().manual_seed(9)).to(DEV)
         (y, g), t = _tags(lambda: _step(pm, x.to(DEV), ei.to(DEV), table.to(DEV), index.to(DEV), cot))
     print(f"[indexed-train] layer {kind} H{H} R{R} C{C_} {mode}: worst err/|ref| {worst:.3e}; tags {t}")
-    _assert_indexed_tags(t)
+    _assert_indexed_tags(t, _step.route)
     gt = g["table"]
     used = torch.zeros(R, dtype=torch.bool)
     used[index.unique()] = True
@@ -157,9 +161,13 @@ def test_forward_bits_equal_no_grad(kind, first):
     with _train(True):
         y, t = _tags(lambda: pm(x, ei, P.IndexedEdgeAttr(table.clone().requires_grad_(True), index), x0))
         assert y.requires_grad and t["edge_idx_logits"] > 0 and t["edge_idx_wsum"] > 0 and t["seg_wsum"] == 0, t
+        route = pm.route(x, ei, P.IndexedEdgeAttr(table.clone().requires_grad_(True), index))
+        assert route.indexed and not route.no_grad and route.kind in ("scalar", "layer_fused"), route
         with torch.no_grad():
             y0, t0 = _tags(lambda: pm(x, ei, P.IndexedEdgeAttr(table, index), x0))
+            route = pm.route(x, ei, P.IndexedEdgeAttr(table, index))
         assert t0["edge_idx_wsum"] > 0, t0
+        assert route.indexed and route.no_grad, route
     assert torch.equal(y.detach(), y0)
 
 
@@ -185,7 +193,7 @@ def test_ratio_rule_vs_dense_training(kind, H):
         rec = P.debug.record_masks(pm)
         with _train(indexed), rec as masks:
             (_, g), t = _tags(lambda: _step(pm, x, ei, table, index, cot, indexed=indexed))
-        (_assert_indexed_tags if indexed else _assert_dense_tags)(t)
+        (_assert_indexed_tags if indexed else _assert_dense_tags)(t, _step.route)
         xr, tr = x_cpu.double().requires_grad_(True), table_cpu.double().requires_grad_(True)
         with O.forced_masks(om64, masks):
             y = om64(xr, ei_cpu, torch.nn.functional.embedding(index_cpu, tr), None)
@@ -246,7 +254,7 @@ def test_deterministic_on_ragged():
     with _train(True):
         (y1, g1), t = _tags(lambda: _step(pm, x, ei, table, index, cot))
         y2, g2 = _step(pm, x, ei, table, index, cot)
-    _assert_indexed_tags(t)
+    _assert_indexed_tags(t, _step.route)
     assert torch.equal(y1, y2)
     for k in GRAD_NAMES:
         assert torch.equal(g1[k], g2[k]), k
@@ -263,7 +271,7 @@ def test_two_disjoint_copies_locality():
     with _train(True):
         y1, g1 = _step(pm, x.to(DEV), ei.to(DEV), table.to(DEV), index.to(DEV), cot.to(DEV))
         (y2, g2), t = _tags(lambda: _step(pm, x2.to(DEV), ei2.to(DEV), table.to(DEV), idx2.to(DEV), cot2.to(DEV)))
-    _assert_indexed_tags(t)
+    _assert_indexed_tags(t, _step.route)
     assert torch.equal(y2[:N], y1)
     assert torch.equal(g2["x"][:N], g1["x"])
 
@@ -291,7 +299,7 @@ def test_whole_layer_node_equals_separate_nodes(first):
             for overlap in (True, False):
                 ops.set_overlap_wgrad(overlap)
                 (y, g), t = _tags(lambda: _step(pm, x, ei, table, index, cot, x0=x0))
-                _assert_indexed_tags(t)
+                _assert_indexed_tags(t, _step.route)
                 res.append((y, g))
     finally:
         ops.set_overlap_wgrad(prev)
@@ -376,7 +384,7 @@ def test_ineligible_keeps_dense_training_path(what):
             with _train(on):
                 (y, g), t = _tags(lambda: _step(pm, x, ei, table, index, cot))
             print(f"[indexed-train] ineligible {what} switch {on}: {t}")
-            _assert_dense_tags(t)
+            _assert_dense_tags(t, _step.route)
             # the dense training launches of each route: the per-edge forward, the segment sums, both per-edge products
             assert t["edge_z"] > 0 and t["seg_wsum"] > 0 and t["edge_ge"] > 0 and t["edge_gw"] > 0, t
             if what == "bf16":

@@ -70,8 +70,11 @@ def test_symbols_exported_and_bound():
     lib = C.CDLL(_lib.LIB_PATH)
     for n in NAMES:
         assert hasattr(lib, n) and n in _lib.PROTOTYPES, n
-    for n in ("EdgeHiddenIndexedFn", "EdgeHiddenHeadsIndexedFn", "vector_indexed_route", "edge_hidden_indexed_ok"):
+    for n in ("EdgeHiddenIndexedFn", "EdgeHiddenHeadsIndexedFn", "edge_hidden_indexed_ok"):
         assert hasattr(ops, n), n
+    from cgat_amd import nets                  # (the route predicate: folded into the layer's one route decision)
+    assert callable(nets.nodes_route) and "edge_hidden_indexed_ok" in nets.NodeFacts._fields
+    assert callable(nets.GATConvNodes.route)
 
 
 def test_predicate_table():

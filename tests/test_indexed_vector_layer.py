@@ -39,13 +39,16 @@ def _tags(fn):
     return out, {k: ops.prof_get(k)[0] for k in NEW_TAGS + GONE_TAGS}
 
 
-def _assert_indexed_tags(t, backward=True):
+def _assert_indexed_tags(t, backward=True, route=None):
+    """`route`: layer.route(...) of the call the tags were counted over (_step.route); it names the same route."""
     assert t["edge_idx_hidden"] > 0 and (t["edge_idx_class_sum"] > 0 or not backward), t
     assert all(t[k] == 0 for k in GONE_TAGS), t
+    assert route is None or route == ("vector", True, False), route
 
 
-def _assert_dense_tags(t):
+def _assert_dense_tags(t, route=None):
     assert all(t[k] == 0 for k in NEW_TAGS), t
+    assert route is None or not route.indexed, route
 
 
 class _vec:
@@ -88,6 +91,7 @@ def _step(pm, x, ei, table, index, cot, indexed=True, x0=None):
     from cgat_amd import ops
     xg, tg = x.clone().requires_grad_(True), table.clone().requires_grad_(True)
     ea = P.IndexedEdgeAttr(tg, index) if indexed else ops.small_embedding(index, tg)
+    _step.route = pm.route(xg, ei, ea)                # (what the call below takes: asserted beside its launch tags)
     y = pm(xg, ei, ea, x0)
     names = [n for n, _ in pm.named_parameters()]
     gs = torch.autograd.grad((y * cot).sum(), [xg, tg] + list(pm.parameters()), allow_unused=True)
@@ -128,7 +132,7 @@ def test_layer_vs_oracle(kind, H):
         pm = _vector_layer(H)
         (y, g), t = _tags(lambda: _step(pm, x.to(DEV), ei.to(DEV), table.to(DEV), index.to(DEV), cot.to(DEV)))
     print(f"[indexed-vector] layer {kind} H{H}: worst err/|ref| {worst:.3e}; tags {t}")
-    _assert_indexed_tags(t)
+    _assert_indexed_tags(t, route=_step.route)
     assert len([k for k in g if k not in ("x", "table")]) == 8 and all(v is not None for v in g.values())
     used = torch.zeros(13, dtype=torch.bool)
     used[index.unique()] = True
@@ -167,7 +171,7 @@ def test_switch_off_is_the_parent_route(H):
         parent, t2 = _tags(lambda: _step(pm, x, ei, table, index, cot, indexed=False))
     print(f"[indexed-vector] switch off H{H}: {t}; parent {t2}")
     _assert_dense_tags(t)
-    _assert_dense_tags(t2)
+    _assert_dense_tags(t2, _step.route)
     assert t["edge_z"] > 0 and t["edge_ge"] > 0 and t["edge_gw"] > 0, t
     _assert_same(off, parent)
 
@@ -197,7 +201,7 @@ def test_deterministic_on_ragged():
     with _vec(True):
         a, t = _tags(lambda: _step(pm, x, ei, table, index, cot))
         b = _step(pm, x, ei, table, index, cot)
-    _assert_indexed_tags(t)
+    _assert_indexed_tags(t, route=_step.route)
     _assert_same(a, b)
 
 
@@ -228,7 +232,7 @@ def test_ineligible_keeps_dense_path(what):
                 with _vec(on):
                     r, t = _tags(lambda: _step(pm, x, ei, table, index, cot, x0=x0))
                 print(f"[indexed-vector] ineligible {what} switch {on}: {t}")
-                _assert_dense_tags(t)
+                _assert_dense_tags(t, _step.route)
                 res.append(r)
     finally:
         P.set_max_edges_per_pass(prev)

@@ -91,6 +91,8 @@ def test_route_taken(switch, vector):
         finally:
             ops.prof_enable(False)
         counts[on] = (ops.prof_get("seg_attnpool_drop_fwd")[0], ops.prof_get("seg_attnpool_drop_bwd")[0])
+        route = layer.route(ins["x"], ins["edge_index"], ins["edge_attr"])
+        assert route == (("vector_dropout" if on else "message"), False, False), route
     assert counts[True][0] >= 1 and counts[True][1] >= 1, counts
     assert counts[False] == (0, 0), counts
     # a subclass overriding message() keeps the MessagePassing-style route
@@ -107,6 +109,7 @@ def test_route_taken(switch, vector):
     finally:
         ops.prof_enable(False)
     assert ops.prof_get("seg_attnpool_drop_fwd")[0] == 0
+    assert sub.route(ins["x"], ins["edge_index"], ins["edge_attr"]) == ("message", False, False)
 
 
 def test_chunked_execution_keeps_the_message_passing_route(switch):
@@ -122,9 +125,12 @@ def test_chunked_execution_keeps_the_message_passing_route(switch):
     try:
         y = CALL(layer, ins)
         torch.cuda.synchronize()
+        c = chunked.closed_chunks(ins["edge_index"], ins["x"].shape[0], chunked.max_edges_per_pass())[0]
+        route = layer.route(ins["x"][c.n0:c.n1], c.edge_index, ins["edge_attr"][c.e0:c.e1], inner_pass=True)
     finally:
         ops.prof_enable(False)
         P.set_max_edges_per_pass(was)
+    assert route == ("message", False, False), route
     assert bool(torch.isfinite(y).all())
     assert ops.prof_get("seg_attnpool_drop_fwd")[0] == 0
     assert ops.prof_get("seg_softmax")[0] >= 2                      # one segment softmax per chunk
