@@ -742,6 +742,17 @@ bool bilinear_wgrad_batch_fast(int n_layers, int NA, int NB, int NC, long ldq, l
   return mode_f16_T() && n_layers >= 1 && n_layers <= WGB_MAX && NA >= 1 && NA <= 128 && NB == 128 && NC == 128 &&
          (ldr % 4) == 0;
 }
+// Does the batched kernel of an n_layers batch take these operands?  The one definition bilinear_wgrad_batch_prep (for
+// its layer's pair: n_given = 1), bilinear_wgrad_batch_launch (for all n_layers pairs) and a caller that decides its route
+// before its first launch share: the mode and the dims, q and r of every given layer 16-byte aligned, and at most 8e6
+// rows (the q^T tile is fetched with 32-bit lane offsets: 128 rows of rows_pad floats must stay below 4 GB).
+bool bilinear_wgrad_batch_takes(int n_layers, int n_given, const float* const* q, long ldq, const float* const* r, long ldr,
+                                int nrows, int NA, int NB, int NC) {
+  bool aligned = true;
+  for (int l = 0; l < n_given && l < WGB_MAX; ++l)
+    aligned = aligned && ((((uintptr_t)q[l]) | ((uintptr_t)r[l])) & 15) == 0;
+  return aligned && nrows > 0 && nrows <= 8000000 && bilinear_wgrad_batch_fast(n_layers, NA, NB, NC, ldq, ldr);
+}
 size_t bilinear_wgrad_batch_ws_bytes(int n_layers, int nrows, int NA, int NB, int NC) {
   const size_t single = bilinear_wgrad_ws_bytes(nrows, NA, NB, NC);
   if (NB != 128 || NC != 128 || NA > 128 || NA < 1 || n_layers > WGB_MAX || n_layers < 1 || nrows <= 0) return single;
@@ -798,8 +809,7 @@ static int wgrad_f16_prepare(const WgradBatchWs& w, int l0, int n, const WgradPr
 int bilinear_wgrad_batch_prep(int slot, int n_layers, const float* p, long ldp, const float* q, long ldq, const float* r,
                               long ldr, int nrows, int NA, int NB, int NC, void* ws, size_t ws_bytes,
                               hipStream_t stream) {
-  if (slot < 0 || slot >= n_layers || ((((uintptr_t)q) | ((uintptr_t)r)) & 15) != 0 || nrows <= 0 || nrows > 8000000 ||
-      !bilinear_wgrad_batch_fast(n_layers, NA, NB, NC, ldq, ldr))
+  if (slot < 0 || slot >= n_layers || !bilinear_wgrad_batch_takes(n_layers, 1, &q, ldq, &r, ldr, nrows, NA, NB, NC))
     return CGAT_ERR_UNSUPPORTED;
   if (mode_f16c())
     return wgradc_prep(slot, 1, n_layers, &p, ldp, &q, ldq, &r, ldr, nrows, NA, ws, ws_bytes, stream);
@@ -818,11 +828,7 @@ int bilinear_wgrad_batch_launch(int n_layers, const float* const* p, long ldp, c
                                 const float* const* r, long ldr, float* const* out, int nrows, int NA, int NB, int NC,
                                 void* ws, size_t ws_bytes, hipStream_t stream, int max_wgs, bool prepared) {
   if (n_layers <= 0) return CGAT_OK;
-  bool aligned = true;
-  for (int l = 0; l < n_layers && l < WGB_MAX; ++l)
-    aligned = aligned && ((((uintptr_t)q[l]) | ((uintptr_t)r[l])) & 15) == 0;
-  // (the q^T tile is fetched with 32-bit lane offsets: 128 rows of rows_pad floats must stay below 4 GB)
-  if (!aligned || nrows <= 0 || nrows > 8000000 || !bilinear_wgrad_batch_fast(n_layers, NA, NB, NC, ldq, ldr)) {
+  if (!bilinear_wgrad_batch_takes(n_layers, n_layers, q, ldq, r, ldr, nrows, NA, NB, NC)) {
     CGAT_CHECK_ARG(!prepared, "bilinear_wgrad_batch: prepared operands but not the batched form");
     for (int l = 0; l < n_layers; ++l)
       CGAT_TRY(bilinear_wgrad_launch(p[l], ldp, q[l], ldq, r[l], ldr, out[l], nrows, NA, NB, NC, ws, ws_bytes, stream,

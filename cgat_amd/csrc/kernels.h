@@ -117,6 +117,9 @@ int bilinear_wgrad_launch(const float* p, long ldp, const float* q, long ldq, co
 // the same for n_layers (<= 8) operand triples in ONE launch (f16x3 mode: batched, software-pipelined kernel; other
 // modes: one launch per layer).  max_wgs: grid size (0 = one workgroup per CU; 128 = half of the chip)
 size_t bilinear_wgrad_batch_ws_bytes(int n_layers, int nrows, int NA, int NB, int NC);
+// host predicate of the batched kernel: q / r = the first n_given layers' operands of an n_layers batch
+bool bilinear_wgrad_batch_takes(int n_layers, int n_given, const float* const* q, long ldq, const float* const* r, long ldr,
+                                int nrows, int NA, int NB, int NC);
 int bilinear_wgrad_batch_launch(int n_layers, const float* const* p, long ldp, const float* const* q, long ldq,
                                 const float* const* r, long ldr, float* const* out, int nrows, int NA, int NB, int NC,
                                 void* ws, size_t ws_bytes, hipStream_t stream, int max_wgs = 0, bool prepared = false);
@@ -138,6 +141,8 @@ struct TPrepBatch {
   void* dst[TPREP_MAX];
 };
 size_t bilinear_prepare_T_batch_ws_floats(int n);
+// host predicate of the batched form (mode, count, layout, the CGAT_NO_TPREP_BATCH switch, every source 16-byte aligned)
+bool bilinear_prepare_T_batch_takes(int n, const float* const* src, int n0, int n1, int n2, int perm1, int perm2);
 int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, int n0, int n1, int n2, int perm0,
                              int perm1, int perm2, float* part, hipStream_t stream, int alternate = 1);
 int bilinear_prepare_T(const float* src, float* dst, int n0, int n1, int n2, int perm0, int perm1, int perm2,

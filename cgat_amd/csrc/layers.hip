@@ -1,173 +1,7 @@
 // Layer orchestrators: the sequence of kernel launches behind each C-ABI entry point.
 // Host code only (no kernel lives here): it decides shapes, carves the caller's workspace and enqueues on the caller's
 // stream -- no allocation, no synchronisation.
-#include <string.h>
-
-#include <initializer_list>
-
-#include "../../include/cgat_hip.h"
-#include "common.h"
-#include "kernels.h"
-#include "mfma_bf16.h"
-
-// ---------------------------------------------------------------------------------------
-// launch context: persistent workspace carve-outs + one scratch region shared (in stream
-// order) by split-K slabs / column-sum partials.  `dry` only measures.
-// ---------------------------------------------------------------------------------------
-struct Ctx {
-  Workspace w;
-  bool dry;
-  hipStream_t s;
-  size_t scratch_need;
-  char* scratch;
-  size_t scratch_bytes;
-  // 128 x 128 dense-layer weights prepared ahead in one launch (f16x3 mode): looked up by (pointer, strides) in gemm()
-  WPrepBatch wprep;
-  float* wprep_images;
-  // ... and, in the 24-bit modes, the dense-layer kernel's own images (three bf16 planes) of the weights gemm() multiplies
-  // by: one launch for all of them instead of one per product
-  WPrepBatch tprep;
-  float* tprep_images;
-  Ctx(void* ws, size_t bytes, bool dry_, hipStream_t st)
-      : w(dry_ ? nullptr : ws, dry_ ? (size_t)-1 / 2 : bytes), dry(dry_), s(st), scratch_need(0), scratch(nullptr),
-        scratch_bytes(0), wprep_images(nullptr), tprep_images(nullptr) { wprep.n = 0; tprep.n = 0; }
-  void tprep_reserve(int max_items) { tprep_images = take<float>((size_t)max_items * 24576); }
-  void tprep_add(const float* W, long so, long sk) {
-    if (tprep.n < WPREP_MAX) { tprep.src[tprep.n] = W; tprep.sb[tprep.n] = sk; tprep.sc[tprep.n] = so; ++tprep.n; }
-  }
-  int tprep_run() {
-    if (dry || !mode_24bit() || tprep.n == 0 || !tprep_images) { if (!mode_24bit()) tprep.n = 0; return CGAT_OK; }
-    return prepare_T_bf16_batch_launch(tprep, tprep_images, s);
-  }
-  const void* tprep_find(const float* W, long so, long sk) const {
-    if (dry || !mode_24bit() || !tprep_images) return nullptr;
-    for (int i = 0; i < tprep.n; ++i)
-      if (tprep.src[i] == W && tprep.sb[i] == sk && tprep.sc[i] == so) return tprep_images + (size_t)i * 24576;
-    return nullptr;
-  }
-  // call before seal(): reserves the image space; add items, then wprep_run() once
-  // (images of the current arithmetic mode: the fp16 chain's in "f16x3", the six-pass bf16 chain's in the 24-bit modes;
-  // the space is reserved for the larger of the two so that a size query does not depend on the mode)
-  void wprep_reserve(int max_items) { wprep_images = take<float>((size_t)max_items * WPREP_IMAGE_FLOATS_MAX); }
-  void wprep_add(const float* W, long so, long sk) {
-    if (wprep.n < WPREP_MAX) { wprep.src[wprep.n] = W; wprep.sb[wprep.n] = sk; wprep.sc[wprep.n] = so; ++wprep.n; }
-  }
-  int wprep_run() {
-    if (dry || wprep_image_floats() == 0 || wprep.n == 0) { if (wprep_image_floats() == 0) wprep.n = 0; return CGAT_OK; }
-    return prepare_W_batch_launch(wprep, wprep_images, s);
-  }
-  const void* wprep_find(const float* W, long so, long sk) const {
-    if (dry || wprep_image_floats() == 0) return nullptr;
-    for (int i = 0; i < wprep.n; ++i)
-      if (wprep.src[i] == W && wprep.sb[i] == sk && wprep.sc[i] == so) return wprep_images + (size_t)i * wprep_image_floats();
-    return nullptr;
-  }
-  template <typename T>
-  T* take(size_t n) { return w.take<T>(n); }
-  void seal() {  // everything after the persistent carve-outs is scratch
-    if (!dry) {
-      scratch = w.base + w.off;
-      scratch_bytes = w.cap > w.off ? w.cap - w.off : 0;
-    }
-  }
-  size_t total() const { return w.off + scratch_need + 256; }
-  void need(size_t b) { if (b > scratch_need) scratch_need = b; }
-
-  int gemm(GemmParams p, bool auto_split = false) {
-    if (auto_split) p.splits = gemm_pick_splits(p.M, p.N, p.K);
-    if (p.splits > 1) need(ws_round((size_t)p.splits * p.M * p.N, 4));
-    // [rows,128] x [128,128] dense layers (trunks, linear terms of the predicted layers): the split-bf16 kernel
-    const bool dense128 = p.K == 128 && p.N >= 128 && p.N % 128 == 0 && !p.a_kmajor && !p.a_rgather && !p.a_block && !p.b_kgather &&
-                          !p.c_scatter && !p.add1 && !p.add2 && p.splits <= 1 && p.alpha == 1.f &&
-                          (p.beta == 0.f || p.beta == 1.f) && (p.act == CGAT_ACT_NONE || p.act == CGAT_ACT_TANH);
-    if (dense128) need(linear128_ws_bytes(p.N));
-    if (dry) return CGAT_OK;
-    // a few hundred rows (the harness' shipped batch): one wave per 16 x 16 output tile straight from global memory
-    // (rowprog.hip, exact fp32) -- the 128-row ring tiles below leave 250 of 256 CUs idle there
-    if (rowprog_gemm_ok(p)) return rowprog_gemm(p, s);
-    if (dense128 && linear128_fast(p.K, p.N, p.lda, p.ldc, p.A, p.C) && scratch_bytes >= linear128_ws_bytes(p.N)) {
-      const long so = p.b_kmajor ? 1 : p.ldb, sk = p.b_kmajor ? p.ldb : 1;
-      return linear128_launch(p.A, p.lda, p.B, so, sk, p.bias, p.act, p.beta == 1.f, p.C, p.ldc, p.M, scratch, s, p.N,
-                              p.N != 128 ? nullptr : (mode_f16() ? wprep_find(p.B, so, sk) : tprep_find(p.B, so, sk)));
-    }
-    return gemm_launch(p, scratch, scratch_bytes, s);
-  }
-  // weight (and bias) gradients of width-128 dense layers: out_k = G^T X_k, bsum = column sums of G (rowsdw.hip);
-  // returns -1 if the shape/alignment is not the fast one (caller falls back to gemm + colsum)
-  int dw128(const float* G, long ldg, const float* X1, long ldx1, float* out1, long ldo1, const float* X2, long ldx2,
-            float* out2, long ldo2, float* bsum, int rows) {
-    need(rows_dw128_ws_bytes(rows, X2 ? 2 : 1));
-    if (dry) return CGAT_OK;
-    if (!rows_dw128_fast(G, ldg, X1, ldx1, X2, ldx2) || scratch_bytes < rows_dw128_ws_bytes(rows, X2 ? 2 : 1)) return -1;
-    return rows_dw128_launch(G, ldg, X1, ldx1, out1, ldo1, X2, ldx2, out2, ldo2, bsum, rows, scratch, scratch_bytes, s);
-  }
-  int colsum(const float* x, long ldx, int rows, int cols, float* out, float alpha) {
-    need(colsum_ws_bytes(rows, cols));
-    if (dry) return CGAT_OK;
-    return colsum_launch(x, ldx, rows, cols, out, alpha, scratch, scratch_bytes, s);
-  }
-  // all predicted layers' dT in one launch (f16x3) on this context's stream
-  int wgrad_batch(int n, const float* const* p, const float* const* q, const float* const* r, float* const* out, int rows,
-                  int W) {
-    need(bilinear_wgrad_batch_ws_bytes(n, rows, W, W, W));
-    if (dry) return CGAT_OK;
-    return bilinear_wgrad_batch_launch(n, p, W, q, W, r, W, out, rows, W, W, W, scratch, scratch_bytes, s);
-  }
-  int bilinear(const float* p, long ldp, const float* q, long ldq, const float* T, const float* init, long ldi,
-               float* out, long ldo, int rows, int NA, int NB, int NC, float* ln_out = nullptr, float ln_eps = 0.f) {
-    need(bilinear_rows_ws_bytes(rows, NA, NB, NC));
-    if (dry) return CGAT_OK;
-    return bilinear_rows_launch(p, ldp, q, ldq, T, init, ldi, out, ldo, rows, NA, NB, NC, scratch, scratch_bytes, s,
-                                ln_out, ln_eps);
-  }
-  int dual(const float* p, long ldp, const float* q, long ldq, const float* zz, long ldz, const float* T,
-           const float* init1, long ldi1, float* out1, long ldo1, const float* init2, long ldi2, float* out2, long ldo2,
-           int rows) {
-    need(bilinear_dual_ws_bytes(rows));
-    if (dry) return CGAT_OK;
-    return bilinear_dual_launch(p, ldp, q, ldq, zz, ldz, T, init1, ldi1, out1, ldo1, init2, ldi2, out2, ldo2, rows,
-                                scratch, scratch_bytes, s);
-  }
-  int mix_bwd(const float* g, const float* a, const float* b, const float* d, float* ga, float* gb, float* gd, long n) {
-    need(4096);
-    if (dry) return CGAT_OK;
-    return mix_bwd_launch(g, a, b, d, ga, gb, gd, n, scratch, scratch_bytes, s);
-  }
-};
-
-#define RUN(expr) do { if (!c.dry) CGAT_TRY(expr); } while (0)
-
-static int check_ws(const Ctx& c, const char* who) {
-  if (c.dry) return CGAT_OK;
-  if (!c.w.ok || c.scratch_bytes < c.scratch_need) {
-    cgat_set_error("%s: workspace too small (have %zu bytes, need %zu)", who, c.w.cap, c.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  return CGAT_OK;
-}
-
-// "Size, check, run": every entry point that runs an orchestrator measures it with a dry pass, refuses a workspace smaller
-// than that, and runs the real pass with the dry pass' scratch requirement carried over; the size queries return what the
-// dry pass measured.  `impl` is an int(Ctx&) that calls the orchestrator with the entry point's operands.
-template <typename Impl>
-static Ctx dry_pass(Impl&& impl) {
-  Ctx dry(nullptr, 0, true, nullptr);
-  impl(dry);
-  return dry;
-}
-template <typename Impl>
-static size_t dry_total(Impl&& impl) { return dry_pass(impl).total(); }
-template <typename Impl>
-static int run_sized(const char* who, void* ws, size_t ws_bytes, void* stream, Impl&& impl) {
-  const Ctx dry = dry_pass(impl);
-  if (ws_bytes < dry.total()) {
-    cgat_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, dry.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  Ctx c(ws, ws_bytes, false, (hipStream_t)stream);
-  c.scratch_need = dry.scratch_need;
-  return impl(c);
-}
+#include "layers.h"
 
 // =======================================================================================
 // GATConvNodes message / softmax / aggregate
@@ -245,15 +79,7 @@ static int stack_in_weights(Ctx& c, const cgat_attn_params* p, const AttnDims& d
   return CGAT_OK;
 }
 
-// ---- routes: which launches a pass takes, decided once from the dims, the arithmetic mode, the edge-storage mode and
-// the alignment of the operands, and read by every step below.  A dry pass takes no route that depends on an operand:
-// it measures the generic steps, and the scratch a fast route needs is asked for by dims alone where that route runs
-// (so the real pass tests no scratch size: run_sized has refused a workspace smaller than the dry pass measured).
-// `ws` stands for the pass' workspace carve-outs in the kernels' 16-byte tests: Workspace::take places every one a
-// multiple of 256 bytes behind the caller's base, so any of them passes exactly when all do.
-static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
-}
+// ---- routes (layers.h: decided once per pass, read by every step; a dry pass takes none that depends on an operand) ----
 
 // How the forward forms and stores Z [E, W2] -- and therefore how the backward finds it: both passes call this with the
 // same x, e, saved buffer and fc_out_A weight (Z = saved; nullptr where the fused inference forms no Z).
@@ -1592,11 +1418,6 @@ extern "C" int cgat_nodes_attention_backward(const cgat_plan* plan, const cgat_a
 
 // ---- debug: the routes of a layer as bit masks (include/cgat_hip.h), for 16-byte aligned operands: the carve and route
 // functions of the real pass over a null, unbounded workspace ----
-static uint32_t route_bits(std::initializer_list<bool> on) {
-  uint32_t m = 0, i = 0;
-  for (bool b : on) m |= (uint32_t)b << i++;
-  return m;
-}
 extern "C" uint32_t cgat_debug_nodes_attention_route(const cgat_plan* plan, const cgat_attn_params* p, int32_t backward) {
   if (attn_check(plan, p) != CGAT_OK) return 0;
   Ctx c(nullptr, (size_t)-1 / 2, false, nullptr);
@@ -1729,563 +1550,4 @@ extern "C" int cgat_debug_edge_gw_rebuilt(const uint32_t* mask, const float* ga,
   if (took_bitplane) *took_bitplane = edge_gw_takes_bitplane(&rc, W2, perm, force_six != 0) ? 1 : 0;
   return run_sized("debug_edge_gw_rebuilt", ws, ws_bytes, stream,
                    [&](Ctx& c) { return debug_edge_gw_impl(c, rc, e, perm, E, force_six != 0, out); });
-}
-
-// =======================================================================================
-// hypernetwork Pooling_NN  (H_Net_0 / H_Net)
-// =======================================================================================
-struct HnetSaved {  // acts[l][s] (s < n_fc), u[l], vin[l] (l >= 1), hin
-  float* base;
-  size_t rw;  // rows * W
-  int n_fc, n_hyper;
-  float* act(int l, int s) const { return base + ((size_t)l * n_fc + s) * rw; }
-  float* u(int l) const { return base + ((size_t)n_hyper * n_fc + l) * rw; }
-  float* vin(int l) const { return base + ((size_t)n_hyper * n_fc + n_hyper + l) * rw; }  // l >= 1 used
-  float* hin() const { return base + ((size_t)n_hyper * n_fc + 2 * (size_t)n_hyper) * rw; }
-};
-extern "C" size_t cgat_hnet_saved_floats(int32_t rows, const cgat_hnet_params* p) {
-  return ((size_t)p->n_hyper * p->n_fc + 2 * (size_t)p->n_hyper + 1) * (size_t)rows * p->W;
-}
-static HnetSaved hnet_saved(float* base, int rows, const cgat_hnet_params* p) {
-  return HnetSaved{base, (size_t)rows * p->W, p->n_fc, p->n_hyper};
-}
-
-static int hnet_check(int rows, const cgat_hnet_params* p) {
-  CGAT_CHECK_ARG(p, "hnet: null params");
-  CGAT_CHECK_ARG(rows >= 0 && p->W > 0, "hnet: bad rows/W");
-  CGAT_CHECK_ARG(p->n_fc >= 1 && p->n_fc <= CGAT_MAX_FC && p->n_hyper >= 1 && p->n_hyper <= CGAT_MAX_HYPER,
-                 "hnet: n_fc=%d n_hyper=%d out of range", p->n_fc, p->n_hyper);
-  return CGAT_OK;
-}
-
-// `side`: optional second stream + workspace.  The four dT contractions (the weight-gradient kernel and its operand
-// preparation) feed nothing else in the backward pass, and they are matrix-core bound while what follows them (the
-// attention backward of the layer) is HBM bound: issued on the side stream they run beside it (measured in isolation:
-// 7.3 ms of contractions + 7.7 ms of streaming take 10.8 ms on two streams instead of 15.0).  Their inputs must then
-// outlive this call's main-stream buffers: every layer's g_u gets its own buffer in the side workspace.
-struct HnetSide {
-  hipStream_t s;
-  void* ws;
-  size_t bytes;
-  int wgrad_wgs;      // workgroups of the dT launch: 0 = one per CU, 128 = half of the chip
-  int dw_side;        // the batched dense-layer weight gradients: 1 = side stream behind the dT launch, 0 = main stream
-};
-// side workspace: [g_u of every predicted layer][g_pre of every trunk layer][slabs of the batched dense-layer weight
-// gradients][workspace of the dT launch]
-struct HnetSideLayout { size_t gu, gpre, dw, wgrad, total; };
-static HnetSideLayout hnet_side_layout(int rows, const cgat_hnet_params* p) {
-  const size_t rw = (size_t)rows * p->W;
-  HnetSideLayout L;
-  L.gu = 0;
-  L.gpre = L.gu + ws_round((size_t)p->n_hyper * rw, 4);
-  L.dw = L.gpre + ws_round((size_t)p->n_hyper * (p->n_fc > 0 ? p->n_fc : 1) * rw, 4);
-  L.wgrad = L.dw + rows_dw128_batch_ws_bytes(p->n_hyper * (p->n_fc + 2), rows);
-  L.total = L.wgrad + bilinear_wgrad_batch_ws_bytes(p->n_hyper, rows, p->W, p->W, p->W) + 256;
-  return L;
-}
-
-// Makes `waiter` wait for everything issued on `signaller` so far.  Events come from a small ring created lazily and
-// never destroyed: under a hipGraph capture (cgat_amd.GraphedStep) the captured dependency keeps referring to the event
-// object, and destroying it right after the wait -- legal in eager mode -- crashed hipStreamEndCapture on the second
-// capture of a process.
-static hipEvent_t g_wait_ring[64];
-static unsigned g_wait_next = 0, g_wait_made = 0;
-static int stream_wait_stream(hipStream_t waiter, hipStream_t signaller) {
-  const unsigned slot = g_wait_next++ % 64;
-  if (slot >= g_wait_made) {
-    CGAT_HIP(hipEventCreateWithFlags(&g_wait_ring[slot], hipEventDisableTiming));
-    g_wait_made = slot + 1;
-  }
-  CGAT_HIP(hipEventRecord(g_wait_ring[slot], signaller));
-  CGAT_HIP(hipStreamWaitEvent(waiter, g_wait_ring[slot], 0));
-  return CGAT_OK;
-}
-
-// The routing decisions and the carved buffers of one hypernetwork pass: made once by hnet_carve, read by every step.
-struct HnetPlan {
-  int rows, W;
-  size_t WW, rw, Tfl;    // W * W, rows * W, floats of one re-laid T
-  bool batch_T;          // the re-laid T of every predicted layer prepared up front in two launches (f16x3, f16x3c)
-  bool batch_w;          // every dense-layer weight image of the pass prepared in one launch
-  float *Tp, *Tpart;
-  // backward only: a trunk's backward as one chain launch; all dense-layer weight gradients in one batched launch at the
-  // end; at few rows the chains themselves in one batched launch; trunk layers with a g_pre buffer (at least one)
-  bool chain_ok, defer_dw, chain_batch;
-  int nfc1;
-  float *g_hin, *g_u, *gvin_buf[2], *g_t_all, *ghin_slabs, *g_pre_all;
-  HnetSideLayout SL;
-};
-
-// Carves the persistent buffers and seals the workspace.  The ORDER and sizes of the take / reserve calls are the
-// workspace layout, the same in the dry and the real pass.
-static HnetPlan hnet_carve(Ctx& c, int rows, const cgat_hnet_params* p, bool backward, const HnetSide* side) {
-  HnetPlan h = {};
-  const int W = p->W;
-  h.rows = rows; h.W = W; h.WW = (size_t)W * W; h.rw = (size_t)rows * W; h.Tfl = bilinear_T_floats(W, W, W);
-  const size_t rw = h.rw;
-  h.batch_T = W == 128 && mode_f16_T() && p->n_hyper <= TPREP_MAX && (!backward || bilinear_dual_fast(W, W, W));
-  h.Tp = c.take<float>((h.batch_T ? (size_t)p->n_hyper : 1) * h.Tfl);
-  h.Tpart = c.take<float>(bilinear_prepare_T_batch_ws_floats(p->n_hyper));
-  h.batch_w = W == 128 && p->n_hyper * (p->n_fc + 2) <= WPREP_MAX;
-  if (backward) {
-    h.g_hin = c.take<float>(rw);
-    h.g_u = c.take<float>((size_t)p->n_hyper * rw);   // one per predicted layer: all dT run in ONE launch at the end
-    h.gvin_buf[0] = c.take<float>(rw);
-    h.gvin_buf[1] = c.take<float>(rw);
-    // the fused trunk chain (chain.hip) leaves every trunk layer's pre-activation gradient behind, so the weight
-    // gradients of all dense layers of all predicted layers can wait for ONE batched launch at the end (rowsdw.hip):
-    // they feed nothing else in the backward pass.  g_pre then needs a buffer per predicted layer.
-    h.chain_ok = h.batch_w && wprep_image_floats() != 0 && p->n_fc >= 1 && p->n_fc <= CHAIN_MAX;
-    h.defer_dw = h.chain_ok && p->n_hyper * (p->n_fc + 2) <= DW_BATCH_MAX;
-    h.nfc1 = p->n_fc > 0 ? p->n_fc : 1;
-    // At a few thousand rows (the harness' shipped batch: 1 280 atoms) a trunk chain is 10 workgroups, and the four chains of
-    // a backward pass -- one per predicted layer, each 57 us, none feeding another: they feed the weight gradients and the
-    // SUM g_hin -- were 1.1 ms of an 18-ms step.  There they wait for ONE batched launch behind the loop (round 6): every
-    // predicted layer keeps its own g_t and writes its g_hin term to a slab; the slabs are added in the order the
-    // accumulating chains ran in (bit-identical).
-    h.chain_batch = h.chain_ok && h.defer_dw && rows <= 8192 && p->n_hyper > 1 && p->n_hyper <= CHAIN_BATCH_MAX &&
-                    !mode_f16();
-    h.g_t_all = c.take<float>((h.chain_batch ? (size_t)p->n_hyper : 1) * rw);
-    h.ghin_slabs = h.chain_batch ? c.take<float>((size_t)p->n_hyper * rw) : nullptr;
-    h.SL = hnet_side_layout(rows, p);
-    h.g_pre_all = (side && h.defer_dw) ? (c.dry ? nullptr : (float*)((char*)side->ws + h.SL.gpre))
-                                       : c.take<float>((size_t)(h.defer_dw ? p->n_hyper : 1) * h.nfc1 * rw);
-  }
-  if (h.batch_w) { c.wprep_reserve(p->n_hyper * (p->n_fc + 2)); c.tprep_reserve(2 * p->n_hyper); }
-  c.seal();
-  if (backward) {
-    if (h.defer_dw && !side) c.need(rows_dw128_batch_ws_bytes(p->n_hyper * (p->n_fc + 2), rows));
-    if (h.defer_dw) c.need(rows_dw128_ws_bytes(rows, 2));   // an operand off the 16-byte grid takes the per-layer launch
-  }
-  return h;
-}
-
-// The re-laid T operands of ALL predicted layers in two launches, T[o,i,k] = head_w[(o*W+i)*W + k] under the index
-// permutation the caller's contraction reads.  *ready stays false where the batched form does not exist: the caller
-// then prepares each layer's operand when it gets there.
-static int hnet_prepare_T_all(Ctx& c, const HnetPlan& h, const cgat_hnet_params* p, int perm0, int perm1, int perm2,
-                              bool* ready) {
-  *ready = false;
-  if (!h.batch_T || c.dry) return CGAT_OK;
-  const float* tsrc[TPREP_MAX];
-  float* tdst[TPREP_MAX];
-  for (int l = 0; l < p->n_hyper; ++l) { tsrc[l] = p->layer[l].head_w; tdst[l] = h.Tp + (size_t)l * h.Tfl; }
-  const int rc_ = bilinear_prepare_T_batch(p->n_hyper, tsrc, tdst, h.W, h.W, h.W, perm0, perm1, perm2, h.Tpart, c.s);
-  if (rc_ == CGAT_OK) *ready = true;
-  else if (rc_ != CGAT_ERR_UNSUPPORTED) return rc_;
-  return CGAT_OK;
-}
-
-// Every dense-layer weight of the pass, prepared in one launch per image kind: forward orientation [out][in], or
-// `transposed` for the backward's g_in = g_out W.  Bm = head_b[:W*W] as [o,i], U = head_w[W*W:].
-static int hnet_prepare_weights(Ctx& c, const HnetPlan& h, const cgat_hnet_params* p, bool transposed) {
-  if (!h.batch_w) return CGAT_OK;
-  const long so = transposed ? 1 : h.W, sk = transposed ? h.W : 1;
-  for (int l = 0; l < p->n_hyper; ++l) {
-    const float* U = p->layer[l].head_w + h.WW * h.W;
-    for (int s = 0; s < p->n_fc; ++s) c.wprep_add(p->layer[l].fc_w[s], so, sk);
-    if (mode_f16()) {
-      c.wprep_add(p->layer[l].head_b, so, sk);   // read by linear128_launch in that mode only
-    } else {                                     // (the 24-bit modes: the dense-layer kernel's image)
-      c.tprep_add(p->layer[l].head_b, so, sk);
-      if (transposed) c.tprep_add(U, so, sk);
-    }
-    c.wprep_add(U, so, sk);
-  }
-  CGAT_TRY(c.wprep_run());
-  CGAT_TRY(c.tprep_run());
-  return CGAT_OK;
-}
-
-// The trunk (n_fc x [Linear + Tanh]) and the trunk-side linear term of the head, u = z @ U^T + b0, as ONE chain per
-// predicted layer (chain.hip) when the weights of the pass have been prepared in a batch (width 128, <= 4 trunk layers)
-// -- and, since every predicted layer's trunk reads the same hyper input, the chains of ALL predicted layers as ONE
-// launch (round 5); the remaining linear term u += vin @ Bm^T follows per layer.  *chained stays false where a chain
-// cannot run: the caller then takes the per-layer products.
-static int hnet_forward_chains(Ctx& c, const HnetPlan& h, const cgat_hnet_params* p, const float* hin, const HnetSaved& sv,
-                               float* y, bool* chained) {
-  *chained = false;
-  if (!h.batch_w || c.dry || wprep_image_floats() == 0 || p->n_fc + 1 > CHAIN_MAX || p->n_hyper > CGAT_MAX_HYPER) return CGAT_OK;
-  const int W = h.W;
-  ChainDesc cds[CGAT_MAX_HYPER];
-  for (int l = 0; l < p->n_hyper; ++l) {
-    const cgat_hyperlinear_params& L = p->layer[l];
-    ChainDesc& cd = cds[l];
-    memset(&cd, 0, sizeof(cd));
-    cd.n_layers = p->n_fc + 1; cd.rows = h.rows; cd.x = hin; cd.ldx = W;
-    for (int s = 0; s < p->n_fc; ++s) {
-      ChainLayer& cl = cd.layer[s];
-      cl.W = (const uint4*)c.wprep_find(L.fc_w[s], W, 1);
-      cl.bias = L.fc_b[s]; cl.act = CGAT_ACT_TANH; cl.out = sv.act(l, s); cl.ld_out = W;
-      if (!cl.W) return CGAT_OK;
-    }
-    ChainLayer& cu = cd.layer[p->n_fc];
-    cu.W = (const uint4*)c.wprep_find(L.head_w + h.WW * W, W, 1);
-    cu.bias = L.head_b + h.WW; cu.act = CGAT_ACT_NONE; cu.out = (l == p->n_hyper - 1) ? y : sv.u(l); cu.ld_out = W;
-    if (!cu.W || !mlp_chain128_fast(cd)) return CGAT_OK;
-  }
-  for (int l0 = 0; l0 < p->n_hyper; l0 += CHAIN_BATCH_MAX)
-    CGAT_TRY(mlp_chain128_batch_launch(cds + l0, p->n_hyper - l0 < CHAIN_BATCH_MAX ? p->n_hyper - l0 : CHAIN_BATCH_MAX, c.s));
-  *chained = true;
-  return CGAT_OK;
-}
-
-static int hnet_forward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const float* h0, const float* v, float* y,
-                             float* saved) {
-  const HnetPlan h = hnet_carve(c, rows, p, /*backward=*/false, nullptr);
-  const int W = h.W;
-  bool T_ready = false, chained = false;
-  CGAT_TRY(hnet_prepare_T_all(c, h, p, 1, 2, 0, &T_ready));   // T re-laid as Tp[i,k,o]
-  CGAT_TRY(hnet_prepare_weights(c, h, p, /*transposed=*/false));
-  HnetSaved sv = hnet_saved(saved, rows, p);
-  const float* hin = h0;
-  if (p->damping) {
-    RUN(mix_launch(h0, v, p->damping, sv.hin(), (long)rows * W, c.s));
-    hin = sv.hin();
-  }
-  CGAT_TRY(hnet_forward_chains(c, h, p, hin, sv, y, &chained));
-  const float* vin = v;
-  for (int l = 0; l < p->n_hyper; ++l) {
-    const cgat_hyperlinear_params& L = p->layer[l];
-    float* u = c.dry ? nullptr : ((l == p->n_hyper - 1) ? y : sv.u(l));
-    const float* z = c.dry ? nullptr : sv.act(l, p->n_fc - 1);
-    if (chained) {   // u holds z @ U^T + b0
-      GemmParams g = gemm_params(rows, W, W, vin, W, L.head_b, W, u, W);
-      g.beta = 1.f;
-      CGAT_TRY(c.gemm(g));
-    } else {
-      const float* t = hin;
-      for (int s = 0; s < p->n_fc; ++s) {  // trunk: Linear + Tanh
-        GemmParams g = gemm_params(rows, W, W, t, W, L.fc_w[s], W, c.dry ? nullptr : sv.act(l, s), W);
-        g.bias = L.fc_b[s];
-        g.act = CGAT_ACT_TANH;
-        CGAT_TRY(c.gemm(g));
-        t = c.dry ? nullptr : sv.act(l, s);
-      }
-      // bias-row terms of the head:  u = vin @ Bm^T + z @ U^T + b0
-      GemmParams g = gemm_params(rows, W, W, vin, W, L.head_b, W, u, W);
-      CGAT_TRY(c.gemm(g));
-      g = gemm_params(rows, W, W, z, W, L.head_w + h.WW * W, W, u, W);
-      g.bias = L.head_b + h.WW;
-      g.beta = 1.f;
-      CGAT_TRY(c.gemm(g));
-    }
-    // trilinear term with T[o,i,k] = head_w[(o*W+i)*W + k] re-laid as Tp[i,k,o]
-    float* Tl = h.Tp + (T_ready ? (size_t)l * h.Tfl : 0);
-    if (!T_ready) RUN(bilinear_prepare_T(L.head_w, Tl, W, W, W, 1, 2, 0, c.s));
-    // (+ LayerNorm + tanh of every layer but the last, fused into the contraction's slab sum at width 128)
-    const bool ln = l < p->n_hyper - 1;
-    const bool ln_fused = ln && W == 128;
-    CGAT_TRY(c.bilinear(vin, W, z, W, Tl, u, W, u, W, rows, W, W, W, (ln_fused && !c.dry) ? sv.vin(l + 1) : nullptr, 1e-5f));
-    if (ln) {
-      if (!ln_fused) RUN(layernorm_tanh_fwd_launch(u, sv.vin(l + 1), rows, W, 1e-5f, c.s));
-      vin = c.dry ? nullptr : sv.vin(l + 1);
-    }
-  }
-  return check_ws(c, "hnet_forward");
-}
-
-// backward: what its steps share -- the plan, the operands and the three queues that wait for a batched launch in the tail
-struct HnetBwd {
-  HnetPlan h;
-  const cgat_hnet_params* p;
-  const cgat_hnet_grads* gr;
-  const HnetSide* side;
-  HnetSaved sv;
-  const float* hin;
-  bool T_ready;
-  DwBatchDesc dwb;                        // dense-layer weight gradients (rowsdw.hip)
-  ChainDesc pending[CHAIN_BATCH_MAX];     // trunk chains (chain_batch); chain i writes slab i of ghin_slabs
-  int n_pending;
-  const float *dT_gu[CGAT_MAX_HYPER], *dT_vin[CGAT_MAX_HYPER], *dT_z[CGAT_MAX_HYPER];   // dT: all predicted layers in one launch
-  float* dT_out[CGAT_MAX_HYPER];
-  int n_deferred;
-  // dT operands are prepared (maxima, scaled transposes, fp16 planes: HBM-bound, 0.25 ms a layer) on the side stream as
-  // soon as a layer's gu exists, beside that layer's matrix-bound contraction on the main stream, so that the dT launch
-  // itself can start the moment the backward has issued its last kernel
-  bool early_prep;
-  int n_prepped;
-};
-
-// Weight (and bias) gradients of one dense layer: out1 = G^T X1 (and out2 = G^T X2 when X2 is given), bsum = column sums
-// of G.  In order of preference: queued for the batched launch of the tail (`may_wait`: G stays as it is until then),
-// the rows kernel now (rowsdw.hip), generic products + column sum.
-static int dense_wgrad(Ctx& c, HnetBwd& b, bool may_wait, const float* G, const float* X1, float* out1, const float* X2,
-                       float* out2, float* bsum) {
-  const int W = b.h.W, rows = b.h.rows;
-  const int nx = X2 ? 2 : 1;
-  if (may_wait && c.dry) return CGAT_OK;   // (hnet_carve has sized the batched launch and the per-layer one)
-  if (may_wait && b.dwb.n + nx <= DW_BATCH_MAX && rows_dw128_fast(G, W, X1, W, X2, X2 ? W : 0)) {
-    b.dwb.it[b.dwb.n++] = {G, X1, out1, bsum};
-    if (X2) b.dwb.it[b.dwb.n++] = {G, X2, out2, nullptr};
-    return CGAT_OK;
-  }
-  const int fused = W == 128 ? c.dw128(G, W, X1, W, out1, W, X2, X2 ? W : 0, out2, X2 ? W : 0, bsum, rows) : -1;
-  if (fused > 0) return fused;
-  if (fused < 0) {
-    GemmParams g = gemm_params(W, W, rows, G, W, X1, W, out1, W);
-    g.a_kmajor = 1; g.b_kmajor = 1;
-    CGAT_TRY(c.gemm(g, true));
-    if (X2) {
-      g = gemm_params(W, W, rows, G, W, X2, W, out2, W);
-      g.a_kmajor = 1; g.b_kmajor = 1;
-      CGAT_TRY(c.gemm(g, true));
-    }
-    CGAT_TRY(c.colsum(G, W, rows, W, bsum, 1.f));
-  }
-  return CGAT_OK;
-}
-
-// ---- head parameter gradients of predicted layer l ----
-static int hnet_head_param_grads(Ctx& c, HnetBwd& b, int l, const float* gu, const float* vin, const float* z) {
-  const HnetPlan& h = b.h;
-  const int W = h.W;
-  const cgat_hyperlinear_grads& G = b.gr->layer[l];
-  // dT[o][i][k] = sum_n gu[n,o] vin[n,i] z[n,k]: deferred, all predicted layers in one launch (hnet_backward_tail)
-  b.dT_gu[b.n_deferred] = gu; b.dT_vin[b.n_deferred] = vin; b.dT_z[b.n_deferred] = z; b.dT_out[b.n_deferred++] = G.head_w;
-  if (b.early_prep) {
-    CGAT_TRY(stream_wait_stream(b.side->s, c.s));
-    const int rc_ = bilinear_wgrad_batch_prep(b.n_deferred - 1, b.p->n_hyper, gu, W, vin, W, z, W, h.rows, W, W, W,
-                                              (char*)b.side->ws + h.SL.wgrad, b.side->bytes - h.SL.wgrad, b.side->s);
-    if (rc_ == CGAT_OK) ++b.n_prepped;
-    else if (rc_ == CGAT_ERR_UNSUPPORTED) b.early_prep = false;
-    else return rc_;
-  }
-  // Bm grad [o][i] = gu^T vin, U grad [o][k] = gu^T z, bias grad = column sums of gu: one pass over the three operands
-  return dense_wgrad(c, b, h.defer_dw, gu, vin, G.head_b, z, G.head_w + h.WW * W, G.head_b + h.WW);
-}
-
-// ---- the head's input gradients: g_t = g_z (wrt the trunk output), g_vin (wrt the layer's input) ----
-static int hnet_head_input_grads(Ctx& c, const HnetBwd& b, int l, const float* gu, const float* vin, const float* z,
-                                 float* g_t, float* g_vin) {
-  const HnetPlan& h = b.h;
-  const int W = h.W, rows = h.rows;
-  const cgat_hyperlinear_params& L = b.p->layer[l];
-  {  // g_z = gu @ U + sum_{o,i} gu[o] vin[i] T[o,i,k]
-    GemmParams g = gemm_params(rows, W, W, gu, W, L.head_w + h.WW * W, W, g_t, W);
-    g.b_kmajor = 1;
-    CGAT_TRY(c.gemm(g));
-  }
-  {  // g_vin = gu @ Bm + sum_{o,k} gu[o] z[k] T[o,i,k]
-    GemmParams g = gemm_params(rows, W, W, gu, W, L.head_b, W, g_vin, W);
-    g.b_kmajor = 1;
-    CGAT_TRY(c.gemm(g));
-  }
-  if (bilinear_dual_fast(W, W, W)) {
-    // both bilinear parts from one contraction: M[n,i,k] = sum_o gu[o] T[o,i,k];  g_z += vin . M,  g_vin += M . z
-    float* Tl = h.Tp + (b.T_ready ? (size_t)l * h.Tfl : 0);
-    if (!b.T_ready) RUN(bilinear_prepare_T(L.head_w, Tl, W, W, W, 1, 0, 2, c.s));   // operand [a = i][b = o][c = k]
-    CGAT_TRY(c.dual(vin, W, gu, W, z, W, Tl, g_t, W, g_t, W, g_vin, W, g_vin, W, rows));
-  } else {
-    RUN(bilinear_prepare_T(L.head_w, h.Tp, W, W, W, 0, 1, 2, c.s));
-    CGAT_TRY(c.bilinear(gu, W, vin, W, h.Tp, g_t, W, g_t, W, rows, W, W, W));
-    RUN(bilinear_prepare_T(L.head_w, h.Tp, W, W, W, 0, 2, 1, c.s));   // T re-laid as [o,k,i]
-    CGAT_TRY(c.bilinear(gu, W, z, W, h.Tp, g_vin, W, g_vin, W, rows, W, W, W));
-  }
-  return CGAT_OK;
-}
-
-// ---- trunk backward of predicted layer l (g_t holds the gradient wrt the trunk output z) ----
-// One chain launch on the transposed weights (chain.hip): rows = g_t * tanh'(t_last) = the last layer's
-// pre-activation gradient, layer i multiplies by W_(n_fc-1-i) and by tanh' of the activation below it, every
-// pre-activation gradient is stored for the weight-gradient kernel, the last product is added to g_hin -- launched now,
-// or queued for the batched launch of the tail (chain_batch).  *chained stays false where the chain cannot run.
-static int hnet_trunk_backward_chain(Ctx& c, HnetBwd& b, int l, const float* g_t, float* g_pre, bool* chained) {
-  *chained = false;
-  const HnetPlan& h = b.h;
-  if (!h.chain_ok || c.dry) return CGAT_OK;
-  const int W = h.W, nf = b.p->n_fc;
-  const size_t rw = h.rw;
-  const cgat_hyperlinear_params& L = b.p->layer[l];
-  const cgat_hyperlinear_grads& G = b.gr->layer[l];
-  auto below = [&](int s) { return s == 0 ? b.hin : b.sv.act(l, s - 1); };   // input rows of trunk layer s
-  // (batched: a weight gradient that cannot wait for the batched launch would read g_pre before the chain has run)
-  bool can_wait = h.chain_batch;
-  for (int s = nf - 1; s >= 0 && can_wait; --s)
-    can_wait = rows_dw128_fast(g_pre + (size_t)s * rw, W, below(s), W, nullptr, 0) && b.dwb.n + nf <= DW_BATCH_MAX;
-  ChainDesc cd;
-  memset(&cd, 0, sizeof(cd));
-  cd.n_layers = nf; cd.rows = h.rows; cd.x = g_t; cd.ldx = W;
-  cd.in_dact = b.sv.act(l, nf - 1); cd.ld_in_dact = W; cd.in_dact_type = CGAT_ACT_TANH;
-  cd.in_store = g_pre + (size_t)(nf - 1) * rw; cd.ld_in_store = W;
-  for (int i = 0; i < nf; ++i) {
-    const int sl = nf - 1 - i;                      // trunk layer whose weight this chain layer multiplies by
-    ChainLayer& cl = cd.layer[i];
-    cl.W = (const uint4*)c.wprep_find(L.fc_w[sl], 1, W);
-    if (!cl.W) return CGAT_OK;
-    cl.act = CGAT_ACT_NONE;
-    cl.ld_out = W;
-    if (sl > 0) {
-      cl.dact = b.sv.act(l, sl - 1); cl.ld_dact = W; cl.dact_type = CGAT_ACT_TANH;
-      cl.out = g_pre + (size_t)(sl - 1) * rw;
-    } else if (can_wait) {
-      cl.out = h.ghin_slabs + (size_t)b.n_pending * rw;   // (summed in the tail, in this order)
-    } else {
-      cl.out = h.g_hin; cl.accumulate = 1;   // every predicted layer's trunk reads the same hyper input
-    }
-  }
-  if (!mlp_chain128_fast(cd)) return CGAT_OK;
-  if (can_wait) b.pending[b.n_pending++] = cd;
-  else CGAT_TRY(mlp_chain128_launch(cd, c.s));
-  for (int s = nf - 1; s >= 0; --s)
-    CGAT_TRY(dense_wgrad(c, b, h.defer_dw, g_pre + (size_t)s * rw, below(s), G.fc_w[s], nullptr, nullptr, G.fc_b[s]));
-  *chained = true;
-  return CGAT_OK;
-}
-
-// ... or layer by layer (what the dry pass sizes): g_pre is ONE buffer for all trunk layers, no weight gradient can wait
-static int hnet_trunk_backward_layers(Ctx& c, HnetBwd& b, int l, float* g_t, float* g_pre) {
-  const HnetPlan& h = b.h;
-  const int W = h.W, rows = h.rows;
-  const cgat_hyperlinear_params& L = b.p->layer[l];
-  const cgat_hyperlinear_grads& G = b.gr->layer[l];
-  for (int s = b.p->n_fc - 1; s >= 0; --s) {
-    const float* tout = c.dry ? nullptr : b.sv.act(l, s);
-    const float* tin = (s == 0) ? b.hin : (c.dry ? nullptr : b.sv.act(l, s - 1));
-    RUN(act_bwd_launch(tout, g_t, g_pre, (long)h.rw, CGAT_ACT_TANH, c.s));
-    CGAT_TRY(dense_wgrad(c, b, /*may_wait=*/false, g_pre, tin, G.fc_w[s], nullptr, nullptr, G.fc_b[s]));
-    GemmParams g = gemm_params(rows, W, W, g_pre, W, L.fc_w[s], W, s == 0 ? h.g_hin : g_t, W);
-    g.b_kmajor = 1;
-    g.beta = (s == 0) ? 1.f : 0.f;  // every predicted layer's trunk reads the same hyper input
-    CGAT_TRY(c.gemm(g));
-  }
-  return CGAT_OK;
-}
-
-// ---- behind the loop: the three queues, and the gradient of the hyper input ----
-static int hnet_backward_tail(Ctx& c, HnetBwd& b, const float* h0, const float* v, float* g_h0, float* g_v) {
-  const HnetPlan& h = b.h;
-  const HnetSide* side = b.side;
-  const int W = h.W, rows = h.rows;
-  if (b.n_pending > 0) {
-    CGAT_TRY(mlp_chain128_batch_launch(b.pending, b.n_pending, c.s));
-    if (b.n_pending == b.p->n_hyper) {   // (g_hin was zero: 0.f + c_last + ... + c_0)
-      RUN(sum_slabs_launch(h.ghin_slabs, b.n_pending, (long)h.rw, h.g_hin, (long)h.rw, c.s));
-    } else {      // some layer took the accumulating route: add the slabs to what it left
-      for (int z = 0; z < b.n_pending; ++z) RUN(axpy_launch(h.g_hin, h.ghin_slabs + (size_t)z * h.rw, 1.f, (long)h.rw, c.s));
-    }
-  }
-  if (b.p->damping) {
-    CGAT_TRY(c.mix_bwd(h.g_hin, h0, v, b.p->damping, g_h0, g_v, b.gr->damping, (long)h.rw));
-  } else {
-    RUN(copy2d_launch(h.g_hin, W, g_h0, W, rows, W, c.s));
-  }
-  bool side_waits = false;   // the side stream has been made to wait for everything issued above
-  auto side_wait = [&]() -> int {
-    if (side_waits) return CGAT_OK;
-    side_waits = true;
-    return stream_wait_stream(side->s, c.s);
-  };
-  if (b.n_deferred > 0) {
-    if (side && !c.dry) {
-      // On the side stream the dT launch starts when everything above has been issued on the main stream, i.e. together
-      // with whatever the caller enqueues next (the HBM-bound attention backward), on `wgrad_wgs` workgroups.
-      CGAT_TRY(side_wait());
-      CGAT_TRY(bilinear_wgrad_batch_launch(b.n_deferred, b.dT_gu, W, b.dT_vin, W, b.dT_z, W, b.dT_out, rows, W, W, W,
-                                           (char*)side->ws + h.SL.wgrad, side->bytes - h.SL.wgrad, side->s, side->wgrad_wgs,
-                                           b.early_prep && b.n_prepped == b.n_deferred));
-    } else {
-      CGAT_TRY(c.wgrad_batch(b.n_deferred, b.dT_gu, b.dT_vin, b.dT_z, b.dT_out, rows, W));
-    }
-  }
-  if (b.dwb.n > 0 && !c.dry) {
-    // HBM-bound, 0.7 ms for 24 products at 83 340 rows; in f16x3 on the main stream, right here.  On the side stream
-    // (f16x3c) it goes BEHIND the dT launch: that launch must be resident before the caller's next kernel floods
-    // the chip with small workgroups (its 132-KB workgroups are not placed while those keep arriving -- measured: 9.5 ms
-    // instead of 6.2 when it started 0.7 ms later), and there it ends up beside the matrix-bound edge_ge (1.3 -> 2.5 ms)
-    if (side && side->dw_side) {
-      CGAT_TRY(side_wait());
-      CGAT_TRY(rows_dw128_batch_launch(b.dwb, (char*)side->ws + h.SL.dw, h.SL.wgrad - h.SL.dw, side->s));
-    } else if (side) {   // main stream; the operands live in the side workspace either way
-      CGAT_TRY(rows_dw128_batch_launch(b.dwb, (char*)side->ws + h.SL.dw, h.SL.wgrad - h.SL.dw, c.s));
-    } else {
-      CGAT_TRY(rows_dw128_batch_launch(b.dwb, c.scratch, c.scratch_bytes, c.s));
-    }
-  }
-  return CGAT_OK;
-}
-
-static int hnet_backward_impl(Ctx& c, int rows, const cgat_hnet_params* p, const float* h0, const float* v,
-                              const float* saved, const float* g_y, float* g_h0, float* g_v,
-                              const cgat_hnet_grads* gr, const HnetSide* side = nullptr) {
-  HnetBwd b = {};
-  b.h = hnet_carve(c, rows, p, /*backward=*/true, side);
-  b.p = p; b.gr = gr; b.side = side;
-  const HnetPlan& h = b.h;
-  const int W = h.W;
-  b.dwb.rows = rows; b.dwb.ldg = W; b.dwb.ldx = W; b.dwb.ldo = W;
-  CGAT_TRY(hnet_prepare_weights(c, h, p, /*transposed=*/true));
-  CGAT_TRY(hnet_prepare_T_all(c, h, p, 1, 0, 2, &b.T_ready));   // the [a = i][b = o][c = k] operands
-  b.sv = hnet_saved(const_cast<float*>(saved), rows, p);
-  b.hin = p->damping ? b.sv.hin() : h0;
-  RUN(fill_launch(h.g_hin, 0.f, (long)h.rw, c.s));
-  b.early_prep = side && !c.dry && rows >= 16384;   // (small batches: 9 more launches cost more than they hide)
-  const float* gout = g_y;  // gradient wrt the output of predicted layer l (post norm for l < last)
-  for (int l = p->n_hyper - 1; l >= 0; --l) {
-    const float* gu = gout;  // gradient wrt the pre-norm output u_l
-    if (l < p->n_hyper - 1) {
-      float* gu_buf = c.dry ? nullptr : ((side ? (float*)side->ws : h.g_u) + (size_t)l * h.rw);
-      RUN(layernorm_tanh_bwd_launch(b.sv.u(l), b.sv.vin(l + 1), gout, gu_buf, rows, W, 1e-5f, c.s));
-      gu = gu_buf;
-    }
-    float* g_vin = (l == 0) ? g_v : h.gvin_buf[l & 1];  // gradient wrt this layer's input
-    float* g_t = c.dry ? nullptr : h.g_t_all + (h.chain_batch ? (size_t)l * h.rw : 0);
-    float* g_pre = c.dry ? nullptr : h.g_pre_all + (h.defer_dw ? (size_t)l * h.nfc1 * h.rw : 0);
-    const float* vin = (l == 0) ? v : b.sv.vin(l);
-    const float* z = c.dry ? nullptr : b.sv.act(l, p->n_fc - 1);
-    CGAT_TRY(hnet_head_param_grads(c, b, l, gu, vin, z));
-    CGAT_TRY(hnet_head_input_grads(c, b, l, gu, vin, z, g_t, g_vin));
-    bool chained = false;
-    CGAT_TRY(hnet_trunk_backward_chain(c, b, l, g_t, g_pre, &chained));
-    if (!chained) CGAT_TRY(hnet_trunk_backward_layers(c, b, l, g_t, g_pre));
-    gout = g_vin;
-  }
-  CGAT_TRY(hnet_backward_tail(c, b, h0, v, g_h0, g_v));
-  return check_ws(c, "hnet_backward");
-}
-
-extern "C" size_t cgat_hnet_forward_workspace_bytes(int32_t rows, const cgat_hnet_params* p) {
-  return dry_total([&](Ctx& c) { return hnet_forward_impl(c, rows, p, nullptr, nullptr, nullptr, nullptr); });
-}
-extern "C" size_t cgat_hnet_backward_workspace_bytes(int32_t rows, const cgat_hnet_params* p) {
-  cgat_hnet_grads g = {};
-  return dry_total([&](Ctx& c) { return hnet_backward_impl(c, rows, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &g); });
-}
-extern "C" int cgat_hnet_forward(int32_t rows, const cgat_hnet_params* p, const float* h0, const float* v, float* y,
-                                 float* saved, void* ws, size_t ws_bytes, void* stream) {
-  CGAT_TRY(hnet_check(rows, p));
-  return run_sized("hnet_forward", ws, ws_bytes, stream,
-                   [&](Ctx& c) { return hnet_forward_impl(c, rows, p, h0, v, y, saved); });
-}
-extern "C" size_t cgat_hnet_backward_side_workspace_bytes(int32_t rows, const cgat_hnet_params* p) {
-  return hnet_side_layout(rows, p).total;
-}
-extern "C" int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_params* p, const float* h0, const float* v,
-                                             const float* saved, const float* g_y, float* g_h0, float* g_v,
-                                             const cgat_hnet_grads* g, void* ws, size_t ws_bytes, void* stream,
-                                             void* side_ws, size_t side_ws_bytes, void* side_stream) {
-  CGAT_TRY(hnet_check(rows, p));
-  CGAT_CHECK_ARG(g, "hnet_backward: null grads");
-  CGAT_CHECK_ARG(side_stream && side_ws && side_ws_bytes >= hnet_side_layout(rows, p).total,
-                 "hnet_backward_overlapped: side stream / workspace missing or too small");
-  // 128 workgroups: half of the chip stays free for the main stream's HBM-bound kernels
-  const int side_wgs = 128;
-  // the batched dense-layer weight gradients: f16x3 -- main stream (behind the dT launch on the side stream the batch
-  // collided with the matrix-bound edge_ge: 24.14 vs 23.95 ms per step); f16x3c -- side stream (the 24-bit dT launch is
-  // twice as long and still running when edge_ge starts either way: 29.0-29.4 vs 29.5 ms, serial order 29.9-30.0;
-  // profiles/r05_side_stream_sweep.txt)
-  const int dw_side = mode_f16c() ? 1 : 0;
-  const HnetSide side = {(hipStream_t)side_stream, side_ws, side_ws_bytes, side_wgs, dw_side};
-  // (sized as cgat_hnet_backward_workspace_bytes sizes it: the main workspace of the serial backward)
-  return run_sized("hnet_backward", ws, ws_bytes, stream, [&](Ctx& c) {
-    return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g, c.dry ? nullptr : &side);
-  });
-}
-extern "C" int cgat_hnet_backward(int32_t rows, const cgat_hnet_params* p, const float* h0, const float* v,
-                                  const float* saved, const float* g_y, float* g_h0, float* g_v,
-                                  const cgat_hnet_grads* g, void* ws, size_t ws_bytes, void* stream) {
-  CGAT_TRY(hnet_check(rows, p));
-  CGAT_CHECK_ARG(g, "hnet_backward: null grads");
-  return run_sized("hnet_backward", ws, ws_bytes, stream,
-                   [&](Ctx& c) { return hnet_backward_impl(c, rows, p, h0, v, saved, g_y, g_h0, g_v, g); });
 }

@@ -380,22 +380,27 @@ __global__ void prepare_T_f16c_batch_kernel(TPrepBatch b, int NA, long sa, long 
 size_t bilinear_prepare_T_batch_ws_floats(int n) { return (size_t)(n > 0 ? n : 1) * TPREP_PARTS; }
 // f16x3 / f16x3c modes, 128-wide interleaved layout only (returns CGAT_ERR_UNSUPPORTED otherwise: prepare one by one);
 // dst[i]: bilinear_T_floats(...) floats each; part: bilinear_prepare_T_batch_ws_floats(n) floats
-int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, int n0, int n1, int n2, int perm0,
-                             int perm1, int perm2, float* part, hipStream_t stream, int alternate) {
-  int dims[3] = {n0, n1, n2};
+// does the batched form exist for these sources?  Host only: a caller that decides its route before its first launch asks
+// this; bilinear_prepare_T_batch answers CGAT_ERR_UNSUPPORTED exactly where it says no.
+bool bilinear_prepare_T_batch_takes(int n, const float* const* src, int n0, int n1, int n2, int perm1, int perm2) {
+  const int dims[3] = {n0, n1, n2};
   static int off = -1;   // CGAT_NO_TPREP_BATCH=1 (debug): prepare the operands one by one
   if (off < 0) { const char* e = getenv("CGAT_NO_TPREP_BATCH"); off = (e && e[0] == '1') ? 1 : 0; }
-  if (off || n < 1 || n > TPREP_MAX || !mode_f16_T() || !bilinear_T_interleaved(dims[perm1], dims[perm2]))
-    return CGAT_ERR_UNSUPPORTED;
+  if (off || n < 1 || n > TPREP_MAX || !mode_f16_T() || !bilinear_T_interleaved(dims[perm1], dims[perm2])) return false;
+  for (int i = 0; i < n; ++i)
+    if ((((uintptr_t)src[i]) & 15) != 0) return false;
+  return true;
+}
+int bilinear_prepare_T_batch(int n, const float* const* src, float* const* dst, int n0, int n1, int n2, int perm0,
+                             int perm1, int perm2, float* part, hipStream_t stream, int alternate) {
+  const int dims[3] = {n0, n1, n2};
+  if (!bilinear_prepare_T_batch_takes(n, src, n0, n1, n2, perm1, perm2)) return CGAT_ERR_UNSUPPORTED;
   const long st[3] = {(long)n1 * n2, (long)n2, 1};
   const int NA = dims[perm0];
   const long total = (long)NA * 128 * 128;
   TPrepBatch b;
   b.n = n;
-  for (int i = 0; i < n; ++i) {
-    if ((((uintptr_t)src[i]) & 15) != 0) return CGAT_ERR_UNSUPPORTED;
-    b.src[i] = src[i]; b.dst[i] = dst[i];
-  }
+  for (int i = 0; i < n; ++i) { b.src[i] = src[i]; b.dst[i] = dst[i]; }
   hipLaunchKernelGGL(absmax_partial_batch_kernel, dim3(TPREP_PARTS, n), dim3(256), 0, stream, b, total, part);
   CGAT_LAUNCH_CHECK();
   if (mode_f16c())

@@ -459,7 +459,7 @@ extern "C" int cgat_rowprog_run(const cgat_rowprog* prog, uint32_t* sync_words, 
   return rowprog_launch(prog->op, prog->n_ops, sync_words, (hipStream_t)stream);
 }
 
-// ---- the layer orchestrators' small-row products (layers.hip, Ctx::gemm) as single-op programs ----
+// ---- the layer orchestrators' small-row products (layers.h, Ctx::gemm) as single-op programs ----
 static int g_rp_max_rows = -1;
 int rowprog_max_rows() {
   if (g_rp_max_rows < 0) {

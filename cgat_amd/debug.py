@@ -170,6 +170,23 @@ def edge_hidden_route(N, E, C_, Ce, W2, backward=False, g_is_pre=False, has_absm
     return {n for i, n in enumerate(EDGE_HIDDEN_ROUTE_BITS["backward" if backward else "forward"]) if mask >> i & 1}
 
 
+# bit i of cgat_debug_hnet_route's mask (include/cgat_hip.h; HnetFwdRoute / HnetBwdRoute of csrc/hnet.hip)
+HNET_ROUTE_BITS = {
+    "forward": ("t_batched", "w_batched", "chained", "ln_fused"),
+    "backward": ("t_batched", "w_batched", "dual", "chain", "chain_queued", "dw_deferred", "head_dw_queued",
+                 "head_dw_rows", "dT_side", "early_prep", "dw_side", "dw_side_ws"),
+}
+
+
+def hnet_route(rows, W, n_fc, n_hyper, backward=False, overlapped=False):
+    """The names of the routes cgat_hnet_forward / _backward (overlapped: _backward_overlapped) take at these shapes in the
+    current arithmetic mode, for 16-byte aligned operands (host only, no GPU needed)."""
+    p = _lib.HnetParams()
+    p.W, p.n_fc, p.n_hyper = W, n_fc, n_hyper
+    mask = lib.cgat_debug_hnet_route(rows, C.byref(p), 1 if backward else 0, 1 if overlapped else 0)
+    return {n for i, n in enumerate(HNET_ROUTE_BITS["backward" if backward else "forward"]) if mask >> i & 1}
+
+
 def edge_ge_rebuilt(mask, ga, alpha, gS, wA, dst, We, H, Hd):
     """grad edge_attr's product alone on caller-supplied ingredients of the rebuilt rows (cgat_debug_edge_ge_rebuilt,
     include/cgat_hip.h): mask int32 [E, 2 H Hd / 32] bit words, ga / alpha [E, H], gS [N, H Hd], wA [H Hd], dst int32 [E],

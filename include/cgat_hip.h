@@ -461,7 +461,22 @@ int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_params* p, const
                                   void* ws, size_t ws_bytes, void* stream, void* side_ws, size_t side_ws_bytes,
                                   void* side_stream);
 
-/* ---- dense layer  y = act(x W^T + b)  (nn.Linear / 1x1 Conv1d group + activation) --------
+/* Debug (tests only): the route cgat_hnet_forward (backward == 0), cgat_hnet_backward (backward != 0) or
+ * cgat_hnet_backward_overlapped (backward != 0 and overlapped != 0) takes at these rows, W, n_fc and n_hyper in the current
+ * arithmetic mode, for 16-byte aligned operands -- host only, no device call; the pointers of `p` are not read.  One bit
+ * per route, from bit 0:
+ *   forward:  t_batched (the re-laid T of every predicted layer in two launches), w_batched (every dense-layer weight
+ *             image in one launch per kind), chained (trunks + trunk-side linear term as chains), ln_fused
+ *   backward: t_batched, w_batched, dual (one contraction for both bilinear input gradients),
+ *             chain (a trunk's backward as one launch, now), chain_queued (... in the batched launch behind the loop;
+ *             neither: layer by layer), dw_deferred (dense weight gradients wait for ONE batched launch), head_dw_queued, head_dw_rows (the head's dense weight gradients: queued, the rows kernel now, or
+ *             neither: generic products), dT_side (the dT launch on the side stream), early_prep (its operands prepared
+ *             per layer on the side stream), dw_side (the batched dense weight gradients on the side stream),
+ *             dw_side_ws (on the main stream over the side workspace; neither: main stream and workspace)
+ * named as HnetFwdRoute / HnetBwdRoute of csrc/hnet.hip.  0 for arguments the calls refuse. */
+uint32_t cgat_debug_hnet_route(int32_t rows, const cgat_hnet_params* p, int32_t backward, int32_t overlapped);
+
+/* ---- dense layer y = act(x W^T + b)  (nn.Linear / 1x1 Conv1d group + activation) --------
  * replaces the Linear/LeakyReLU/ReLU/Tanh pairs of CGAT/message_changed.py:58-63,124-130,
  * CGAT/roost_message.py:348-352 and one head of MultiHeadNetwork (CGAT/CGAT.py:103-109).
  * act: 0 none, 1 tanh, 2 LeakyReLU(0.01), 3 ReLU.  ldx/ldw/ldy are row strides in floats. */
