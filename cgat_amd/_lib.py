@@ -102,6 +102,12 @@ class RowProgOp(C.Structure):
                 ("rowsum", vp)]
 
 
+class EdgeZForm(C.Structure):
+    """cgat_edge_z_form"""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "passes", "adds", "z_bf16", "wide_mode", "groups", "blocks_per_group",
+                                         "grid_x", "tile_rows")]
+
+
 ROWPROG_MAX_OPS = 24
 ROWPROG_SYNC_WORDS = (1024 + 1) * 16
 
@@ -153,6 +159,7 @@ PROTOTYPES = {
     "cgat_debug_nodes_attention_signs_indexed": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, C.c_int32, vp, vp,
                                                            vp, C.c_size_t, vp]),
     "cgat_debug_nodes_attention_route": (C.c_uint32, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
+    "cgat_debug_edge_z_form": (C.c_int, [C.c_int32] * 6 + [C.c_int64] + [C.c_int32] * 5 + [C.POINTER(EdgeZForm)]),
     "cgat_debug_nodes_attention_signs": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, vp]),
     "cgat_debug_edge_ge_rebuilt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "cgat_debug_edge_ge_rebuilt": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp,

@@ -117,8 +117,11 @@ extern "C" int cgat_linear_forward(const float* x, int64_t ldx, const float* w, 
   hipStream_t s = (hipStream_t)stream;
   const bool have_ws = ws && ws_bytes >= cgat_linear_forward_workspace_bytes(M, K, N);
   if (have_ws && (!bias || (((uintptr_t)bias) & 15) == 0)) {
-    if (linear_route_z(K, N, act, ldx, ldy, x, y))
-      return linear128_launch(x, ldx, w, ldw, 1, bias, act, 0, y, ldy, M, ws, s, N);
+    if (linear_route_z(K, N, act, ldx, ldy, x, y)) {
+      Linear128Params l = linear128_params(x, ldx, w, ldw, 1, y, ldy, M, N);
+      l.bias = bias; l.act = act;
+      return linear128_launch(l, ws, s);
+    }
     if (linear_route_ge(K, N, act, ldx, ldy, x, y))
       return edge_ge_launch(x, ldx, 128, w, 1, ldw, (float*)ws, K, y, ldy, nullptr, M, 0, bias, s, x_absmax);
   }
@@ -245,8 +248,10 @@ extern "C" int cgat_heads_linear_backward_dact(const float* x, int64_t ldx, int6
                        (g_b && j == 0) ? g_b + h * s_gb : nullptr};
     if (rows_dw128_batch_fast(b)) {
       // weight seen as out(o = k) x in(n): element W_h[n * ldw + k]  ->  so = 1, sk = ldw
-      CGAT_TRY(linear128_heads_launch(H, g_y, ldgy, s_gy, w, 1, ldw, s_w, nullptr, 0, CGAT_ACT_NONE, 0, g_x, ldgx, s_gx, M, ws,
-                                      s, K, gx_dact, ld_dact, s_dact, gx_absmax));
+      Linear128Params l = linear128_params(g_y, ldgy, w, 1, ldw, g_x, ldgx, M, K);
+      l.dact = gx_dact; l.ld_dact = ld_dact; l.omax = gx_absmax;
+      l.heads = H; l.s_in = s_gy; l.s_w = s_w; l.s_out = s_gx; l.s_dact = s_dact;
+      CGAT_TRY(linear128_heads_launch(l, ws, s));
       return rows_dw128_batch_launch(b, ws, ws_bytes, s);
     }
   }
@@ -275,8 +280,9 @@ static int linear_backward_impl(const float* x, int64_t ldx, const float* w, int
     const bool have_ws = ws && ws_bytes >= cgat_linear_backward_workspace_bytes(M, K, N);
     if (have_ws && N == 128 && linear128_fast(N, K, ldgp, ldgx, gp, g_x)) {
       // weight seen as out(o = k) x in(n): element W[n * ldw + k]  ->  so = 1, sk = ldw
-      CGAT_TRY(linear128_launch(gp, ldgp, w, 1, ldw, nullptr, CGAT_ACT_NONE, accumulate_gx, g_x, ldgx, M, ws, s, K, nullptr,
-                                gx_dact, ld_dact, gx_absmax));
+      Linear128Params l = linear128_params(gp, ldgp, w, 1, ldw, g_x, ldgx, M, K);
+      l.accumulate = accumulate_gx; l.dact = gx_dact; l.ld_dact = ld_dact; l.omax = gx_absmax;
+      CGAT_TRY(linear128_launch(l, ws, s));
     } else if (have_ws && K == 128 && N > 128 && edge_ge_fast(128, N, ldgp, 128, ldgx, gp, g_x)) {
       // inputs n (N of them) -> 128 outputs k: element (col = n, out = k) at W[n * ldw + k]
       CGAT_TRY(edge_ge_launch(gp, ldgp, 128, w, ldw, 1, (float*)ws, N, g_x, ldgx, nullptr, M, accumulate_gx, nullptr, s));

@@ -27,6 +27,7 @@
 // width 128, and the per-edge launch of shapes / modes the wide-tile kernels do not take), edge_z6w_kernel (the per-edge
 // launch of the default 24-bit modes: the same six-pass arithmetic on 256-row workgroups, bit-identical, 3.20 -> 2.84 ms),
 // edge_zx_kernel (f16x3 mode, K = 256).
+#include "../../include/cgat_hip.h"
 #include "common.h"
 #include "kernels.h"
 #include "mfma_bf16.h"
@@ -1040,36 +1041,44 @@ __global__ __launch_bounds__(256) void prepare_W2_f16_kernel(const float* __rest
     }
 }
 
+// =======================================================================================
+// Launchers.  Every launch takes its operands as one record (kernels.h), asks edge_z_form ONCE which kernel runs in which
+// shape, and hands record and form to the one function that expands them into that kernel's argument list.
+// =======================================================================================
+// Every kernel instantiation of this file.  First use decides the order in which the device code is emitted; naming them
+// here, in the order they have always had, keeps the code object byte-identical whatever order the launchers below take.
+[[maybe_unused]] static const void* const k_instantiations[] = {
+    (const void*)edge_zx_kernel<true>, (const void*)edge_zx_kernel<false>,
+    (const void*)edge_z6w_kernel<false, 3>, (const void*)edge_z6w_kernel<true, 0>, (const void*)edge_z6w_kernel<false, 0>,
+    (const void*)edge_z_kernel<2, true>, (const void*)edge_z_kernel<2, false>, (const void*)edge_z_kernel<6, true, true>,
+    (const void*)edge_z_kernel<6, true>, (const void*)edge_z_kernel<6, false>, (const void*)edge_z_kernel<3, true>,
+    (const void*)edge_z_kernel<3, false>, (const void*)edge_z6w_kernel<false, 1>,
+    (const void*)edge_msg_wsum_kernel<true>, (const void*)edge_msg_wsum_kernel<false>};
 size_t edge_zx_wq_floats(int W2) { return (size_t)W2 * 256 + W2 / 128 + 64; }
-bool edge_zx_fast(int C, int Ce, int W2, int H, int Hd, long ld_add, long ldz, const void* e, const void* x,
-                  const void* Pi, const void* Z, const void* wA) {
-  return mode_f16() && C == 128 && Ce == 128 && W2 % 128 == 0 && Hd % 128 == 0 && H * Hd * 2 == W2 &&
-         (ld_add % 4) == 0 && (ldz % 4) == 0 &&
-         ((((uintptr_t)e) | ((uintptr_t)x) | ((uintptr_t)Pi) | ((uintptr_t)Z) | ((uintptr_t)wA)) & 15) == 0;
+bool edge_zx_dims(int C, int Ce, int W2, long ld_add, long ldz) {
+  return mode_f16() && C == 128 && Ce == 128 && W2 % 128 == 0 && (ld_add % 4) == 0 && (ldz % 4) == 0;
 }
 // We / Wj: the edge_attr and x_j slices of the stacked first-layer weight (row stride ldw); Wq: edge_zx_wq_floats(W2)
-int edge_zx_launch(const float* e, long lde, const int* perm, const float* x, long ldx, const float* We, const float* Wj,
-                   long ldw, float* Wq, int W2, const float* Pi, const int* dsti, const int* srci, long ld_add, float* Z,
-                   long ldz, int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream, int z_bf16) {
-  if (E <= 0) return CGAT_OK;
-  const int ncb = W2 / 128;
-  hipLaunchKernelGGL(prepare_W2_f16_kernel, dim3(ncb), dim3(256), 0, stream, We, Wj, ldw, (_Float16*)Wq,
-                     Wq + (size_t)ncb * 32768);
+int edge_zx_launch(const EdgeZParams& p, hipStream_t stream) {
+  if (p.rows <= 0) return CGAT_OK;
+  const int ncb = p.W2 / 128;
+  hipLaunchKernelGGL(prepare_W2_f16_kernel, dim3(ncb), dim3(256), 0, stream, p.We, p.Wj, p.ldw, (_Float16*)p.Wq,
+                     p.Wq + (size_t)ncb * 32768);
   CGAT_LAUNCH_CHECK();
   CGAT_PROF("edge_z", stream);
-#define EZX_GO(ZB_) hipLaunchKernelGGL((edge_zx_kernel<ZB_>), dim3(cdiv(E, 128)), dim3(256), 0, stream, e, lde, perm, x, ldx, (const uint4*)Wq, ncb, Pi, dsti, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out)
-  if (z_bf16) EZX_GO(true);
+#define EZX_GO(ZB_)                                                                                                   \
+  hipLaunchKernelGGL((edge_zx_kernel<ZB_>), dim3(cdiv(p.rows, 128)), dim3(256), 0, stream, p.e, p.lde, p.perm, p.x, p.ldx, \
+                     (const uint4*)p.Wq, ncb, p.Pi, p.dsti, p.srci, p.ld_add, p.Z, p.ldz, p.rows, p.wA, p.bA, p.H,    \
+                     p.Hd / 128, p.a_out)
+  if (p.store == Z_BF16) EZX_GO(true);
   else EZX_GO(false);
 #undef EZX_GO
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
 
-bool edge_z_fast(int Ce, int W2, int H, int Hd, long lde, long ld_add, long ldz, const void* e, const void* Pi,
-                 const void* Pj, const void* Z, const void* wA) {
-  return mode_split() && Ce == 128 && W2 % 128 == 0 && Hd % 128 == 0 && H * Hd * 2 == W2 && (lde % 4) == 0 &&
-         (ld_add % 4) == 0 && (ldz % 4) == 0 &&
-         ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)Z) | ((uintptr_t)wA)) & 15) == 0;
+bool edge_z_dims(int K, int W2, long lde, long ld_add, long ldz) {
+  return mode_split() && K == 128 && W2 % 128 == 0 && (lde % 4) == 0 && (ld_add % 4) == 0 && (ldz % 4) == 0;
 }
 
 // floats of workspace for the pre-split weight
@@ -1077,98 +1086,157 @@ bool edge_z_fast(int Ce, int W2, int H, int Hd, long lde, long ld_add, long ldz,
 // (edgebwd.hip: H * 128 <= W2 / 2 floats at edge_ge_cs_offset)
 size_t edge_ge_cs_offset(int W2) { return (((size_t)W2 * 128 * 3 + 1) / 2 + 3) / 4 * 4; }
 size_t edge_z_wq_floats(int W2) { return edge_ge_cs_offset(W2) + (size_t)W2; }
-static bool edge_z6w_on() {   // CGAT_EDGE_Z6W=0: the 128-row form of the six-pass per-edge launch (A/B switch)
+
+// ---- which kernel runs: the parts of the decision, then the decision ----
+// CGAT_EDGE_Z6W=0: the 128-row form of the six-pass per-edge launch (A/B switch); with it off there is no fused inference
+static bool z6w_on() {
   static const bool on = [] { const char* e = getenv("CGAT_EDGE_Z6W"); return !(e && e[0] == '0'); }();
-  return on;
+  return mode_24bit() && on;
 }
 // CGAT_Z_COL_GROUPS=0: no column groups over grid.y at few row tiles (A/B switch of the bit-identity test, like CGAT_EDGE_Z6W)
 static int z_groups(int row_tiles, int ncb, int unit = 1) {
   static const bool on = [] { const char* e = getenv("CGAT_Z_COL_GROUPS"); return !(e && e[0] == '0'); }();
   return on ? z_col_groups(row_tiles, ncb, unit) : 1;
 }
-
+// Below 128 row tiles of 256 (the harness' shipped 64-crystal batch: 60 - 120 tiles) the 256-row kernels leave CUs idle:
+// the training forward takes the 128-row kernel with column groups instead, the forward without grad deals the column
+// blocks of its own two launches to grid.y groups; CGAT_Z_COL_GROUPS=0 turns both off.
+static bool few_row_tiles(int rows) { return cdiv(rows, 256) < 128; }
+// edge_z6w_kernel's operand limits: fc_out_A's weight within its LDS (hhd_logits: H * Hd of a launch that forms logits,
+// else 0) and 32-bit gather offsets into n_add_rows known rows -- N * 4 * 2 H Hd < 2^32 bytes, kept as a guard rather than
+// widened (100 000 atoms at H * Hd = 2048 use 1.6 GB of it)
+static bool z6w_operands(long hhd_logits, int n_add_rows, long ld_add) {
+  return hhd_logits <= 2048 && n_add_rows > 0 && (long)n_add_rows * 4 * ld_add < (1l << 32);
+}
 // Does the per-edge launch of these dims run edge_z6w_kernel (given gathered addends, a slot permutation and an activation
-// it has): the 24-bit modes, not the few-row form (below 128 of its 256-row tiles -- the harness' shipped batch: 60
-// workgroups walking 12 blocks, 119 us -- the 128-row kernel with its column blocks dealt to grid.y groups fills the chip
-// instead), fc_out_A's weight within the kernel's LDS, 32-bit gather offsets.  hhd_logits: H * Hd of a launch that forms
-// logits, else 0.
+// it has): the 24-bit modes, not the few-row form (the harness' shipped batch: 60 workgroups walking 12 blocks, 119 us --
+// the 128-row kernel with its column blocks dealt to grid.y groups fills the chip instead), and the operand limits.
 static bool z6w_shape(int E, int ncb, int unit_z, bool z_bf16, long hhd_logits, int n_add_rows, long ld_add) {
-  const bool few_rows = !z_bf16 && cdiv(E, 256) < 128 && z_groups(cdiv(E, 128), ncb, unit_z) > 1;
-  return mode_24bit() && edge_z6w_on() && !few_rows && hhd_logits <= 2048 && n_add_rows > 0 &&
-         (long)n_add_rows * 4 * ld_add < (1l << 32);
+  const bool few_rows = !z_bf16 && few_row_tiles(E) && z_groups(cdiv(E, 128), ncb, unit_z) > 1;
+  return z6w_on() && !few_rows && z6w_operands(hhd_logits, n_add_rows, ld_add);
+}
+
+// edge_z_launch, edge_logits_launch (p.Z == null) and, as the plain product of linear128_rows below, the dense layer.
+//   * edge_z6w_kernel: the six-pass per-edge launch on 256-row workgroups (same arithmetic, bit-identical results), where
+//     z6w_shape holds and the launch has what that kernel is written for; the running maximum shares a register with the
+//     logits, so not both.
+//   * edge_z_kernel otherwise.  Few rows beside many column blocks -- at the harness' shipped batch the per-node
+//     projections are 10 workgroups and the per-edge first layer of a vector-attention layer 240, each walking 20 blocks
+//     (149 / 180 us per launch, 2.4 ms of an 18-ms step) -- : the column blocks are dealt to grid.y groups (round 6).  A
+//     workgroup then splits its rows once per group (64 KB, L2-resident) and walks ncb / G blocks; every block is computed
+//     as before: bit-identical.  The 24-bit modes only (the fp16 image keeps its scale behind the LAST block), fp32 storage.
+//     With logits a group holds whole heads: a head's logit is the sum over ITS column blocks only, and the group carries
+//     the number of blocks in front of it (head index, fc_out_A's weight row).
+EdgeZForm edge_z_form(const EdgeZParams& p) {
+  EdgeZForm f = {};
+  if (p.rows <= 0) return f;
+  const int ncb = p.W2 / 128;
+  const bool logits = p.a_out != nullptr;
+  const int unit = logits ? p.Hd / 128 : 1;   // column blocks that stay in one group
+  f.passes = mode_f16() ? 2 : mode_bf16x3() ? 3 : 6;
+  f.adds = p.Pj != nullptr;
+  f.zb = p.store == Z_BF16;
+  f.G = 1;
+  f.ncb_g = ncb;
+  if (!p.Z) {   // logits only: the attention column blocks, in groups of whole heads at few row tiles
+    f.kernel = EZK_ROWS256; f.z6w_mode = 1; f.tile_rows = 256;
+    f.grid_x = cdiv(p.rows, 256);
+    if (few_row_tiles(p.rows)) f.G = z_groups(f.grid_x, p.H * p.Hd / 128, unit);
+    f.ncb_g = p.H * p.Hd / 128 / f.G;
+  } else if (z6w_shape(p.rows, ncb, unit, f.zb, logits ? (long)p.H * p.Hd : 0, p.n_add_rows, p.ld_add) && p.Pj && p.perm &&
+             (p.act == CGAT_ACT_NONE || p.act == CGAT_ACT_LEAKY) && !(p.omax && logits)) {
+    f.kernel = EZK_ROWS256; f.z6w_mode = p.store == Z_BITS ? 3 : 0; f.tile_rows = 256;
+    f.grid_x = cdiv(p.rows, 256);
+  } else {
+    f.kernel = EZK_ROWS128; f.tile_rows = 128;
+    f.grid_x = cdiv(p.rows, 128);
+    if (mode_24bit() && !f.zb) f.G = z_groups(f.grid_x, ncb, unit);
+    f.ncb_g = ncb / f.G;
+  }
+  return f;
+}
+// what edge_z_launch refuses, given the form it would run
+static int edge_z_check(const EdgeZParams& p, const EdgeZForm& f) {
+  CGAT_CHECK_ARG(p.store != Z_BF16 || (p.Pj != nullptr && mode_24bit() && p.act == CGAT_ACT_NONE && !p.omax),
+                 "edge_z: bf16 storage is the per-edge launch of the six-pass form only");
+  CGAT_CHECK_ARG(p.store != Z_BITS || (f.kernel == EZK_ROWS256 && p.Pj && p.perm && p.a_out && p.wA && p.act == CGAT_ACT_NONE &&
+                                       !p.omax && p.ld_add == p.ldz && 2l * p.n_add_rows + cdiv(p.rows, 32) <= (long)p.rows &&
+                                       (long)p.H * p.Hd == p.W2 / 2),
+                 "edge_z: the bit form of the training forward is edge_z6w_kernel's, with logits (edge_z6w_takes)");
+  return CGAT_OK;
+}
+
+// A record of what edge_z_form reads and no more -- dims, storage and which optional operands are PRESENT -- for the
+// questions asked before there are operands (edge_z6w_takes, the debug query).  Never launched.
+static EdgeZParams edge_z_shape(int rows, int W2, int H, int Hd, int n_add_rows, long ld_add, ZStore store, bool adds,
+                                bool logits, bool omax, int act, bool z = true) {
+  alignas(16) static float present_f;
+  static int present_i;
+  EdgeZParams p = {};
+  p.rows = rows; p.W2 = W2; p.H = H; p.Hd = Hd; p.n_add_rows = n_add_rows; p.ld_add = p.ldz = ld_add; p.store = store;
+  p.act = act;
+  p.e = &present_f;
+  if (z) p.Z = &present_f;
+  if (adds) { p.Pi = p.Pj = &present_f; p.perm = p.dsti = p.srci = &present_i; }
+  if (logits) { p.wA = &present_f; p.a_out = &present_f; }
+  if (omax) p.omax = &present_f;
+  return p;
 }
 // ... the fp32 training forward of a scalar-attention layer [E, 2 H Hd] over N nodes, at 128 row tiles or more -- where no
 // switch (CGAT_Z_COL_GROUPS) decides between this kernel and the few-row form (layers.hip: the bit form's predicate)
 bool edge_z6w_takes(int N, int E, int H, int Hd) {
-  const long W2 = 2l * H * Hd;
-  return E > 0 && Hd % 128 == 0 && cdiv(E, 256) >= 128 &&
-         z6w_shape(E, (int)(W2 / 128), Hd / 128, false, (long)H * Hd, N, W2);
+  const int W2 = 2 * H * Hd;
+  return Hd % 128 == 0 && !few_row_tiles(E) &&
+         edge_z_form(edge_z_shape(E, W2, H, Hd, N, W2, Z_F32, true, true, false, CGAT_ACT_NONE)).kernel == EZK_ROWS256;
 }
 
-// We: the edge_attr slice of the stacked first-layer weight, element (out, k) at We[out * ldw + k].
-// With Pj == nullptr the kernel computes the plain product Z = e We^T + bias (Pi = bias vector or nullptr, no logits):
-// the per-node projections of the operand split.
-int edge_z_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
-                  const float* Pi, const int* dsti, const float* Pj, const int* srci, long ld_add, float* Z, long ldz,
-                  int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream, int act,
-                  float* omax, int z_bf16, int n_add_rows, int z_bits) {
-  if (E <= 0) return CGAT_OK;
-  const int ncb = W2 / 128;
-  CGAT_CHECK_ARG(!z_bf16 || (Pj != nullptr && mode_24bit() && act == CGAT_ACT_NONE && !omax),
-                 "edge_z: bf16 storage is the per-edge launch of the six-pass form only");
+// ---- the kernels' argument lists, each expanded here and nowhere else ----
+// per-group offsets of a launch whose grid.y runs over the form's column groups (HeadBatch: w in 16-byte pieces)
+static HeadBatch col_groups(const EdgeZForm& f) {
+  if (f.G == 1) return HeadBatch{};
+  const long c = (long)f.ncb_g * 128;
+  return HeadBatch{0, (long)f.ncb_g * 6144, c, c, c, c, (long)f.ncb_g};
+}
+// grid.y = f.G groups (or heads) whose operands lie hb apart; accumulate / dact / ld_dact: the dense layer's extras
+static void edge_z_rows128(const EdgeZForm& f, const EdgeZParams& p, const HeadBatch& hb, hipStream_t stream,
+                           int accumulate = 0, const float* dact = nullptr, long ld_dact = 0) {
+#define EZ_GO(P_, A_, ZB_)                                                                                            \
+  hipLaunchKernelGGL((edge_z_kernel<P_, A_, ZB_>), dim3(f.grid_x, f.G), dim3(256), 0, stream, p.e, p.lde, p.perm,     \
+                     (const uint4*)p.Wq, f.ncb_g, p.Pi, p.dsti, p.Pj, p.srci, p.ld_add, p.Z, p.ldz, p.rows, p.wA, p.bA, p.H, \
+                     p.Hd / 128, p.a_out, p.act, accumulate, p.omax, dact, ld_dact, hb)
+  if (f.passes == 2) { if (f.adds) EZ_GO(2, true, false); else EZ_GO(2, false, false); }
+  else if (f.passes == 6 && f.zb) EZ_GO(6, true, true);
+  else if (f.passes == 6) { if (f.adds) EZ_GO(6, true, false); else EZ_GO(6, false, false); }
+  else { if (f.adds) EZ_GO(3, true, false); else EZ_GO(3, false, false); }
+#undef EZ_GO
+}
+static void edge_z_rows256(const EdgeZForm& f, const EdgeZParams& p, hipStream_t stream) {
+  // the bit form's holes behind the two half projections: rows 2 N + g of Z
+  unsigned* zbits = f.z6w_mode == 3 ? reinterpret_cast<unsigned*>(p.Z + 2l * p.n_add_rows * p.ldz) : nullptr;
+#define Z6_GO(ZB_, M_)                                                                                                \
+  hipLaunchKernelGGL((edge_z6w_kernel<ZB_, M_>), dim3(f.grid_x, f.G), dim3(512), 0, stream, p.e, p.lde, p.perm,       \
+                     (const uint4*)p.Wq, f.ncb_g, p.Pi, p.dsti, p.Pj, p.srci, p.ld_add, p.Z, p.ldz, p.rows, p.wA, p.bA, p.H, \
+                     p.Hd / 128, p.a_out, p.act, p.omax, zbits)
+  if (f.z6w_mode == 3) Z6_GO(false, 3);
+  else if (f.z6w_mode == 0 && f.zb) Z6_GO(true, 0);
+  else if (f.z6w_mode == 0) Z6_GO(false, 0);
+  else Z6_GO(false, 1);
+#undef Z6_GO
+}
+
+int edge_z_launch(const EdgeZParams& p, hipStream_t stream) {
+  if (p.rows <= 0) return CGAT_OK;
+  const int ncb = p.W2 / 128;
+  const EdgeZForm f = edge_z_form(p);
+  CGAT_TRY(edge_z_check(p, f));
   // operand (a = column block, b = k, c = column in block) = We[(128 a + c) * ldw + b]
   // (We == nullptr: the caller has prepared that image in Wq already, e.g. several slices in one launch)
-  if (!We) {}
-  else if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(We, Wq, ncb, 128 * ldw, 1, ldw, stream));
-  else CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * ldw, 1, ldw, 0, stream));
-  CGAT_PROF(Pj ? "edge_z" : "edge_proj", stream);   // the per-edge launch / the per-node projections
-  // the six-pass per-edge launch on 256-row workgroups (edge_z6w_kernel: same arithmetic, bit-identical results; the
-  // few-row launches take the 128-row kernel below instead: z6w_shape)
-  const bool z6w = z6w_shape(E, ncb, a_out ? Hd / 128 : 1, z_bf16 != 0, a_out ? (long)H * Hd : 0, n_add_rows, ld_add);
-  CGAT_CHECK_ARG(!z_bits || (z6w && !z_bf16 && Pj && perm && a_out && wA && act == CGAT_ACT_NONE && !omax && ld_add == ldz &&
-                             2l * n_add_rows + cdiv(E, 32) <= (long)E && (long)H * Hd == W2 / 2),
-                 "edge_z: the bit form of the training forward is edge_z6w_kernel's, with logits (edge_z6w_takes)");
-  if (z6w && Pj != nullptr && perm && (act == CGAT_ACT_NONE || act == CGAT_ACT_LEAKY) &&
-      !(omax && a_out)) {   // (the running maximum shares a register with the logits)
-    unsigned* none = nullptr;
-    if (z_bits)   // the holes behind the two half projections: rows 2 N + g of Z
-      hipLaunchKernelGGL((edge_z6w_kernel<false, 3>), dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq, ncb,
-                         Pi, dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax,
-                         reinterpret_cast<unsigned*>(Z + 2l * n_add_rows * ldz));
-    else if (z_bf16)
-      hipLaunchKernelGGL(edge_z6w_kernel<true>, dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq, ncb, Pi,
-                         dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax, none);
-    else
-      hipLaunchKernelGGL(edge_z6w_kernel<false>, dim3(cdiv(E, 256)), dim3(512), 0, stream, e, lde, perm, (const uint4*)Wq, ncb, Pi,
-                         dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, omax, none);
-    CGAT_LAUNCH_CHECK();
-    return CGAT_OK;
-  }
-  const int grid = cdiv(E, 128);
-  // Few rows beside many column blocks -- at the harness' shipped batch the per-node projections are 10 workgroups and the
-  // per-edge first layer of a vector-attention layer 240, each walking 20 blocks (149 / 180 us per launch, 2.4 ms of an
-  // 18-ms step) -- : the column blocks are dealt to grid.y groups (round 6).  A workgroup then splits its rows once per group
-  // (64 KB, L2-resident) and walks ncb / G blocks; every block is computed as before: bit-identical.  The 24-bit modes
-  // without logits (the fp16 image keeps its scale behind the LAST block).
-  // With logits (a_out) a group holds whole heads: a head's logit is the sum over ITS column blocks only, and the group
-  // carries the number of blocks in front of it (head index, fc_out_A's weight row).
-  int G = 1;
-  if (mode_24bit() && !z_bf16) G = z_groups(grid, ncb, a_out ? Hd / 128 : 1);
-  const int ncb_g = ncb / G;
-  const HeadBatch hbz = {0, (long)ncb_g * 6144, (long)ncb_g * 128, (long)ncb_g * 128, 0, (long)ncb_g * 128, (long)ncb_g};
-#define EZ_GO(P_, A_)                                                                                                \
-  hipLaunchKernelGGL((edge_z_kernel<P_, A_>), dim3(grid, G), dim3(256), 0, stream, e, lde, perm, (const uint4*)Wq, ncb_g, \
-                     Pi, dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, 0, omax, (const float*)nullptr, 0l, \
-                     G > 1 ? hbz : HeadBatch{})
-  const bool adds = Pj != nullptr;
-  if (mode_f16()) { if (adds) EZ_GO(2, true); else EZ_GO(2, false); }
-  else if (!mode_bf16x3() && z_bf16)
-    hipLaunchKernelGGL((edge_z_kernel<6, true, true>), dim3(grid), dim3(256), 0, stream, e, lde, perm, (const uint4*)Wq, ncb,
-                       Pi, dsti, Pj, srci, ld_add, Z, ldz, E, wA, bA, H, Hd / 128, a_out, act, 0, omax, (const float*)nullptr,
-                       0l, HeadBatch{});
-  else if (!mode_bf16x3()) { if (adds) EZ_GO(6, true); else EZ_GO(6, false); }
-  else { if (adds) EZ_GO(3, true); else EZ_GO(3, false); }
-#undef EZ_GO
+  if (!p.We) {}
+  else if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(p.We, p.Wq, ncb, 128 * p.ldw, 1, p.ldw, stream));
+  else CGAT_TRY(prepare_T_planes_launch(p.We, p.Wq, ncb, 128 * p.ldw, 1, p.ldw, 0, stream));
+  CGAT_PROF(p.Pj ? "edge_z" : "edge_proj", stream);   // the per-edge launch / the per-node projections
+  if (f.kernel == EZK_ROWS256) edge_z_rows256(f, p, stream);
+  else edge_z_rows128(f, p, col_groups(f), stream);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
@@ -1177,65 +1245,65 @@ int edge_z_launch(const float* e, long lde, const int* perm, const float* We, lo
 // The shapes at which edge_z_launch runs the per-edge launch of the 24-bit modes with the six-pass arithmetic (C = Ce =
 // 128, Hd % 128 == 0; as edge_z6w_kernel or, below 128 row tiles of 256, as the 128-row kernel with column groups: the
 // same Z and logits), with
-//   * at most 2048 columns per half (fc_out_A's weight in edge_z6w_kernel's LDS, as in edge_z_launch; the carry of
-//     edge_msg_wsum_kernel stays within its 16 KB by column groups) and at most 8 heads (its alpha staging);
-//   * E * H % 4 == 0;
-//   * 32-bit gather offsets: N * 4 * 2 H Hd < 2^32 bytes, kept as a guard rather than widened (the training forward's
-//     six-pass launch has the same bound; 100 000 atoms at H * Hd = 2048 use 1.6 GB of it).
+//   * edge_z6w_kernel's operand limits at W2 = 2 H Hd (the carry of edge_msg_wsum_kernel stays within its 16 KB by column
+//     groups) and at most 8 heads (its alpha staging);
+//   * E * H % 4 == 0.
 bool edge_infer_fused(int N, int E, int C, int Ce, int H, int Hd) {
   const long HHd = (long)H * Hd;
-  return mode_24bit() && edge_z6w_on() &&
-         C == 128 && Ce == 128 && Hd % 128 == 0 && HHd <= 2048 && H <= 8 && N > 0 && E > 0 &&
+  return z6w_on() && C == 128 && Ce == 128 && Hd % 128 == 0 && H <= 8 && E > 0 &&
          // the training forward's S sits behind Z and alpha in the saved buffer and is 16-byte aligned only when
          // E * H % 4 == 0; otherwise seg_wsum_launch takes its scalar kernel, whose order is not the one built here
-         ((long)E * H) % 4 == 0 &&
-         (long)N * 4 * (2 * HHd) < (1l << 32);
+         ((long)E * H) % 4 == 0 && z6w_operands(HHd, N, 2 * HHd);
 }
-// Below 128 row tiles of 256 (the harness' shipped 64-crystal batch: 60 - 120 tiles) both launches deal their column
-// blocks to grid.y groups, as the training forward's few-row launch does; CGAT_Z_COL_GROUPS=0 turns that off.
-static bool infer_few_rows(int E) { return cdiv(E, 256) < 128; }
-int edge_logits_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
-                       const float* Pi, const int* dsti, const float* Pj, const int* srci, int E, const float* wA,
-                       const float* bA, int H, int Hd, float* a_out, hipStream_t stream) {
-  const int ncb = H * Hd / 128;
-  CGAT_CHECK_ARG(W2 == 2 * H * Hd && Hd % 128 == 0 && H * Hd <= 2048 && (lde % 4) == 0 && wA && a_out && perm &&
-                 ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)wA)) & 15) == 0,
+int edge_logits_launch(const EdgeZParams& p, hipStream_t stream) {
+  CGAT_CHECK_ARG(p.W2 == 2 * p.H * p.Hd && p.Hd % 128 == 0 && p.H * p.Hd <= 2048 && (p.lde % 4) == 0 && p.wA && p.a_out &&
+                 p.perm && !p.Z && aligned16(p.e, p.Pi, p.Pj, p.wA),
                  "edge_logits: needs Hd %% 128 == 0, H * Hd <= 2048, 16-byte aligned rows and fc_out_A's weight");
-  CGAT_TRY(prepare_T_planes_launch(We, Wq, W2 / 128, 128 * ldw, 1, ldw, 0, stream));   // (the whole W2 image: edge_msg_wsum's too)
-  const int G = infer_few_rows(E) ? z_groups(cdiv(E, 256), ncb, Hd / 128) : 1;       // groups of whole heads
+  if (p.rows <= 0) return CGAT_OK;
+  CGAT_TRY(prepare_T_planes_launch(p.We, p.Wq, p.W2 / 128, 128 * p.ldw, 1, p.ldw, 0, stream));   // (the whole W2 image: edge_msg_wsum's too)
   CGAT_PROF("edge_logits", stream);
-  hipLaunchKernelGGL((edge_z6w_kernel<false, 1>), dim3(cdiv(E, 256), G), dim3(512), 0, stream, e, lde, perm,
-                     (const uint4*)Wq, ncb / G, Pi, dsti, Pj, srci, (long)W2, (float*)nullptr, 0l, E, wA, bA, H, Hd / 128,
-                     a_out, CGAT_ACT_NONE, (float*)nullptr, (unsigned*)nullptr);
+  edge_z_rows256(edge_z_form(p), p, stream);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
-// Wq: the image edge_logits_launch made; Pi / Pj: [N, W2] (the message columns are the second half)
-int edge_msg_wsum_launch(const float* e, long lde, const int* perm, const float* Wq, int W2, const float* Pi,
-                         const int* dsti, const float* Pj, const int* srci, int N, int E, int H, int Hd, const float* alpha,
-                         const int* rowptr, float* S, int z_bf16, hipStream_t stream) {
-  const int HHd = H * Hd, ncb = HHd / 128;
-  CGAT_CHECK_ARG(W2 == 2 * HHd && Hd % 128 == 0 && HHd <= 2048 && H <= 8 && (lde % 4) == 0 && perm && N > 0 &&
-                 ((((uintptr_t)e) | ((uintptr_t)Pi) | ((uintptr_t)Pj) | ((uintptr_t)S)) & 15) == 0,
-                 "edge_msg_wsum: needs Hd %% 128 == 0, H * Hd <= 2048, H <= 8 and 16-byte aligned rows");
-  if (E <= 0) return CGAT_OK;
-  // rows per workgroup: a range that starts and ends at segment boundaries is at most R + (longest segment - 1) rows, so
-  // 256 minus the mean in-degree (rounded up to 16) keeps ordinary ranges in one 256-row sub-tile
-  const long deg = cdiv(E, N);
-  const int R = (int)(deg >= 128 ? 128 : 256 - 16 * cdiv(deg, 16));
-  // column groups: to fill the chip at few rows, and at least as many as keep the carry of a long segment's Glong row
-  // groups within WSUM_CARRY floats (the kernel's ncb = ncb / G)
+// rows per workgroup: a range that starts and ends at segment boundaries is at most R + (longest segment - 1) rows, so
+// 256 minus the mean in-degree (rounded up to 16) keeps ordinary ranges in one 256-row sub-tile.
+// column groups: to fill the chip at few rows, and at least as many as keep the carry of a long segment's Glong row
+// groups within WSUM_CARRY floats
+static EdgeZForm edge_msg_wsum_form(const EdgeZParams& p) {
+  EdgeZForm f = {};
+  if (p.rows <= 0) return f;
+  const int HHd = p.H * p.Hd, ncb = HHd / 128;
+  const long deg = cdiv(p.rows, p.N);
+  f.kernel = EZK_MSG_WSUM; f.passes = 6; f.adds = true; f.zb = p.store == Z_BF16;
+  f.tile_rows = (int)(deg >= 128 ? 128 : 256 - 16 * cdiv(deg, 16));
+  f.grid_x = cdiv(p.rows, f.tile_rows);
   const int Glong = 1024 / (HHd / 4 < 256 ? HHd / 4 : 256);
-  int G = infer_few_rows(E) ? z_groups(cdiv(E, R), ncb) : 1;
-  while (ncb % G != 0 || (long)Glong * (ncb / G) * 128 > WSUM_CARRY) ++G;
-  const uint4* Wm = reinterpret_cast<const uint4*>(Wq) + (long)ncb * 6144;   // the message column blocks' image
+  f.G = few_row_tiles(p.rows) ? z_groups(f.grid_x, ncb) : 1;
+  while (ncb % f.G != 0 || (long)Glong * (ncb / f.G) * 128 > WSUM_CARRY) ++f.G;
+  f.ncb_g = ncb / f.G;
+  return f;
+}
+static int edge_msg_wsum_check(const EdgeZParams& p) {
+  CGAT_CHECK_ARG(p.W2 == 2 * p.H * p.Hd && p.Hd % 128 == 0 && p.H * p.Hd <= 2048 && p.H <= 8 && (p.lde % 4) == 0 && p.perm &&
+                 p.N > 0 && aligned16(p.e, p.Pi, p.Pj, p.S),
+                 "edge_msg_wsum: needs Hd %% 128 == 0, H * Hd <= 2048, H <= 8 and 16-byte aligned rows");
+  return CGAT_OK;
+}
+// Wq: the image edge_logits_launch made; Pi / Pj: [N, W2] (the message columns are the second half)
+int edge_msg_wsum_launch(const EdgeZParams& p, hipStream_t stream) {
+  CGAT_TRY(edge_msg_wsum_check(p));
+  if (p.rows <= 0) return CGAT_OK;
+  const int HHd = p.H * p.Hd;
+  const EdgeZForm f = edge_msg_wsum_form(p);
+  const uint4* Wm = reinterpret_cast<const uint4*>(p.Wq) + (long)(HHd / 128) * 6144;   // the message column blocks' image
   CGAT_PROF("edge_msg_wsum", stream);
-  if (z_bf16)
-    hipLaunchKernelGGL(edge_msg_wsum_kernel<true>, dim3(cdiv(E, R), G), dim3(512), 0, stream, e, lde, perm, Wm, ncb / G,
-                       Pi + HHd, dsti, Pj + HHd, srci, (long)W2, H, Hd, alpha, rowptr, N, R, S);
-  else
-    hipLaunchKernelGGL(edge_msg_wsum_kernel<false>, dim3(cdiv(E, R), G), dim3(512), 0, stream, e, lde, perm, Wm, ncb / G,
-                       Pi + HHd, dsti, Pj + HHd, srci, (long)W2, H, Hd, alpha, rowptr, N, R, S);
+#define WSUM_GO(ZB_)                                                                                                  \
+  hipLaunchKernelGGL(edge_msg_wsum_kernel<ZB_>, dim3(f.grid_x, f.G), dim3(512), 0, stream, p.e, p.lde, p.perm, Wm, f.ncb_g, \
+                     p.Pi + HHd, p.dsti, p.Pj + HHd, p.srci, (long)p.W2, p.H, p.Hd, p.alpha, p.rowptr, p.N, f.tile_rows, p.S)
+  if (f.zb) WSUM_GO(true);
+  else WSUM_GO(false);
+#undef WSUM_GO
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
@@ -1246,72 +1314,75 @@ int edge_msg_wsum_launch(const float* e, long lde, const int* perm, const float*
 // Here they run as the one-column-block case of the kernel above (rows split once into registers, 96 KB of weight
 // planes through the LDS-DMA ring).
 bool linear128_fast(int K, int N, long ldi, long ldo, const void* in, const void* out) {
-  return mode_split() && K == 128 && N >= 128 && N % 128 == 0 && (ldi % 4) == 0 && (ldo % 4) == 0 &&
-         ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0;
+  return mode_split() && K == 128 && N >= 128 && N % 128 == 0 && (ldi % 4) == 0 && (ldo % 4) == 0 && aligned16(in, out);
 }
 size_t linear128_ws_bytes(int n_out) { return ws_round((size_t)n_out * 128 * 3 / 2 + 4, 4); }
-int linear128_launch(const float* in, long ldi, const float* W, long so, long sk, const float* bias, int act, int accumulate,
-                     float* out, long ldo, int rows, void* ws, hipStream_t stream, int n_out, const void* prepared,
-                     const float* dact, long ld_dact, float* omax) {
-  if (rows <= 0) return CGAT_OK;
-  const int ncb = n_out / 128;
+// the layer as the per-edge kernel's plain product: e = in, Pi = the bias vector, Z = out, no logits
+static EdgeZParams linear128_rows(const Linear128Params& p, void* image) {
+  EdgeZParams r = {};
+  r.e = p.in; r.lde = p.ldi; r.rows = p.rows;
+  r.Wq = (float*)image; r.W2 = p.n_out;
+  r.Pi = p.bias;
+  r.Z = p.out; r.ldz = p.ldo;
+  r.H = 1; r.Hd = 128;
+  r.act = p.act; r.omax = p.omax;
+  return r;
+}
+int linear128_launch(const Linear128Params& p, void* ws, hipStream_t stream) {
+  if (p.rows <= 0) return CGAT_OK;
+  const int ncb = p.n_out / 128;
   // operand (a = output block, b = k, c = output in block) = W[(128 a + c) * so + b * sk]
   // prepared: the mode's image of this weight made ahead of time (f16x3: prepare_W_f16_batch_launch; the bf16 forms:
   // prepare_T_bf16_batch_launch), n_out == 128 only
-  if (prepared && n_out == 128) ws = const_cast<void*>(prepared);
-  else if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(W, ws, ncb, 128 * so, sk, so, stream));
-  else CGAT_TRY(prepare_T_planes_launch(W, ws, ncb, 128 * so, sk, so, 0, stream));
+  if (p.prepared && p.n_out == 128) ws = const_cast<void*>(p.prepared);
+  else if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(p.W, ws, ncb, 128 * p.so, p.sk, p.so, stream));
+  else CGAT_TRY(prepare_T_planes_launch(p.W, ws, ncb, 128 * p.so, p.sk, p.so, 0, stream));
   CGAT_PROF("linear128", stream);
-  const int grid = cdiv(rows, 128);
-  // (column blocks over grid.y when the row tiles leave CUs idle: edge_z_launch above)
-  const int G = mode_24bit() ? z_groups(grid, ncb) : 1;
-  const int ncb_g = ncb / G;
-  const HeadBatch hbz = {0, (long)ncb_g * 6144, (long)ncb_g * 128, (long)ncb_g * 128, (long)ncb_g * 128, 0};
-#define L128_GO(P_)                                                                                                   \
-  hipLaunchKernelGGL((edge_z_kernel<P_, false>), dim3(grid, G), dim3(256), 0, stream, in, ldi, (const int*)nullptr,   \
-                     (const uint4*)ws, ncb_g, bias, (const int*)nullptr, (const float*)nullptr, (const int*)nullptr, 0l, \
-                     out, ldo, rows, (const float*)nullptr, (const float*)nullptr, 1, 1, (float*)nullptr, act, accumulate, \
-                     omax, dact, ld_dact, G > 1 ? hbz : HeadBatch{})
-  if (mode_f16()) L128_GO(2); else if (!mode_bf16x3()) L128_GO(6); else L128_GO(3);
-#undef L128_GO
+  const EdgeZParams r = linear128_rows(p, ws);
+  const EdgeZForm f = edge_z_form(r);   // (column blocks over grid.y when the row tiles leave CUs idle)
+  edge_z_rows128(f, r, col_groups(f), stream, p.accumulate, p.dact, p.ld_dact);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
 
-// The same product for `heads` independent (input, weight, output) triples in ONE launch pair (f16x3 mode): head h
-// reads in + h * s_in, W + h * s_w (the same (so, sk) element strides), bias + h * s_bias, dact + h * s_dact and writes
+// The same product for `heads` independent (input, weight, output) triples in ONE launch pair: head h reads
+// in + h * s_in, W + h * s_w (the same (so, sk) element strides), bias + h * s_bias, dact + h * s_dact and writes
 // out + h * s_out.  The per-head second layers of a vector-attention layer at the harness' shipped batch are 2 H chains
 // of [prepare, product] launches of 20-40 us each that fill a fraction of the chip; as grid.y they are one.
 // ws: heads * linear128_heads_image_floats(n_out) floats.
 // (sized for the six-pass image: three bf16 planes per 128 x 128 block)
 size_t linear128_heads_image_floats(int n_out) { return (size_t)(n_out / 128) * 24576 + ((n_out / 128 + 3) & ~3); }
-int linear128_heads_launch(int heads, const float* in, long ldi, long s_in, const float* W, long so, long sk, long s_w,
-                           const float* bias, long s_bias, int act, int accumulate, float* out, long ldo, long s_out, int rows,
-                           void* ws, hipStream_t stream, int n_out, const float* dact, long ld_dact, long s_dact,
-                           float* omax) {
-  if (rows <= 0 || heads <= 0) return CGAT_OK;
-  CGAT_CHECK_ARG((mode_f16() || mode_24bit()) && n_out % 128 == 0,
+int linear128_heads_launch(const Linear128Params& p, void* ws, hipStream_t stream) {
+  if (p.rows <= 0 || p.heads <= 0) return CGAT_OK;
+  CGAT_CHECK_ARG((mode_f16() || mode_24bit()) && p.n_out % 128 == 0,
                  "linear128_heads: split arithmetic modes and 128-wide output blocks only");
-  const int ncb = n_out / 128;
-  const long img = (long)linear128_heads_image_floats(n_out);
-  if (!mode_f16()) {     // the 24-bit modes (round 6): one image launch for all heads, one six-pass product launch
-    CGAT_TRY(prepare_T_planes_launch(W, ws, ncb, 128 * so, sk, so, 0, stream, nullptr, heads, s_w, img));
-    CGAT_PROF("linear128", stream);
-    const HeadBatch hb6 = {s_in, img / 4, s_bias, s_out, s_dact};
-    hipLaunchKernelGGL((edge_z_kernel<6, false>), dim3(cdiv(rows, 128), heads), dim3(256), 0, stream, in, ldi,
-                       (const int*)nullptr, (const uint4*)ws, ncb, bias, (const int*)nullptr, (const float*)nullptr,
-                       (const int*)nullptr, 0l, out, ldo, rows, (const float*)nullptr, (const float*)nullptr, 1, 1,
-                       (float*)nullptr, act, accumulate, omax, dact, ld_dact, hb6);
-    CGAT_LAUNCH_CHECK();
-    return CGAT_OK;
-  }
-  CGAT_TRY(prepare_W_f16_launch(W, ws, ncb, 128 * so, sk, so, stream, heads, s_w, img));
+  const int ncb = p.n_out / 128;
+  const long img = (long)linear128_heads_image_floats(p.n_out);
+  // one image launch for all heads (the 24-bit modes, round 6: the six-pass image), one product launch
+  if (mode_f16()) CGAT_TRY(prepare_W_f16_launch(p.W, ws, ncb, 128 * p.so, p.sk, p.so, stream, p.heads, p.s_w, img));
+  else CGAT_TRY(prepare_T_planes_launch(p.W, ws, ncb, 128 * p.so, p.sk, p.so, 0, stream, nullptr, p.heads, p.s_w, img));
   CGAT_PROF("linear128", stream);
-  const HeadBatch hb = {s_in, img / 4, s_bias, s_out, s_dact};
-  hipLaunchKernelGGL((edge_z_kernel<2, false>), dim3(cdiv(rows, 128), heads), dim3(256), 0, stream, in, ldi,
-                     (const int*)nullptr, (const uint4*)ws, ncb, bias, (const int*)nullptr, (const float*)nullptr,
-                     (const int*)nullptr, 0l, out, ldo, rows, (const float*)nullptr, (const float*)nullptr, 1, 1,
-                     (float*)nullptr, act, accumulate, omax, dact, ld_dact, hb);
+  const EdgeZParams r = linear128_rows(p, ws);
+  EdgeZForm f = edge_z_form(r);
+  f.G = p.heads; f.ncb_g = ncb;         // grid.y runs over the heads, each over all its column blocks: no column groups
+  edge_z_rows128(f, r, HeadBatch{p.s_in, img / 4, p.s_bias, p.s_out, p.s_dact}, stream, p.accumulate, p.dact, p.ld_dact);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
+
+// debug (include/cgat_hip.h): the form of a launch of these dims, storage and present operands in the current mode
+extern "C" int cgat_debug_edge_z_form(int32_t launch, int32_t rows, int32_t W2, int32_t H, int32_t Hd, int32_t n_add_rows,
+                                      int64_t ld_add, int32_t store, int32_t adds, int32_t logits, int32_t omax,
+                                      int32_t act, cgat_edge_z_form* out) {
+  CGAT_CHECK_ARG(out && launch >= 0 && launch <= 2 && store >= Z_F32 && store <= Z_BITS && rows >= 0 && W2 > 0 &&
+                 W2 % 128 == 0 && H > 0 && Hd > 0, "debug_edge_z_form: bad arguments");
+  EdgeZParams p = edge_z_shape(rows, W2, H, Hd, n_add_rows, ld_add, (ZStore)store, adds != 0 || launch != 0,
+                               logits != 0 || launch == 1, omax != 0, act, launch == 0);
+  p.N = n_add_rows;
+  EdgeZForm f;
+  if (launch == 2) { CGAT_TRY(edge_msg_wsum_check(p)); f = edge_msg_wsum_form(p); }
+  else { f = edge_z_form(p); if (launch == 0) CGAT_TRY(edge_z_check(p, f)); }
+  *out = {f.kernel, f.passes, f.adds, f.zb, f.z6w_mode, f.G, f.ncb_g, f.grid_x, f.tile_rows};
+  return CGAT_OK;
+}
+

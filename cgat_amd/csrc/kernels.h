@@ -172,27 +172,73 @@ int permute3_launch(const float* src, float* dst, int n0, int n1, int n2, int pe
 // (the batched weight images of the dense layers: below, beside WPrepBatch)
 
 // ---- fused edge pre-activations + attention logits, edgez.hip ----
-bool edge_z_fast(int Ce, int W2, int H, int Hd, long lde, long ld_add, long ldz, const void* e, const void* Pi,
-                 const void* Pj, const void* Z, const void* wA);
+// 16-byte test of a caller's own pointers (null passes); the dims / leading-dimension / mode half of each predicate is
+// a function of its own below
+template <typename... P>
+static inline bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15) == 0; }
+enum ZStore : int { Z_F32 = 0, Z_BF16 = 1, Z_BITS = 2 };
+// Operands of the per-edge family: edge_z_launch, edge_zx_launch, edge_logits_launch, edge_msg_wsum_launch.
+//     Z[t, :] = act(We e[perm[t]] + Pi[dsti[t]] + Pj[srci[t]]),   a_out[t, h] = bA[h] + sum_j leaky(Z[t, h Hd + j]) wA[h Hd + j]
+struct EdgeZParams {
+  const float* e;        // the rows operand [rows, 128], row stride lde
+  long lde;
+  const int* perm;       // row t reads e[perm[t]] (null: e[t])
+  int rows;
+  const float* We;       // weight, element (out, k) at We[out * ldw + k]; null: Wq already holds the current mode's image
+  long ldw;              //   (prepare_T_planes_launch / prepare_W_f16_launch with edge_z_launch's strides) and is only read
+  float* Wq;             // the weight image: edge_z_wq_floats(W2) (edge_zx_launch: edge_zx_wq_floats(W2))
+  int W2;                // output columns
+  const float* Pi;       // first addend, gathered by dsti; with Pj == null: a bias vector [W2] or null (the plain product)
+  const int* dsti;
+  const float* Pj;       // second addend, gathered by srci
+  const int* srci;
+  long ld_add;           // row stride of Pi and Pj
+  int n_add_rows;        // rows of Pi / Pj.  0 = unknown: never the 256-row kernel, which addresses them by 32-bit offsets
+  float* Z;              // output, row stride ldz in elements whatever the storage; null: logits only (edge_logits_launch)
+  long ldz;
+  ZStore store;          // Z_BF16: Z stored as bf16; Z_BITS: the attention columns leave sign words in the holes of rows
+                         // 2 n_add_rows + g of Z instead of values (edge_z6w_kernel<false, 3>; layers.hip attn_z_form)
+  const float* wA;       // the logits: fc_out_A's weight [H * Hd] and bias [H] (nullable), a_out [rows, H] (null: none)
+  const float* bA;
+  int H, Hd;
+  float* a_out;
+  int act;               // CGAT_ACT_*
+  float* omax;           // max |Z| folded into omax[0] (not zeroed here)
+  // edge_zx_launch: the x_j projection folded in (f16x3 mode, C == Ce == 128)
+  const float* x;        // [N, 128], row stride ldx, gathered by srci
+  long ldx;
+  const float* Wj;       // the x_j slice of the stacked weight (row stride ldw)
+  // edge_msg_wsum_launch: S[n, :] = sum over the rows of segment n of alpha[t, h] leaky(z_M[t, :])
+  int N;
+  const float* alpha;    // [rows, H]
+  const int* rowptr;     // [N + 1]
+  float* S;              // [N, H * Hd]
+};
+// Which kernel a launch of this family runs, with its template arguments and its grid: decided once per launch by
+// edge_z_form (host only; DESIGN.md lists the forms) and read by the launcher, the predicates below and the debug query.
+enum EdgeZKernel : int { EZK_NONE = 0, EZK_ROWS128 = 1, EZK_ROWS256 = 2, EZK_MSG_WSUM = 3 };
+struct EdgeZForm {
+  EdgeZKernel kernel;    // edge_z_kernel (128-row workgroups) / edge_z6w_kernel (256-row) / edge_msg_wsum_kernel; none: no rows
+  int passes;            // 2 (two fp16 planes), 3 or 6 (three bf16 planes)
+  bool adds;             // edge_z_kernel<., ADDS, .>: gathered addends
+  bool zb;               // Z stored (edge_msg_wsum_kernel: rounded) as bf16
+  int z6w_mode;          // edge_z6w_kernel<., MODE>: 0 training forward, 3 its bit form, 1 logits only
+  int G, ncb_g;          // grid.y column groups and the column blocks of each (G == 1: no groups)
+  int grid_x, tile_rows; // row tiles, and the rows of each: 128, 256, or edge_msg_wsum_kernel's R
+};
+EdgeZForm edge_z_form(const EdgeZParams& p);
+// the kernels' dims, leading dimensions and mode: K == 128 inputs, whole 128-column blocks, float4 rows
+bool edge_z_dims(int K, int W2, long lde, long ld_add, long ldz);
+// ... of a launch over the two stacked networks of H heads: a head is whole column blocks
+static inline bool edge_z_heads(int W2, int H, int Hd) { return Hd % 128 == 0 && H * Hd * 2 == W2; }
 size_t edge_ge_cs_offset(int W2);  // floats in front of those column sums
 size_t edge_z_wq_floats(int W2);   // the three-plane image, then W2 floats for the column sums of edge_ge's bit-plane form
 // per-edge launch with the x_j projection folded in (f16x3 mode, C == Ce == 128): edgez.hip edge_zx_kernel
 size_t edge_zx_wq_floats(int W2);
-bool edge_zx_fast(int C, int Ce, int W2, int H, int Hd, long ld_add, long ldz, const void* e, const void* x,
-                  const void* Pi, const void* Z, const void* wA);
-int edge_zx_launch(const float* e, long lde, const int* perm, const float* x, long ldx, const float* We, const float* Wj,
-                   long ldw, float* Wq, int W2, const float* Pi, const int* dsti, const int* srci, long ld_add, float* Z,
-                   long ldz, int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream,
-                   int z_bf16 = 0);   // z_bf16: Z stored as bf16 (ldz in elements either way)
-// (We == nullptr: Wq already holds the image of the current mode -- prepare_T_planes_launch / prepare_W_f16_launch with
-// this function's strides -- and is only read)
-int edge_z_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
-                  const float* Pi, const int* dsti, const float* Pj, const int* srci, long ld_add, float* Z, long ldz,
-                  int E, const float* wA, const float* bA, int H, int Hd, float* a_out, hipStream_t stream,
-                  int act = CGAT_ACT_NONE, float* omax = nullptr, int z_bf16 = 0,   // z_bf16: as edge_zx_launch
-                  int n_add_rows = 0,    // rows of Pi / Pj (0 = unknown: the f16x3c kernel addresses them by 32-bit offsets)
-                  int z_bits = 0);       // the bit form (edge_z6w_kernel<false, 3>): the attention columns leave sign words in
-                                         // the holes of rows 2 N + g of Z instead of values (layers.hip attn_z_form)
+bool edge_zx_dims(int C, int Ce, int W2, long ld_add, long ldz);
+int edge_zx_launch(const EdgeZParams& p, hipStream_t stream);   // reads We, Wj, x; stores fp32 or bf16
+// With Pj == null the kernel computes the plain product Z = e We^T + bias: the per-node projections of the operand split
+int edge_z_launch(const EdgeZParams& p, hipStream_t stream);
 // would the fp32 training forward of a scalar-attention layer run edge_z6w_kernel (mode, switches, shape; host only)
 bool edge_z6w_takes(int N, int E, int H, int Hd);
 // Per-head offsets of a launch whose grid.y runs over the heads of a multi-head second layer (elements of each operand;
@@ -217,12 +263,8 @@ static inline int z_col_groups(int row_tiles, int ncb, int unit = 1) {
 // blocks, no Z) and the message blocks reduced straight into S[N, H * Hd] = the softmax-weighted segment sums that
 // seg_wsum_launch forms from Z, bit-identical.  edge_infer_fused: the host-only predicate of shapes, mode and storage.
 bool edge_infer_fused(int N, int E, int C, int Ce, int H, int Hd);
-int edge_logits_launch(const float* e, long lde, const int* perm, const float* We, long ldw, float* Wq, int W2,
-                       const float* Pi, const int* dsti, const float* Pj, const int* srci, int E, const float* wA,
-                       const float* bA, int H, int Hd, float* a_out, hipStream_t stream);
-int edge_msg_wsum_launch(const float* e, long lde, const int* perm, const float* Wq, int W2, const float* Pi,
-                         const int* dsti, const float* Pj, const int* srci, int N, int E, int H, int Hd, const float* alpha,
-                         const int* rowptr, float* S, int z_bf16, hipStream_t stream);
+int edge_logits_launch(const EdgeZParams& p, hipStream_t stream);    // Z == null; makes the whole W2 image in Wq
+int edge_msg_wsum_launch(const EdgeZParams& p, hipStream_t stream);  // Wq: that image; Pi / Pj: [N, W2]; store Z_BF16: z rounded
 // ---- the same per-edge phase for edge_attr = table[idx] of R rows (shell-indexed edge features), edgeidx.hip ----
 // Te [R, W2] = table W_e^T (no bias); idx [E] int64 in original edge order, reached through perm; Pi / Pj [N, W2].
 // Gathers and fp32 VALU only: any arithmetic mode, any E.  edge_idx_ok: the host-only predicate of the shapes.
@@ -272,10 +314,6 @@ int edge_idx_hidden_launch(const float* Te, int R, const int64_t* idx, const int
 int edge_idx_signs_launch(const float* Te, int R, const int64_t* idx, const int* perm, const float* Pi, const float* Pj,
                           const int* srci, const int* dsti, int W2, long E, uint8_t* mask, hipStream_t stream);
 size_t linear128_heads_image_floats(int n_out);
-int linear128_heads_launch(int heads, const float* in, long ldi, long s_in, const float* W, long so, long sk, long s_w,
-                           const float* bias, long s_bias, int act, int accumulate, float* out, long ldo, long s_out, int rows,
-                           void* ws, hipStream_t stream, int n_out, const float* dact, long ld_dact, long s_dact,
-                           float* omax);
 // batched form for 128 x 128 dense-layer weights W(o, k) = src[o * so + k * sk]: image i at dst + i * WPREP_IMAGE_FLOATS
 #define WPREP_MAX 48
 #define WPREP_IMAGE_FLOATS (16384 + 4)
@@ -295,11 +333,36 @@ int prepare_T_bf16_rows_launch(const float* rows, long ld, const int* gather, in
 // dense layer at width 128 on the split-bf16 kernel: out = act(in W^T + bias) (+ out),  W(o, k) = W[o*so + k*sk]
 bool linear128_fast(int K, int N, long ldi, long ldo, const void* in, const void* out);
 size_t linear128_ws_bytes(int n_out = 128);
-int linear128_launch(const float* in, long ldi, const float* W, long so, long sk, const float* bias, int act, int accumulate,
-                     float* out, long ldo, int rows, void* ws, hipStream_t stream, int n_out = 128,
-                     const void* prepared = nullptr,    // prepared: image from prepare_W_f16_batch_launch (f16x3, n_out 128)
-                     const float* dact = nullptr, long ld_dact = 0,   // out *= LeakyReLU'(sign of dact[row, col])
-                     float* omax = nullptr);            // max |out| folded into omax[0] (not zeroed here)
+struct Linear128Params {
+  const float* in;       // [rows, 128], row stride ldi
+  long ldi;
+  const float* W;        // element (o, k) at W[o * so + k * sk]
+  long so, sk;
+  const float* bias;     // [n_out] or null
+  int act;               // CGAT_ACT_*
+  int accumulate;        // out += result
+  float* out;            // [rows, n_out], row stride ldo
+  long ldo;
+  int rows, n_out;
+  const void* prepared;  // the mode's image of W made ahead (prepare_W_f16_batch_launch / prepare_T_bf16_batch_launch), n_out == 128
+  const float* dact;     // out *= LeakyReLU'(sign of dact[row, col]), row stride ld_dact; null: none
+  long ld_dact;
+  float* omax;           // max |out| folded into omax[0] (not zeroed here)
+  // linear128_heads_launch: `heads` independent (in, W, bias, out, dact) in one launch pair, head h at + h * s_*
+  // (elements).  heads == 1 with zero strides: the single-operand launch
+  int heads;
+  long s_in, s_w, s_bias, s_out, s_dact;
+};
+static inline Linear128Params linear128_params(const float* in, long ldi, const float* W, long so, long sk, float* out,
+                                               long ldo, int rows, int n_out = 128) {
+  Linear128Params p = {};
+  p.in = in; p.ldi = ldi; p.W = W; p.so = so; p.sk = sk; p.out = out; p.ldo = ldo; p.rows = rows; p.n_out = n_out;
+  p.heads = 1;
+  return p;
+}
+int linear128_launch(const Linear128Params& p, void* ws, hipStream_t stream);
+// ws: heads * linear128_heads_image_floats(n_out) floats; the f16x3 and 24-bit modes
+int linear128_heads_launch(const Linear128Params& p, void* ws, hipStream_t stream);
 // ---- a chain of width-128 dense layers in one launch (f16x3 mode), chain.hip ----
 #define CHAIN_MAX 5
 struct ChainLayer {

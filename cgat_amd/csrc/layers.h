@@ -88,8 +88,10 @@ struct Ctx {
     if (rowprog_gemm_ok(p)) return rowprog_gemm(p, s);
     if (dense128 && linear128_fast(p.K, p.N, p.lda, p.ldc, p.A, p.C) && scratch_bytes >= linear128_ws_bytes(p.N)) {
       const long so = p.b_kmajor ? 1 : p.ldb, sk = p.b_kmajor ? p.ldb : 1;
-      return linear128_launch(p.A, p.lda, p.B, so, sk, p.bias, p.act, p.beta == 1.f, p.C, p.ldc, p.M, scratch, s, p.N,
-                              p.N != 128 ? nullptr : (mode_f16() ? wprep_find(p.B, so, sk) : tprep_find(p.B, so, sk)));
+      Linear128Params l = linear128_params(p.A, p.lda, p.B, so, sk, p.C, p.ldc, p.M, p.N);
+      l.bias = p.bias; l.act = p.act; l.accumulate = p.beta == 1.f;
+      l.prepared = p.N != 128 ? nullptr : (mode_f16() ? wprep_find(p.B, so, sk) : tprep_find(p.B, so, sk));
+      return linear128_launch(l, scratch, s);
     }
     return gemm_launch(p, scratch, scratch_bytes, s);
   }
@@ -175,10 +177,7 @@ static int run_sized(const char* who, void* ws, size_t ws_bytes, void* stream, I
 // generic steps, and the scratch a fast route needs is asked for by dims alone where that route runs (so the real pass
 // tests no scratch size: run_sized has refused a workspace smaller than the dry pass measured).
 // `ws` stands for a pass' workspace carve-outs in the kernels' 16-byte tests: Workspace::take places every one a multiple
-// of 256 bytes behind the caller's base, so any of them passes exactly when all do.
-static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
-}
+// of 256 bytes behind the caller's base, so any of them passes exactly when all do (aligned16: kernels.h).
 
 // debug: a route as a bit mask (include/cgat_hip.h), bit i = the i-th flag
 static uint32_t route_bits(std::initializer_list<bool> on) {

@@ -104,9 +104,10 @@ static bool attn_bit_form_dims(const AttnDims& d) {
 }
 static ZForm attn_z_form(const AttnDims& d, const float* e, const float* x, const float* Z, const float* wA, const void* ws) {
   ZForm z;
-  z.zx = d.N > 0 && edge_zx_fast(d.C, d.Ce, d.W2, d.H, d.Hd, d.W2, d.W2, e, x, ws, Z, wA) &&
-         edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, ws, ws, ws, ws);
-  const bool per_edge = edge_z_fast(d.Ce, d.W2, d.H, d.Hd, d.Ce, d.W2, d.W2, e, ws, ws, Z, wA);
+  const bool heads = edge_z_heads(d.W2, d.H, d.Hd);
+  z.zx = d.N > 0 && heads && edge_zx_dims(d.C, d.Ce, d.W2, d.W2, d.W2) && aligned16(e, x, ws, Z, wA) &&
+         edge_z_dims(d.C, d.W2, d.C, d.W2, d.W2);       // (the projection Pi on the per-edge kernel)
+  const bool per_edge = heads && edge_z_dims(d.Ce, d.W2, d.Ce, d.W2, d.W2) && aligned16(e, ws, Z, wA);
   z.fused_z = per_edge && !z.zx;
   z.bf16_six = attn_bf16(d) && per_edge && !mode_f16();
   z.bf16 = (attn_bf16(d) && z.zx) || z.bf16_six;
@@ -154,7 +155,8 @@ static AttnFwdRoute attn_fwd_route(bool dry, const AttnDims& d, bool infer, cons
   r.zx = z.zx; r.fused_z = z.fused_z; r.z_bf16 = z.bf16; r.z_bits = z.bits;
   // (a few hundred atoms: the generic branch, whose products run as 16 x 16 wave tiles -- rowprog.hip -- instead of
   // five 256-row workgroups streaming the whole weight image: 86 -> ~10 us per projection at 1 280 atoms)
-  r.proj_fast = d.N > rowprog_max_rows() && edge_z_fast(d.C, d.W2, d.H, d.Hd, d.C, d.W2, d.W2, x, ws, ws, ws, ws);
+  r.proj_fast = d.N > rowprog_max_rows() && edge_z_heads(d.W2, d.H, d.Hd) && edge_z_dims(d.C, d.W2, d.C, d.W2, d.W2) &&
+                aligned16(x, ws);
   r.out_one = attn_out_one_shape(d) && edge_ge_fast(128, d.HHd, d.HHd, 128, d.C, S, aggr) && aligned16(p->M_out_w);
   return r;
 }
@@ -232,15 +234,23 @@ static AttnFwd attn_fwd_carve(Ctx& c, const cgat_plan* plan, const cgat_attn_par
 // Pi = x W_i^T + bias, Pj = x W_j^T of the stacked weight W [W2, D]: two launches of the per-edge kernel, or the GEMM pair
 // (which forms Pj whether or not the per-edge phase reads it)
 struct NodeProj { float *Pi, *Pj, *Wq; };
+// the plain product [N, C] -> [N, W2] of the per-edge kernel: no gathered addends, no logits; weight and output to be set
+static EdgeZParams node_proj_params(const AttnDims& d, const float* x, float* Wq) {
+  EdgeZParams z = {};
+  z.e = x; z.lde = d.C; z.rows = d.N;
+  z.Wq = Wq; z.W2 = d.W2; z.ldz = d.W2;
+  z.H = d.H; z.Hd = d.Hd;
+  return z;
+}
 static int node_projections(Ctx& c, const AttnDims& d, bool fast, bool need_Pj, const float* x, const float* W,
                             const float* bias, const NodeProj& o) {
   float *Pi = o.Pi, *Pj = o.Pj, *Wq = o.Wq;
   if (fast) {
-    RUN(edge_z_launch(x, d.C, nullptr, W, d.D, Wq, d.W2, bias, nullptr, nullptr, nullptr, 0, Pi, d.W2, d.N, nullptr,
-                      nullptr, d.H, d.Hd, nullptr, c.s));
-    if (need_Pj)
-      RUN(edge_z_launch(x, d.C, nullptr, W + d.C + d.Ce, d.D, Wq, d.W2, nullptr, nullptr, nullptr, nullptr, 0, Pj, d.W2,
-                        d.N, nullptr, nullptr, d.H, d.Hd, nullptr, c.s));
+    EdgeZParams z = node_proj_params(d, x, Wq);
+    z.We = W; z.ldw = d.D; z.Pi = bias; z.Z = Pi;
+    RUN(edge_z_launch(z, c.s));
+    z.We = W + d.C + d.Ce; z.Pi = nullptr; z.Z = Pj;
+    if (need_Pj) RUN(edge_z_launch(z, c.s));
     return CGAT_OK;
   }
   GemmParams g = gemm_params(d.N, d.W2, d.C, x, d.C, W, d.D, Pi, d.W2);
@@ -250,17 +260,29 @@ static int node_projections(Ctx& c, const AttnDims& d, bool fast, bool need_Pj, 
   return c.gemm(g);
 }
 
+// the per-edge operands of both forwards: edge rows in slot order, W_e, the two gathered projections, the logits
+static EdgeZParams attn_edge_params(const AttnFwd& f) {
+  const AttnDims& d = f.d;
+  EdgeZParams z = {};
+  z.e = f.e; z.lde = d.Ce; z.perm = f.plan->dst_perm; z.rows = d.E;
+  z.We = f.Wcat + d.C; z.ldw = d.D; z.Wq = f.Wq; z.W2 = d.W2;
+  z.Pi = f.Pi; z.dsti = f.plan->dst_sorted; z.Pj = f.Pj; z.srci = f.plan->src_sorted; z.ld_add = d.W2; z.n_add_rows = d.N;
+  z.wA = f.p->A_out_w; z.bA = f.p->A_out_b; z.H = d.H; z.Hd = d.Hd; z.a_out = f.a;
+  return z;
+}
+
 // logits, softmax (the same launch as the training forward's), message columns summed straight into S
 static int attn_fwd_edges_infer(Ctx& c, const AttnFwd& f) {
   const AttnDims& d = f.d;
   const cgat_plan* plan = f.plan;
   CGAT_CHECK_ARG(aligned16(f.e, f.Pi, f.Pj) && aligned16(f.p->A_out_w),
                  "nodes_attention_infer: edge_attr and MH_A.fc_out.weight must be 16-byte aligned");
-  RUN(edge_logits_launch(f.e, d.Ce, plan->dst_perm, f.Wcat + d.C, d.D, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj,
-                         plan->src_sorted, d.E, f.p->A_out_w, f.p->A_out_b, d.H, d.Hd, f.a, c.s));
+  EdgeZParams z = attn_edge_params(f);   // Z stays null: nothing of size E x W2 is formed
+  RUN(edge_logits_launch(z, c.s));
   RUN(seg_softmax_fwd_launch(f.a, nullptr, plan->dst_rowptr, d.N, d.H, 1e-16f, f.sv.alpha, f.sv.ssum, c.s));
-  RUN(edge_msg_wsum_launch(f.e, d.Ce, plan->dst_perm, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj, plan->src_sorted, d.N, d.E,
-                           d.H, d.Hd, f.sv.alpha, plan->dst_rowptr, f.sv.S, attn_bf16(d) ? 1 : 0, c.s));
+  z.N = d.N; z.alpha = f.sv.alpha; z.rowptr = plan->dst_rowptr; z.S = f.sv.S;
+  z.store = attn_bf16(d) ? Z_BF16 : Z_F32;
+  RUN(edge_msg_wsum_launch(z, c.s));
   return CGAT_OK;
 }
 
@@ -285,10 +307,11 @@ static int attn_fwd_edges_train(Ctx& c, const AttnFwd& f) {
     return CGAT_ERR_UNSUPPORTED;
   }
   const int zb = r.z_bf16 ? 1 : 0;
+  EdgeZParams z = attn_edge_params(f);
+  z.Z = sv.Z; z.ldz = d.W2; z.store = r.z_bits ? Z_BITS : r.z_bf16 ? Z_BF16 : Z_F32;
   if (r.zx) {
-    RUN(edge_zx_launch(f.e, d.Ce, plan->dst_perm, f.x, d.C, f.Wcat + d.C, f.Wcat + d.C + d.Ce, d.D, f.Wq, d.W2, f.Pi,
-                       plan->dst_sorted, plan->src_sorted, d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, f.a, c.s,
-                       zb));
+    z.x = f.x; z.ldx = d.C; z.Wj = f.Wcat + d.C + d.Ce;
+    RUN(edge_zx_launch(z, c.s));
   } else if (r.fused_z) {
     if (r.z_bits) {   // the attention halves of the two projections into the holes of rows 0 .. 2 N - 1 (ZForm)
       Copy2DJobs j;
@@ -297,9 +320,7 @@ static int attn_fwd_edges_train(Ctx& c, const AttnFwd& f) {
       j.job[1] = {f.Pj, d.W2, sv.Z + (size_t)d.N * d.W2, d.W2, d.N, d.HHd};
       RUN(copy2d_multi_launch(j, c.s));
     }
-    RUN(edge_z_launch(f.e, d.Ce, plan->dst_perm, f.Wcat + d.C, d.D, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj,
-                      plan->src_sorted, d.W2, sv.Z, d.W2, d.E, p->A_out_w, p->A_out_b, d.H, d.Hd, f.a, c.s, CGAT_ACT_NONE,
-                      nullptr, zb, d.N, r.z_bits ? 1 : 0));
+    RUN(edge_z_launch(z, c.s));
   } else {
     GemmParams g = gemm_params(d.E, d.W2, d.Ce, f.e, d.Ce, f.Wcat + d.C, d.D, sv.Z, d.W2);
     g.a_rgather = plan->dst_perm;
@@ -436,10 +457,11 @@ static int node_projections_indexed(Ctx& c, const AttnFwdIndexed& g) {
   // operand (a = column block, b = k, c = column in block) = W[(128 a + c) * D + b]; slice 1 starts C + Ce columns further
   if (mode_f16()) RUN(prepare_W_f16_launch(f.Wcat, f.Wq, ncb, 128l * d.D, 1, d.D, c.s, 2, d.C + d.Ce, img));
   else RUN(prepare_T_planes_launch(f.Wcat, f.Wq, ncb, 128l * d.D, 1, d.D, 0, c.s, nullptr, 2, d.C + d.Ce, img));
-  RUN(edge_z_launch(f.x, d.C, nullptr, nullptr, d.D, f.Wq, d.W2, f.bcat, nullptr, nullptr, nullptr, 0, f.Pi, d.W2, d.N,
-                    nullptr, nullptr, d.H, d.Hd, nullptr, c.s));
-  RUN(edge_z_launch(f.x, d.C, nullptr, nullptr, d.D, f.Wq + img, d.W2, nullptr, nullptr, nullptr, nullptr, 0, f.Pj, d.W2,
-                    d.N, nullptr, nullptr, d.H, d.Hd, nullptr, c.s));
+  EdgeZParams z = node_proj_params(d, f.x, f.Wq);   // We stays null: the images are made
+  z.Pi = f.bcat; z.Z = f.Pi;
+  RUN(edge_z_launch(z, c.s));
+  z.Wq = f.Wq + img; z.Pi = nullptr; z.Z = f.Pj;
+  RUN(edge_z_launch(z, c.s));
   return CGAT_OK;
 }
 // Te = table W_e^T (no bias: Pi carries it) on whichever engine takes R rows: a single-op small-row program below
@@ -744,8 +766,9 @@ static int attn_bwd_out_layer(Ctx& c, const AttnBwd& b) {
     RUN(scale_launch(b.g_aggr, invH, b.gas, (long)d.N * d.C, c.s));
     if (b.r.out_heads_one) {
       // all heads in one launch pair (round 6): head h reads the same gas, its weight at + h * C * Hd, writes gS + h * Hd
-      CGAT_TRY(linear128_heads_launch(d.H, b.gas, d.C, 0, p->M_out_w, 1, d.Hd, (long)d.C * d.Hd, nullptr, 0, CGAT_ACT_NONE, 0,
-                                      b.gS, d.HHd, d.Hd, d.N, c.scratch, c.s, d.Hd, nullptr, 0, 0, nullptr));
+      Linear128Params l = linear128_params(b.gas, d.C, p->M_out_w, 1, d.Hd, b.gS, d.HHd, d.N, d.Hd);
+      l.heads = d.H; l.s_w = (long)d.C * d.Hd; l.s_out = d.Hd;
+      CGAT_TRY(linear128_heads_launch(l, c.scratch, c.s));
     } else {
       for (int h = 0; h < d.H; ++h) {   // gS[:,h,:] = gas @ fc_out_M[h]
         GemmParams g = gemm_params(d.N, d.Hd, d.C, b.gas, d.C, p->M_out_w + (size_t)h * d.C * d.Hd, d.Hd,
@@ -1004,8 +1027,8 @@ static HiddenFwd hidden_fwd_carve(Ctx& c, const AttnDims& d, const float* b_in, 
   f.Pj = c.take<float>((size_t)d.N * d.W2);
   f.Wq = c.take<float>(edge_z_wq_floats(d.W2));
   c.seal();
-  f.fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 && d.C == 128 &&
-           edge_z_fast(d.Ce, d.W2, 1, d.W2 / 2, d.Ce, d.W2, d.W2, e, f.Pi, f.Pj, Hout, b_in) && aligned16(x);
+  f.fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 && d.C == 128 && edge_z_dims(d.Ce, d.W2, d.Ce, d.W2, d.W2) &&
+           aligned16(e, f.Pi, Hout, b_in, x);
   return f;
 }
 
@@ -1014,8 +1037,15 @@ static int edge_hidden_forward_impl(Ctx& c, const cgat_plan* plan, const AttnDim
   const HiddenFwd f = hidden_fwd_carve(c, d, b_in, x, e, Hout);
   CGAT_TRY(node_projections(c, d, f.fast, true, x, w_in, b_in, NodeProj{f.Pi, f.Pj, f.Wq}));
   if (f.fast) {
-    RUN(edge_z_launch(e, d.Ce, plan->dst_perm, w_in + d.C, d.D, f.Wq, d.W2, f.Pi, plan->dst_sorted, f.Pj, plan->src_sorted,
-                      d.W2, Hout, d.W2, d.E, nullptr, nullptr, 1, d.W2 / 2, nullptr, c.s, CGAT_ACT_LEAKY, hmax));
+    EdgeZParams z = {};
+    z.e = e; z.lde = d.Ce; z.perm = plan->dst_perm; z.rows = d.E;
+    z.We = w_in + d.C; z.ldw = d.D; z.Wq = f.Wq; z.W2 = d.W2;
+    z.Pi = f.Pi; z.dsti = plan->dst_sorted; z.Pj = f.Pj; z.srci = plan->src_sorted; z.ld_add = d.W2;
+    z.n_add_rows = 0;   // not given, as ever: this launch never runs the 256-row kernel (the table of forms)
+    z.Z = Hout; z.ldz = d.W2;
+    z.H = d.H; z.Hd = d.Hd;   // (hidden_dims: one "head" of W2 / 2 columns; no logits)
+    z.act = CGAT_ACT_LEAKY; z.omax = hmax;
+    RUN(edge_z_launch(z, c.s));
   } else {
     GemmParams g = gemm_params(d.E, d.W2, d.Ce, e, d.Ce, w_in + d.C, d.D, Hout, d.W2);
     g.a_rgather = plan->dst_perm;
@@ -1139,8 +1169,8 @@ static HiddenFwdIndexed hidden_fwd_indexed_carve(Ctx& c, const AttnDims& d, int 
   f.Te = c.take<float>((size_t)R * d.W2);
   f.Wq = c.take<float>(edge_z_wq_floats(d.W2));
   c.seal();
-  f.fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 &&
-           edge_z_fast(d.C, d.W2, 1, d.W2 / 2, d.C, d.W2, d.W2, x, f.Pi, f.Pj, Hout, b_in);
+  f.fast = !c.dry && d.N > 0 && d.W2 % 256 == 0 && edge_z_dims(d.C, d.W2, d.C, d.W2, d.W2) &&
+           aligned16(x, f.Pi, Hout, b_in);
   return f;
 }
 static int edge_hidden_forward_indexed_impl(Ctx& c, const cgat_plan* plan, const AttnDims& d, const float* w_in,

@@ -187,6 +187,26 @@ def hnet_route(rows, W, n_fc, n_hyper, backward=False, overlapped=False):
     return {n for i, n in enumerate(HNET_ROUTE_BITS["backward" if backward else "forward"]) if mask >> i & 1}
 
 
+EDGE_Z_KERNELS = ("none", "rows128", "rows256", "msg_wsum")     # cgat_edge_z_form.kernel
+EDGE_Z_LAUNCHES = ("edge_z", "edge_logits", "edge_msg_wsum")    # cgat_debug_edge_z_form's `launch`
+EDGE_Z_STORES = ("f32", "bf16", "bits")
+
+
+def edge_z_form(rows, W2, H=1, Hd=128, n_add_rows=0, ld_add=None, store="f32", adds=False, logits=False, omax=False, act=0,
+                launch="edge_z"):
+    """Which kernel a launch of the per-edge family (csrc/edgez.hip) runs at these dims in the current arithmetic mode, as
+    a dict of cgat_edge_z_form's fields with `kernel` by name (host only, no GPU needed); None where the launch refuses the
+    combination.  The defaults are the dense layer at width 128 with W2 outputs."""
+    f = _lib.EdgeZForm()
+    rc = lib.cgat_debug_edge_z_form(EDGE_Z_LAUNCHES.index(launch), rows, W2, H, Hd, n_add_rows, W2 if ld_add is None else ld_add,
+                                    EDGE_Z_STORES.index(store), int(adds), int(logits), int(omax), act, C.byref(f))
+    if rc != 0:
+        return None
+    d = {n: getattr(f, n) for n, _ in f._fields_}
+    d["kernel"] = EDGE_Z_KERNELS[f.kernel]
+    return d
+
+
 def edge_ge_rebuilt(mask, ga, alpha, gS, wA, dst, We, H, Hd):
     """grad edge_attr's product alone on caller-supplied ingredients of the rebuilt rows (cgat_debug_edge_ge_rebuilt,
     include/cgat_hip.h): mask int32 [E, 2 H Hd / 32] bit words, ga / alpha [E, H], gS [N, H Hd], wA [H Hd], dst int32 [E],

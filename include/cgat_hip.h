@@ -302,6 +302,32 @@ int cgat_debug_nodes_attention_signs_indexed(const cgat_plan* plan, const cgat_a
  * named as the route structs of csrc/layers.hip, which say what each stands for.  0 for a layer attn_check refuses. */
 uint32_t cgat_debug_nodes_attention_route(const cgat_plan* plan, const cgat_attn_params* p, int32_t backward);
 
+/* Debug (tests only): WHICH KERNEL a launch of the per-edge family (csrc/edgez.hip) runs, and in what shape, in the
+ * current arithmetic mode -- host only, no device call.  The forms of one launch are bit-identical by design, so no
+ * result can tell which ran; this names it.
+ *   launch 0: the per-edge launch, the per-node projections (adds == 0, logits == 0) and the dense layer at width 128
+ *             (the same with W2 = its outputs, H = 1, Hd = 128);
+ *          1: the logits launch of the forward without grad;   2: its message / weighted-sum launch (n_add_rows = N).
+ *   rows, W2 (output columns), H, Hd; n_add_rows: rows of the gathered addends, 0 = not given (as the first layer of the
+ *   vector-attention variants calls it); ld_add: their row stride; store: 0 fp32, 1 bf16, 2 the bit form;
+ *   adds / logits / omax: whether the launch has gathered addends (and a slot permutation), forms logits, folds max |Z|;
+ *   act: 0 none, 1 tanh, 2 LeakyReLU, 3 ReLU.
+ * CGAT_ERR_ARG (1) where the launch itself refuses the combination. */
+typedef struct cgat_edge_z_form {
+  int32_t kernel;            /* 0 none (no rows), 1 the 128-row kernel, 2 the 256-row kernel, 3 the message / weighted-sum kernel */
+  int32_t passes;            /* matrix passes per product: 2 (fp16 planes; three MFMA passes), 3 or 6 (bf16 planes) */
+  int32_t adds;              /* the kernel variant with gathered addends */
+  int32_t z_bf16;            /* Z stored (kernel 3: rounded) as bf16 */
+  int32_t wide_mode;         /* kernel 2: 0 the training forward, 3 its bit form, 1 logits only */
+  int32_t groups;            /* grid.y: groups the column blocks are dealt to (1: none) */
+  int32_t blocks_per_group;  /* 128-column blocks each group walks */
+  int32_t grid_x;            /* row tiles */
+  int32_t tile_rows;         /* rows per tile */
+} cgat_edge_z_form;
+int cgat_debug_edge_z_form(int32_t launch, int32_t rows, int32_t W2, int32_t H, int32_t Hd, int32_t n_add_rows,
+                           int64_t ld_add, int32_t store, int32_t adds, int32_t logits, int32_t omax, int32_t act,
+                           cgat_edge_z_form* out);
+
 /* Debug / parity instrumentation (tests only, not on the hot path): the LeakyReLU derivative pattern the backward of
  * cgat_nodes_attention_forward will use -- mask[e, c] = (Z[slot(e), c] > 0) for the pre-activations of MH_A (columns
  * [0, H*Hd)) and MH_M ([H*Hd, 2*H*Hd)) of CGAT/CGAT.py:96,105-108, in ORIGINAL edge order.  LeakyReLU's derivative
