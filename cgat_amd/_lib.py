@@ -267,6 +267,9 @@ PROTOTYPES = {
                                       C.c_int32, C.c_int32, vp, C.c_size_t, vp]),
     "cgat_layernorm_tanh_forward": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_float, vp]),
     "cgat_layernorm_tanh_backward": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp]),
+    "cgat_gp_predict_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "cgat_gp_predict": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp] + [C.c_float] * 5 +
+                        [vp] * 5 + [vp, C.c_size_t, vp]),
 }
 
 

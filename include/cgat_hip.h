@@ -793,6 +793,30 @@ int cgat_layernorm_tanh_forward(const float* u, float* y, int32_t rows, int32_t 
 int cgat_layernorm_tanh_backward(const float* u, const float* y, const float* g_y, float* g_u, int32_t rows, int32_t W,
                                  float eps, void* stream);
 
+/* ---- sparse variational GP head on graph embeddings (prediction with uncertainty) -----------------------
+ * The prediction side of the reference's screening flow: CGAT/gaussian_process.py:45-66 (ScaleKernel(RBFKernel) with one
+ * lengthscale, ConstantMean / ZeroMean, whitened VariationalStrategy + CholeskyVariationalDistribution) as evaluated at
+ * :247-268 (latent distribution, no likelihood noise; confidence region mean +- 2 stddev; denorm by std, mean) and used
+ * by Utilities/gp_predict.py:29 (uncertainty = upper - prediction).  With k_x[m] = s exp(-max(|x - z_m|^2, 0) inv_two_l2),
+ * L = chol(K_zz + jitter I), a = L^-T m, W1 = L^-1, W2 = L_S^T L^-1:
+ *   mean_f = c + k_x . a        var_f = max(s - |W1 k_x|^2 + |W2 k_x|^2, 0)
+ *   pred = mean_f tgt_std + tgt_mean        lower / upper = (mean_f -+ 2 sqrt(var_f)) tgt_std + tgt_mean
+ * One launch over tiles of 32 rows of X on the f32-input matrix cores; the tile of the G x M cross-kernel matrix stays in
+ * LDS (32 x M x 4 B), hence M <= 1024: a larger M returns 4 (unsupported) with a message.  G = 0 launches nothing.
+ * Operands (device, fp32; Mp = M rounded up to 32, Dp = D rounded up to 64; padding is zero):
+ *   X [G, D] rows ldx apart;  centroid [D] of Z;  znorm [Mp] = |z_m - centroid|^2;
+ *   Zimg: the packed image of Z - centroid as [Mp, Dp];  factors: a [Mp], then the packed image of [W1; W2] as
+ *   [2 Mp, Mp] (W1 in rows 0 .., W2 in rows Mp ..).  W1 must be lower triangular: its column blocks past the diagonal
+ *   are not read.  Packed image of P [R, Kd]: img[((c Kd/8 + k8) 64 + lane) 4 + q] = P[32 c + (lane & 31)][8 k8 + 2 q +
+ *   (lane >> 5)]; both images 16-byte aligned.
+ * Outputs [G]: mean_f, var_f; pred, lower, upper each or NULL.  No workspace is needed (the query returns 0).  No
+ * atomics: bitwise deterministic; caller's stream, no allocation, no synchronisation. */
+size_t cgat_gp_predict_workspace_bytes(int32_t G, int32_t M, int32_t D);
+int cgat_gp_predict(const float* X, int64_t ldx, int32_t G, int32_t D, const float* Zimg, int32_t M,
+                    const float* centroid, const float* znorm, const float* factors, float c, float s, float inv_two_l2,
+                    float tgt_mean, float tgt_std, float* mean_f, float* var_f, float* pred, float* lower, float* upper,
+                    void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
