@@ -108,6 +108,13 @@ class EdgeZForm(C.Structure):
                                          "grid_x", "tile_rows")]
 
 
+class EdgeBwdForm(C.Structure):
+    """cgat_edge_bwd_form"""
+    _fields_ = [(n, C.c_int32) for n in ("passes", "rc", "bitplane", "prep", "grid_x", "groups", "blocks_per_group", "heads",
+                                         "bit_shape", "te_only", "ranges", "SA", "SM", "message_pairs", "bit_grid_x",
+                                         "reserved")] + [("ws_end", C.c_int64), ("ws_floats", C.c_int64)]
+
+
 ROWPROG_MAX_OPS = 24
 ROWPROG_SYNC_WORDS = (1024 + 1) * 16
 
@@ -160,6 +167,7 @@ PROTOTYPES = {
                                                            vp, C.c_size_t, vp]),
     "cgat_debug_nodes_attention_route": (C.c_uint32, [C.POINTER(Plan), C.POINTER(AttnParams), C.c_int32]),
     "cgat_debug_edge_z_form": (C.c_int, [C.c_int32] * 6 + [C.c_int64] + [C.c_int32] * 5 + [C.POINTER(EdgeZForm)]),
+    "cgat_debug_edge_bwd_form": (C.c_int, [C.c_int32] * 11 + [C.POINTER(EdgeBwdForm)]),
     "cgat_debug_nodes_attention_signs": (C.c_int, [C.POINTER(Plan), C.POINTER(AttnParams), vp, vp, vp]),
     "cgat_debug_edge_ge_rebuilt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "cgat_debug_edge_ge_rebuilt": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp,

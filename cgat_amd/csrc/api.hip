@@ -100,7 +100,7 @@ static bool linear_route_z(int K, int N, int act, long ldx, long ldy, const void
   return (act == CGAT_ACT_NONE || act == CGAT_ACT_TANH || act == CGAT_ACT_LEAKY) && linear128_fast(K, N, ldx, ldy, x, y);
 }
 static bool linear_route_ge(int K, int N, int act, long ldx, long ldy, const void* x, const void* y) {
-  return act == CGAT_ACT_NONE && N == 128 && K > 128 && edge_ge_fast(128, K, ldx, 128, ldy, x, y);
+  return act == CGAT_ACT_NONE && N == 128 && K > 128 && edge_ge_dims(128, K, ldx, 128, ldy) && aligned16(x, y);
 }
 extern "C" size_t cgat_linear_forward_workspace_bytes(int32_t M, int32_t K, int32_t N) {
   (void)M;
@@ -122,8 +122,12 @@ extern "C" int cgat_linear_forward(const float* x, int64_t ldx, const float* w, 
       l.bias = bias; l.act = act;
       return linear128_launch(l, ws, s);
     }
-    if (linear_route_ge(K, N, act, ldx, ldy, x, y))
-      return edge_ge_launch(x, ldx, 128, w, 1, ldw, (float*)ws, K, y, ldy, nullptr, M, 0, bias, s, x_absmax);
+    if (linear_route_ge(K, N, act, ldx, ldy, x, y)) {
+      // K inputs -> 128 outputs n: element (col = k, out = n) at W[n * ldw + k]
+      EdgeGeParams g = edge_ge_params(x, ldx, 128, w, 1, ldw, (float*)ws, K, y, ldy, M);
+      g.bias = bias; g.amax = x_absmax;
+      return edge_ge_launch(g, s);
+    }
   }
   GemmParams g = gemm_params(M, N, K, x, ldx, w, ldw, y, ldy);
   g.bias = bias;
@@ -205,8 +209,12 @@ extern "C" int cgat_heads_linear_forward(const float* x, int64_t ldx, int64_t s_
   hipStream_t s = (hipStream_t)stream;
   const bool have_ws = ws && ws_bytes >= cgat_heads_linear_forward_workspace_bytes(M, K, N, H);
   if (have_ws && H > 1 && N == 128 && K > 128 && heads_strides_ok(s_x, s_w, s_bias, s_y) &&
-      (!bias || (((uintptr_t)bias) & 15) == 0) && edge_ge_heads_fast(H, K, ldx, ldy, ldw, x, w, y, x_absmax))
-    return edge_ge_heads_launch(H, x, ldx, s_x, w, s_w, bias, s_bias, y, ldy, s_y, M, K, (float*)ws, s, x_absmax);
+      edge_ge_heads_dims(H, K, ldx, ldy, ldw, x_absmax != nullptr) && aligned16(x, w, y, bias)) {
+    EdgeGeParams g = edge_ge_params(x, ldx, 128, w, 1, K, (float*)ws, K, y, ldy, M);
+    g.bias = bias; g.amax = x_absmax;
+    g.heads = H; g.s_x = s_x; g.s_w = s_w; g.s_bias = s_bias; g.s_y = s_y;
+    return edge_ge_launch(g, s);
+  }
   for (int h = 0; h < H; ++h)
     CGAT_TRY(cgat_linear_forward(x + h * s_x, ldx, w + h * s_w, ldw, bias ? bias + h * s_bias : nullptr, y + h * s_y, ldy, M,
                                  K, N, CGAT_ACT_NONE, x_absmax, ws, ws_bytes, stream));
@@ -283,9 +291,11 @@ static int linear_backward_impl(const float* x, int64_t ldx, const float* w, int
       Linear128Params l = linear128_params(gp, ldgp, w, 1, ldw, g_x, ldgx, M, K);
       l.accumulate = accumulate_gx; l.dact = gx_dact; l.ld_dact = ld_dact; l.omax = gx_absmax;
       CGAT_TRY(linear128_launch(l, ws, s));
-    } else if (have_ws && K == 128 && N > 128 && edge_ge_fast(128, N, ldgp, 128, ldgx, gp, g_x)) {
+    } else if (have_ws && K == 128 && N > 128 && edge_ge_dims(128, N, ldgp, 128, ldgx) && aligned16(gp, g_x)) {
       // inputs n (N of them) -> 128 outputs k: element (col = n, out = k) at W[n * ldw + k]
-      CGAT_TRY(edge_ge_launch(gp, ldgp, 128, w, ldw, 1, (float*)ws, N, g_x, ldgx, nullptr, M, accumulate_gx, nullptr, s));
+      EdgeGeParams g = edge_ge_params(gp, ldgp, 128, w, ldw, 1, (float*)ws, N, g_x, ldgx, M);
+      g.accumulate = accumulate_gx;
+      CGAT_TRY(edge_ge_launch(g, s));
     } else {
       GemmParams g = gemm_params(M, K, N, gp, ldgp, w, ldw, g_x, ldgx);
       g.b_kmajor = 1;

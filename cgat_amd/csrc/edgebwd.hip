@@ -6,6 +6,8 @@
 // (bilinear.hip: six v_mfma_f32_16x16x32_bf16 passes, fp32 accumulation, fp32-equivalent) happens in the loop
 // -- ~64 VALU instructions per 96 MFMAs and wave, overlapped by the second wave of the SIMD -- while W_e
 // arrives pre-split in fragment order through a double-buffered LDS tile shared by the 8 waves.
+#include <string.h>
+#include "../../include/cgat_hip.h"
 #include "common.h"
 #include "kernels.h"
 #include "mfma_bf16.h"
@@ -872,6 +874,22 @@ __global__ __launch_bounds__(512, 2) void edge_gw_kernel(const float* __restrict
 #undef GW_FLUSH
 }
 
+// =======================================================================================
+// Launchers.  Every launch takes its operands as one record (kernels.h), asks edge_ge_form / edge_gw_form ONCE which kernel
+// runs on which image, grid and workspace carve, and hands record and form to the one function that expands them into that
+// kernel's argument list.
+// =======================================================================================
+// Every instantiation of the two kernels.  First use decides the order in which the device code is emitted; naming them
+// here, in the order they have always had, keeps the code object byte-identical whatever order the launchers below take.
+[[maybe_unused]] static const void* const k_instantiations[] = {
+    (const void*)edge_ge_kernel<6, true, true>, (const void*)edge_ge_kernel<1, true>, (const void*)edge_ge_kernel<2, true>,
+    (const void*)edge_ge_kernel<6, true>, (const void*)edge_ge_kernel<3, true>, (const void*)edge_ge_kernel<2, false>,
+    (const void*)edge_ge_kernel<6, false>, (const void*)edge_ge_kernel<3, false>,
+    (const void*)edge_gw_kernel<6, true, true>, (const void*)edge_gw_kernel<1, true>, (const void*)edge_gw_kernel<2, true>,
+    (const void*)edge_gw_kernel<6, true>, (const void*)edge_gw_kernel<3, true>, (const void*)edge_gw_kernel<2, false>,
+    (const void*)edge_gw_kernel<6, false>, (const void*)edge_gw_kernel<3, false>};
+
+// ---- edge_ge: the parts of the decision, then the decision ----
 // The rebuilt rows take the bit-plane body (edge_ge_kernel<6, true, true>) in the 24-bit modes when the attention half is
 // whole heads of whole 128-column blocks (at most 8: the kernel's LDS copy of cs) and a launch group of ncb_g column
 // blocks starts at a head's first block (a group that is the whole row always does).
@@ -879,67 +897,25 @@ static bool edge_ge_bitplane(const EdgeRC* rc, int W2, int ncb_g) {
   return rc && mode_24bit() && !edge_mma_bf16() && rc->H >= 1 && rc->H <= 8 && rc->Hd % 128 == 0 &&
          rc->HHd == rc->H * rc->Hd && rc->HHd <= W2 && rc->nw * 32 == W2 && (ncb_g * 128) % rc->Hd == 0;
 }
-bool edge_ge_fast(int Ce, int W2, long ldg, long gzb, long ldo, const void* gZ, const void* out) {
-  return mode_split() && Ce == 128 && W2 % 128 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
-         (ldo % 4) == 0 && ((((uintptr_t)gZ) | ((uintptr_t)out)) & 15) == 0;
+bool edge_ge_dims(int Ce, int W2, long ldg, long gzb, long ldo) {
+  return mode_split() && Ce == 128 && W2 % 128 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 && (ldo % 4) == 0;
 }
-
-// We: element (col, k) at We[col * s_col + k * s_out] (col < W2 inputs, k < 128 outputs).  Wq: edge_z_wq_floats(W2)
-// floats of workspace.  bias [128] or null (added to the product, before any accumulation into `out`).
-// amax (f16x3 mode only): device pointer to max |gZ|; without it the bf16x6 form runs.
-int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_col, long s_out, float* Wq, int W2,
-                   float* out, long ldo, const int* scatter, int E, int accumulate, const float* bias,
-                   hipStream_t stream, const float* amax, const EdgeRC* rc) {
-  if (E <= 0) return CGAT_OK;
-  const int ncb = W2 / 128;
-  // f16x3 form: with max |gZ| known, for a weight whose 128 outputs are contiguous (s_out == 1: the backward products)
-  // or whose W2 inputs are (s_col == 1: a forward nn.Linear weight [128, W2], round 3)
-  const bool out_contig = s_out == 1 && (s_col % 4) == 0, in_contig = s_col == 1 && (s_out % 4) == 0 && W2 % 128 == 0;
-  const bool f16 = mode_f16() && amax && (out_contig || in_contig) && (((uintptr_t)We) & 15) == 0;
-  // operand (a = column block, b = column in block, c = output k) = We[(128 a + b) * s_col + c * s_out]
-  const bool bp = !f16 && edge_ge_bitplane(rc, W2, ncb);
-  EdgeRC rcv = rc ? *rc : EdgeRC{};
-  rcv.cs = Wq + edge_ge_cs_offset(W2);
-  if (f16) {   // per-tensor weight scale: max |We| behind the two planes
-    float* wmax = Wq + (size_t)ncb * 16384;
-    CGAT_TRY(fill_launch(wmax, 0.f, 1, stream));
-    if (out_contig) CGAT_TRY(absmax_rows128_launch(We, s_col, W2, wmax, stream));
-    else
-      for (int j = 0; j < ncb; ++j) CGAT_TRY(absmax_rows128_launch(We + 128 * j, s_out, 128, wmax, stream));
-    CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream, wmax));
-  } else if (bp) {
-    CGAT_TRY(prepare_T_bf16_attn_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, rcv.wA, rcv.H, rcv.Hd,
-                                        const_cast<float*>(rcv.cs), stream));
-  } else {
-    CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
-  }
-  CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);   // the per-edge launch / node-side and dense-layer uses
-  const int grid = cdiv(E, 256);
-#define GE_GO(P_, R_)                                                                                                 \
-  hipLaunchKernelGGL((edge_ge_kernel<P_, R_>), dim3(grid), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq, ncb, \
-                     out, ldo, scatter, E, accumulate, bias, amax, rcv, HeadBatch{})
-  // (the per-EDGE launch only -- rc: the rebuilt gZ rows -- and never in the fp16 mode, which has its own bf16 storage form)
-  const bool one = rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
-  if (bp)
-    hipLaunchKernelGGL((edge_ge_kernel<6, true, true>), dim3(grid), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq,
-                       ncb, out, ldo, scatter, E, accumulate, bias, amax, rcv, HeadBatch{});
-  else if (one) GE_GO(1, true);
-  else if (rc) { if (f16) GE_GO(2, true); else if (!mode_bf16x3()) GE_GO(6, true); else GE_GO(3, true); }
-  else { if (f16) GE_GO(2, false); else if (!mode_bf16x3()) GE_GO(6, false); else GE_GO(3, false); }
-#undef GE_GO
-  CGAT_LAUNCH_CHECK();
-  return CGAT_OK;
+// (the six-pass image is the larger one: three bf16 planes per 128 x 128 block)
+size_t edge_ge_heads_image_floats(int W2) { return (size_t)(W2 / 128) * 24576 + 4; }
+bool edge_ge_heads_dims(int heads, int W2, long ldx, long ldy, long ldw, bool have_amax) {
+  const bool f16 = mode_f16() && have_amax;
+  const bool six = mode_24bit();      // round 6: the 24-bit modes batch their heads too
+  return (f16 || six) && heads >= 1 && heads <= TPREP_MAX && W2 % 128 == 0 && ldw == W2 && edge_ge_dims(128, W2, ldx, 128, ldy);
 }
-
-// K-split form of the product above for FEW row tiles beside a long K (round 6; the harness' shipped batch: g_edge_attr at
-// 30 720 edges is 120 workgroups walking 20 column blocks, the node-side input gradients at 1 280 atoms 5 workgroups --
-// or, as small-row programs, 0.84 GFLOP on the fp64 matrix instruction: 100-160 us a launch).  The column blocks are dealt
-// to S groups (grid.y), group s multiplies its blocks into slab s ([E, 128] each, at slabs + s * E * 128, scattered rows as
-// `out` would be); the caller adds the slabs in group order (sum_slabs_launch).  A group holds an EVEN number of blocks,
-// so that a block's position in its group has the parity of its position in the row (the sign alternation above).
-// Returns the number of groups a launch of this shape takes; 1 = not worth it / not available (then use edge_ge_launch).
-int edge_ge_ksplit_groups(int E, int W2) {
-  if (!mode_24bit()) return 1;
+// K-split form for FEW row tiles beside a long K (round 6; the harness' shipped batch: g_edge_attr at 30 720 edges is 120
+// workgroups walking 20 column blocks, the node-side input gradients at 1 280 atoms 5 workgroups -- or, as small-row
+// programs, 0.84 GFLOP on the fp64 matrix instruction: 100-160 us a launch).  The column blocks are dealt to S groups
+// (grid.y), group s multiplies its blocks into slab s; the caller adds the slabs in group order (sum_slabs_launch).  A group
+// holds an EVEN number of blocks, so that a block's position in its group has the parity of its position in the row (the
+// sign alternation above).  The groups have six-pass bodies only: none for rebuilt rows under "bf16-mma", which run one pass.
+// Returns the number of groups a launch of this shape takes; 1 = not worth it / not available (then the plain launch).
+int edge_ge_ksplit_groups(int E, int W2, bool rebuilt) {
+  if (!mode_24bit() || (rebuilt && edge_mma_bf16())) return 1;
   const int ncb = W2 / 128, tiles = cdiv(E, 256);
   if (W2 % 128 != 0 || E < 1024 || tiles >= 192) return 1;     // (the reference's fixtures stay on the unsplit forms)
   int best = 1;
@@ -947,100 +923,115 @@ int edge_ge_ksplit_groups(int E, int W2) {
     if (ncb % S == 0 && ((ncb / S) & 1) == 0) { best = S; if (tiles * S >= 192) break; }
   return best;
 }
-int edge_ge_ksplit_launch(const float* gZ, long ldg, long gzb, const float* We, long s_col, long s_out, float* Wq, int W2,
-                          float* slabs, const int* scatter, int E, int S, hipStream_t stream, const EdgeRC* rc) {
-  if (E <= 0) return CGAT_OK;
-  const int ncb = W2 / 128;
-  CGAT_CHECK_ARG(S >= 1 && ncb % S == 0 && (S == 1 || ((ncb / S) & 1) == 0) && mode_24bit(),
-                 "edge_ge_ksplit: %d groups of %d column blocks", S, ncb);
-  const int ncb_g = ncb / S;
-  const bool bp = edge_ge_bitplane(rc, W2, ncb_g);   // groups that start inside a head keep the six-pass body
-  EdgeRC rcv = rc ? *rc : EdgeRC{};
-  rcv.cs = Wq + edge_ge_cs_offset(W2);
-  if (bp)
-    CGAT_TRY(prepare_T_bf16_attn_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, rcv.wA, rcv.H, rcv.Hd,
-                                        const_cast<float*>(rcv.cs), stream));
-  else
-    CGAT_TRY(prepare_T_planes_launch(We, Wq, ncb, 128 * s_col, s_col, s_out, /*alternate=*/1, stream));
-  CGAT_PROF(scatter ? "edge_ge" : "rows_ge", stream);
-  const HeadBatch hb = {(long)ncb_g * gzb, (long)ncb_g * 6144, 0, (long)E * 128, 0, 0, (long)ncb_g * 4};
-  if (bp)
-    hipLaunchKernelGGL((edge_ge_kernel<6, true, true>), dim3(cdiv(E, 256), S), dim3(512), 0, stream, gZ, ldg, gzb,
-                       (const uint4*)Wq, ncb_g, slabs, 128l, scatter, E, 0, (const float*)nullptr, (const float*)nullptr,
-                       rcv, hb);
-  else if (rc)     // the rows rebuilt from their ingredients (struct EdgeRC): a group's k-steps start at ks0
-    hipLaunchKernelGGL((edge_ge_kernel<6, true>), dim3(cdiv(E, 256), S), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq,
-                       ncb_g, slabs, 128l, scatter, E, 0, (const float*)nullptr, (const float*)nullptr, *rc, hb);
-  else
-    hipLaunchKernelGGL((edge_ge_kernel<6, false>), dim3(cdiv(E, 256), S), dim3(512), 0, stream, gZ, ldg, gzb, (const uint4*)Wq,
-                       ncb_g, slabs, 128l, scatter, E, 0, (const float*)nullptr, (const float*)nullptr, rcv, hb);
-  CGAT_LAUNCH_CHECK();
-  return CGAT_OK;
-}
 
-// out[t, :] (+)= sum over the ncb 128-column blocks of x[t, :] times an ALREADY prepared six-pass image (block a at
-// Wq + a * 24576 floats, odd blocks negated: prepare_T_planes_launch with alternate = 1) -- the per-node
-// second layer of the message network, whose H per-head weights are not one affine operand (layers.hip)
-int edge_ge_prepared_launch(const float* x, long ldx, const void* Wq, int ncb, float* out, long ldo, int rows,
-                            int accumulate, hipStream_t stream) {
-  if (rows <= 0) return CGAT_OK;
-  CGAT_PROF("rows_ge", stream);
-  const EdgeRC none = {};
-  hipLaunchKernelGGL((edge_ge_kernel<6, false>), dim3(cdiv(rows, 256)), dim3(512), 0, stream, x, ldx, 128l, (const uint4*)Wq,
-                     ncb, out, ldo, (const int*)nullptr, rows, accumulate, (const float*)nullptr, (const float*)nullptr, none,
-                     HeadBatch{});
-  CGAT_LAUNCH_CHECK();
-  return CGAT_OK;
-}
-
-// `heads` products y_h = x_h W_h^T + b_h (x_h = x + h * s_x: W2 columns of a wider matrix; W_h = W + h * s_w: [128, W2]
-// row-major with leading dimension W2, contiguous; y_h = y + h * s_y) in three launches instead of 4-5 per head: the
-// heads' weight maxima and fp16 planes through the batched preparation of the contraction kernels (opimage.hip), then
-// ONE launch of the kernel above with grid.y = head.  f16x3 mode with max |x| known (amax), heads <= TPREP_MAX.
-// ws: heads * edge_ge_heads_image_floats(W2) + bilinear_prepare_T_batch_ws_floats(heads) floats.
-// (the six-pass image is the larger one: three bf16 planes per 128 x 128 block)
-size_t edge_ge_heads_image_floats(int W2) { return (size_t)(W2 / 128) * 24576 + 4; }
-bool edge_ge_heads_fast(int heads, int W2, long ldx, long ldy, long ldw, const void* x, const void* w, const void* y,
-                        const float* amax) {
-  const bool f16 = mode_f16() && amax;
-  const bool six = mode_24bit();      // round 6: the 24-bit modes batch their heads too
-  return (f16 || six) && heads >= 1 && heads <= TPREP_MAX && W2 % 128 == 0 && ldw == W2 &&
-         (((uintptr_t)w) & 15) == 0 && edge_ge_fast(128, W2, ldx, 128, ldy, x, y);
-}
-int edge_ge_heads_launch(int heads, const float* x, long ldx, long s_x, const float* W, long s_w, const float* bias,
-                         long s_bias, float* y, long ldy, long s_y, int E, int W2, float* ws, hipStream_t stream,
-                         const float* amax) {
-  if (E <= 0 || heads <= 0) return CGAT_OK;
-  const int ncb = W2 / 128;
-  const size_t img = edge_ge_heads_image_floats(W2);
-  const HeadBatch hb = {s_x, (long)(img / 4), s_bias, s_y, 0};
-  const EdgeRC none = {};
-  if (!mode_f16()) {
-    // operand (a = column block, b = column in block, c = output k) = W_h[c * W2 + 128 a + b], as edge_ge_launch's
-    CGAT_TRY(prepare_T_planes_launch(W, ws, ncb, 128, 1, W2, /*alternate=*/1, stream, nullptr, heads, s_w, (long)img));
-    CGAT_PROF("rows_ge", stream);
-    hipLaunchKernelGGL((edge_ge_kernel<6, false>), dim3(cdiv(E, 256), heads), dim3(512), 0, stream, x, ldx, 128l,
-                       (const uint4*)ws, ncb, y, ldy, (const int*)nullptr, E, 0, bias, (const float*)nullptr, none, hb);
-    CGAT_LAUNCH_CHECK();
-    return CGAT_OK;
+// The form of an edge_ge_launch, by the kind of its record:
+//   * the heads launch (heads > 0): grid.y = head; two fp16 planes in the f16x3 mode (max |x| known: edge_ge_heads_dims),
+//     the six-pass image otherwise, either prepared for all heads at once;
+//   * a prepared image (We == null): the six-pass kernel on the caller's image -- the per-node second layer of the message
+//     network, whose H per-head weights are not one affine operand (layers.hip);
+//   * else the f16x3 form with max |rows| known, for a weight whose 128 outputs are contiguous (s_out == 1: the backward
+//     products) or whose W2 inputs are (s_col == 1: a forward nn.Linear weight [128, W2], round 3); the bit-plane body
+//     where edge_ge_bitplane holds for the launch's K groups (groups that start inside a head keep the six-pass body); ONE
+//     bf16 pass for the per-EDGE launch under "bf16-mma" (rc: the rebuilt rows -- and never in the fp16 mode, which has its
+//     own bf16 storage form); else six passes, three in the bf16x3 mode.
+EdgeGeForm edge_ge_form(const EdgeGeParams& p) {
+  EdgeGeForm f = {};
+  if (p.rows <= 0) return f;
+  const int ncb = p.W2 / 128;
+  f.grid_x = cdiv(p.rows, 256);
+  f.groups = 1; f.ncb_g = ncb;
+  if (p.heads > 0) {
+    f.heads = p.heads;
+    f.passes = mode_f16() ? 2 : 6;
+    f.prep = mode_f16() ? GE_PREP_HEADS_F16 : GE_PREP_PLANES;
+    return f;
   }
-  float* part = ws + (size_t)heads * img;
-  const float* src[TPREP_MAX];
-  float* dst[TPREP_MAX];
-  for (int h = 0; h < heads; ++h) { src[h] = W + (long)h * s_w; dst[h] = ws + (size_t)h * img; }
-  // operand (a = column block, b = column in block, c = output k) = W_h[c * W2 + 128 a + b]: source dims (k, a, b)
-  const int rc_ = bilinear_prepare_T_batch(heads, src, dst, 128, ncb, 128, 1, 2, 0, part, stream, /*alternate=*/1);
-  if (rc_ != CGAT_OK) return rc_;
-  CGAT_PROF("rows_ge", stream);
-  hipLaunchKernelGGL((edge_ge_kernel<2, false>), dim3(cdiv(E, 256), heads), dim3(512), 0, stream, x, ldx, 128l,
-                     (const uint4*)ws, ncb, y, ldy, (const int*)nullptr, E, 0, bias, amax, none, hb);
+  if (!p.We) { f.passes = 6; f.prep = GE_PREP_NONE; return f; }
+  if (p.slabs) { f.groups = p.S; f.ncb_g = p.S >= 1 ? ncb / p.S : 0; }
+  const bool out_contig = p.s_out == 1 && (p.s_col % 4) == 0, in_contig = p.s_col == 1 && (p.s_out % 4) == 0 && p.W2 % 128 == 0;
+  const bool f16 = mode_f16() && p.amax && (out_contig || in_contig) && aligned16(p.We);
+  f.rc = p.rc != nullptr;
+  f.bitplane = !f16 && edge_ge_bitplane(p.rc, p.W2, f.ncb_g);
+  const bool one = f.rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
+  f.passes = f.bitplane ? 6 : one ? 1 : f16 ? 2 : mode_bf16x3() ? 3 : 6;
+  f.prep = f16 ? GE_PREP_F16_TMAX : f.bitplane ? GE_PREP_ATTN : GE_PREP_PLANES;
+  return f;
+}
+// what edge_ge_launch refuses, given the form it would run
+static int edge_ge_check(const EdgeGeParams& p, const EdgeGeForm& f) {
+  CGAT_CHECK_ARG(!p.slabs || (f.groups >= 1 && f.groups * f.ncb_g == p.W2 / 128 && (f.groups == 1 || (f.ncb_g & 1) == 0) &&
+                              mode_24bit()),
+                 "edge_ge_ksplit: %d groups of %d column blocks", p.S, p.W2 / 128);
+  return CGAT_OK;
+}
+
+// ---- edge_ge_kernel's argument list, expanded here and nowhere else ----
+// grid.y = the form's K groups or heads, whose operands lie hb apart
+static void edge_ge_go(const EdgeGeForm& f, const EdgeGeParams& p, const HeadBatch& hb, hipStream_t stream) {
+  EdgeRC rcv = {};
+  if (f.rc) { rcv = *p.rc; rcv.cs = p.Wq + edge_ge_cs_offset(p.W2); }   // (cs: where GE_PREP_ATTN leaves the column sums)
+  const dim3 grid(f.grid_x, f.heads > 0 ? f.heads : f.groups);
+#define GE_GO(P_, R_, B_)                                                                                             \
+  hipLaunchKernelGGL((edge_ge_kernel<P_, R_, B_>), grid, dim3(512), 0, stream, p.gZ, p.ldg, p.gzb, (const uint4*)p.Wq,  \
+                     f.ncb_g, p.out, p.ldo, p.scatter, p.rows, p.accumulate, p.bias, p.amax, rcv, hb)
+  if (f.bitplane) GE_GO(6, true, true);
+  else if (f.passes == 1) GE_GO(1, true, false);
+  else if (f.rc) { if (f.passes == 2) GE_GO(2, true, false); else if (f.passes == 6) GE_GO(6, true, false); else GE_GO(3, true, false); }
+  else { if (f.passes == 2) GE_GO(2, false, false); else if (f.passes == 6) GE_GO(6, false, false); else GE_GO(3, false, false); }
+#undef GE_GO
+}
+
+int edge_ge_launch(const EdgeGeParams& p0, hipStream_t stream) {
+  if (p0.rows <= 0) return CGAT_OK;
+  const EdgeGeForm f = edge_ge_form(p0);
+  CGAT_TRY(edge_ge_check(p0, f));
+  EdgeGeParams p = p0;
+  const int ncb = p.W2 / 128;
+  const long img = (long)edge_ge_heads_image_floats(p.W2);
+  HeadBatch hb = {};
+  if (f.heads > 0) hb = {p.s_x, img / 4, p.s_bias, p.s_y, 0};
+  if (p.slabs) {   // the slabs are the output: group s walks its ncb_g blocks from k-step ks0 into slab s
+    p.out = p.slabs; p.ldo = 128; p.accumulate = 0; p.bias = nullptr; p.amax = nullptr;
+    hb = {(long)f.ncb_g * p.gzb, (long)f.ncb_g * 6144, 0, (long)p.rows * 128, 0, 0, (long)f.ncb_g * 4};
+  }
+  // operand (a = column block, b = column in block, c = output k) = We[(128 a + b) * s_col + c * s_out]
+  switch (f.prep) {
+    case GE_PREP_NONE: break;
+    case GE_PREP_PLANES:
+      CGAT_TRY(prepare_T_planes_launch(p.We, p.Wq, ncb, 128 * p.s_col, p.s_col, p.s_out, /*alternate=*/1, stream, nullptr,
+                                       f.heads > 0 ? f.heads : 1, p.s_w, f.heads > 0 ? img : 0));
+      break;
+    case GE_PREP_F16_TMAX: {   // per-tensor weight scale: max |We| behind the two planes
+      float* wmax = p.Wq + (size_t)ncb * 16384;
+      CGAT_TRY(fill_launch(wmax, 0.f, 1, stream));
+      if (p.s_out == 1) CGAT_TRY(absmax_rows128_launch(p.We, p.s_col, p.W2, wmax, stream));
+      else
+        for (int j = 0; j < ncb; ++j) CGAT_TRY(absmax_rows128_launch(p.We + 128 * j, p.s_out, 128, wmax, stream));
+      CGAT_TRY(prepare_T_planes_launch(p.We, p.Wq, ncb, 128 * p.s_col, p.s_col, p.s_out, /*alternate=*/1, stream, wmax));
+      break;
+    }
+    case GE_PREP_ATTN:
+      CGAT_TRY(prepare_T_bf16_attn_launch(p.We, p.Wq, ncb, 128 * p.s_col, p.s_col, p.s_out, p.rc->wA, p.rc->H, p.rc->Hd,
+                                          p.Wq + edge_ge_cs_offset(p.W2), stream));
+      break;
+    case GE_PREP_HEADS_F16: {   // source dims (k, a, b) of W_h[c * W2 + 128 a + b]; the partial maxima behind the images
+      const float* src[TPREP_MAX];
+      float* dst[TPREP_MAX];
+      for (int h = 0; h < f.heads; ++h) { src[h] = p.We + (long)h * p.s_w; dst[h] = p.Wq + (size_t)h * img; }
+      CGAT_TRY(bilinear_prepare_T_batch(f.heads, src, dst, 128, ncb, 128, 1, 2, 0, p.Wq + (size_t)f.heads * img, stream,
+                                        /*alternate=*/1));
+      break;
+    }
+  }
+  CGAT_PROF(p.scatter ? "edge_ge" : "rows_ge", stream);   // the per-edge launch / node-side and dense-layer uses
+  edge_ge_go(f, p, hb, stream);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }
 
-bool edge_gw_fast(int Ce, int W2, long ldg, long gzb, const void* gZ) {
-  return mode_split() && Ce == 128 && W2 % 256 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0 &&
-         (((uintptr_t)gZ) & 15) == 0;
+// ---- edge_gw: the parts of the decision, then the decision ----
+bool edge_gw_dims(int Ce, int W2, long ldg, long gzb) {
+  return mode_split() && Ce == 128 && W2 % 256 == 0 && gzb != 0 && (gzb % 4) == 0 && (ldg % 4) == 0;
 }
 static int edge_gw_splits(int W2) {   // ranges x column-block pairs ~ one workgroup per CU
   const int npair = W2 / 256;
@@ -1068,17 +1059,69 @@ static bool gw_bitplane_shape(int H, int Hd, int HHd, int W2, int* SA, int* SM) 
   *SM = (256 - H * sa) / npm;
   return true;
 }
-static bool edge_gw_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six, int* SA, int* SM) {
-  if (!rc || !perm || force_six || g_gw_force_six || rc->nw * 32 != W2) return false;
-  return gw_bitplane_shape(rc->H, rc->Hd, rc->HHd, W2, SA, SM);
+// The plain form: S k-ranges per column-block pair, slabs summed by splitk_reduce; fp16 planes with both maxima known in the
+// f16x3 mode, ONE bf16 pass for rebuilt rows under "bf16-mma" (as edge_ge_form), else six passes, three in the bf16x3 mode.
+// The bit-plane form replaces it for rebuilt rows with a slot permutation where gw_bitplane_shape holds (bit_shape), unless a
+// debug switch keeps the six-pass form.  te -- the edge part of grad fc_out_A -- comes from the bit-plane form's column
+// sums.  With that form switched off for this launch it still runs first, for that sum alone (te_only), and the six-pass
+// form writes `out`: on that debug route the whole bit-plane launch and its reducer are paid on top of the six-pass launch
+// (about twice the work of either), and the six-pass launch then reuses the same slab workspace, behind them on the same
+// stream.  It keeps grad fc_out_A's bits independent of the switch (tests/test_edge_gw_bitplane.py compares a layer step
+// with the switch on and off bit for bit in everything but the two W_e blocks).
+EdgeGwForm edge_gw_form(const EdgeGwParams& p) {
+  EdgeGwForm f = {};
+  if (p.E <= 0) return f;
+  const bool f16 = mode_f16() && p.gmax && p.emax;
+  f.rc = p.rc != nullptr;
+  const bool one = f.rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
+  f.passes = one ? 1 : f16 ? 2 : mode_bf16x3() ? 3 : 6;
+  f.S = edge_gw_splits(p.W2);
+  f.grid_x = f.S * (p.W2 / 256);
+  f.slab = (((size_t)cdiv(p.E, 128) * 128 * 128 * 3 + 1) / 2 + 15) / 16 * 16;
+  f.ws_end = f.slab + (size_t)f.S * p.W2 * 128;
+  f.bit_shape = !f16 && p.rc && p.perm && p.rc->nw * 32 == p.W2 &&
+                gw_bitplane_shape(p.rc->H, p.rc->Hd, p.rc->HHd, p.W2, &f.SA, &f.SM);
+  f.bitplane = f.bit_shape && !p.force_six && !g_gw_force_six;
+  f.te_only = p.te && !f.bitplane;
+  if (f.bit_shape) {
+    const int H = p.rc->H, HHd = p.rc->HHd;
+    f.npm = (p.W2 - HHd) / 256;
+    f.bit_grid_x = f.SM * f.npm + f.SA * H;
+    f.slabA = f.slab + (size_t)f.SM * (p.W2 - HHd) * 128;
+    f.csl = f.slabA + (size_t)f.SA * HHd * 128;
+    const size_t end = f.csl + (size_t)f.SA * H * 8 * 128;
+    if (end > f.ws_end) f.ws_end = end;
+  }
+  return f;
 }
+// what edge_gw_launch refuses, given the form it would run
+static int edge_gw_check(const EdgeGwParams&, const EdgeGwForm& f) {
+  CGAT_CHECK_ARG(!f.te_only || f.bit_shape, "edge_gw: the edge part of grad fc_out_A needs the shape of the bit-plane form");
+  return CGAT_OK;
+}
+// A record of what edge_gw_form reads and no more -- dims and which optional operands are PRESENT -- for the questions
+// asked before there are operands (edge_gw_bitplane_layer, the debug queries).  Never launched.
+static EdgeGwParams edge_gw_shape(int E, int W2, const EdgeRC* rc, bool maxima, bool perm, bool force_six, bool te) {
+  alignas(16) static float present_f;
+  static int present_i;
+  static GwTe present_te;
+  EdgeGwParams p = edge_gw_params(&present_f, 128, (long)E * 128, &present_f, 128, perm ? &present_i : nullptr, E, W2, nullptr,
+                                  nullptr, 128);
+  p.rc = rc;
+  if (maxima) p.gmax = p.emax = &present_f;
+  p.force_six = force_six;
+  if (te) p.te = &present_te;
+  return p;
+}
+static EdgeRC edge_rc_shape_only(int H, int Hd, int W2) {
+  EdgeRC rc = {};
+  rc.H = H; rc.Hd = Hd; rc.HHd = H * Hd; rc.nw = W2 / 32;
+  return rc;
+}
+// (bit_shape, not bitplane: independent of the debug switches -- the bit form of the layer's saved buffer rests on that)
 bool edge_gw_bitplane_layer(int H, int Hd) {
-  int sa, sm;
-  return gw_bitplane_shape(H, Hd, H * Hd, 2 * H * Hd, &sa, &sm);
-}
-bool edge_gw_takes_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six) {
-  int sa, sm;
-  return edge_gw_bitplane(rc, W2, perm, force_six, &sa, &sm);
+  const EdgeRC rc = edge_rc_shape_only(H, Hd, 2 * H * Hd);
+  return edge_gw_form(edge_gw_shape(1, 2 * H * Hd, &rc, false, true, false, false)).bit_shape;
 }
 // workspace floats: e planes (zero-padded to a multiple of 128 slots) + slabs.  The slab part is the MAXIMUM over both
 // forms on purpose (the bit-plane form: at most 256 workgroup tiles of 256 x 128 and 256 x 8 rows of column sums, 35 MB;
@@ -1144,68 +1187,52 @@ __global__ void gw_te_add_kernel(const double* __restrict__ part, int HHd, float
   out[col] = (float)(((p[0] + p[1]) + (p[2] + p[3])) + (double)out[col]);
 }
 
+// ---- edge_gw_kernel's argument list, expanded here and nowhere else: the bit-plane form (bit) or the plain form ----
+static void edge_gw_go(const EdgeGwForm& f, const EdgeGwParams& p, bool bit, hipStream_t stream) {
+  const EdgeRC rcv = f.rc ? *p.rc : EdgeRC{};
+#define GW_GO(P_, R_, B_)                                                                                             \
+  hipLaunchKernelGGL((edge_gw_kernel<P_, R_, B_>), dim3(B_ ? f.bit_grid_x : f.grid_x), dim3(512), 0, stream, p.gZ, p.ldg,  \
+                     p.gzb, (const uint4*)p.ws, p.ws + f.slab, p.E, p.W2 / 128, cdiv(p.E, 32), B_ ? f.SM : f.S, p.gmax,  \
+                     p.emax, rcv, B_ ? p.e : nullptr, B_ ? p.lde : 0l, B_ ? p.perm : nullptr, B_ ? f.SA : 0,           \
+                     B_ ? p.ws + f.slabA : nullptr, B_ ? p.ws + f.csl : nullptr)
+  if (bit) GW_GO(6, true, true);
+  else if (f.passes == 1) GW_GO(1, true, false);
+  else if (f.rc) { if (f.passes == 2) GW_GO(2, true, false); else if (f.passes == 6) GW_GO(6, true, false); else GW_GO(3, true, false); }
+  else { if (f.passes == 2) GW_GO(2, false, false); else if (f.passes == 6) GW_GO(6, false, false); else GW_GO(3, false, false); }
+#undef GW_GO
+}
+
 // out[col * ldo + k] = sum_t G[t, col] * e[perm[t] * lde + k],   G[t, 128 a + j] at gZ[t * ldg + a * gzb + j]
-// gmax, emax (f16x3 mode only): device pointers to max |gZ| and max |e|; without them the bf16x6 form runs.
-int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde, const int* perm, int E, int W2,
-                   float* ws, float* out, long ldo, hipStream_t stream, const float* gmax, const float* emax,
-                   const EdgeRC* rc, bool force_six, const GwTe* te) {
-  if (E <= 0) {
-    GemmParams z = gemm_params(W2, 128, 0, nullptr, 1, nullptr, 1, out, ldo);
+int edge_gw_launch(const EdgeGwParams& p, hipStream_t stream) {
+  if (p.E <= 0) {
+    GemmParams z = gemm_params(p.W2, 128, 0, nullptr, 1, nullptr, 1, p.out, p.ldo);
     return gemm_launch(z, nullptr, 0, stream);   // K = 0: zero fill
   }
-  const int ncb = W2 / 128, na = cdiv(E, 128), S = edge_gw_splits(W2);
-  float* planes = ws;
-  float* slab = ws + (((size_t)na * 128 * 128 * 3 + 1) / 2 + 15) / 16 * 16;
+  const EdgeGwForm f = edge_gw_form(p);
+  CGAT_TRY(edge_gw_check(p, f));
   // operand (a = slot block, b = slot in block, c = k) = e[perm[128 a + b] * lde + c], zero past E
-  const bool f16 = mode_f16() && gmax && emax;
-  CGAT_TRY(prepare_T_bf16_rows_launch(e, lde, perm, E, planes, na, stream, f16 ? emax : nullptr));
-  const int nsteps = cdiv(E, 32);
-  int SA = 0, SM = 0;
-  const bool bitplane = !f16 && edge_gw_bitplane(rc, W2, perm, force_six, &SA, &SM);
-  // The edge part of grad fc_out_A comes from the bit-plane form's column sums.  With that form switched off for this
-  // launch (the debug switches) it still runs first, for that sum alone, and the six-pass form below writes `out`: on
-  // that debug route the whole bit-plane launch and its reducer are paid on top of the six-pass launch (about twice the
-  // work of either), and the six-pass launch then reuses the same slab workspace, behind them on the same stream.  It
-  // keeps grad fc_out_A's bits independent of the switch (tests/test_edge_gw_bitplane.py compares a layer step with the
-  // switch on and off bit for bit in everything but the two W_e blocks).
-  const bool te_only = te && !bitplane;
-  if (te_only)
-    CGAT_CHECK_ARG(!f16 && rc && perm && rc->nw * 32 == W2 && gw_bitplane_shape(rc->H, rc->Hd, rc->HHd, W2, &SA, &SM),
-                   "edge_gw: the edge part of grad fc_out_A needs the shape of the bit-plane form");
-  if (bitplane || te_only) {
-    const int H = rc->H, HHd = rc->HHd, npm = (W2 - HHd) / 256;
-    float* slabA = slab + (size_t)SM * (W2 - HHd) * 128;
-    float* csl = slabA + (size_t)SA * HHd * 128;
+  CGAT_TRY(prepare_T_bf16_rows_launch(p.e, p.lde, p.perm, p.E, p.ws, cdiv(p.E, 128), stream, f.passes == 2 ? p.emax : nullptr));
+  if (f.bitplane || f.te_only) {
     {
       CGAT_PROF("edge_gw", stream);
-      hipLaunchKernelGGL((edge_gw_kernel<6, true, true>), dim3(SM * npm + SA * H), dim3(512), 0, stream, gZ, ldg, gzb,
-                         (const uint4*)planes, slab, E, ncb, nsteps, SM, gmax, emax, *rc, e, lde, perm, SA, slabA, csl);
+      edge_gw_go(f, p, true, stream);
       CGAT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(edge_gw_bit_reduce_kernel, dim3(W2 * 4), dim3(256), 0, stream, slab, SM, slabA, SA, csl, rc->wA, H,
-                       HHd, W2, te_only ? nullptr : out, ldo, te ? *te : GwTe{});
+    hipLaunchKernelGGL(edge_gw_bit_reduce_kernel, dim3(p.W2 * 4), dim3(256), 0, stream, p.ws + f.slab, f.SM, p.ws + f.slabA, f.SA,
+                       p.ws + f.csl, p.rc->wA, p.rc->H, p.rc->HHd, p.W2, f.te_only ? nullptr : p.out, p.ldo, p.te ? *p.te : GwTe{});
     CGAT_LAUNCH_CHECK();
-    if (te) {
-      hipLaunchKernelGGL(gw_te_add_kernel, dim3(cdiv(HHd, 256)), dim3(256), 0, stream, te->part, HHd, te->out);
+    if (p.te) {
+      hipLaunchKernelGGL(gw_te_add_kernel, dim3(cdiv(p.rc->HHd, 256)), dim3(256), 0, stream, p.te->part, p.rc->HHd, p.te->out);
       CGAT_LAUNCH_CHECK();
     }
-    if (!te_only) return CGAT_OK;
+    if (!f.te_only) return CGAT_OK;
   }
   {
-    CGAT_PROF(perm ? "edge_gw" : "rows_gw", stream);
-    const EdgeRC none = {};
-#define GW_GO(P_, R_)                                                                                                  \
-  hipLaunchKernelGGL((edge_gw_kernel<P_, R_>), dim3(S * (ncb / 2)), dim3(512), 0, stream, gZ, ldg, gzb,                \
-                     (const uint4*)planes, slab, E, ncb, nsteps, S, gmax, emax, R_ ? *rc : none, (const float*)nullptr,   \
-                     0l, (const int*)nullptr, 0, (float*)nullptr, (float*)nullptr)
-    const bool one = rc && !f16 && edge_mma_bf16() && !mode_bf16x3();
-    if (one) GW_GO(1, true);
-    else if (rc) { if (f16) GW_GO(2, true); else if (!mode_bf16x3()) GW_GO(6, true); else GW_GO(3, true); }
-    else { if (f16) GW_GO(2, false); else if (!mode_bf16x3()) GW_GO(6, false); else GW_GO(3, false); }
-#undef GW_GO
+    CGAT_PROF(p.perm ? "edge_gw" : "rows_gw", stream);
+    edge_gw_go(f, p, false, stream);
     CGAT_LAUNCH_CHECK();
   }
-  return splitk_reduce_launch(slab, S, W2, 128, out, ldo, stream);
+  return splitk_reduce_launch(p.ws + f.slab, f.S, p.W2, 128, p.out, p.ldo, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1271,5 +1298,41 @@ int edge_gj_launch(const EdgeRC& rc, const int* src_rowptr, const int* src_pos, 
   hipLaunchKernelGGL(edge_gj_kernel, dim3(cdiv(cdiv(N, GJ_NODES), 8) * 8), dim3(256), 0, stream, rc, src_rowptr, src_pos,
                      N, W2, Gj, ldo, gjmax);
   CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
+}
+
+// debug (include/cgat_hip.h): the form of a launch of these dims and present operands in the current arithmetic and
+// edge-storage modes, on records that are never launched.  The weight lies as the backward products' (128 contiguous
+// outputs per input column; the heads launch: [128, W2] row-major); the K-split launch takes edge_ge_ksplit_groups' groups.
+extern "C" int cgat_debug_edge_bwd_form(int32_t product, int32_t launch, int32_t rows, int32_t W2, int32_t H, int32_t Hd,
+                                        int32_t rebuilt, int32_t maxima, int32_t perm, int32_t force_six, int32_t te,
+                                        cgat_edge_bwd_form* out) {
+  CGAT_CHECK_ARG(out && (product == 0 || product == 1) && launch >= 0 && launch <= (product == 0 ? 3 : 0) && rows >= 0 &&
+                 W2 > 0 && W2 % 128 == 0 && H > 0 && Hd > 0, "debug_edge_bwd_form: bad arguments");
+  alignas(16) static float present_f;
+  static int present_i;
+  const EdgeRC rc = edge_rc_shape_only(H, Hd, W2);
+  memset(out, 0, sizeof(*out));
+  if (product == 1) {
+    const EdgeGwParams p = edge_gw_shape(rows, W2, rebuilt ? &rc : nullptr, maxima != 0, perm != 0, force_six != 0, te != 0);
+    const EdgeGwForm f = edge_gw_form(p);
+    CGAT_TRY(edge_gw_check(p, f));
+    out->passes = f.passes; out->rc = f.rc; out->bitplane = f.bitplane; out->grid_x = f.grid_x;
+    out->bit_shape = f.bit_shape; out->te_only = f.te_only; out->ranges = f.S; out->SA = f.SA; out->SM = f.SM;
+    out->message_pairs = f.npm; out->bit_grid_x = f.bit_grid_x;
+    out->ws_end = (int64_t)f.ws_end; out->ws_floats = (int64_t)edge_gw_ws_floats(rows, W2);
+    return CGAT_OK;
+  }
+  EdgeGeParams p = edge_ge_params(&present_f, 128, (long)rows * 128, launch == 2 ? nullptr : &present_f, launch == 3 ? 1 : 128,
+                                  launch == 3 ? W2 : 1, &present_f, W2, &present_f, 128, rows);
+  if (rebuilt) p.rc = &rc;
+  if (maxima) p.amax = &present_f;
+  if (perm) p.scatter = &present_i;
+  if (launch == 1) { p.slabs = &present_f; p.S = edge_ge_ksplit_groups(rows, W2, rebuilt != 0); }
+  if (launch == 3) p.heads = H;
+  const EdgeGeForm f = edge_ge_form(p);
+  CGAT_TRY(edge_ge_check(p, f));
+  out->passes = f.passes; out->rc = f.rc; out->bitplane = f.bitplane; out->prep = f.prep; out->grid_x = f.grid_x;
+  out->groups = f.groups; out->blocks_per_group = f.ncb_g; out->heads = f.heads;
   return CGAT_OK;
 }

@@ -440,36 +440,119 @@ struct GwTe {
   double* part;
   float* out;
 };
-bool edge_gw_bitplane_layer(int H, int Hd);   // mode and shape of the bit-plane form for a scalar-attention layer
-bool edge_gw_fast(int Ce, int W2, long ldg, long gzb, const void* gZ);
-size_t edge_gw_ws_floats(int E, int W2);
-int edge_gw_launch(const float* gZ, long ldg, long gzb, const float* e, long lde, const int* perm, int E, int W2,
-                   float* ws, float* out, long ldo, hipStream_t stream, const float* gmax = nullptr,
-                   const float* emax = nullptr,            // device maxima of |gZ| and |e| -> fp16 form in the f16x3 mode
-                   const EdgeRC* rc = nullptr,
-                   bool force_six = false,                 // debug: this launch keeps the six-pass form on every column
-                   const GwTe* te = nullptr);
-// the bit-plane form of the attention half (edge_gw_kernel<6, true, true>): would this launch take it / debug: never take it
-bool edge_gw_takes_bitplane(const EdgeRC* rc, int W2, const int* perm, bool force_six = false);
-bool edge_gw_force_six(bool on);   // the process-wide switch; returns the previous setting
-bool edge_ge_fast(int Ce, int W2, long ldg, long gzb, long ldo, const void* gZ, const void* out);
+// Operands of the K = W2 -> 128 product (edge_ge_kernel): out[scatter[t], :] (+)= rows[t, :] @ W + bias.  One record for the
+// plain launch, the K-split launch (slabs != null), the launch on a prepared image (We == null) and the heads launch
+// (heads > 0); edge_ge_launch tells them apart by those fields.
+struct EdgeGeParams {
+  const float* gZ;       // the rows operand, element (t, 128 a + j) at gZ[t * ldg + a * gzb + j] (see above); unused with rc
+  long ldg, gzb;
+  const EdgeRC* rc;      // non-null: the rows are rebuilt from *rc (the per-edge launch of the scalar-attention backward)
+  const float* We;       // weight, element (col, k) at We[col * s_col + k * s_out] (col < W2 inputs, k < 128 outputs);
+  long s_col, s_out;     //   null: Wq already holds the six-pass image (prepare_T_planes_launch, alternate = 1) and is only read
+  float* Wq;             // the weight image: edge_z_wq_floats(W2) floats; heads: heads * edge_ge_heads_image_floats(W2) +
+                         //   bilinear_prepare_T_batch_ws_floats(heads)
+  int W2;                // input columns (K)
+  int rows;
+  float* out;            // [rows, 128], row stride ldo; row t goes to scatter[t] (null: t)
+  long ldo;
+  const int* scatter;
+  int accumulate;        // out += result
+  const float* bias;     // [128] or null: added to the product, before any accumulation into `out`
+  const float* amax;     // f16x3 mode only: device max |rows| -> the fp16 form; without it the six-pass form runs
+  // the K-split launch: group s of S multiplies its column blocks into slab s ([rows, 128] each at slabs + s * rows * 128,
+  // scattered rows as `out` would be); the caller adds the slabs in group order.  out / accumulate / bias / amax unused.
+  float* slabs;
+  int S;                 // edge_ge_ksplit_groups(rows, W2, rc != null)
+  // the heads launch: `heads` products y_h = x_h W_h^T + b_h in one launch pair, head h's operands at + h * s_* (elements);
+  // W_h [128, W2] row-major and contiguous (s_col == 1, s_out == W2)
+  int heads;
+  long s_x, s_w, s_bias, s_y;
+};
+// the plain launch on row-major or column-blocked rows (everything else: set the field)
+static inline EdgeGeParams edge_ge_params(const float* gZ, long ldg, long gzb, const float* We, long s_col, long s_out,
+                                          float* Wq, int W2, float* out, long ldo, int rows) {
+  EdgeGeParams p = {};
+  p.gZ = gZ; p.ldg = ldg; p.gzb = gzb; p.We = We; p.s_col = s_col; p.s_out = s_out; p.Wq = Wq; p.W2 = W2;
+  p.out = out; p.ldo = ldo; p.rows = rows;
+  return p;
+}
+// Which edge_ge_kernel a launch runs, on which image and grid: decided once per launch by edge_ge_form (host only;
+// DESIGN.md lists the forms) and read by the launcher, edge_ge_ksplit_groups' callers and the debug query.
+enum EdgeGePrep : int {
+  GE_PREP_NONE = 0,      // the caller's image
+  GE_PREP_PLANES = 1,    // three bf16 planes, odd blocks negated (all heads' in one launch)
+  GE_PREP_F16_TMAX = 2,  // two fp16 planes scaled by the weight's maximum, which is formed first
+  GE_PREP_ATTN = 3,      // three planes with the attention blocks scaled by wA, and their column sums (the bit-plane body)
+  GE_PREP_HEADS_F16 = 4  // the heads' maxima and fp16 planes by the contractions' batched preparation (opimage.hip)
+};
+struct EdgeGeForm {
+  int passes;            // edge_ge_kernel<PASSES, ., .>: 1 (one bf16 plane), 2 (two fp16 planes), 3 or 6 (three bf16 planes); 0: no rows
+  bool rc;               // <., RC, .>: rebuilt rows
+  bool bitplane;         // <6, true, BP>: the attention half on the stored bit
+  EdgeGePrep prep;
+  int grid_x;            // row tiles of 256
+  int groups, ncb_g;     // K groups over grid.y (1: none) and the column blocks of each
+  int heads;             // heads over grid.y (0: not the heads launch)
+};
+EdgeGeForm edge_ge_form(const EdgeGeParams& p);
+// the kernel's dims, leading dimensions and mode: 128 outputs, whole 128-column blocks, float4 rows (callers add aligned16)
+bool edge_ge_dims(int Ce, int W2, long ldg, long gzb, long ldo);
+// ... of the heads launch: x_h / y_h as edge_ge_dims, weights [128, W2] with ldw == W2, a mode that batches its heads
+bool edge_ge_heads_dims(int heads, int W2, long ldx, long ldy, long ldw, bool have_amax);
 size_t edge_ge_heads_image_floats(int W2);
-bool edge_ge_heads_fast(int heads, int W2, long ldx, long ldy, long ldw, const void* x, const void* w, const void* y,
-                        const float* amax);
-int edge_ge_heads_launch(int heads, const float* x, long ldx, long s_x, const float* W, long s_w, const float* bias,
-                         long s_bias, float* y, long ldy, long s_y, int E, int W2, float* ws, hipStream_t stream,
-                         const float* amax);
-int edge_ge_ksplit_groups(int E, int W2);   // K-split form for few row tiles: groups a launch takes (1: use edge_ge_launch)
-int edge_ge_ksplit_launch(const float* gZ, long ldg, long gzb, const float* We, long s_col, long s_out, float* Wq, int W2,
-                          float* slabs, const int* scatter, int E, int S, hipStream_t stream,
-                          const EdgeRC* rc = nullptr);   // S slabs [E,128]; caller sums
-int edge_ge_prepared_launch(const float* x, long ldx, const void* Wq, int ncb, float* out, long ldo, int rows,
-                            int accumulate, hipStream_t stream);   // six-pass image made by the caller (odd blocks negated)
-int edge_ge_launch(const float* gZ, long ldg, long gzb, const float* We, long s_col, long s_out, float* Wq, int W2,
-                   float* out, long ldo, const int* scatter, int E, int accumulate, const float* bias,
-                   hipStream_t stream,
-                   const float* amax = nullptr,            // amax: device max |gZ| -> fp16 form in the f16x3 mode
-                   const EdgeRC* rc = nullptr);
+// K-split form for few row tiles beside a long K: the groups a launch of this shape takes (1: the plain launch).  rebuilt:
+// the rows come from an EdgeRC
+int edge_ge_ksplit_groups(int rows, int W2, bool rebuilt);
+int edge_ge_launch(const EdgeGeParams& p, hipStream_t stream);
+
+// Operands of the K = E -> W2 x 128 product (edge_gw_kernel): out[col, :] = sum_t rows[t, col] * e[perm[t], :]
+struct EdgeGwParams {
+  const float* gZ;       // the rows operand as EdgeGeParams'; unused with rc
+  long ldg, gzb;
+  const EdgeRC* rc;      // non-null: the rows are rebuilt from *rc
+  const float* e;        // [., 128], row stride lde; slot t reads e[perm[t]] (null: e[t])
+  long lde;
+  const int* perm;
+  int E;                 // rows of gZ (the reduction index)
+  int W2;                // columns of gZ = rows of out
+  float* ws;             // edge_gw_ws_floats(E, W2) floats
+  float* out;            // [W2, 128], row stride ldo
+  long ldo;
+  const float* gmax;     // f16x3 mode only: device max |gZ| and max |e| -> the fp16 form; without them the six-pass form
+  const float* emax;
+  bool force_six;        // debug: this launch keeps the six-pass form on every column
+  const GwTe* te;        // non-null: the bit-plane form's reducer also adds the edge part of grad fc_out_A (above)
+};
+static inline EdgeGwParams edge_gw_params(const float* gZ, long ldg, long gzb, const float* e, long lde, const int* perm,
+                                          int E, int W2, float* ws, float* out, long ldo) {
+  EdgeGwParams p = {};
+  p.gZ = gZ; p.ldg = ldg; p.gzb = gzb; p.e = e; p.lde = lde; p.perm = perm; p.E = E; p.W2 = W2; p.ws = ws;
+  p.out = out; p.ldo = ldo;
+  return p;
+}
+// Which edge_gw_kernel a launch runs and how it carves its workspace: decided once per launch by edge_gw_form (host only)
+struct EdgeGwForm {
+  int passes;            // edge_gw_kernel<PASSES, ., .> of the plain form: 1, 2, 3 or 6; 0: no rows (out is zero-filled)
+  bool rc;               // <., RC, .>
+  bool bit_shape;        // mode and shape admit the bit-plane form -- what no debug switch changes (the bit form of the layer's
+                         // saved buffer rests on this alone)
+  bool bitplane;         // edge_gw_kernel<6, true, true> and its reducer write `out`; the plain form does not run
+  bool te_only;          // ... run for te alone (the debug switches keep the six-pass form), then the plain form writes `out`
+  int S, grid_x;         // the plain form: k-ranges, and workgroups = S * column-block pairs
+  int SA, SM, npm;       // the bit-plane form: k-ranges per attention pair / per message pair, message pairs
+  int bit_grid_x;        //   its workgroups: SM * npm + SA * H <= 256
+  size_t slab;           // floats from ws: the slabs (either form), behind the planes of e
+  size_t slabA, csl;     //   the bit-plane form's attention slabs and column sums
+  size_t ws_end;         //   the end of what the launch touches
+};
+EdgeGwForm edge_gw_form(const EdgeGwParams& p);
+// mode and shape of the bit-plane form for a scalar-attention layer of H heads of Hd (edge_gw_form's bit_shape)
+bool edge_gw_bitplane_layer(int H, int Hd);
+// the kernel's dims, leading dimensions and mode: 128 outputs, whole column-block pairs (callers add aligned16)
+bool edge_gw_dims(int Ce, int W2, long ldg, long gzb);
+size_t edge_gw_ws_floats(int E, int W2);
+bool edge_gw_force_six(bool on);   // debug: the process-wide switch; returns the previous setting
+int edge_gw_launch(const EdgeGwParams& p, hipStream_t stream);
 // Gj[n, :] = sum over the edges leaving n of the rebuilt gZ rows (src_rowptr / src_pos: slots grouped by source)
 int edge_gj_launch(const EdgeRC& rc, const int* src_rowptr, const int* src_pos, int N, int W2, float* Gj, long ldo,
                    hipStream_t stream, float* gjmax = nullptr);   // gjmax: max |Gj| folded in (zeroed by the caller)

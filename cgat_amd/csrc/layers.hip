@@ -157,7 +157,7 @@ static AttnFwdRoute attn_fwd_route(bool dry, const AttnDims& d, bool infer, cons
   // five 256-row workgroups streaming the whole weight image: 86 -> ~10 us per projection at 1 280 atoms)
   r.proj_fast = d.N > rowprog_max_rows() && edge_z_heads(d.W2, d.H, d.Hd) && edge_z_dims(d.C, d.W2, d.C, d.W2, d.W2) &&
                 aligned16(x, ws);
-  r.out_one = attn_out_one_shape(d) && edge_ge_fast(128, d.HHd, d.HHd, 128, d.C, S, aggr) && aligned16(p->M_out_w);
+  r.out_one = attn_out_one_shape(d) && edge_ge_dims(128, d.HHd, d.HHd, 128, d.C) && aligned16(S, aggr, p->M_out_w);
   return r;
 }
 
@@ -350,7 +350,8 @@ static int attn_fwd_out(Ctx& c, const AttnFwd& f) {
     // operand (a = block of head h, b = column in block, c = output) = M_out_w[h * C * Hd + c * Hd + 128 a + b]
     CGAT_TRY(prepare_T_planes_launch(p->M_out_w, c.scratch, ncb_h, 128, 1, d.Hd, /*alternate=*/1, c.s, nullptr, d.H,
                                      (long)d.C * d.Hd, (long)ncb_h * 24576));
-    CGAT_TRY(edge_ge_prepared_launch(sv.S, d.HHd, c.scratch, d.H * ncb_h, f.aggr, d.C, d.N, 0, c.s));
+    // (We == null: the image in the scratch region, all heads' blocks as one K = H * Hd operand)
+    CGAT_TRY(edge_ge_launch(edge_ge_params(sv.S, d.HHd, 128, nullptr, 0, 0, (float*)c.scratch, d.HHd, f.aggr, d.C, d.N), c.s));
   } else if (f.r.out_fast) {
     for (int h = 0; h < d.H; ++h)
       for (int j = 0; j < ncb_h; ++j) {
@@ -494,10 +495,12 @@ static int attn_fwd_out_indexed(Ctx& c, const AttnFwd& f) {
   c.need((size_t)d.H * ncb_h * 24576 * sizeof(float));
   CGAT_TRY(prepare_T_planes_launch(f.p->M_out_w, c.scratch, ncb_h, 128, 1, d.Hd, /*alternate=*/1, c.s, nullptr, d.H,
                                    (long)d.C * d.Hd, (long)ncb_h * 24576));
-  for (int h = 0; h < d.H; ++h)
-    CGAT_TRY(edge_ge_prepared_launch(f.sv.S + (size_t)h * d.Hd, d.HHd,
-                                     reinterpret_cast<const float*>(c.scratch) + (size_t)h * ncb_h * 24576, ncb_h, f.aggr,
-                                     d.C, d.N, h > 0 ? 1 : 0, c.s));
+  for (int h = 0; h < d.H; ++h) {   // (We == null: head h's blocks of the image, K = Hd)
+    EdgeGeParams g = edge_ge_params(f.sv.S + (size_t)h * d.Hd, d.HHd, 128, nullptr, 0, 0,
+                                    reinterpret_cast<float*>(c.scratch) + (size_t)h * ncb_h * 24576, d.Hd, f.aggr, d.C, d.N);
+    g.accumulate = h > 0 ? 1 : 0;
+    CGAT_TRY(edge_ge_launch(g, c.s));
+  }
   GemmParams g = gemm_params(d.N, d.C, d.H, f.sv.ssum, d.H, f.p->M_out_b, d.C, f.aggr, d.C);
   g.b_kmajor = 1;
   g.alpha = 1.f / d.H;
@@ -569,14 +572,14 @@ static TailRoute tail_route(bool dry, const AttnDims& d, const EdgeTail& t) {
   r.node_scales = t.rc ? maxima
                        : maxima && t.node_scales && !dry && d.N > 0 && d.W2 % 128 == 0 && aligned16(t.Gi, t.Gj);
   // (K-split forms of the two K = W2 -> 128 products at few row tiles, edgebwd.hip: slabs in the scratch region)
-  r.Sx = (!r.node_scales && d.C == 128) ? edge_ge_ksplit_groups(d.N, d.W2) : 1;
-  r.Se = (!t.scales && d.Ce == 128 && !(t.rc && edge_mma_bf16())) ? edge_ge_ksplit_groups(d.E, d.W2) : 1;
-  const bool node_fast = !dry && d.N > 0 && edge_ge_fast(d.C, d.W2, d.W2, 128, d.C, t.Gi, t.g_x) &&
-                         edge_gw_fast(d.C, d.W2, d.W2, 128, t.Gi) && aligned16(t.Gj, t.x) && d.N <= d.E;
+  r.Sx = (!r.node_scales && d.C == 128) ? edge_ge_ksplit_groups(d.N, d.W2, false) : 1;
+  r.Se = (!t.scales && d.Ce == 128) ? edge_ge_ksplit_groups(d.E, d.W2, t.rc != nullptr) : 1;
+  const bool node_fast = !dry && d.N > 0 && edge_ge_dims(d.C, d.W2, d.W2, 128, d.C) && edge_gw_dims(d.C, d.W2, d.W2, 128) &&
+                         aligned16(t.Gi, t.g_x, t.Gj, t.x) && d.N <= d.E;
   r.node = !node_fast ? NODE_GEMM : r.Sx > 1 ? NODE_KSPLIT : d.N <= rowprog_max_rows() ? NODE_SMALL_ROWS : NODE_LAUNCHES;
-  const bool ge_fast = !dry && edge_ge_fast(d.Ce, d.W2, t.gZ.ld, t.gZ.block, d.Ce, t.gZ.ptr, t.g_e);
+  const bool ge_fast = !dry && edge_ge_dims(d.Ce, d.W2, t.gZ.ld, t.gZ.block, d.Ce) && aligned16(t.gZ.ptr, t.g_e);
   r.ge = !ge_fast ? PRODUCT_GEMM : r.Se > 1 ? PRODUCT_KSPLIT : PRODUCT_LAUNCH;
-  r.gw = (!dry && edge_gw_fast(d.Ce, d.W2, t.gZ.ld, t.gZ.block, t.gZ.ptr)) ? PRODUCT_LAUNCH : PRODUCT_GEMM;
+  r.gw = (!dry && edge_gw_dims(d.Ce, d.W2, t.gZ.ld, t.gZ.block) && aligned16(t.gZ.ptr)) ? PRODUCT_LAUNCH : PRODUCT_GEMM;
   return r;
 }
 static long tail_xblock(const AttnDims& d, const EdgeTail& t) {   // block stride of a stored gZ; 0 = plain row-major
@@ -617,6 +620,12 @@ static int tail_gx_gemm_pair(Ctx& c, const AttnDims& d, const EdgeTail& t) {   /
 static int tail_node_products(Ctx& c, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
   const float* ns = r.node_scales ? t.scales + 2 : nullptr;
   const float* Wj = t.Wcat + d.C + d.Ce;
+  // the node-side records: g_x (+)= G W for G = Gi, Gj [N, W2] row-major, and grad W = G^T x
+  EdgeGeParams gi = edge_ge_params(t.Gi, d.W2, 128, t.Wcat, d.D, 1, t.Wq, d.W2, t.g_x, d.C, d.N);
+  EdgeGeParams gj = edge_ge_params(t.Gj, d.W2, 128, Wj, d.D, 1, t.Wq, d.W2, t.g_x, d.C, d.N);
+  EdgeGwParams wi = edge_gw_params(t.Gi, d.W2, 128, t.x, d.C, nullptr, d.N, d.W2, t.gw_ws, t.gWcat, d.D);
+  EdgeGwParams wj = edge_gw_params(t.Gj, d.W2, 128, t.x, d.C, nullptr, d.N, d.W2, t.gw_ws, t.gWcat + d.C + d.Ce, d.D);
+  if (ns) { gi.amax = wi.gmax = ns; gj.amax = wj.gmax = ns + 1; wi.emax = wj.emax = ns + 2; }
   if (r.Sx > 1) c.need((size_t)2 * r.Sx * d.N * 128 * sizeof(float));
   if (r.node == NODE_GEMM) {
     CGAT_TRY(tail_gx_gemm_pair(c, d, t));
@@ -631,35 +640,37 @@ static int tail_node_products(Ctx& c, const AttnDims& d, const EdgeTail& t, cons
   if (r.node == NODE_KSPLIT) {
     // g_x = Gi W_i + Gj W_j as 2 Sx slabs, added in order (round 6: 2 x 100 us of fp64 small-row products -> 3 launches)
     float* sl = (float*)c.scratch;
-    RUN(edge_ge_ksplit_launch(t.Gi, d.W2, 128, t.Wcat, d.D, 1, t.Wq, d.W2, sl, nullptr, d.N, r.Sx, c.s));
-    RUN(edge_ge_ksplit_launch(t.Gj, d.W2, 128, Wj, d.D, 1, t.Wq, d.W2, sl + (size_t)r.Sx * d.N * 128, nullptr, d.N, r.Sx, c.s));
+    gi.slabs = sl; gj.slabs = sl + (size_t)r.Sx * d.N * 128;
+    gi.S = gj.S = r.Sx;
+    RUN(edge_ge_launch(gi, c.s));
+    RUN(edge_ge_launch(gj, c.s));
     RUN(sum_slabs_launch(sl, 2 * r.Sx, (long)d.N * 128, t.g_x, (long)d.N * 128, c.s));
   } else if (r.node == NODE_SMALL_ROWS) {
     // a few hundred atoms: the 256-row tiles of the per-edge kernel are 5 workgroups walking K = 1536 (91 us a launch
     // at 1 280 atoms); as 16 x 16 wave tiles with the k range dealt over a workgroup's waves the chip is full
     CGAT_TRY(tail_gx_gemm_pair(c, d, t));
   } else {
-    RUN(edge_ge_launch(t.Gi, d.W2, 128, t.Wcat, d.D, 1, t.Wq, d.W2, t.g_x, d.C, nullptr, d.N, 0, nullptr, c.s, ns));
-    RUN(edge_ge_launch(t.Gj, d.W2, 128, Wj, d.D, 1, t.Wq, d.W2, t.g_x, d.C, nullptr, d.N, 1, nullptr, c.s,
-                       ns ? ns + 1 : nullptr));
+    gj.accumulate = 1;
+    RUN(edge_ge_launch(gi, c.s));
+    RUN(edge_ge_launch(gj, c.s));
   }
-  RUN(edge_gw_launch(t.Gi, d.W2, 128, t.x, d.C, nullptr, d.N, d.W2, t.gw_ws, t.gWcat, d.D, c.s, ns, ns ? ns + 2 : nullptr));
-  RUN(edge_gw_launch(t.Gj, d.W2, 128, t.x, d.C, nullptr, d.N, d.W2, t.gw_ws, t.gWcat + d.C + d.Ce, d.D, c.s,
-                     ns ? ns + 1 : nullptr, ns ? ns + 2 : nullptr));
+  RUN(edge_gw_launch(wi, c.s));
+  RUN(edge_gw_launch(wj, c.s));
   return c.colsum(t.Gi, d.W2, d.N, d.W2, t.gbcat, 1.f);
 }
 
 // grad edge_attr[perm[t]] = gZ[t] @ W_e: split-bf16 kernel at the benchmark widths, generic GEMM otherwise
 static int tail_edge_ge(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
   if (r.Se > 1) c.need((size_t)r.Se * d.E * 128 * sizeof(float));
+  EdgeGeParams g = edge_ge_params(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.Wcat + d.C, d.D, 1, t.Wq, d.W2, t.g_e, d.Ce, d.E);
+  g.rc = t.rc; g.scatter = plan->dst_perm;
   if (r.ge == PRODUCT_KSPLIT) {
-    float* sl = (float*)c.scratch;
-    RUN(edge_ge_ksplit_launch(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.Wcat + d.C, d.D, 1, t.Wq, d.W2, sl, plan->dst_perm, d.E, r.Se,
-                              c.s, t.rc));
-    RUN(sum_slabs_launch(sl, r.Se, (long)d.E * 128, t.g_e, (long)d.E * 128, c.s));
+    g.slabs = (float*)c.scratch; g.S = r.Se;
+    RUN(edge_ge_launch(g, c.s));
+    RUN(sum_slabs_launch(g.slabs, r.Se, (long)d.E * 128, t.g_e, (long)d.E * 128, c.s));
   } else if (r.ge == PRODUCT_LAUNCH) {
-    RUN(edge_ge_launch(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.Wcat + d.C, d.D, 1, t.Wq, d.W2, t.g_e, d.Ce, plan->dst_perm, d.E, 0,
-                       nullptr, c.s, t.scales, t.rc));
+    g.amax = t.scales;
+    RUN(edge_ge_launch(g, c.s));
   } else {
     GemmParams g = gemm_params(d.E, d.Ce, d.W2, t.gZ.ptr, t.gZ.ld, t.Wcat + d.C, d.D, t.g_e, d.Ce);
     g.a_block = tail_xblock(d, t);
@@ -672,8 +683,12 @@ static int tail_edge_ge(Ctx& c, const cgat_plan* plan, const AttnDims& d, const 
 // grad W_e = gZ^T @ e[perm]
 static int tail_edge_gw(Ctx& c, const cgat_plan* plan, const AttnDims& d, const EdgeTail& t, const TailRoute& r) {
   if (r.gw == PRODUCT_LAUNCH) {
-    RUN(edge_gw_launch(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.e, d.Ce, plan->dst_perm, d.E, d.W2, t.gw_ws, t.gWcat + d.C, d.D, c.s,
-                       t.scales, t.scales ? t.scales + 1 : nullptr, t.rc, t.gw_force_six, t.te.out ? &t.te : nullptr));
+    EdgeGwParams w = edge_gw_params(t.gZ.ptr, t.gZ.ld, t.gZ.block, t.e, d.Ce, plan->dst_perm, d.E, d.W2, t.gw_ws,
+                                    t.gWcat + d.C, d.D);
+    w.rc = t.rc; w.force_six = t.gw_force_six;
+    if (t.scales) { w.gmax = t.scales; w.emax = t.scales + 1; }
+    if (t.te.out) w.te = &t.te;
+    RUN(edge_gw_launch(w, c.s));
     return CGAT_OK;
   }
   CGAT_CHECK_ARG(!t.te.out, "nodes_attention_backward: the bit form of the saved buffer needs grad W_e's per-edge launch");
@@ -1577,7 +1592,11 @@ extern "C" int cgat_debug_edge_gw_rebuilt(const uint32_t* mask, const float* ga,
   CGAT_CHECK_ARG(ws_bytes >= cgat_debug_edge_gw_rebuilt_workspace_bytes(E, H, Hd) && aligned16(gS, wA, e) && aligned16(out, ws),
                  "debug_edge_gw_rebuilt: workspace too small or operands not 16-byte aligned");
   const EdgeRC rc = edge_rc_make(mask, ga, alpha, gS, wA, dst, H, Hd);
-  if (took_bitplane) *took_bitplane = edge_gw_takes_bitplane(&rc, W2, perm, force_six != 0) ? 1 : 0;
+  if (took_bitplane) {   // the form of a record like the launch's own (tail_edge_gw); not launched
+    EdgeGwParams w = edge_gw_params(nullptr, 128, (long)E * 128, e, 128, perm, E, W2, nullptr, out, 128);
+    w.rc = &rc; w.force_six = force_six != 0;
+    *took_bitplane = edge_gw_form(w).bitplane ? 1 : 0;
+  }
   return run_sized("debug_edge_gw_rebuilt", ws, ws_bytes, stream,
                    [&](Ctx& c) { return debug_edge_gw_impl(c, rc, e, perm, E, force_six != 0, out); });
 }

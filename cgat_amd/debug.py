@@ -207,6 +207,29 @@ def edge_z_form(rows, W2, H=1, Hd=128, n_add_rows=0, ld_add=None, store="f32", a
     return d
 
 
+EDGE_GE_LAUNCHES = ("plain", "ksplit", "prepared", "heads")      # cgat_debug_edge_bwd_form's `launch` for product "ge"
+EDGE_GE_PREPS = ("none", "planes", "f16_tmax", "attn", "heads_f16")    # cgat_edge_bwd_form.prep
+
+
+def edge_bwd_form(product, rows, W2, H=1, Hd=128, launch="plain", rebuilt=False, maxima=False, perm=False, force_six=False,
+                  te=False):
+    """Which form a launch of the backward per-edge family (csrc/edgebwd.hip) runs at these dims in the current arithmetic
+    and edge-storage modes: product "ge" (rows @ W, K = W2 -> 128) or "gw" (rows^T @ e, K = rows), as a dict of the fields
+    of cgat_edge_bwd_form that belong to the product, `prep` by name (host only, no GPU needed); None where the launch
+    refuses the combination."""
+    f = _lib.EdgeBwdForm()
+    rc = lib.cgat_debug_edge_bwd_form(("ge", "gw").index(product), EDGE_GE_LAUNCHES.index(launch), rows, W2, H, Hd, int(rebuilt),
+                                      int(maxima), int(perm), int(force_six), int(te), C.byref(f))
+    if rc != 0:
+        return None
+    if product == "ge":
+        d = {n: getattr(f, n) for n in ("passes", "rc", "bitplane", "prep", "grid_x", "groups", "blocks_per_group", "heads")}
+        d["prep"] = EDGE_GE_PREPS[f.prep]
+        return d
+    return {n: getattr(f, n) for n in ("passes", "rc", "bitplane", "grid_x", "bit_shape", "te_only", "ranges", "SA", "SM",
+                                       "message_pairs", "bit_grid_x", "ws_end", "ws_floats")}
+
+
 def edge_ge_rebuilt(mask, ga, alpha, gS, wA, dst, We, H, Hd):
     """grad edge_attr's product alone on caller-supplied ingredients of the rebuilt rows (cgat_debug_edge_ge_rebuilt,
     include/cgat_hip.h): mask int32 [E, 2 H Hd / 32] bit words, ga / alpha [E, H], gS [N, H Hd], wA [H Hd], dst int32 [E],

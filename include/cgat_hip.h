@@ -328,6 +328,40 @@ int cgat_debug_edge_z_form(int32_t launch, int32_t rows, int32_t W2, int32_t H, 
                            int64_t ld_add, int32_t store, int32_t adds, int32_t logits, int32_t omax, int32_t act,
                            cgat_edge_z_form* out);
 
+/* Debug (tests only): WHICH FORM a launch of the backward per-edge family (csrc/edgebwd.hip) runs in the current arithmetic
+ * and edge-storage modes -- host only, no device call.  The forms of one launch agree within tolerance (the bit-plane and
+ * K-split forms re-round), so no parity test can tell which ran; this names it.
+ *   product 0: out[t, :] = rows[t, :] @ W (edge_ge_kernel, K = W2 -> 128), launch 0 the plain launch, 1 the K-split launch
+ *              with the groups the layers would give it, 2 on a caller-prepared image, 3 the heads launch (H heads);
+ *           1: out[col, :] = sum_t rows[t, col] e[perm[t], :] (edge_gw_kernel, K = rows), launch 0.
+ *   rows, W2 (columns of the row operand), H, Hd (the heads of a rebuilt row operand);
+ *   rebuilt: the rows are rebuilt from sign bits and coefficients (the scalar-attention backward's per-edge launches);
+ *   maxima: the f16x3 mode's operand maxima are given; perm: a scatter (product 0) / slot permutation (product 1) is given;
+ *   force_six, te (product 1): the launch's debug switch; the edge part of grad fc_out_A is asked for.
+ * CGAT_ERR_ARG (1) where the launch itself refuses the combination. */
+typedef struct cgat_edge_bwd_form {
+  int32_t passes;            /* matrix passes of the product: 1 (one bf16 plane), 2 (fp16 planes), 3 or 6 (bf16 planes); 0: no rows */
+  int32_t rc;                /* the kernel variant that rebuilds its rows */
+  int32_t bitplane;          /* the attention half runs on the stored bit */
+  int32_t prep;              /* product 0, the weight image: 0 the caller's, 1 three bf16 planes, 2 fp16 planes scaled by the tensor
+                                maximum, 3 the attention-scaled image with column sums, 4 the batched fp16 images of the heads */
+  int32_t grid_x;            /* product 0: row tiles of 256; product 1: workgroups of the plain form */
+  int32_t groups;            /* product 0: K groups over grid.y (1: none) */
+  int32_t blocks_per_group;  /*            128-column blocks each group walks */
+  int32_t heads;             /*            heads over grid.y (0: not the heads launch) */
+  int32_t bit_shape;         /* product 1: mode and shape admit the bit-plane form, whatever the debug switches say */
+  int32_t te_only;           /*            the bit-plane form runs for the edge part of grad fc_out_A alone, the plain form writes out */
+  int32_t ranges;            /*            k-ranges per column-block pair of the plain form */
+  int32_t SA, SM;            /*            k-ranges per attention pair / per message pair of the bit-plane form (0: no such shape) */
+  int32_t message_pairs;
+  int32_t bit_grid_x;        /*            workgroups of the bit-plane form: SM * message_pairs + SA * H */
+  int32_t reserved;
+  int64_t ws_end;            /*            floats of workspace the launch touches; ws_floats: what the size query returns */
+  int64_t ws_floats;
+} cgat_edge_bwd_form;
+int cgat_debug_edge_bwd_form(int32_t product, int32_t launch, int32_t rows, int32_t W2, int32_t H, int32_t Hd, int32_t rebuilt,
+                             int32_t maxima, int32_t perm, int32_t force_six, int32_t te, cgat_edge_bwd_form* out);
+
 /* Debug / parity instrumentation (tests only, not on the hot path): the LeakyReLU derivative pattern the backward of
  * cgat_nodes_attention_forward will use -- mask[e, c] = (Z[slot(e), c] > 0) for the pre-activations of MH_A (columns
  * [0, H*Hd)) and MH_M ([H*Hd, 2*H*Hd)) of CGAT/CGAT.py:96,105-108, in ORIGINAL edge order.  LeakyReLU's derivative
