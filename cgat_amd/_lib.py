@@ -267,6 +267,10 @@ PROTOTYPES = {
     "cgat_neighbor_tables": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
     "cgat_debug_neighbor_tables": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double,
                                              vp, vp, vp, vp, vp, vp, vp]),
+    "cgat_pack_dataset_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cgat_pack_dataset_plan": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_size_t, vp]),
+    "cgat_pack_dataset_write": (C.c_int, [vp] * 7 + [C.c_int32] * 6 + [vp, vp, C.c_size_t] + [C.c_int32] * 3 + [vp] * 10 +
+                                [vp]),
     "cgat_bilinear_dual_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "cgat_bilinear_dual": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp,
                                      C.c_int64, vp, C.c_int64, C.c_int32, vp, C.c_size_t, vp]),

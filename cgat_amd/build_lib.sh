@@ -4,7 +4,7 @@ set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 OUT="$HERE/libcgat_hip.so"
-SRCS=(api gemm gemmsplit bilinear opimage bilwgrad wgradc edgez edgebwd rowsdw collate optim rowops segment edgecomb edgeidx plan layers hnet segbwd chain rowprog neighbors gphead)
+SRCS=(api gemm gemmsplit bilinear opimage bilwgrad wgradc edgez edgebwd rowsdw collate optim rowops segment edgecomb edgeidx plan layers hnet segbwd chain rowprog neighbors gphead pack)
 OBJS=()
 PIDS=()
 mkdir -p "$HERE/csrc/build"

@@ -123,6 +123,43 @@ int cgat_debug_neighbor_tables(const double* lattice, const double* frac, const 
                                int32_t* self_idx, int32_t* nbr_idx, double* dist, int32_t* status, int32_t* passes,
                                void* stream);
 
+/* ---- packing a dataset on the device (between the neighbour tables and the first batch) -----------
+ * replaces the per-crystal host loop of cgat_amd/collate.py:72-95 (PackedDataset.from_dict) and, in the reference,
+ * CGAT/data.py:61-103 and 140-141 (CompositionData.__getitem__: element rows, composition, tables sliced to
+ * max_neighbor_number, y = target * n_atoms) with the slicing into per-crystal arrays before it
+ * (cgat_amd/neighbors.py dataset_dict_from_structures; CGAT/prepare_data.py:146-169).  Inputs, all device pointers:
+ * atom_ptr [G+1] (non-decreasing from 0 to N), atom_elem [N] rows of the embedding table, shell / self_idx / nbr_idx
+ * [N, Ks] as cgat_neighbor_tables writes them, status [G] or NULL (a crystal is kept iff its status is 0; NULL keeps all),
+ * target [G] fp64 per-cell values or NULL (y = 0).  Outputs are the arrays of a cgat_packed_dataset for the kept crystals
+ * in input order, bit-identical to the host loop's: atom_ptr' [Gk+1], atom_elem' [Nk], the first K <= Ks columns of every
+ * kept row as [Nk, K], comp_ptr' [Gk+1], comp_elem' [Uk] (the crystal's distinct ids in first-appearance order, not
+ * sorted), comp_weight' [Uk] = (float)((double)count / (double)n_atoms), y_val [Gk] = (float)(target / (double)n) * (float)n
+ * in target_mode 0 and (float)(target / (double)n) in target_mode 1 (the reference's target == "volume"), kept [Gk]
+ * (indices into the input crystals).
+ *   cgat_pack_dataset_plan   fills the workspace (per-crystal distinct counts and output offsets: exclusive prefix sums
+ *       over the crystals, tiled, no atomics) and totals[4] = {Gk, Nk, Uk, bad}: bad counts the element ids outside
+ *       [0, n_elem) plus the crystals whose atom_ptr range does not lie inside [0, N] (those read as empty).
+ *   cgat_pack_dataset_write  writes the outputs; the caller has read totals, allocated exactly those sizes and passes
+ *       them back as Gk, Nk, Uk with the same inputs, workspace and totals.  A write whose sizes differ from the record,
+ *       or whose workspace came from other inputs, writes nothing outside the given sizes.
+ * Distinct elements are found by comparing ids, nothing is gathered through one: no bound on n_elem or on the atoms of a
+ * crystal, and a bad id cannot fault.  1 <= K <= Ks, N * Ks < 2^31.  Rows are copied 16 bytes at a time when K and Ks are
+ * multiples of 4 and the tables are 16-byte aligned.  Bitwise deterministic; caller's stream, no allocation, no host
+ * synchronisation in either call. */
+size_t cgat_pack_dataset_workspace_bytes(int32_t G, int32_t N);
+int cgat_pack_dataset_plan(const int32_t* atom_ptr /* [G+1] */, const int32_t* atom_elem /* [N] */,
+                           const int32_t* status /* [G] or NULL */, int32_t G, int32_t N, int32_t n_elem,
+                           int32_t* totals /* [4] */, void* ws, size_t ws_bytes, void* stream);
+int cgat_pack_dataset_write(const int32_t* atom_ptr, const int32_t* atom_elem, const int32_t* shell /* [N,Ks] */,
+                            const int32_t* self_idx, const int32_t* nbr_idx, const int32_t* status,
+                            const double* target /* [G] or NULL */, int32_t G, int32_t N, int32_t Ks, int32_t K,
+                            int32_t n_elem, int32_t target_mode, const int32_t* totals, const void* ws, size_t ws_bytes,
+                            int32_t Gk, int32_t Nk, int32_t Uk, int32_t* out_atom_ptr /* [Gk+1] */,
+                            int32_t* out_atom_elem /* [Nk] */, int32_t* out_shell /* [Nk,K] */, int32_t* out_self_idx,
+                            int32_t* out_nbr_idx, int32_t* out_comp_ptr /* [Gk+1] */, int32_t* out_comp_elem /* [Uk] */,
+                            float* out_comp_weight /* [Uk] */, float* out_y_val /* [Gk] */, int32_t* kept /* [Gk] */,
+                            void* stream);
+
 /* Gradient of a small embedding table looked up once per edge (reference CGAT/CGAT.py: nbr_embedding =
  * nn.Embedding(neighbor_number + 1, nbr_embedding_size), CGAtNet.forward): g_table[k, :] = sum_{t: idx[t] == k} g[t, :].
  * Deterministic (no atomics).  idx: int64 [rows]; C <= 128, K * C <= 8192. */
