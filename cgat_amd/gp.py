@@ -2,8 +2,9 @@
 
 The reference's screening / active-learning flow continues past the graph embedding: `train-GP`
 (CGAT/gaussian_process.py) fits a sparse variational GP on the embeddings and Utilities/gp_predict.py writes, per
-candidate, `prediction` and `uncertainty = upper - prediction`.  This module is the PREDICTION side of that GP, fused
-into one HIP launch (csrc/gphead.hip); training the GP (the ELBO) is out of scope.
+candidate, `prediction` and `uncertainty = upper - prediction`.  This module is the prediction side of that GP, fused
+into one HIP launch (csrc/gphead.hip), and a fit of the head on the device (`GPHead.fit`; below).  Learning
+the inducing points and the lengthscale by stochastic gradient, as the reference's AdamW loop does, is out of scope.
 
 Model (gaussian_process.py:45-66, evaluated at :247-268): ScaleKernel(RBFKernel) with one lengthscale l and outputscale
 s, ConstantMean c (0 under --zero-mean), whitened VariationalStrategy with a CholeskyVariationalDistribution (mean m,
@@ -23,8 +24,32 @@ indefinite form k^T B k loses the variance in fp32 when K_zz is poorly condition
     unc = head.uncertainty(embeddings)                   # upper - pred, gp_predict.py:29
     pred, lower, upper = head.predict_batch(model, batch, b_comp)
 
-Inference only: outputs carry no grad; non-GPU and non-fp32 inputs are refused like everywhere else in the package.
+Fit (gaussian_process.py:59, :233: VariationalELBO under a GaussianLikelihood).  For a Gaussian likelihood the bound has
+a closed-form maximiser in (m, L_S) for fixed (Z, l, s, noise sigma^2, c): Titsias' collapsed bound.  With
+a_n = W1 k(Z, x_n), y~ = (y - mean) / std and the augmented row a~_n = [a_n, y~_n, 1] the data enter only through
+
+    G = sum_n a~_n a~_n^T  [(M+2) x (M+2)]:   Psi = G[:M,:M],  Ay = G[:M,M],  A1 = G[:M,M+1],  y~.y~,  sum y~,  N
+
+one streaming pass over the embeddings (`fit_statistics`: csrc/gpfit.hip, the whitened rows accumulated, fp32 products,
+fp64 sums).  With beta = Ay - c A1, rr = y~.y~ - 2 c sum y~ + c^2 N and Lambda = I + Psi / sigma^2 (`solve_collapsed`,
+host fp64):
+
+    S = Lambda^-1,   m = Lambda^-1 beta / sigma^2,   L_S = chol(S)
+    F = -N/2 log(2 pi sigma^2) - 1/2 log|Lambda| - rr / (2 sigma^2) + beta^T Lambda^-1 beta / (2 sigma^4)
+        - (N s - tr Psi) / (2 sigma^2)
+
+F is the bound sum_n E_q[log N(y~_n | f_n, sigma^2)] - KL(q(v) || N(0, I)) at that (m, L_S), in total nats.  c has a
+closed form (F is quadratic in it), sigma^2 is found by a bounded 1-D search, l and s come from a caller's grid by the
+larger F, Z is a fixed subset of the training rows (the reference's initialisation, :223-226).  gpytorch's
+VariationalELBO is meant to be this bound divided by N (`elbo_per_point`); gpytorch is not installed where this package
+is built, so that scaling is unconfirmed, like the default of `jitter`.
+
+    head, report = GPHead.fit(embeddings, targets, inducing_points=1000, lengthscale="median")
+
+Outputs carry no grad; non-GPU and non-fp32 inputs are refused like everywhere else in the package.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -40,6 +65,181 @@ def _pack_image(P):
     img[((c Kd/8 + k8) 64 + lane) 4 + q] = P[32 c + (lane & 31)][8 k8 + 2 q + (lane >> 5)]."""
     R, Kd = P.shape
     return P.view(R // 32, 32, Kd // 8, 4, 2).permute(0, 2, 4, 1, 3).contiguous().view(-1)
+
+
+def _centred64(Z):
+    """In fp64 on the host, from Z [M, D] (fp64, CPU): the centroid of Z, Zc = Z - centroid, |zc|^2."""
+    cen = Z.mean(dim=0)
+    Zc = Z - cen
+    return cen, Zc, (Zc * Zc).sum(dim=1)
+
+
+def _whitening64(Zc, zn, s, ell, jitter):
+    """In fp64 on the host: L = chol(K_zz + jitter I) and W1 = L^-1 (exactly lower triangular)."""
+    M = Zc.shape[0]
+    d2 = (zn[:, None] + zn[None, :] - 2.0 * (Zc @ Zc.T)).clamp_min(0.0)
+    d2.fill_diagonal_(0.0)
+    Kzz = s * torch.exp(-0.5 * d2 / (ell * ell))
+    L = torch.linalg.cholesky(Kzz + jitter * torch.eye(M, dtype=torch.float64))
+    W1 = torch.linalg.solve_triangular(L, torch.eye(M, dtype=torch.float64), upper=False).tril()
+    return L, W1
+
+
+def _tile_operands(cen, Zc, zn, dev):
+    """The fp32 operands of phase (a) of both kernels on `dev`: the packed image of Zc [Mp, Dp], the centroid, |zc|^2
+    [Mp]; padding is zero."""
+    M, D = Zc.shape
+    Mp, Dp = (M + 31) // 32 * 32, (D + 63) // 64 * 64
+    Zp = torch.zeros(Mp, Dp, dtype=torch.float32)
+    Zp[:M, :D] = Zc
+    znp = torch.zeros(Mp, dtype=torch.float32)
+    znp[:M] = zn
+    return dict(zimg=_pack_image(Zp).to(dev), centroid=cen.to(torch.float32).to(dev), znorm=znp.to(dev))
+
+
+def _check_embeddings(what, embeddings, D):
+    """[N, D] fp32 on the GPU, unit column stride and a row stride of at least D (copied otherwise)."""
+    if not isinstance(embeddings, torch.Tensor) or embeddings.dim() != 2:
+        raise ValueError(f"{what}: embeddings must be a [N, D] tensor")
+    if embeddings.dtype != torch.float32:
+        raise TypeError(f"cgat_amd: expected float32, got {embeddings.dtype}")
+    if embeddings.shape[1] != D:
+        raise ValueError(f"{what}: embeddings have width {embeddings.shape[1]}, the inducing points {D}")
+    _require_gpu(embeddings)
+    x = embeddings.detach()
+    if x.shape[0] and (x.stride(1) != 1 or x.stride(0) < D):
+        x = x.contiguous()
+    return x
+
+
+DEFAULT_CHUNK_ROWS = 32768
+
+
+class _StatisticsPass:
+    """What a cgat_gp_fit_stats call needs and (l, s) do not change: the checked operands, the centred image of Z on the
+    device, the workspace, the output.  Calling it with (s, l, jitter) factors K_zz on the host in fp64, uploads the
+    image of W1 and enqueues the pass; a later call overwrites the same `gram`."""
+
+    def __init__(self, what, embeddings, y_norm, inducing_points, chunk_rows):
+        Z = torch.as_tensor(inducing_points)
+        if Z.dim() != 2 or Z.shape[0] < 1 or Z.shape[1] < 1:
+            raise ValueError(f"{what}: inducing_points must be [M, D], got {tuple(Z.shape)}")
+        self.M, self.D = Z.shape
+        self.chunk = DEFAULT_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+        if self.chunk < 32 or self.chunk % 32:
+            raise ValueError(f"{what}: chunk_rows = {self.chunk} is not a positive multiple of 32")
+        self.what = what
+        self.x = _check_embeddings(what, embeddings, self.D)
+        self.N, dev = self.x.shape[0], self.x.device
+        y = torch.as_tensor(y_norm)
+        if y.numel() != self.N or self.N < 1:
+            raise ValueError(f"{what}: {self.N} rows of embeddings, {y.numel()} targets (at least one row is needed)")
+        self.y32 = y.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        cen, self.Zc, self.zn = _centred64(Z.detach().to("cpu", torch.float64))
+        self.ops = _tile_operands(cen, self.Zc, self.zn, dev)
+        self.gram = torch.empty(self.M + 2, self.M + 2, dtype=torch.float64, device=dev)
+        self.ws_bytes = _lib.lib.cgat_gp_fit_stats_workspace_bytes(self.N, self.M, self.D, self.chunk)
+        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
+
+    def __call__(self, outputscale, lengthscale, jitter):
+        s, ell = float(outputscale), float(lengthscale)
+        if not (s > 0.0 and ell > 0.0):
+            raise ValueError(f"{self.what}: outputscale and lengthscale must be positive")
+        M, x, ops, dev = self.M, self.x, self.ops, self.x.device
+        _, W1 = _whitening64(self.Zc, self.zn, s, ell, float(jitter))
+        Mp = (M + 31) // 32 * 32
+        W1p = torch.zeros(Mp, Mp, dtype=torch.float32)
+        W1p[:M, :M] = W1
+        w1img = _pack_image(W1p).to(dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib.cgat_gp_fit_stats(_ptr(x), x.stride(0), _ptr(self.y32), self.N, self.D, _ptr(ops["zimg"]), M,
+                                            _ptr(ops["centroid"]), _ptr(ops["znorm"]), _ptr(w1img), s, 0.5 / (ell * ell),
+                                            self.chunk, _ptr(self.gram), _ptr(self.ws), self.ws_bytes, _stream())
+        _lib.check(rc, "cgat_gp_fit_stats")
+        return self.gram
+
+
+def fit_statistics(embeddings, y_norm, inducing_points, outputscale, lengthscale, jitter=1e-4, chunk_rows=None):
+    """G = sum_n a~_n a~_n^T, a~_n = [W1 k(Z, x_n), y_norm[n], 1], as an fp64 [M+2, M+2] tensor on the device of
+    `embeddings` (one cgat_gp_fit_stats call; layout in include/cgat_hip.h).  `embeddings` [N, D] fp32 on the GPU,
+    `y_norm` [N] the normalised targets, `inducing_points` [M, D] (any device; its factors are computed on the host in
+    fp64 exactly as GPHead.prepare() does and rounded to fp32).  `chunk_rows`: rows per chunk, a positive multiple of 32
+    (default 32768)."""
+    return _StatisticsPass("fit_statistics", embeddings, y_norm, inducing_points, chunk_rows)(outputscale, lengthscale,
+                                                                                              jitter)
+
+
+_LOG_NOISE_BOUNDS = (math.log(1e-8), math.log(1e2))     # of sigma^2, in units of the normalised targets' variance
+
+
+def solve_collapsed(gram, N, outputscale, noise=None, zero_mean=False):
+    """The maximiser of the bound from its statistics, on the host in fp64.  `gram` [M+2, M+2] as fit_statistics returns
+    it, `N` the number of rows, `outputscale` the s it was computed with.  `noise`: the likelihood's sigma^2 (of the
+    normalised targets), or None for a bounded search over log sigma^2 in [1e-8, 1e2] (a grid, then golden section).
+    Returns a dict: variational_mean [M], chol_variational_covar [M, M] (lower), constant, noise, elbo (total nats).
+    Eigenvalues of Psi are clamped at 0."""
+    G = torch.as_tensor(gram).detach().to("cpu", torch.float64)
+    if G.dim() != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 3:
+        raise ValueError(f"solve_collapsed: gram must be [M+2, M+2], got {tuple(G.shape)}")
+    M = G.shape[0] - 2
+    N, s = int(N), float(outputscale)
+    Psi = 0.5 * (G[:M, :M] + G[:M, :M].T)
+    lam, Q = torch.linalg.eigh(Psi)
+    lam = lam.clamp_min(0.0)
+    by, b1 = Q.T @ G[:M, M], Q.T @ G[:M, M + 1]
+    yy, sy, tr = float(G[M, M]), float(G[M, M + 1]), float(torch.trace(Psi))
+
+    def at(v):
+        d = v / (v + lam)                                   # eigenvalues of Lambda^-1
+        c = 0.0
+        if not zero_mean:
+            c = (sy - float((d * b1 * by).sum()) / v) / (N - float((d * b1 * b1).sum()) / v)
+        beta = by - c * b1
+        rr = yy - 2.0 * c * sy + c * c * N
+        F = (-0.5 * N * math.log(2.0 * math.pi * v) - 0.5 * float(torch.log1p(lam / v).sum()) - rr / (2.0 * v)
+             + float((d * beta * beta).sum()) / (2.0 * v * v) - (N * s - tr) / (2.0 * v))
+        return F, c, d, beta
+
+    if noise is None:
+        lo, hi = _LOG_NOISE_BOUNDS
+        n_grid = 113
+        grid = [lo + (hi - lo) * i / (n_grid - 1) for i in range(n_grid)]
+        best = max(range(n_grid), key=lambda i: at(math.exp(grid[i]))[0])
+        a, b = grid[max(best - 1, 0)], grid[min(best + 1, n_grid - 1)]
+        g = (math.sqrt(5.0) - 1.0) / 2.0
+        x1, x2 = b - g * (b - a), a + g * (b - a)
+        f1, f2 = at(math.exp(x1))[0], at(math.exp(x2))[0]
+        while b - a > 1e-12:
+            if f1 < f2:
+                a, x1, f1 = x1, x2, f2
+                x2 = a + g * (b - a)
+                f2 = at(math.exp(x2))[0]
+            else:
+                b, x2, f2 = x2, x1, f1
+                x1 = b - g * (b - a)
+                f1 = at(math.exp(x1))[0]
+        v = math.exp(0.5 * (a + b))
+    else:
+        if not float(noise) > 0.0:
+            raise ValueError("solve_collapsed: noise must be positive")
+        v = float(noise)
+    F, c, d, beta = at(v)
+    S = (Q * d) @ Q.T
+    return dict(variational_mean=Q @ (d * beta) / v, chol_variational_covar=torch.linalg.cholesky(0.5 * (S + S.T)),
+                constant=c, noise=v, elbo=F)
+
+
+def median_lengthscale(Z):
+    """sqrt of the median off-diagonal |z_i - z_j|^2, in fp64 on the host."""
+    Z = torch.as_tensor(Z).detach().to("cpu", torch.float64)
+    M = Z.shape[0]
+    if M < 2:
+        raise ValueError('GPHead.fit: lengthscale="median" needs at least two inducing points')
+    Zc = Z - Z.mean(dim=0)
+    zn = (Zc * Zc).sum(dim=1)
+    d2 = (zn[:, None] + zn[None, :] - 2.0 * (Zc @ Zc.T)).clamp_min(0.0)
+    i, j = torch.tril_indices(M, M, offset=-1)
+    return math.sqrt(float(d2[i, j].median()))
 
 
 class GPHead(nn.Module):
@@ -92,6 +292,65 @@ class GPHead(nn.Module):
             raise KeyError(f"GPHead.from_tensors: expected exactly the keys {sorted(_KEYS)}, got {sorted(mapping)}")
         return cls(*(mapping[k] for k in _KEYS), jitter=jitter)
 
+    @classmethod
+    def fit(cls, embeddings, targets, inducing_points=1000, lengthscale="median", outputscale=1.0, zero_mean=False,
+            noise=None, jitter=1e-4, seed=0, chunk_rows=None):
+        """Fits a head to `embeddings` [N, D] (fp32, GPU) and `targets` [N] at the optimum of the collapsed bound (module
+        docstring); returns (head, report), the head on the device of the embeddings.
+
+        inducing_points   an int M: that many distinct training rows, drawn with a torch.Generator seeded by `seed`
+                          (the reference's initialisation, gaussian_process.py:223-226); or a [M, D] tensor.  M <= 1024.
+        lengthscale,      a float or a sequence of floats each; a sequence runs one pass over the data per
+        outputscale       (lengthscale, outputscale) pair and keeps the pair with the largest bound.  "median": the
+                          square root of the median off-diagonal |z_i - z_j|^2.
+        zero_mean         the reference's --zero-mean: constant = 0.  Otherwise the constant's closed form.
+        noise             the likelihood's sigma^2 in units of the normalised targets, or None to search it.
+        mean, std         torch.mean / torch.std of the targets (gaussian_process.py:200-204), hence N >= 2.
+
+        report: noise, elbo (total nats), elbo_per_point (= elbo / N), lengthscale, outputscale, constant, and
+        `candidates`, a list of dicts (lengthscale, outputscale, noise, constant, elbo), one per pair tried.
+        Z stays where it was drawn and l, s come from the grid: learning them by stochastic gradient is not built."""
+        Zin = inducing_points
+        D = Zin.shape[1] if isinstance(Zin, torch.Tensor) and Zin.dim() == 2 else (
+            embeddings.shape[1] if isinstance(embeddings, torch.Tensor) and embeddings.dim() == 2 else None)
+        x = _check_embeddings("GPHead.fit", embeddings, D)
+        N, dev = x.shape[0], x.device
+        y = torch.as_tensor(targets).detach().reshape(-1)
+        if y.numel() != N:
+            raise ValueError(f"GPHead.fit: {N} rows of embeddings, {y.numel()} targets")
+        if N < 2:
+            raise ValueError("GPHead.fit: at least two rows are needed (the targets' standard deviation)")
+        y64 = y.to("cpu", torch.float64)
+        tm, ts = float(torch.mean(y64).float()), float(torch.std(y64).float())     # as the head stores them: fp32
+        if not ts > 0.0:
+            raise ValueError("GPHead.fit: the targets are constant")
+        y_norm = ((y64 - tm) / ts).to(torch.float32).to(dev)
+        if isinstance(Zin, torch.Tensor):
+            Z = Zin.detach().to("cpu", torch.float32)
+        else:
+            M = int(Zin)
+            if not 1 <= M <= N:
+                raise ValueError(f"GPHead.fit: {M} inducing points from {N} rows")
+            perm = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:M]
+            Z = x[perm.to(dev)].to("cpu")
+        as_list = lambda v: [float(t) for t in torch.as_tensor(v, dtype=torch.float64).reshape(-1)]
+        ells = [median_lengthscale(Z)] if isinstance(lengthscale, str) and lengthscale == "median" else as_list(lengthscale)
+        data_pass = _StatisticsPass("GPHead.fit", x, y_norm, Z, chunk_rows)    # Z's image and the workspace: once
+        candidates, best = [], None
+        for ell in ells:
+            for s in as_list(outputscale):
+                sol = solve_collapsed(data_pass(s, ell, jitter), N, s, noise=noise, zero_mean=zero_mean)
+                candidates.append(dict(lengthscale=ell, outputscale=s, noise=sol["noise"], constant=sol["constant"],
+                                       elbo=sol["elbo"]))
+                if best is None or sol["elbo"] > best[1]["elbo"]:
+                    best = (candidates[-1], sol)
+        row, sol = best
+        head = cls(Z, sol["variational_mean"], sol["chol_variational_covar"], constant=sol["constant"],
+                   outputscale=row["outputscale"], lengthscale=row["lengthscale"], mean=tm, std=ts, jitter=jitter).to(dev)
+        report = dict(noise=sol["noise"], elbo=sol["elbo"], elbo_per_point=sol["elbo"] / N, constant=sol["constant"],
+                      lengthscale=row["lengthscale"], outputscale=row["outputscale"], candidates=candidates)
+        return head, report
+
     # --------------------------------------------------------------------------------------------------------------
     def _key(self):
         return (self.jitter,) + tuple((t.data_ptr(), t._version, t.device) for t in (getattr(self, k) for k in _KEYS))
@@ -105,16 +364,9 @@ class GPHead(nn.Module):
         c, s, ell, tm, ts = (float(getattr(self, k)) for k in ("constant", "outputscale", "lengthscale", "mean", "std"))
         if not (s > 0.0 and ell > 0.0):
             raise ValueError("GPHead: outputscale and lengthscale must be positive")
-        M = Z.shape[0]
-        cen = Z.mean(dim=0)
-        Zc = Z - cen
-        zn = (Zc * Zc).sum(dim=1)
-        d2 = (zn[:, None] + zn[None, :] - 2.0 * (Zc @ Zc.T)).clamp_min(0.0)
-        d2.fill_diagonal_(0.0)
-        Kzz = s * torch.exp(-0.5 * d2 / (ell * ell))
-        L = torch.linalg.cholesky(Kzz + self.jitter * torch.eye(M, dtype=torch.float64))
+        cen, Zc, zn = _centred64(Z)
+        L, W1 = _whitening64(Zc, zn, s, ell, self.jitter)
         a = torch.linalg.solve_triangular(L.T, m[:, None], upper=True)[:, 0]
-        W1 = torch.linalg.solve_triangular(L, torch.eye(M, dtype=torch.float64), upper=False).tril()
         return dict(c=c, s=s, inv_two_l2=0.5 / (ell * ell), mean=tm, std=ts, centroid=cen, Zc=Zc, znorm=zn, a=a, W1=W1,
                     W2=LS.T @ W1)
 
@@ -128,20 +380,15 @@ class GPHead(nn.Module):
         dev = self.inducing_points.device
         f = self._factors64()
         M, D = f["Zc"].shape
-        Mp, Dp = (M + 31) // 32 * 32, (D + 63) // 64 * 64
-        Zp = torch.zeros(Mp, Dp, dtype=torch.float32)
-        Zp[:M, :D] = f["Zc"]
+        Mp = (M + 31) // 32 * 32
         F = torch.zeros(2 * Mp, Mp, dtype=torch.float32)
         F[:M, :M] = f["W1"]
         F[Mp:Mp + M, :M] = f["W2"]
         factors = torch.zeros(Mp + 2 * Mp * Mp, dtype=torch.float32)
         factors[:M] = f["a"]
         factors[Mp:] = _pack_image(F)
-        znp = torch.zeros(Mp, dtype=torch.float32)
-        znp[:M] = f["znorm"]
         self._image = dict(M=M, D=D, c=f["c"], s=f["s"], inv_two_l2=f["inv_two_l2"], mean=f["mean"], std=f["std"],
-                           zimg=_pack_image(Zp).to(dev), centroid=f["centroid"].to(torch.float32).to(dev),
-                           znorm=znp.to(dev), factors=factors.to(dev))
+                           factors=factors.to(dev), **_tile_operands(f["centroid"], f["Zc"], f["znorm"], dev))
         self._image_key = key
         return self._image
 

@@ -888,6 +888,28 @@ int cgat_gp_predict(const float* X, int64_t ldx, int32_t G, int32_t D, const flo
                     float tgt_mean, float tgt_std, float* mean_f, float* var_f, float* pred, float* lower, float* upper,
                     void* ws, size_t ws_bytes, void* stream);
 
+/* ---- sufficient statistics of the collapsed sparse-GP bound (fitting the head above) ---------------------
+ * The reference trains the GP of CGAT/gaussian_process.py:45-66 by minibatch AdamW on gpytorch's VariationalELBO with a
+ * GaussianLikelihood (:59, :233), targets normalised by torch.mean / torch.std (:200-204), Z a random batch of training
+ * embeddings (:223-226).  For a Gaussian likelihood that bound has a closed-form maximiser in the variational
+ * distribution (Titsias' collapsed bound), and the data enter only through
+ *   gram = sum_n a~_n a~_n^T,   a~_n = [W1 k(Z, x_n), y_norm[n], 1],   k as in cgat_gp_predict,   W1 = L^-1
+ * which this entry accumulates in one pass over X (cgat_amd/gp.py solves the rest on the host in fp64).
+ * gram [(M+2) x (M+2)], fp64, row-major, symmetric (both triangles are written, bit-equal):
+ *   gram[i][j], i, j < M : Psi = sum_n a_n a_n^T        gram[i][M] : sum_n a_n y_n        gram[i][M+1] : sum_n a_n
+ *   gram[M][M] : sum_n y_n^2        gram[M][M+1] : sum_n y_n        gram[M+1][M+1] : N (exactly)
+ * Operands as for cgat_gp_predict (X [N, D] rows ldx apart, Zimg, centroid, znorm); W1img is the packed image of W1 as
+ * [Mp, Mp], lower triangular, zero padded, 16-byte aligned; y_norm [N] fp32.  X is processed in chunks of chunk_rows rows
+ * (a positive multiple of 32; 32768 is the intended value; more than N rounded up to 32 counts as that): per chunk the
+ * whitened rows go to a chunk buffer in the workspace, their Gram product is formed on the f32-input matrix cores in
+ * fp32 over slabs of 1024 rows, and the slabs are added in fp64 in a fixed order.  M > 1024 returns 4 (unsupported) with
+ * a message, as cgat_gp_predict does.  The workspace (query below; 0 for arguments the entry refuses) must be 16-byte
+ * aligned.  No atomics: bitwise deterministic; caller's stream, no allocation, no synchronisation. */
+size_t cgat_gp_fit_stats_workspace_bytes(int32_t N, int32_t M, int32_t D, int32_t chunk_rows);
+int cgat_gp_fit_stats(const float* X, int64_t ldx, const float* y_norm, int32_t N, int32_t D, const float* Zimg, int32_t M,
+                      const float* centroid, const float* znorm, const float* W1img, float s, float inv_two_l2,
+                      int32_t chunk_rows, double* gram, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
