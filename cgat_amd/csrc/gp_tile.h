@@ -1,7 +1,10 @@
-// Device code shared by the sparse-GP kernels: csrc/gphead.hip (prediction) and csrc/gpfit.hip (the fit
-// statistics).  Both work on a tile of 32 rows of X with one 512-thread workgroup (8 waves, two per SIMD):
+// Device code shared by the sparse-GP kernels: csrc/gphead.hip (prediction), csrc/gpfit.hip (the fit
+// statistics) and csrc/gpgrad.hip (the gradient of the bound).  All work on a tile of 32 rows of
+// X with one 512-thread workgroup (8 waves, two per SIMD):
+//   gp_distance_tile    max(|x_row - z_m|^2, 0) of the tile, handed to a functor
 //   gp_kernel_tile      K^T[m][row] = s exp(-max(|x_row - z_m|^2, 0) inv_two_l2) of the tile, into LDS
 //   gp_factor_products  NB 32-row chunks of a packed factor image times that K^T tile, on the f32-input matrix cores
+// and gp_launch_whiten_rows (host, defined in csrc/gpfit.hip) enqueues the whitening kernel of 10c for 10d.
 //
 // Packed operand image of a row-major matrix P [R, Kd] (R a multiple of 32, Kd a multiple of 8):
 //   img[((c * Kd/8 + k8) * 64 + lane) * 4 + q] = P[32 c + (lane & 31)][8 k8 + 2 q + (lane >> 5)]
@@ -17,6 +20,24 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GP_WAVES 8
 #define GP_XK 64                   // columns of X staged per step (the packed image of Zc is padded to this)
 #define GP_XP 33                   // pitch of the staged X tile: [k][row], conflict-free to write and to read
+
+// Operands of gp_whiten_rows (csrc/gpfit.hip): A~^T = [W1 K^T; y~; 1; 0] of one chunk of rows.
+struct GpWhitenArgs {
+  const float* X;                  // already offset to the chunk's first row
+  long ldx;
+  int G, D, M;                     // G: rows of X left from the chunk's first row (tiles past it are zero filled)
+  int Mp, Dp, Map;
+  const float4* Zimg;
+  const float* centroid;
+  const float* znorm;
+  const float4* W1img;             // packed image of W1 [Mp, Mp], lower triangular, zero padded
+  const float* y_norm;             // offset like X
+  float s, inv_two_l2;
+  float* At;                       // [Map][pitch]
+  long pitch;
+};
+// One workgroup per tile of 32 rows on `stream`; the caller follows it with CGAT_LAUNCH_CHECK().
+void gp_launch_whiten_rows(const GpWhitenArgs& args, int n_tiles, hipStream_t stream);
 
 // Inducing index of accumulator register t of chunk c on a lane of the upper (hi = 1) or lower half of the wave; the X
 // row of the tile is lane & 31.
@@ -67,12 +88,13 @@ __device__ __forceinline__ void gp_factor_products(const float4* __restrict__ Fi
   }
 }
 
-// Phase (a) of both kernels: cross products of the tile's rows (row0 ..) with every inducing point, norms, exp.  `p`
-// carries X, ldx, G (rows of X), D, M, Mp, Dp, Zimg, centroid, znorm, s, inv_two_l2.  Kt [Mp][32] and Xs [64][33] are
-// LDS; the caller synchronises before it reads Kt.  Rows of the tile at or past G are staged as zeros (their K^T column
-// is that of x = centroid: finite, and the caller's to discard).
-template <class Args>
-__device__ __forceinline__ void gp_kernel_tile(const Args& p, long row0, float* Kt, float* Xs) {
+// Phase (a) of the kernels: cross products of the tile's rows (row0 ..) with every inducing point and the norms;
+// store(m, d2) receives max(|x_r - z_m|^2, 0) of inducing index m < Mp and X row r = lane & 31 of the tile, once each, in
+// wave-uniform control flow.  `p` carries X, ldx, G (rows of X), D, Mp, Dp, Zimg, centroid, znorm.  Xs [64][33] is LDS.
+// Rows of the tile at or past G are staged as zeros (their distances are those of x = centroid: finite, and the caller's
+// to discard).
+template <class Args, class Store>
+__device__ __forceinline__ void gp_distance_tile(const Args& p, long row0, float* Xs, Store store) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, hi = lane >> 5;
   const int nC = p.Mp >> 5;
@@ -132,9 +154,19 @@ __device__ __forceinline__ void gp_kernel_tile(const Args& p, long row0, float* 
         const int m = 32 * c + (t & 3) + 8 * (t >> 2) + 4 * hi;
         float d2 = xn + p.znorm[m] - 2.f * acc[j][t];
         d2 = fmaxf(d2, 0.f);
-        const float kv = p.s * expf(-d2 * p.inv_two_l2);
-        Kt[m * GP_ROWS + r] = m < p.M ? kv : 0.f;
+        store(m, d2);
       }
     }
   }
+}
+
+// K^T[m][row] = s exp(-d2 inv_two_l2) of the tile into Kt [Mp][32] (LDS), 0 for m >= M; `p` carries M, s, inv_two_l2 as
+// well.  The caller synchronises before it reads Kt.
+template <class Args>
+__device__ __forceinline__ void gp_kernel_tile(const Args& p, long row0, float* Kt, float* Xs) {
+  const int r = threadIdx.x & 31;
+  gp_distance_tile(p, row0, Xs, [&](int m, float d2) {
+    const float kv = p.s * expf(-d2 * p.inv_two_l2);
+    Kt[m * GP_ROWS + r] = m < p.M ? kv : 0.f;
+  });
 }

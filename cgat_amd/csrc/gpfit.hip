@@ -34,21 +34,6 @@
 #define GF_SLAB 1024               // rows of the chunk per partial
 #define GF_THREADS 256
 
-struct GpWhitenArgs {
-  const float* X;                  // already offset to the chunk's first row
-  long ldx;
-  int G, D, M;                     // G: rows of X left from the chunk's first row (tiles past it are zero filled)
-  int Mp, Dp, Map;
-  const float4* Zimg;
-  const float* centroid;
-  const float* znorm;
-  const float4* W1img;             // packed image of W1 [Mp, Mp], lower triangular, zero padded
-  const float* y_norm;             // offset like X
-  float s, inv_two_l2;
-  float* At;                       // [Map][pitch]
-  long pitch;
-};
-
 // Stores the accumulators of NB chunks of W1 K^T: inducing index m to row m of A~^T, X row r to column col.
 template <int NB>
 __device__ __forceinline__ void gp_whiten_group(const GpWhitenArgs& p, const float* Kt, int c0, int nC, int nk8,
@@ -105,6 +90,10 @@ __global__ __launch_bounds__(GP_THREADS) void gp_whiten_rows(GpWhitenArgs p) {
     if (g < p.G) v = m == p.M ? p.y_norm[g] : (m == p.M + 1 ? 1.f : 0.f);
     p.At[(long)m * p.pitch + g] = v;
   }
+}
+
+void gp_launch_whiten_rows(const GpWhitenArgs& args, int n_tiles, hipStream_t stream) {
+  hipLaunchKernelGGL(gp_whiten_rows, dim3(n_tiles), dim3(GP_THREADS), 0, stream, args);
 }
 
 // Lower-triangle tile number t -> (ti, tj), tj <= ti.
@@ -275,7 +264,7 @@ extern "C" int cgat_gp_fit_stats(const float* X, int64_t ldx, const float* y_nor
     const int rows_p = (rows + 31) & ~31;
     const int n_slabs = cdiv(rows_p, GF_SLAB);
     a.X = X + base * (long)ldx; a.y_norm = y_norm + base; a.G = rows;
-    hipLaunchKernelGGL(gp_whiten_rows, dim3(rows_p / GP_ROWS), dim3(GP_THREADS), 0, st, a);
+    gp_launch_whiten_rows(a, rows_p / GP_ROWS, st);
     CGAT_LAUNCH_CHECK();
     hipLaunchKernelGGL(gp_gram_slabs, dim3(g.n_tiles, n_slabs), dim3(GF_THREADS), 0, st, At, (long)g.eff_chunk, g.Map, rows_p,
                        part, g.n_tiles);

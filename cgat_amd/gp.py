@@ -3,8 +3,9 @@
 The reference's screening / active-learning flow continues past the graph embedding: `train-GP`
 (CGAT/gaussian_process.py) fits a sparse variational GP on the embeddings and Utilities/gp_predict.py writes, per
 candidate, `prediction` and `uncertainty = upper - prediction`.  This module is the prediction side of that GP, fused
-into one HIP launch (csrc/gphead.hip), and a fit of the head on the device (`GPHead.fit`; below).  Learning
-the inducing points and the lengthscale by stochastic gradient, as the reference's AdamW loop does, is out of scope.
+into one HIP launch (csrc/gphead.hip), and a fit of the head on the device (`GPHead.fit`; below).
+What the reference's AdamW loop learns by stochastic gradient -- the inducing points, the lengthscale, the outputscale --
+`GPHead.fit(learn=...)` learns by a quasi-Newton ascent of the collapsed bound with its exact full-batch gradient.
 
 Model (gaussian_process.py:45-66, evaluated at :247-268): ScaleKernel(RBFKernel) with one lengthscale l and outputscale
 s, ConstantMean c (0 under --zero-mean), whitened VariationalStrategy with a CholeskyVariationalDistribution (mean m,
@@ -45,6 +46,18 @@ VariationalELBO is meant to be this bound divided by N (`elbo_per_point`); gpyto
 is built, so that scaling is unconfirmed, like the default of `jitter`.
 
     head, report = GPHead.fit(embeddings, targets, inducing_points=1000, lengthscale="median")
+
+Gradient.  With (m, L_S, c, sigma^2) at their maximisers, dF*/d(Z, log l, log s) is the partial derivative at
+fixed (c, sigma^2) (the envelope theorem).  With G^ = dF/dPsi = (I - S - m m^T) / (2 sigma^2) and g = dF/dbeta = m / sigma^2
+(`collapsed_adjoints`), per row q_n = 2 G^ a_n + g (y~_n - c), u_n = W1^T q_n = dF/dk_n, r_nm = u_nm k_nm, and a second
+pass over the embeddings (csrc/gpgrad.hip) returns colsum = sum_n r_n, d2sum_m = sum_n r_nm |x_n - z_m|^2 and
+P = sum_n r_n (x_n - centroid)^T in fp64:
+
+    dF/dlog l = sum(d2sum) / l^2 + host      dF/dZ = (P - colsum o Zc) / l^2 + host      dF/dlog s = sum(colsum) - N s / (2 sigma^2) + host
+
+`host` (`whitening_pullback`) is what reaches the parameters through W1 = chol(K_zz + jitter I)^-1: dF/dW1 =
+(2 G^ Psi + g beta^T) L^T pulled back by torch autograd on the M x M host graph.  `bound_and_gradient` is the two passes
+and the solve; `GPHead.fit(learn=("lengthscale", "outputscale", "inducing_points"))` ascends the bound with it.
 
 Outputs carry no grad; non-GPU and non-fp32 inputs are refused like everywhere else in the package.
 """
@@ -120,7 +133,7 @@ class _StatisticsPass:
     device, the workspace, the output.  Calling it with (s, l, jitter) factors K_zz on the host in fp64, uploads the
     image of W1 and enqueues the pass; a later call overwrites the same `gram`."""
 
-    def __init__(self, what, embeddings, y_norm, inducing_points, chunk_rows):
+    def __init__(self, what, embeddings, y_norm, inducing_points, chunk_rows, extra_workspace=None):
         Z = torch.as_tensor(inducing_points)
         if Z.dim() != 2 or Z.shape[0] < 1 or Z.shape[1] < 1:
             raise ValueError(f"{what}: inducing_points must be [M, D], got {tuple(Z.shape)}")
@@ -135,11 +148,28 @@ class _StatisticsPass:
         if y.numel() != self.N or self.N < 1:
             raise ValueError(f"{what}: {self.N} rows of embeddings, {y.numel()} targets (at least one row is needed)")
         self.y32 = y.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
-        cen, self.Zc, self.zn = _centred64(Z.detach().to("cpu", torch.float64))
-        self.ops = _tile_operands(cen, self.Zc, self.zn, dev)
+        self.set_inducing_points(Z)
         self.gram = torch.empty(self.M + 2, self.M + 2, dtype=torch.float64, device=dev)
         self.ws_bytes = _lib.lib.cgat_gp_fit_stats_workspace_bytes(self.N, self.M, self.D, self.chunk)
-        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
+        # one workspace serves the passes of a _GradientPass too: they follow each other on one stream
+        also = 0 if extra_workspace is None else extra_workspace(self.N, self.M, self.D, self.chunk)
+        self.ws = torch.empty(max(self.ws_bytes, also, 16), dtype=torch.uint8, device=dev)
+
+    def set_inducing_points(self, Z):
+        """Replaces Z (same shape): its fp64 centred form on the host and the fp32 operands of phase (a) on the device."""
+        Z = torch.as_tensor(Z).detach().to("cpu", torch.float64)
+        if tuple(Z.shape) != (self.M, self.D):
+            raise ValueError(f"{self.what}: inducing_points must stay [{self.M}, {self.D}], got {tuple(Z.shape)}")
+        self.Z = Z
+        cen, self.Zc, self.zn = _centred64(Z)
+        self.ops = _tile_operands(cen, self.Zc, self.zn, self.x.device)
+
+    def _image(self, P):
+        """The packed image of P [M, M] padded with zeros to [Mp, Mp], fp32 on the device."""
+        M, Mp = self.M, (self.M + 31) // 32 * 32
+        Pp = torch.zeros(Mp, Mp, dtype=torch.float32)
+        Pp[:M, :M] = P
+        return _pack_image(Pp).to(self.x.device)
 
     def __call__(self, outputscale, lengthscale, jitter):
         s, ell = float(outputscale), float(lengthscale)
@@ -147,10 +177,8 @@ class _StatisticsPass:
             raise ValueError(f"{self.what}: outputscale and lengthscale must be positive")
         M, x, ops, dev = self.M, self.x, self.ops, self.x.device
         _, W1 = _whitening64(self.Zc, self.zn, s, ell, float(jitter))
-        Mp = (M + 31) // 32 * 32
-        W1p = torch.zeros(Mp, Mp, dtype=torch.float32)
-        W1p[:M, :M] = W1
-        w1img = _pack_image(W1p).to(dev)
+        self.W1 = W1
+        self.w1img = w1img = self._image(W1)
         with torch.cuda.device(dev):
             rc = _lib.lib.cgat_gp_fit_stats(_ptr(x), x.stride(0), _ptr(self.y32), self.N, self.D, _ptr(ops["zimg"]), M,
                                             _ptr(ops["centroid"]), _ptr(ops["znorm"]), _ptr(w1img), s, 0.5 / (ell * ell),
@@ -229,6 +257,179 @@ def solve_collapsed(gram, N, outputscale, noise=None, zero_mean=False):
                 constant=c, noise=v, elbo=F)
 
 
+def collapsed_adjoints(gram, N, outputscale, solution):
+    """The adjoints of the statistics at a solution of the collapsed bound, on the host in fp64.  `gram`,
+    `N`, `outputscale` as for solve_collapsed, `solution` what it returned for them.  With v = sigma^2,
+    beta = Ay - c A1, S = Lambda^-1 = L_S L_S^T and m = S beta / v, returns a dict:
+
+        G_hat            dF/dPsi  = (I - S - m m^T) / (2 v)                            [M, M], symmetric
+        g                dF/dbeta = m / v                                              [M]
+        dF_dW1           2 G_hat Psi + g beta^T: dF/dW1 = dF_dW1 L^T                   [M, M]
+        log_outputscale  2 tr(G_hat Psi) + m.beta / v - N s / (2 v): dF/dlog s at fixed W1 (a float)
+
+    c and sigma^2 are held fixed: at their maximisers that is the total derivative (the envelope theorem).  The
+    eigenvalue clamp of solve_collapsed is not differentiated."""
+    G = torch.as_tensor(gram).detach().to("cpu", torch.float64)
+    if G.dim() != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 3:
+        raise ValueError(f"collapsed_adjoints: gram must be [M+2, M+2], got {tuple(G.shape)}")
+    M = G.shape[0] - 2
+    v, c, s = float(solution["noise"]), float(solution["constant"]), float(outputscale)
+    m = solution["variational_mean"].to(torch.float64)
+    LS = solution["chol_variational_covar"].to(torch.float64).tril()
+    Psi = 0.5 * (G[:M, :M] + G[:M, :M].T)
+    beta = G[:M, M] - c * G[:M, M + 1]
+    G_hat = (torch.eye(M, dtype=torch.float64) - LS @ LS.T - torch.outer(m, m)) / (2.0 * v)
+    G_hat = 0.5 * (G_hat + G_hat.T)
+    g = m / v
+    GP = G_hat @ Psi
+    return dict(G_hat=G_hat, g=g, dF_dW1=2.0 * GP + torch.outer(g, beta),
+                log_outputscale=2.0 * float(torch.trace(GP)) + float(m @ beta) / v - int(N) * s / (2.0 * v))
+
+
+def whitening_pullback(Z, lengthscale, outputscale, jitter, dF_dW1):
+    """The part of the gradient that reaches (Z, log l, log s) through W1 = chol(K_zz + jitter I)^-1, on the host in fp64:
+    torch autograd through the Cholesky factorisation of the [M, M] matrix that _whitening64 builds (distances of the
+    centred Z, the diagonal pinned to 0).  `dF_dW1` as collapsed_adjoints returns it.  Returns a dict: inducing_points
+    [M, D], log_lengthscale, log_outputscale."""
+    Z = torch.as_tensor(Z).detach().to("cpu", torch.float64).clone().requires_grad_(True)
+    T = torch.as_tensor(dF_dW1).detach().to("cpu", torch.float64)
+    M = Z.shape[0]
+    log_l = torch.tensor(math.log(float(lengthscale)), dtype=torch.float64, requires_grad=True)
+    log_s = torch.tensor(math.log(float(outputscale)), dtype=torch.float64, requires_grad=True)
+    eye = torch.eye(M, dtype=torch.float64)
+    Zc = Z - Z.detach().mean(dim=0)
+    zn = (Zc * Zc).sum(dim=1)
+    d2 = (zn[:, None] + zn[None, :] - 2.0 * (Zc @ Zc.T)).clamp_min(0.0) * (1.0 - eye)
+    Kzz = torch.exp(log_s - 0.5 * d2 * torch.exp(-2.0 * log_l))
+    L = torch.linalg.cholesky(Kzz + float(jitter) * eye)
+    W1 = torch.linalg.solve_triangular(L, eye, upper=False)
+    gZ, gl, gs = torch.autograd.grad(((T @ L.detach().T).tril() * W1).sum(), (Z, log_l, log_s))
+    return dict(inducing_points=gZ, log_lengthscale=float(gl), log_outputscale=float(gs))
+
+
+class _GradientPass:
+    """What bound_and_gradient needs and (Z, l, s) do not change: a _StatisticsPass (the checked x, the targets, the one
+    workspace both passes use) and the fp64 outputs of cgat_gp_fit_grad.  An optimiser calls it repeatedly, with
+    set_inducing_points in between when Z moves."""
+
+    def __init__(self, what, embeddings, y_norm, inducing_points, chunk_rows):
+        self.stats = st = _StatisticsPass(what, embeddings, y_norm, inducing_points, chunk_rows,
+                                          extra_workspace=_lib.lib.cgat_gp_fit_grad_workspace_bytes)
+        dev = st.x.device
+        self.ws_bytes = _lib.lib.cgat_gp_fit_grad_workspace_bytes(st.N, st.M, st.D, st.chunk)
+        self.colsum = torch.empty(st.M, dtype=torch.float64, device=dev)
+        self.d2sum = torch.empty(st.M, dtype=torch.float64, device=dev)
+        self.P = torch.empty(st.M, st.D, dtype=torch.float64, device=dev)
+
+    def set_inducing_points(self, Z):
+        self.stats.set_inducing_points(Z)
+
+    def sums(self, outputscale, lengthscale, two_G_hat, g, constant):
+        """Enqueues cgat_gp_fit_grad with the W1 of the statistics pass that went before; (colsum, d2sum, P)."""
+        st = self.stats
+        s, ell = float(outputscale), float(lengthscale)
+        x, ops, dev = st.x, st.ops, st.x.device
+        w1timg = st._image(st.W1.T)
+        g2img = st._image(torch.as_tensor(two_G_hat).to("cpu", torch.float64))
+        g32 = torch.as_tensor(g).to("cpu", torch.float64).to(torch.float32).to(dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib.cgat_gp_fit_grad(_ptr(x), x.stride(0), _ptr(st.y32), st.N, st.D, _ptr(ops["zimg"]), st.M,
+                                           _ptr(ops["centroid"]), _ptr(ops["znorm"]), _ptr(st.w1img), _ptr(w1timg),
+                                           _ptr(g2img), _ptr(g32), float(constant), s, 0.5 / (ell * ell), st.chunk,
+                                           _ptr(self.colsum), _ptr(self.d2sum), _ptr(self.P), _ptr(st.ws), self.ws_bytes,
+                                           _stream())
+        _lib.check(rc, "cgat_gp_fit_grad")
+        return self.colsum, self.d2sum, self.P
+
+    def __call__(self, outputscale, lengthscale, jitter, noise=None, zero_mean=False):
+        st = self.stats
+        s, ell = float(outputscale), float(lengthscale)
+        gram = st(s, ell, jitter)
+        sol = solve_collapsed(gram, st.N, s, noise=noise, zero_mean=zero_mean)
+        adj = collapsed_adjoints(gram, st.N, s, sol)
+        colsum, d2sum, P = (t.cpu() for t in self.sums(s, ell, 2.0 * adj["G_hat"], adj["g"], sol["constant"]))
+        host = whitening_pullback(st.Z, ell, s, jitter, adj["dF_dW1"])
+        l2 = ell * ell
+        grads = dict(log_lengthscale=float(d2sum.sum()) / l2 + host["log_lengthscale"],
+                     log_outputscale=adj["log_outputscale"] + host["log_outputscale"],
+                     inducing_points=(P - colsum[:, None] * st.Zc) / l2 + host["inducing_points"])
+        return sol, grads
+
+
+def fit_gradient_sums(embeddings, y_norm, inducing_points, outputscale, lengthscale, two_G_hat, g, constant, jitter=1e-4,
+                      chunk_rows=None):
+    """The three sums of one cgat_gp_fit_grad call (csrc/gpgrad.hip, layout in include/cgat_hip.h) as fp64 tensors on the
+    device of `embeddings`: colsum [M], d2sum [M], P [M, D], for the adjoints `two_G_hat` [M, M] (= 2 dF/dPsi), `g` [M]
+    and the constant c.  The other arguments as for fit_statistics; W1 is computed as there."""
+    p = _GradientPass("fit_gradient_sums", embeddings, y_norm, inducing_points, chunk_rows)
+    st = p.stats
+    _, st.W1 = _whitening64(st.Zc, st.zn, float(outputscale), float(lengthscale), float(jitter))
+    st.w1img = st._image(st.W1)
+    return p.sums(outputscale, lengthscale, two_G_hat, g, constant)
+
+
+def bound_and_gradient(embeddings, y_norm, inducing_points, outputscale, lengthscale, jitter=1e-4, noise=None,
+                       zero_mean=False, chunk_rows=None):
+    """The collapsed bound at its maximiser in (m, L_S, c, sigma^2) and its exact full-batch gradient in the kernel's
+    parameters: one statistics pass, one solve, one gradient pass.  Returns (solution, grads): `solution` as
+    solve_collapsed returns it, `grads` a dict of fp64 host values: log_lengthscale, log_outputscale (floats) and
+    inducing_points [M, D], the derivatives of solution["elbo"] (c and sigma^2 re-solved, or `noise` held)."""
+    return _GradientPass("bound_and_gradient", embeddings, y_norm, inducing_points, chunk_rows)(
+        outputscale, lengthscale, jitter, noise=noise, zero_mean=zero_mean)
+
+
+LEARNABLE = ("lengthscale", "outputscale", "inducing_points")
+# The box of GPHead.fit(learn=...) on l and on s, as factors of the values the ascent starts from.  On data the kernel
+# cannot explain the bound rises all the way to s -> 0, on near-linear targets toward l, s -> infinity, where
+# K_zz + jitter I leaves what the fp32 factors of the kernels resolve (W1 reaches 1 / sqrt(jitter), DESIGN 10d).  A start
+# from a grid or the median distance is within a small factor of the optimum; 8 in l and 16 in s keep s / jitter below
+# 2e5 for s = 1.
+DEFAULT_BOUNDS = dict(lengthscale=(1.0 / 8.0, 8.0), outputscale=(1.0 / 16.0, 16.0))
+
+
+def _ascend(evaluate, theta0, lo, hi, max_iter):
+    """L-BFGS (torch.optim.LBFGS, strong-Wolfe line search) ascent of evaluate(theta) -> (F, dF/dtheta) over the fp64
+    vector theta.  The box lo <= theta <= hi (+-inf where there is none) is enforced by composition: the objective is
+    F(clamp(theta)), whose gradient is that of F with the clamped coordinates zeroed, so an iterate that leaves the box
+    sees a function that is flat in that coordinate and the returned point is its projection.  Returns (theta, steps,
+    evaluations): the last accepted iterate, the bound at each accepted iterate (non-decreasing: an L-BFGS step that
+    does not raise the bound ends the ascent at the iterate before it), the number of evaluate calls."""
+    x = theta0.clone().clamp(lo, hi).requires_grad_(True)
+    seen, count = {}, [0]
+
+    def at(t):
+        t = t.detach().clamp(lo, hi)
+        key = t.numpy().tobytes()
+        if key not in seen:
+            count[0] += 1
+            F, grad = evaluate(t)
+            inside = (t > lo) & (t < hi)
+            seen[key] = (float(F), torch.where(inside, grad, torch.zeros_like(grad)))
+        return seen[key]
+
+    def closure():
+        F, grad = at(x)
+        x.grad = -grad.clone()
+        return torch.tensor(-F, dtype=torch.float64)
+
+    opt = torch.optim.LBFGS([x], lr=1.0, max_iter=1, max_eval=30, history_size=10, tolerance_grad=0.0,
+                            tolerance_change=0.0, line_search_fn="strong_wolfe")
+    steps = [at(x)[0]]
+    for _ in range(int(max_iter)):
+        before = x.detach().clone()
+        opt.step(closure)
+        F, grad = at(x)
+        if not F >= steps[-1] or not bool(torch.isfinite(x).all()):
+            with torch.no_grad():
+                x.copy_(before)
+            break
+        gain = F - steps[-1]
+        steps.append(F)
+        if gain <= 1e-9 * abs(F) or float(grad.abs().max()) <= 1e-7 * max(abs(F), 1.0):
+            break
+    return x.detach().clamp(lo, hi), steps, count[0]
+
+
 def median_lengthscale(Z):
     """sqrt of the median off-diagonal |z_i - z_j|^2, in fp64 on the host."""
     Z = torch.as_tensor(Z).detach().to("cpu", torch.float64)
@@ -294,7 +495,7 @@ class GPHead(nn.Module):
 
     @classmethod
     def fit(cls, embeddings, targets, inducing_points=1000, lengthscale="median", outputscale=1.0, zero_mean=False,
-            noise=None, jitter=1e-4, seed=0, chunk_rows=None):
+            noise=None, jitter=1e-4, seed=0, chunk_rows=None, learn=(), max_iter=50, bounds=None):
         """Fits a head to `embeddings` [N, D] (fp32, GPU) and `targets` [N] at the optimum of the collapsed bound (module
         docstring); returns (head, report), the head on the device of the embeddings.
 
@@ -309,7 +510,18 @@ class GPHead(nn.Module):
 
         report: noise, elbo (total nats), elbo_per_point (= elbo / N), lengthscale, outputscale, constant, and
         `candidates`, a list of dicts (lengthscale, outputscale, noise, constant, elbo), one per pair tried.
-        Z stays where it was drawn and l, s come from the grid: learning them by stochastic gradient is not built."""
+
+        learn             a subset of ("lengthscale", "outputscale", "inducing_points"); () (the default) stops at the
+                          grid's best pair.  Otherwise the bound, re-solved in (m, L_S, c, sigma^2) at every point, is
+                          ascended from that pair over (log l, log s, Z) by L-BFGS with a strong-Wolfe line search on
+                          the host in fp64 with the exact full-batch gradient (bound_and_gradient: two passes over the
+                          data per evaluation), at most `max_iter` iterations.
+        bounds            {"lengthscale": (low, high), "outputscale": (low, high)}: the box of the ascent as factors of
+                          the values it starts from, default DEFAULT_BOUNDS = (1/8, 8) and (1/16, 16).  The ascent
+                          maximises the bound of the parameters projected onto the box.
+        With `learn` the report gains: learned, steps (the bound at each accepted iterate, non-decreasing, steps[0] the
+        grid's best), evaluations (of bound_and_gradient) and active_bounds (e.g. ["outputscale:lower"]; empty when the
+        optimum is interior).  elbo, noise and constant are those of the returned head (Z rounded to fp32)."""
         Zin = inducing_points
         D = Zin.shape[1] if isinstance(Zin, torch.Tensor) and Zin.dim() == 2 else (
             embeddings.shape[1] if isinstance(embeddings, torch.Tensor) and embeddings.dim() == 2 else None)
@@ -335,7 +547,19 @@ class GPHead(nn.Module):
             Z = x[perm.to(dev)].to("cpu")
         as_list = lambda v: [float(t) for t in torch.as_tensor(v, dtype=torch.float64).reshape(-1)]
         ells = [median_lengthscale(Z)] if isinstance(lengthscale, str) and lengthscale == "median" else as_list(lengthscale)
-        data_pass = _StatisticsPass("GPHead.fit", x, y_norm, Z, chunk_rows)    # Z's image and the workspace: once
+        learn = (learn,) if isinstance(learn, str) else tuple(learn)
+        if len(set(learn)) != len(learn) or not set(learn) <= set(LEARNABLE):
+            raise ValueError(f"GPHead.fit: learn must be a subset of {LEARNABLE}, got {learn}")
+        box = dict(DEFAULT_BOUNDS)
+        if bounds is not None:
+            if not set(bounds) <= set(box):
+                raise ValueError(f"GPHead.fit: bounds has the keys {sorted(box)}, got {sorted(bounds)}")
+            box.update({k: (float(lo), float(hi)) for k, (lo, hi) in bounds.items()})
+        if any(not 0.0 < lo <= 1.0 <= hi < math.inf for lo, hi in box.values()):
+            raise ValueError("GPHead.fit: bounds are pairs of factors (low, high) with 0 < low <= 1 <= high < inf")
+        # Z's image and the workspace: once
+        gradient_pass = _GradientPass("GPHead.fit", x, y_norm, Z, chunk_rows) if learn else None
+        data_pass = gradient_pass.stats if learn else _StatisticsPass("GPHead.fit", x, y_norm, Z, chunk_rows)
         candidates, best = [], None
         for ell in ells:
             for s in as_list(outputscale):
@@ -345,11 +569,69 @@ class GPHead(nn.Module):
                 if best is None or sol["elbo"] > best[1]["elbo"]:
                     best = (candidates[-1], sol)
         row, sol = best
+        learned = {}
+        if learn:
+            row, sol, Z, learned = cls._learn(gradient_pass, row, Z, learn, box, int(max_iter), jitter, noise, zero_mean)
         head = cls(Z, sol["variational_mean"], sol["chol_variational_covar"], constant=sol["constant"],
                    outputscale=row["outputscale"], lengthscale=row["lengthscale"], mean=tm, std=ts, jitter=jitter).to(dev)
         report = dict(noise=sol["noise"], elbo=sol["elbo"], elbo_per_point=sol["elbo"] / N, constant=sol["constant"],
-                      lengthscale=row["lengthscale"], outputscale=row["outputscale"], candidates=candidates)
+                      lengthscale=row["lengthscale"], outputscale=row["outputscale"], candidates=candidates, **learned)
         return head, report
+
+    @staticmethod
+    def _learn(gradient_pass, start, Z, learn, box, max_iter, jitter, noise, zero_mean):
+        """The ascent of fit(learn=...) from the grid's best candidate `start`: theta = (log l, log s, Z) restricted to
+        what `learn` names, in fp64 on the host; one evaluation is bound_and_gradient's two device passes.  Returns the
+        final (row, solution, Z) and the report's extra entries."""
+        l0, s0 = start["lengthscale"], start["outputscale"]
+        Z0 = Z.to(torch.float64)
+        M, D = Z0.shape
+        parts, lo, hi = [], [], []
+        for name, v0 in (("lengthscale", l0), ("outputscale", s0)):
+            if name in learn:
+                parts.append(torch.tensor([math.log(v0)], dtype=torch.float64))
+                lo.append(torch.tensor([math.log(v0 * box[name][0])], dtype=torch.float64))
+                hi.append(torch.tensor([math.log(v0 * box[name][1])], dtype=torch.float64))
+        if "inducing_points" in learn:
+            parts.append(Z0.reshape(-1))
+            lo.append(torch.full((M * D,), -math.inf, dtype=torch.float64))
+            hi.append(torch.full((M * D,), math.inf, dtype=torch.float64))
+        lo, hi = torch.cat(lo), torch.cat(hi)
+
+        def split(theta):
+            i, ell, s, Zt = 0, l0, s0, Z0
+            if "lengthscale" in learn:
+                ell, i = math.exp(float(theta[i])), i + 1
+            if "outputscale" in learn:
+                s, i = math.exp(float(theta[i])), i + 1
+            if "inducing_points" in learn:
+                Zt = theta[i:].reshape(M, D)
+            return ell, s, Zt
+
+        def run(theta):
+            ell, s, Zt = split(theta)
+            if "inducing_points" in learn:
+                gradient_pass.set_inducing_points(Zt)
+            return (ell, s, Zt) + gradient_pass(s, ell, jitter, noise=noise, zero_mean=zero_mean)
+
+        def evaluate(theta):
+            _, _, _, sol, grads = run(theta)
+            g = [torch.tensor([grads["log_" + k]], dtype=torch.float64) for k in ("lengthscale", "outputscale") if k in learn]
+            if "inducing_points" in learn:
+                g.append(grads["inducing_points"].reshape(-1))
+            return sol["elbo"], torch.cat(g)
+
+        theta, steps, evaluations = _ascend(evaluate, torch.cat(parts), lo, hi, max_iter)
+        # the head holds Z in fp32: the final statistics pass and solve are made at the rounded Z
+        ell, s, Zt = split(theta)
+        Zt = Zt.to(torch.float32)
+        gradient_pass.set_inducing_points(Zt)
+        sol = solve_collapsed(gradient_pass.stats(s, ell, jitter), gradient_pass.stats.N, s, noise=noise, zero_mean=zero_mean)
+        active = []
+        for i, name in enumerate(k for k in ("lengthscale", "outputscale") if k in learn):
+            active += [f"{name}:{side}" for side, edge in (("lower", lo[i]), ("upper", hi[i])) if float(theta[i]) == float(edge)]
+        row = dict(lengthscale=ell, outputscale=s, noise=sol["noise"], constant=sol["constant"], elbo=sol["elbo"])
+        return row, sol, Zt, dict(learned=tuple(learn), steps=steps, evaluations=evaluations, active_bounds=active)
 
     # --------------------------------------------------------------------------------------------------------------
     def _key(self):

@@ -910,6 +910,26 @@ int cgat_gp_fit_stats(const float* X, int64_t ldx, const float* y_norm, int32_t 
                       const float* centroid, const float* znorm, const float* W1img, float s, float inv_two_l2,
                       int32_t chunk_rows, double* gram, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- data part of the gradient of the collapsed bound in (Z, log l, log s) ------------------------------
+ * With (m, L_S, c, sigma^2) at their maximisers the derivative of the bound with respect to the kernel's parameters is the
+ * partial derivative at fixed (c, sigma^2).  Its dependence on the data is a second pass over X with the adjoints of the
+ * statistics, G2 = 2 dF/dPsi [M x M] (symmetric) and g = dF/dbeta [M], computed on the host in fp64 (cgat_amd/gp.py):
+ *   a_n = W1 k_n,  q_n = G2 a_n + g (y_norm[n] - c),  u_n = W1^T q_n,  r_nm = u_nm k_nm,  k as in cgat_gp_predict
+ *   colsum[m] = sum_n r_nm    d2sum[m] = sum_n r_nm max(|x_n - z_m|^2, 0)    P[m][d] = sum_n r_nm (x_n[d] - centroid[d])
+ * from which dF/dlog l = sum_m d2sum[m] / l^2 and dF/dZ = (P - colsum o (Z - centroid)) / l^2 (data parts).
+ * Outputs fp64: colsum [M], d2sum [M], P [M, D] row-major.  Operands as for cgat_gp_fit_stats, plus W1timg and G2img, the
+ * packed images of W1^T (upper triangular: its column blocks before the diagonal are not read) and of G2 as [Mp, Mp], zero
+ * padded, 16-byte aligned; g [M] and c in fp32.  The three products are formed one after the other on the f32-input matrix
+ * cores per tile of 32 rows (never as one M x M factor), the intermediates pass through a chunk buffer in the workspace,
+ * the distances are recomputed next to k; the sums over rows are fp32 per tile of 32 rows (colsum, d2sum) or per slab of
+ * 1024 rows (P) and added in fp64 in a fixed order.  chunk_rows, M > 1024, the workspace and its query as for
+ * cgat_gp_fit_stats.  No atomics: bitwise deterministic; caller's stream, no allocation, no synchronisation. */
+size_t cgat_gp_fit_grad_workspace_bytes(int32_t N, int32_t M, int32_t D, int32_t chunk_rows);
+int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm, int32_t N, int32_t D, const float* Zimg, int32_t M,
+                     const float* centroid, const float* znorm, const float* W1img, const float* W1timg,
+                     const float* G2img, const float* g, float c, float s, float inv_two_l2, int32_t chunk_rows,
+                     double* colsum, double* d2sum, double* P, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
