@@ -1,16 +1,21 @@
-// Device code shared by the sparse-GP kernels: csrc/gphead.hip (prediction), csrc/gpfit.hip (the fit
+// Device and host code shared by the sparse-GP entries: csrc/gphead.hip (prediction), csrc/gpfit.hip (the fit
 // statistics) and csrc/gpgrad.hip (the gradient of the bound).  All work on a tile of 32 rows of
 // X with one 512-thread workgroup (8 waves, two per SIMD):
+//   GpTile              the operands of phase (a), filled by gp_tile_operands; the kernels that run it derive theirs from it
 //   gp_distance_tile    max(|x_row - z_m|^2, 0) of the tile, handed to a functor
 //   gp_kernel_tile      K^T[m][row] = s exp(-max(|x_row - z_m|^2, 0) inv_two_l2) of the tile, into LDS
 //   gp_factor_products  NB 32-row chunks of a packed factor image times that K^T tile, on the f32-input matrix cores
-// and gp_launch_whiten_rows (host, defined in csrc/gpfit.hip) enqueues the whitening kernel of 10c for 10d.
+//   gp_for_wave_pairs   the chunk pairs of a triangular factor that a wave owns
+//   gp_check_entry      (host) the argument checks the three C entries share
+// and gp_launch_whiten_rows (host, defined in csrc/gpfit.hip) enqueues the whitening kernel of 10c for 10d.  The slab
+// products over a chunk of rows and the chunk walk of 10c and 10d are in gp_slab.h.
 //
 // Packed operand image of a row-major matrix P [R, Kd] (R a multiple of 32, Kd a multiple of 8):
 //   img[((c * Kd/8 + k8) * 64 + lane) * 4 + q] = P[32 c + (lane & 31)][8 k8 + 2 q + (lane >> 5)]
 // i.e. float4 number (c, k8, lane) holds lane's A operand of the four MFMA k-steps 8 k8 .. 8 k8 + 7 of chunk c.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -21,18 +26,53 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GP_XK 64                   // columns of X staged per step (the packed image of Zc is padded to this)
 #define GP_XP 33                   // pitch of the staged X tile: [k][row], conflict-free to write and to read
 
-// Operands of gp_whiten_rows (csrc/gpfit.hip): A~^T = [W1 K^T; y~; 1; 0] of one chunk of rows.
-struct GpWhitenArgs {
-  const float* X;                  // already offset to the chunk's first row
+// What gp_distance_tile and gp_kernel_tile read.
+struct GpTile {
+  const float* X;                  // offset to the first row the launch covers
   long ldx;
-  int G, D, M;                     // G: rows of X left from the chunk's first row (tiles past it are zero filled)
-  int Mp, Dp, Map;
-  const float4* Zimg;
-  const float* centroid;
-  const float* znorm;
+  int G, D, M;                     // G: rows of X from that row on (tiles past them are zero filled)
+  int Mp, Dp;                      // M rounded up to 32, D rounded up to 64
+  const float4* Zimg;              // packed image of Zc [Mp, Dp], zero padded
+  const float* centroid;           // [D]
+  const float* znorm;              // [Mp] |z_m - centroid|^2, zero padded
+  float s, inv_two_l2;
+};
+
+static inline int gp_pad_m(int M) { return (M + 31) & ~31; }
+static inline int gp_pad_d(int D) { return (D + GP_XK - 1) & ~(GP_XK - 1); }
+
+static inline GpTile gp_tile_operands(const float* X, int64_t ldx, int G, int D, const float* Zimg, int M,
+                                      const float* centroid, const float* znorm, float s, float inv_two_l2) {
+  return GpTile{X, (long)ldx, G, D, M, gp_pad_m(M), gp_pad_d(D), (const float4*)Zimg, centroid, znorm, s, inv_two_l2};
+}
+
+// The checks the three entries share, in the order they report: the shape (`rows_name` = `rows` >= min_rows), the refusal
+// of M > GP_MAX_M (`lds_clause`: who keeps the tile in LDS), chunk_rows where the entry has chunks (null otherwise), then,
+// unless the call is empty, the row stride, `operands` (every pointer the entry needs is there), `images` (the packed
+// images' addresses or-ed together) and the kernel's parameters.
+static inline int gp_check_entry(const char* name, const char* rows_name, int rows, int min_rows, int M, int D,
+                                 const char* lds_clause, const int32_t* chunk_rows, int64_t ldx, bool operands,
+                                 uintptr_t images, float s, float inv_two_l2) {
+  CGAT_CHECK_ARG(rows >= min_rows && M >= 1 && D >= 1, "%s: %s = %d, M = %d, D = %d", name, rows_name, rows, M, D);
+  if (M > GP_MAX_M) {
+    cgat_set_error("%s: M = %d inducing points; %s M <= %d", name, M, lds_clause, GP_MAX_M);
+    return CGAT_ERR_UNSUPPORTED;
+  }
+  CGAT_CHECK_ARG(!chunk_rows || (*chunk_rows >= 32 && (*chunk_rows & 31) == 0),
+                 "%s: chunk_rows = %d is not a positive multiple of 32", name, (int)*chunk_rows);
+  if (rows == 0) return CGAT_OK;
+  CGAT_CHECK_ARG(ldx >= D, "%s: ldx = %ld < D = %d", name, (long)ldx, D);
+  CGAT_CHECK_ARG(operands, "%s: null operand", name);
+  CGAT_CHECK_ARG((images & 15) == 0, "%s: the packed images need 16-byte alignment", name);
+  CGAT_CHECK_ARG(s >= 0.f && inv_two_l2 > 0.f, "%s: outputscale / lengthscale out of range", name);
+  return CGAT_OK;
+}
+
+// Operands of gp_whiten_rows (csrc/gpfit.hip): A~^T = [W1 K^T; y~; 1; 0] of one chunk of rows.
+struct GpWhitenArgs : GpTile {
+  int Map;
   const float4* W1img;             // packed image of W1 [Mp, Mp], lower triangular, zero padded
   const float* y_norm;             // offset like X
-  float s, inv_two_l2;
   float* At;                       // [Map][pitch]
   long pitch;
 };
@@ -88,9 +128,24 @@ __device__ __forceinline__ void gp_factor_products(const float4* __restrict__ Fi
   }
 }
 
+// The chunk pairs of a triangular factor [Mp, Mp] (nC = Mp / 32 chunks): pair q covers chunks 2 q and 2 q + 1, whose
+// column blocks stop (lower triangle) or start (upper) at their diagonal, so the work of a pair grows with q.  Pairs q and
+// 15 - q of every sixteen go to the same wave, which balances the triangle over the 8 waves.  body(c0) receives the first
+// chunk c0 = 2 q of each pair `wave` owns, in that order.
+template <class Body>
+__device__ __forceinline__ void gp_for_wave_pairs(int nC, int wave, Body body) {
+  const int n_pairs = (nC + 1) >> 1;
+  for (int base = 0; base < n_pairs; base += 16) {
+    const int q[2] = {base + wave, base + 15 - wave};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (q[i] < n_pairs) body(2 * q[i]);
+  }
+}
+
 // Phase (a) of the kernels: cross products of the tile's rows (row0 ..) with every inducing point and the norms;
 // store(m, d2) receives max(|x_r - z_m|^2, 0) of inducing index m < Mp and X row r = lane & 31 of the tile, once each, in
-// wave-uniform control flow.  `p` carries X, ldx, G (rows of X), D, Mp, Dp, Zimg, centroid, znorm.  Xs [64][33] is LDS.
+// wave-uniform control flow.  `p` is a GpTile or derives from one.  Xs [64][33] is LDS.
 // Rows of the tile at or past G are staged as zeros (their distances are those of x = centroid: finite, and the caller's
 // to discard).
 template <class Args, class Store>
@@ -151,7 +206,7 @@ __device__ __forceinline__ void gp_distance_tile(const Args& p, long row0, float
     if (c < nC) {
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
-        const int m = 32 * c + (t & 3) + 8 * (t >> 2) + 4 * hi;
+        const int m = gp_acc_index(c, t, hi);
         float d2 = xn + p.znorm[m] - 2.f * acc[j][t];
         d2 = fmaxf(d2, 0.f);
         store(m, d2);
@@ -160,8 +215,8 @@ __device__ __forceinline__ void gp_distance_tile(const Args& p, long row0, float
   }
 }
 
-// K^T[m][row] = s exp(-d2 inv_two_l2) of the tile into Kt [Mp][32] (LDS), 0 for m >= M; `p` carries M, s, inv_two_l2 as
-// well.  The caller synchronises before it reads Kt.
+// K^T[m][row] = s exp(-d2 inv_two_l2) of the tile into Kt [Mp][32] (LDS), 0 for m >= M.  The caller synchronises before it
+// reads Kt.
 template <class Args>
 __device__ __forceinline__ void gp_kernel_tile(const Args& p, long row0, float* Kt, float* Xs) {
   const int r = threadIdx.x & 31;

@@ -20,19 +20,15 @@
 //                     the buffer; sum over the tile's 32 rows of r and of r d2 by lane shuffles, one fp32 partial per
 //                     (tile, m).  d2 is the recomputed distance, never -log(k / s) 2 l^2.
 //   gp_centre_rows    Xc^T [D][pitch] = (x - centroid)^T of the chunk, rows at or past N zero
-//   gp_pair_slabs     R^T Xc over the chunk on the f32-input matrix cores, the structure of gp_gram_slabs with two
-//                     operands: 128 x 128 output tiles (grid.x), fixed slabs of 1024 rows (grid.y), one fp32 partial each
-//   gp_grad_reduce_*  VALU fp64: tiles / slabs added in order; the first chunk stores, later chunks add.
+//   gp_pair_slabs     R^T Xc over the chunk on the f32-input matrix cores, gp_slab_product (gp_slab.h) as gp_gram_slabs
+//                     but with two operands: 128 x 128 output tiles (grid.x), fixed slabs of 1024 rows (grid.y), one fp32
+//                     partial each
+//   gp_grad_reduce_*  VALU fp64: tiles / slabs added in order (the pairs by gp_slab_reduce); the first chunk stores, later
+//                     chunks add.
 // No atomics: bitwise deterministic.  No allocation, no host synchronisation; the only host loop enqueues launches.
 #include "../../include/cgat_hip.h"
 #include "common.h"
-#include "gp_tile.h"
-
-#define GQ_TILE 128                // output tile of R^T Xc
-#define GQ_KS 32                   // rows of the chunk per staged panel
-#define GQ_PITCH 36                // floats per panel row in LDS
-#define GQ_SLAB 1024               // rows of the chunk per partial
-#define GQ_THREADS 256
+#include "gp_slab.h"
 
 struct GpApplyArgs {
   float* At;                       // [Map][pitch]; rows < M of the tile's 32 columns are replaced
@@ -57,44 +53,28 @@ __global__ __launch_bounds__(GP_THREADS) void gp_apply_factor(GpApplyArgs p) {
   const long col = row0 + r;
   const bool live = col < p.G;
   const float yc = p.g && live ? p.y_norm[col] - p.c : 0.f;
-  const int n_pairs = (nC + 1) >> 1;
-  for (int base = 0; base < n_pairs; base += 16) {
-    const int q[2] = {base + wave, base + 15 - wave};
+  gp_for_wave_pairs(nC, wave, [&](int c0) {
+    const int k8_0 = p.upper ? 4 * c0 : 0;
+    f32x16 acc[2];
+    gp_factor_products<2>(p.Fimg + (long)k8_0 * 64, Bt + k8_0 * 8 * GP_ROWS, c0, nC, nk8, nk8 - k8_0, lane, acc);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (q[i] < n_pairs) {
-        const int c0 = 2 * q[i];
-        const int k8_0 = p.upper ? 4 * c0 : 0;
-        f32x16 acc[2];
-        gp_factor_products<2>(p.Fimg + (long)k8_0 * 64, Bt + k8_0 * 8 * GP_ROWS, c0, nC, nk8, nk8 - k8_0, lane, acc);
+    for (int j = 0; j < 2; ++j) {
+      if (c0 + j < nC) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (c0 + j < nC) {
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-              const int m = gp_acc_index(c0 + j, t, hi);
-              if (m < p.M) {
-                float v = acc[j][t];
-                if (p.g) v = fmaf(p.g[m], yc, v);
-                p.At[(long)m * p.pitch + col] = live ? v : 0.f;
-              }
-            }
+        for (int t = 0; t < 16; ++t) {
+          const int m = gp_acc_index(c0 + j, t, hi);
+          if (m < p.M) {
+            float v = acc[j][t];
+            if (p.g) v = fmaf(p.g[m], yc, v);
+            p.At[(long)m * p.pitch + col] = live ? v : 0.f;
           }
         }
       }
     }
-  }
+  });
 }
 
-struct GpWeightArgs {
-  const float* X;                  // already offset to the chunk's first row
-  long ldx;
-  int G, D, M;
-  int Mp, Dp;
-  const float4* Zimg;
-  const float* centroid;
-  const float* znorm;
-  float s, inv_two_l2;
+struct GpWeightArgs : GpTile {
   float* At;                       // [Map][pitch]: u in, r = u k out
   long pitch;
   float* pc;                       // [tile][Mp]: sum over the tile's rows of r
@@ -153,94 +133,24 @@ __global__ __launch_bounds__(256) void gp_centre_rows(const float* __restrict__ 
 
 // Rt [>= M][pitch], Xt [D][pitch]; rows_p (a multiple of 32) columns are valid.  part [slab][tile][128][128], tile =
 // ti tiles_d + tj over (M, D).
-__global__ __launch_bounds__(GQ_THREADS) void gp_pair_slabs(const float* __restrict__ Rt, const float* __restrict__ Xt,
+__global__ __launch_bounds__(GS_THREADS) void gp_pair_slabs(const float* __restrict__ Rt, const float* __restrict__ Xt,
                                                             long pitch, int M, int D, int rows_p, float* __restrict__ part,
                                                             int tiles_d) {
-  __shared__ __attribute__((aligned(16))) float panel[2][GQ_TILE * GQ_PITCH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, hi = lane >> 5;
-  const int i0 = (blockIdx.x / tiles_d) * GQ_TILE, j0 = (blockIdx.x % tiles_d) * GQ_TILE;
-  const int n0 = blockIdx.y * GQ_SLAB;
-  const int n_stage = (min(GQ_SLAB, rows_p - n0)) / GQ_KS;
-  const int wi = 64 * (wave >> 1), wj = 64 * (wave & 1);       // this wave's 64 x 64 quadrant
+  int wi, wj;
+  gp_slab_quadrant(wi, wj);
+  const int i0 = (blockIdx.x / tiles_d) * GS_TILE, j0 = (blockIdx.x % tiles_d) * GS_TILE;
   const bool active = i0 + wi < M && j0 + wj < D;
-
-  // global -> registers: thread covers float4 (row = tid / 8 + 32 u, columns 4 (tid % 8) ..) of each panel
-  const int lrow = tid >> 3, lc4 = (tid & 7) * 4;
-  float4 gA[4], gB[4];
-  auto fetch = [&](int stage) {
-    const long col = (long)n0 + (long)stage * GQ_KS + lc4;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int ra = i0 + lrow + 32 * u, rb = j0 + lrow + 32 * u;
-      gA[u] = ra < M ? *(const float4*)(Rt + (long)ra * pitch + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-      gB[u] = rb < D ? *(const float4*)(Xt + (long)rb * pitch + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int t = 0; t < 16; ++t) acc[a][b][t] = 0.f;
-
-  fetch(0);
-  for (int stage = 0; stage < n_stage; ++stage) {
-    __syncthreads();                 // the previous stage's reads are done
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      *(float4*)(panel[0] + (lrow + 32 * u) * GQ_PITCH + lc4) = gA[u];
-      *(float4*)(panel[1] + (lrow + 32 * u) * GQ_PITCH + lc4) = gB[u];
-    }
-    __syncthreads();
-    if (stage + 1 < n_stage) fetch(stage + 1);
-    if (active) {
-#pragma unroll
-      for (int k8 = 0; k8 < GQ_KS / 8; ++k8) {
-        float4 fa[2], fb[2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          fa[a] = *(const float4*)(panel[0] + (wi + 32 * a + r) * GQ_PITCH + 8 * k8 + 4 * hi);
-          fb[a] = *(const float4*)(panel[1] + (wj + 32 * a + r) * GQ_PITCH + 8 * k8 + 4 * hi);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a].x, fb[b].x, acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a].y, fb[b].y, acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a].z, fb[b].z, acc[a][b], 0, 0, 0);
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[a].w, fb[b].w, acc[a][b], 0, 0, 0);
-          }
-      }
-    }
-  }
-  if (active) {
-    float* out = part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (GQ_TILE * GQ_TILE);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-          const int i = wi + gp_acc_index(a, t, hi), j = wj + 32 * b + r;
-          out[i * GQ_TILE + j] = acc[a][b][t];
-        }
-  }
+  gp_slab_product(Rt, M, Xt, D, pitch, i0, j0, blockIdx.y * GS_SLAB, rows_p, active,
+                  part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (GS_TILE * GS_TILE));
 }
 
 // P [M][D].  grid (n_tiles, 128 * 128 / 256): one thread per element of the output tiles.
 __global__ __launch_bounds__(256) void gp_grad_reduce_pairs(const float* __restrict__ part, int tiles_d, int n_slabs, int M,
                                                             int D, double* __restrict__ P, int first) {
   const int e = blockIdx.y * 256 + threadIdx.x;
-  const int i = (blockIdx.x / tiles_d) * GQ_TILE + (e >> 7), j = (blockIdx.x % tiles_d) * GQ_TILE + (e & 127);
+  const int i = (blockIdx.x / tiles_d) * GS_TILE + (e >> 7), j = (blockIdx.x % tiles_d) * GS_TILE + (e & 127);
   if (i >= M || j >= D) return;
-  const float* src = part + (long)blockIdx.x * (GQ_TILE * GQ_TILE) + e;
-  double sum = 0.0;
-  for (int sl = 0; sl < n_slabs; ++sl) sum += (double)src[(long)sl * gridDim.x * (GQ_TILE * GQ_TILE)];
-  if (!first) sum += P[(long)i * D + j];
-  P[(long)i * D + j] = sum;
+  gp_slab_reduce(part, gridDim.x, n_slabs, e, P + (long)i * D + j, first);
 }
 
 // colsum [M], d2sum [M] from the per-tile partials [n_row_tiles][Mp].  A block owns GQ_RC_COLS columns; the tiles are
@@ -278,32 +188,18 @@ __global__ __launch_bounds__(GQ_RC_COLS * GQ_RC_SEGS) void gp_grad_reduce_column
 }
 
 // ---- host ----
-struct GqShape {
-  int Mp, Dp, Map, tiles_m, tiles_d, eff_chunk, max_slabs;
-  size_t at_bytes, xt_bytes, col_bytes, part_bytes;
-  size_t total() const { return at_bytes + xt_bytes + 2 * col_bytes + part_bytes; }
-};
-
-static GqShape gq_shape(int N, int M, int D, int chunk_rows) {
-  GqShape g;
-  g.Mp = (M + 31) & ~31;
-  g.Dp = (D + GP_XK - 1) & ~(GP_XK - 1);
-  g.Map = (M + 2 + 31) & ~31;
-  g.tiles_m = cdiv(M, GQ_TILE);
-  g.tiles_d = cdiv(D, GQ_TILE);
-  const long n_p = ((long)N + 31) & ~31L;                 // a chunk never holds more than the rows there are
-  g.eff_chunk = (int)(n_p < (long)chunk_rows ? n_p : (long)chunk_rows);
-  g.max_slabs = cdiv(g.eff_chunk, GQ_SLAB);
-  g.at_bytes = ws_round((size_t)g.Map * g.eff_chunk, sizeof(float));
-  g.xt_bytes = ws_round((size_t)D * g.eff_chunk, sizeof(float));
-  g.col_bytes = ws_round((size_t)(g.eff_chunk / GP_ROWS) * g.Mp, sizeof(float));
-  g.part_bytes = ws_round((size_t)g.max_slabs * g.tiles_m * g.tiles_d * GQ_TILE * GQ_TILE, sizeof(float));
-  return g;
+static int gq_tiles(int M, int D) { return cdiv(M, GS_TILE) * cdiv(D, GS_TILE); }
+static size_t gq_xt_elems(const GpChunks& c, int D) { return (size_t)D * c.eff_chunk; }
+static size_t gq_col_elems(const GpChunks& c) { return (size_t)(c.eff_chunk / GP_ROWS) * c.Mp; }
+static size_t gq_part_elems(const GpChunks& c, int M, int D) {
+  return (size_t)c.max_slabs * gq_tiles(M, D) * GS_TILE * GS_TILE;
 }
 
 extern "C" size_t cgat_gp_fit_grad_workspace_bytes(int32_t N, int32_t M, int32_t D, int32_t chunk_rows) {
-  if (N < 1 || M < 1 || M > GP_MAX_M || D < 1 || chunk_rows < 32 || (chunk_rows & 31)) return 0;
-  return gq_shape(N, M, D, chunk_rows).total();
+  if (!GpChunks::fits(N, M, D, chunk_rows)) return 0;
+  const GpChunks c(N, M, D, chunk_rows);
+  return ws_round(c.at_elems(), sizeof(float)) + ws_round(gq_xt_elems(c, D), sizeof(float)) +
+         2 * ws_round(gq_col_elems(c), sizeof(float)) + ws_round(gq_part_elems(c, M, D), sizeof(float));
 }
 
 extern "C" int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm, int32_t N, int32_t D, const float* Zimg,
@@ -312,76 +208,52 @@ extern "C" int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm
                                 float inv_two_l2, int32_t chunk_rows, double* colsum, double* d2sum, double* P, void* ws,
                                 size_t ws_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  CGAT_CHECK_ARG(N >= 1 && M >= 1 && D >= 1, "gp_fit_grad: N = %d, M = %d, D = %d", (int)N, (int)M, (int)D);
-  if (M > GP_MAX_M) {
-    cgat_set_error("gp_fit_grad: M = %d inducing points; the kernels keep a 32 x M tile of the cross-kernel matrix in LDS "
-                   "and support M <= %d", (int)M, GP_MAX_M);
-    return CGAT_ERR_UNSUPPORTED;
-  }
-  CGAT_CHECK_ARG(chunk_rows >= 32 && (chunk_rows & 31) == 0, "gp_fit_grad: chunk_rows = %d is not a positive multiple of 32",
-                 (int)chunk_rows);
-  CGAT_CHECK_ARG(ldx >= D, "gp_fit_grad: ldx = %ld < D = %d", (long)ldx, (int)D);
-  CGAT_CHECK_ARG(X && y_norm && Zimg && centroid && znorm && W1img && W1timg && G2img && g && colsum && d2sum && P,
-                 "gp_fit_grad: null operand");
-  CGAT_CHECK_ARG((((uintptr_t)Zimg | (uintptr_t)W1img | (uintptr_t)W1timg | (uintptr_t)G2img) & 15) == 0,
-                 "gp_fit_grad: the packed images need 16-byte alignment");
-  CGAT_CHECK_ARG(s >= 0.f && inv_two_l2 > 0.f, "gp_fit_grad: outputscale / lengthscale out of range");
-  const GqShape q = gq_shape(N, M, D, chunk_rows);
-  if (!ws || ws_bytes < q.total()) {
-    cgat_set_error("gp_fit_grad: workspace of %zu bytes, %zu needed", ws ? ws_bytes : (size_t)0, q.total());
-    return CGAT_ERR_WORKSPACE;
-  }
-  CGAT_CHECK_ARG(((uintptr_t)ws & 15) == 0, "gp_fit_grad: the workspace needs 16-byte alignment");
+  CGAT_TRY(gp_check_entry(
+      "gp_fit_grad", "N", N, 1, M, D, "the kernels keep a 32 x M tile of the cross-kernel matrix in LDS and support",
+      &chunk_rows, ldx, X && y_norm && Zimg && centroid && znorm && W1img && W1timg && G2img && g && colsum && d2sum && P,
+      (uintptr_t)Zimg | (uintptr_t)W1img | (uintptr_t)W1timg | (uintptr_t)G2img, s, inv_two_l2));
+  CGAT_TRY(gp_check_workspace("gp_fit_grad", ws, ws_bytes, cgat_gp_fit_grad_workspace_bytes(N, M, D, chunk_rows)));
+  GpChunks ch(N, M, D, chunk_rows);
   Workspace w(ws, ws_bytes);
-  float* At = w.take<float>((size_t)q.Map * q.eff_chunk);
-  float* Xt = w.take<float>((size_t)D * q.eff_chunk);
-  float* pc = w.take<float>((size_t)(q.eff_chunk / GP_ROWS) * q.Mp);
-  float* pd = w.take<float>((size_t)(q.eff_chunk / GP_ROWS) * q.Mp);
-  float* part = w.take<float>((size_t)q.max_slabs * q.tiles_m * q.tiles_d * GQ_TILE * GQ_TILE);
-  const long pitch = q.eff_chunk;
-  GpWhitenArgs a;
-  a.ldx = (long)ldx; a.D = D; a.M = M; a.Mp = q.Mp; a.Dp = q.Dp; a.Map = q.Map;
-  a.Zimg = (const float4*)Zimg; a.centroid = centroid; a.znorm = znorm; a.W1img = (const float4*)W1img;
-  a.s = s; a.inv_two_l2 = inv_two_l2; a.At = At; a.pitch = pitch;
+  float* At = w.take<float>(ch.at_elems());
+  float* Xt = w.take<float>(gq_xt_elems(ch, D));
+  float* pc = w.take<float>(gq_col_elems(ch));
+  float* pd = w.take<float>(gq_col_elems(ch));
+  float* part = w.take<float>(gq_part_elems(ch, M, D));
+  const long pitch = ch.eff_chunk;
+  const GpTile tile = gp_tile_operands(X, ldx, 0, D, Zimg, M, centroid, znorm, s, inv_two_l2);
+  GpWhitenArgs a{tile, ch.Map, (const float4*)W1img, nullptr, At, pitch};
+  GpWeightArgs k{tile, At, pitch, pc, pd};
   GpApplyArgs f;
-  f.At = At; f.pitch = pitch; f.M = M; f.Mp = q.Mp; f.c = c;
-  GpWeightArgs k;
-  k.ldx = (long)ldx; k.D = D; k.M = M; k.Mp = q.Mp; k.Dp = q.Dp;
-  k.Zimg = (const float4*)Zimg; k.centroid = centroid; k.znorm = znorm; k.s = s; k.inv_two_l2 = inv_two_l2;
-  k.At = At; k.pitch = pitch; k.pc = pc; k.pd = pd;
-  const int n_tiles = q.tiles_m * q.tiles_d;
+  f.At = At; f.pitch = pitch; f.M = M; f.Mp = ch.Mp; f.c = c;
+  const int n_tiles = gq_tiles(M, D), tiles_d = cdiv(D, GS_TILE);
   CGAT_PROF("gp_fit_grad", st);
-  for (long base = 0; base < N; base += q.eff_chunk) {
-    const long left = (long)N - base;
-    const int rows = (int)(left < q.eff_chunk ? left : (long)q.eff_chunk);
-    const int rows_p = (rows + 31) & ~31;
-    const int row_tiles = rows_p / GP_ROWS;
-    const int n_slabs = cdiv(rows_p, GQ_SLAB);
-    const int first = base == 0 ? 1 : 0;
-    a.X = X + base * (long)ldx; a.y_norm = y_norm + base; a.G = rows;
-    gp_launch_whiten_rows(a, row_tiles, st);
+  while (ch.next()) {
+    ch.place(a, X);
+    ch.place(k, X);
+    a.y_norm = f.y_norm = y_norm + ch.base;
+    f.G = ch.rows;
+    gp_launch_whiten_rows(a, ch.row_tiles, st);
     CGAT_LAUNCH_CHECK();
-    f.G = rows; f.y_norm = y_norm + base;
     f.Fimg = (const float4*)G2img; f.upper = 0; f.g = g;
-    hipLaunchKernelGGL(gp_apply_factor, dim3(row_tiles), dim3(GP_THREADS), 0, st, f);
+    hipLaunchKernelGGL(gp_apply_factor, dim3(ch.row_tiles), dim3(GP_THREADS), 0, st, f);
     CGAT_LAUNCH_CHECK();
     f.Fimg = (const float4*)W1timg; f.upper = 1; f.g = nullptr;
-    hipLaunchKernelGGL(gp_apply_factor, dim3(row_tiles), dim3(GP_THREADS), 0, st, f);
+    hipLaunchKernelGGL(gp_apply_factor, dim3(ch.row_tiles), dim3(GP_THREADS), 0, st, f);
     CGAT_LAUNCH_CHECK();
-    k.X = a.X; k.G = rows;
-    hipLaunchKernelGGL(gp_weight_rows, dim3(row_tiles), dim3(GP_THREADS), 0, st, k);
+    hipLaunchKernelGGL(gp_weight_rows, dim3(ch.row_tiles), dim3(GP_THREADS), 0, st, k);
     CGAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gp_centre_rows, dim3(row_tiles, cdiv(D, 32)), dim3(256), 0, st, a.X, (long)ldx, rows, (int)D, centroid,
-                       Xt, pitch);
+    hipLaunchKernelGGL(gp_centre_rows, dim3(ch.row_tiles, cdiv(D, 32)), dim3(256), 0, st, a.X, (long)ldx, ch.rows, (int)D,
+                       centroid, Xt, pitch);
     CGAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gp_pair_slabs, dim3(n_tiles, n_slabs), dim3(GQ_THREADS), 0, st, At, Xt, pitch, (int)M, (int)D, rows_p,
-                       part, q.tiles_d);
+    hipLaunchKernelGGL(gp_pair_slabs, dim3(n_tiles, ch.n_slabs), dim3(GS_THREADS), 0, st, At, Xt, pitch, (int)M, (int)D,
+                       ch.rows_p, part, tiles_d);
     CGAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gp_grad_reduce_pairs, dim3(n_tiles, GQ_TILE * GQ_TILE / 256), dim3(256), 0, st, part, q.tiles_d, n_slabs,
-                       (int)M, (int)D, P, first);
+    hipLaunchKernelGGL(gp_grad_reduce_pairs, dim3(n_tiles, GS_TILE * GS_TILE / 256), dim3(256), 0, st, part, tiles_d,
+                       ch.n_slabs, (int)M, (int)D, P, ch.first);
     CGAT_LAUNCH_CHECK();
     hipLaunchKernelGGL(gp_grad_reduce_columns, dim3(cdiv(M, GQ_RC_COLS)), dim3(GQ_RC_COLS * GQ_RC_SEGS), 0, st, pc, pd,
-                       row_tiles, q.Mp, (int)M, colsum, d2sum, first);
+                       ch.row_tiles, ch.Mp, (int)M, colsum, d2sum, ch.first);
     CGAT_LAUNCH_CHECK();
   }
   return CGAT_OK;

@@ -19,28 +19,21 @@
 //       LDS without bank conflicts: 32 x 1024 x 4 B = 128 KiB of the CU's 160.  It never goes to HBM.
 //   (b) U = F . K^T with F = [W1; W2] streamed from L2 / HBM through the same packed image, the K^T tile as the B
 //       operand from LDS.  Again row-on-lane: each lane squares and sums its 16 registers per chunk.  W1 is lower
-//       triangular, so its chunk pairs stop at the diagonal block; pairs q and 15 - q go to the same wave, which
-//       balances the triangle over the 8 waves.  k_x . a is a VALU pass over the tile.
+//       triangular, so its chunk pairs stop at the diagonal block and are dealt to the waves by gp_for_wave_pairs.
+//       k_x . a is a VALU pass over the tile.
 //   (c) the per-wave partial sums are added in a fixed order and 32 lanes write the outputs.
 // No atomics: bitwise deterministic.  No workspace, no host synchronisation: capturable.
 //
-// The packed operand image, the tile constants and the device code of (a) and of the products of (b) are in gp_tile.h,
-// shared with csrc/gpfit.hip.
+// The packed operand image, the tile constants, the operand record GpTile, the device code of (a) and of the products
+// of (b) and the entries' argument check are in gp_tile.h, shared with csrc/gpfit.hip and csrc/gpgrad.hip.
 #include "../../include/cgat_hip.h"
 #include "common.h"
 #include "gp_tile.h"
 
-struct GpArgs {
-  const float* X;
-  long ldx;
-  int G, D, M;
-  int Mp, Dp;                      // M rounded up to 32, D rounded up to 64
-  const float4* Zimg;              // packed image of Zc [Mp, Dp], zero padded
-  const float* centroid;           // [D]
-  const float* znorm;              // [Mp] |z_m - centroid|^2, zero padded
+struct GpArgs : GpTile {
   const float* avec;               // [Mp] a, zero padded
   const float4* Fimg;              // packed image of [W1; W2], each section [Mp, Mp], zero padded
-  float c, s, inv_two_l2, tgt_mean, tgt_std;
+  float c, tgt_mean, tgt_std;
   float *mean_f, *var_f, *pred, *lower, *upper;
 };
 
@@ -88,18 +81,10 @@ __global__ __launch_bounds__(GP_THREADS) void gp_predict_kernel(GpArgs p) {
   float ss1 = 0.f, ss2 = 0.f;
   const int nk8 = p.Mp >> 3;
   {
-    // W1, chunk pairs: pair q covers chunks 2q, 2q + 1 and the column blocks up to their diagonal
-    const int n_pairs = (nC + 1) >> 1;
-    for (int base = 0; base < n_pairs; base += 16) {
-      const int q[2] = {base + wave, base + 15 - wave};
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (q[i] < n_pairs) {
-          const int c0 = 2 * q[i];
-          ss1 += gp_factor_group<2>(p.Fimg, Kt, c0, nC, nk8, min(nk8, 4 * (c0 + 2)), lane);
-        }
-      }
-    }
+    // W1, chunk pairs up to their diagonal block
+    gp_for_wave_pairs(nC, wave, [&](int c0) {
+      ss1 += gp_factor_group<2>(p.Fimg, Kt, c0, nC, nk8, min(nk8, 4 * (c0 + 2)), lane);
+    });
     // W2, chunk quads over the full width
     const int n_quads = (nC + 3) >> 2;
     const float4* F2 = p.Fimg + (long)nC * nk8 * 64;
@@ -146,27 +131,13 @@ extern "C" int cgat_gp_predict(const float* X, int64_t ldx, int32_t G, int32_t D
                                float* lower, float* upper, void* ws, size_t ws_bytes, void* stream) {
   (void)ws; (void)ws_bytes;
   hipStream_t st = (hipStream_t)stream;
-  CGAT_CHECK_ARG(G >= 0 && M >= 1 && D >= 1, "gp_predict: G = %d, M = %d, D = %d", (int)G, (int)M, (int)D);
-  if (M > GP_MAX_M) {
-    cgat_set_error("gp_predict: M = %d inducing points; the fused kernel keeps a 32 x M tile of the cross-kernel matrix in "
-                   "LDS and supports M <= %d", (int)M, GP_MAX_M);
-    return CGAT_ERR_UNSUPPORTED;
-  }
+  CGAT_TRY(gp_check_entry("gp_predict", "G", G, 0, M, D,
+                          "the fused kernel keeps a 32 x M tile of the cross-kernel matrix in LDS and supports", nullptr, ldx,
+                          X && Zimg && centroid && znorm && factors && mean_f && var_f,
+                          (uintptr_t)Zimg | (uintptr_t)factors, s, inv_two_l2));
   if (G == 0) return CGAT_OK;
-  CGAT_CHECK_ARG(ldx >= D, "gp_predict: ldx = %ld < D = %d", (long)ldx, (int)D);
-  CGAT_CHECK_ARG(X && Zimg && centroid && znorm && factors && mean_f && var_f, "gp_predict: null operand");
-  CGAT_CHECK_ARG((((uintptr_t)Zimg | (uintptr_t)factors) & 15) == 0, "gp_predict: the packed images need 16-byte alignment");
-  CGAT_CHECK_ARG(s >= 0.f && inv_two_l2 > 0.f, "gp_predict: outputscale / lengthscale out of range");
-  GpArgs a;
-  a.X = X; a.ldx = (long)ldx; a.G = G; a.D = D; a.M = M;
-  a.Mp = (M + 31) & ~31;
-  a.Dp = (D + GP_XK - 1) & ~(GP_XK - 1);
-  a.Zimg = (const float4*)Zimg;
-  a.centroid = centroid; a.znorm = znorm;
-  a.avec = factors;
-  a.Fimg = (const float4*)(factors + a.Mp);
-  a.c = c; a.s = s; a.inv_two_l2 = inv_two_l2; a.tgt_mean = tgt_mean; a.tgt_std = tgt_std;
-  a.mean_f = mean_f; a.var_f = var_f; a.pred = pred; a.lower = lower; a.upper = upper;
+  const GpTile t = gp_tile_operands(X, ldx, G, D, Zimg, M, centroid, znorm, s, inv_two_l2);
+  const GpArgs a{t, factors, (const float4*)(factors + t.Mp), c, tgt_mean, tgt_std, mean_f, var_f, pred, lower, upper};
   CGAT_PROF("gp_predict", st);
   hipLaunchKernelGGL(gp_predict_kernel, dim3(cdiv(G, GP_ROWS)), dim3(GP_THREADS), 0, st, a);
   CGAT_LAUNCH_CHECK();

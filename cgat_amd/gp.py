@@ -130,8 +130,8 @@ DEFAULT_CHUNK_ROWS = 32768
 
 class _StatisticsPass:
     """What a cgat_gp_fit_stats call needs and (l, s) do not change: the checked operands, the centred image of Z on the
-    device, the workspace, the output.  Calling it with (s, l, jitter) factors K_zz on the host in fp64, uploads the
-    image of W1 and enqueues the pass; a later call overwrites the same `gram`."""
+    device, the workspace, the output.  factor(s, l, jitter) factors K_zz on the host in fp64 and uploads the image of
+    W1; calling the object does that and enqueues the pass; a later call overwrites the same `gram`."""
 
     def __init__(self, what, embeddings, y_norm, inducing_points, chunk_rows, extra_workspace=None):
         Z = torch.as_tensor(inducing_points)
@@ -163,26 +163,34 @@ class _StatisticsPass:
         self.Z = Z
         cen, self.Zc, self.zn = _centred64(Z)
         self.ops = _tile_operands(cen, self.Zc, self.zn, self.x.device)
+        self.W1 = self.w1img = None                         # of the Z before; factor() sets them
 
-    def _image(self, P):
+    def image(self, P):
         """The packed image of P [M, M] padded with zeros to [Mp, Mp], fp32 on the device."""
         M, Mp = self.M, (self.M + 31) // 32 * 32
         Pp = torch.zeros(Mp, Mp, dtype=torch.float32)
         Pp[:M, :M] = P
         return _pack_image(Pp).to(self.x.device)
 
+    _image = image
+
+    def factor(self, outputscale, lengthscale, jitter):
+        """W1 = chol(K_zz + jitter I)^-1 for (s, l) in fp64 on the host, as `W1`, and its image on the device, as `w1img`:
+        what both passes whiten with until the next call."""
+        _, self.W1 = _whitening64(self.Zc, self.zn, float(outputscale), float(lengthscale), float(jitter))
+        self.w1img = self.image(self.W1)
+
     def __call__(self, outputscale, lengthscale, jitter):
         s, ell = float(outputscale), float(lengthscale)
         if not (s > 0.0 and ell > 0.0):
             raise ValueError(f"{self.what}: outputscale and lengthscale must be positive")
         M, x, ops, dev = self.M, self.x, self.ops, self.x.device
-        _, W1 = _whitening64(self.Zc, self.zn, s, ell, float(jitter))
-        self.W1 = W1
-        self.w1img = w1img = self._image(W1)
+        self.factor(s, ell, jitter)
         with torch.cuda.device(dev):
             rc = _lib.lib.cgat_gp_fit_stats(_ptr(x), x.stride(0), _ptr(self.y32), self.N, self.D, _ptr(ops["zimg"]), M,
-                                            _ptr(ops["centroid"]), _ptr(ops["znorm"]), _ptr(w1img), s, 0.5 / (ell * ell),
-                                            self.chunk, _ptr(self.gram), _ptr(self.ws), self.ws_bytes, _stream())
+                                            _ptr(ops["centroid"]), _ptr(ops["znorm"]), _ptr(self.w1img), s,
+                                            0.5 / (ell * ell), self.chunk, _ptr(self.gram), _ptr(self.ws), self.ws_bytes,
+                                            _stream())
         _lib.check(rc, "cgat_gp_fit_stats")
         return self.gram
 
@@ -325,12 +333,16 @@ class _GradientPass:
         self.stats.set_inducing_points(Z)
 
     def sums(self, outputscale, lengthscale, two_G_hat, g, constant):
-        """Enqueues cgat_gp_fit_grad with the W1 of the statistics pass that went before; (colsum, d2sum, P)."""
+        """Enqueues cgat_gp_fit_grad with the W1 of the last stats.factor() (a statistics pass makes one); (colsum, d2sum,
+        P)."""
         st = self.stats
+        if st.W1 is None:
+            raise RuntimeError(f"{st.what}: no factorisation of K_zz yet; call stats.factor(outputscale, lengthscale, "
+                               "jitter) or the statistics pass before sums()")
         s, ell = float(outputscale), float(lengthscale)
         x, ops, dev = st.x, st.ops, st.x.device
-        w1timg = st._image(st.W1.T)
-        g2img = st._image(torch.as_tensor(two_G_hat).to("cpu", torch.float64))
+        w1timg = st.image(st.W1.T)
+        g2img = st.image(torch.as_tensor(two_G_hat).to("cpu", torch.float64))
         g32 = torch.as_tensor(g).to("cpu", torch.float64).to(torch.float32).to(dev)
         with torch.cuda.device(dev):
             rc = _lib.lib.cgat_gp_fit_grad(_ptr(x), x.stride(0), _ptr(st.y32), st.N, st.D, _ptr(ops["zimg"]), st.M,
@@ -362,9 +374,7 @@ def fit_gradient_sums(embeddings, y_norm, inducing_points, outputscale, lengthsc
     device of `embeddings`: colsum [M], d2sum [M], P [M, D], for the adjoints `two_G_hat` [M, M] (= 2 dF/dPsi), `g` [M]
     and the constant c.  The other arguments as for fit_statistics; W1 is computed as there."""
     p = _GradientPass("fit_gradient_sums", embeddings, y_norm, inducing_points, chunk_rows)
-    st = p.stats
-    _, st.W1 = _whitening64(st.Zc, st.zn, float(outputscale), float(lengthscale), float(jitter))
-    st.w1img = st._image(st.W1)
+    p.stats.factor(outputscale, lengthscale, jitter)
     return p.sums(outputscale, lengthscale, two_G_hat, g, constant)
 
 

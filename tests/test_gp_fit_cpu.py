@@ -176,6 +176,22 @@ def test_workspace_query_positive_and_monotone():
     assert q(100, 1025, 8, 32768) == 0 and q(100, 8, 8, 48) == 0      # what the entry refuses
 
 
+# cgat_gp_fit_stats_workspace_bytes at the cases' (N, M, D, chunk_rows) (None: the default of 32768) and at training size
+WORKSPACE_BYTES = {"n70_m1_d1": 77824, "n150_m33_d5": 81920, "n300_m96_d65": 229376, "n1000_m129_d130": 851968,
+                   "n1100_m1000_d128": 9306112, "n1100_m1024_d384": 10629120, "n31_m30_d7": 69632}
+
+
+def test_workspace_query_pinned():
+    """The sizes the query has returned since the entry exists: the chunk plan it shares with the entry must not move them."""
+    from cgat_amd import _lib
+    q = _lib.lib.cgat_gp_fit_stats_workspace_bytes
+    assert set(WORKSPACE_BYTES) == set(F.CASES)
+    for name, kw in F.CASES.items():
+        assert q(kw["N"], kw["M"], kw["D"], kw.get("chunk_rows") or 32768) == WORKSPACE_BYTES[name], name
+    assert q(1000000, 1000, 384, 32768) == 209715200
+    assert q(100, 1025, 8, 32768) == 0 and q(100, 8, 8, 48) == 0 and q(0, 8, 8, 32) == 0
+
+
 def test_fit_and_statistics_refuse_cpu_dtype_and_width():
     import cgat_amd as P
     inp = F.case("n150_m33_d5")["inp"]

@@ -113,6 +113,22 @@ def test_total_gradients_and_the_colsum_identity(name):
     assert grads2["log_lengthscale"] == grads["log_lengthscale"] and grads2["log_outputscale"] == grads["log_outputscale"]
 
 
+def test_sums_before_any_factorisation_raise():
+    """_GradientPass.sums needs the W1 of a factorisation; without one, and again after the inducing points were
+    replaced, it says so and enqueues nothing."""
+    from cgat_amd import gp
+    c = Gc.case("n70_m1_d1")
+    inp, adj = c["inp"], c["adj"]
+    p = gp._GradientPass("test", inp["X"].to(DEV), c["y_norm"].to(DEV), inp["Z"], c["chunk_rows"])
+    with pytest.raises(RuntimeError, match="no factorisation"):
+        p.sums(c["s"], c["ell"], 2.0 * adj["G_hat"], adj["g"], c["c"])
+    p.stats.factor(c["s"], c["ell"], Gc.JITTER)
+    p.sums(c["s"], c["ell"], 2.0 * adj["G_hat"], adj["g"], c["c"])
+    p.set_inducing_points(inp["Z"])
+    with pytest.raises(RuntimeError, match="no factorisation"):
+        p.sums(c["s"], c["ell"], 2.0 * adj["G_hat"], adj["g"], c["c"])
+
+
 def _fit_n600(learn, **kw):
     import cgat_amd as P
     f = Gc.fit_case()

@@ -174,6 +174,22 @@ def test_workspace_query():
     assert q(100, 1025, 8, 32768) == 0 and q(100, 8, 8, 48) == 0 and q(0, 8, 8, 32) == 0      # what the entry refuses
 
 
+# cgat_gp_fit_grad_workspace_bytes at the (N, M, D, chunk_rows) of every case of gp_fit_cases (None: the default of 32768)
+WORKSPACE_BYTES = {"n70_m1_d1": 79360, "n150_m33_d5": 84224, "n300_m96_d65": 320256, "n1000_m129_d130": 1490944,
+                   "n1100_m1000_d128": 6496256, "n1100_m1024_d384": 9883648, "n31_m30_d7": 71168}
+
+
+def test_workspace_query_pinned():
+    """The sizes the query has returned since the entry exists: the chunk plan it shares with the entry must not move them."""
+    from cgat_amd import _lib
+    q = _lib.lib.cgat_gp_fit_grad_workspace_bytes
+    assert set(WORKSPACE_BYTES) == set(F.CASES)
+    for name, kw in F.CASES.items():
+        assert q(kw["N"], kw["M"], kw["D"], kw.get("chunk_rows") or 32768) == WORKSPACE_BYTES[name], name
+    assert q(1000000, 1000, 384, 32768) == 243269632
+    assert q(100, 1025, 8, 32768) == 0 and q(100, 8, 8, 48) == 0 and q(0, 8, 8, 32) == 0
+
+
 def test_entry_refuses_bad_arguments_before_any_launch():
     """The sibling's codes and messages, from host memory that no kernel could read: every refusal precedes the launches."""
     from cgat_amd import _lib

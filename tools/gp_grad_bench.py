@@ -93,13 +93,14 @@ def main():
         Z, ell = X[:M].cpu(), math.sqrt(D)
         both = gp._GradientPass("gp_grad_bench", X, y, Z, None)
         st = both.stats
-        sol, _ = both(s, ell, jitter)                                   # leaves W1 and its image on `st`
+        sol, _ = both(s, ell, jitter)
         adj = gp.collapsed_adjoints(st.gram, N, s, sol)
         two_G_hat, c = 2.0 * adj["G_hat"], sol["constant"]
         eager = EagerSums(Z, s, ell, jitter, two_G_hat, adj["g"], c, args.chunk, dev)
         # the C entries alone, on operands prepared once
         ops, inv = st.ops, 0.5 / (ell * ell)
-        w1img, w1timg, g2img = st.w1img, st._image(st.W1.T), st._image(two_G_hat)
+        st.factor(s, ell, jitter)
+        w1img, w1timg, g2img = st.w1img, st.image(st.W1.T), st.image(two_G_hat)
         g32 = adj["g"].to(torch.float32).to(dev)
         grad_ws = _lib.lib.cgat_gp_fit_grad_workspace_bytes(N, M, D, st.chunk)
 
