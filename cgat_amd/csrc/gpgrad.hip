@@ -19,6 +19,9 @@
 //   gp_weight_rows    phase (a) again (gp_distance_tile): d2 and k = s exp(-d2 inv_two_l2) in registers, r = u k back to
 //                     the buffer; sum over the tile's 32 rows of r and of r d2 by lane shuffles, one fp32 partial per
 //                     (tile, m).  d2 is the recomputed distance, never -log(k / s) 2 l^2.
+//   gp_input_rows     (only where dF/dX is asked for) dX = (R^T-tile x Zc - rho o (x - centroid)) / l^2 of the
+//                     chunk's rows: the tile of r in LDS as in gp_apply_factor, rho its column sums, gp_factor_products
+//                     with the packed image of Zc^T as the factor; reads the buffer only
 //   gp_centre_rows    Xc^T [D][pitch] = (x - centroid)^T of the chunk, rows at or past N zero
 //   gp_pair_slabs     R^T Xc over the chunk on the f32-input matrix cores, gp_slab_product (gp_slab.h) as gp_gram_slabs
 //                     but with two operands: 128 x 128 output tiles (grid.x), fixed slabs of 1024 rows (grid.y), one fp32
@@ -107,6 +110,113 @@ __global__ __launch_bounds__(GP_THREADS) void gp_weight_rows(GpWeightArgs p) {
       pd[m] = ds;
     }
   });
+}
+
+// dF/dx of the chunk's rows from r: dX[row][d] = (sum_m r[m][row] zc[m][d] - rho[row] (x[row][d] - centroid[d]))
+// / l^2 with rho = sum_m r[m][row].  One workgroup per tile of 32 rows, the tile of r [Mp][32] in LDS like gp_apply_factor's;
+// rows m >= M of the buffer are y~, 1 and padding (gp_whiten_rows) and are loaded as zero.
+struct GpInputArgs {
+  const float* At;                 // [Map][pitch]: r in rows < M
+  long pitch;
+  int G, M, Mp, D;                 // G: rows of the chunk (rows at or past it are not written)
+  const float4* Ztimg;             // packed image of Zc^T [D rounded up to 32, Mp], zero padded
+  const float* X;                  // offset to the chunk's first row, like dX
+  long ldx;
+  const float* centroid;
+  float inv_two_l2;
+  float* dX;
+  long lddx;
+  int vec_x, vec_dx;               // 16-byte loads of X / stores of dX are aligned
+};
+
+__global__ __launch_bounds__(GP_THREADS) void gp_input_rows(GpInputArgs p) {
+  __shared__ __attribute__((aligned(16))) float Bt[GP_ROWS * GP_MAX_M];      // the tile [Mp][32]
+  __shared__ float part[GP_THREADS];                                        // [16][32] partial column sums
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, hi = lane >> 5;
+  const int nC = (p.D + 31) >> 5, nk8 = p.Mp >> 3;
+  const long row0 = (long)blockIdx.x * GP_ROWS;
+  // thread tid copies column tid & 31 of rows tid >> 5, + 16, ...: its partial sum of that column, in row order
+  float ps = 0.f;
+  for (int i = tid; i < p.Mp * GP_ROWS; i += GP_THREADS) {
+    const int m = i >> 5;
+    const float v = m < p.M ? p.At[(long)m * p.pitch + row0 + (i & 31)] : 0.f;
+    Bt[i] = v;
+    ps += v;
+  }
+  part[tid] = ps;
+  __syncthreads();
+  float rho = 0.f;
+#pragma unroll
+  for (int j = 0; j < GP_THREADS / GP_ROWS; ++j) rho += part[j * GP_ROWS + r];     // the 16 partials in a fixed order
+
+  const long row = row0 + r;
+  const bool live = row < p.G;
+  const float scale = 2.f * p.inv_two_l2;
+  const float* xrow = p.X + row * p.ldx;
+  float* orow = p.dX + row * p.lddx;
+  // one rounding sequence whichever path loads and stores: the bits do not depend on the strides
+  auto value = [&](float acc, float x, int d) { return scale * fmaf(-rho, x - p.centroid[d], acc); };
+  auto emit = [&](int c, const f32x16& acc) {
+    if (!live) return;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int d0 = gp_acc_index(c, 4 * q, hi);                            // registers 4 q .. 4 q + 3: d0 .. d0 + 3
+      if (d0 + 3 < p.D) {
+        float x[4];
+        if (p.vec_x) {
+          const float4 xv = *(const float4*)(xrow + d0);
+          x[0] = xv.x; x[1] = xv.y; x[2] = xv.z; x[3] = xv.w;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) x[i] = xrow[d0 + i];
+        }
+        float o[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = value(acc[4 * q + i], x[i], d0 + i);
+        if (p.vec_dx) {
+          *(float4*)(orow + d0) = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) orow[d0 + i] = o[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int d = d0 + i;
+          if (d < p.D) orow[d] = value(acc[4 * q + i], xrow[d], d);
+        }
+      }
+    }
+  };
+  // The nC chunks of 32 embedding dimensions in 8 contiguous shares, the nC % 8 larger ones to the first waves: waves w and
+  // w + 4 run on one SIMD, so the matrix work per SIMD is even where nC % 8 <= 4 (D = 384: shares of 2 and 1 chunks, 3 per
+  // SIMD; D = 640: of 3 and 2, 5 per SIMD).  A share runs as pairs, its last three chunks as one triple (one pass over the
+  // tile in place of two).  Measured at N = 10^6, M = 1000: against shares dealt 1, 2, 1, 2, .. and pairs
+  // plus a single, 11.7 -> 9.9 ms at D = 384 and 17.0 -> 14.4 ms at D = 640.
+  const int base = nC / GP_WAVES, rem = nC % GP_WAVES;
+  const int c_lo = wave * base + min(wave, rem), c_hi = c_lo + base + (wave < rem ? 1 : 0);
+  for (int c = c_lo; c < c_hi;) {
+    if (c + 3 == c_hi) {
+      f32x16 acc[3];
+      gp_factor_products<3>(p.Ztimg, Bt, c, nC, nk8, nk8, lane, acc);
+      emit(c, acc[0]);
+      emit(c + 1, acc[1]);
+      emit(c + 2, acc[2]);
+      c += 3;
+    } else if (c + 1 < c_hi) {
+      f32x16 acc[2];
+      gp_factor_products<2>(p.Ztimg, Bt, c, nC, nk8, nk8, lane, acc);
+      emit(c, acc[0]);
+      emit(c + 1, acc[1]);
+      c += 2;
+    } else {
+      f32x16 acc[1];
+      gp_factor_products<1>(p.Ztimg, Bt, c, nC, nk8, nk8, lane, acc);
+      emit(c, acc[0]);
+      c += 1;
+    }
+  }
 }
 
 // Xt [D][pitch]: column n of the chunk is x_n - centroid, 0 for n >= G.  grid (rows_p / 32, cdiv(D, 32)).
@@ -202,17 +312,23 @@ extern "C" size_t cgat_gp_fit_grad_workspace_bytes(int32_t N, int32_t M, int32_t
          2 * ws_round(gq_col_elems(c), sizeof(float)) + ws_round(gq_part_elems(c, M, D), sizeof(float));
 }
 
-extern "C" int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm, int32_t N, int32_t D, const float* Zimg,
-                                int32_t M, const float* centroid, const float* znorm, const float* W1img,
-                                const float* W1timg, const float* G2img, const float* g, float c, float s,
-                                float inv_two_l2, int32_t chunk_rows, double* colsum, double* d2sum, double* P, void* ws,
-                                size_t ws_bytes, void* stream) {
+// Both entries: `inputs` asks for dX as well (Ztimg, dX, lddx are then checked; ignored otherwise).
+static int gp_fit_grad_run(const char* name, bool inputs, const float* X, int64_t ldx, const float* y_norm, int32_t N,
+                           int32_t D, const float* Zimg, int32_t M, const float* centroid, const float* znorm,
+                           const float* W1img, const float* W1timg, const float* G2img, const float* g, float c, float s,
+                           float inv_two_l2, int32_t chunk_rows, double* colsum, double* d2sum, double* P,
+                           const float* Ztimg, float* dX, int64_t lddx, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   CGAT_TRY(gp_check_entry(
-      "gp_fit_grad", "N", N, 1, M, D, "the kernels keep a 32 x M tile of the cross-kernel matrix in LDS and support",
+      name, "N", N, 1, M, D, "the kernels keep a 32 x M tile of the cross-kernel matrix in LDS and support",
       &chunk_rows, ldx, X && y_norm && Zimg && centroid && znorm && W1img && W1timg && G2img && g && colsum && d2sum && P,
       (uintptr_t)Zimg | (uintptr_t)W1img | (uintptr_t)W1timg | (uintptr_t)G2img, s, inv_two_l2));
-  CGAT_TRY(gp_check_workspace("gp_fit_grad", ws, ws_bytes, cgat_gp_fit_grad_workspace_bytes(N, M, D, chunk_rows)));
+  if (inputs) {
+    CGAT_CHECK_ARG(Ztimg && dX, "%s: null operand", name);
+    CGAT_CHECK_ARG(lddx >= D, "%s: lddx = %ld < D = %d", name, (long)lddx, D);
+    CGAT_CHECK_ARG(((uintptr_t)Ztimg & 15) == 0, "%s: the packed images need 16-byte alignment", name);
+  }
+  CGAT_TRY(gp_check_workspace(name, ws, ws_bytes, cgat_gp_fit_grad_workspace_bytes(N, M, D, chunk_rows)));
   GpChunks ch(N, M, D, chunk_rows);
   Workspace w(ws, ws_bytes);
   float* At = w.take<float>(ch.at_elems());
@@ -226,8 +342,10 @@ extern "C" int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm
   GpWeightArgs k{tile, At, pitch, pc, pd};
   GpApplyArgs f;
   f.At = At; f.pitch = pitch; f.M = M; f.Mp = ch.Mp; f.c = c;
+  GpInputArgs in{At, pitch, 0, (int)M, ch.Mp, (int)D, (const float4*)Ztimg, X, (long)ldx, centroid, inv_two_l2, dX, (long)lddx,
+                 (((uintptr_t)X & 15) == 0 && (ldx & 3) == 0) ? 1 : 0, (((uintptr_t)dX & 15) == 0 && (lddx & 3) == 0) ? 1 : 0};
   const int n_tiles = gq_tiles(M, D), tiles_d = cdiv(D, GS_TILE);
-  CGAT_PROF("gp_fit_grad", st);
+  CGAT_PROF(name, st);
   while (ch.next()) {
     ch.place(a, X);
     ch.place(k, X);
@@ -243,6 +361,13 @@ extern "C" int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm
     CGAT_LAUNCH_CHECK();
     hipLaunchKernelGGL(gp_weight_rows, dim3(ch.row_tiles), dim3(GP_THREADS), 0, st, k);
     CGAT_LAUNCH_CHECK();
+    if (inputs) {
+      in.G = ch.rows;
+      in.X = a.X;
+      in.dX = dX + ch.base * lddx;
+      hipLaunchKernelGGL(gp_input_rows, dim3(ch.row_tiles), dim3(GP_THREADS), 0, st, in);
+      CGAT_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(gp_centre_rows, dim3(ch.row_tiles, cdiv(D, 32)), dim3(256), 0, st, a.X, (long)ldx, ch.rows, (int)D,
                        centroid, Xt, pitch);
     CGAT_LAUNCH_CHECK();
@@ -257,4 +382,23 @@ extern "C" int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm
     CGAT_LAUNCH_CHECK();
   }
   return CGAT_OK;
+}
+
+extern "C" int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm, int32_t N, int32_t D, const float* Zimg,
+                                int32_t M, const float* centroid, const float* znorm, const float* W1img,
+                                const float* W1timg, const float* G2img, const float* g, float c, float s,
+                                float inv_two_l2, int32_t chunk_rows, double* colsum, double* d2sum, double* P, void* ws,
+                                size_t ws_bytes, void* stream) {
+  return gp_fit_grad_run("gp_fit_grad", false, X, ldx, y_norm, N, D, Zimg, M, centroid, znorm, W1img, W1timg, G2img, g, c, s,
+                         inv_two_l2, chunk_rows, colsum, d2sum, P, nullptr, nullptr, 0, ws, ws_bytes, stream);
+}
+
+extern "C" int cgat_gp_fit_grad_inputs(const float* X, int64_t ldx, const float* y_norm, int32_t N, int32_t D,
+                                       const float* Zimg, int32_t M, const float* centroid, const float* znorm,
+                                       const float* W1img, const float* W1timg, const float* G2img, const float* g, float c,
+                                       float s, float inv_two_l2, int32_t chunk_rows, double* colsum, double* d2sum,
+                                       double* P, const float* Ztimg, float* dX, int64_t lddx, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  return gp_fit_grad_run("gp_fit_grad_inputs", true, X, ldx, y_norm, N, D, Zimg, M, centroid, znorm, W1img, W1timg, G2img, g,
+                         c, s, inv_two_l2, chunk_rows, colsum, d2sum, P, Ztimg, dX, lddx, ws, ws_bytes, stream);
 }

@@ -59,7 +59,18 @@ P = sum_n r_n (x_n - centroid)^T in fp64:
 (2 G^ Psi + g beta^T) L^T pulled back by torch autograd on the M x M host graph.  `bound_and_gradient` is the two passes
 and the solve; `GPHead.fit(learn=("lengthscale", "outputscale", "inducing_points"))` ascends the bound with it.
 
-Outputs carry no grad; non-GPU and non-fp32 inputs are refused like everywhere else in the package.
+Deep-kernel learning.  k(x, x) = s is constant, so the bound depends on the embeddings only through k_nm, and
+the r of the second pass gives its derivative in them as well (same envelope argument):
+
+    dF/dx_n = (sum_m r_nm (z_m - centroid) - rho_n (x_n - centroid)) / l^2,    rho_n = sum_m r_nm
+
+one more product per tile of 32 rows in that pass (`cgat_gp_fit_grad_inputs`), [N, D] fp32 that stays on the device:
+`bound_and_gradient(..., wrt_embeddings=True)`.  `collapsed_bound` is the bound as a tensor that is differentiable in the
+embeddings, `deep_kernel_gradient` the exact full-batch gradient of -F / N in a network's parameters at the memory cost
+of one batch.
+
+Outputs carry no grad, with the one exception of `collapsed_bound`; non-GPU and non-fp32 inputs are refused like
+everywhere else in the package.
 """
 import math
 
@@ -108,6 +119,16 @@ def _tile_operands(cen, Zc, zn, dev):
     znp = torch.zeros(Mp, dtype=torch.float32)
     znp[:M] = zn
     return dict(zimg=_pack_image(Zp).to(dev), centroid=cen.to(torch.float32).to(dev), znorm=znp.to(dev))
+
+
+def _transposed_image(Zc, dev):
+    """The fp32 factor of gp_input_rows on `dev`: the packed image of Zc^T [Dq, Mp], Dq = D rounded up to 32; padding is
+    zero."""
+    M, D = Zc.shape
+    Mp, Dq = (M + 31) // 32 * 32, (D + 31) // 32 * 32
+    Zt = torch.zeros(Dq, Mp, dtype=torch.float32)
+    Zt[:D, :M] = Zc.T
+    return _pack_image(Zt).to(dev)
 
 
 def _check_embeddings(what, embeddings, D):
@@ -163,6 +184,7 @@ class _StatisticsPass:
         self.Z = Z
         cen, self.Zc, self.zn = _centred64(Z)
         self.ops = _tile_operands(cen, self.Zc, self.zn, self.x.device)
+        self.ops["ztimg"] = _transposed_image(self.Zc, self.x.device)
         self.W1 = self.w1img = None                         # of the Z before; factor() sets them
 
     def image(self, P):
@@ -332,9 +354,10 @@ class _GradientPass:
     def set_inducing_points(self, Z):
         self.stats.set_inducing_points(Z)
 
-    def sums(self, outputscale, lengthscale, two_G_hat, g, constant):
+    def sums(self, outputscale, lengthscale, two_G_hat, g, constant, input_grad=False):
         """Enqueues cgat_gp_fit_grad with the W1 of the last stats.factor() (a statistics pass makes one); (colsum, d2sum,
-        P)."""
+        P).  `input_grad`: cgat_gp_fit_grad_inputs in its place; (colsum, d2sum, P, dX), dX = dF/dX a new contiguous
+        [N, D] fp32 tensor on the device."""
         st = self.stats
         if st.W1 is None:
             raise RuntimeError(f"{st.what}: no factorisation of K_zz yet; call stats.factor(outputscale, lengthscale, "
@@ -344,27 +367,36 @@ class _GradientPass:
         w1timg = st.image(st.W1.T)
         g2img = st.image(torch.as_tensor(two_G_hat).to("cpu", torch.float64))
         g32 = torch.as_tensor(g).to("cpu", torch.float64).to(torch.float32).to(dev)
+        common = (_ptr(x), x.stride(0), _ptr(st.y32), st.N, st.D, _ptr(ops["zimg"]), st.M, _ptr(ops["centroid"]),
+                  _ptr(ops["znorm"]), _ptr(st.w1img), _ptr(w1timg), _ptr(g2img), _ptr(g32), float(constant), s,
+                  0.5 / (ell * ell), st.chunk, _ptr(self.colsum), _ptr(self.d2sum), _ptr(self.P))
+        if not input_grad:
+            with torch.cuda.device(dev):
+                rc = _lib.lib.cgat_gp_fit_grad(*common, _ptr(st.ws), self.ws_bytes, _stream())
+            _lib.check(rc, "cgat_gp_fit_grad")
+            return self.colsum, self.d2sum, self.P
+        dX = torch.empty(st.N, st.D, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.lib.cgat_gp_fit_grad(_ptr(x), x.stride(0), _ptr(st.y32), st.N, st.D, _ptr(ops["zimg"]), st.M,
-                                           _ptr(ops["centroid"]), _ptr(ops["znorm"]), _ptr(st.w1img), _ptr(w1timg),
-                                           _ptr(g2img), _ptr(g32), float(constant), s, 0.5 / (ell * ell), st.chunk,
-                                           _ptr(self.colsum), _ptr(self.d2sum), _ptr(self.P), _ptr(st.ws), self.ws_bytes,
-                                           _stream())
-        _lib.check(rc, "cgat_gp_fit_grad")
-        return self.colsum, self.d2sum, self.P
+            rc = _lib.lib.cgat_gp_fit_grad_inputs(*common, _ptr(ops["ztimg"]), _ptr(dX), dX.stride(0), _ptr(st.ws),
+                                                  self.ws_bytes, _stream())
+        _lib.check(rc, "cgat_gp_fit_grad_inputs")
+        return self.colsum, self.d2sum, self.P, dX
 
-    def __call__(self, outputscale, lengthscale, jitter, noise=None, zero_mean=False):
+    def __call__(self, outputscale, lengthscale, jitter, noise=None, zero_mean=False, wrt_embeddings=False):
         st = self.stats
         s, ell = float(outputscale), float(lengthscale)
         gram = st(s, ell, jitter)
         sol = solve_collapsed(gram, st.N, s, noise=noise, zero_mean=zero_mean)
         adj = collapsed_adjoints(gram, st.N, s, sol)
-        colsum, d2sum, P = (t.cpu() for t in self.sums(s, ell, 2.0 * adj["G_hat"], adj["g"], sol["constant"]))
+        out = self.sums(s, ell, 2.0 * adj["G_hat"], adj["g"], sol["constant"], input_grad=wrt_embeddings)
+        colsum, d2sum, P = (t.cpu() for t in out[:3])
         host = whitening_pullback(st.Z, ell, s, jitter, adj["dF_dW1"])
         l2 = ell * ell
         grads = dict(log_lengthscale=float(d2sum.sum()) / l2 + host["log_lengthscale"],
                      log_outputscale=adj["log_outputscale"] + host["log_outputscale"],
                      inducing_points=(P - colsum[:, None] * st.Zc) / l2 + host["inducing_points"])
+        if wrt_embeddings:
+            grads["embeddings"] = out[3]
         return sol, grads
 
 
@@ -379,13 +411,73 @@ def fit_gradient_sums(embeddings, y_norm, inducing_points, outputscale, lengthsc
 
 
 def bound_and_gradient(embeddings, y_norm, inducing_points, outputscale, lengthscale, jitter=1e-4, noise=None,
-                       zero_mean=False, chunk_rows=None):
+                       zero_mean=False, chunk_rows=None, wrt_embeddings=False):
     """The collapsed bound at its maximiser in (m, L_S, c, sigma^2) and its exact full-batch gradient in the kernel's
     parameters: one statistics pass, one solve, one gradient pass.  Returns (solution, grads): `solution` as
     solve_collapsed returns it, `grads` a dict of fp64 host values: log_lengthscale, log_outputscale (floats) and
-    inducing_points [M, D], the derivatives of solution["elbo"] (c and sigma^2 re-solved, or `noise` held)."""
+    inducing_points [M, D], the derivatives of solution["elbo"] (c and sigma^2 re-solved, or `noise` held).  With
+    `wrt_embeddings` it also holds "embeddings": the derivative in the embeddings (Z an independent operand) as a
+    contiguous [N, D] fp32 tensor on their device."""
     return _GradientPass("bound_and_gradient", embeddings, y_norm, inducing_points, chunk_rows)(
-        outputscale, lengthscale, jitter, noise=noise, zero_mean=zero_mean)
+        outputscale, lengthscale, jitter, noise=noise, zero_mean=zero_mean, wrt_embeddings=wrt_embeddings)
+
+
+class _BoundOfEmbeddings(torch.autograd.Function):
+    """The bound as a function of the embeddings alone: the value and dF/dX of one bound_and_gradient call."""
+
+    @staticmethod
+    def forward(ctx, embeddings, elbo, dX):
+        ctx.save_for_backward(dX)
+        return torch.tensor(elbo, dtype=torch.float64, device=embeddings.device)
+
+    @staticmethod
+    def backward(ctx, grad_bound):
+        dX, = ctx.saved_tensors
+        return dX * grad_bound.to(torch.float32), None, None
+
+
+def collapsed_bound(embeddings, y_norm, inducing_points, outputscale, lengthscale, jitter=1e-4, noise=None,
+                    zero_mean=False, chunk_rows=None):
+    """(bound, solution): the collapsed bound of bound_and_gradient as a 0-dim fp64 tensor on the device of `embeddings`,
+    equal to solution["elbo"] and differentiable in `embeddings` (its backward is dF/dX of the same evaluation times the
+    incoming scalar, in fp32).  The inducing points, the lengthscale and the outputscale are plain values here: their
+    gradients are bound_and_gradient's."""
+    sol, grads = _GradientPass("collapsed_bound", embeddings, y_norm, inducing_points, chunk_rows)(
+        outputscale, lengthscale, jitter, noise=noise, zero_mean=zero_mean, wrt_embeddings=True)
+    return _BoundOfEmbeddings.apply(embeddings, float(sol["elbo"]), grads["embeddings"]), sol
+
+
+def deep_kernel_gradient(model, batches, y_norm, inducing_points, outputscale, lengthscale, jitter=1e-4, noise=None,
+                         zero_mean=False, chunk_rows=None):
+    """The exact full-batch gradient of the loss -F / N in the parameters of `model` (a CGAtNet), F the collapsed bound
+    of the graph embeddings of all `batches`, at the memory cost of one batch.  `batches`: a sequence of
+    (batch, b_comp) pairs as the model takes them; `y_norm` [N] the normalised targets in the graphs' order across the
+    batches.  Three steps: the embeddings E [N, D] of every batch under eval() and no_grad; one bound_and_gradient(E, ...,
+    wrt_embeddings=True); every batch forward again with grad (still eval()) and emb.backward(-dX[rows] / N), which
+    accumulates into the parameters' .grad: the caller zeroes them and steps its optimiser.  The training flag is restored.
+    Returns a dict: loss (= -elbo / N, a float), solution, grads (of F in Z, log l, log s, from the same evaluation, so
+    the head's parameters can move too) and embeddings (E)."""
+    # both sweeps read b_comp: a generator is materialised once
+    batches = [(b, c if isinstance(c, (tuple, list, torch.Tensor)) else tuple(c)) for b, c in batches]
+    if not batches:
+        raise ValueError("deep_kernel_gradient: no batches")
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            E = torch.cat([model(b, c, return_graph_embedding=True) for b, c in batches])
+        N = E.shape[0]
+        sol, grads = bound_and_gradient(E, y_norm, inducing_points, outputscale, lengthscale, jitter=jitter, noise=noise,
+                                        zero_mean=zero_mean, chunk_rows=chunk_rows, wrt_embeddings=True)
+        seed = grads.pop("embeddings") * (-1.0 / N)
+        row = 0
+        for b, c in batches:
+            emb = model(b, c, return_graph_embedding=True)
+            emb.backward(seed[row:row + emb.shape[0]])
+            row += emb.shape[0]
+    finally:
+        model.train(was_training)
+    return dict(loss=-sol["elbo"] / N, solution=sol, grads=grads, embeddings=E)
 
 
 LEARNABLE = ("lengthscale", "outputscale", "inducing_points")

@@ -930,6 +930,24 @@ int cgat_gp_fit_grad(const float* X, int64_t ldx, const float* y_norm, int32_t N
                      const float* G2img, const float* g, float c, float s, float inv_two_l2, int32_t chunk_rows,
                      double* colsum, double* d2sum, double* P, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same pass with the gradient of the bound in the embeddings (deep-kernel learning) ---------------
+ * The reference fits its GP (CGAT/gaussian_process.py:45-66, bound at :233) on the embeddings of a frozen network; to train
+ * the network under that bound one needs dF/dX.  The RBF kernel's k(x, x) = s is constant, so the bound depends on X only
+ * through k_nm, and with r of cgat_gp_fit_grad and rho_n = sum_m r_nm (at fixed (m, L_S, c, sigma^2): the envelope theorem)
+ *   dX[n][d] = (sum_m r_nm (Z - centroid)[m][d] - rho_n (x_n[d] - centroid[d])) 2 inv_two_l2 = dF/dx_n[d]
+ * one more product per tile of 32 rows on the f32-input matrix cores, from the r the pass leaves in its chunk buffer, with
+ * rho added over m in a fixed order.  Everything else is cgat_gp_fit_grad: both entries run one implementation, colsum,
+ * d2sum and P are bit-equal between them, and cgat_gp_fit_grad_workspace_bytes serves both (dX is written directly).
+ * Ztimg: the packed image of (Z - centroid)^T as [Dq, Mp], Dq = D rounded up to 32, zero padded, 16-byte aligned.
+ * dX [N, D] fp32, rows lddx >= D apart; columns at or past D of a row and rows at or past N are never written; 16-byte
+ * stores are used where dX and lddx allow them.  A null Ztimg or dX, lddx < D or a misaligned Ztimg return 1 (argument)
+ * before any launch.  No atomics: bitwise deterministic, and a row's dX does not depend on chunk_rows. */
+int cgat_gp_fit_grad_inputs(const float* X, int64_t ldx, const float* y_norm, int32_t N, int32_t D, const float* Zimg,
+                            int32_t M, const float* centroid, const float* znorm, const float* W1img, const float* W1timg,
+                            const float* G2img, const float* g, float c, float s, float inv_two_l2, int32_t chunk_rows,
+                            double* colsum, double* d2sum, double* P, const float* Ztimg, float* dX, int64_t lddx,
+                            void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
