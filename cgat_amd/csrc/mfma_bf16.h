@@ -235,4 +235,10 @@ __device__ __forceinline__ void glds_b32(const void* sbase, unsigned voff, unsig
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
 }
+// global address = a full per-lane pointer (lanes may point into different allocations); LDS address = lds_addr + 4 * lane
+__device__ __forceinline__ void glds_b32_ptr(const void* vaddr, unsigned lds_addr) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(vaddr), "s"(lds_addr) : "memory");
+}
 

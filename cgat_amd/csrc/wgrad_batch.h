@@ -8,6 +8,9 @@ struct WgradBatchDesc {
   float* slab;           // [layer][split][NA][128][128] partial sums (splits > 1)
   long sT, sR;           // per-layer strides: floats of pT / qT (qF); uint4 of Rq (f16x3) or bytes of the r stream (f16x3c)
   int n_layers, splits, npairs, NA, rows_pad, rows_per_split;
+  const float* p[WGB_MAX];   // f16x3c: the row-major first operands themselves (the kernel fetches its p columns from them)
+  long ldp;
+  int rows;
 };
 struct WgradPrepDesc {
   const float* p[WGB_MAX];

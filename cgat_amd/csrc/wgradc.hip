@@ -19,7 +19,9 @@
 //    matrix time).
 //  * r arrives by LDS-DMA as a prepared stream of 50 KB per chunk (fp16 planes in B-fragment order + 6-bit images),
 //    three ring slots; q is read by each wave directly in fragment order (qF: 8 coalesced 1-KB loads per chunk);
-//    p as two 64-float rows per chunk through the ring slot.
+//    p as two 64-float columns per chunk through the ring slot, fetched by dword LDS-DMA from the row-major tensor
+//    itself (lane = row; the pair's two columns are neighbours, and the 64-byte sectors the 64 units of a layer share
+//    are L2 hits); the product's power-of-two scale and the sign of the 512-row group ride on qF.
 //  * ONE workgroup barrier per iteration publishes the next slot and retires the oldest.
 #include "kernels.h"
 #include "mfma_bf16.h"
@@ -34,8 +36,8 @@ typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
 #define WGC_PL_B 32768                      // fp16 planes of a chunk: [k-step 4][plane h,l][column block 4][lane 64][16 B]
 #define WGC_IM_B 18432                      // 6-bit images: [image l6,h6,t6][column block 4][lane 64 x 16 B | lane 64 x 8 B]
 #define WGC_RS_B (WGC_PL_B + WGC_IM_B)      // the r stream of a chunk: 50 pieces of 1 KB
-#define WGC_P_B 2048                        // the two staged p rows, one 1-KB LDS-DMA piece each (256 B used)
-#define WGC_SLOT_B (WGC_P_B + WGC_RS_B)     // ring slot: [p rows][r stream]
+#define WGC_P_B 2048                        // the two staged p columns, 256 B (one dword LDS-DMA piece) at the head of 1 KB each
+#define WGC_SLOT_B (WGC_P_B + WGC_RS_B)     // ring slot: [p columns][r stream]
 #define WGC_SLOTS 3
 #define WGC_NDMA0 7                         // LDS-DMA pieces per chunk a grp-0 wave issues (of 13 per wb; grp 1: the rest)
 #ifndef WGC_PRIO
@@ -45,73 +47,65 @@ typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
 // ------------------------------- operand preparation -------------------------------
 // (the maxima: absmax_rows_batch_launch, bilwgrad.hip)
 
-// One 64-row chunk of one operand of one layer per workgroup (256 threads; blockIdx.z = operand):
-//  pT [128][rows_pad]      = (p * 2^k * sign(n))^T: 2^k from max|p| max|q| (the products must fit fp16), sign(n) = -1 in the
-//                            odd 512-row groups of n's row split (the kernel's partial sums alternate in sign)
-//  qF [chunk][wb 4][j 8][lane 64][4]  = q in the order a lane of wave wb consumes it: value i = 4 j + e of lane (r, hi)
-//                            is q[n0 + 16 (i >> 3) + 8 hi + (i & 7)][32 wb + r]
+// One 64-row chunk of one operand of one layer per workgroup (256 threads; blockIdx.z = 0: q, 1: r):
+//  qF [chunk][wb 4][j 8][lane 64][4]  = q * 2^k * sign(n) in the order a lane of wave wb consumes it: value i = 4 j + e of
+//                            lane (r, hi) is q[n0 + 16 (i >> 3) + 8 hi + (i & 7)][32 wb + r].  2^k from max|p| max|q| (the
+//                            products must fit fp16), sign(n) = -1 in the odd 512-row groups of n's row split (the kernel's
+//                            partial sums alternate in sign).  Both are exact multipliers of the product p q, and the
+//                            kernel takes p as it stands in memory, so they ride on the q factor.
 //  Rs [chunk][50 KB]       = fp16 planes of 2^k' r in B-fragment order + the three 6-bit images (same value order)
-// Rows beyond `rows` and columns of p beyond NA are zero.
-__global__ __launch_bounds__(256) void wgc_prep_kernel(WgradPrepDesc d, int l0, long ldp, long ldq, long ldr, int rows,
-                                                       int NA, int rows_pad, int rows_per_split,
-                                                       float* __restrict__ pT, float* __restrict__ qF,
+// Rows beyond `rows` are zero.
+// Every thread reads its values straight from the row-major tensor, 32 independent dword loads issued before the first
+// use: a wave instruction covers the two 128-byte row segments of its two row halves (hi = 0, 1), and every segment of
+// the chunk is read by exactly one instruction.  No tile in LDS and no barrier.
+__global__ __launch_bounds__(256) void wgc_prep_kernel(WgradPrepDesc d, int l0, long ldq, long ldr, int rows,
+                                                       int rows_per_split, float* __restrict__ qF,
                                                        unsigned char* __restrict__ Rs, long sT, long sR_bytes,
                                                        const float* __restrict__ mx) {
-  __shared__ float tile[64][129];
   const int layer = blockIdx.y, chunk = blockIdx.x, n0 = chunk * WGC_ROWS, tid = threadIdx.x;
-  const int which = blockIdx.z;      // 0 p, 1 q, 2 r: one operand per workgroup (three independent streams in flight per chunk)
+  const int which = blockIdx.z;      // 0 q, 1 r: one operand per workgroup (two independent streams in flight per chunk)
   const float* mxl = mx + 4 * (l0 + layer);
-  // ---- p: transpose, scale, sign ----
+  const int lane = tid & 63, w = tid >> 6, col = lane & 31, hi = lane >> 5, c = 32 * w + col;
+  const int last = rows - 1 - n0;    // chunk rows past it: the load is clamped to it and the value replaced by zero
+  // value i of the thread = row 16 (i >> 3) + 8 hi + (i & 7) of the chunk, column c: the same 32 values in both jobs
+  float v[32];
+  {
+    const float* t = which == 0 ? d.q[layer] : d.r[layer];
+    const long ld = which == 0 ? ldq : ldr;
+    const float* tc = t + (long)n0 * ld + c;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const int n = 16 * (i >> 3) + 8 * hi + (i & 7);
+      v[i] = tc[(long)(n < last ? n : last) * ld];
+    }
+  }
+  // ---- q: fragment order, scale, sign ----
   if (which == 0) {
     float spq, ipq;
     pow2_scale(mxl[0] * mxl[1], spq, ipq);
     if ((((n0 % rows_per_split) >> 6) >> 3) & 1) spq = -spq;       // a 64-row chunk never straddles a 512-row group
-    const float* p = d.p[layer];
-    for (int i = tid; i < 64 * 128; i += 256) {
-      const int n = i >> 7, c = i & 127;
-      tile[n][c] = (n0 + n < rows && c < NA) ? p[(long)(n0 + n) * ldp + c] * spq : 0.f;
+    float4* o = reinterpret_cast<float4*>(qF + (long)(l0 + layer) * sT + (long)chunk * (64 * 128)) + (w * 8) * 64 + lane;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float x[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int i = 4 * j + e, n = 16 * (i >> 3) + 8 * hi + (i & 7);
+        x[e] = n <= last ? v[i] * spq : 0.f;
+      }
+      o[j * 64] = make_float4(x[0], x[1], x[2], x[3]);
     }
-    __syncthreads();
-    float* o = pT + (long)(l0 + layer) * sT;
-    for (int i = tid; i < 128 * 64; i += 256) {
-      const int c = i >> 6, n = i & 63;
-      o[(long)c * rows_pad + n0 + n] = tile[n][c];
-    }
-    __syncthreads();
-  }
-  // ---- q: fragment order ----
-  if (which == 1) {
-    const float* q = d.q[layer];
-    for (int i = tid; i < 64 * 128; i += 256) {
-      const int n = i >> 7, c = i & 127;
-      tile[n][c] = (n0 + n < rows) ? q[(long)(n0 + n) * ldq + c] : 0.f;
-    }
-    __syncthreads();
-    float4* o = reinterpret_cast<float4*>(qF + (long)(l0 + layer) * sT + (long)chunk * (64 * 128));
-    for (int i = tid; i < 4 * 8 * 64; i += 256) {
-      const int lane = i & 63, j = (i >> 6) & 7, wb = i >> 9;
-      const int r = lane & 31, hi = lane >> 5, b = 32 * wb + r;
-      const int nb = 16 * (j >> 1) + 8 * hi + 4 * (j & 1);
-      o[i] = make_float4(tile[nb][b], tile[nb + 1][b], tile[nb + 2][b], tile[nb + 3][b]);
-    }
-    __syncthreads();
   }
   // ---- r: fp16 planes + 6-bit images; thread = (column block, lane) ----
-  if (which == 2) {
-    const float* rr = d.r[layer];
+  if (which == 1) {
+    const int cb = w;
     float sr, ir;
     pow2_scale(mxl[2], sr, ir);
-    for (int i = tid; i < 64 * 128; i += 256) {
-      const int n = i >> 7, c = i & 127;
-      tile[n][c] = (n0 + n < rows) ? rr[(long)(n0 + n) * ldr + c] * sr : 0.f;
-    }
-    __syncthreads();
-    const int lane = tid & 63, cb = tid >> 6, col = lane & 31, hi = lane >> 5, c = 32 * cb + col;
     unsigned H[16], L[16], T[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) {                      // value pair (2k, 2k+1): k-step k >> 2, element 2 (k & 3)
       const int n = 16 * (k >> 2) + 8 * hi + 2 * (k & 3);
-      const float a = tile[n][c], b = tile[n + 1][c];
+      const float a = n <= last ? v[2 * k] * sr : 0.f, b = n + 1 <= last ? v[2 * k + 1] * sr : 0.f;
       const f16x2 h = __builtin_convertvector((f32x2){a, b}, f16x2);
       const float ra = a - (float)h[0], rb = b - (float)h[1];
       const f16x2 l = __builtin_convertvector((f32x2){ra, rb}, f16x2);
@@ -157,8 +151,7 @@ __device__ __forceinline__ f32x16 wgc_mma16(uint4 a, uint4 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-__global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const float* __restrict__ pT_,
-                                                                        const float* __restrict__ qF_,
+__global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const float* __restrict__ qF_,
                                                                         const unsigned char* __restrict__ Rs_,
                                                                         const float* __restrict__ mx_,
                                                                         WgradBatchDesc u) {
@@ -192,7 +185,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
     const int nend = min(rows_pad, nbeg + u.rows_per_split);
     const int nchunks = (nend - nbeg) / WGC_ROWS;   // rows_per_split and rows_pad are multiples of 64
     const int cg0 = nbeg / WGC_ROWS;
-    const char* pT = reinterpret_cast<const char*>(pT_ + (long)layer * u.sT + (long)a0 * rows_pad);
+    const float* pl = u.p[layer];
     const char* qF = reinterpret_cast<const char*>(qF_ + (long)layer * u.sT) + ((long)cg0 * 4 + wb) * 8192;   // uniform
     const unsigned char* Rs = Rs_ + (long)layer * u.sR + (long)cg0 * WGC_RS_B;
     const float* mx = mx_ + 4 * layer;
@@ -210,14 +203,14 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
       inv_all = ipq * ir;
     }
     if (nchunks > 0) {
-      // chunk ci -> ring slot ci % 3, 52 pieces: 0..49 the r stream, 50 / 51 the p rows of a0 / a0 + 1; wave wb of the
+      // chunk ci -> ring slot ci % 3, 52 pieces: 0..49 the r stream, 50 / 51 columns a0 / a0 + 1 of p; wave wb of the
       // issuing group takes the 13 pieces k = wb + 4 m.  In the loop the grp-1 waves issue them ONE PER TWO GROUPS inside
       // their matrix phase (WGC_STEP): issued as a burst by the grp-0 waves before their split, the 13 pieces cost those
       // waves ~800 cycles of their critical path, and the burst of 52 KB landing in LDS beside the fragment reads of the
       // partner's matrix phase and the p reads of the split stretched BOTH (any two of the three cost nothing, all three
       // +0.45 ms per launch, round 5: the ablation build is in the history at 43b4fa4).  The chunk index is clamped: the last iterations re-load
       // the last chunk into a slot nobody reads.
-#define WGC_DMA_PIECE(m_, sl_, rb_, cc_, vo16_, vo4_)   /* branch-free: every piece is one 1-KB global_load_lds_dwordx4 */ \
+#define WGC_DMA_PIECE(m_, sl_, rb_, cc_, vo16_, vo4_)   /* every piece is ONE LDS-DMA instruction of its wave: 1 KB of the r stream, or 256 B of p */ \
   {                                                                                          \
     /* the bases are laundered so that each piece's address arithmetic happens HERE: hoisted to the top of the phase   \
        (13 pieces x 64-bit source + LDS address) it spilled 38 SGPRs into vector registers and 159 of those to scratch */ \
@@ -227,12 +220,16 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
     const int k_ = wb + 4 * (m_);                                                            \
     if ((m_) < 12) {                                                                         \
       glds_b128(rbl_ + k_ * 1024, vo16_, (unsigned)__builtin_amdgcn_readfirstlane((int)(sll_ + WGC_P_B + k_ * 1024))); \
-    } else {   /* k_ = 48, 49: r stream; 50, 51: the p row of a0 + k_ - 50 (256 B, fetched four times over) */     \
-      const bool isr_ = wb < 2;                                                              \
-      const unsigned char* src_ = isr_ ? rbl_ + k_ * 1024                                    \
-                                       : reinterpret_cast<const unsigned char*>(pT) + ((long)(wb - 2) * rows_pad + nbeg + (long)(cc_) * WGC_ROWS) * 4; \
-      const unsigned dst_ = isr_ ? sll_ + WGC_P_B + k_ * 1024 : sll_ + (wb - 2) * 1024;      \
-      glds_b128(src_, isr_ ? (vo16_) : ((vo16_) & 255u), (unsigned)__builtin_amdgcn_readfirstlane((int)dst_)); \
+    } else if (wb < 2) {   /* k_ = 48, 49: r stream */                                       \
+      glds_b128(rbl_ + k_ * 1024, vo16_, (unsigned)__builtin_amdgcn_readfirstlane((int)(sll_ + WGC_P_B + k_ * 1024))); \
+    } else {   /* k_ = 50, 51: column a0 + k_ - 50 of the chunk's 64 rows of p, straight from the row-major tensor:   \
+                  lane = row, one dword each (256 B).  A row past the tensor's end or a column past NA reads the      \
+                  layer's spare maxima slot instead, which the preparation zeroed: an exact +0 and no read out of     \
+                  bounds.  One vector-memory instruction per wave like every other piece, so the counted waits hold */ \
+      const int row0_ = nbeg + (cc_) * WGC_ROWS, ln4_ = (int)((vo4_) >> 2);                  \
+      const float* col_ = pl + ((long)row0_ * u.ldp + a0 + (wb - 2));   /* uniform; 63 ldp fits 32 bits (wgradc_launch) */ \
+      const float* src_ = (ln4_ < u.rows - row0_ && a0 + (wb - 2) < u.NA) ? col_ + (unsigned)ln4_ * (unsigned)u.ldp : mx + 3; \
+      glds_b32_ptr(src_, (unsigned)__builtin_amdgcn_readfirstlane((int)(sll_ + (wb - 2) * 1024))); \
     }                                                                                        \
   }
 #define WGC_DMA(ci_, M0_, M1_)   /* pieces m in [M0_, M1_) of this wave */                   \
@@ -310,7 +307,7 @@ __global__ __launch_bounds__(512, 2) void bilinear_wgrad128_f16c_kernel(const fl
       // each operand right before its use and the wave sits out the LDS latency 20 times per chunk, and with two groups
       // of lead a matrix phase still took 2700 cycles for 1920 of matrix work (s_memtime stamps: a diagnostic build in the
       // history at 43b4fa4).  512-row partial
-      // sums (8 chunks) go to `tot` with alternating sign (the sign is in the staged p: cancels the matrix instruction's
+      // sums (8 chunks) go to `tot` with alternating sign (the sign is in qF: cancels the matrix instruction's
       // accumulator rounding bias, see bilinear_rows128_ring16_kernel).
 #define WGC_LOADG(g_, X_, Y_)                                                                                     \
   {                                                                                                               \
@@ -477,30 +474,35 @@ int wgradc_pick(int n_layers, int nrows, int NA, int* rps_out) {
   if (rps_out) *rps_out = rps;
   return cdiv(np, rps);
 }
-size_t wgradc_ws(int n_layers, int nrows, int NA, int splits, size_t* o_pT, size_t* o_qF, size_t* o_Rs, size_t* o_slab,
-                 size_t* o_mx) {
+size_t wgradc_ws(int n_layers, int nrows, int NA, int splits, size_t* o_qF, size_t* o_Rs, size_t* o_slab, size_t* o_mx) {
   const size_t np = (size_t)cdiv(nrows, WGC_ROWS) * WGC_ROWS;
   size_t off = 0;
-  *o_pT = off; off += ws_round((size_t)n_layers * np * 128, 4);
   *o_qF = off; off += ws_round((size_t)n_layers * np * 128, 4);
   *o_Rs = off; off += ws_round((size_t)n_layers * (np / WGC_ROWS) * WGC_RS_B, 1);
   *o_slab = off; if (splits > 1) off += ws_round((size_t)n_layers * splits * NA * 128 * 128, 4);
   *o_mx = off; off += 256;
   return off;
 }
+// What the size queries report.  The layout above no longer holds the transposed fp32 copy of p ([128][rows_pad] floats
+// per layer) that the kernel used to read, and a launch accepts a workspace of the layout's size; the queries still
+// count that region, because the sizes they return are recorded values that callers and the size tests hold the
+// library to (tests/golden/bilinear_workspace_bytes.json, hnet_workspace_bytes.json).  The region is not touched.
 size_t wgradc_ws_bytes(int n_layers, int nrows, int NA) {
-  size_t a, b, c, d, e;
-  return wgradc_ws(n_layers, nrows, NA, wgradc_pick(n_layers, nrows, NA, nullptr), &a, &b, &c, &d, &e);
+  size_t a, b, c, d;
+  const size_t np = (size_t)cdiv(nrows, WGC_ROWS) * WGC_ROWS;
+  return wgradc_ws(n_layers, nrows, NA, wgradc_pick(n_layers, nrows, NA, nullptr), &a, &b, &c, &d) +
+         ws_round((size_t)n_layers * np * 128, 4);
 }
 
-// operands of layers [l0, l0 + n) of an n_layers batch (their maxima, scaled transposes, fragment orders, planes, images)
+// operands of layers [l0, l0 + n) of an n_layers batch: their maxima, q in fragment order (scaled, signed), the r stream.
+// p is only measured here: the kernel reads it where it lies, so it must still hold its values when the kernel runs.
 int wgradc_prep(int l0, int n, int n_layers, const float* const* p, long ldp, const float* const* q, long ldq,
                 const float* const* r, long ldr, int nrows, int NA, void* ws, size_t ws_bytes, hipStream_t stream) {
   const int np = cdiv(nrows, WGC_ROWS) * WGC_ROWS;
   int rps = 0;
   const int splits = wgradc_pick(n_layers, nrows, NA, &rps);
-  size_t o_pT, o_qF, o_Rs, o_slab, o_mx;
-  const size_t need = wgradc_ws(n_layers, nrows, NA, splits, &o_pT, &o_qF, &o_Rs, &o_slab, &o_mx);
+  size_t o_qF, o_Rs, o_slab, o_mx;
+  const size_t need = wgradc_ws(n_layers, nrows, NA, splits, &o_qF, &o_Rs, &o_slab, &o_mx);
   if (!ws || ws_bytes < need) {
     cgat_set_error("bilinear_wgrad (f16x3c): workspace too small (%zu < %zu)", ws_bytes, need);
     return CGAT_ERR_WORKSPACE;
@@ -511,8 +513,8 @@ int wgradc_prep(int l0, int n, int n_layers, const float* const* p, long ldp, co
   float* mx = (float*)((char*)ws + o_mx);
   CGAT_TRY(fill_launch(mx + 4 * l0, 0.f, 4 * n, stream));
   CGAT_TRY(absmax_rows_batch_launch(pd, l0, n, ldp, ldq, ldr, nrows, NA, mx, nrows < 2048 ? cdiv(nrows, 8) : 256, stream));
-  hipLaunchKernelGGL(wgc_prep_kernel, dim3(np / WGC_ROWS, n, 3), dim3(256), 0, stream, pd, l0, ldp, ldq, ldr, nrows, NA, np, rps,
-                     (float*)((char*)ws + o_pT), (float*)((char*)ws + o_qF), (unsigned char*)ws + o_Rs, (long)np * 128,
+  hipLaunchKernelGGL(wgc_prep_kernel, dim3(np / WGC_ROWS, n, 2), dim3(256), 0, stream, pd, l0, ldq, ldr, nrows, rps,
+                     (float*)((char*)ws + o_qF), (unsigned char*)ws + o_Rs, (long)np * 128,
                      (long)(np / WGC_ROWS) * WGC_RS_B, (const float*)mx);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
@@ -526,16 +528,18 @@ int wgradc_launch(int n_layers, const float* const* p, long ldp, const float* co
   const int np = cdiv(nrows, WGC_ROWS) * WGC_ROWS;
   int rps = 0;
   const int splits = wgradc_pick(n_layers, nrows, NA, &rps);
-  size_t o_pT, o_qF, o_Rs, o_slab, o_mx;
-  const size_t need = wgradc_ws(n_layers, nrows, NA, splits, &o_pT, &o_qF, &o_Rs, &o_slab, &o_mx);
+  size_t o_qF, o_Rs, o_slab, o_mx;
+  const size_t need = wgradc_ws(n_layers, nrows, NA, splits, &o_qF, &o_Rs, &o_slab, &o_mx);
   if (!ws || ws_bytes < need) {
     cgat_set_error("bilinear_wgrad (f16x3c): workspace too small (%zu < %zu)", ws_bytes, need);
     return CGAT_ERR_WORKSPACE;
   }
+  CGAT_CHECK_ARG(ldp >= 0 && ldp < (1L << 25), "bilinear_wgrad (f16x3c): leading dimension of p out of range");
   if (!prepared) CGAT_TRY(wgradc_prep(0, n_layers, n_layers, p, ldp, q, ldq, r, ldr, nrows, NA, ws, ws_bytes, stream));
   WgradBatchDesc u;
   memset(&u, 0, sizeof(u));
-  for (int l = 0; l < n_layers; ++l) u.out[l] = out[l];
+  for (int l = 0; l < n_layers; ++l) { u.out[l] = out[l]; u.p[l] = p[l]; }
+  u.ldp = ldp; u.rows = nrows;
   u.slab = (float*)((char*)ws + o_slab);
   u.sT = (long)np * 128;
   u.sR = (long)(np / WGC_ROWS) * WGC_RS_B;
@@ -544,7 +548,7 @@ int wgradc_launch(int n_layers, const float* const* p, long ldp, const float* co
   const int grid = units < max_wgs ? units : max_wgs;
   {
     CGAT_PROF("bilinear_wgrad", stream);
-    hipLaunchKernelGGL(bilinear_wgrad128_f16c_kernel, dim3(grid), dim3(512), 0, stream, (const float*)((char*)ws + o_pT),
+    hipLaunchKernelGGL(bilinear_wgrad128_f16c_kernel, dim3(grid), dim3(512), 0, stream,
                        (const float*)((char*)ws + o_qF), (const unsigned char*)ws + o_Rs, (const float*)((char*)ws + o_mx), u);
   }
   CGAT_LAUNCH_CHECK();
