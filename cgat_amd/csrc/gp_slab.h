@@ -2,6 +2,8 @@
 //   gp_slab_product  one 128 x 128 tile of A B^T over one slab of 1024 rows, on the f32-input matrix cores
 //   gp_slab_reduce   one element of such a tile: its slabs added in slab order in fp64, stored or added to the result
 //   GpChunks         (host) the walk over the chunks of rows and what the workspace of a chunk holds
+//   GpRowSumsWorkspace, gp_launch_row_sums  (host) the workspace of a chunk of 10d and the launches that end it: R^T Xc and
+//                    the column sums, which csrc/gpkmeans.hip runs with a one-hot R
 // Both operands are inducing-major, [rows][pitch] with the chunk's rows along the pitch, as gp_whiten_rows stores A~^T.
 #pragma once
 #include "gp_tile.h"
@@ -146,6 +148,39 @@ struct GpChunks {
     t.G = rows;
   }
 };
+
+// The workspace of a chunk of the gradient pass, which the k-means step (csrc/gpkmeans.hip, 10f) lays out
+// the same way: the chunk buffer [Map][eff_chunk], Xc^T [D][eff_chunk], the per-tile partials pc, pd [eff_chunk / 32][Mp]
+// and the slab partials of R^T Xc [max_slabs][tiles of (M, D)][128][128].
+struct GpRowSumsWorkspace {
+  float *At, *Xt, *pc, *pd, *part;
+  static int tiles(int M, int D) { return cdiv(M, GS_TILE) * cdiv(D, GS_TILE); }
+  static size_t xt_elems(const GpChunks& c, int D) { return (size_t)D * c.eff_chunk; }
+  static size_t col_elems(const GpChunks& c) { return (size_t)(c.eff_chunk / GP_ROWS) * c.Mp; }
+  static size_t part_elems(const GpChunks& c, int M, int D) {
+    return (size_t)c.max_slabs * tiles(M, D) * GS_TILE * GS_TILE;
+  }
+  static size_t bytes(const GpChunks& c, int M, int D) {
+    return ws_round(c.at_elems(), sizeof(float)) + ws_round(xt_elems(c, D), sizeof(float)) +
+           2 * ws_round(col_elems(c), sizeof(float)) + ws_round(part_elems(c, M, D), sizeof(float));
+  }
+  GpRowSumsWorkspace(const GpChunks& c, int M, int D, void* ws, size_t ws_bytes) {
+    Workspace w(ws, ws_bytes);
+    At = w.take<float>(c.at_elems());
+    Xt = w.take<float>(xt_elems(c, D));
+    pc = w.take<float>(col_elems(c));
+    pd = w.take<float>(col_elems(c));
+    part = w.take<float>(part_elems(c, M, D));
+  }
+};
+
+// The sums over the rows of the current chunk `ch` that end a chunk of both passes (defined in csrc/gpgrad.hip), on
+// `stream`: with R^T = rows < M of w.At and the partials w.pc, w.pd [ch.row_tiles][Mp] the caller's kernels have written,
+//   gp_centre_rows, gp_pair_slabs, gp_grad_reduce_pairs   P [M][D] (+)= R^T (X - centroid) over the chunk's rows
+//   gp_grad_reduce_columns                                colsum, d2sum [M] (+)= the tiles of pc, pd added in tile order
+// fp64, stored by the first chunk and added to by the later ones.  `X`: the chunk's first row.  Returns a CGAT_* code.
+int gp_launch_row_sums(const GpRowSumsWorkspace& w, const GpChunks& ch, const float* X, long ldx, int M, int D,
+                       const float* centroid, double* colsum, double* d2sum, double* P, hipStream_t stream);
 
 static inline int gp_check_workspace(const char* name, const void* ws, size_t ws_bytes, size_t needed) {
   if (!ws || ws_bytes < needed) {

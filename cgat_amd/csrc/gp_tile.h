@@ -1,12 +1,13 @@
 // Device and host code shared by the sparse-GP entries: csrc/gphead.hip (prediction), csrc/gpfit.hip (the fit
-// statistics) and csrc/gpgrad.hip (the gradient of the bound).  All work on a tile of 32 rows of
-// X with one 512-thread workgroup (8 waves, two per SIMD):
+// statistics), csrc/gpgrad.hip (the gradient of the bound) and csrc/gpkmeans.hip (the k-means step
+// for the inducing points).  All work on a tile of 32 rows of X with one 512-thread workgroup (8 waves, two
+// per SIMD):
 //   GpTile              the operands of phase (a), filled by gp_tile_operands; the kernels that run it derive theirs from it
 //   gp_distance_tile    max(|x_row - z_m|^2, 0) of the tile, handed to a functor
 //   gp_kernel_tile      K^T[m][row] = s exp(-max(|x_row - z_m|^2, 0) inv_two_l2) of the tile, into LDS
 //   gp_factor_products  NB 32-row chunks of a packed factor image times that K^T tile, on the f32-input matrix cores
 //   gp_for_wave_pairs   the chunk pairs of a triangular factor that a wave owns
-//   gp_check_entry      (host) the argument checks the three C entries share
+//   gp_check_entry      (host) the argument checks the C entries share
 // and gp_launch_whiten_rows (host, defined in csrc/gpfit.hip) enqueues the whitening kernel of 10c for 10d.  The slab
 // products over a chunk of rows and the chunk walk of 10c and 10d are in gp_slab.h.
 //
@@ -46,7 +47,7 @@ static inline GpTile gp_tile_operands(const float* X, int64_t ldx, int G, int D,
   return GpTile{X, (long)ldx, G, D, M, gp_pad_m(M), gp_pad_d(D), (const float4*)Zimg, centroid, znorm, s, inv_two_l2};
 }
 
-// The checks the three entries share, in the order they report: the shape (`rows_name` = `rows` >= min_rows), the refusal
+// The checks the entries share, in the order they report: the shape (`rows_name` = `rows` >= min_rows), the refusal
 // of M > GP_MAX_M (`lds_clause`: who keeps the tile in LDS), chunk_rows where the entry has chunks (null otherwise), then,
 // unless the call is empty, the row stride, `operands` (every pointer the entry needs is there), `images` (the packed
 // images' addresses or-ed together) and the kernel's parameters.

@@ -298,18 +298,28 @@ __global__ __launch_bounds__(GQ_RC_COLS * GQ_RC_SEGS) void gp_grad_reduce_column
 }
 
 // ---- host ----
-static int gq_tiles(int M, int D) { return cdiv(M, GS_TILE) * cdiv(D, GS_TILE); }
-static size_t gq_xt_elems(const GpChunks& c, int D) { return (size_t)D * c.eff_chunk; }
-static size_t gq_col_elems(const GpChunks& c) { return (size_t)(c.eff_chunk / GP_ROWS) * c.Mp; }
-static size_t gq_part_elems(const GpChunks& c, int M, int D) {
-  return (size_t)c.max_slabs * gq_tiles(M, D) * GS_TILE * GS_TILE;
+int gp_launch_row_sums(const GpRowSumsWorkspace& w, const GpChunks& ch, const float* X, long ldx, int M, int D,
+                       const float* centroid, double* colsum, double* d2sum, double* P, hipStream_t st) {
+  const int n_tiles = GpRowSumsWorkspace::tiles(M, D), tiles_d = cdiv(D, GS_TILE);
+  const long pitch = ch.eff_chunk;
+  hipLaunchKernelGGL(gp_centre_rows, dim3(ch.row_tiles, cdiv(D, 32)), dim3(256), 0, st, X, ldx, ch.rows, D, centroid, w.Xt,
+                     pitch);
+  CGAT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gp_pair_slabs, dim3(n_tiles, ch.n_slabs), dim3(GS_THREADS), 0, st, w.At, w.Xt, pitch, M, D, ch.rows_p,
+                     w.part, tiles_d);
+  CGAT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gp_grad_reduce_pairs, dim3(n_tiles, GS_TILE * GS_TILE / 256), dim3(256), 0, st, w.part, tiles_d,
+                     ch.n_slabs, M, D, P, ch.first);
+  CGAT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gp_grad_reduce_columns, dim3(cdiv(M, GQ_RC_COLS)), dim3(GQ_RC_COLS * GQ_RC_SEGS), 0, st, w.pc, w.pd,
+                     ch.row_tiles, ch.Mp, M, colsum, d2sum, ch.first);
+  CGAT_LAUNCH_CHECK();
+  return CGAT_OK;
 }
 
 extern "C" size_t cgat_gp_fit_grad_workspace_bytes(int32_t N, int32_t M, int32_t D, int32_t chunk_rows) {
   if (!GpChunks::fits(N, M, D, chunk_rows)) return 0;
-  const GpChunks c(N, M, D, chunk_rows);
-  return ws_round(c.at_elems(), sizeof(float)) + ws_round(gq_xt_elems(c, D), sizeof(float)) +
-         2 * ws_round(gq_col_elems(c), sizeof(float)) + ws_round(gq_part_elems(c, M, D), sizeof(float));
+  return GpRowSumsWorkspace::bytes(GpChunks(N, M, D, chunk_rows), M, D);
 }
 
 // Both entries: `inputs` asks for dX as well (Ztimg, dX, lddx are then checked; ignored otherwise).
@@ -330,12 +340,8 @@ static int gp_fit_grad_run(const char* name, bool inputs, const float* X, int64_
   }
   CGAT_TRY(gp_check_workspace(name, ws, ws_bytes, cgat_gp_fit_grad_workspace_bytes(N, M, D, chunk_rows)));
   GpChunks ch(N, M, D, chunk_rows);
-  Workspace w(ws, ws_bytes);
-  float* At = w.take<float>(ch.at_elems());
-  float* Xt = w.take<float>(gq_xt_elems(ch, D));
-  float* pc = w.take<float>(gq_col_elems(ch));
-  float* pd = w.take<float>(gq_col_elems(ch));
-  float* part = w.take<float>(gq_part_elems(ch, M, D));
+  const GpRowSumsWorkspace w(ch, M, D, ws, ws_bytes);
+  float *At = w.At, *pc = w.pc, *pd = w.pd;
   const long pitch = ch.eff_chunk;
   const GpTile tile = gp_tile_operands(X, ldx, 0, D, Zimg, M, centroid, znorm, s, inv_two_l2);
   GpWhitenArgs a{tile, ch.Map, (const float4*)W1img, nullptr, At, pitch};
@@ -344,7 +350,6 @@ static int gp_fit_grad_run(const char* name, bool inputs, const float* X, int64_
   f.At = At; f.pitch = pitch; f.M = M; f.Mp = ch.Mp; f.c = c;
   GpInputArgs in{At, pitch, 0, (int)M, ch.Mp, (int)D, (const float4*)Ztimg, X, (long)ldx, centroid, inv_two_l2, dX, (long)lddx,
                  (((uintptr_t)X & 15) == 0 && (ldx & 3) == 0) ? 1 : 0, (((uintptr_t)dX & 15) == 0 && (lddx & 3) == 0) ? 1 : 0};
-  const int n_tiles = gq_tiles(M, D), tiles_d = cdiv(D, GS_TILE);
   CGAT_PROF(name, st);
   while (ch.next()) {
     ch.place(a, X);
@@ -368,18 +373,7 @@ static int gp_fit_grad_run(const char* name, bool inputs, const float* X, int64_
       hipLaunchKernelGGL(gp_input_rows, dim3(ch.row_tiles), dim3(GP_THREADS), 0, st, in);
       CGAT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(gp_centre_rows, dim3(ch.row_tiles, cdiv(D, 32)), dim3(256), 0, st, a.X, (long)ldx, ch.rows, (int)D,
-                       centroid, Xt, pitch);
-    CGAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gp_pair_slabs, dim3(n_tiles, ch.n_slabs), dim3(GS_THREADS), 0, st, At, Xt, pitch, (int)M, (int)D,
-                       ch.rows_p, part, tiles_d);
-    CGAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gp_grad_reduce_pairs, dim3(n_tiles, GS_TILE * GS_TILE / 256), dim3(256), 0, st, part, tiles_d,
-                       ch.n_slabs, (int)M, (int)D, P, ch.first);
-    CGAT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gp_grad_reduce_columns, dim3(cdiv(M, GQ_RC_COLS)), dim3(GQ_RC_COLS * GQ_RC_SEGS), 0, st, pc, pd,
-                       ch.row_tiles, ch.Mp, (int)M, colsum, d2sum, ch.first);
-    CGAT_LAUNCH_CHECK();
+    CGAT_TRY(gp_launch_row_sums(w, ch, a.X, (long)ldx, M, D, centroid, colsum, d2sum, P, st));
   }
   return CGAT_OK;
 }

@@ -41,7 +41,8 @@ host fp64):
 
 F is the bound sum_n E_q[log N(y~_n | f_n, sigma^2)] - KL(q(v) || N(0, I)) at that (m, L_S), in total nats.  c has a
 closed form (F is quadratic in it), sigma^2 is found by a bounded 1-D search, l and s come from a caller's grid by the
-larger F, Z is a fixed subset of the training rows (the reference's initialisation, :223-226).  gpytorch's
+larger F, Z is a fixed subset of the training rows (the reference's initialisation, :223-226) or the k-means centres
+started from it (`init`, below).  gpytorch's
 VariationalELBO is meant to be this bound divided by N (`elbo_per_point`); gpytorch is not installed where this package
 is built, so that scaling is unconfirmed, like the default of `jitter`.
 
@@ -68,6 +69,13 @@ one more product per tile of 32 rows in that pass (`cgat_gp_fit_grad_inputs`), [
 `bound_and_gradient(..., wrt_embeddings=True)`.  `collapsed_bound` is the bound as a tensor that is differentiable in the
 embeddings, `deep_kernel_gradient` the exact full-batch gradient of -F / N in a network's parameters at the memory cost
 of one batch.
+
+Where Z starts.  The reference's only choice is that random batch of training rows.  `kmeans_step` is one
+Lloyd step on the device (csrc/gpkmeans.hip: the distance tile of the passes above with an argmin, then the R^T X product
+of the gradient pass with a one-hot R): assignment, counts, within-cluster sums of squares and sum_{a_n = m} (x_n -
+centroid) in fp64.  `kmeans_inducing_points` iterates it from the subset `fit` would draw, moving the centres on the host
+in fp64, and `GPHead.fit(init="kmeans")` or `init=("subset", "kmeans")` starts the fit there or from whichever of the two
+has the larger bound: k-means is usually the better start, not always.
 
 Outputs carry no grad, with the one exception of `collapsed_bound`; non-GPU and non-fp32 inputs are refused like
 everywhere else in the package.
@@ -545,6 +553,131 @@ def median_lengthscale(Z):
     return math.sqrt(float(d2[i, j].median()))
 
 
+def _subset_rows(x, M, seed):
+    """M distinct rows of x [N, D] (device), drawn with a torch.Generator seeded by `seed`, on the host
+    (the reference's initialisation, gaussian_process.py:223-226)."""
+    perm = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(int(seed)))[:M]
+    return x[perm.to(x.device)].to("cpu")
+
+
+def _width_of(inducing_points, embeddings):
+    """D as the caller states it: of a [M, D] start, else of the embeddings (None when neither is a matrix)."""
+    if isinstance(inducing_points, torch.Tensor) and inducing_points.dim() == 2:
+        return inducing_points.shape[1]
+    return embeddings.shape[1] if isinstance(embeddings, torch.Tensor) and embeddings.dim() == 2 else None
+
+
+class _KMeansPass:
+    """What a cgat_gp_kmeans_step call needs and the centres do not change: the checked embeddings and the workspace.
+    Calling it with centres [M, D] uploads their operands of phase (a) (_centred64 in fp64 on the host, rounded to fp32:
+    _tile_operands) and enqueues one step; the outputs are new tensors."""
+
+    def __init__(self, what, embeddings, M, D, chunk_rows):
+        self.what, self.M, self.D = what, int(M), int(D)
+        self.chunk = DEFAULT_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+        if self.chunk < 32 or self.chunk % 32:
+            raise ValueError(f"{what}: chunk_rows = {self.chunk} is not a positive multiple of 32")
+        self.x = _check_embeddings(what, embeddings, self.D)
+        self.N = self.x.shape[0]
+        if self.N < 1:
+            raise ValueError(f"{what}: at least one row of embeddings is needed")
+        self.ws_bytes = _lib.lib.cgat_gp_kmeans_step_workspace_bytes(self.N, self.M, self.D, self.chunk)
+        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=self.x.device)
+
+    def __call__(self, centres):
+        Z = torch.as_tensor(centres).detach().to("cpu", torch.float64)
+        if tuple(Z.shape) != (self.M, self.D):
+            raise ValueError(f"{self.what}: centres must be [{self.M}, {self.D}], got {tuple(Z.shape)}")
+        x, dev, M, D = self.x, self.x.device, self.M, self.D
+        ops = _tile_operands(*_centred64(Z), dev)
+        assign = torch.empty(self.N, dtype=torch.int32, device=dev)
+        counts = torch.empty(M, dtype=torch.float64, device=dev)
+        wss = torch.empty(M, dtype=torch.float64, device=dev)
+        sums = torch.empty(M, D, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib.cgat_gp_kmeans_step(_ptr(x), x.stride(0), self.N, D, _ptr(ops["zimg"]), M, _ptr(ops["centroid"]),
+                                              _ptr(ops["znorm"]), self.chunk, _ptr(assign), _ptr(counts), _ptr(wss),
+                                              _ptr(sums), _ptr(self.ws), self.ws_bytes, _stream())
+        _lib.check(rc, "cgat_gp_kmeans_step")
+        return dict(assign=assign, counts=counts, wss=wss, sums=sums, centroid=ops["centroid"])
+
+
+def _centres_of(what, centres):
+    Z = torch.as_tensor(centres)
+    if Z.dim() != 2 or Z.shape[0] < 1 or Z.shape[1] < 1:
+        raise ValueError(f"{what}: the centres must be [M, D], got {tuple(Z.shape)}")
+    return Z
+
+
+def kmeans_step(embeddings, centres, chunk_rows=None):
+    """One Lloyd step (one cgat_gp_kmeans_step call, csrc/gpkmeans.hip) of `embeddings` [N, D] (fp32, GPU)
+    against `centres` [M, D] (any device, M <= 1024).  Returns a dict of tensors on the device of the embeddings:
+
+        assign [N] int32    the nearest centre of each row, a tie to the smaller index
+        counts [M] fp64     rows per centre (exact integers)
+        wss [M] fp64        per centre, the sum of its rows' squared distances to it; wss.sum() is the inertia
+        sums [M, D] fp64    per centre, the sum of (x_n - centroid) over its rows
+        centroid [D] fp32   the mean of the centres the kernel centred with: the next centre m is
+                            centroid + sums[m] / counts[m] where counts[m] > 0
+
+    `chunk_rows` as for fit_statistics."""
+    Z = _centres_of("kmeans_step", centres)
+    return _KMeansPass("kmeans_step", embeddings, Z.shape[0], Z.shape[1], chunk_rows)(Z)
+
+
+def kmeans_inducing_points(embeddings, inducing_points, iters=10, seed=0, chunk_rows=None):
+    """Inducing points for GPHead.fit by Lloyd's k-means on `embeddings` [N, D] (fp32, GPU); returns (Z, report), Z
+    [M, D] fp32 on the host.
+
+    inducing_points   an int M: the start is the subset GPHead.fit draws for the same `seed` (so iters=0 returns exactly
+                      that subset); or a start [M, D].  M <= 1024.
+    iters             at most that many steps.  A step is one kmeans_step at the current Z, then, on the host in fp64,
+                      Z_m <- centroid + sums_m / counts_m (a centre without rows stays where it is), rounded to fp32.
+                      When a step finds the assignment of the step before it, the iteration has converged and stops
+                      without that (repeated) update.
+
+    report: iterations (updates of Z made), converged, inertia (sum_n min_m |x_n - z_m|^2 of every assignment
+    evaluated, i.e. at the Z each step started from) and empty (per update, the number of centres without rows).
+    Per step one upload of the centres' image and one read-back of (sums, counts, wss)."""
+    what = "kmeans_inducing_points"
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError(f"{what}: iters = {iters} is negative")
+    x = _check_embeddings(what, embeddings, _width_of(inducing_points, embeddings))
+    if isinstance(inducing_points, torch.Tensor):
+        Z = _centres_of(what, inducing_points).detach().to("cpu", torch.float32)
+    else:
+        M = int(inducing_points)
+        if not 1 <= M <= x.shape[0]:
+            raise ValueError(f"{what}: {M} inducing points from {x.shape[0]} rows")
+        Z = _subset_rows(x, M, seed)
+    report = dict(iterations=0, converged=False, inertia=[], empty=[])
+    if iters == 0:
+        return Z, report
+    step = _KMeansPass(what, x, Z.shape[0], Z.shape[1], chunk_rows)
+    before = None
+    for _ in range(iters):
+        out = step(Z)
+        M, D = Z.shape
+        back = torch.cat([out["sums"].reshape(-1), out["counts"], out["wss"]]).cpu()      # the one read-back
+        sums, counts, wss = back[:M * D].reshape(M, D), back[M * D:M * D + M], back[M * D + M:]
+        report["inertia"].append(float(wss.sum()))
+        if before is not None and torch.equal(out["assign"], before):
+            report["converged"] = True
+            break
+        before = out["assign"]
+        filled = counts > 0
+        centroid = _centred64(Z.to(torch.float64))[0].to(torch.float32)         # what the step centred with, out["centroid"]
+        moved = centroid.to(torch.float64) + sums / counts.clamp_min(1.0)[:, None]
+        Z = torch.where(filled[:, None], moved, Z.to(torch.float64)).to(torch.float32)
+        report["empty"].append(int((~filled).sum()))
+        report["iterations"] += 1
+    return Z, report
+
+
+INITS = ("subset", "kmeans")
+
+
 class GPHead(nn.Module):
     """Sparse variational GP head.  Buffers (what each corresponds to in the reference's GLightningModel; no gpytorch
     checkpoint key names are claimed):
@@ -597,12 +730,22 @@ class GPHead(nn.Module):
 
     @classmethod
     def fit(cls, embeddings, targets, inducing_points=1000, lengthscale="median", outputscale=1.0, zero_mean=False,
-            noise=None, jitter=1e-4, seed=0, chunk_rows=None, learn=(), max_iter=50, bounds=None):
+            noise=None, jitter=1e-4, seed=0, chunk_rows=None, learn=(), max_iter=50, bounds=None, init=None,
+            kmeans_iters=10):
         """Fits a head to `embeddings` [N, D] (fp32, GPU) and `targets` [N] at the optimum of the collapsed bound (module
         docstring); returns (head, report), the head on the device of the embeddings.
 
         inducing_points   an int M: that many distinct training rows, drawn with a torch.Generator seeded by `seed`
                           (the reference's initialisation, gaussian_process.py:223-226); or a [M, D] tensor.  M <= 1024.
+        init              where an int M starts from (a [M, D] tensor is used as it is and reported as "given"):
+                          "subset", those rows; "kmeans",
+                          kmeans_inducing_points(embeddings, M, iters=kmeans_iters, seed=seed) from those rows
+                          (DESIGN 10f); or a sequence of these: the (lengthscale, outputscale) grid then runs once per
+                          start, "median" taken from each start's own Z, and the start of the largest bound wins
+                          (k-means is usually the better start, not always).  None (the default) is "subset" with the
+                          report as it was before there was a choice.  Otherwise every row of `candidates` gains the key
+                          `init` and the report `init` (the winning start) and `kmeans` (the report of
+                          kmeans_inducing_points, None where "kmeans" was not tried).  `learn` ascends from the winner.
         lengthscale,      a float or a sequence of floats each; a sequence runs one pass over the data per
         outputscale       (lengthscale, outputscale) pair and keeps the pair with the largest bound.  "median": the
                           square root of the median off-diagonal |z_i - z_j|^2.
@@ -625,9 +768,12 @@ class GPHead(nn.Module):
         grid's best), evaluations (of bound_and_gradient) and active_bounds (e.g. ["outputscale:lower"]; empty when the
         optimum is interior).  elbo, noise and constant are those of the returned head (Z rounded to fp32)."""
         Zin = inducing_points
-        D = Zin.shape[1] if isinstance(Zin, torch.Tensor) and Zin.dim() == 2 else (
-            embeddings.shape[1] if isinstance(embeddings, torch.Tensor) and embeddings.dim() == 2 else None)
-        x = _check_embeddings("GPHead.fit", embeddings, D)
+        inits = ("subset",) if init is None else (init,) if isinstance(init, str) else tuple(init)
+        if not inits or len(set(inits)) != len(inits) or not set(inits) <= set(INITS):
+            raise ValueError(f"GPHead.fit: init must be one of {INITS} or a sequence of them, got {init!r}")
+        if int(kmeans_iters) < 0:
+            raise ValueError(f"GPHead.fit: kmeans_iters = {kmeans_iters} is negative")
+        x = _check_embeddings("GPHead.fit", embeddings, _width_of(Zin, embeddings))
         N, dev = x.shape[0], x.device
         y = torch.as_tensor(targets).detach().reshape(-1)
         if y.numel() != N:
@@ -639,16 +785,21 @@ class GPHead(nn.Module):
         if not ts > 0.0:
             raise ValueError("GPHead.fit: the targets are constant")
         y_norm = ((y64 - tm) / ts).to(torch.float32).to(dev)
+        kmeans_report = None
         if isinstance(Zin, torch.Tensor):
-            Z = Zin.detach().to("cpu", torch.float32)
+            starts = [("given", Zin.detach().to("cpu", torch.float32))]
         else:
             M = int(Zin)
             if not 1 <= M <= N:
                 raise ValueError(f"GPHead.fit: {M} inducing points from {N} rows")
-            perm = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:M]
-            Z = x[perm.to(dev)].to("cpu")
+            starts = []
+            for name in inits:
+                if name == "kmeans":
+                    Zk, kmeans_report = kmeans_inducing_points(x, M, iters=kmeans_iters, seed=seed, chunk_rows=chunk_rows)
+                    starts.append((name, Zk))
+                else:
+                    starts.append((name, _subset_rows(x, M, seed)))
         as_list = lambda v: [float(t) for t in torch.as_tensor(v, dtype=torch.float64).reshape(-1)]
-        ells = [median_lengthscale(Z)] if isinstance(lengthscale, str) and lengthscale == "median" else as_list(lengthscale)
         learn = (learn,) if isinstance(learn, str) else tuple(learn)
         if len(set(learn)) != len(learn) or not set(learn) <= set(LEARNABLE):
             raise ValueError(f"GPHead.fit: learn must be a subset of {LEARNABLE}, got {learn}")
@@ -659,21 +810,30 @@ class GPHead(nn.Module):
             box.update({k: (float(lo), float(hi)) for k, (lo, hi) in bounds.items()})
         if any(not 0.0 < lo <= 1.0 <= hi < math.inf for lo, hi in box.values()):
             raise ValueError("GPHead.fit: bounds are pairs of factors (low, high) with 0 < low <= 1 <= high < inf")
-        # Z's image and the workspace: once
+        # the workspace: once; Z's image: once per start
+        Z = starts[0][1]
         gradient_pass = _GradientPass("GPHead.fit", x, y_norm, Z, chunk_rows) if learn else None
         data_pass = gradient_pass.stats if learn else _StatisticsPass("GPHead.fit", x, y_norm, Z, chunk_rows)
         candidates, best = [], None
-        for ell in ells:
-            for s in as_list(outputscale):
-                sol = solve_collapsed(data_pass(s, ell, jitter), N, s, noise=noise, zero_mean=zero_mean)
-                candidates.append(dict(lengthscale=ell, outputscale=s, noise=sol["noise"], constant=sol["constant"],
-                                       elbo=sol["elbo"]))
-                if best is None or sol["elbo"] > best[1]["elbo"]:
-                    best = (candidates[-1], sol)
-        row, sol = best
-        learned = {}
+        for name, Zs in starts:
+            if Zs is not Z:
+                data_pass.set_inducing_points(Zs)
+            ells = ([median_lengthscale(Zs)] if isinstance(lengthscale, str) and lengthscale == "median"
+                    else as_list(lengthscale))
+            for ell in ells:
+                for s in as_list(outputscale):
+                    sol = solve_collapsed(data_pass(s, ell, jitter), N, s, noise=noise, zero_mean=zero_mean)
+                    candidates.append(dict(lengthscale=ell, outputscale=s, noise=sol["noise"], constant=sol["constant"],
+                                           elbo=sol["elbo"], **({} if init is None else {"init": name})))
+                    if best is None or sol["elbo"] > best[1]["elbo"]:
+                        best = (candidates[-1], sol, name, Zs)
+        row, sol, start, Z = best
+        learned = {} if init is None else dict(init=start, kmeans=kmeans_report)
         if learn:
-            row, sol, Z, learned = cls._learn(gradient_pass, row, Z, learn, box, int(max_iter), jitter, noise, zero_mean)
+            if Z is not starts[-1][1]:
+                gradient_pass.set_inducing_points(Z)            # the ascent starts from the winner's Z
+            row, sol, Z, ascent = cls._learn(gradient_pass, row, Z, learn, box, int(max_iter), jitter, noise, zero_mean)
+            learned.update(ascent)
         head = cls(Z, sol["variational_mean"], sol["chol_variational_covar"], constant=sol["constant"],
                    outputscale=row["outputscale"], lengthscale=row["lengthscale"], mean=tm, std=ts, jitter=jitter).to(dev)
         report = dict(noise=sol["noise"], elbo=sol["elbo"], elbo_per_point=sol["elbo"] / N, constant=sol["constant"],

@@ -948,6 +948,24 @@ int cgat_gp_fit_grad_inputs(const float* X, int64_t ldx, const float* y_norm, in
                             double* colsum, double* d2sum, double* P, const float* Ztimg, float* dX, int64_t lddx,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* ---- one Lloyd step of k-means over the embeddings: inducing points at the centres of the data ----------
+ * The reference normalises the targets and starts its inducing points from one random batch of training embeddings
+ * (CGAT/gaussian_process.py:208-226); the usual recipe for a sparse GP moves such a start by k-means.  Per row n of X
+ *   a_n = argmin_{m < M} max(|x_n - z_m|^2, 0), a tie to the smaller m;   d_n = that minimum
+ *   counts[m] = #{n : a_n = m}     wss[m] = sum_{a_n = m} d_n     P[m][d] = sum_{a_n = m} (x_n[d] - centroid[d])
+ * so the next centre is centroid + P[m] / counts[m] (an empty cluster has counts[m] = 0 and P[m] = 0) and sum_m wss[m] is
+ * the inertia of the assignment.  Outputs: assign [N] int32; fp64 counts [M] (exact integers), wss [M], P [M, D]
+ * row-major.  Operands as for cgat_gp_fit_stats: X [N, D] rows ldx apart, Zimg / centroid / znorm of the centres Z (a
+ * padded centre never receives a row).  The distances are formed as in cgat_gp_predict on the f32-input matrix cores; the
+ * one-hot assignment of a chunk passes through the chunk buffer and P is formed by the slab product of cgat_gp_fit_grad;
+ * the sums are fp32 per tile of 32 rows (counts, wss) or per slab of 1024 rows (P) and added in fp64 in a fixed order.
+ * chunk_rows, M > 1024, the workspace and its query (equal to cgat_gp_fit_grad_workspace_bytes) as for cgat_gp_fit_stats.
+ * No atomics: bitwise deterministic; caller's stream, no allocation, no synchronisation. */
+size_t cgat_gp_kmeans_step_workspace_bytes(int32_t N, int32_t M, int32_t D, int32_t chunk_rows);
+int cgat_gp_kmeans_step(const float* X, int64_t ldx, int32_t N, int32_t D, const float* Zimg, int32_t M,
+                        const float* centroid, const float* znorm, int32_t chunk_rows, int32_t* assign, double* counts,
+                        double* wss, double* P, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
