@@ -186,6 +186,8 @@ PROTOTYPES = {
     "cgat_hnet_backward_overlapped": (C.c_int, [C.c_int32, C.POINTER(HnetParams), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(HnetGrads), vp, C.c_size_t, vp, vp, C.c_size_t, vp]),
     "cgat_debug_hnet_route": (C.c_uint32, [C.c_int32, C.POINTER(HnetParams), C.c_int32, C.c_int32]),
+    "cgat_debug_colsum_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cgat_debug_colsum": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_float, vp, C.c_size_t, vp]),
     "cgat_linear_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "cgat_linear_forward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "cgat_linear_forward": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_int32,

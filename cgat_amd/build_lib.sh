@@ -17,7 +17,7 @@ if [ ! -f "$FLAGS_STAMP" ] || [ "$(cat "$FLAGS_STAMP")" != "${CGAT_HIPCC_FLAGS}"
 fi
 for s in "${SRCS[@]}"; do
   src="$HERE/csrc/$s.hip"; obj="$HERE/csrc/build/$s.o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/csrc/kernels.h" -nt "$obj" ] || [ "$HERE/csrc/common.h" -nt "$obj" ] || [ "$HERE/csrc/mfma_bf16.h" -nt "$obj" ] || [ "$HERE/csrc/wgrad_batch.h" -nt "$obj" ] || [ "$HERE/csrc/layers.h" -nt "$obj" ] || [ "$HERE/csrc/gp_tile.h" -nt "$obj" ] || [ "$HERE/csrc/gp_slab.h" -nt "$obj" ] || [ "$HERE/../include/cgat_hip.h" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/csrc/kernels.h" -nt "$obj" ] || [ "$HERE/csrc/common.h" -nt "$obj" ] || [ "$HERE/csrc/mfma_bf16.h" -nt "$obj" ] || [ "$HERE/csrc/wgrad_batch.h" -nt "$obj" ] || [ "$HERE/csrc/layers.h" -nt "$obj" ] || [ "$HERE/csrc/gp_tile.h" -nt "$obj" ] || [ "$HERE/csrc/gp_slab.h" -nt "$obj" ] || [ "$HERE/csrc/rowops_grid.h" -nt "$obj" ] || [ "$HERE/../include/cgat_hip.h" -nt "$obj" ]; then
     extra=""
     # MFMA kernels with VALU epilogues: no SLP packing into v_pk_*_f32 (see the note in csrc/edgez.hip)
     if [ "$s" = edgez ] || [ "$s" = edgebwd ] || [ "$s" = bilinear ] || [ "$s" = opimage ] || [ "$s" = bilwgrad ] || [ "$s" = wgradc ] || [ "$s" = chain ] || [ "$s" = rowsdw ] || [ "$s" = gemmsplit ] || [ "$s" = gphead ] || [ "$s" = gpfit ] || [ "$s" = gpgrad ] || [ "$s" = gpkmeans ]; then extra="-fno-slp-vectorize"; fi

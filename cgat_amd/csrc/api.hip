@@ -337,6 +337,13 @@ static int linear_backward_impl(const float* x, int64_t ldx, const float* w, int
   return CGAT_OK;
 }
 
+extern "C" size_t cgat_debug_colsum_workspace_bytes(int32_t rows, int32_t cols) { return colsum_ws_bytes(rows, cols) + 256; }
+extern "C" int cgat_debug_colsum(const float* x, int64_t ldx, int32_t rows, int32_t cols, float* out, float alpha, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  CGAT_CHECK_ARG(rows >= 0 && cols >= 0 && ldx >= cols, "debug_colsum: rows %d, cols %d, ldx %ld", rows, cols, (long)ldx);
+  return colsum_launch(x, ldx, rows, cols, out, alpha, ws, ws_bytes, (hipStream_t)stream);
+}
+
 // ---- segment ops ----
 extern "C" int cgat_segment_softmax_forward(const float* a, const float* mult, const int32_t* rowptr, int32_t S,
                                             int32_t F, float eps, float* alpha, void* stream) {

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "mfma_bf16.h"
+#include "rowops_grid.h"
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -72,9 +73,87 @@ int layernorm_tanh_fwd_launch(const float* u, float* y, int rows, int W, float e
   return CGAT_OK;
 }
 
+// The same at W = 128, bit for bit.  One wave still reduces one row: lane k holds columns k and k + 64 of u, y and gy in
+// registers (each loaded once), adds the two in that order wherever the kernel above loops over c = lane, lane + 64, and
+// the xor butterfly 32 .. 1 of wave_sum follows.  A wave walks rows with a grid stride and requests the next row's six
+// dwords before it reduces the present one, so two rows are in flight per wave; the grid is sized to the chip (LN128_WGS
+// workgroups of four waves, rowops_grid.h: 32 waves per CU), not to rows / 4.
+// The roundings are part of the contract and are pinned here (contraction off, fmaf where one rounding is meant); they are
+// the ones hipcc gives the kernel above at two columns per lane:
+//   s = (0 + x0) + x1;  d_k = x_k - mean;  v = fma(d1, d1, fma(d0, d0, 0));  rstd = rsqrtf(sum(v) / W + eps)
+//   one_k = fma(-y_k, y_k, 1);  gx_k = g_k * one_k;  s1 = (0 + gx0) + gx1;  s2 = (0 + t0) + t1,  t_k = ((x_k - mean) * gx_k) * rstd
+//   gu_k = rstd * fma(-s2, rstd * (x_k - mean), fma(g_k, one_k, -s1))        (s1, s2 the row means)
+__device__ __forceinline__ float ln128_gu(float x, float yy, float g, float mean, float rstd, float s1, float s2) {
+#pragma clang fp contract(off)
+  const float one = __builtin_fmaf(-yy, yy, 1.f);
+  const float xh = rstd * (x - mean);
+  return rstd * __builtin_fmaf(-s2, xh, __builtin_fmaf(g, one, -s1));
+}
+struct Ln128Row {
+  float x0, x1, y0, y1, g0, g1;
+};
+__device__ __forceinline__ Ln128Row ln128_load(const float* __restrict__ u, const float* __restrict__ y,
+                                               const float* __restrict__ gy, long o) {
+  return {u[o], u[o + 64], y[o], y[o + 64], gy[o], gy[o + 64]};
+}
+__device__ __forceinline__ float2 ln128_row(const Ln128Row& r, float eps) {
+#pragma clang fp contract(off)
+  constexpr int W = 128;
+  float s = 0.f;
+  s += r.x0;
+  s += r.x1;
+  const float mean = wave_sum(s) / W;
+  const float d0 = r.x0 - mean, d1 = r.x1 - mean;
+  const float v = __builtin_fmaf(d1, d1, __builtin_fmaf(d0, d0, 0.f));
+  const float rstd = rsqrtf(wave_sum(v) / W + eps);
+  const float gx0 = r.g0 * __builtin_fmaf(-r.y0, r.y0, 1.f), gx1 = r.g1 * __builtin_fmaf(-r.y1, r.y1, 1.f);
+  float s1 = 0.f, s2 = 0.f;
+  s1 += gx0;
+  s2 += ((r.x0 - mean) * gx0) * rstd;
+  s1 += gx1;
+  s2 += ((r.x1 - mean) * gx1) * rstd;
+  s1 = wave_sum(s1) / W;
+  s2 = wave_sum(s2) / W;
+  return make_float2(ln128_gu(r.x0, r.y0, r.g0, mean, rstd, s1, s2), ln128_gu(r.x1, r.y1, r.g1, mean, rstd, s1, s2));
+}
+__global__ __launch_bounds__(256) void layernorm_tanh_bwd128_kernel(const float* __restrict__ u, const float* __restrict__ y,
+                                                                    const float* __restrict__ gy, float* __restrict__ gu,
+                                                                    int rows, float eps) {
+  constexpr int W = 128;
+  const int lane = threadIdx.x & 63;
+  const long stride = (long)gridDim.x * (blockDim.x >> 6);
+  long ra = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (ra >= rows) return;
+  // two register sets, a and b, in turn: the loads of one are requested before the other is reduced.  Loads and
+  // arithmetic are unconditional and only the stores are guarded (a wave past its last row requests that row again and
+  // drops the result), so that no load can be moved behind a branch, next to its first use
+  Ln128Row a = ln128_load(u, y, gy, ra * W + lane);
+  while (true) {
+    const long rb = ra + stride;
+    const Ln128Row b = ln128_load(u, y, gy, (rb < rows ? rb : ra) * W + lane);
+    const float2 oa = ln128_row(a, eps);
+    gu[ra * W + lane] = oa.x;
+    gu[ra * W + lane + 64] = oa.y;
+    const long rn = rb + stride;
+    a = ln128_load(u, y, gy, (rn < rows ? rn : ra) * W + lane);
+    const float2 ob = ln128_row(b, eps);
+    if (rb < rows) {
+      gu[rb * W + lane] = ob.x;
+      gu[rb * W + lane + 64] = ob.y;
+    }
+    if (rn >= rows) break;
+    ra = rn;
+  }
+}
+
 int layernorm_tanh_bwd_launch(const float* u, const float* y, const float* gy, float* gu, int rows, int W, float eps,
                               hipStream_t s) {
   if (rows <= 0) return CGAT_OK;
+  if (W == 128) {
+    hipLaunchKernelGGL(layernorm_tanh_bwd128_kernel, dim3(ln128_wgs(rows)), dim3(256), 0, s, u, y, gy, gu, rows, eps);
+    CGAT_LAUNCH_CHECK();
+    return CGAT_OK;
+  }
   hipLaunchKernelGGL(layernorm_tanh_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, u, y, gy, gu, rows, W, eps);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
@@ -144,10 +223,12 @@ int act_bwd_launch(const float* y, const float* gy, float* gpre, long n, int act
   return CGAT_OK;
 }
 
-// ---- column sums: partial[chunk][c] over 128-row chunks (256 threads = 64 columns x 4 row lanes,
-// LDS-combined), then a second pass of the same shape over the partials; fixed summation order,
-// hence deterministic ----
-#define COLSUM_ROWS 128
+// ---- column sums: partial[chunk][c] over 128-row chunks, then a second pass of the same shape over the partials, until
+// one chunk is left.  The summation order is fixed, hence deterministic, and the same in all three kernels below:
+//   lane sum rl (0..3) of (chunk, column) = x[r0 + rl] + x[r0 + rl + 4] + ... in ascending row order, starting from 0.f;
+//   partial[chunk][c] = alpha * (red[0] + red[1] + red[2] + red[3]), left to right.
+// What differs is how threads map to (chunk, column, row lane). ----
+// any shape: 64 columns x 4 row lanes per workgroup, one chunk per blockIdx.y
 __global__ void colsum_partial_kernel(const float* __restrict__ x, long ldx, int rows, int cols,
                                       float* __restrict__ partial, float alpha) {
   __shared__ float red[4][64];
@@ -161,7 +242,69 @@ __global__ void colsum_partial_kernel(const float* __restrict__ x, long ldx, int
   __syncthreads();
   if (rl == 0 && c < cols) partial[(long)blockIdx.y * cols + c] = alpha * (red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl]);
 }
-static inline int colsum_chunks(int rows) { return cdiv(rows > 0 ? rows : 1, COLSUM_ROWS); }
+// narrow form (cols <= COLSUM_NARROW = 16, rowops_grid.h): the (chunk, column) pairs are numbered chunk * cols + c and a workgroup takes 64
+// of them, so it covers 64 / cols chunks and all 256 threads have work.  The row lane is the LOW two bits of the thread
+// index: one wave instruction reads four adjacent rows of 16 pairs.  Eight rows are requested before the first add.
+__global__ __launch_bounds__(256) void colsum_narrow_kernel(const float* __restrict__ x, long ldx, int rows, int cols,
+                                                            long pairs, float* __restrict__ partial, float alpha) {
+  __shared__ float red[4][64];
+  const int rl = threadIdx.x & 3, sl = threadIdx.x >> 2;
+  const long pair = (long)blockIdx.x * 64 + sl;
+  float s = 0.f;
+  if (pair < pairs) {
+    const int chunk = (int)(pair / cols), c = (int)(pair % cols);
+    const int r0 = chunk * COLSUM_ROWS, r1 = min(rows, r0 + COLSUM_ROWS);
+    const float* xc = x + c;
+    int r = r0 + rl;
+    for (; r + 28 < r1; r += 32) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = xc[(long)(r + 4 * j) * ldx];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += v[j];
+    }
+    for (; r < r1; r += 4) s += xc[(long)r * ldx];
+  }
+  red[rl][sl] = s;
+  __syncthreads();
+  if (rl == 0 && pair < pairs) partial[pair] = alpha * (red[0][sl] + red[1][sl] + red[2][sl] + red[3][sl]);
+}
+// wide form (cols % 4 == 0, ldx % 4 == 0, x and partial 16-byte aligned): a thread owns four adjacent columns and reads
+// them as one 16-byte load per row.  The (chunk, column quad) pairs are numbered chunk * (cols / 4) + quad, 64 of them per
+// workgroup; a wave is one row lane, so a wave instruction reads 1 KiB of one row where cols >= 256.  Eight rows are
+// requested before the first add; each of the four columns keeps its own sum, in the order above.
+__global__ __launch_bounds__(256) void colsum_wide_kernel(const float* __restrict__ x, long ldx, int rows, int quads,
+                                                          long pairs, float* __restrict__ partial, float alpha) {
+  __shared__ float4 red[4][64];
+  const int sl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const long pair = (long)blockIdx.x * 64 + sl;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (pair < pairs) {
+    const int chunk = (int)(pair / quads), q = (int)(pair % quads);
+    const int r0 = chunk * COLSUM_ROWS, r1 = min(rows, r0 + COLSUM_ROWS);
+    const float* xc = x + 4 * q;
+    int r = r0 + rl;
+    for (; r + 28 < r1; r += 32) {
+      float4 v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float4*>(xc + (long)(r + 4 * j) * ldx);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w; }
+    }
+    for (; r < r1; r += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(xc + (long)r * ldx);
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+  }
+  red[rl][sl] = s;
+  __syncthreads();
+  if (rl == 0 && pair < pairs) {
+    const float4 a = red[0][sl], b = red[1][sl], c = red[2][sl], d = red[3][sl];
+    reinterpret_cast<float4*>(partial)[pair] =
+        make_float4(alpha * (a.x + b.x + c.x + d.x), alpha * (a.y + b.y + c.y + d.y), alpha * (a.z + b.z + c.z + d.z),
+                    alpha * (a.w + b.w + c.w + d.w));
+  }
+}
 size_t colsum_ws_bytes(int rows, int cols) {
   size_t c1 = colsum_chunks(rows), c2 = colsum_chunks((int)c1);
   return ws_round(c1 * cols, 4) + ws_round(c2 * cols, 4);
@@ -180,8 +323,18 @@ int colsum_launch(const float* x, long ldx, int rows, int cols, float* out, floa
   while (true) {
     int chunks = colsum_chunks(n);
     float* dst = chunks == 1 ? out : bufs[level & 1];
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(cdiv(cols, 64), chunks), dim3(256), 0, s, src, ld, n, cols, dst,
-                       level == 0 ? alpha : 1.f);
+    const float a = level == 0 ? alpha : 1.f;
+    const ColsumGrid g = colsum_grid(n, cols, ld, src, dst);
+    switch (g.form) {
+      case COLSUM_FORM_NARROW:
+        hipLaunchKernelGGL(colsum_narrow_kernel, dim3(g.gx), dim3(256), 0, s, src, ld, n, cols, g.pairs, dst, a);
+        break;
+      case COLSUM_FORM_WIDE:
+        hipLaunchKernelGGL(colsum_wide_kernel, dim3(g.gx), dim3(256), 0, s, src, ld, n, cols / 4, g.pairs, dst, a);
+        break;
+      default:
+        hipLaunchKernelGGL(colsum_partial_kernel, dim3(g.gx, g.gy), dim3(256), 0, s, src, ld, n, cols, dst, a);
+    }
     CGAT_LAUNCH_CHECK();
     if (chunks == 1) break;
     src = dst;
@@ -208,43 +361,78 @@ int mix_launch(const float* a, const float* b, const float* d, float* out, long 
 }
 
 // ga = d*g ; gb += (1-d)*g ; gd = sum g*(a-b)   (block partials -> fixed-order final sum)
-__global__ void mix_bwd_kernel(const float* __restrict__ g, const float* __restrict__ a, const float* __restrict__ b,
-                               const float* __restrict__ d, float* __restrict__ ga, float* __restrict__ gb, long n,
-                               float* __restrict__ partial) {
+// The order is part of the contract: the grid is min(grid_for(n), 1024) workgroups of 256 threads, a thread's elements are
+// i, i + stride, ... and it adds their g*(a-b) to its s in that order; wave_sum, then red[0]+red[1]+red[2]+red[3]; the
+// workgroup partials are added as ((p[0]+p[1])+p[2])+...  The loop is unrolled by four: the loads of g, a, b, gb of four
+// iterations are requested before the arithmetic of the first.  Roundings, pinned: ga = d * g;  gb = fma(1 - d, g, gb);
+// s = fma(g, a - b, s).
+template <bool GA, bool GB>
+__global__ __launch_bounds__(256) void mix_bwd_kernel(const float* __restrict__ g, const float* __restrict__ a,
+                                                      const float* __restrict__ b, const float* __restrict__ d,
+                                                      float* __restrict__ ga, float* __restrict__ gb, long n,
+                                                      float* __restrict__ partial) {
+#pragma clang fp contract(off)
   __shared__ float red[4];
-  float dv = d[0];
+  const float dv = d[0], dc = 1.f - dv;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
   float s = 0.f;
+  for (; i + 3 * stride < n; i += 4 * stride) {
+    float gv[4], av[4], bv[4], gbv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      gv[j] = g[i + j * stride];
+      av[j] = a[i + j * stride];
+      bv[j] = b[i + j * stride];
+      if (GB) gbv[j] = gb[i + j * stride];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (GA) ga[i + j * stride] = dv * gv[j];
+      if (GB) gb[i + j * stride] = __builtin_fmaf(dc, gv[j], gbv[j]);
+      s = __builtin_fmaf(gv[j], av[j] - bv[j], s);
+    }
+  }
   for (; i < n; i += stride) {
     float gv = g[i];
-    if (ga) ga[i] = dv * gv;
-    if (gb) gb[i] += (1.f - dv) * gv;
-    s += gv * (a[i] - b[i]);
+    if (GA) ga[i] = dv * gv;
+    if (GB) gb[i] = __builtin_fmaf(dc, gv, gb[i]);
+    s = __builtin_fmaf(gv, a[i] - b[i], s);
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
-__global__ void sum_partials_kernel(const float* __restrict__ partial, int n, float* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < n; ++i) s += partial[i];
-    out[0] = s;
+// out = ((p[0]+p[1])+p[2])+... : the whole workgroup loads the partials, coalesced, into LDS (tiles of 1024), and thread 0
+// adds them from there in index order
+__global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ partial, int n, float* __restrict__ out) {
+  __shared__ float p[1024];
+  float s = 0.f;
+  for (int base = 0; base < n; base += 1024) {
+    const int m = min(n - base, 1024);
+    for (int i = threadIdx.x; i < m; i += blockDim.x) p[i] = partial[base + i];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int i = 0; i < m; ++i) s += p[i];
+    __syncthreads();
   }
+  if (threadIdx.x == 0) out[0] = s;
 }
 int mix_bwd_launch(const float* g, const float* a, const float* b, const float* d, float* ga, float* gb_accum,
                    float* gd, long n, void* ws, size_t ws_bytes, hipStream_t s) {
-  int blocks = grid_for(n);
-  if (blocks > 1024) blocks = 1024;
+  const int blocks = mix_bwd_wgs(n);
   if (!ws || ws_bytes < (size_t)blocks * 4) {
     cgat_set_error("mix_bwd: workspace too small");
     return CGAT_ERR_WORKSPACE;
   }
-  hipLaunchKernelGGL(mix_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, a, b, d, ga, gb_accum, n, (float*)ws);
+  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, g, a, b, d, ga, gb_accum, n, (float*)ws); };
+  if (ga && gb_accum) launch(mix_bwd_kernel<true, true>);
+  else if (ga) launch(mix_bwd_kernel<true, false>);
+  else if (gb_accum) launch(mix_bwd_kernel<false, true>);
+  else launch(mix_bwd_kernel<false, false>);
   CGAT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, blocks, gd);
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, blocks, gd);
   CGAT_LAUNCH_CHECK();
   return CGAT_OK;
 }

@@ -573,6 +573,13 @@ int cgat_hnet_backward_overlapped(int32_t rows, const cgat_hnet_params* p, const
  * named as HnetFwdRoute / HnetBwdRoute of csrc/hnet.hip.  0 for arguments the calls refuse. */
 uint32_t cgat_debug_hnet_route(int32_t rows, const cgat_hnet_params* p, int32_t backward, int32_t overlapped);
 
+/* Debug (tests only): the library's column sum alone, out[c] = alpha * sum_r x[r * ldx + c] in its fixed order (128-row
+ * chunks of four lane sums each, repeated on the partials; csrc/rowops.hip), which every bias gradient goes through with
+ * alpha = 1.  ws of at least cgat_debug_colsum_workspace_bytes(rows, cols). */
+size_t cgat_debug_colsum_workspace_bytes(int32_t rows, int32_t cols);
+int cgat_debug_colsum(const float* x, int64_t ldx, int32_t rows, int32_t cols, float* out, float alpha, void* ws,
+                      size_t ws_bytes, void* stream);
+
 /* ---- dense layer y = act(x W^T + b)  (nn.Linear / 1x1 Conv1d group + activation) --------
  * replaces the Linear/LeakyReLU/ReLU/Tanh pairs of CGAT/message_changed.py:58-63,124-130,
  * CGAT/roost_message.py:348-352 and one head of MultiHeadNetwork (CGAT/CGAT.py:103-109).
