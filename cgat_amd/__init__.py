@@ -27,7 +27,8 @@ from . import neighbors
 from .neighbors import NeighborTables, neighbor_tables, dataset_dict_from_structures, synthetic_structures
 from . import debug
 from . import gp
-from .gp import GPHead, bound_and_gradient, collapsed_bound, deep_kernel_gradient, kmeans_inducing_points
+from .gp import (GPHead, bound_and_gradient, collapsed_bound, deep_kernel_gradient, kmeans_inducing_points,
+                 latent_adjoints, predictive_backward)
 
 __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAttention", "H_Net", "H_Net_0",
            "HyperFC", "SimpleNetwork", "ResidualNetwork", "Rezero", "Roost", "MessageLayer", "WeightedAttention",
@@ -39,4 +40,4 @@ __all__ = ["CGAtNet", "GATConvNodes", "GATConvEdges", "MultiHeadNetwork", "MHAtt
            "get_indexed_edge_attr", "set_indexed_edge_training", "get_indexed_edge_training", "set_indexed_vector_attention",
            "get_indexed_vector_attention", "GraphedStep", "debug", "neighbors", "NeighborTables", "neighbor_tables",
            "dataset_dict_from_structures", "synthetic_structures", "gp", "GPHead", "bound_and_gradient", "collapsed_bound",
-           "deep_kernel_gradient", "kmeans_inducing_points"]
+           "deep_kernel_gradient", "kmeans_inducing_points", "latent_adjoints", "predictive_backward"]

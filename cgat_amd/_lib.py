@@ -293,6 +293,9 @@ PROTOTYPES = {
     "cgat_gp_fit_grad_inputs": (C.c_int, [vp, C.c_int64, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp,
                                           C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp,
                                           C.c_size_t, vp]),
+    "cgat_gp_predict_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cgat_gp_predict_backward": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           C.c_float, C.c_float, C.c_int32, vp, vp, C.c_int64, vp, C.c_size_t, vp]),
     "cgat_gp_kmeans_step_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "cgat_gp_kmeans_step": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp,
                                       vp, C.c_size_t, vp]),

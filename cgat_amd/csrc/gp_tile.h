@@ -1,12 +1,13 @@
 // Device and host code shared by the sparse-GP entries: csrc/gphead.hip (prediction), csrc/gpfit.hip (the fit
-// statistics), csrc/gpgrad.hip (the gradient of the bound) and csrc/gpkmeans.hip (the k-means step
-// for the inducing points).  All work on a tile of 32 rows of X with one 512-thread workgroup (8 waves, two
-// per SIMD):
+// statistics), csrc/gpgrad.hip (the gradient of the bound), csrc/gpkmeans.hip (the k-means step
+// for the inducing points) and csrc/gpback.hip (the backward of the prediction).  All work on a
+// tile of 32 rows of X with one 512-thread workgroup (8 waves, two per SIMD):
 //   GpTile              the operands of phase (a), filled by gp_tile_operands; the kernels that run it derive theirs from it
 //   gp_distance_tile    max(|x_row - z_m|^2, 0) of the tile, handed to a functor
 //   gp_kernel_tile      K^T[m][row] = s exp(-max(|x_row - z_m|^2, 0) inv_two_l2) of the tile, into LDS
 //   gp_factor_products  NB 32-row chunks of a packed factor image times that K^T tile, on the f32-input matrix cores
 //   gp_for_wave_pairs   the chunk pairs of a triangular factor that a wave owns
+//   gp_input_tile       dX of the tile's rows from a tile of r in LDS: the product with Zc^T and the stores (10e, 10g)
 //   gp_check_entry      (host) the argument checks the C entries share
 // and gp_launch_whiten_rows (host, defined in csrc/gpfit.hip) enqueues the whitening kernel of 10c for 10d.  The slab
 // products over a chunk of rows and the chunk walk of 10c and 10d are in gp_slab.h.
@@ -212,6 +213,85 @@ __device__ __forceinline__ void gp_distance_tile(const Args& p, long row0, float
         d2 = fmaxf(d2, 0.f);
         store(m, d2);
       }
+    }
+  }
+}
+
+// dX[row][d] = (sum_m r[m][row] zc[m][d] - rho (x[row][d] - centroid[d])) 2 inv_two_l2 of the tile's rows row0 .. that are
+// below p.G, from the tile of r, Rt [Mp][32] in LDS (rows m >= M zero), and this lane's rho = sum_m r[m][lane & 31].  `p`
+// has X, ldx, dX, lddx (all offset to the launch's first row), G, D, Mp, centroid, inv_two_l2, Ztimg (the packed image of
+// Zc^T [D rounded up to 32, Mp], zero padded) and vec_x / vec_dx (16-byte loads of X / stores of dX are aligned).
+// Columns at or past D and rows at or past G are never written.
+template <class Args>
+__device__ __forceinline__ void gp_input_tile(const Args& p, const float* Rt, float rho, long row0) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 31, hi = lane >> 5;
+  const int nC = (p.D + 31) >> 5, nk8 = p.Mp >> 3;
+  const long row = row0 + r;
+  const bool live = row < p.G;
+  const float scale = 2.f * p.inv_two_l2;
+  const float* xrow = p.X + row * p.ldx;
+  float* orow = p.dX + row * p.lddx;
+  // one rounding sequence whichever path loads and stores: the bits do not depend on the strides
+  auto value = [&](float acc, float x, int d) { return scale * fmaf(-rho, x - p.centroid[d], acc); };
+  auto emit = [&](int c, const f32x16& acc) {
+    if (!live) return;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int d0 = gp_acc_index(c, 4 * q, hi);                            // registers 4 q .. 4 q + 3: d0 .. d0 + 3
+      if (d0 + 3 < p.D) {
+        float x[4];
+        if (p.vec_x) {
+          const float4 xv = *(const float4*)(xrow + d0);
+          x[0] = xv.x; x[1] = xv.y; x[2] = xv.z; x[3] = xv.w;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) x[i] = xrow[d0 + i];
+        }
+        float o[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = value(acc[4 * q + i], x[i], d0 + i);
+        if (p.vec_dx) {
+          *(float4*)(orow + d0) = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) orow[d0 + i] = o[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int d = d0 + i;
+          if (d < p.D) orow[d] = value(acc[4 * q + i], xrow[d], d);
+        }
+      }
+    }
+  };
+  // The nC chunks of 32 embedding dimensions in 8 contiguous shares, the nC % 8 larger ones to the first waves: waves w and
+  // w + 4 run on one SIMD, so the matrix work per SIMD is even where nC % 8 <= 4 (D = 384: shares of 2 and 1 chunks, 3 per
+  // SIMD; D = 640: of 3 and 2, 5 per SIMD).  A share runs as pairs, its last three chunks as one triple (one pass over the
+  // tile in place of two).  Measured at N = 10^6, M = 1000: against shares dealt 1, 2, 1, 2, .. and pairs
+  // plus a single, 11.7 -> 9.9 ms at D = 384 and 17.0 -> 14.4 ms at D = 640.
+  const int base = nC / GP_WAVES, rem = nC % GP_WAVES;
+  const int c_lo = wave * base + min(wave, rem), c_hi = c_lo + base + (wave < rem ? 1 : 0);
+  for (int c = c_lo; c < c_hi;) {
+    if (c + 3 == c_hi) {
+      f32x16 acc[3];
+      gp_factor_products<3>(p.Ztimg, Rt, c, nC, nk8, nk8, lane, acc);
+      emit(c, acc[0]);
+      emit(c + 1, acc[1]);
+      emit(c + 2, acc[2]);
+      c += 3;
+    } else if (c + 1 < c_hi) {
+      f32x16 acc[2];
+      gp_factor_products<2>(p.Ztimg, Rt, c, nC, nk8, nk8, lane, acc);
+      emit(c, acc[0]);
+      emit(c + 1, acc[1]);
+      c += 2;
+    } else {
+      f32x16 acc[1];
+      gp_factor_products<1>(p.Ztimg, Rt, c, nC, nk8, nk8, lane, acc);
+      emit(c, acc[0]);
+      c += 1;
     }
   }
 }

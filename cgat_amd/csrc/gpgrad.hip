@@ -132,9 +132,7 @@ struct GpInputArgs {
 __global__ __launch_bounds__(GP_THREADS) void gp_input_rows(GpInputArgs p) {
   __shared__ __attribute__((aligned(16))) float Bt[GP_ROWS * GP_MAX_M];      // the tile [Mp][32]
   __shared__ float part[GP_THREADS];                                        // [16][32] partial column sums
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, hi = lane >> 5;
-  const int nC = (p.D + 31) >> 5, nk8 = p.Mp >> 3;
+  const int tid = threadIdx.x, r = tid & 31;
   const long row0 = (long)blockIdx.x * GP_ROWS;
   // thread tid copies column tid & 31 of rows tid >> 5, + 16, ...: its partial sum of that column, in row order
   float ps = 0.f;
@@ -149,74 +147,7 @@ __global__ __launch_bounds__(GP_THREADS) void gp_input_rows(GpInputArgs p) {
   float rho = 0.f;
 #pragma unroll
   for (int j = 0; j < GP_THREADS / GP_ROWS; ++j) rho += part[j * GP_ROWS + r];     // the 16 partials in a fixed order
-
-  const long row = row0 + r;
-  const bool live = row < p.G;
-  const float scale = 2.f * p.inv_two_l2;
-  const float* xrow = p.X + row * p.ldx;
-  float* orow = p.dX + row * p.lddx;
-  // one rounding sequence whichever path loads and stores: the bits do not depend on the strides
-  auto value = [&](float acc, float x, int d) { return scale * fmaf(-rho, x - p.centroid[d], acc); };
-  auto emit = [&](int c, const f32x16& acc) {
-    if (!live) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int d0 = gp_acc_index(c, 4 * q, hi);                            // registers 4 q .. 4 q + 3: d0 .. d0 + 3
-      if (d0 + 3 < p.D) {
-        float x[4];
-        if (p.vec_x) {
-          const float4 xv = *(const float4*)(xrow + d0);
-          x[0] = xv.x; x[1] = xv.y; x[2] = xv.z; x[3] = xv.w;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) x[i] = xrow[d0 + i];
-        }
-        float o[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = value(acc[4 * q + i], x[i], d0 + i);
-        if (p.vec_dx) {
-          *(float4*)(orow + d0) = make_float4(o[0], o[1], o[2], o[3]);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) orow[d0 + i] = o[i];
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int d = d0 + i;
-          if (d < p.D) orow[d] = value(acc[4 * q + i], xrow[d], d);
-        }
-      }
-    }
-  };
-  // The nC chunks of 32 embedding dimensions in 8 contiguous shares, the nC % 8 larger ones to the first waves: waves w and
-  // w + 4 run on one SIMD, so the matrix work per SIMD is even where nC % 8 <= 4 (D = 384: shares of 2 and 1 chunks, 3 per
-  // SIMD; D = 640: of 3 and 2, 5 per SIMD).  A share runs as pairs, its last three chunks as one triple (one pass over the
-  // tile in place of two).  Measured at N = 10^6, M = 1000: against shares dealt 1, 2, 1, 2, .. and pairs
-  // plus a single, 11.7 -> 9.9 ms at D = 384 and 17.0 -> 14.4 ms at D = 640.
-  const int base = nC / GP_WAVES, rem = nC % GP_WAVES;
-  const int c_lo = wave * base + min(wave, rem), c_hi = c_lo + base + (wave < rem ? 1 : 0);
-  for (int c = c_lo; c < c_hi;) {
-    if (c + 3 == c_hi) {
-      f32x16 acc[3];
-      gp_factor_products<3>(p.Ztimg, Bt, c, nC, nk8, nk8, lane, acc);
-      emit(c, acc[0]);
-      emit(c + 1, acc[1]);
-      emit(c + 2, acc[2]);
-      c += 3;
-    } else if (c + 1 < c_hi) {
-      f32x16 acc[2];
-      gp_factor_products<2>(p.Ztimg, Bt, c, nC, nk8, nk8, lane, acc);
-      emit(c, acc[0]);
-      emit(c + 1, acc[1]);
-      c += 2;
-    } else {
-      f32x16 acc[1];
-      gp_factor_products<1>(p.Ztimg, Bt, c, nC, nk8, nk8, lane, acc);
-      emit(c, acc[0]);
-      c += 1;
-    }
-  }
+  gp_input_tile(p, Bt, rho, row0);                                                 // the product and the stores (gp_tile.h)
 }
 
 // Xt [D][pitch]: column n of the chunk is x_n - centroid, 0 for n >= G.  grid (rows_p / 32, cdiv(D, 32)).

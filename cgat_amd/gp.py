@@ -77,7 +77,20 @@ centroid) in fp64.  `kmeans_inducing_points` iterates it from the subset `fit` w
 in fp64, and `GPHead.fit(init="kmeans")` or `init=("subset", "kmeans")` starts the fit there or from whichever of the two
 has the larger bound: k-means is usually the better start, not always.
 
-Outputs carry no grad, with the one exception of `collapsed_bound`; non-GPU and non-fp32 inputs are refused like
+Differentiable predictions.  `latent`, `predict` and `uncertainty` are differentiable in the embeddings
+where autograd records (grad mode on and `embeddings.requires_grad`); the head's own buffers are constants.  With
+alpha = W1 k_x and S = L_S L_S^T the latent distribution reads mean_f = c + alpha . m, var_f = s + alpha^T (S - I) alpha, so
+for upstream gradients gm = dL/dmean_f and gv = dL/dvar_f per row (`latent_adjoints` reduces those of the five outputs to
+these two)
+
+    u = dL/dk = W1^T (gv 2 (S - I) alpha + gm m),   r_m = u_m k_m,   dL/dx = (sum_m r_m (z_m - centroid) - rho (x - centroid)) / l^2
+
+the chain of the bound's gradient without its row sums (`predictive_backward`: cgat_gp_predict_backward, csrc/gpback.hip).
+`GPHead.nlpd` is the negative log predictive density of held-out targets on top of `latent`:
+
+    head.nlpd(model(batch, b_comp, return_graph_embedding=True), y, report["noise"]).mean().backward()
+
+Every other output carries no grad, with the exception of `collapsed_bound`; non-GPU and non-fp32 inputs are refused like
 everywhere else in the package.
 """
 import math
@@ -139,6 +152,14 @@ def _transposed_image(Zc, dev):
     return _pack_image(Zt).to(dev)
 
 
+def _square_image(P, dev):
+    """The packed image of P [M, M] padded with zeros to [Mp, Mp], fp32 on `dev`."""
+    M, Mp = P.shape[0], (P.shape[0] + 31) // 32 * 32
+    Pp = torch.zeros(Mp, Mp, dtype=torch.float32)
+    Pp[:M, :M] = P
+    return _pack_image(Pp).to(dev)
+
+
 def _check_embeddings(what, embeddings, D):
     """[N, D] fp32 on the GPU, unit column stride and a row stride of at least D (copied otherwise)."""
     if not isinstance(embeddings, torch.Tensor) or embeddings.dim() != 2:
@@ -197,10 +218,7 @@ class _StatisticsPass:
 
     def image(self, P):
         """The packed image of P [M, M] padded with zeros to [Mp, Mp], fp32 on the device."""
-        M, Mp = self.M, (self.M + 31) // 32 * 32
-        Pp = torch.zeros(Mp, Mp, dtype=torch.float32)
-        Pp[:M, :M] = P
-        return _pack_image(Pp).to(self.x.device)
+        return _square_image(P, self.x.device)
 
     _image = image
 
@@ -720,6 +738,8 @@ class GPHead(nn.Module):
         self.jitter = float(jitter)
         self._image = None
         self._image_key = None
+        self._backward_image = None                         # of prepare_backward(), under the same key
+        self._backward_key = None
 
     @classmethod
     def from_tensors(cls, mapping, jitter=1e-4):
@@ -901,7 +921,7 @@ class GPHead(nn.Module):
 
     def _factors64(self):
         """c, s, l, mean, std as Python floats and, in fp64 on the host: the centroid of Z, Zc = Z - centroid, |zc|^2,
-        a = L^-T m, W1 = L^-1 (exactly lower triangular), W2 = L_S^T L^-1."""
+        a = L^-T m, W1 = L^-1 (exactly lower triangular), W2 = L_S^T L^-1, m and L_S (its lower triangle)."""
         Z = self.inducing_points.detach().to("cpu", torch.float64)
         m = self.variational_mean.detach().to("cpu", torch.float64)
         LS = self.chol_variational_covar.detach().to("cpu", torch.float64).tril()
@@ -912,7 +932,7 @@ class GPHead(nn.Module):
         L, W1 = _whitening64(Zc, zn, s, ell, self.jitter)
         a = torch.linalg.solve_triangular(L.T, m[:, None], upper=True)[:, 0]
         return dict(c=c, s=s, inv_two_l2=0.5 / (ell * ell), mean=tm, std=ts, centroid=cen, Zc=Zc, znorm=zn, a=a, W1=W1,
-                    W2=LS.T @ W1)
+                    W2=LS.T @ W1, m=m, LS=LS)
 
     def prepare(self):
         """Builds the fp32 factor image the kernel reads -- a, W1, W2, |z|^2 and the centroid of Z, computed once in
@@ -936,8 +956,32 @@ class GPHead(nn.Module):
         self._image_key = key
         return self._image
 
+    def prepare_backward(self):
+        """The fp32 images the backward of a prediction reads beside those of prepare(): W1, W1^T,
+        G2 = 2 (L_S L_S^T - I), m and Zc^T, from the same fp64 host factors.  Built by the first backward and again after
+        any buffer changed: a forward-only user never pays for them."""
+        key = self._key()
+        if self._backward_image is not None and self._backward_key == key:
+            return self._backward_image
+        dev = self.inducing_points.device
+        f = self._factors64()
+        M = f["Zc"].shape[0]
+        G2 = 2.0 * (f["LS"] @ f["LS"].T - torch.eye(M, dtype=torch.float64))
+        self._backward_image = dict(w1img=_square_image(f["W1"], dev), w1timg=_square_image(f["W1"].T, dev),
+                                    g2img=_square_image(G2, dev), m=f["m"].to(torch.float32).to(dev),
+                                    ztimg=_transposed_image(f["Zc"], dev))
+        self._backward_key = key
+        return self._backward_image
+
     # --------------------------------------------------------------------------------------------------------------
     def _run(self, embeddings, with_region):
+        """The outputs of one cgat_gp_predict call: (mean_f, var_f) or all five.  Where autograd records (grad mode on and
+        embeddings.requires_grad) they are differentiable in the embeddings (_Prediction); otherwise plain tensors."""
+        if isinstance(embeddings, torch.Tensor) and embeddings.requires_grad and torch.is_grad_enabled():
+            return list(_Prediction.apply(self, embeddings, with_region))
+        return self._predict(embeddings, with_region)
+
+    def _predict(self, embeddings, with_region):
         if not isinstance(embeddings, torch.Tensor) or embeddings.dim() != 2:
             raise ValueError("GPHead: embeddings must be a [G, D] tensor")
         _require_gpu(embeddings, self.inducing_points)
@@ -965,7 +1009,8 @@ class GPHead(nn.Module):
         return outs
 
     def latent(self, embeddings):
-        """(mean_f, var_f) of the latent distribution, [G] each."""
+        """(mean_f, var_f) of the latent distribution, [G] each; differentiable in `embeddings` where autograd records
+        (module docstring), like `predict` and `uncertainty`."""
         mean_f, var_f = self._run(embeddings, False)
         return mean_f, var_f
 
@@ -979,6 +1024,23 @@ class GPHead(nn.Module):
         pred, _, upper = self.predict(embeddings)
         return upper - pred
 
+    def nlpd(self, embeddings, targets, noise):
+        """The negative log predictive density of `targets` [G] under the Gaussian likelihood, per row and in the targets'
+        units: the density N(pred, (var_f + noise) std^2).  `noise` is the likelihood's sigma^2 in units of the normalised
+        targets, the value the report of `fit` carries.  Plain torch on top of `latent`, hence differentiable in the
+        embeddings like it."""
+        noise = float(noise)
+        if not noise > 0.0:
+            raise ValueError("GPHead.nlpd: noise must be positive")
+        mean_f, var_f = self.latent(embeddings)
+        im = self.prepare()
+        y = torch.as_tensor(targets).detach().reshape(-1).to(device=mean_f.device, dtype=torch.float32)
+        if y.numel() != mean_f.numel():
+            raise ValueError(f"GPHead.nlpd: {mean_f.numel()} rows of embeddings, {y.numel()} targets")
+        var = (var_f + noise) * (im["std"] * im["std"])
+        resid = y - (mean_f * im["std"] + im["mean"])
+        return 0.5 * (torch.log(2.0 * math.pi * var) + resid * resid / var)
+
     def predict_batch(self, model, batch, b_comp):
         """The graph embedding of `model` (a CGAtNet) for this batch, under eval() and no_grad, then `predict`."""
         was_training = model.training
@@ -989,3 +1051,94 @@ class GPHead(nn.Module):
         finally:
             model.train(was_training)
         return self.predict(emb)
+
+
+def latent_adjoints(grads, var_f, std):
+    """Reduces the incoming gradients of the five outputs of a prediction to those of the latent pair.
+    `grads`: (g_mean_f, g_var_f, g_pred, g_lower, g_upper), [G] each or None; `var_f` [G] as the forward returned it (clamped
+    at 0); `std` the target normalisation scalar.  Returns (gm, gv) = (dL/dmean_f, dL/dvar_f), each [G] or None where no
+    output reaches it:
+
+        gm = g_mean_f + std (g_pred + g_lower + g_upper)        gv = g_var_f + std (g_upper - g_lower) / sqrt(var_f)
+
+    Where var_f is 0 the forward clamped it and the whole gv of that row is 0 (the subgradient torch's clamp_min takes):
+    no infinity leaves this function.  Plain torch on the device of its arguments."""
+    g_mean, g_var, g_pred, g_lower, g_upper = grads
+    std = float(std)
+    gm = g_mean
+    for g in (g_pred, g_lower, g_upper):
+        if g is not None:
+            gm = std * g if gm is None else gm + std * g
+    gv = g_var
+    if g_lower is not None or g_upper is not None:
+        positive = var_f > 0
+        spread = g_upper if g_lower is None else -g_lower if g_upper is None else g_upper - g_lower
+        term = std * spread * torch.where(positive, var_f, torch.ones_like(var_f)).rsqrt()
+        gv = term if gv is None else gv + term
+    if gv is not None:
+        gv = torch.where(var_f > 0, gv, torch.zeros_like(gv))
+    return gm, gv
+
+
+def predictive_backward(head, embeddings, grad_mean, grad_var, chunk_rows=None):
+    """dL/d embeddings [G, D] (a new contiguous fp32 tensor on their device) of a loss L of the latent prediction of
+    `head` (a GPHead), given grad_mean = dL/dmean_f and grad_var = dL/dvar_f, [G] each; either may be None (mean only,
+    variance only).  One cgat_gp_predict_backward call (csrc/gpback.hip); the head's buffers are constants.
+    The clamp of var_f at 0 is not seen here: `latent_adjoints` zeroes grad_var there.  `chunk_rows` as for
+    fit_statistics."""
+    what = "predictive_backward"
+    if not isinstance(head, GPHead):
+        raise TypeError(f"{what}: head must be a GPHead")
+    _require_gpu(head.inducing_points)
+    im = head.prepare()
+    x = _check_embeddings(what, embeddings, im["D"])
+    if x.device != head.inducing_points.device:
+        raise ValueError(f"{what}: embeddings and the head must live on one device")
+    chunk = DEFAULT_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+    if chunk < 32 or chunk % 32:
+        raise ValueError(f"{what}: chunk_rows = {chunk} is not a positive multiple of 32")
+    G, D, M, dev = x.shape[0], im["D"], im["M"], x.device
+    ups = []
+    for name, g in (("grad_mean", grad_mean), ("grad_var", grad_var)):
+        if g is not None:
+            if not isinstance(g, torch.Tensor) or g.numel() != G:
+                raise ValueError(f"{what}: {name} must hold one value per row of the embeddings ({G})")
+            g = g.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        ups.append(g)
+    gm, gv = ups
+    if G == 0 or (gm is None and gv is None):
+        return torch.zeros(G, D, dtype=torch.float32, device=dev)
+    back = head.prepare_backward()
+    ws_bytes = _lib.lib.cgat_gp_predict_backward_workspace_bytes(G, M, D, chunk)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    dX = torch.empty(G, D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib.cgat_gp_predict_backward(
+            _ptr(x), x.stride(0), G, D, _ptr(im["zimg"]), M, _ptr(im["centroid"]), _ptr(im["znorm"]), _ptr(back["w1img"]),
+            _ptr(back["w1timg"]), _ptr(back["g2img"]), _ptr(back["m"]), None if gm is None else _ptr(gm),
+            None if gv is None else _ptr(gv), im["s"], im["inv_two_l2"], chunk, _ptr(back["ztimg"]), _ptr(dX), dX.stride(0),
+            _ptr(ws), ws_bytes, _stream())
+    _lib.check(rc, "cgat_gp_predict_backward")
+    return dX
+
+
+class _Prediction(torch.autograd.Function):
+    """cgat_gp_predict as a function of the embeddings: the forward is GPHead._predict, the backward reduces the incoming
+    gradients to (gm, gv) (latent_adjoints) and runs predictive_backward.  Saves the embeddings, var_f and std."""
+
+    @staticmethod
+    def forward(ctx, head, embeddings, with_region):
+        outs = head._predict(embeddings, with_region)
+        ctx.head, ctx.key, ctx.std = head, head._key(), head.prepare()["std"]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(embeddings, outs[1])
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        embeddings, var_f = ctx.saved_tensors
+        if ctx.head._key() != ctx.key:
+            raise RuntimeError("GPHead: a buffer of the head changed between a prediction and its backward")
+        gm, gv = latent_adjoints(tuple(grads) + (None,) * (5 - len(grads)), var_f, ctx.std)
+        return None, predictive_backward(ctx.head, embeddings, gm, gv), None

@@ -955,6 +955,32 @@ int cgat_gp_fit_grad_inputs(const float* X, int64_t ldx, const float* y_norm, in
                             double* colsum, double* d2sum, double* P, const float* Ztimg, float* dX, int64_t lddx,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* ---- derivative of the head's prediction in its input: the backward of cgat_gp_predict -------------------
+ * The reference evaluates its GP at CGAT/gaussian_process.py:247-268 on the embeddings of a frozen network; a loss of the
+ * prediction (held-out error, predictive density, an acquisition value) that is to reach the network needs dL/dX.  With
+ * alpha = W1 k_x, S = L_S L_S^T and k as in cgat_gp_predict, mean_f = c + alpha . m and var_f = s + alpha^T (S - I) alpha,
+ * so per row n with the upstream gradients gm[n] = dL/dmean_f and gv[n] = dL/dvar_f and G2 = 2 (S - I)
+ *   q_n = gv[n] G2 alpha_n + gm[n] m,   u_n = W1^T q_n,   r_nm = u_nm k_nm,   rho_n = sum_m r_nm
+ *   dX[n][d] = (sum_m r_nm (Z - centroid)[m][d] - rho_n (x_n[d] - centroid[d])) 2 inv_two_l2 = dL/dx_n[d]
+ * the chain of cgat_gp_fit_grad_inputs with a per-row coefficient on the G2 product and without its sums over the rows.
+ * Operands as there: X [G, D] rows ldx apart, Zimg / centroid / znorm, the packed images W1img (lower triangular), W1timg
+ * (upper), G2img (symmetric) as [Mp, Mp] and Ztimg as [Dq, Mp], zero padded, 16-byte aligned; m [M] the variational mean;
+ * gm, gv [G] fp32, finite.  A null gv means "mean only" (alpha is then not formed), a null gm "variance only"; both null is
+ * an argument error.  The clamp of var_f at 0 is the caller's: pass gv = 0 for such a row.  Per chunk of chunk_rows rows the
+ * three products are formed one after the other on the f32-input matrix cores through a chunk buffer in the workspace; the
+ * last kernel recomputes the distances, keeps the tile of r in LDS, adds rho over m in a fixed order and forms dX, so r never
+ * reaches memory.  dX [G, D] fp32, rows lddx >= D apart; columns at or past D of a row are never written.  G < 1, lddx < D, a
+ * null or misaligned operand return 1 (argument), M > 1024 returns 4 (unsupported), a short workspace 3, each with a message
+ * and before any launch.  The workspace (query below; 0 for arguments the entry refuses) is the chunk buffer alone,
+ * 16-byte aligned.  No atomics: bitwise deterministic, and a row's dX does not depend on chunk_rows; caller's stream, no
+ * allocation, no synchronisation. */
+size_t cgat_gp_predict_backward_workspace_bytes(int32_t G, int32_t M, int32_t D, int32_t chunk_rows);
+int cgat_gp_predict_backward(const float* X, int64_t ldx, int32_t G, int32_t D, const float* Zimg, int32_t M,
+                             const float* centroid, const float* znorm, const float* W1img, const float* W1timg,
+                             const float* G2img, const float* m, const float* gm, const float* gv, float s,
+                             float inv_two_l2, int32_t chunk_rows, const float* Ztimg, float* dX, int64_t lddx, void* ws,
+                             size_t ws_bytes, void* stream);
+
 /* ---- one Lloyd step of k-means over the embeddings: inducing points at the centres of the data ----------
  * The reference normalises the targets and starts its inducing points from one random batch of training embeddings
  * (CGAT/gaussian_process.py:208-226); the usual recipe for a sparse GP moves such a start by k-means.  Per row n of X
